@@ -1,12 +1,15 @@
 """bench.py -- molecules/sec of one full Grappa train step (GrappaModel -> Energy with forces -> MolwiseLoss ->
 backward -> all-reduce -> fused Adam with grad clipping) on N MI355X of one node.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2                     # the headline alone
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full              # ... and every other measurement and check listed below
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR  # ... and what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N = 1 (the headline line): BASELINE.json configs[1]: 256 molecules of 20-40 atoms drawn from the Espaloma
 molecule pool, 32 conformations, production model (40.8 M parameters, keyed init), fp32-grade arithmetic, train mode (dropout on),
-synthetic charges / coordinates / reference energies+forces, inputs resident in HBM.  The same JSON line also carries
+synthetic charges / coordinates / reference energies+forces, inputs resident in HBM.  A plain run sets up, warms up, times --steps
+steps and prints the line.  With --full the same JSON line also carries
   `roofline`      the dominant kernel family (the dense products): algorithmic 2MNK FLOPs / HIP-event time per call, measured in an
                   instrumented repetition of the same steps right after the timed region; plus the GAT kernels vs HBM,
   `cpu_baseline`  the oracle's CPU restatement of the same train step on a bounded sample (rank 0, N = 1 only),
@@ -19,7 +22,9 @@ synthetic charges / coordinates / reference energies+forces, inputs resident in 
   `predict_latency_ms`  `Grappa.predict` on one ~40-atom molecule (grappa.py:36-57): eager and through the cache of recorded forwards.
 N > 1 (default): STRONG scaling of BASELINE configs[3] (C4): ONE global batch of 4096 molecules dealt to the ranks by size
 (dist.shard_indices), loss scaled by 1/4096 on every rank, gradients summed with a two-bucket RCCL all-reduce of the flat gradient
-buffer after backward(); `--weak` switches to weak scaling of C2 (256 molecules per GPU).
+buffer after backward(); `--weak` switches to weak scaling of C2 (256 molecules per GPU).  With --full: the all-reduce time of an
+instrumented pass, the collective layer's self-check (`dist`) and rank 0's single-GPU run of the same global batch
+(`strong_scaling_reference`, `scaling_factor`).
 """
 import argparse
 import hashlib
@@ -319,6 +324,47 @@ def finite_loss(what: str, loss) -> float:
     return v
 
 
+DUMP_ROWS_CAP = 1 << 20          # elements per dumped array beyond which a fixed sample of its rows is written
+DUMP_WEIGHTS_SAMPLE = 1 << 20     # draws for the sample of the flat weight / gradient buffers
+
+
+def dump_outputs(path: str, graphs, flat, loss: float) -> dict:
+    """what the last timed train step handed its caller, as `path`/<name>.npy (float32): the loss, per conformation the energies
+    (molecules, C) and forces (atoms, C, 3), the parameters each tuple level was given (k, eq), and a fixed sample of the updated
+    weights and of the gradients they were updated with.  Several chunks: their rows one after another.  An array above DUMP_ROWS_CAP
+    elements keeps a sample of its rows drawn by a generator seeded with its name, so that two builds write the same rows.
+    -> {name: shape}"""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def rows_sample(name, a):
+        if a.size <= DUMP_ROWS_CAP or a.shape[0] < 2:
+            return a
+        per_row = a.size // a.shape[0]
+        rng = np.random.default_rng(zlib.crc32(name.encode()))
+        return a[np.unique(rng.integers(0, a.shape[0], size=max(DUMP_ROWS_CAP // per_row, 1)))]
+
+    arrays = {"loss": np.array([loss], dtype=np.float32),
+              "energy": torch.cat([g.nodes["g"].data["energy"].detach() for g in graphs]),
+              "forces": torch.cat([g.nodes["n1"].data["gradient"].detach() for g in graphs])}
+    for lvl in ("n2", "n3", "n4", "n4_improper"):
+        for k in ("k", "eq"):
+            if k in graphs[0].nodes[lvl].data:
+                arrays[f"{lvl}_{k}"] = torch.cat([g.nodes[lvl].data[k].detach() for g in graphs])
+    idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, flat.numel, size=DUMP_WEIGHTS_SAMPLE))).to(flat.data.device)
+    arrays["weights_sample"] = flat.data[idx]
+    arrays["weight_grads_sample"] = flat.grad[idx]
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy() if torch.is_tensor(a) else a
+        arrays[name] = np.ascontiguousarray(rows_sample(name, a), dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 * 2 ** 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def log(*a):
     print(f"[bench {time.strftime('%H:%M:%S')}]", *a, file=sys.stderr, flush=True)
 
@@ -356,7 +402,17 @@ def main():
                     "N-rank path on a machine without a GPU; the caller must have installed a test backend (the product has none for the CPU), "
                     "no kernel timing, never a measurement")
     ap.add_argument("--tiny-model", action="store_true", help="TEST ONLY: a 60 k-parameter model instead of the production one (with --device cpu)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: CPU baseline, instrumented "
+                    "roofline pass, other GEMM arithmetics, weight planes, the other writer-head stream setting, C3 / C3-bf16 / C4 on one GPU, "
+                    "recorded steps, launch counts, b32, predict, C5; at N > 1 the collective self-check and the single-GPU scaling reference.  "
+                    "--no-cpu-baseline, --no-extras, --alt-precision, --bwd-precision, --shape-table and --no-scaling-reference act within it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed (loss, "
+                    "energies, forces, the parameters per tuple level, a fixed sample of the updated weights and of their gradients) as "
+                    "DIR/<name>.npy, float32, at most 64 MB in all (larger arrays: a fixed, seeded sample of their rows); rank 0 only")
     args = ap.parse_args()
+    for opt_name, given in (("--shape-table", args.shape_table), ("--bwd-precision", args.bwd_precision)):
+        if given and not args.full:
+            ap.error(f"{opt_name} belongs to the measurements of --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: this process has not touched the GPU; it starts the N ranks (one process per GPU) as children and
@@ -377,7 +433,7 @@ def main():
     workload = args.workload or ("C4-espaloma-b4096" if strong else "C2-pubchem-b256")
     # CPU baseline first, in child processes, before this process initialises the GPU (rank 0 at N = 1 only)
     cpu_base = None
-    if world == 1 and args.gpus == 1 and not args.no_cpu_baseline and args.device == "cuda":
+    if args.full and world == 1 and args.gpus == 1 and not args.no_cpu_baseline and args.device == "cuda":
         log(f"cpu baseline (oracle, {args.cpu_sample} molecules, limit {args.cpu_limit:.0f} s) ...")
         cpu_base = cpu_baseline(workload, args.cpu_sample, 5, 2, args.cpu_limit)
         log(f"cpu baseline: {cpu_base}")
@@ -544,7 +600,12 @@ def main():
             torch.cuda.empty_cache()
 
     dt, final_loss = job.timed(args.steps, args.warmup)
-    log(f"timed region done: {1e3 * dt / args.steps:.1f} ms/step; instrumented pass")
+    log(f"timed region done: {1e3 * dt / args.steps:.1f} ms/step")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below moves the weights or overwrites the graphs' outputs
+        dumped = dump_outputs(args.dump_outputs, job.graphs, flat, final_loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
 
     GEMM_PEAK_NOTE = ("achieved = algorithmic 2MNK FLOPs / HIP-event time of the calls; peak = bf16 dense MFMA peak (16 x 157.3 TFLOP/s, "
                       "MI355X_MICROARCH.md; the fp16 one is the same) / partial products issued per fp32 product; the time of the operands' "
@@ -668,8 +729,10 @@ def main():
         return roof, gat, 1e3 * dtp / steps, ar_ms
 
     head_streams = model.parameter_writer.head_streams
-    roof, gat, ms_instr, allreduce_ms = instrument(job, args.steps)
-    log("instrumented pass done")
+    roof = gat = ms_instr = allreduce_ms = None
+    if args.full:
+        roof, gat, ms_instr, allreduce_ms = instrument(job, args.steps)
+        log("instrumented pass done")
 
     def alt_run(setter, restore):
         setter()
@@ -679,7 +742,7 @@ def main():
 
     # the same K steps with the dense products on the native fp32 matrix instruction, for reference next to the default
     alt = {}
-    for name in [a for a in args.alt_precision.split(",") if on_gpu and a and a != be.gemm_precision_name]:
+    for name in [a for a in args.alt_precision.split(",") if args.full and on_gpu and a and a != be.gemm_precision_name]:
         default_precision = be.gemm_precision_name
         alt[name] = alt_run(lambda: be.set_gemm_precision(name), lambda: be.set_gemm_precision(default_precision))
         alt[name]["gemm_precision"] = name
@@ -694,7 +757,7 @@ def main():
 
     # opt-in kernel (GRAPPA_WEIGHT_PLANES): the same steps with the weights read from their pre-split bf16 planes by LDS-DMA
     wpl = None
-    if on_gpu and world == 1 and not args.no_extras and not be.weight_planes and args.act_dtype == "f32":
+    if args.full and on_gpu and world == 1 and not args.no_extras and not be.weight_planes and args.act_dtype == "f32":
         default_precision = be.gemm_precision_name
         be.set_gemm_precision("f32_bf16x6")            # the plane format is a bf16 split: it rides on the bf16x6 arithmetic
         be.weight_planes = True
@@ -708,7 +771,7 @@ def main():
 
     # the other stream setting of the writer heads beside the default (four HIP streams since round 3), never `value`
     heads_alt = None
-    if on_gpu and world == 1 and not args.no_extras and args.act_dtype == "f32":
+    if args.full and on_gpu and world == 1 and not args.no_extras and args.act_dtype == "f32":
         default_streams = model.parameter_writer.head_streams
         other = 1 if default_streams > 1 else 4
         model.parameter_writer.head_streams = other
@@ -723,7 +786,7 @@ def main():
     # N = 1: the other single-GPU configurations, timed right after the headline measurement: C3 in the headline arithmetic, C3 in the
     # bf16 STORAGE configuration BASELINE configs[2] names (never `value`), and the 4096-molecule batch of C4 on one GPU
     extras = {}
-    if on_gpu and world == 1 and not args.no_extras and not strong and workload == "C2-pubchem-b256" and args.act_dtype == "f32":
+    if args.full and on_gpu and world == 1 and not args.no_extras and not strong and workload == "C2-pubchem-b256" and args.act_dtype == "f32":
         headline_graphs = job.graphs
         default_precision = be.gemm_precision_name
         for key, name, steps, bf16 in (("c3", "C3-espaloma-b1024", 5, False), ("c3_bf16", "C3-espaloma-b1024", 5, True),
@@ -956,7 +1019,7 @@ def main():
 
     # N > 1: what the collective layer actually saw, so that the first real multi-GPU run checks itself
     dist_info = None
-    if world > 1:
+    if args.full and world > 1:
         me = {"rank": rank, "local_rank": local_rank, "device_index": torch.cuda.current_device() if on_gpu else None, "pid": os.getpid(),
               "device_name": torch.cuda.get_device_name() if on_gpu else "cpu",
               "device_uuid": str(getattr(torch.cuda.get_device_properties(dev), "uuid", "")) if on_gpu else None}
@@ -1009,7 +1072,7 @@ def main():
     # accumulated, one optimiser step, no collective) while the other ranks wait at the barrier that follows; last, so that nothing
     # measured above sees rank 0's parameters drift from the others'
     scaling_ref = None
-    if world > 1 and strong and not args.no_scaling_reference:
+    if args.full and world > 1 and strong and not args.no_scaling_reference:
         if rank == 0:
             try:
                 total = job.global_batch
@@ -1033,7 +1096,7 @@ def main():
         # rocprofv3 --pmc summary of this same command (tools/pmc_traffic.py -> profiles/pmc_traffic_c2.json) is reported -- only
         # while the kernel sources it was measured on are the ones running
         tpath = os.path.join(ROOT, "profiles", "pmc_traffic_c2.json")
-        if job.name == "C2-pubchem-b256" and os.path.exists(tpath):
+        if roof is not None and job.name == "C2-pubchem-b256" and os.path.exists(tpath):
             try:
                 tj = json.load(open(tpath))
                 if tj.get("kernel_source_hash") == kernel_source_hash():
@@ -1099,6 +1162,16 @@ def main():
             out["strong_scaling_reference"] = scaling_ref
             out["scaling_factor"] = (out["value"] / scaling_ref["value"]) if scaling_ref.get("value") else None
         out["cpu_baseline"] = cpu_base
+        out["full"] = args.full
+        if not args.full:
+            # a plain run measures the headline alone: the fields that only --full measures are left out of its line
+            for k in ("roofline", "roofline_gat", "ms_per_step_instrumented", "writer_heads_other_stream_setting", "cpu_baseline"):
+                out.pop(k)
+            for k in ("native_f32_mfma", "f32_bf16x6", "backward_reduced", "weight_planes"):
+                out["gemm_arithmetic"].pop(k)
+            out["config"].pop("extras")
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

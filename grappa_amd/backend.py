@@ -210,6 +210,7 @@ class HipBackend:
         self._wplanes = {}     # (data_ptr, rows, cols, transposed) -> (version key, planes tensor)
         self._wpairs = {}      # (data_ptr, rows, cols, "pairs" | "pairsT") -> [version key, pairs, weakref of the weight, epoch of last use, transposed, maxima record]
         self._wptable = None   # (device table of grappa_split_pairs_item, count, tiles, records kept alive)
+        self._wpairs_ready = None  # (event after the last batched pairs refresh, recorded while capturing, handles of the streams ordered after it)
         self._wepoch = 0
         # precision "f32_f16x3": largest |element| per row / column of every operand (grappa_amax_f32).  Weights: cached until the
         # optimiser step; activations: an `Amax` record travels with the tensor through ops.py (gemm returns it, the backward
@@ -284,6 +285,7 @@ class HipBackend:
         if hit is not None:
             hit[3] = self._wepoch
             if hit[0] == ver:
+                self._after_pairs_refresh()
                 return hit[1]
             self._refresh_weight_pairs()
             if hit[0] == ver:
@@ -327,6 +329,25 @@ class HipBackend:
         _chk(self.lib.grappa_split_pairs_f32_batched(self._stream(), n, tiles, tab.data_ptr()), "grappa_split_pairs_f32_batched")
         for e in live:
             e[0] = (e[2]()._version, self._wepoch)
+        # the first stale use is usually a writer head's product on its own stream (no GNN product reads weight pairs at C2 sizes), and the
+        # launch above rewrites the pairs of EVERY head's weights: the other heads' streams must not read theirs before it has run
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self._wpairs_ready = (ev, torch.cuda.is_current_stream_capturing(), {self._stream()})
+
+    def _after_pairs_refresh(self) -> None:
+        """order the current stream after the last batched refresh of the weights' pairs (once per stream and refresh).  An event recorded
+        outside a hipGraph capture is not waited for inside one, nor the other way round: the capture starts and ends on synchronised streams"""
+        r = self._wpairs_ready
+        if r is None:
+            return
+        ev, captured, ordered = r
+        h = self._stream()
+        if h in ordered:
+            return
+        ordered.add(h)
+        if torch.cuda.is_current_stream_capturing() == captured:
+            torch.cuda.current_stream().wait_event(ev)
 
     def to_pairs(self, x: torch.Tensor, have: "Optional[Amax]" = None) -> "Amax":
         """an fp32 (rows, cols) tensor in the pair format by a pass of its own (producers that hold whole rows write it themselves:

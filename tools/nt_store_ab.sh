@@ -7,7 +7,7 @@ for v in ${VARIANTS:-"" nt1 nt2 "" nt1 nt2}; do
   [ "$v" = shipped ] && v=""
   echo "== variant ${v:-shipped}"
   lib=""; [ -n "$v" ] && lib="$PWD/build/variants/libgrappa_hip_$v.so"
-  GRAPPA_HIP_LIB=$lib python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
+  GRAPPA_HIP_LIB=$lib python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

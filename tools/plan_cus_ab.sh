@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for cus in 256 128 96 64 256 128; do
   echo "== GRAPPA_PLAN_CUS=$cus"
-  GRAPPA_PLAN_CUS=$cus python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
+  GRAPPA_PLAN_CUS=$cus python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

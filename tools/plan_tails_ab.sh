@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 for hs in 4 1; do
 for tails in 1 0 1 0; do
   echo "== GRAPPA_HEAD_STREAMS=$hs GRAPPA_PLAN_TAILS=$tails"
-  GRAPPA_HEAD_STREAMS=$hs GRAPPA_PLAN_TAILS=$tails python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
+  GRAPPA_HEAD_STREAMS=$hs GRAPPA_PLAN_TAILS=$tails python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --alt-precision '' 2>&1 | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -1,8 +1,8 @@
 """Aggregate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py` into per-kernel-family HBM traffic per launch.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc/bench_FETCH_SIZE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --alt-precision '' --bwd-precision ''
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc/bench_WRITE_SIZE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --alt-precision '' --bwd-precision ''
-    python tools/pmc_traffic.py gpurun_out/pmc/bench_FETCH_SIZE gpurun_out/pmc/bench_WRITE_SIZE > gpurun_out/pmc_traffic_c2.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d results/pmc/bench_FETCH_SIZE -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --alt-precision '' --bwd-precision ''
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d results/pmc/bench_WRITE_SIZE -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --alt-precision '' --bwd-precision ''
+    python tools/pmc_traffic.py results/pmc/bench_FETCH_SIZE results/pmc/bench_WRITE_SIZE > results/pmc_traffic_c2.json
 
 Units and corrections (MI355X_MICROARCH.md, HBM section): the counters are in KiB; on gfx950 FETCH_SIZE reports exactly half of the
 bytes of wide coalesced (16 B/lane) streaming reads, so it is doubled; WRITE_SIZE is exact for 16 B/lane stores.
