@@ -1,0 +1,291 @@
+"""Float64 references of the non-GEMM kernels and the elementwise gates the domain tests assert with (tests/test_gpu_kernel_domains.py,
+tests/test_gpu_mm_float64.py; checked against oracle/ops_ref.RefBackend and cpu_ref.RefMolwiseLoss on the CPU by
+tests/test_kernel_domain_refs.py).
+
+The references are independent of the kernels' closed forms: they state each operation directly in float64 and take gradients with
+torch.autograd (the GAT from cpu_ref.dot_gat, the MM terms from cpu_ref.bond_length / bond_angle / dihedral)."""
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+U32 = 2.0 ** -24          # unit roundoff of float32
+BF = torch.bfloat16
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- gates
+def rowmax(t: torch.Tensor) -> torch.Tensor:
+    """the largest magnitude of each row (first axis), shaped to broadcast against t"""
+    t = t.detach().double()
+    if t.shape[0] == 0:
+        return t.abs()
+    return t.abs().reshape(t.shape[0], -1).amax(1).reshape(-1, *([1] * (t.dim() - 1)))
+
+
+def assert_el(got, want64, c, scale, what):
+    """fp32 kernels, elementwise: |got - f64| <= c * u32 * (|f64| + scale)  (scale: the row's or head's largest magnitude)"""
+    got = got.detach().cpu().double()
+    want64 = want64.detach().cpu().double()
+    assert got.shape == want64.shape, (what, got.shape, want64.shape)
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
+    bound = c * U32 * (want64.abs() + torch.as_tensor(scale, dtype=torch.float64))
+    d = (got - want64).abs()
+    bad = d > bound
+    if bool(bad.any()):
+        i = int(torch.argmax((d / bound.clamp_min(1e-300)).reshape(-1)))
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside c={c} u32 (|f64| + scale); worst at flat index {i}: "
+                             f"got {float(got.reshape(-1)[i]):.9g} f64 {float(want64.reshape(-1)[i]):.9g} ({float(d.reshape(-1)[i] / bound.reshape(-1)[i]):.3g}x the bound)")
+
+
+def assert_calibrated(got, ref32, want64, c, scale, what, period=None, ref32b=None):
+    """the self-calibrating gate, row by row: max|gpu - f64| <= 2 * max|fp32 RefBackend - f64| + c * u32 * scale.
+    period: compare modulo period (angles: +pi and -pi are the same torsion).  ref32b: a second fp32 implementation (another summation
+    order); the farther of the two calibrates the gate."""
+    got, ref32, want64 = (t.detach().cpu().double() for t in (got, ref32, want64))
+    assert got.shape == want64.shape == ref32.shape, what
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
+
+    def dist(a):
+        d = a - want64
+        if period is not None:
+            d = torch.remainder(d + period / 2, period) - period / 2
+        return d.abs().reshape(max(d.shape[0], 1) if d.numel() else 0, -1).amax(1) if d.numel() else d.reshape(0)
+
+    dg, dr = dist(got), dist(ref32)
+    if ref32b is not None:
+        dr = torch.maximum(dr, dist(ref32b.detach().cpu().double()))
+    floor = c * U32 * torch.as_tensor(scale, dtype=torch.float64).reshape(-1).expand(dg.shape[0]) if dg.numel() else dg
+    bad = dg > 2.0 * dr + floor
+    if bool(bad.any()):
+        i = int(torch.argmax(dg - 2.0 * dr - floor))
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} rows fail; row {i}: gpu {float(dg[i]):.3e} vs 2 x fp32 ref "
+                             f"{float(dr[i]):.3e} + floor {float(floor[i]):.3e}")
+
+
+def close_bf16(got16, want64, what, frac=0.97, steps=2.0):
+    """bf16 kernels (tests/test_gpu_writer_layer.py's _close_bf16 on a float64 reference of the bf16-rounded inputs): most elements are
+    the bf16 rounding of the float64 value, none is more than `steps` bf16 steps (2^-7 relative) away -- of the value or of the tensor's
+    RMS where a sum cancels"""
+    got = got16.detach().cpu().double()
+    want = want64.detach().cpu().double()
+    assert got.shape == want.shape, what
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
+    if got.numel() == 0:
+        return
+    want16 = want.to(BF).double()
+    same = float((got == want16).double().mean())
+    d = (got - want).abs()
+    bound = steps * 2.0 ** -7 * (want.abs() + want.pow(2).mean().sqrt())
+    bad = int((d > bound).sum())
+    assert same >= frac and bad == 0, f"{what}: equal {same:.4f}, outside {steps} steps: {bad}, worst {float((d / bound.clamp_min(1e-300)).max()):.2f}"
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- graph
+class CsrPlan:
+    """the fields HipBackend's graph entry points read (_csr_check: N, E, indptr, indices, rev), built from a symmetric edge list the
+    way batch._plan_arrays_numpy does: CSR by destination, sources ascending, rev = the slot of the reverse edge"""
+
+    def __init__(self, N, src, dst, device="cpu"):
+        src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+        order = np.lexsort((src, dst))
+        s, d = src[order], dst[order]
+        indptr = np.zeros(N + 1, dtype=np.int64)
+        np.add.at(indptr, d + 1, 1)
+        indptr = np.cumsum(indptr)
+        key, rkey = d * max(N, 1) + s, s * max(N, 1) + d
+        rev = np.searchsorted(key, rkey)
+        assert len(s) == 0 or (np.all(rev < len(s)) and np.all(key[np.minimum(rev, len(s) - 1)] == rkey)), "edge list must be symmetric"
+        self.N, self.E = N, len(s)
+        self.src, self.dst = torch.from_numpy(s), torch.from_numpy(d)          # (CPU, int64, CSR order: edge e = src[e] -> dst[e])
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)      # noqa: E731
+        self.indptr, self.indices, self.rev = i32(indptr), i32(s), i32(rev)
+        self.device = torch.device(device)
+
+    def to(self, device):
+        p = CsrPlan.__new__(CsrPlan)
+        p.__dict__.update(self.__dict__)
+        p.indptr, p.indices, p.rev = self.indptr.to(device), self.indices.to(device), self.rev.to(device)
+        p.device = torch.device(device)
+        return p
+
+    @property
+    def degree(self):
+        return (self.indptr[1:] - self.indptr[:-1]).long().cpu()
+
+
+def domain_graph(real_src=None, real_dst=None, n_real=0, hub_leaves=120):
+    """a real batch's bonds (optional), then a star whose hub has `hub_leaves` neighbours, a single atom (degree 0), and a 2-atom molecule
+    behind it -> (N, src, dst, hub index, isolated atom index)"""
+    src = list(real_src) if real_src is not None else []
+    dst = list(real_dst) if real_dst is not None else []
+    hub = n_real
+    for j in range(1, hub_leaves + 1):
+        src += [hub, hub + j]
+        dst += [hub + j, hub]
+    iso = hub + hub_leaves + 1
+    a, b = iso + 1, iso + 2
+    src += [a, b]
+    dst += [b, a]
+    return b + 1, np.array(src), np.array(dst), hub, iso
+
+
+def gat_ref64(ft, plan, H, D, dout):
+    """-> out, alpha (E,H) in CSR order, dft: cpu_ref.dot_gat in float64, alpha by a dense masked softmax, dft by autograd"""
+    from oracle.cpu_ref import dot_gat
+    N = ft.shape[0]
+    f = ft.detach().double().clone().requires_grad_(True)
+    out = dot_gat(f.view(N, H, D), plan.src, plan.dst).reshape(N, H * D)
+    dft, = torch.autograd.grad(out, f, dout.double())
+    with torch.no_grad():
+        fv = f.view(N, H, D)
+        sc = torch.full((N, N, H), float("-inf"), dtype=torch.float64)        # [destination, source, head]
+        sc[plan.dst, plan.src] = (fv[plan.src] * fv[plan.dst]).sum(-1) / math.sqrt(D)
+        has = plan.degree > 0
+        p = torch.zeros_like(sc)
+        p[has] = torch.softmax(sc[has], dim=1)
+        alpha = p[plan.dst, plan.src]
+    return out.detach(), alpha, dft
+
+
+def neighbor_mean_ref64(x, plan, scale_by_neighbor):
+    """out_v = sum over in-neighbours u of x_u / deg(u) (scale_by_neighbor) or / deg(v); 0 for an atom without neighbours"""
+    x = x.double()
+    deg = plan.degree.double()
+    w = 1.0 / (deg[plan.src] if scale_by_neighbor else deg[plan.dst])
+    return torch.zeros_like(x).index_add(0, plan.dst, x[plan.src] * w[:, None])
+
+
+def neighbour_abs_max(x, plan):
+    """per destination: the largest |x| over its in-neighbours' rows (0 without neighbours) -- the scale of a convex combination"""
+    m = x.detach().double().abs().amax(1)
+    return torch.zeros(plan.N, dtype=torch.float64).index_reduce(0, plan.dst, m[plan.src], "amax", include_self=True)[:, None]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- row-wise
+def layernorm_ref64(x, gamma, beta, dy):
+    """-> y, mean, rstd, dx, dgamma, dbeta in float64 (F.layer_norm + autograd), eps = 1e-5 as the kernels"""
+    xd = x.detach().double().clone().requires_grad_(True)
+    gd = gamma.detach().double().clone().requires_grad_(True)
+    bd = beta.detach().double().clone().requires_grad_(True)
+    W = x.shape[1]
+    y = F.layer_norm(xd, (W,), gd, bd, 1e-5)
+    dx, dg, db = torch.autograd.grad(y, (xd, gd, bd), dy.double())
+    with torch.no_grad():
+        mean = xd.mean(1)
+        rstd = 1.0 / torch.sqrt(xd.var(1, unbiased=False) + 1e-5)
+    return y.detach(), mean, rstd, dx, dg, db
+
+
+def act_dropout_ref64(dy, y, p, seed):
+    """dz = dy * keep / (1 - p) * ELU'(y), keep = the documented counter hash of the element index row * N + col"""
+    from oracle.ops_ref import dropout_keep
+    M, N = dy.shape
+    v = dy.double()
+    keep = None
+    if p > 0:
+        keep = dropout_keep(seed, torch.arange(M * N).view(M, N), p)
+        v = torch.where(keep, v / (1.0 - p), torch.zeros_like(v))
+    if y is not None:
+        yd = y.double()
+        v = v * torch.where(yd > 0, torch.ones_like(yd), yd + 1.0)
+    return v, keep
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- tuples
+def seqattn_ref64(qkv, dout, s, T, nheads):
+    """softmax attention over each tuple's s tokens (rows pos * T + t), per head, scale 1/sqrt(dh); -> out, dqkv (autograd)"""
+    Fd = qkv.shape[1] // 3
+    dh = Fd // nheads
+    x = qkv.detach().double().clone().requires_grad_(True)
+    q, k, v = (t.reshape(s, T, nheads, dh) for t in x.split(Fd, dim=1))
+    sc = torch.einsum("ithd,jthd->thij", q, k) / math.sqrt(dh)
+    out = torch.einsum("thij,jthd->ithd", torch.softmax(sc, dim=-1), v).reshape(s * T, Fd)
+    dqkv = torch.autograd.grad(out, x, dout.double())[0] if dout is not None else None
+    return out.detach(), dqkv
+
+
+def perm_concat_ref64(x, s, T, perms, dz):
+    """z[p*T + t] = concat_j x[perms[p][j] * T + t]; dx = the sum of the slots each row went to"""
+    xd = x.detach().double().clone().requires_grad_(True)
+    xv = xd.view(s, T, -1)
+    z = torch.cat([torch.cat([xv[i] for i in p], dim=1) for p in perms], dim=0)
+    dx, = torch.autograd.grad(z, xd, dz.double())
+    return z.detach(), dx
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- MM
+def mm_ref64(idx, mol_ptr, B, xyz, ks, eqs, n_per, offset_torsion, gE, gG, dtype=torch.float64):
+    """the MM energy of a batch in float64 from cpu_ref.bond_length / bond_angle / dihedral:
+    E (B,C), term energies (4,B,C), tuple energies and internal coordinates per level, G = dE/dx (N,C,3, create_graph), and
+    gk, geq = d/d(k, eq) of <gE, E> + <gG, G> (what csrc/mm_energy.hip's double backward stands for).
+    idx: 4 (T,s) int64 tensors; mol_ptr: 4 (B+1,) tensors; ks: [(T,), (T,), (T,n2), (T,n3)]; eqs: [(T,), (T,), None, None].
+    dtype=float32: the same formulas in fp32 (a second fp32 implementation for the self-calibrating gate)."""
+    from oracle.cpu_ref import bond_angle, bond_length, dihedral
+    x = xyz.detach().to(dtype).clone().requires_grad_(True)
+    kk = [k.detach().to(dtype).clone().requires_grad_(True) for k in ks]
+    ee = [None if q is None else q.detach().to(dtype).clone().requires_grad_(True) for q in eqs]
+    C = xyz.shape[1]
+    E = torch.zeros(B, C, dtype=dtype)
+    terms, tes, txs = [], [], []
+    for l in range(4):
+        ix = idx[l].long()
+        T = ix.shape[0]
+        if T == 0:
+            te = tx = torch.zeros(0, C, dtype=dtype)
+        else:
+            pos = [x[ix[:, j]] for j in range(ix.shape[1])]
+            if l == 0:
+                tx = bond_length(*pos)
+            elif l == 1:
+                tx = bond_angle(*pos)
+            else:
+                tx = dihedral(*pos)
+            if l < 2:
+                te = 0.5 * kk[l][:, None] * (tx - ee[l][:, None]) ** 2
+            else:
+                k = kk[l].view(T, n_per[l])
+                n = torch.arange(1, n_per[l] + 1, dtype=dtype).view(1, -1, 1)
+                te = (k[:, :, None] * torch.cos(n * tx[:, None, :])).sum(1)
+                if offset_torsion:
+                    te = te + k.abs().sum(1, keepdim=True)
+        ptr = mol_ptr[l].long()
+        seg = torch.repeat_interleave(torch.arange(B), ptr[1:] - ptr[:-1])
+        contrib = torch.zeros(B, C, dtype=dtype).index_add(0, seg, te)
+        terms.append(contrib)
+        tes.append(te)
+        txs.append(tx)
+        E = E + contrib
+    G, = torch.autograd.grad(E.sum(), x, create_graph=True)
+    L = (gE.to(dtype) * E).sum() + (gG.to(dtype) * G).sum()
+    wrt = [kk[0], kk[1], kk[2], kk[3], ee[0], ee[1]]
+    g = torch.autograd.grad(L, wrt, allow_unused=True)
+    g = [torch.zeros_like(w) if gi is None else gi for gi, w in zip(g, wrt)]
+    det = lambda t: t.detach()          # noqa: E731
+    return dict(E=det(E), terms=det(torch.stack(terms)), te=[det(t) for t in tes], tx=[det(t) for t in txs], G=det(G),
+                gk=[det(t) for t in g[:4]], geq=[det(g[4]), det(g[5])])
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- loss
+def loss_ef_ref64(atom_counts, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B):
+    """the molecule-wise energy + force loss, everything in float64: per molecule, the real conformations' energies centred on their
+    mean (wE * mean squared difference) and the forces' mean squared difference over atoms x real conformations x 3 (wG); the
+    gradients of inv_B * sum(loss) by autograd.  -> loss per molecule (B,), d/d energy (B,C), d/d grad (N,C,3), eval_se (B,4) =
+    {sum of squared centred energy differences, real conformations, sum of squared force differences, atoms x real conformations}"""
+    cnt = torch.as_tensor(atom_counts, dtype=torch.int64)
+    B, C = energy.shape
+    e = energy.detach().double().clone().requires_grad_(True)
+    g = grad.detach().double().clone().requires_grad_(True)
+    m = torch.ones(B, C, dtype=torch.float64) if is_dummy is None else (is_dummy == 0).double()
+    nreal = m.sum(1)
+    er = energy_ref.double()
+    d = (e - (m * e).sum(1, keepdim=True) / nreal[:, None]) - (er - (m * er).sum(1, keepdim=True) / nreal[:, None])
+    se_e = (m * d * d).sum(1)
+    seg = torch.repeat_interleave(torch.arange(B), cnt)
+    sq = (m[seg] * ((g - grad_ref.double()) ** 2).sum(-1)).sum(1)
+    se_g = torch.zeros(B, dtype=torch.float64).index_add(0, seg, sq)
+    n_g = cnt.double() * nreal
+    loss = wE * se_e / nreal + wG * se_g / (n_g * 3.0)
+    gE, gG = torch.autograd.grad(inv_B * loss.sum(), (e, g))
+    se = torch.stack([se_e, nreal, se_g, n_g], 1).detach()
+    return loss.detach(), gE, gG, se

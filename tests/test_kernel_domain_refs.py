@@ -1,0 +1,213 @@
+"""CPU: the float64 references of tests/kernel_refs.py (what the GPU domain tests compare the kernels with) agree with the op-by-op
+restatement oracle/ops_ref.RefBackend run in float64 on the same inputs (the loss also with cpu_ref.RefMolwiseLoss), and the gates
+reject what they must."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import kernel_refs as kr
+
+D64 = torch.float64
+
+
+@pytest.fixture(scope="module")
+def ref():
+    from oracle.ops_ref import RefBackend
+    return RefBackend()
+
+
+@pytest.fixture(scope="module")
+def plan():
+    from grappa_amd.datasets import build_batch_from_pool
+    p = build_batch_from_pool([300, 301], n_confs=1, seed=0).plan()
+    deg = (p.indptr[1:] - p.indptr[:-1]).long()
+    dst = torch.repeat_interleave(torch.arange(p.N), deg).numpy()
+    N, s, d, hub, iso = kr.domain_graph(p.indices.long().numpy(), dst, p.N, hub_leaves=20)
+    pc = kr.CsrPlan(N, s, d)
+    assert int(pc.degree[hub]) == 20 and int(pc.degree[iso]) == 0
+    # the reverse-edge slot of every edge holds the opposite edge
+    assert torch.equal(pc.src[pc.rev.long()], pc.dst) and torch.equal(pc.dst[pc.rev.long()], pc.src)
+    return pc
+
+
+def _close(a, b, what, tol=1e-12):
+    a, b = a.double(), b.double()
+    err = float((a - b).abs().max()) / max(float(b.abs().max()), 1e-300) if b.numel() else 0.0
+    assert err < tol, f"{what}: {err:.3e}"
+
+
+@pytest.mark.parametrize("H,D", [(2, 8), (1, 4), (3, 16)])
+def test_gat_reference(ref, plan, H, D):
+    gen = torch.Generator().manual_seed(H * D)
+    N, F = plan.N, H * D
+    ft, dout = torch.randn(N, F, generator=gen, dtype=D64), torch.randn(N, F, generator=gen, dtype=D64)
+    out, alpha, dft = kr.gat_ref64(ft, plan, H, D, dout)
+    o, a, d = torch.empty(N, F, dtype=D64), torch.empty(plan.E, H, dtype=D64), torch.empty(N, F, dtype=D64)
+    ref.gat_fwd(plan, ft, H, D, o, a)
+    ref.gat_bwd(plan, ft, o, a, dout, H, D, d)
+    _close(out, o, "out"), _close(alpha, a, "alpha"), _close(dft, d, "dft")
+
+
+@pytest.mark.parametrize("flag", [False, True])
+def test_neighbor_mean_reference(ref, plan, flag):
+    x = torch.randn(plan.N, 12, generator=torch.Generator().manual_seed(1), dtype=D64)
+    o = torch.empty_like(x)
+    ref.neighbor_mean(plan, x, o, flag)
+    _close(kr.neighbor_mean_ref64(x, plan, flag), o, f"neighbor_mean {flag}")
+
+
+@pytest.mark.parametrize("M,W", [(7, 4), (5, 260), (1, 516)])
+def test_layernorm_reference(ref, M, W):
+    gen = torch.Generator().manual_seed(M + W)
+    x, dy = torch.randn(M, W, generator=gen, dtype=D64) * 2 + 0.5, torch.randn(M, W, generator=gen, dtype=D64)
+    g, b = 1 + 0.1 * torch.randn(W, generator=gen, dtype=D64), 0.1 * torch.randn(W, generator=gen, dtype=D64)
+    y64, m64, r64, dx64, dg64, db64 = kr.layernorm_ref64(x, g, b, dy)
+    y, m, r = torch.empty(M, W, dtype=D64), torch.empty(M, dtype=D64), torch.empty(M, dtype=D64)
+    ref.layernorm_fwd(x, g, b, y, m, r)
+    dx, dg, db = torch.empty(M, W, dtype=D64), torch.zeros(W, dtype=D64), torch.zeros(W, dtype=D64)
+    ref.layernorm_bwd(dy, x, m, r, g, dx, dg, db, True)
+    for u, v, n in ((y64, y, "y"), (m64, m, "mean"), (r64, r, "rstd"), (dx64, dx, "dx"), (dg64, dg, "dgamma"), (db64, db, "dbeta")):
+        _close(u, v, n)
+
+
+def test_act_dropout_reference(ref):
+    gen = torch.Generator().manual_seed(3)
+    dy, y = torch.randn(9, 130, generator=gen, dtype=D64), torch.nn.functional.elu(torch.randn(9, 130, generator=gen, dtype=D64))
+    for p, yy in ((0.3, y), (0.3, None), (0.0, y)):
+        o = torch.empty_like(dy)
+        ref.act_dropout_bwd(dy, yy, p, 4242, o)
+        want, keep = kr.act_dropout_ref64(dy, yy, p, 4242)
+        _close(want, o, f"act_dropout p={p}")
+        if keep is not None:
+            assert abs(float(keep.double().mean()) - (1 - p)) < 0.05
+
+
+@pytest.mark.parametrize("s,nh,dh,T", [(1, 2, 4, 3), (3, 2, 8, 5), (4, 1, 16, 1)])
+def test_seqattn_reference(ref, s, nh, dh, T):
+    gen = torch.Generator().manual_seed(s * dh)
+    Fd = nh * dh
+    qkv, dout = torch.randn(s * T, 3 * Fd, generator=gen, dtype=D64), torch.randn(s * T, Fd, generator=gen, dtype=D64)
+    out, dq = kr.seqattn_ref64(qkv, dout, s, T, nh)
+    o, d = torch.empty(s * T, Fd, dtype=D64), torch.empty(s * T, 3 * Fd, dtype=D64)
+    ref.seqattn_fwd(qkv, s, T, nh, o)
+    ref.seqattn_bwd(qkv, dout, s, T, nh, d)
+    _close(out, o, "out"), _close(dq, d, "dqkv")
+    if s == 1:
+        _close(out, qkv[:, 2 * Fd:], "s = 1: the output is v")
+
+
+@pytest.mark.parametrize("s,perms", [(1, [[0]]), (3, [[0, 1, 2], [2, 0, 1], [1, 2, 0]])])
+def test_perm_concat_reference(ref, s, perms):
+    gen = torch.Generator().manual_seed(s)
+    T, Fd, P = 5, 8, len(perms)
+    x, dz = torch.randn(s * T, Fd, generator=gen, dtype=D64), torch.randn(P * T, s * Fd, generator=gen, dtype=D64)
+    z, dx = kr.perm_concat_ref64(x, s, T, perms, dz)
+    z1, dx1 = torch.empty(P * T, s * Fd, dtype=D64), torch.empty(s * T, Fd, dtype=D64)
+    ref.perm_concat_fwd(x, s, T, perms, z1)
+    ref.perm_concat_bwd(dz, s, T, perms, dx1)
+    assert torch.equal(z, z1)
+    _close(dx, dx1, "perm_concat dx")
+
+
+@pytest.mark.parametrize("n_per,offset", [((0, 0, 1, 8), False), ((0, 0, 6, 3), True)])
+def test_mm_reference_autograd_equals_closed_forms(ref, n_per, offset):
+    """autograd of the reference's formulas = the kernels' closed forms (RefBackend), both in float64: energy, dE/dx and the double
+    backward's gk / geq"""
+    from grappa_amd.datasets import build_batch_from_pool
+    lv = ["n2", "n3", "n4", "n4_improper"]
+    g = build_batch_from_pool([300, 301], n_confs=3, seed=1)
+    p = g.plan()
+    xyz = g.nodes["n1"].data["xyz"].double()
+    gen = torch.Generator().manual_seed(5)
+    ks = [700 + 100 * torch.rand(p.T["n2"], generator=gen, dtype=D64), 100 + 20 * torch.rand(p.T["n3"], generator=gen, dtype=D64),
+          torch.randn(p.T["n4"], n_per[2], generator=gen, dtype=D64), torch.randn(p.T["n4_improper"], n_per[3], generator=gen, dtype=D64)]
+    eqs = [1.2 + 0.1 * torch.randn(p.T["n2"], generator=gen, dtype=D64), 1.9 + 0.1 * torch.randn(p.T["n3"], generator=gen, dtype=D64), None, None]
+    B, C, N = p.B, 3, p.N
+    gE, gG = torch.randn(B, C, generator=gen, dtype=D64), torch.randn(N, C, 3, generator=gen, dtype=D64)
+    want = kr.mm_ref64([p.idx32[l].long() for l in lv], [p.mol_ptr[l] for l in lv], B, xyz, ks, eqs, list(n_per), offset, gE, gG)
+    e, terms, grad = torch.empty(B, C, dtype=D64), torch.empty(4, B, C, dtype=D64), torch.empty(N, C, 3, dtype=D64)
+    te = [torch.empty(p.T[l], C, dtype=D64) for l in lv]
+    tx = [torch.empty(p.T[l], C, dtype=D64) for l in lv]
+    ref.mm_energy_fwd(p, xyz, ks, eqs, list(n_per), offset, e, terms, te, tx)
+    ref.mm_gradient_fwd(p, xyz, ks, eqs, list(n_per), grad)
+    gks, geqs = [torch.zeros_like(k) for k in ks], [torch.zeros_like(eqs[0]), torch.zeros_like(eqs[1]), None, None]
+    ref.mm_bwd(p, xyz, ks, eqs, list(n_per), offset, gE, gG, gks, geqs)
+    _close(want["E"], e, "energy", 1e-10), _close(want["G"], grad, "dE/dx", 1e-10)
+    for l in range(4):
+        _close(want["te"][l], te[l], f"tuple energy {lv[l]}", 1e-10), _close(want["tx"][l], tx[l], f"internal coordinate {lv[l]}", 1e-10)
+        _close(want["gk"][l], gks[l], f"gk {lv[l]}", 1e-9)
+    for l in range(2):
+        _close(want["geq"][l], geqs[l], f"geq {lv[l]}", 1e-9)
+
+
+def test_gates_reject_what_they_must():
+    want = torch.linspace(-1, 1, 50, dtype=D64).reshape(5, 10)
+    kr.assert_el(want.float(), want, 1, 0.0, "fp32 rounding of the values")
+    bad = want.clone()
+    bad[3, 7] += 1e-5
+    with pytest.raises(AssertionError):
+        kr.assert_el(bad, want, 64, kr.rowmax(want), "one wrong element")
+    with pytest.raises(AssertionError):
+        kr.assert_el(torch.full_like(want, float("nan")), want, 64, 1.0, "non-finite")
+    # calibrated gate: the same distance as the fp32 reference passes, a row 10x further fails; angles compare modulo 2 pi
+    r32 = want + 1e-6
+    kr.assert_calibrated(want + 1.5e-6, r32, want, 0, 1.0, "within 2x")
+    worse = want + 1e-6
+    worse[2] += 1e-5
+    with pytest.raises(AssertionError):
+        kr.assert_calibrated(worse, r32, want, 0, 1.0, "a row 10x further")
+    ang = torch.tensor([[math.pi - 1e-7], [0.5]], dtype=D64)
+    kr.assert_calibrated(torch.tensor([[-math.pi + 1e-7], [0.5]]), ang, ang, 64, 1.0, "branch cut", period=2 * math.pi)
+    with pytest.raises(AssertionError):
+        kr.assert_calibrated(torch.tensor([[-math.pi + 1e-7], [0.5]]), ang, ang, 64, 1.0, "branch cut without the period")
+    # bf16: the rounding of the value passes, two steps off fails
+    w = torch.randn(1000, generator=torch.Generator().manual_seed(0), dtype=D64)
+    kr.close_bf16(w.to(kr.BF), w, "bf16 rounding")
+    with pytest.raises(AssertionError):
+        kr.close_bf16((w * (1 + 3 * 2.0 ** -7)).to(kr.BF), w, "three steps off")
+
+
+@pytest.mark.parametrize("dummies", [False, True])
+def test_loss_reference_against_ref_molwise_loss(ref, dummies):
+    """kernel_refs.loss_ef_ref64 (the GPU loss tests' float64 reference) = cpu_ref.RefMolwiseLoss run in float64: the loss per molecule
+    and, by autograd through RefMolwiseLoss, the gradients of the batch loss; its eval_se = RefBackend.eval_se on float64 inputs"""
+    from grappa_amd.datasets import build_batch_from_pool
+    from oracle.cpu_ref import RefMolwiseLoss
+    C = 5
+    g = build_batch_from_pool([300, 301, 302], n_confs=C, seed=2)
+    B, N = g.num_nodes("g"), g.num_nodes("n1")
+    sizes = g.batch_num_nodes("n1").long()
+    gen = torch.Generator().manual_seed(7)
+    e, er = torch.randn(B, C, generator=gen, dtype=D64) * 5 + 100, torch.randn(B, C, generator=gen, dtype=D64) * 5 - 40
+    gr, grr = torch.randn(N, C, 3, generator=gen, dtype=D64) * 10, torch.randn(N, C, 3, generator=gen, dtype=D64) * 10
+    dm = None
+    if dummies:
+        dm = torch.zeros(B, C, dtype=D64)
+        dm[0, 3:] = 1
+        dm[2, 1:] = 1
+    wE, wG = 1.0, 0.8
+    loss, gE, gG, se = kr.loss_ef_ref64(sizes, e, er, dm, gr, grr, wE, wG, 1.0 / B)
+    e_, g_ = e.clone().requires_grad_(True), gr.clone().requires_grad_(True)
+    g.nodes["g"].data["energy"], g.nodes["g"].data["energy_ref"] = e_, er
+    g.nodes["n1"].data["gradient"], g.nodes["n1"].data["gradient_ref"] = g_, grr
+    if dm is not None:
+        g.nodes["g"].data["is_dummy"] = dm
+    lf = RefMolwiseLoss(gradient_weight=wG, energy_weight=wE, param_weight=0.0)
+    total = lf(g)
+    gE_r, gG_r = torch.autograd.grad(total, (e_, g_))
+    _close(loss, lf.last_per_molecule, "loss per molecule"), _close(gE, gE_r, "d/d energy"), _close(gG, gG_r, "d/d gradient")
+    se_r = torch.zeros(B, 4, dtype=D64)
+
+    class P:
+        pass
+    p = P()
+    p.B, p.N, p.atom_molptr = B, N, torch.cat([torch.zeros(1, dtype=torch.int64), sizes.cumsum(0)]).int()
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(D64)          # (RefBackend.eval_se makes its sums with the default dtype)
+    try:
+        ref.eval_se(p, e, er, dm, gr, grr, se_r)
+    finally:
+        torch.set_default_dtype(old)
+    _close(se, se_r, "eval_se")
