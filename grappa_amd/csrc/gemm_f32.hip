@@ -385,6 +385,8 @@ struct CostModel {
 constexpr bool pairs_tile_choice() { return true; }      // the round-5 planner: a tile per product from the fitted staircase model
 constexpr int pairs_cfg() { return 6; }                   // the 256 x 128 tile where the model has no say (fp32 A + weight pairs)
 
+// (tests/gemm_routes.py restates the rules below for a forced tile and a forced split -- the ladder of split factors, the rounding of
+//  k_per_split, the tail launch -- to name the kernel every case of the route sweep reaches: change the two together)
 Plan make_plan(int M, int N, int K, const PlanOpts& opt, bool vec = true, bool bf16x = false, bool planes = false, bool pairs = false, bool pairs_small = false,
                int planes_tile = 0) {      // 256 / 128: the bf16 pinned-pipeline kernel's other tiles (GRAPPA_BF16_TILE)
     Plan best;
@@ -642,6 +644,7 @@ bool group_desc_ok(const grappa_gemm_desc& d, int precision) {
 
 // one K chunk for every problem of the group: the chunk that minimises rounds x tile time + the slab round trips (same cost units
 // as CostModel: CU-cycles)
+// (restated by tests/gemm_routes.py group_plan: change the two together)
 GroupPlan plan_group(const grappa_gemm_desc* descs, int n) {
     GroupPlan g;
     double work = 0;

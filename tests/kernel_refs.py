@@ -1,9 +1,10 @@
-"""Float64 references of the non-GEMM kernels and the elementwise gates the domain tests assert with (tests/test_gpu_kernel_domains.py,
-tests/test_gpu_mm_float64.py; checked against oracle/ops_ref.RefBackend and cpu_ref.RefMolwiseLoss on the CPU by
-tests/test_kernel_domain_refs.py).
+"""Float64 references of the kernels and the elementwise gates the domain tests assert with (tests/test_gpu_kernel_domains.py,
+tests/test_gpu_mm_float64.py, tests/test_gpu_gemm_routes.py; checked against oracle/ops_ref.RefBackend and cpu_ref.RefMolwiseLoss on the
+CPU by tests/test_kernel_domain_refs.py).
 
 The references are independent of the kernels' closed forms: they state each operation directly in float64 and take gradients with
 torch.autograd (the GAT from cpu_ref.dot_gat, the MM terms from cpu_ref.bond_length / bond_angle / dihedral)."""
+import functools
 import math
 
 import numpy as np
@@ -289,3 +290,184 @@ def loss_ef_ref64(atom_counts, energy, energy_ref, is_dummy, grad, grad_ref, wE,
     gE, gG = torch.autograd.grad(inv_B * loss.sum(), (e, g))
     se = torch.stack([se_e, nreal, se_g, n_g], 1).detach()
     return loss.detach(), gE, gG, se
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- dense products
+GOLDEN64 = 0x9E3779B97F4A7C15      # include/grappa_hip.h, drop_salt: seed + word * 0x9E3779B97F4A7C15 (mod 2^64)
+FP32_GRADE = ("f32", "f32_bf16x9", "f32_bf16x6", "f32_f16x3")
+
+
+def bf16_round(t):
+    """round to nearest even bf16, back in float64: what a bf16 tensor (`*_nplanes = 1`, C1p, Cp) holds"""
+    return t.float().to(BF).double()
+
+
+@functools.lru_cache(maxsize=2)
+def gemm_keep_mask(drop_seed, drop_salt, M, N, drop_p):
+    """the documented keep mask of an [M, N] output: oracle.ops_ref.dropout_keep(seed + salt * 0x9E3779B97F4A7C15, m * N + n, p), p as the fp32
+    value the descriptor carries"""
+    from oracle.ops_ref import dropout_keep
+    seed = (int(drop_seed) + int(drop_salt) * GOLDEN64) & ((1 << 64) - 1)
+    return dropout_keep(seed, torch.arange(M * N).view(M, N), float(np.float32(drop_p)))
+
+
+def gemm_operands64(A, B, layout):
+    """the operands as the header's A(m, k) and B(n, k), float64: "fwd" A[M,K] B[N,K]; "dgrad" A[M,K] B[K,N]; "wgrad" A[K,M] B[K,N]"""
+    A, B = A.detach().cpu().double(), B.detach().cpu().double()
+    if layout == "fwd":
+        return A, B
+    if layout == "dgrad":
+        return A, B.t()
+    assert layout == "wgrad", layout
+    return A.t(), B.t()
+
+
+def gemm_ref64(A, B, layout, *, pre=None, bias=None, act=0, aux=None, drop_p=0.0, drop_seed=0, drop_salt=0, res=None, res_ln=None,
+               old=None, two_outputs=False, a_colsum_old=None):
+    """The dense product as include/grappa_hip.h documents it (the comment above GRAPPA_ACT_NONE; res_ln_*: ABI 7; a_colsum), in float64 on
+    what the kernel is given (a bf16 tensor is passed in already rounded: bf16_round).  -> (C, OUT, colsum):
+        v = sum_k A(m,k) B(n,k);  v += pre;  v += bias[n];  v = elu(v) (act == 1);  v *= (aux > 0 ? 1 : aux + 1);
+        C = v (two_outputs: the copy before dropout, else None);
+        v = keep(seed + salt * 0x9E3779B97F4A7C15, m * N + n) ? v / (1 - p) : 0;
+        v += res, or with res_ln = (mean, rstd, gamma, beta): v += (res - mean[m]) * rstd[m] * gamma[n] + beta[n];
+        v += old (accumulate);  OUT = v;   colsum[m] = a_colsum_old[m] + sum_k A(m, k).
+    C1p / Cp are bf16_round(C) / bf16_round(OUT).  The keep mask is oracle.ops_ref.dropout_keep (tests/test_capi_symbols.py ties it to the
+    library's host function)."""
+    a, b = gemm_operands64(A, B, layout)
+    d = lambda t: None if t is None else t.detach().cpu().double()          # noqa: E731
+    v = a @ b.t()
+    M, N = v.shape
+    if pre is not None:
+        v = v + d(pre)
+    if bias is not None:
+        v = v + d(bias)[None, :]
+    if act == 1:
+        v = torch.where(v > 0, v, torch.expm1(v))
+    if aux is not None:
+        x = d(aux)
+        v = v * torch.where(x > 0, torch.ones_like(x), x + 1.0)
+    C = v.clone() if two_outputs else None
+    if drop_p > 0:
+        keep = gemm_keep_mask(int(drop_seed), int(drop_salt), M, N, float(drop_p))
+        v = torch.where(keep, v / (1.0 - float(np.float32(drop_p))), torch.zeros_like(v))
+    if res is not None:
+        r = d(res)
+        if res_ln is not None:
+            mean, rstd, gamma, beta = (d(t) for t in res_ln)
+            r = (r - mean[:, None]) * rstd[:, None] * gamma[None, :] + beta[None, :]
+        v = v + r
+    if old is not None:
+        v = v + d(old)
+    colsum = None if a_colsum_old is None else d(a_colsum_old) + a.sum(1)
+    return C, v, colsum
+
+
+def gemm_terms(A, B, layout, *, pre=None, bias=None, drop_p=0.0, drop_seed=0, drop_salt=0, res=None, res_ln=None, old=None, amax_bcast=0):
+    """what assert_gemm's bound is made of, all float64 (M, N): S = sum_k |a_mk| |b_nk| + |pre| + |bias|; gain = 1 / (1 - p) where the
+    dropout keeps the element (1 elsewhere and without dropout); |res| (the LayerNorm rows with res_ln), |old|; h = the absolute term
+    of F32_F16X3, amax_A[m] ||b_n||_1 + amax_B[n] ||a_m||_1 (amax_bcast bit 0 / 1: the whole operand's maximum instead of the row's)"""
+    a, b = gemm_operands64(A, B, layout)
+    a, b = a.abs(), b.abs()
+    S = a @ b.t()
+    M, N = S.shape
+    d = lambda t: t.detach().cpu().double()          # noqa: E731
+    if pre is not None:
+        S = S + d(pre).abs()
+    if bias is not None:
+        S = S + d(bias).abs()[None, :]
+    gain = torch.ones_like(S)
+    if drop_p > 0:
+        keep = gemm_keep_mask(int(drop_seed), int(drop_salt), M, N, float(drop_p))
+        gain = torch.where(keep, gain / (1.0 - float(np.float32(drop_p))), gain)
+    zero = torch.zeros_like(S)
+    r = zero
+    if res is not None:
+        r = d(res)
+        if res_ln is not None:
+            mean, rstd, gamma, beta = (d(t) for t in res_ln)
+            r = ((r - mean[:, None]) * rstd[:, None] * gamma[None, :]).abs() + beta.abs()[None, :]
+        r = r.abs()
+    am_a = a.amax(1) if not (amax_bcast & 1) else a.amax().expand(M)
+    am_b = b.amax(1) if not (amax_bcast & 2) else b.amax().expand(N)
+    h = am_a[:, None] * b.sum(1)[None, :] + am_b[None, :] * a.sum(1)[:, None]
+    return dict(S=S, gain=gain, res=r, old=zero if old is None else d(old).abs(), h=h)
+
+
+def gemm_rep(arithmetic, terms):
+    """the representation error include/grappa_hip.h states for each GRAPPA_GEMM_* arithmetic, as an absolute bound per element:
+      f32, f32_bf16x9  0: "every partial product is exact, the result differs from an fp32 FMA chain only by accumulation order";
+      f32_bf16x6       3 u32 S: "drops terms <= 2^-24 |a||b|": the three dropped piece products, each at most 2^-24 |a||b|;
+      f32_f16x3        3 u32 S + 2^-39 h: "a - hi - lo <= 2^-24 |a|" for each operand and "the dropped lo*lo is <= 2^-24 |a||b|" (three
+                       terms of u32 S), and "elements more than 2^16 below their row's maximum lose relative (never absolute: <= 2^-39 of
+                       the maximum) precision": |da| <= 2^-39 amax_A[m] against |b|, |db| <= 2^-39 amax_B[n] against |a| (h of gemm_terms);
+      bf16x3           4 * 2^-16 S: "2 pieces / 3 products (~2^-16 relative)" -- the header's figure once for each operand's two-piece
+                       representation, once for the dropped lo*lo product, rounded up to a power of two;
+      bf16             (2 + 2^-8) 2^-8 S: "operands rounded to bf16", unit roundoff 2^-8 each: (1 + 2^-8)^2 - 1; 0 ("bf16_given") where both
+                       operands are handed over as bf16 tensors and the reference is taken on those: the kernel rounds nothing."""
+    S = terms["S"]
+    if arithmetic in ("f32", "f32_bf16x9", "bf16_given"):       # bf16_given: BF16 on operands handed over as bf16 (both in one plane) -- exact products
+        return torch.zeros_like(S)
+    if arithmetic == "f32_bf16x6":
+        return 3.0 * U32 * S
+    if arithmetic == "f32_f16x3":
+        return 3.0 * U32 * S + 2.0 ** -39 * terms["h"]
+    if arithmetic == "bf16x3":
+        return 4.0 * 2.0 ** -16 * S
+    assert arithmetic == "bf16", arithmetic
+    return (2.0 + 2.0 ** -8) * 2.0 ** -8 * S
+
+
+def gemm_bound(want64, terms, arithmetic, c_acc, bf16_out=False):
+    """gain * (c_acc * u32 * S + rep) + 4 * u32 * (|f64| + |res| + |old|)  [+ 2^-8 |f64| for a bf16 output]: the accumulation of K products
+    in fp32 in some order (c_acc, calibrated on two fp32 CPU references: tests/gemm_routes.py), the arithmetic's representation error, and
+    four roundings of the epilogue's additions (bias / activation, dropout scale, residual, accumulate).  ELU and ELU' do not amplify
+    (slopes <= 1)."""
+    w = want64.abs()
+    bound = terms["gain"] * (c_acc * U32 * terms["S"] + gemm_rep(arithmetic, terms)) + 4.0 * U32 * (w + terms["res"] + terms["old"])
+    if bf16_out:
+        bound = bound + 2.0 ** -8 * w
+    return bound
+
+
+def gemm_ratio(got, want64, terms):
+    """max |got - f64| / (u32 * gain * S): the figure c_acc is compared with (the report of the GPU sweep)"""
+    d = (got.detach().cpu().double() - want64).abs() / (U32 * terms["gain"] * terms["S"]).clamp_min(1e-300)
+    return float(d.max()) if d.numel() else 0.0
+
+
+def gemm_c_acc_used(got, want64, terms, arithmetic, bf16_out=False):
+    """the smallest c_acc under which `got` passes assert_gemm: max over the elements of the error left after the arithmetic's
+    representation term and the epilogue's roundings, in units of u32 gain S (0 where those alone cover the error)"""
+    d = (got.detach().cpu().double() - want64).abs() - gemm_bound(want64, terms, arithmetic, 0.0, bf16_out)
+    d = d / (U32 * terms["gain"] * terms["S"]).clamp_min(1e-300)
+    return max(float(d.max()), 0.0) if d.numel() else 0.0
+
+
+def assert_gemm(got, want64, terms, arithmetic, what, c_acc, bf16_out=False):
+    """the elementwise gate of the dense products (gemm_bound)"""
+    got = got.detach().cpu().double()
+    want64 = want64.detach().cpu().double()
+    assert got.shape == want64.shape, (what, got.shape, want64.shape)
+    if not bool(torch.isfinite(got).all()):
+        i = int(torch.argmax((~torch.isfinite(got)).reshape(-1).int()))
+        raise AssertionError(f"{what}: {int((~torch.isfinite(got)).sum())} non-finite values (unwritten?), first at (m, n) = {divmod(i, got.shape[1])}")
+    bound = gemm_bound(want64, terms, arithmetic, c_acc, bf16_out)
+    d = (got - want64).abs()
+    bad = d > bound
+    if bool(bad.any()):
+        i = int(torch.argmax((d / bound.clamp_min(1e-300)).reshape(-1)))
+        m, n = divmod(i, got.shape[1])
+        rows, cols = torch.nonzero(bad.any(1)).reshape(-1), torch.nonzero(bad.any(0)).reshape(-1)
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the {arithmetic} gate (c_acc {c_acc}); worst at (m, n) = ({m}, {n}): "
+                             f"got {float(got[m, n]):.9g} f64 {float(want64[m, n]):.9g} ({float(d[m, n] / bound[m, n]):.3g}x the bound); "
+                             f"rows {int(rows[0])}..{int(rows[-1])}, columns {int(cols[0])}..{int(cols[-1])}")
+
+
+def matmul_chain32(a, b, block=8):
+    """a second fp32 summation order of a(M,K) b(N,K)^T: a sequential fp32 chain over blocks of `block` columns of K, each block summed
+    exactly (float64, rounded once)"""
+    a64, b64 = a.double(), b.double()
+    acc = torch.zeros(a.shape[0], b.shape[0], dtype=torch.float32)
+    for k0 in range(0, a.shape[1], block):
+        acc = acc + (a64[:, k0:k0 + block] @ b64[:, k0:k0 + block].t()).float()
+    return acc

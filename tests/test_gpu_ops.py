@@ -76,8 +76,9 @@ def test_gemm_layouts(hip, ref, M, N, K, ak, bk):
     _cmp(out_h, out_r, 2e-5, f"gemm {M}x{N}x{K} ak={ak} bk={bk}")
 
 
-@pytest.mark.parametrize("precision", ["f32", "f32_bf16x9", "f32_bf16x6"])
+@pytest.mark.parametrize("precision", ["f32", "f32_bf16x9", "f32_bf16x6", "f32_f16x3", "bf16x3", "bf16"])
 def test_gemm_epilogues(hip, ref, precision):
+    tol = GEMM_MODE_TOL[precision] if precision in ("bf16x3", "bf16") else 2e-5          # (the fp32-grade bound as it was; the two bf16 arithmetics their own)
     g = torch.Generator().manual_seed(1)
     M, N, K = 333, 192, 160
     A, B = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
@@ -94,9 +95,9 @@ def test_gemm_epilogues(hip, ref, precision):
         kw_h = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in kw.items()}
         hip.gemm(A.cuda(), B.cuda(), o_h, M=M, N=N, K=K, out2=o2_h, precision=precision, **kw_h)
         torch.cuda.synchronize()
-        _cmp(o_h, o_r, 2e-5, f"gemm[{precision}] epilogue {sorted(kw)}")
+        _cmp(o_h, o_r, tol, f"gemm[{precision}] epilogue {sorted(kw)}")
         if two:
-            _cmp(o2_h, o2_r, 2e-5, f"gemm epilogue out2 {sorted(kw)}")
+            _cmp(o2_h, o2_r, tol, f"gemm epilogue out2 {sorted(kw)}")
             # the dropout mask itself must be the documented counter hash: identical zero pattern
             assert torch.equal((o2_h.cpu() - res) == 0, (o2_r - res) == 0) or kw.get("drop_p", 0) == 0
 

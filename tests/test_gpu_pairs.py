@@ -61,11 +61,12 @@ def test_split_k_ranges_of_the_pair_kernels_do_not_overlap(cfg, M, N, K, nsplit)
 
 
 def test_randomised_shapes_formats_plans_and_epilogues_stay_inside_the_arithmetic_error():
-    """48 seeded random cases (tools/gemm_fuzz.py: shape, operand format, forced tile / split-K / tail launch, epilogue) against float64"""
+    """48 seeded random cases (tools/gemm_fuzz.py: shape, operand format, forced tile / split-K / tail launch, epilogue) against float64; the
+    generator draws only plans the planner accepts (tests/test_gemm_route_table.py checks that on the CPU), so no case may be refused"""
     import gemm_fuzz
     worst, refused, bad = gemm_fuzz.run(48, 0, verbose=False)
     assert not bad, bad
-    assert refused < 24, refused
+    assert refused == 0, refused
 
 
 def test_pair_layout_and_rejections():

@@ -211,3 +211,122 @@ def test_loss_reference_against_ref_molwise_loss(ref, dummies):
     finally:
         torch.set_default_dtype(old)
     _close(se, se_r, "eval_se")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- dense products
+import gemm_routes as gr  # noqa: E402
+
+
+def _gemm_case(form, layout="fwd", M=70, N=52, K=96, arith="f32_f16x3"):
+    return gr.Case("cpu", "gate", form, M, N, K, layout=layout, arith=arith, scaled=1)
+
+
+@pytest.mark.parametrize("form,layout", [(f, lay) for f in gr.FORMS if f not in gr.BF16_FORMS and f != "h" for lay in ("fwd", "dgrad", "wgrad")
+                                         if f != "l" or lay == "wgrad"])
+def test_gemm_reference_agrees_with_the_ref_backend(ref, form, layout):
+    """every epilogue form RefBackend.gemm takes (it has no res_ln_* and no bf16 tensors; a_colsum on the wgrad layout only), in float64 on
+    the same inputs"""
+    c = _gemm_case(form, layout)
+    o = gr.operands(c)
+    f = c.f
+    C64, OUT64, cs64, _ = gr.reference(c, o, seed=77)
+    d = lambda t: None if t is None else t.double()          # noqa: E731
+    out = d(o["old"]).clone() if o["old"] is not None else torch.full((c.M, c.N), float("nan"), dtype=D64)
+    out2 = torch.full((c.M, c.N), float("nan"), dtype=D64) if f["c2"] else None
+    colsum = d(o["colsum_old"]).clone() if f["colsum"] else None
+    first = out if not f["c2"] else torch.full((c.M, c.N), float("nan"), dtype=D64)
+    ref.gemm(d(o["A"]), d(o["B"]), first, M=c.M, N=c.N, K=c.K, a_kcontig=layout != "wgrad", b_kcontig=layout == "fwd", bias=d(o["bias"]), res=d(o["res"]),
+             aux=d(o["aux"]), pre=d(o["pre"]), act=f["act"], drop_p=float(np.float32(f["drop"])), drop_seed=77, accumulate=bool(f["acc"]), out2=out2, a_colsum=colsum)
+    _close(OUT64, out2 if f["c2"] else first, f"OUT {form}")
+    if f["c2"]:
+        _close(C64, first, f"C {form}")
+    if f["colsum"]:
+        _close(cs64, colsum, "a_colsum")
+
+
+def test_gemm_reference_res_ln_and_salt():
+    """what RefBackend has no argument for: the residual recomputed from the rows before their LayerNorm equals the residual given
+    normalised; the salt moves the seed by salt * 0x9E3779B97F4A7C15"""
+    c = _gemm_case("h")
+    o = gr.operands(c)
+    _, with_ln, _, _ = gr.reference(c, o, seed=5)
+    y = torch.nn.functional.layer_norm(o["res"].double(), (c.N,), o["ln"][2].double(), o["ln"][3].double(), 1e-5)
+    _, plain, _ = kr.gemm_ref64(o["A"], o["B"], "fwd", bias=o["bias"], drop_p=c.f["drop"], drop_seed=5, res=y)
+    assert float((with_ln - plain).abs().max()) < 1e-5          # (mean / rstd travel as fp32)
+    _, salted, _ = kr.gemm_ref64(o["A"], o["B"], "fwd", bias=o["bias"], drop_p=0.25, drop_seed=5, drop_salt=3)
+    _, moved, _ = kr.gemm_ref64(o["A"], o["B"], "fwd", bias=o["bias"], drop_p=0.25, drop_seed=(5 + 3 * kr.GOLDEN64) & ((1 << 64) - 1))
+    _, unsalted, _ = kr.gemm_ref64(o["A"], o["B"], "fwd", bias=o["bias"], drop_p=0.25, drop_seed=5)
+    assert torch.equal(salted, moved) and not torch.equal(salted, unsalted)
+
+
+def _fp32_product(c, o, seed, a=None, keep_shift=0, res_before_drop=False):
+    """the documented product in fp32 on the CPU (torch.matmul + the epilogue), with the faults the gate must catch"""
+    from oracle.ops_ref import dropout_keep
+    f = c.f
+    a64, b64 = kr.gemm_operands64(o["A"], o["B"], c.layout)
+    v = (a64.float() if a is None else a) @ b64.float().t()
+    if o["pre"] is not None:
+        v = v + o["pre"]
+    if o["bias"] is not None:
+        v = v + o["bias"]
+    if f["act"]:
+        v = torch.nn.functional.elu(v)
+    if o["aux"] is not None:
+        v = v * torch.where(o["aux"] > 0, torch.ones_like(v), o["aux"] + 1.0)
+    if res_before_drop and o["res"] is not None:
+        v = v + o["res"]
+    if f["drop"] > 0:
+        p = float(np.float32(f["drop"]))
+        keep = dropout_keep(seed, torch.arange(c.M * c.N).view(c.M, c.N) + keep_shift, p)
+        v = torch.where(keep, v * np.float32(1.0 / (1.0 - p)), torch.zeros_like(v))
+    if not res_before_drop and o["res"] is not None:
+        v = v + o["res"]
+    if o["old"] is not None:
+        v = v + o["old"]
+    return v
+
+
+def _hi_only(a64):
+    """A with its low piece lost: the fp16 HI part under the row scale of include/grappa_hip.h (ABI 5), s = 141 - exponent field of the row maximum"""
+    am = a64.abs().amax(1, keepdim=True).float()
+    s = 141 - ((am.view(torch.int32) >> 23) & 0xff)
+    scale = torch.exp2(s.double())
+    return ((a64 * scale).to(torch.float16).double() / scale).float()
+
+
+@pytest.mark.parametrize("arith", kr.FP32_GRADE)
+@pytest.mark.parametrize("form,K", [("a", 6), ("d", 96), ("i", 400), ("g", 1104), ("d", 5000)])
+def test_gemm_gate_is_sharp(arith, form, K):
+    """on the sweep's own operand generator: the fp32 CPU product passes assert_gemm; a product whose A lost its low fp16 piece (what a dropped
+    hi * lo term or a flushed denormal gives, ~2^-12), one element with the neighbouring column's bias, a keep mask shifted by one index and
+    a residual added before the dropout all fail, under every fp32-grade arithmetic"""
+    c = _gemm_case(form, M=96, N=64, K=K, arith=arith)
+    o = gr.operands(c)
+    _, OUT64, _, terms = gr.reference(c, o, seed=9)
+    good = _fp32_product(c, o, 9)
+    kr.assert_gemm(good, OUT64, terms, arith, "fp32 CPU product", gr.C_ACC)
+    a64, _ = kr.gemm_operands64(o["A"], o["B"], c.layout)
+    with pytest.raises(AssertionError):
+        kr.assert_gemm(_fp32_product(c, o, 9, a=_hi_only(a64)), OUT64, terms, arith, "A without its low piece", gr.C_ACC)
+    if c.f["bias"]:
+        bad = good.clone()
+        keep = terms["gain"] > 1.0
+        m, n = (int(x) for x in torch.nonzero(keep)[5])
+        bad[m, n] = bad[m, n] + (o["bias"][(n + 1) % c.N] - o["bias"][n]) * float(terms["gain"][m, n])
+        with pytest.raises(AssertionError):
+            kr.assert_gemm(bad, OUT64, terms, arith, "one element with its neighbour's bias", gr.C_ACC)
+    if c.f["drop"] > 0:
+        with pytest.raises(AssertionError):
+            kr.assert_gemm(_fp32_product(c, o, 9, keep_shift=1), OUT64, terms, arith, "keep mask shifted by one", gr.C_ACC)
+        with pytest.raises(AssertionError):
+            kr.assert_gemm(_fp32_product(c, o, 9, res_before_drop=True), OUT64, terms, arith, "residual before the dropout", gr.C_ACC)
+
+
+def test_c_acc_is_twice_the_cpu_references_error():
+    """gemm_routes.C_ACC = 2 x the larger error of two fp32 CPU summation orders over every product of the table, in units of u32 S; the
+    block-of-8 chain is deterministic and must reproduce its tabulated figure, torch.matmul's blocking depends on the CPU and must stay
+    inside the gate it calibrates"""
+    assert gr.C_ACC == 2.0 * max(gr.R_MATMUL, gr.R_CHAIN)
+    r_mm, r_ch = gr.calibrate()
+    assert gr.R_CHAIN - 0.01 <= r_ch <= gr.R_CHAIN, r_ch
+    assert r_mm <= gr.C_ACC, r_mm

@@ -1,6 +1,6 @@
 """GPU: randomised shapes x operand formats x forced plans x epilogues for the fp32-grade dense products, each against a float64 product
 (error bound of the arithmetic, 3e-6 of the row's largest magnitude): the all-pairs kernels (three tiles), fp32 A + weight pairs, the
-fp32-operand split kernel.  A forced plan the planner refuses (status != 0) is skipped and counted.
+fp32-operand split kernel.  A case the library refuses (status != 0) is counted; plan_accepted restates the refusal conditions on the host.
     python tools/gemm_fuzz.py [n_cases] [seed]          # tests/test_gpu_pairs.py runs 48 cases of seed 0"""
 import os
 import sys
@@ -15,7 +15,33 @@ import gemm_pairs_check as g  # noqa: E402
 dev = "cuda"
 
 
-def one_case(rng, gen):
+def plan_accepted(p):
+    """grappa_gemm_f32's refusal conditions (gemm_f32.hip) for a drawn case, host only: the shapes and alignments the operand formats take,
+    the tile the forced plan names, the 4 GiB limit of the DMA-read operands; fp32 operands also ask grappa_gemm_f32_plan_desc.  The draw
+    has been free of refusals since the planner began to round a forced split to what K allows: this is the check of that, not a filter."""
+    M, N, K, plan = p["M"], p["N"], p["K"], p["plan"]
+    if min(M, N, K) <= 0 or plan.get("plan_nsplit", 0) < 0 or not 0 <= plan.get("plan_tail", 0) <= 3:
+        return False
+    if p["kind"] != "split":
+        kpad = (K + 31) // 32 * 32
+        if M <= 32 or N <= 32 or max(M, N) * 2 * kpad * 2 >= 1 << 32:              # pair rows: 2 * kpad fp16 elements
+            return False
+        if p["kind"] == "wpairs":                                                 # fp32 A: whole slabs of 16, 16-byte rows, the 256 x 128 tile only
+            return K % 16 == 0 and "plan_cfg" not in plan and M * K * 4 < 1 << 32
+        return plan.get("plan_cfg", 7) - 1 in (6, 7, 8)
+    import ctypes as C
+    from grappa_amd import _lib
+    d = _lib.GemmDesc()
+    d.M, d.N, d.K, d.precision = M, N, K, _lib.GEMM_PRECISIONS["f32_f16x3"]
+    for k, v in plan.items():
+        setattr(d, k, v)
+    out = [C.c_int() for _ in range(5)]
+    return _lib.load().grappa_gemm_f32_plan_desc(C.byref(d), *[C.byref(o) for o in out]) == 0
+
+
+def draw(rng):
+    """one case from the numpy generator alone (shape, operand format, scales, epilogue, forced plan): the same sequence of draws with or
+    without a GPU (plan_accepted says, host only, whether the library takes it)"""
     kind = rng.choice(["pairs", "pairs", "wpairs", "wpairs", "split"])
     M = int(np.exp(rng.uniform(np.log(1), np.log(60000))))
     N = int(rng.choice([32, 64, 96, 128, 160, 256, 384, 512, 516, 768, 1536, 2048]))
@@ -24,26 +50,8 @@ def one_case(rng, gen):
         M, N = max(M, 33), max(N, 64)
     if M * max(N, K) > 48_000_000:
         M = 48_000_000 // max(N, K)
-    dgrad = bool(rng.integers(0, 2)) and kind != "split"
-    A = torch.randn((M, K), generator=gen, device=dev) * float(np.exp(rng.uniform(-6, 6)))
-    if rng.integers(0, 3) == 0:
-        A = A * torch.exp2(torch.randint(-30, 30, (M, 1), generator=gen, device=dev).float())
-    W = torch.randn((K, N) if dgrad else (N, K), generator=gen, device=dev) * 0.05
-    am_a, am_b = g.amax(A), g.amax(W, rows=not dgrad)
-    ref = A.double() @ (W.double() if dgrad else W.double().t())
-    kw, epi = {}, []
-    if rng.integers(0, 2):
-        kw["bias"] = torch.randn(N, generator=gen, device=dev)
-        ref = ref + kw["bias"].double()
-        epi.append("b")
-    if rng.integers(0, 3) == 0:
-        kw["act"] = 1
-        ref = torch.nn.functional.elu(ref)
-        epi.append("e")
-    if rng.integers(0, 2):
-        kw["res"] = torch.randn((M, N), generator=gen, device=dev)
-        ref = ref + kw["res"].double()
-        epi.append("r")
+    p = dict(kind=str(kind), M=M, N=N, K=K, dgrad=bool(rng.integers(0, 2)) and kind != "split", a_scale=float(np.exp(rng.uniform(-6, 6))),
+             scale_rows=rng.integers(0, 3) == 0, bias=bool(rng.integers(0, 2)), act=rng.integers(0, 3) == 0, res=bool(rng.integers(0, 2)))
     plan = {}
     ns = int(rng.choice([0, 0, 1, 2, 3, 5, 8]))
     if ns:
@@ -51,6 +59,32 @@ def one_case(rng, gen):
     if kind == "pairs" and rng.integers(0, 2):
         plan["plan_cfg"] = int(rng.choice([6, 7, 8])) + 1
     plan["plan_tail"] = int(rng.choice([0, 1, 2]))
+    p["plan"] = plan
+    return p
+
+
+def one_case(rng, gen):
+    p = draw(rng)
+    kind, M, N, K, dgrad, plan = p["kind"], p["M"], p["N"], p["K"], p["dgrad"], p["plan"]
+    A = torch.randn((M, K), generator=gen, device=dev) * p["a_scale"]
+    if p["scale_rows"]:
+        A = A * torch.exp2(torch.randint(-30, 30, (M, 1), generator=gen, device=dev).float())
+    W = torch.randn((K, N) if dgrad else (N, K), generator=gen, device=dev) * 0.05
+    am_a, am_b = g.amax(A), g.amax(W, rows=not dgrad)
+    ref = A.double() @ (W.double() if dgrad else W.double().t())
+    kw, epi = {}, []
+    if p["bias"]:
+        kw["bias"] = torch.randn(N, generator=gen, device=dev)
+        ref = ref + kw["bias"].double()
+        epi.append("b")
+    if p["act"]:
+        kw["act"] = 1
+        ref = torch.nn.functional.elu(ref)
+        epi.append("e")
+    if p["res"]:
+        kw["res"] = torch.randn((M, N), generator=gen, device=dev)
+        ref = ref + kw["res"].double()
+        epi.append("r")
     out = torch.full((M, N), float("nan"), device=dev)
     g.EXTRA = plan
     try:
