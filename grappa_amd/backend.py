@@ -11,7 +11,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import List, Optional, Sequence
+from collections import namedtuple
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -91,6 +92,7 @@ def _flat(t: torch.Tensor, name: str, dev, dtype=torch.float32) -> None:
 
 
 DEFAULT_GEMM_PRECISION = "f32_f16x3"
+_P_F32, _P_BF16, _P_F16X3 = (_lib.GEMM_PRECISIONS[k] for k in ("f32", "bf16", "f32_f16x3"))
 
 
 _AMAX_LOG = None      # tools/amax_passes.py sets a list here
@@ -118,13 +120,58 @@ class Amax:
         self.pairs = pairs
 
 
+class _Route(NamedTuple):
+    """how a dense product reaches the library (HipBackend._route)"""
+    # "pairs": A (its producer wrote the pairs) and the weight in the pair format | "wpairs": fp32 A against the weight's pairs | "bf16_planes": a
+    # bf16 A as a one-plane operand against the weight's bf16 planes | "weight_planes": fp32 A against opt-in weight planes | "wgrad_planes": two
+    # bf16 activations, weight-gradient layout | "split": fp32 operands on the split kernels | "native": the native fp32 kernel
+    name: str
+    layout: str            # "fwd" | "dgrad" | "wgrad": what the caller asked for (pair operands turn every layout into k-contiguous rows)
+    big: bool              # M, N > 32
+    a_f32: bool            # A / B must be converted to fp32 first
+    b_f32: bool
+    precision: int         # the arithmetic actually used (GRAPPA_GEMM_*)
+
+    @property
+    def fmt(self) -> str:              # operand formats, as the profile details name them
+        return self.name if self.name in ("pairs", "wpairs") else ("planes" if self.name.endswith("planes") else "f32")
+
+    @property
+    def fp16_split(self) -> bool:      # the fp16-split kernel families: they launch as groups and can leave their output maxima as per-segment partials
+        return self.name in ("pairs", "wpairs", "split")
+
+
 class _PendingGemm:
     """a product whose descriptor is built but not launched (HipBackend.gemm_group)"""
-    __slots__ = ("d", "shape", "flops", "nbytes", "ret", "dev", "keep", "groupable", "key")
+    __slots__ = ("d", "route", "shape", "flops", "nbytes", "ret", "dev", "keep", "groupable", "key")
 
-    def __init__(self, d, shape, flops, nbytes, ret, dev, keep, groupable):
-        self.d, self.shape, self.flops, self.nbytes, self.ret, self.dev, self.keep, self.groupable = d, shape, flops, nbytes, ret, dev, keep, groupable
-        self.key = (int(d.b_kcontig), int(d.a_planes), int(d.b_planes), int(d.precision))
+    def __init__(self, d, route, shape, flops, nbytes, ret, dev, keep, groupable):
+        self.d, self.route, self.shape, self.flops, self.nbytes, self.ret, self.dev, self.keep, self.groupable = d, route, shape, flops, nbytes, ret, dev, keep, groupable
+        # one launch takes one operand format, layout and arithmetic (pair operands are k-contiguous rows whatever the layout)
+        self.key = (route.name, route.name == "split" and route.layout, route.precision)
+
+
+# ---- what the caches and queues of HipBackend hold
+_PlanesEntry = namedtuple("_PlanesEntry", "ver planes ref")                      # _wplanes: version key, planes / packed tensor, weakref of the weight
+_PairsTable = namedtuple("_PairsTable", "tab n tiles keep")                      # _wptable: device table of grappa_split_pairs_item, count, tiles, records kept alive
+_AmaxTable = namedtuple("_AmaxTable", "tab n")                                   # _wtable: device table of grappa_amax_item, count
+_PairsRefresh = namedtuple("_PairsRefresh", "event captured ordered")            # _wpairs_ready: event, recorded while capturing, handles of the streams ordered after it
+_WgradItem = namedtuple("_WgradItem", "dz x dw db am pz px")                     # a queued weight-gradient product: fp32 operands (None: read from the pairs), dW, db, maxima records
+_LnItem = namedtuple("_LnItem", "part nrows W dgamma_ptr dbeta_ptr dgamma dbeta stream task")      # a deferred LayerNorm parameter-gradient reduction
+
+
+class _PairsEntry:                      # _wpairs: the pairs of one weight in one orientation
+    __slots__ = ("ver", "pairs", "ref", "epoch", "transposed", "amax")
+
+    def __init__(self, ver, pairs, ref, epoch, transposed, amax):
+        self.ver, self.pairs, self.ref, self.epoch, self.transposed, self.amax = ver, pairs, ref, epoch, transposed, amax
+
+
+class _AmaxEntry:                       # _wamax: the row / column maxima of one weight, which the entry keeps alive
+    __slots__ = ("ver", "w", "amax", "epoch", "batchable")
+
+    def __init__(self, ver, w, amax, epoch, batchable):
+        self.ver, self.w, self.amax, self.epoch, self.batchable = ver, w, amax, epoch, batchable
 
 
 class HipBackend:
@@ -153,9 +200,9 @@ class HipBackend:
         # weight-gradient products of a backward pass are queued and launched together (grappa_gemm_f32_grouped): alone, each must
         # cut its K (= tokens) 10 - 32 ways to fill the chip and pays for that many partial tiles per output tile
         self.defer_wgrads = os.environ.get("GRAPPA_DEFER_WGRADS", "1") not in ("0", "")
-        self._wq = {}                  # (autograd graph task id, stream handle) -> (stream, [(dz, x, dW, db, maxima) kept alive until the launch])
+        self._wq = {}                  # (autograd graph task id, stream handle) -> (stream, [_WgradItem kept alive until the launch])
         self.defer_ln = os.environ.get("GRAPPA_DEFER_LN_REDUCTIONS", "1") not in ("0", "")      # tuning: 0 = reduce every LayerNorm's parameter gradients at once
-        self._lnq = []                 # deferred LayerNorm parameter gradients: (partials, rows, W, dgamma ptr, dbeta ptr, dgamma, dbeta, stream, task id)
+        self._lnq = []                 # deferred LayerNorm parameter gradients (_LnItem)
         self._tasks = set()            # autograd graph task ids (backward passes) that have an end-of-pass callback registered and not yet run
         self.wgrad_queue_bytes = int(float(os.environ.get("GRAPPA_WGRAD_QUEUE_GB", "12")) * 2 ** 30)
         # inference (no gradient asked for): LayerNorm and the tuple attention write the A operand of the product behind them in the pair
@@ -207,16 +254,16 @@ class HipBackend:
         # ... and the first layer of the angle / proper heads (ops.ProjFirstLayerFn: LayerNorm + q | k | v on (atom, position) rows) through the same
         # kernels in their gather mode; 0: the unfused sequence behind the table-level products
         self.fused_first_layer = os.environ.get("GRAPPA_FUSED_FIRST_LAYER", "1") not in ("0", "")
-        self._wplanes = {}     # (data_ptr, rows, cols, transposed) -> (version key, planes tensor)
-        self._wpairs = {}      # (data_ptr, rows, cols, "pairs" | "pairsT") -> [version key, pairs, weakref of the weight, epoch of last use, transposed, maxima record]
-        self._wptable = None   # (device table of grappa_split_pairs_item, count, tiles, records kept alive)
-        self._wpairs_ready = None  # (event after the last batched pairs refresh, recorded while capturing, handles of the streams ordered after it)
+        self._wplanes = {}     # (data_ptr, rows, cols, transposed) -> _PlanesEntry
+        self._wpairs = {}      # (data_ptr, rows, cols, "pairs" | "pairsT") -> _PairsEntry
+        self._wptable = None   # _PairsTable of the registered pairs
+        self._wpairs_ready = None  # _PairsRefresh of the last batched pairs refresh
         self._wepoch = 0
         # precision "f32_f16x3": largest |element| per row / column of every operand (grappa_amax_f32).  Weights: cached until the
         # optimiser step; activations: an `Amax` record travels with the tensor through ops.py (gemm returns it, the backward
         # products receive it), anything missing is computed by one pass over the tensor
-        self._wamax = {}       # (data_ptr, rows, cols, ld) -> [version key, weight kept alive, Amax, epoch of last use, batchable]
-        self._wtable = None    # (device table of grappa_amax_item, count) of the batchable entries
+        self._wamax = {}       # (data_ptr, rows, cols, ld) -> _AmaxEntry
+        self._wtable = None    # _AmaxTable of the batchable entries
         # weight-gradient products reduce over the tokens, so each operand gets ONE scale (its largest magnitude): columns more than
         # 2^16 below it lose relative precision gradually.  GRAPPA_WGRAD_COLUMN_MAXIMA=1 gives every column its own scale instead,
         # at the price of one extra pass over both operands of every weight-gradient product (rigorous, ~15 % slower steps)
@@ -246,30 +293,36 @@ class HipBackend:
         the parameter itself (`p.copy_`, `load_state_dict`) and `FusedAdam.step` need no call."""
         self._wepoch += 1
 
-    def _planes_of_weight(self, w: torch.Tensor, transposed: bool) -> torch.Tensor:
-        """bf16 planes (3, rows_pad, cols_pad) of W (rows x cols) or of W^T; zero padded to multiples of 32, cached per weight and
-        refreshed when the weight changed (torch's version counter for in-place torch ops, the epoch for the fused Adam)"""
-        R, Cc = w.shape
-        key = (w.data_ptr(), R, Cc, transposed)
+    def _cached_form(self, w: torch.Tensor, tag, alloc, fill) -> torch.Tensor:
+        """a tensor made from the weight W (`alloc()`, written by `fill(tensor)`), cached per weight and form and written again when the weight
+        changed (torch's version counter for in-place torch ops, the epoch for the fused Adam)"""
+        key = (w.data_ptr(), *w.shape, tag)
         ver = (w._version, self._wepoch)
         hit = self._wplanes.get(key)
         # an entry belongs to ONE tensor object (weak reference): a weight freed and another allocated at the same address with the same
         # shape and version count must not be served the old one's planes (two models loaded one after the other, no optimiser step between)
-        if hit is not None and hit[2]() is not w:
+        if hit is not None and hit.ref() is not w:
             hit = None
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        rows, cols = (Cc, R) if transposed else (R, Cc)
+        if hit is not None and hit.ver == ver:
+            return hit.planes
         if hit is not None:
-            planes = hit[1]
+            t = hit.planes
         else:
-            planes = torch.zeros((3, (rows + 31) // 32 * 32, (cols + 31) // 32 * 32), dtype=torch.bfloat16, device=w.device)
-            for k in [k for k, e in self._wplanes.items() if e[2]() is None]:      # entries of weights that no longer exist
+            t = alloc()
+            for k in [k for k, e in self._wplanes.items() if e.ref() is None]:      # entries of weights that no longer exist
                 del self._wplanes[k]
-        _chk(self.lib.grappa_split_planes_f32(self._stream(), R, Cc, w.data_ptr(), _f32_2d(w, "W", w.device), planes.data_ptr(), planes.stride(1),
-                                              planes.stride(0), int(transposed)), "grappa_split_planes_f32")
-        self._wplanes[key] = (ver, planes, weakref.ref(w))
-        return planes
+        fill(t)
+        self._wplanes[key] = _PlanesEntry(ver, t, weakref.ref(w))
+        return t
+
+    def _planes_of_weight(self, w: torch.Tensor, transposed: bool) -> torch.Tensor:
+        """bf16 planes (3, rows_pad, cols_pad) of W (rows x cols) or of W^T; zero padded to multiples of 32"""
+        R, Cc = w.shape
+        rows, cols = (Cc, R) if transposed else (R, Cc)
+        return self._cached_form(
+            w, transposed, lambda: torch.zeros((3, (rows + 31) // 32 * 32, (cols + 31) // 32 * 32), dtype=torch.bfloat16, device=w.device),
+            lambda pl: _chk(self.lib.grappa_split_planes_f32(self._stream(), R, Cc, w.data_ptr(), _f32_2d(w, "W", w.device), pl.data_ptr(), pl.stride(1),
+                                                             pl.stride(0), int(transposed)), "grappa_split_planes_f32"))
 
     def _pairs_of_weight(self, w: torch.Tensor, transposed: bool = False) -> torch.Tensor:
         """W (out features x in features) in the pair format, rows scaled by their own maxima -- the B operand of the forward products -- or
@@ -280,24 +333,24 @@ class HipBackend:
         key = (w.data_ptr(), R, Cc, "pairsT" if transposed else "pairs")
         ver = (w._version, self._wepoch)
         hit = self._wpairs.get(key)
-        if hit is not None and hit[2]() is not w:
+        if hit is not None and hit.ref() is not w:
             hit = None
         if hit is not None:
-            hit[3] = self._wepoch
-            if hit[0] == ver:
+            hit.epoch = self._wepoch
+            if hit.ver == ver:
                 self._after_pairs_refresh()
-                return hit[1]
+                return hit.pairs
             self._refresh_weight_pairs()
-            if hit[0] == ver:
-                return hit[1]
+            if hit.ver == ver:
+                return hit.pairs
         am = self._amax_of_weight(w)
         rows, cols = (Cc, R) if transposed else (R, Cc)
         pairs = torch.zeros((rows, 2 * ((cols + 31) // 32 * 32)), dtype=torch.float16, device=w.device)
         _chk(self.lib.grappa_split_pairs_f32(self._stream(), R, Cc, w.data_ptr(), _f32_2d(w, "W", w.device), (am.col if transposed else am.row).data_ptr(),
                                              pairs.data_ptr(), pairs.stride(0), int(transposed)), "grappa_split_pairs_f32")
-        for k in [k for k, e in self._wpairs.items() if e[2]() is None]:      # entries of weights that no longer exist
+        for k in [k for k, e in self._wpairs.items() if e.ref() is None]:      # entries of weights that no longer exist
             del self._wpairs[k]
-        self._wpairs[key] = [ver, pairs, weakref.ref(w), self._wepoch, transposed, am]
+        self._wpairs[key] = _PairsEntry(ver, pairs, weakref.ref(w), self._wepoch, transposed, am)
         self._wptable = None
         return pairs
 
@@ -306,34 +359,34 @@ class HipBackend:
         # (never while a hipGraph is being recorded: a changed table is a host-to-device copy, which a capture cannot hold; what would have
         # aged out is refreshed once more instead)
         ageing = not torch.cuda.is_current_stream_capturing()
-        for k in [k for k, e in self._wpairs.items() if e[2]() is None or (ageing and e[3] < self._wepoch - 1)]:      # dead, or unused since the step before last
+        for k in [k for k, e in self._wpairs.items() if e.ref() is None or (ageing and e.epoch < self._wepoch - 1)]:      # dead, or unused since the step before last
             del self._wpairs[k]
             self._wptable = None
-        live = [e for e in self._wpairs.values()]
+        live = list(self._wpairs.values())
         if not live:
             return
         for e in live:                                  # the maxima first (one batched launch of their own when stale)
-            e[5] = self._amax_of_weight(e[2]())
+            e.amax = self._amax_of_weight(e.ref())
         if self._wptable is None:
             dt = np.dtype([("x", "<u8"), ("amax", "<u8"), ("pairs", "<u8"), ("R", "<i4"), ("C", "<i4"), ("ldx", "<i4"), ("ldp", "<i4"),
                            ("transpose", "<i4"), ("tile_begin", "<i4")])
             tab = np.zeros(len(live), dtype=dt)
             tiles = 0
             for i, e in enumerate(live):
-                w, am = e[2](), e[5]
-                tab[i] = (w.data_ptr(), (am.col if e[4] else am.row).data_ptr(), e[1].data_ptr(), w.shape[0], w.shape[1], w.stride(0), e[1].stride(0),
-                          int(e[4]), tiles)
+                w, am = e.ref(), e.amax
+                tab[i] = (w.data_ptr(), (am.col if e.transposed else am.row).data_ptr(), e.pairs.data_ptr(), w.shape[0], w.shape[1], w.stride(0),
+                          e.pairs.stride(0), int(e.transposed), tiles)
                 tiles += ((w.shape[0] + 31) // 32) * ((w.shape[1] + 31) // 32)
-            self._wptable = (torch.from_numpy(tab.view(np.uint8).copy()).to(live[0][1].device), len(live), tiles, [e[5] for e in live])
-        tab, n, tiles, _keep = self._wptable
-        _chk(self.lib.grappa_split_pairs_f32_batched(self._stream(), n, tiles, tab.data_ptr()), "grappa_split_pairs_f32_batched")
+            self._wptable = _PairsTable(torch.from_numpy(tab.view(np.uint8).copy()).to(live[0].pairs.device), len(live), tiles, [e.amax for e in live])
+        t = self._wptable
+        _chk(self.lib.grappa_split_pairs_f32_batched(self._stream(), t.n, t.tiles, t.tab.data_ptr()), "grappa_split_pairs_f32_batched")
         for e in live:
-            e[0] = (e[2]()._version, self._wepoch)
+            e.ver = (e.ref()._version, self._wepoch)
         # the first stale use is usually a writer head's product on its own stream (no GNN product reads weight pairs at C2 sizes), and the
         # launch above rewrites the pairs of EVERY head's weights: the other heads' streams must not read theirs before it has run
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
-        self._wpairs_ready = (ev, torch.cuda.is_current_stream_capturing(), {self._stream()})
+        self._wpairs_ready = _PairsRefresh(ev, torch.cuda.is_current_stream_capturing(), {self._stream()})
 
     def _after_pairs_refresh(self) -> None:
         """order the current stream after the last batched refresh of the weights' pairs (once per stream and refresh).  An event recorded
@@ -341,13 +394,12 @@ class HipBackend:
         r = self._wpairs_ready
         if r is None:
             return
-        ev, captured, ordered = r
         h = self._stream()
-        if h in ordered:
+        if h in r.ordered:
             return
-        ordered.add(h)
-        if torch.cuda.is_current_stream_capturing() == captured:
-            torch.cuda.current_stream().wait_event(ev)
+        r.ordered.add(h)
+        if torch.cuda.is_current_stream_capturing() == r.captured:
+            torch.cuda.current_stream().wait_event(r.event)
 
     def to_pairs(self, x: torch.Tensor, have: "Optional[Amax]" = None) -> "Amax":
         """an fp32 (rows, cols) tensor in the pair format by a pass of its own (producers that hold whole rows write it themselves:
@@ -383,19 +435,11 @@ class HipBackend:
         row = (row_out if row_out is not None else torch.empty(R, dtype=torch.int32, device=dev)) if rows else None
         col = (col_out if col_out is not None else torch.empty(Cc, dtype=torch.int32, device=dev)) if cols else None
         need = self.lib.grappa_amax_f32_workspace_bytes(R, Cc) if cols else 0
-        ws = self._workspace_amax(need, dev) if need else None
+        ws = self._workspace(need, dev, "amax") if need else None      # (not the products' workspace: a queued group may hold that)
         self._timed("amax", 0.0, 4.0 * R * Cc,
                     lambda: _chk(self.lib.grappa_amax_f32(self._stream(), R, Cc, t.data_ptr(), ld, _ptr(row), _ptr(col), _ptr(ws),
                                                           ws.numel() if ws is not None else 0), "grappa_amax_f32"))
         return row, col
-
-    def _workspace_amax(self, nbytes: int, dev) -> torch.Tensor:
-        key = (dev, self._stream(), "amax")      # not the products' workspace: a queued group may hold that
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=dev)
-            self._ws[key] = ws
-        return ws
 
     def amax(self, t: torch.Tensor, have: "Optional[Amax]" = None, rows: bool = False, cols: bool = False, tmax: bool = False) -> "Amax":
         """`have` completed by the maxima asked for (one pass over t for missing row / column maxima; the whole-tensor maximum is
@@ -451,23 +495,23 @@ class HipBackend:
         ver = (w._version, self._wepoch)
         hit = self._wamax.get(key)
         if hit is not None:
-            hit[3] = self._wepoch
-            if hit[0] == ver:
-                return hit[2]
-            if hit[4]:                                     # registered for the batched refresh
+            hit.epoch = self._wepoch
+            if hit.ver == ver:
+                return hit.amax
+            if hit.batchable:                              # registered for the batched refresh
                 self._refresh_weight_amax()
-                if hit[0] == ver:
-                    return hit[2]
-            elif hit[1] is w:
+                if hit.ver == ver:
+                    return hit.amax
+            elif hit.w is w:
                 # a weight the batched kernel cannot take (odd width): a pass of its own INTO the arrays it already has -- the same
                 # addresses every step (a recorded hipGraph holds them) and no change to the batched kernel's table
-                self._amax_launch(w, True, True, hit[2].row, hit[2].col)
-                hit[2].tmax = None
-                hit[0] = ver
-                return hit[2]
+                self._amax_launch(w, True, True, hit.amax.row, hit.amax.col)
+                hit.amax.tmax = None
+                hit.ver = ver
+                return hit.amax
         am = self.amax(w, None, rows=True, cols=True)      # a new weight: a pass of its own
         batchable = Cc % 4 == 0 and Cc <= 2048 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0 and w.stride(1) == 1
-        self._wamax[key] = [ver, w, am, self._wepoch, batchable]
+        self._wamax[key] = _AmaxEntry(ver, w, am, self._wepoch, batchable)
         self._wtable = None
         return am
 
@@ -476,24 +520,24 @@ class HipBackend:
         # weights not used since the step before last leave the table (dead models of a test session, frozen heads, ...) -- not while a
         # hipGraph is being recorded (see _refresh_weight_pairs)
         if not torch.cuda.is_current_stream_capturing():
-            for k in [k for k, e in self._wamax.items() if e[3] < self._wepoch - 1]:
+            for k in [k for k, e in self._wamax.items() if e.epoch < self._wepoch - 1]:
                 del self._wamax[k]
                 self._wtable = None
-        live = [e for e in self._wamax.values() if e[4]]
+        live = [e for e in self._wamax.values() if e.batchable]
         if not live:
             return
         if self._wtable is None:
             dt = np.dtype([("x", "<u8"), ("R", "<i4"), ("C", "<i4"), ("ld", "<i4"), ("pad", "<i4"), ("row", "<u8"), ("col", "<u8")])
             tab = np.zeros(len(live), dtype=dt)
             for i, e in enumerate(live):
-                w, am = e[1], e[2]
+                w, am = e.w, e.amax
                 tab[i] = (w.data_ptr(), w.shape[0], w.shape[1], w.stride(0), 0, am.row.data_ptr(), am.col.data_ptr())
-            self._wtable = (torch.from_numpy(tab.view(np.uint8).copy()).to(live[0][1].device), len(live))
-        tab, n = self._wtable
-        self._timed("amax", 0.0, 4.0 * sum(e[1].numel() for e in live),
-                    lambda: _chk(self.lib.grappa_amax_f32_batched(self._stream(), n, tab.data_ptr()), "grappa_amax_f32_batched"))
+            self._wtable = _AmaxTable(torch.from_numpy(tab.view(np.uint8).copy()).to(live[0].w.device), len(live))
+        t = self._wtable
+        self._timed("amax", 0.0, 4.0 * sum(e.w.numel() for e in live),
+                    lambda: _chk(self.lib.grappa_amax_f32_batched(self._stream(), t.n, t.tab.data_ptr()), "grappa_amax_f32_batched"))
         for e in live:
-            e[0] = (e[1]._version, self._wepoch)
+            e.ver = (e.w._version, self._wepoch)
 
     # ------------------------------------------------------------------ in-process kernel timing (bench.py roofline)
     def start_profile(self) -> None:
@@ -531,12 +575,8 @@ class HipBackend:
         self._prof.append((name, float(flops), float(nbytes), e0, e1, detail() if callable(detail) else detail))
 
     @staticmethod
-    def _gemm_detail(d) -> dict:
-        """profiling only: what a product launch was (shape, layout, operand formats, epilogue) -- read back from its descriptor"""
-        lay = getattr(d, "_layout", None) or ("fwd" if d.a_kcontig and d.b_kcontig else ("dgrad" if d.a_kcontig else "wgrad"))
-        fmt = ("pairs" if d.a_planes and d.b_planes and d.precision == _lib.GEMM_PRECISIONS["f32_f16x3"] else
-               "wpairs" if d.b_planes and not d.a_planes and d.precision == _lib.GEMM_PRECISIONS["f32_f16x3"] else
-               "planes" if d.a_planes or d.b_planes else "f32")
+    def _gemm_detail(d, lay, fmt) -> dict:
+        """profiling only: what a product launch was -- shape, the layout and operand formats of its route, the epilogue its descriptor asks for"""
         epi = "".join(c for c, on in (("b", d.bias), ("e", d.act), ("x", d.aux or d.auxp), ("d", d.drop_p > 0), ("r", d.res or d.resp), ("2", d.C2 or d.C1p),
                                       ("p", d.pre), ("+", d.accumulate), ("m", d.out_amax or d.out_amax_parts), ("c", d.a_colsum)) if on)
         return {"M": d.M, "N": d.N, "K": d.K, "layout": lay, "fmt": fmt, "epi": epi or "-"}
@@ -547,8 +587,8 @@ class HipBackend:
         # Stream object through three Python layers (3 - 4 us, twice per launch: 8 ms of host time per C2 train step, 1.2 ms per predict)
         return _raw_stream(torch._C._cuda_getDevice())
 
-    def _workspace(self, nbytes: int, dev) -> torch.Tensor:
-        key = (dev, self._stream())
+    def _workspace(self, nbytes: int, dev, *tag) -> torch.Tensor:
+        key = (dev, self._stream(), *tag)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=dev)
@@ -580,6 +620,51 @@ class HipBackend:
         """a bf16 operand the LDS-DMA kernels can read: 16-byte aligned base, rows a multiple of 16 bytes apart"""
         return t.data_ptr() % 16 == 0 and ld % 8 == 0
 
+    def _pairs_readable(self, a_pairs, b, M, N, K, a_kcontig, precision, a_colsum) -> bool:
+        """first question of the route: can this product read A from the pairs its producer wrote (forward / input-gradient layout,
+        default arithmetic)?  Asked before the shapes are checked, because `a` itself may then be None"""
+        return (a_kcontig and M > 32 and N > 32 and K % 32 == 0 and precision is None and self.gemm_precision_bwd is None
+                and self.gemm_precision_name == "f32_f16x3" and b.dtype == torch.float32 and a_colsum is None and tuple(a_pairs.shape) == (M, 2 * K))
+
+    def _route(self, a, b, M, N, K, a_kcontig, b_kcontig, a_pairs, a_colsum, precision) -> _Route:
+        """which kernel family a product takes, from its layout, shapes, element types, alignment, `precision=` and the backend's switches
+        (a_pairs: A's pairs where _pairs_readable said yes).  Launches nothing and writes no descriptor field."""
+        layout = "fwd" if a_kcontig and b_kcontig else ("dgrad" if a_kcontig else "wgrad")
+        if precision is not None:
+            prec = _lib.GEMM_PRECISIONS[precision]
+        elif layout == "fwd" or self.gemm_precision_bwd is None:
+            prec = self.gemm_precision
+        else:
+            prec = self.gemm_precision_bwd      # dgrad (B row-contiguous) and wgrad (both row-contiguous) products: backward pass only
+        bf16 = torch.bfloat16
+        big = M > 32 and N > 32
+        if a_pairs is not None:
+            return _Route("pairs", layout, big, False, False, prec)
+        if not a_kcontig:
+            if b_kcontig:
+                raise ValueError("gemm: layout a_kcontig=0, b_kcontig=1 is never needed by the path")
+            if a.dtype == bf16 and b.dtype == bf16 and big and self._dma_ok(a, a.stride(0)) and self._dma_ok(b, b.stride(0)):
+                return _Route("wgrad_planes", layout, big, False, False, _P_BF16)
+            return _Route("split" if big and prec != _P_F32 else "native", layout, big, a.dtype != torch.float32, b.dtype != torch.float32, prec)
+        # forward / dgrad: B is a weight matrix (fp32 parameter)
+        if b.dtype != torch.float32:
+            raise ValueError("gemm: the weight operand must be float32")
+        a_f32 = False
+        if a.dtype == bf16:
+            if big and K % 32 == 0 and self._dma_ok(a, a.stride(0)) and a_colsum is None:
+                return _Route("bf16_planes", layout, big, False, False, _P_BF16)
+            a_f32 = True
+        # the routes that read the weight from a cached form and A's rows by 16-byte loads (an fp32 copy is contiguous and aligned by its allocation)
+        if ((self.weight_planes or M >= self.weight_pairs_min_rows) and big and K % 32 == 0 and a_colsum is None and b.requires_grad
+                and (a_f32 or (a.data_ptr() % 16 == 0 and a.stride(0) % 4 == 0))):
+            if self.weight_planes and prec not in (_P_F32, _P_F16X3):
+                return _Route("weight_planes", layout, big, a_f32, False, prec)
+            if (M >= self.weight_pairs_min_rows and prec == _P_F16X3 and precision is None and self.gemm_precision_bwd is None
+                    and (a_f32 or (a.dtype == torch.float32 and a.stride(1) == 1))
+                    and M * (K if a_f32 else a.stride(0)) * 4 < 2 ** 32):      # (the LDS-DMA kernels address an operand through 32-bit offsets)
+                return _Route("wpairs", layout, big, a_f32, False, prec)
+        return _Route("split" if big and prec != _P_F32 else "native", layout, big, a_f32, False, prec)
+
     def gemm(self, a, b, out, *, M, N, K, a_kcontig=True, b_kcontig=True, bias=None, res=None, aux=None, pre=None, act=0,
              drop_p=0.0, drop_seed=0, accumulate=False, out2=None, a_colsum=None, precision=None, a_scales=None, b_scales=None, out_amax=False,
              res_ln=None, _defer=False):
@@ -587,123 +672,137 @@ class HipBackend:
         configuration -- bfloat16: a bf16 A (and, for the wgrad layout, B) is read by the LDS-DMA plane kernels as a one-plane
         operand when the shape allows it, otherwise converted to fp32 first; out / out2 / res / aux are written / read in their own
         element type by the shared epilogue.
-        Precision "f32_f16x3": returns the `Amax` record of A (given as a_scales, completed as needed; in the forward layout with a
-        completed as needed); otherwise None.  out_amax=True: the kernel also writes the row maxima of the final output and the
-        return value becomes (record of A, record of the output) -- for an output that is the A operand of the next product."""
+        Precision "f32_f16x3": returns the `Amax` record of A (given as a_scales, completed as needed); otherwise None.  out_amax=True: the
+        kernel also writes the row maxima of the final output and the return value becomes (record of A, record of the output) -- for an
+        output that is the A operand of the next product.
+        Reads as: validate -> route (_route) -> bind (_bind_operands, _bind_epilogue, _bind_scales) -> workspace -> launch or return pending."""
         dev = out.device
-        d = _lib.GemmDesc()
-        d.M, d.N, d.K = M, N, K
-        d._layout = "fwd" if a_kcontig and b_kcontig else ("dgrad" if a_kcontig else "wgrad")      # (profiling only: pair operands turn every layout into k-contiguous rows)
-        ar, ac = (M, K) if a_kcontig else (K, M)
-        br, bc = (N, K) if b_kcontig else (K, N)
-        # A in the pair format (its producer wrote it: a_scales.pairs): forward layout, default arithmetic; `a` itself may then be None
+        # ---- validate.  A in the pair format (its producer wrote it: a_scales.pairs): `a` itself may then be None
         a_pairs = getattr(a_scales, "pairs", None) if a_scales is not None else None
-        if a_pairs is not None and not (a_kcontig and M > 32 and N > 32 and K % 32 == 0 and precision is None and self.gemm_precision_bwd is None
-                                        and self.gemm_precision_name == "f32_f16x3" and b.dtype == torch.float32 and a_colsum is None
-                                        and tuple(a_pairs.shape) == (M, 2 * K)):
+        if a_pairs is not None and not self._pairs_readable(a_pairs, b, M, N, K, a_kcontig, precision, a_colsum):
             if a is None:
                 raise ValueError("gemm: A was given in the pair format only, which this product cannot read")
             a_pairs = None
-        if (a_pairs is None and tuple(a.shape) != (ar, ac)) or tuple(b.shape) != (br, bc) or tuple(out.shape) != (M, N):
+        if ((a_pairs is None and tuple(a.shape) != ((M, K) if a_kcontig else (K, M))) or tuple(b.shape) != ((N, K) if b_kcontig else (K, N))
+                or tuple(out.shape) != (M, N)):
             raise ValueError(f"gemm: shapes A{tuple(a.shape)} B{tuple(b.shape)} C{tuple(out.shape)} do not match M={M} N={N} K={K}")
         if M == 0 or N == 0:
             return (None, None) if out_amax else None
         if K == 0:
             raise ValueError("gemm: K == 0")
-        if precision is not None:
-            d.precision = _lib.GEMM_PRECISIONS[precision]
-        elif a_kcontig and b_kcontig or self.gemm_precision_bwd is None:
-            d.precision = self.gemm_precision
-        else:
-            d.precision = self.gemm_precision_bwd      # dgrad (B row-contiguous) and wgrad (both row-contiguous) products: backward pass only
-        bf16 = torch.bfloat16
-        big = M > 32 and N > 32
-        # ---- operands
-        planes_a = planes_b = None
-        if a_pairs is not None:
-            pass                                     # both operands are set below, from the pairs
-        elif a_kcontig:
-            # forward / dgrad: B is a weight matrix (fp32 parameter)
-            if b.dtype != torch.float32:
-                raise ValueError("gemm: the weight operand must be float32")
-            if a.dtype == bf16:
-                if big and K % 32 == 0 and self._dma_ok(a, a.stride(0)) and a_colsum is None:
-                    planes_a = a                                                     # one plane = the bf16 tensor itself
-                    planes_b = self._planes_of_weight(b, transposed=not b_kcontig)
-                    d.precision = _lib.GEMM_PRECISIONS["bf16"]
-                else:
-                    a = self.to_f32(a)
-            if planes_a is None and (self.weight_planes and b.requires_grad and big and K % 32 == 0 and a_colsum is None
-                                     and d.precision not in (_lib.GEMM_PRECISIONS["f32"], _lib.GEMM_PRECISIONS["f32_f16x3"])
-                                     and a.data_ptr() % 16 == 0 and a.stride(0) % 4 == 0):
-                planes_b = self._planes_of_weight(b, transposed=not b_kcontig)      # fp32 activations x pre-split weight planes
-        else:
-            if b_kcontig:
-                raise ValueError("gemm: layout a_kcontig=0, b_kcontig=1 is never needed by the path")
-            if a.dtype == bf16 and b.dtype == bf16 and big and self._dma_ok(a, a.stride(0)) and self._dma_ok(b, b.stride(0)):
-                planes_a, planes_b = a, b                                            # wgrad: both operands are bf16 activations
-                d.precision = _lib.GEMM_PRECISIONS["bf16"]
+        # ---- route
+        rt = self._route(a, b, M, N, K, a_kcontig, b_kcontig, a_pairs, a_colsum, precision)
+        if rt.a_f32:
+            a = self.to_f32(a)
+        if rt.b_f32:
+            b = self.to_f32(b)
+        if rt.name == "native" and any(t is not None and t.dtype == torch.bfloat16 for t in (out, out2, res, aux)):
+            return self._gemm_on_f32_copies(a, b, out, out_amax, dict(
+                M=M, N=N, K=K, a_kcontig=a_kcontig, b_kcontig=b_kcontig, bias=bias, res=res, aux=aux, pre=pre, act=act, drop_p=drop_p, drop_seed=drop_seed,
+                accumulate=accumulate, out2=out2, a_colsum=a_colsum, precision=precision))
+        # ---- bind
+        d = _lib.GemmDesc()
+        d.M, d.N, d.K, d.precision = M, N, K, rt.precision
+        sa = self._bind_operands(d, rt, a, b, a_pairs, a_scales, dev)
+        final = self._bind_epilogue(d, rt, out, out2, bias, res, res_ln, aux, pre, a_colsum, accumulate, dev)
+        d.act, d.drop_p, d.drop_seed, d.accumulate = int(act), float(drop_p), int(drop_seed) & (2 ** 64 - 1), int(accumulate)
+        self._call_options(d)
+        if rt.name == "split" and rt.precision == _P_F16X3:
+            sa = self._bind_scales(d, rt, a, b, a_scales, b_scales)
+        so = None
+        if out_amax is True and final.dtype == torch.float32:          # (out_amax == "pair": the caller only wants the pair returned)
+            if self.amax_parts and rt.fp16_split:
+                nseg = (N + 31) // 32
+                so = Amax(parts=torch.empty(nseg * M, dtype=torch.int32, device=dev), nseg=nseg)
+                d.out_amax_parts = so.parts.data_ptr()
             else:
-                a, b = self.to_f32(a), self.to_f32(b)
-        # fp32 A + the weight's pairs ("weight pairs": the library splits A's fragments in registers)
-        w_only = (a_pairs is None and planes_a is None and planes_b is None and a_kcontig and big and M >= self.weight_pairs_min_rows
-                  and d.precision == _lib.GEMM_PRECISIONS["f32_f16x3"] and precision is None and self.gemm_precision_bwd is None and K % 32 == 0
-                  and a.dtype == torch.float32 and b.dtype == torch.float32 and b.requires_grad and a_colsum is None
-                  and a.data_ptr() % 16 == 0 and a.stride(0) % 4 == 0 and a.stride(1) == 1
-                  and M * a.stride(0) * 4 < 2 ** 32)      # (the LDS-DMA kernels address an operand through 32-bit offsets)
-        if a_pairs is not None:
-            # forward: B = the pairs of W (rows = out features); input gradient (b_kcontig False): B = the pairs of W^T (rows = in features)
-            w_pairs = self._pairs_of_weight(b, transposed=not b_kcontig)
-            wm = self._amax_of_weight(b)
-            d.A, d.lda, d.a_planes = a_pairs.data_ptr(), a_pairs.stride(0), 1
-            d.B, d.ldb, d.b_planes = w_pairs.data_ptr(), w_pairs.stride(0), 1
-            d.a_kcontig, d.b_kcontig = 1, 1
-            d.a_amax, d.b_amax = a_scales.row.data_ptr(), (wm.row if b_kcontig else wm.col).data_ptr()
-        elif w_only:
-            w_pairs = self._pairs_of_weight(b, transposed=not b_kcontig)
-            wm = self._amax_of_weight(b)
-            if a_scales is not None and a_scales.row is None and a_scales.parts is not None and a_scales.parts.numel() == a_scales.nseg * M:
-                sa_w, am_w = a_scales, a_scales.parts          # the producer's per-segment partials: the kernel combines them (a_amax_nseg)
-                d.a_amax_nseg = a_scales.nseg
-            else:
-                sa_w = self.amax(a, a_scales, rows=True)
-                am_w = sa_w.row
-                if am_w.numel() != M:
-                    raise ValueError("gemm: operand maxima do not match the operands")
-            d.A, d.lda = a.data_ptr(), _f32_2d(a, "A", dev)
-            d.B, d.ldb, d.b_planes = w_pairs.data_ptr(), w_pairs.stride(0), 1
-            d.a_kcontig, d.b_kcontig = 1, 1
-            d.a_amax, d.b_amax = am_w.data_ptr(), (wm.row if b_kcontig else wm.col).data_ptr()
-        elif planes_a is not None:
-            d.A, d.lda, d.a_planes, d.a_plane_stride = planes_a.data_ptr(), planes_a.stride(0), 1, 0
-            _f32_2d(planes_a, "A", dev, bf16)
+                so = Amax(row=torch.empty(M, dtype=torch.int32, device=dev))
+                d.out_amax = so.row.data_ptr()
+        # ---- workspace
+        need = self._ws_bytes(d, (M, N, K))
+        ws = self._workspace(need, dev) if need else None
+        el = lambda t: 0 if t is None else t.element_size()      # noqa: E731
+        # algorithmic bytes of the fused call: both operands once, the result, and what the epilogue has to read / write beside it
+        # (residual, saved activation for ELU', fp32 addend, the second output, an accumulated result's old value)
+        nbytes = float(M * K * (2 if rt.name in ("bf16_planes", "wgrad_planes") else 4) + N * K * (2 if rt.name.endswith("planes") else 4) + M * N * el(final)
+                       + M * N * (el(res) + el(aux) + el(pre) + (el(out) if out2 is not None else 0) + (el(final) if accumulate else 0)))
+        # ---- launch, or return pending
+        ret = (sa, so) if out_amax else sa
+        if _defer:                               # gemm_group: the caller launches this product together with others
+            return _PendingGemm(d, rt, (M, N, K), 2.0 * M * N * K, nbytes, ret, dev, (a, b, out, out2, res, aux, pre, bias, a_pairs, sa, so, res_ln),
+                                groupable=rt.fp16_split and a_kcontig and final.dtype == torch.float32)
+        if self._prof is None:
+            self._launch_gemm(d, ws, dev, (M, N, K))
         else:
+            self._timed("gemm_f32", 2.0 * M * N * K, nbytes, lambda: self._launch_gemm(d, ws, dev, (M, N, K)), lambda: [self._gemm_detail(d, rt.layout, rt.fmt)])
+        return ret
+
+    def _gemm_on_f32_copies(self, a, b, out, out_amax, kw):
+        """the native fp32 kernel (precision "f32", or M / N <= 32) has no bf16 epilogue: run it on fp32 copies (tiny or non-default)"""
+        dev, bf16, M, N = out.device, torch.bfloat16, kw["M"], kw["N"]
+        _f32_2d(a, "A", dev), _f32_2d(b, "B", dev)
+        f = lambda t: None if t is None else (self.to_f32(t) if t.dtype == bf16 else t)      # noqa: E731
+        out2 = kw["out2"]
+        o32 = torch.empty((M, N), dtype=torch.float32, device=dev) if out.dtype == bf16 else out
+        o232 = None if out2 is None else (torch.empty((M, N), dtype=torch.float32, device=dev) if out2.dtype == bf16 else out2)
+        self.gemm(a, b, o32, **dict(kw, res=f(kw["res"]), aux=f(kw["aux"]), out2=o232))
+        for dst, src in ((out, o32), (out2, o232)):
+            if dst is not None and dst is not src:
+                _chk(self.lib.grappa_convert_f32_to_bf16(self._stream(), M, N, src.data_ptr(), N, dst.data_ptr(), _f32_2d(dst, "out", dev, bf16)),
+                     "grappa_convert_f32_to_bf16")
+        return (None, None) if out_amax else None
+
+    def _row_maxima(self, d, a, a_scales):
+        """the maxima of A's rows for a product that reduces along them -> (record, array for a_amax): the producer's per-segment partials
+        where they fit (the kernel combines them: a_amax_nseg), else one array -- given, combined from partials or made by a pass over A"""
+        if a_scales is not None and a_scales.row is None and a_scales.parts is not None and a_scales.parts.numel() == a_scales.nseg * d.M:
+            d.a_amax_nseg = a_scales.nseg
+            return a_scales, a_scales.parts
+        sa = self.amax(a, a_scales, rows=True)
+        if sa.row.numel() != d.M:
+            raise ValueError("gemm: operand maxima do not match the operands")
+        return sa, sa.row
+
+    def _bind_operands(self, d, rt, a, b, a_pairs, a_scales, dev):
+        """A and B in the formats of the route, with the cached forms of the weight it reads -> the `Amax` record of A where the scales come with
+        the operand format (pairs, wpairs), else None"""
+        fwd = rt.layout == "fwd"
+        if rt.name in ("split", "native"):
             d.A, d.lda = a.data_ptr(), _f32_2d(a, "A", dev)
-        if a_pairs is not None or w_only:
-            pass
-        elif planes_b is not None and planes_b.dim() == 3:                           # weight planes (3, rows_pad, cols_pad)
-            d.B, d.ldb, d.b_planes, d.b_plane_stride = planes_b.data_ptr(), planes_b.stride(1), 1, planes_b.stride(0)
-            d.a_kcontig, d.b_kcontig = 1, 1
-        elif planes_b is not None:
-            d.B, d.ldb, d.b_planes, d.b_plane_stride = planes_b.data_ptr(), planes_b.stride(0), 1, 0
-            d.a_kcontig, d.b_kcontig = 0, 0
-        else:
             d.B, d.ldb = b.data_ptr(), _f32_2d(b, "B", dev)
-            d.a_kcontig, d.b_kcontig = int(a_kcontig), int(b_kcontig)
-        # ---- the native fp32 kernel (precision "f32", or M / N <= 32) has no bf16 epilogue: run it on fp32 copies (tiny or non-default)
-        native = planes_a is None and a_pairs is None and not w_only and (not big or d.precision == _lib.GEMM_PRECISIONS["f32"])
-        if native and any(t is not None and t.dtype == bf16 for t in (out, out2, res, aux)):
-            f = lambda t: None if t is None else (self.to_f32(t) if t.dtype == bf16 else t)      # noqa: E731
-            o32 = torch.empty((M, N), dtype=torch.float32, device=dev) if out.dtype == bf16 else out
-            o232 = None if out2 is None else (torch.empty((M, N), dtype=torch.float32, device=dev) if out2.dtype == bf16 else out2)
-            self.gemm(a, b, o32, M=M, N=N, K=K, a_kcontig=a_kcontig, b_kcontig=b_kcontig, bias=bias, res=f(res), aux=f(aux), pre=pre, act=act,
-                      drop_p=drop_p, drop_seed=drop_seed, accumulate=accumulate, out2=o232, a_colsum=a_colsum, precision=precision)
-            for dst, src in ((out, o32), (out2, o232)):
-                if dst is not None and dst is not src:
-                    _chk(self.lib.grappa_convert_f32_to_bf16(self._stream(), M, N, src.data_ptr(), N, dst.data_ptr(), _f32_2d(dst, "out", dev, bf16)),
-                         "grappa_convert_f32_to_bf16")
-            return (None, None) if out_amax else None
-        # ---- outputs and epilogue tensors, each in its own element type
+            d.a_kcontig, d.b_kcontig = int(rt.layout != "wgrad"), int(fwd)
+            return None
+        if rt.name in ("pairs", "wpairs"):
+            # forward: B = the pairs of W (rows = out features); input gradient: B = the pairs of W^T (rows = in features)
+            w_pairs = self._pairs_of_weight(b, transposed=not fwd)
+            wm = self._amax_of_weight(b)
+            if rt.name == "pairs":
+                sa, am = a_scales, a_scales.row
+                d.A, d.lda, d.a_planes = a_pairs.data_ptr(), a_pairs.stride(0), 1
+            else:
+                sa, am = self._row_maxima(d, a, a_scales)
+                d.A, d.lda = a.data_ptr(), _f32_2d(a, "A", dev)
+            d.B, d.ldb, d.b_planes = w_pairs.data_ptr(), w_pairs.stride(0), 1
+            d.a_kcontig, d.b_kcontig = 1, 1
+            d.a_amax, d.b_amax = am.data_ptr(), (wm.row if fwd else wm.col).data_ptr()
+            return sa
+        if rt.name == "wgrad_planes":
+            d.B, d.ldb, d.b_planes, d.b_plane_stride = b.data_ptr(), b.stride(0), 1, 0
+        else:                                                                        # the weight's planes (3, rows_pad, cols_pad)
+            planes = self._planes_of_weight(b, transposed=not fwd)
+            d.B, d.ldb, d.b_planes, d.b_plane_stride = planes.data_ptr(), planes.stride(1), 1, planes.stride(0)
+            d.a_kcontig, d.b_kcontig = 1, 1
+        if rt.name == "weight_planes":
+            d.A, d.lda = a.data_ptr(), _f32_2d(a, "A", dev)
+        else:
+            d.A, d.lda, d.a_planes, d.a_plane_stride = a.data_ptr(), a.stride(0), 1, 0      # one plane = the bf16 tensor itself
+            _f32_2d(a, "A", dev, torch.bfloat16)
+        return None
+
+    def _bind_epilogue(self, d, rt, out, out2, bias, res, res_ln, aux, pre, a_colsum, accumulate, dev):
+        """outputs and epilogue tensors, each in its own element type -> the tensor that holds the final value"""
+        bf16, (M, N) = torch.bfloat16, out.shape
+
         def plane_ok(t, name):
             ld = _f32_2d(t, name, dev, bf16)
             if t.data_ptr() % 8 or ld % 4:
@@ -741,7 +840,7 @@ class HipBackend:
         if res_ln is not None:
             # res holds the rows BEFORE a LayerNorm; the epilogue adds LayerNorm(res) = what the LayerNorm kernel would have written
             mean_, rstd_, gamma_, beta_ = res_ln
-            if res is None or res.dtype != torch.float32 or not big or d.precision == _lib.GEMM_PRECISIONS["f32"]:
+            if res is None or res.dtype != torch.float32 or not rt.big or rt.precision == _P_F32:
                 raise ValueError("gemm: res_ln needs a float32 residual and a product of the split kernels (M, N > 32, not the native fp32 MFMA)")
             for t_, n_, k_ in ((mean_, "mean", M), (rstd_, "rstd", M), (gamma_, "gamma", N), (beta_, "beta", N)):
                 _flat(t_, f"res_ln {n_}", dev)
@@ -761,69 +860,38 @@ class HipBackend:
             d.pre, d.ldpre = pre.data_ptr(), _f32_2d(pre, "pre", dev)
         if a_colsum is not None:
             _flat(a_colsum, "a_colsum", dev)
-            if a_kcontig or a_colsum.numel() != M:
+            if rt.layout != "wgrad" or a_colsum.numel() != M:
                 raise ValueError("gemm: a_colsum needs the row-contiguous A layout and length M")
             d.a_colsum = a_colsum.data_ptr()
-        d.act, d.drop_p, d.drop_seed, d.accumulate = int(act), float(drop_p), int(drop_seed) & (2 ** 64 - 1), int(accumulate)
-        self._call_options(d)
-        sa = so = None
-        if a_pairs is not None:
-            sa = a_scales
-        elif w_only:
-            sa = sa_w
-        elif d.precision == _lib.GEMM_PRECISIONS["f32_f16x3"] and big and planes_a is None and planes_b is None:
-            # power-of-two scales of both operands from their largest magnitudes along the reduced dimension
-            if a_kcontig:
-                wm = self._amax_of_weight(b)
-                bm = wm.row if b_kcontig else wm.col
-                if a_scales is not None and a_scales.row is None and a_scales.parts is not None and a_scales.parts.numel() == a_scales.nseg * M:
-                    sa, am = a_scales, a_scales.parts              # the producer's partials: this product combines them (a_amax_nseg)
-                    d.a_amax_nseg = a_scales.nseg
-                else:
-                    sa = self.amax(a, a_scales, rows=True)
-                    am = sa.row
-                    if am.numel() != M:
-                        raise ValueError("gemm: operand maxima do not match the operands")
-                if bm.numel() != N:
-                    raise ValueError("gemm: operand maxima do not match the operands")
-            elif self.wgrad_column_maxima:
-                sa = self.amax(a, a_scales, cols=True)
-                am, bm = sa.col, self.amax(b, b_scales, cols=True).col
-            else:
-                # weight gradient: the reduction runs over the rows (tokens) of both operands -> one scale per operand
-                sa = self.amax(a, a_scales, tmax=True)
-                am, bm = sa.tmax, self.amax(b, b_scales, tmax=True).tmax
-                d.amax_bcast = 3
-            d.a_amax, d.b_amax = am.data_ptr(), bm.data_ptr()
-        if out_amax is True and final.dtype == torch.float32:          # (out_amax == "pair": the caller only wants the pair returned)
-            if self.amax_parts and big and not native and planes_a is None and (planes_b is None or a_pairs is not None):
-                nseg = (N + 31) // 32
-                so = Amax(parts=torch.empty(nseg * M, dtype=torch.int32, device=dev), nseg=nseg)
-                d.out_amax_parts = so.parts.data_ptr()
-            else:
-                so = Amax(row=torch.empty(M, dtype=torch.int32, device=dev))
-                d.out_amax = so.row.data_ptr()
-        need = self._ws_bytes(d, (M, N, K))
-        ws = self._workspace(need, dev) if need else None
-        el = lambda t: 0 if t is None else t.element_size()      # noqa: E731
-        # algorithmic bytes of the fused call: both operands once, the result, and what the epilogue has to read / write beside it
-        # (residual, saved activation for ELU', fp32 addend, the second output, an accumulated result's old value)
-        epi = M * N * (el(res) + el(aux) + el(pre) + (el(out) if out2 is not None else 0) + (el(final) if accumulate else 0))
-        nbytes = float(M * K * (4 if a_pairs is not None else el(a if planes_a is None else planes_a)) + N * K * (2 if planes_b is not None else 4)
-                       + M * N * el(final) + epi)
-        ret = (sa, so) if out_amax else sa
-        if _defer:                               # gemm_group: the caller launches this product together with others
-            return _PendingGemm(d, (M, N, K), 2.0 * M * N * K, nbytes, ret, dev, (a, b, out, out2, res, aux, pre, bias, a_pairs, sa, so, res_ln),
-                                groupable=big and a_kcontig and a_colsum is None and planes_a is None and (planes_b is None or a_pairs is not None)
-                                and not native and final.dtype == torch.float32)
-        self._timed("gemm_f32", 2.0 * M * N * K, nbytes, lambda: self._launch_gemm(d, ws, dev, (M, N, K)), lambda: [self._gemm_detail(d)])
-        return ret
+        return final
 
-    def _call_options(self, d) -> None:
-        """the per-call options of a product (C ABI 10: they used to be process-wide setters of the library)"""
-        d.drop_salt = self._salt_ptr
+    def _bind_scales(self, d, rt, a, b, a_scales, b_scales):
+        """the fp16-split product of fp32 operands: power-of-two scales of both from their largest magnitudes along the reduced dimension
+        -> the `Amax` record of A"""
+        if rt.layout != "wgrad":
+            wm = self._amax_of_weight(b)
+            bm = wm.row if rt.layout == "fwd" else wm.col
+            sa, am = self._row_maxima(d, a, a_scales)
+            if bm.numel() != d.N:
+                raise ValueError("gemm: operand maxima do not match the operands")
+        elif self.wgrad_column_maxima:
+            sa = self.amax(a, a_scales, cols=True)
+            am, bm = sa.col, self.amax(b, b_scales, cols=True).col
+        else:
+            # weight gradient: the reduction runs over the rows (tokens) of both operands -> one scale per operand
+            sa = self.amax(a, a_scales, tmax=True)
+            am, bm = sa.tmax, self.amax(b, b_scales, tmax=True).tmax
+            d.amax_bcast = 3
+        d.a_amax, d.b_amax = am.data_ptr(), bm.data_ptr()
+        return sa
+
+    def _call_options(self, d, plan=True) -> None:
+        """the per-call options of a product (C ABI 10: they used to be process-wide setters of the library); plan=False: the grouped
+        weight-gradient launch, which deliberately sends no plan fields"""
+        d.drop_salt, d.splitk_reduce = self._salt_ptr, self.splitk_reduce
+        if not plan:
+            return
         d.plan_tail = 0 if self._tails is None else (1 if self._tails else 2)
-        d.splitk_reduce = self.splitk_reduce
         if self.plan_override is not None:
             cfg, ns, tail = self.plan_override
             d.plan_cfg, d.plan_nsplit = (cfg + 1 if cfg >= 0 else 0), max(int(ns), 0)
@@ -863,7 +931,7 @@ class HipBackend:
             for q in grp:
                 need = self._ws_bytes(q.d, q.shape)
                 ws = self._workspace(need, q.dev) if need else None
-                self._timed("gemm_f32", q.flops, q.nbytes, lambda q=q, ws=ws: self._launch_gemm(q.d, ws, q.dev, q.shape), lambda q=q: [self._gemm_detail(q.d)])
+                self._timed("gemm_f32", q.flops, q.nbytes, lambda q=q, ws=ws: self._launch_gemm(q.d, ws, q.dev, q.shape), lambda q=q: [self._gemm_detail(q.d, q.route.layout, q.route.fmt)])
         return out
 
     def _launch_gemm_group(self, grp) -> bool:
@@ -877,7 +945,7 @@ class HipBackend:
 
         def launch():
             rc[0] = self.lib.grappa_gemm_f32_group(self._stream(), arr, n, _ptr(ws), ws.numel() if ws is not None else 0)
-        self._timed("gemm_f32", sum(q.flops for q in grp), sum(q.nbytes for q in grp), launch, lambda: [self._gemm_detail(q.d) for q in grp])
+        self._timed("gemm_f32", sum(q.flops for q in grp), sum(q.nbytes for q in grp), launch, lambda: [self._gemm_detail(q.d, q.route.layout, q.route.fmt) for q in grp])
         if rc[0] == -1:                          # GRAPPA_ERR_ARG: a combination the grouped entry does not take (nothing was launched)
             if self._prof:
                 self._prof.pop()
@@ -941,8 +1009,8 @@ class HipBackend:
         # one queue per backward pass and HIP stream (the writer heads run their backward passes on streams of their own): a full queue is
         # launched on the stream that filled it, what is left when the pass ends is launched together by flush_wgrads
         st = torch.cuda.current_stream()
-        q = self._wq.setdefault((task, st.cuda_stream), (st, []))[1]
-        q.append((dz if pz is None else None, x if px is None else None, dw, db, am, pz, px))
+        _, q = self._wq.setdefault((task, st.cuda_stream), (st, []))
+        q.append(_WgradItem(dz if pz is None else None, x if px is None else None, dw, db, am, pz, px))
         if task < 0:                              # not inside a backward pass: nothing will call back
             self.flush_wgrads(-1)
             return sdz
@@ -955,7 +1023,7 @@ class HipBackend:
 
     @staticmethod
     def _item_bytes(it) -> int:
-        return sum(t.numel() * t.element_size() for t in (it[0], it[1], it[5], it[6]) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (it.dz, it.x, it.pz, it.px) if t is not None)
 
     @property
     def _wq_task(self):
@@ -1015,7 +1083,7 @@ class HipBackend:
             return
         cur = torch.cuda.current_stream()
         task = torch._C._current_graph_task_id()
-        keys = [k for k in self._wq if k[0] == task and (all_streams or k[1] == cur.cuda_stream)]      # this pass's queues only
+        keys = [(t, h) for t, h in self._wq if t == task and (all_streams or h == cur.cuda_stream)]      # this pass's queues only
         queues = [self._wq.pop(k) for k in keys]
         items = [it for _, q in queues for it in q]
         if not items:
@@ -1047,13 +1115,13 @@ class HipBackend:
             task = torch._C._current_graph_task_id()
             if task < 0:
                 if self._wq or self._lnq or self._tasks:
-                    self._wq = {k: v for k, v in self._wq.items() if k[0] < 0}
-                    self._lnq = [it for it in self._lnq if it[8] < 0]
+                    self._wq = {(t, h): v for (t, h), v in self._wq.items() if t < 0}
+                    self._lnq = [it for it in self._lnq if it.task < 0]
                     self._tasks = set()
                 task = -1
         self._tasks.discard(task)
         cur = torch.cuda.current_stream()
-        keys = [k for k in self._wq if k[0] == task]
+        keys = [(t, h) for t, h in self._wq if t == task]
         if keys:
             items = []
             for k in keys:
@@ -1063,17 +1131,16 @@ class HipBackend:
                 items += q
             for i in range(0, len(items), _lib.GEMM_GROUP_MAX):
                 self._launch_wgrad_group(items[i:i + _lib.GEMM_GROUP_MAX])
-        mine = [it for it in self._lnq if it[8] == task]
+        mine = [it for it in self._lnq if it.task == task]
         if mine:
-            self._lnq = [it for it in self._lnq if it[8] != task]
+            self._lnq = [it for it in self._lnq if it.task != task]
             for it in mine:
-                if it[7] != cur:
-                    cur.wait_stream(it[7])
-            items = [it[:7] for it in mine]
-            arr = (_lib.ColsumItem * len(items))()
-            for d, (ws, nrows, W, pg, pb, _g, _b) in zip(arr, items):
-                d.part, d.nrows, d.n, d.out, d.out2, d.n_first, d.accumulate = ws.data_ptr(), nrows, 2 * W, pg, pb, W, 1
-            _chk(self.lib.grappa_colsum_partials_batched(self._stream(), arr, len(items)), "grappa_colsum_partials_batched")
+                if it.stream != cur:
+                    cur.wait_stream(it.stream)
+            arr = (_lib.ColsumItem * len(mine))()
+            for d, it in zip(arr, mine):
+                d.part, d.nrows, d.n, d.out, d.out2, d.n_first, d.accumulate = it.part.data_ptr(), it.nrows, 2 * it.W, it.dgamma_ptr, it.dbeta_ptr, it.W, 1
+            _chk(self.lib.grappa_colsum_partials_batched(self._stream(), arr, len(mine)), "grappa_colsum_partials_batched")
         self._join_aside()                        # the gradients launched beside the pass are complete for whatever follows on this stream
 
     def _launch_wgrad_group(self, items) -> None:
@@ -1084,46 +1151,49 @@ class HipBackend:
             return t is None or (t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and (t.shape[1] + 3) // 4 * 4 <= t.stride(0))
         groups = {}
         for it in items:
-            groups.setdefault(vec(it[0]) and vec(it[1]), []).append(it)        # (operand formats may mix inside a launch: C ABI 8)
+            groups.setdefault(vec(it.dz) and vec(it.x), []).append(it)        # (operand formats may mix inside a launch: C ABI 8)
         for part in groups.values():
             self._launch_wgrad_items(part)
 
     def _launch_wgrad_items(self, items) -> None:
         n = len(items)
-        dev = items[0][2].device
+        dev = items[0].dw.device
         prec = self.gemm_precision if self.gemm_precision_bwd is None else self.gemm_precision_bwd
         arr = (_lib.GemmDesc * n)()
         flops = nbytes = 0.0
         if not self.wgrad_column_maxima:
-            self._tmax_of([r for it in items if it[4] is not None for r in it[4]], dev)
-        for d, (dz, x, dw, db, am, pz, px) in zip(arr, items):
-            d.M, d.N = dw.shape
-            d.K = (dz if dz is not None else pz).shape[0]
+            self._tmax_of([r for it in items if it.am is not None for r in it.am], dev)
+        for d, it in zip(arr, items):
+            d.M, d.N = it.dw.shape
+            d.K = (it.dz if it.dz is not None else it.pz).shape[0]
             d.a_kcontig, d.b_kcontig = 0, 0
-            if pz is not None:
-                d.A, d.lda, d.a_planes, d.a_rowmax = pz.data_ptr(), pz.stride(0), 1, am[0].row.data_ptr()
+            sz, sx = it.am if it.am is not None else (None, None)
+            if it.pz is not None:
+                d.A, d.lda, d.a_planes, d.a_rowmax = it.pz.data_ptr(), it.pz.stride(0), 1, sz.row.data_ptr()
             else:
-                d.A, d.lda = dz.data_ptr(), dz.stride(0)
-            if px is not None:
-                d.B, d.ldb, d.b_planes, d.b_rowmax = px.data_ptr(), px.stride(0), 1, am[1].row.data_ptr()
+                d.A, d.lda = it.dz.data_ptr(), it.dz.stride(0)
+            if it.px is not None:
+                d.B, d.ldb, d.b_planes, d.b_rowmax = it.px.data_ptr(), it.px.stride(0), 1, sx.row.data_ptr()
             else:
-                d.B, d.ldb = x.data_ptr(), x.stride(0)
-            d.C, d.ldc = dw.data_ptr(), dw.stride(0)
-            d.a_colsum = None if db is None else db.data_ptr()
+                d.B, d.ldb = it.x.data_ptr(), it.x.stride(0)
+            d.C, d.ldc = it.dw.data_ptr(), it.dw.stride(0)
+            d.a_colsum = None if it.db is None else it.db.data_ptr()
             d.accumulate, d.precision = 1, prec
-            d.drop_salt, d.splitk_reduce = self._salt_ptr, self.splitk_reduce
-            if am is not None:
+            self._call_options(d, plan=False)
+            if it.am is not None:
                 if self.wgrad_column_maxima:
-                    d.a_amax, d.b_amax = am[0].col.data_ptr(), am[1].col.data_ptr()
+                    d.a_amax, d.b_amax = sz.col.data_ptr(), sx.col.data_ptr()
                 else:
-                    d.a_amax, d.b_amax, d.amax_bcast = am[0].tmax.data_ptr(), am[1].tmax.data_ptr(), 3
+                    d.a_amax, d.b_amax, d.amax_bcast = sz.tmax.data_ptr(), sx.tmax.data_ptr(), 3
             flops += 2.0 * d.M * d.N * d.K
             nbytes += 4.0 * (d.M * d.K + d.N * d.K + d.M * d.N)
         need = self.lib.grappa_gemm_f32_grouped_workspace_bytes(arr, n)
         ws = self._workspace(need, dev)
+        # (the formats as the single products name them: pair-format dz alone reads as a one-plane A operand)
+        fmt = lambda it: ("pairs" if it.pz is not None else "wpairs") if it.px is not None else ("planes" if it.pz is not None else "f32")      # noqa: E731
         self._timed("gemm_f32", flops, nbytes,
                     lambda: _chk(self.lib.grappa_gemm_f32_grouped(self._stream(), arr, n, ws.data_ptr(), ws.numel()), "grappa_gemm_f32_grouped"),
-                    lambda: [self._gemm_detail(d) for d in arr])
+                    lambda: [self._gemm_detail(d, "wgrad", fmt(it)) for d, it in zip(arr, items)])
 
     def colsum(self, x, out, accumulate=False) -> None:
         dev = out.device
@@ -1223,7 +1293,7 @@ class HipBackend:
         # inside a backward pass the parameter gradients wait: the kernel leaves its per-block partial sums in a buffer of their own and
         # ONE launch reduces those of all LayerNorms when the pass ends (flush_wgrads) instead of two small launches per LayerNorm
         task = self._queue_flush() if (accumulate and self.defer_wgrads and self.defer_ln and M > 0) else -1
-        defer = task >= 0 and all(q[3] != dgamma.data_ptr() for q in self._lnq if q[8] == task)      # (once per pass and parameter)
+        defer = task >= 0 and all(q.dgamma_ptr != dgamma.data_ptr() for q in self._lnq if q.task == task)      # (once per pass and parameter)
         need = self.lib.grappa_layernorm_bwd_workspace_bytes(M, W)
         ws = torch.empty(need, dtype=torch.uint8, device=dev) if defer else self._workspace(need, dev)
         row = self._new_row_amax(dx, True, amax)
@@ -1231,8 +1301,8 @@ class HipBackend:
                 mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), dx.data_ptr(), _f32_2d(dx, "dx", dev, dt),
                 dgamma.data_ptr(), dbeta.data_ptr(), 2 if defer else int(accumulate), ws.data_ptr(), ws.numel())
         if defer:
-            self._lnq.append((ws, self.lib.grappa_layernorm_bwd_partial_rows(M), W, dgamma.data_ptr(), dbeta.data_ptr(), dgamma, dbeta,
-                              torch.cuda.current_stream(), task))
+            self._lnq.append(_LnItem(ws, self.lib.grappa_layernorm_bwd_partial_rows(M), W, dgamma.data_ptr(), dbeta.data_ptr(), dgamma, dbeta,
+                                     torch.cuda.current_stream(), task))
         if drop is not None:
             p, seed = drop
             if not self.drop_fusable(x) or not (0.0 < p < 1.0):
@@ -1292,7 +1362,7 @@ class HipBackend:
         if not self._rows_ok(*[t for it in items for t in (it[0], it[1])]) or any(it[1].shape[0] == 0 for it in items):
             return None
         task = self._queue_flush()
-        if task < 0 or any(q[3] == it[5].data_ptr() for it in items for q in self._lnq if q[8] == task):
+        if task < 0 or any(q.dgamma_ptr == it[5].data_ptr() for it in items for q in self._lnq if q.task == task):
             return None
         if len({it[5].data_ptr() for it in items}) != n:
             return None
@@ -1314,7 +1384,7 @@ class HipBackend:
             row = torch.empty(M, dtype=torch.int32, device=dev) if want else None
             a.M, a.W, a.dy, a.lddy, a.x, a.ldx = M, W, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0)
             a.mean, a.rstd, a.gamma, a.dx, a.lddx, a.part, a.dx_amax = mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), dx.data_ptr(), dx.stride(0), ws.data_ptr(), _ptr(row)
-            self._lnq.append((ws, self.lib.grappa_layernorm_bwd_partial_rows(M), W, dgamma.data_ptr(), dbeta.data_ptr(), dgamma, dbeta, cur, task))
+            self._lnq.append(_LnItem(ws, self.lib.grappa_layernorm_bwd_partial_rows(M), W, dgamma.data_ptr(), dbeta.data_ptr(), dgamma, dbeta, cur, task))
             out.append((dx, Amax(row=row) if want else None))
         _chk(self.lib.grappa_layernorm_bwd_batched_f32(self._stream(), arr, n), "grappa_layernorm_bwd_batched_f32")
         return out
@@ -1501,27 +1571,13 @@ class HipBackend:
 
     # ------------------------------------------------------------------ the fused writer-head layer (C ABI 11)
     def _packed_weight(self, w: torch.Tensor, transposed: bool = False) -> torch.Tensor:
-        """W (out x in features) -- or W^T -- as bf16 in the MFMA fragment order of the fused writer layer (grappa_writer_pack_weight);
-        cached per weight and refreshed when the weight changed, like _planes_of_weight"""
+        """W (out x in features) -- or W^T -- as bf16 in the MFMA fragment order of the fused writer layer (grappa_writer_pack_weight)"""
         R, Cc = w.shape
-        key = (w.data_ptr(), R, Cc, "packT" if transposed else "pack")
-        ver = (w._version, self._wepoch)
-        hit = self._wplanes.get(key)
-        if hit is not None and hit[2]() is not w:
-            hit = None
-        if hit is not None and hit[0] == ver:
-            return hit[1]
         N, K = (Cc, R) if transposed else (R, Cc)
-        if hit is not None:
-            pk = hit[1]
-        else:
-            pk = torch.empty(N * K, dtype=torch.bfloat16, device=w.device)
-            for k in [k for k, e in self._wplanes.items() if e[2]() is None]:
-                del self._wplanes[k]
-        _chk(self.lib.grappa_writer_pack_weight(self._stream(), N, K, w.data_ptr(), _f32_2d(w, "W", w.device), int(transposed), _lib.WRITER_BF16,
-                                                pk.data_ptr()), "grappa_writer_pack_weight")
-        self._wplanes[key] = (ver, pk, weakref.ref(w))
-        return pk
+        return self._cached_form(
+            w, "packT" if transposed else "pack", lambda: torch.empty(N * K, dtype=torch.bfloat16, device=w.device),
+            lambda pk: _chk(self.lib.grappa_writer_pack_weight(self._stream(), N, K, w.data_ptr(), _f32_2d(w, "W", w.device), int(transposed), _lib.WRITER_BF16,
+                                                               pk.data_ptr()), "grappa_writer_pack_weight"))
 
     def writer_layer_ok(self, x: torch.Tensor, s: int, nheads: int, *params) -> bool:
         """can grappa_writer_head_fwd run this transformer layer?  (bf16 storage configuration, 512 features, 8 heads, tuples of 2 - 4 tokens,
@@ -1661,8 +1717,8 @@ class HipBackend:
         dg = _pgrad(gamma) if gamma.requires_grad else torch.zeros_like(gamma)
         db = _pgrad(beta) if beta.requires_grad else torch.zeros_like(beta)
         task = self._queue_flush() if (self.defer_wgrads and self.defer_ln) else -1
-        if task >= 0 and all(q[3] != dg.data_ptr() for q in self._lnq if q[8] == task):
-            self._lnq.append((part, nrows, W, dg.data_ptr(), db.data_ptr(), dg, db, torch.cuda.current_stream(), task))
+        if task >= 0 and all(q.dgamma_ptr != dg.data_ptr() for q in self._lnq if q.task == task):
+            self._lnq.append(_LnItem(part, nrows, W, dg.data_ptr(), db.data_ptr(), dg, db, torch.cuda.current_stream(), task))
             return
         arr = (_lib.ColsumItem * 1)()
         a = arr[0]

@@ -37,9 +37,9 @@ def _pinned_by_graph(be):
 def _touch_weight_caches(be) -> None:
     """the recorded graph uses every cached per-weight entry at every replay: keep them from ageing out of the backend's tables"""
     for e in be._wamax.values():
-        e[3] = be._wepoch
+        e.epoch = be._wepoch
     for e in be._wpairs.values():
-        e[3] = be._wepoch
+        e.epoch = be._wepoch
 
 
 def _drop_outputs(g) -> None:

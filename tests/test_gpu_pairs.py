@@ -341,7 +341,7 @@ def test_training_through_the_pair_format_equals_the_fp32_operand_path(min_rows,
 def test_grouped_weight_gradients_of_mixed_operand_formats_in_one_launch():
     """one grouped launch over products whose operands come as fp32 or as pairs, product by product (C ABI 8, the kernel reads each product's
     own flags): the same results as launching every product alone in its own format"""
-    from grappa_amd.backend import get_backend
+    from grappa_amd.backend import _WgradItem, get_backend
     be = get_backend()
     torch.manual_seed(5)
     T = 3000
@@ -360,7 +360,7 @@ def test_grouped_weight_gradients_of_mixed_operand_formats_in_one_launch():
     items = []
     for (dz, x, rz, rx, pz, px), out in zip(ops_, outs):
         am = (rz if pz else be.amax(dz, None, rows=True), rx if px else be.amax(x, None, rows=True))
-        items.append((None if pz else dz, None if px else x, out, None, am, rz.pairs if pz else None, rx.pairs if px else None))
+        items.append(_WgradItem(None if pz else dz, None if px else x, out, None, am, rz.pairs if pz else None, rx.pairs if px else None))
     be._launch_wgrad_group(items)
     torch.cuda.synchronize()
     for got, w, (dz, x, *_r) in zip(outs, want, ops_):

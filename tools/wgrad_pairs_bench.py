@@ -6,7 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from grappa_amd.backend import get_backend  # noqa: E402
+from grappa_amd.backend import _WgradItem, get_backend  # noqa: E402
 
 
 BIAS = True          # with the bias gradient (column sums of dz) as in the train step
@@ -27,7 +27,7 @@ def main():
         for i, (dz, x, rz, rx, dw, db) in enumerate(ops):
             pz, px = fmt[i]
             am = (rz if pz else be.amax(dz, None, rows=True), rx if px else be.amax(x, None, rows=True))
-            out.append((None if pz else dz, None if px else x, dw, db if BIAS else None, am, rz.pairs if pz else None, rx.pairs if px else None))
+            out.append(_WgradItem(None if pz else dz, None if px else x, dw, db if BIAS else None, am, rz.pairs if pz else None, rx.pairs if px else None))
         return out
 
     def timed(fmt, n=10):
