@@ -114,6 +114,9 @@ class WriterLayerBwdDesc(C.Structure):
 
 WRITER_BF16 = 1
 
+EVAL_NMOM = 10               # GRAPPA_EVAL_NMOM: doubles per moment row (grappa_eval_moments_f32)
+EVAL_METRICS = ("std_energies", "std_gradients", "rmse_energies", "mae_energies", "rmse_gradients", "crmse_gradients", "mae_gradients")     # GRAPPA_EVAL_NMETRICS
+
 COLLATE_MODES = {"copy": 0, "add": 1, "inv_rows": 2, "inc_code": 3, "conf": 4}
 
 VP4 = C.c_void_p * 4
@@ -187,6 +190,9 @@ SIGNATURES = {
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the bootstrapped Evaluator (additions to ABI 11)
+    "grappa_eval_moments_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_eval_bootstrap_f64": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "grappa_collate_batch": (_i, [_vp, _vp, C.POINTER(CollateDesc), _i, _i]),
     "grappa_sumsq_workspace_bytes": (_sz, [_sz]),
     "grappa_sumsq_f32": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _sz]),

@@ -1901,10 +1901,65 @@ class HipBackend:
         _chk(self.lib.grappa_eval_se_f32(self._stream(), _loss_mols(plan), energy.shape[1], plan.N, plan.atom_molptr.data_ptr(), energy.data_ptr(),
                                          energy_ref.data_ptr(), _ptr(is_dummy), _ptr(grad), _ptr(grad_ref), out.data_ptr()), "grappa_eval_se_f32")
 
+    def eval_moments(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, out) -> None:
+        """out (B, EVAL_NMOM) float64 = per molecule the sums every metric of the Evaluator is made of (include/grappa_hip.h
+        grappa_eval_moments_f32); rows of a trailing padding molecule are left as the caller made them"""
+        dev = out.device
+        for t, n in ((energy, "energy"), (energy_ref, "energy_ref"), (is_dummy, "is_dummy"), (grad, "grad"), (grad_ref, "grad_ref")):
+            if t is not None:
+                _flat(t, n, dev)
+        _flat(out, "out", dev, torch.float64)
+        if out.dim() != 2 or out.shape[1] != _lib.EVAL_NMOM or out.shape[0] < _loss_mols(plan):
+            raise ValueError(f"out: expected ({plan.B}, {_lib.EVAL_NMOM}), got {tuple(out.shape)}")
+        _chk(self.lib.grappa_eval_moments_f32(self._stream(), _loss_mols(plan), energy.shape[1], plan.N, plan.atom_molptr.data_ptr(), energy.data_ptr(),
+                                              energy_ref.data_ptr(), _ptr(is_dummy), _ptr(grad), _ptr(grad_ref), out.data_ptr()), "grappa_eval_moments_f32")
+
+    def eval_bootstrap(self, mom, ds_ptr, idx, n_rep: int, rep0: int, rep1: int, rep_metrics, mean, std) -> None:
+        """the replicates rep0 <= r < rep1 of a bootstrap over the moment rows `mom` (M, EVAL_NMOM), grouped by dataset through ds_ptr
+        (n_ds + 1,) int32; idx (rep1 - rep0, M) int32 holds their resamples, local to each dataset; rep_metrics (n_rep, n_ds, 7), and with
+        the last range mean / std (n_ds, 7), all float64 (include/grappa_hip.h grappa_eval_bootstrap_f64).
+        ds_ptr and idx may be HOST tensors: they are then checked here -- an index outside its dataset is GRAPPA_ERR_ARG -- and uploaded.
+        Tensors that already live on the device cannot be looked at without a read-back: the kernel clamps what is out of range."""
+        dev = mom.device
+        _flat(mom, "mom", dev, torch.float64)
+        for t, n in ((rep_metrics, "rep_metrics"), (mean, "mean"), (std, "std")):
+            _flat(t, n, dev, torch.float64)
+        M, n_ds = mom.shape[0], ds_ptr.numel() - 1
+        if mom.dim() != 2 or mom.shape[1] != _lib.EVAL_NMOM:
+            raise ValueError(f"mom: expected (M, {_lib.EVAL_NMOM}), got {tuple(mom.shape)}")
+        if ds_ptr.dtype != torch.int32 or idx.dtype != torch.int32 or not idx.is_contiguous() or not ds_ptr.is_contiguous():
+            raise ValueError("ds_ptr / idx: expected contiguous int32 tensors")
+        nm = _lib.EVAL_METRICS
+        if n_ds >= 1 and n_rep >= 1 and (rep_metrics.numel() != n_rep * n_ds * len(nm) or mean.numel() != n_ds * len(nm) or std.numel() != n_ds * len(nm)):
+            raise ValueError("rep_metrics / mean / std: expected (n_rep, n_ds, 7), (n_ds, 7), (n_ds, 7)")
+        if idx.numel() != max(rep1 - rep0, 0) * M:
+            _chk(-1, "grappa_eval_bootstrap_f64 (idx is not (rep1 - rep0, M))")
+        if ds_ptr.device.type == "cpu":
+            p = ds_ptr.numpy()
+            if n_ds < 1 or p[0] != 0 or p[-1] != M or (p[1:] < p[:-1]).any():
+                _chk(-1, "grappa_eval_bootstrap_f64 (ds_ptr does not partition the rows)")
+            if idx.device.type == "cpu" and idx.numel():
+                a = idx.numpy().reshape(-1, M)
+                for d in range(n_ds):
+                    blk = a[:, p[d]:p[d + 1]]
+                    if blk.size and (blk.min() < 0 or blk.max() >= p[d + 1] - p[d]):
+                        _chk(-1, f"grappa_eval_bootstrap_f64 (an index outside dataset {d})")
+        keep = []
+        if ds_ptr.device != dev:
+            ds_ptr = ds_ptr.to(dev, non_blocking=True)
+            keep.append(ds_ptr)
+        if idx.device != dev:
+            host = idx.pin_memory() if dev.type == "cuda" else idx
+            idx = host.to(dev, non_blocking=True)
+            keep += [host, idx]
+        _chk(self.lib.grappa_eval_bootstrap_f64(self._stream(), mom.data_ptr(), M, n_ds, ds_ptr.data_ptr(), idx.data_ptr(), int(n_rep), int(rep0),
+                                                int(rep1), rep_metrics.data_ptr(), mean.data_ptr(), std.data_ptr()), "grappa_eval_bootstrap_f64")
+        self._keep_eval = keep               # the copies and the kernel read them asynchronously: alive until the next call
+
     def loss_param(self, plan, params, refs, fac, reg, pw, inv_B, loss_mol, gps) -> None:
         """params/refs/gps: lists of 6 tensors-or-None in the order n2_k, n2_eq, n3_k, n3_eq, n4_k, n4_improper_k."""
         dev = loss_mol.device
-        lv = ["n2", "n2", "n3", "n3", "n4", "n4_improper"]
+        lv =["n2", "n2", "n3", "n3", "n4", "n4_improper"]
         d = _lib.PLossDesc()
         d.B = _loss_mols(plan)
         for l in range(6):

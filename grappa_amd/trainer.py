@@ -21,7 +21,7 @@ import torch.distributed as tdist
 from .device_dataset import DeviceDataset, ShapeBuckets
 from .dist import BucketedGradReducer, shard_indices
 from .energy import Energy
-from .evaluation import FastEvaluator
+from .evaluation import Evaluator, FastEvaluator
 from .loss import MolwiseLoss
 from .optim import FlatParams, FusedAdam
 from .schedule import TrainSchedule
@@ -103,6 +103,7 @@ class Trainer:
         self._prep_stream, self._load_done = None, None
         self._unrecordable: Dict[tuple, str] = {}          # shape signatures whose recording failed (reason): served eagerly
         self._val_buckets: Optional[ShapeBuckets] = None
+        self._test_buckets: Dict[tuple, ShapeBuckets] = {}
         self._eval_steps: Dict[tuple, object] = {}
         self.pipelined, self._prep_pool = bool(pipelined), None
         self.recorded_stats = {"replayed": 0, "eager": 0, "graphs_recorded": 0, "padding_rows": 0, "real_rows": 0}
@@ -363,15 +364,20 @@ class Trainer:
         es = self.schedule.on_validation_epoch_end(epoch, metrics)
         return metrics, es
 
-    def _validate_recorded(self, ids: np.ndarray) -> bool:
+    def _validate_recorded(self, ids: np.ndarray, dataset=None, buckets=None, conf_strategy=None, sink=None) -> bool:
         """one validation batch through a recorded forward + energy pass (capture.CapturedEvalStep); False: no bucket takes it or its recording
-        failed -- the caller runs it eagerly"""
+        failed -- the caller runs it eagerly.  `test()` sends its batches through the same recorded passes: its dataset, buckets, conformation
+        strategy and the evaluator step that takes the result (sink(graph, names)) in place of the validation set's"""
         from .capture import CapturedEvalStep, train_signature
-        tot = self.val_set.totals(ids)
-        caps = self._val_buckets.choose(tot)
-        if caps is None or any(caps[k] - tot[k] > self.val_set.pad_caps[k] for k in tot):
+        dataset = self.val_set if dataset is None else dataset
+        buckets = self._val_buckets if buckets is None else buckets
+        conf_strategy = self.val_conf_strategy if conf_strategy is None else conf_strategy
+        sink = self.evaluator.step if sink is None else sink
+        tot = dataset.totals(ids)
+        caps = buckets.choose(tot)
+        if caps is None or any(caps[k] - tot[k] > dataset.pad_caps[k] for k in tot):
             return False
-        g, names = self.val_set.collate(ids, self.val_conf_strategy, pad_to=caps)
+        g, names = dataset.collate(ids, conf_strategy, pad_to=caps)
         key = (train_signature(g), "eval")
         if key in self._unrecordable:
             return False
@@ -390,9 +396,43 @@ class Trainer:
         else:
             step.load(g)
         self._eval_steps[key] = step
-        self.evaluator.step(step(), list(names))
+        sink(step(), list(names))
         self.recorded_stats["eval_replayed"] = self.recorded_stats.get("eval_replayed", 0) + 1
         return True
+
+    @torch.no_grad()
+    def test(self, test_set: DeviceDataset, n_bootstrap: int = 1000, seed: int = 0, batch_size: Optional[int] = None) -> Dict:
+        """the test metrics of the model as it stands (the reference's training/evaluation.py `Evaluator` + eval_model.py): eval mode, no
+        gradients, every conformation of every molecule, -> {dataset: {metric: {'mean', 'std'}, 'n_confs', 'n_mols'}} over `n_bootstrap`
+        resamples (n_bootstrap=0: the plain metrics).  batch_size: molecules per batch (default: the validation batch size).
+        Data parallel: the batches are dealt to the ranks round-robin as in `validate()`, the per-molecule rows all-gathered and put back
+        into the dataset's order, so every rank returns the single-rank result bit for bit.  `recorded=True`: the batches go through the
+        recorded forward + energy passes where `validate()` would use them."""
+        was_training = self.model.training
+        self.model.eval()
+        ev = Evaluator()
+        bs = self.val_batch_size if batch_size is None else int(max(1, batch_size))
+        batches = epoch_batches(test_set.names, bs, shuffle=False)
+        use_graphs = self.recorded and self.world == 1 and torch.cuda.is_available() and test_set.bonds_are_n2
+        buckets = None
+        if use_graphs:
+            key = (id(test_set), bs)
+            buckets = self._test_buckets.get(key)
+            if buckets is None:
+                buckets = self._test_buckets[key] = ShapeBuckets(test_set, batches, n_buckets=self.shape_buckets)
+            test_set.enable_padding(buckets.max_pad)
+        for b, ids in enumerate(batches):
+            if b % self.world != self.rank:
+                continue
+            ids = np.asarray(ids)
+            sink = lambda g, names, ids=ids: ev.step(g, names, order=ids.tolist())      # noqa: E731  (ordinal = position in the dataset)
+            if use_graphs and self._validate_recorded(ids, test_set, buckets, "all", sink):
+                continue
+            g, names = test_set.collate(ids, "all")
+            sink(self.energy(self.model(g)), list(names))
+        metrics = ev.pool(n_bootstrap=n_bootstrap, seed=seed)           # (gathers over the ranks first)
+        self.model.train(was_training)
+        return metrics
 
     def fit(self, max_epochs: int, log=None, checkpoint: Optional[str] = None, checkpoint_every: int = 1) -> List[Dict]:
         """epochs [next_epoch, max_epochs): a fresh trainer starts at 0, one that has loaded a checkpoint where that run stopped.

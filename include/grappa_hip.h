@@ -528,6 +528,41 @@ int grappa_collate_batch(void* stream, const grappa_collate_desc* descs_device, 
 int grappa_eval_se_f32(void* stream, int B, int C, int N, const int* atom_molptr, const float* energy, const float* energy_ref,
                        const float* is_dummy, const float* grad, const float* grad_ref, float* out);
 
+/* The bootstrapped Evaluator (training/evaluation.py:164-386: step :207-261, collect :264-311, pool :314-355, get_metrics :358-386)
+ * on per-molecule moments.  Every metric of get_metrics is a function of a few sums over the molecules of a (resampled) dataset, so a
+ * bootstrap replicate gathers and adds rows instead of torch.cat over thousands of per-molecule tensors.  (Additions to ABI 11.)
+ *
+ * grappa_eval_moments_f32 replaces Evaluator.step's unbatch + per-molecule slicing: same inputs as grappa_eval_se_f32, one workgroup per
+ * molecule, fp32 inputs, every operation from the first subtraction on in double, fixed-order sums without atomics (same input, same
+ * bits).  out[b][GRAPPA_EVAL_NMOM] (16-byte aligned; a row is 80 bytes), over the REAL conformations of molecule b:
+ *   0 n_E       real conformations                         5 n_V        atoms x real conformations (3-vectors)
+ *   1 sum d^2   d = centred prediction - centred reference  6 sum |dg|^2  dg = G - G_ref of one atom and conformation
+ *   2 sum |d|                                              7 sum |dg|
+ *   3 sum r     r = centred reference energy                8 sum g       all components of G_ref
+ *   4 sum r^2                                              9 sum g^2
+ * (energies centred per molecule over its real conformations, utils/graph_utils.py:35-63).  grad == grad_ref == NULL: columns 5..9 are 0. */
+#define GRAPPA_EVAL_NMOM 10
+/* metrics per dataset, in get_metrics' order (:368-377): std_energies (unbiased std of r), std_gradients (unbiased std of all components
+ * of G_ref, x sqrt 3), rmse_energies, mae_energies, rmse_gradients = sqrt(sum |dg|^2 / n_V), crmse_gradients = sqrt(sum |dg|^2 / 3 n_V),
+ * mae_gradients = sum |dg| / n_V.  A zero count gives NaN, as torch's mean / std of an empty tensor.  The two stds come from raw moments
+ * (sum, sum of squares): their relative error is that of a double sum times (1 + mean^2 / variance) -- centred energies have mean 0, and
+ * the components of forces average to zero over a molecule at rest. */
+#define GRAPPA_EVAL_NMETRICS 7
+int grappa_eval_moments_f32(void* stream, int B, int C, int N, const int* atom_molptr, const float* energy, const float* energy_ref,
+                            const float* is_dummy, const float* grad, const float* grad_ref, double* out);
+/* grappa_eval_bootstrap_f64 replaces collect(bootstrap_seed) + get_metrics per replicate and pool's mean / np.std over the replicates
+ * (:320-351).  mom[M][GRAPPA_EVAL_NMOM]: the moment rows grouped by dataset, dataset d = rows ds_ptr[d] .. ds_ptr[d+1]-1 (ds_ptr[n_ds+1],
+ * DEVICE memory).  The call covers the replicates rep0 <= r < rep1 of n_rep; idx[rep1-rep0][M] (int32, DEVICE memory) holds THEIR
+ * resamples: replicate rep0 + i of dataset d sums the rows ds_ptr[d] + idx[i][ds_ptr[d] + j], j < ds_ptr[d+1] - ds_ptr[d], in a fixed
+ * order (one workgroup per (dataset, replicate), no atomics) and writes rep_metrics[rep0 + i][d][GRAPPA_EVAL_NMETRICS].  The call whose
+ * range ends at n_rep adds a second launch: mean[d][..] and std[d][..] (population std, np.std) of every metric over all n_rep
+ * replicates, which earlier calls on the same stream must have written.  At most 65535 replicates per call.
+ * GRAPPA_ERR_ARG: a NULL pointer, M < 1, n_ds < 1, n_rep < 1, an empty or misplaced range.  ds_ptr and idx live in device memory, which
+ * the entry point cannot read: an index outside [0, rows of its dataset) is CLAMPED into the dataset by the kernel, and ds_ptr into
+ * [0, M]; the front end (grappa_amd.backend.HipBackend.eval_bootstrap) refuses host-side index tables that are out of range. */
+int grappa_eval_bootstrap_f64(void* stream, const double* mom, int M, int n_ds, const int* ds_ptr, const int* idx, int n_rep, int rep0,
+                              int rep1, double* rep_metrics, double* mean, double* stdev);
+
 /* ------------------------------------------------------------------------------------------------
  * Optimiser (training/lightning_model.py:297-299 Adam; lightning_trainer.py:92 gradient_clip_val=10):
  * sumsq: out[0] (+)= sum x^2.  adam: p -= lr * mhat/(sqrt(vhat)+eps) with g scaled by
