@@ -77,6 +77,13 @@ class MMDesc(C.Structure):
                 ("atom_molptr", C.c_void_p)]
 
 
+class NbDesc(C.Structure):
+    """grappa_nb_desc (additions to ABI 11): nonbonded energy and gradient"""
+    _fields_ = [("N", C.c_int), ("C", C.c_int), ("B", C.c_int), ("xyz", C.c_void_p), ("atom_molptr", C.c_void_p),
+                ("charge", C.c_void_p), ("sigma", C.c_void_p), ("epsilon", C.c_void_p), ("exc_ptr", C.c_void_p), ("exc_atom", C.c_void_p),
+                ("exc_qq", C.c_void_p), ("exc_sigma", C.c_void_p), ("exc_eps", C.c_void_p)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -187,6 +194,12 @@ SIGNATURES = {
     "grappa_mm_energy_fwd_f32": (_i, [_vp, C.POINTER(MMDesc), _vp, _vp, C.POINTER(VP4), C.POINTER(VP4)]),
     "grappa_mm_gradient_fwd_f32": (_i, [_vp, C.POINTER(MMDesc), _vp]),
     "grappa_mm_bwd_f32": (_i, [_vp, C.POINTER(MMDesc), _vp, _vp, C.POINTER(VP4), C.POINTER(VP4)]),
+    # nonbonded energy and gradient (additions to ABI 11)
+    "grappa_nonbonded_iblock": (_i, []),
+    "grappa_nonbonded_workspace_bytes": (_sz, [_i, _i, _i]),
+    "grappa_nonbonded_fwd_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _vp, _vp, _vp, _sz]),
+    "grappa_nonbonded_plan": (C.c_longlong, [_i, _i, _i, _vp, _vp, C.c_longlong]),
+    "grappa_nonbonded_fwd_planned_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _i, _i, _vp, _vp, _vp, _vp, _sz]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -240,3 +253,8 @@ def load():
         raise RuntimeError("libgrappa_hip.so: ABI version mismatch")
     _lib = lib
     return lib
+
+
+def nonbonded_iblock() -> int:
+    """i-atoms per workgroup of the nonbonded kernel (GRAPPA_NB_IBLOCK of the loaded library): its tests put molecule sizes around it"""
+    return int(load().grappa_nonbonded_iblock())

@@ -1852,6 +1852,73 @@ class HipBackend:
         b = _lib.VP4(*[_ptr(t) for t in geqs])
         _chk(self.lib.grappa_mm_bwd_f32(self._stream(), C.byref(d), _ptr(gE), _ptr(gG), C.byref(a), C.byref(b)), "grappa_mm_bwd_f32")
 
+    # ------------------------------------------------------------------ nonbonded
+    def nonbonded_plan(self, atom_molptr_host, N: int, n_confs: int, device) -> "tuple":
+        """the work-item list of the nonbonded kernel for C = n_confs, built on the host from a HOST atom_molptr (int32, (B+1,)) and
+        uploaded: (table on the device, n_items, n_blocks, C) for `nonbonded(..., plan=)` (include/grappa_hip.h grappa_nonbonded_plan)"""
+        _flat(atom_molptr_host, "atom_molptr_host", torch.device("cpu"), torch.int32)
+        B = atom_molptr_host.numel() - 1
+        if B < 1 or n_confs < 1:
+            return (None, 0, 0, int(n_confs))
+        need = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), None, 0)
+        if need < 0:
+            _chk(int(need), "grappa_nonbonded_plan")
+        table = torch.empty(int(need), dtype=torch.int32)
+        rc = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), table.data_ptr(), table.numel())
+        if rc < 0:
+            _chk(int(rc), "grappa_nonbonded_plan")
+        return (table.to(device), int(table[0]), int(table[1]), int(n_confs))
+
+    def nonbonded(self, xyz, atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps, energy, term_energy=None, grad=None,
+                  plan=None) -> None:
+        """Lennard-Jones + Coulomb energy and gradient over all pairs of every molecule (include/grappa_hip.h grappa_nonbonded_fwd_f32):
+        xyz (N,C,3), atom_molptr (B+1,) int32, charge / sigma / epsilon (N,), the symmetric CSR exception table exc_ptr (N+1,) int32,
+        exc_atom int32, exc_qq / exc_sigma / exc_eps (at least one element each) -> energy (B,C), term_energy (2,B,C) or None,
+        grad (N,C,3) or None.  Angstrom, kcal/mol, elementary charges; the gradient is +dE/dxyz.
+        plan: what `nonbonded_plan` returned for this atom_molptr and C (the work-item list built once on the host: one launch less and
+        an exact grid); None: the list is built on the device by every call.  Same bits either way.
+        Out of scope: gradients with respect to charge, sigma or epsilon (no autograd wrapper: the term has no learnable input);
+        cutoffs, periodic boxes, PME."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"nonbonded: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
+        dev = xyz.device
+        _flat(xyz, "xyz", dev)
+        for t, n in ((atom_molptr, "atom_molptr"), (exc_ptr, "exc_ptr"), (exc_atom, "exc_atom")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {torch.int32} tensor on {dev}")
+            _flat(t, n, dev, torch.int32)
+        for t, n in ((charge, "charge"), (sigma, "sigma"), (epsilon, "epsilon"), (exc_qq, "exc_qq"), (exc_sigma, "exc_sigma"), (exc_eps, "exc_eps"),
+                     (energy, "energy"), (term_energy, "term_energy"), (grad, "grad")):
+            if t is None and n in ("term_energy", "grad"):
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {torch.float32} tensor on {dev}")
+            _flat(t, n, dev)
+        N, Cc, B = xyz.shape[0], xyz.shape[1], atom_molptr.numel() - 1
+        if B < 0 or exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (charge, sigma, epsilon)):
+            raise ValueError("nonbonded: atom_molptr must be (B+1,), exc_ptr (N+1,), charge / sigma / epsilon (N,)")
+        if not (exc_atom.numel() == exc_qq.numel() == exc_sigma.numel() == exc_eps.numel() >= 1):
+            raise ValueError("nonbonded: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+        if energy.numel() != B * Cc or (term_energy is not None and term_energy.numel() != 2 * B * Cc) or (grad is not None and grad.shape != xyz.shape):
+            raise ValueError("nonbonded: expected energy (B,C), term_energy (2,B,C), grad (N,C,3)")
+        d = _lib.NbDesc()
+        d.N, d.C, d.B = N, Cc, B
+        d.xyz, d.atom_molptr = xyz.data_ptr(), atom_molptr.data_ptr()
+        d.charge, d.sigma, d.epsilon = charge.data_ptr(), sigma.data_ptr(), epsilon.data_ptr()
+        d.exc_ptr, d.exc_atom = exc_ptr.data_ptr(), exc_atom.data_ptr()
+        d.exc_qq, d.exc_sigma, d.exc_eps = exc_qq.data_ptr(), exc_sigma.data_ptr(), exc_eps.data_ptr()
+        if plan is not None and plan[0] is not None:
+            table, n_items, n_blocks, plan_c = plan
+            if plan_c != Cc or table.device != dev or table.dtype != torch.int32 or table.numel() < 4 + B + 1 + 4 * n_items:
+                raise ValueError(f"nonbonded: the plan was made for C = {plan_c} on {table.device}, the call has C = {Cc} on {dev}")
+            ws = self._workspace(16 * n_blocks * Cc, dev)
+            _chk(self.lib.grappa_nonbonded_fwd_planned_f32(self._stream(), C.byref(d), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
+                                                           _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()), "grappa_nonbonded_fwd_planned_f32")
+            return
+        ws = self._workspace(self.lib.grappa_nonbonded_workspace_bytes(N, Cc, B), dev)
+        _chk(self.lib.grappa_nonbonded_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()),
+             "grappa_nonbonded_fwd_f32")
+
     # ------------------------------------------------------------------ loss
     def loss_ef(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B, loss_mol, gE, gG) -> None:
         dev = loss_mol.device

@@ -15,6 +15,11 @@ TUPLE_LEVELS = ["n2", "n3", "n4", "n4_improper"]
 LEVEL_ARITY = {"n2": 2, "n3": 3, "n4": 4, "n4_improper": 4}
 BONDED_CONTRIBUTIONS = [("n2", "k"), ("n2", "eq"), ("n3", "k"), ("n3", "eq"), ("n4", "k"), ("n4_improper", "k")]
 
+# Coulomb's constant in kcal A / (mol e^2): OpenMM's ONE_4PI_EPS0 (138.93545764438198 kJ nm / (mol e^2)) converted
+COULOMB_CONSTANT = 138.93545764438198 * 10 / 4.184
+NM_TO_ANGSTROM = 10.0
+KJ_TO_KCAL = 1.0 / 4.184
+
 # default input-feature widths, reference models/graph_attention.py:60-70
 DEFAULT_FEAT_DIMS = {
     "atomic_number": MAX_ELEMENT,

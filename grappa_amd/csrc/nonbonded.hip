@@ -1,0 +1,370 @@
+// Nonbonded energy and gradient (Lennard-Jones + Coulomb, no cutoff: OpenMM's NonbondedForce with NoCutoff) over all atom pairs of
+// every molecule of a batch, fp32, xyz[N,C,3] (include/grappa_hip.h grappa_nb_desc).
+//   table  : the work-item list.  A work item is (molecule, block of ni <= NB_T i-atoms, nc conformations); it depends on the molecule's
+//            size and on C only, never on the molecule's place in the batch.  grappa_nonbonded_plan builds the list on the HOST from a
+//            host copy of atom_molptr, once per (batch, C); the caller keeps it in device memory and grappa_nonbonded_fwd_planned_f32
+//            launches exactly one workgroup per item.  A caller that holds atom_molptr in device memory only calls
+//            grappa_nonbonded_fwd_f32: one workgroup (nb_setup_kernel) builds the same list in the workspace first, and the pairs grid
+//            is its upper bound.  Both paths run the same items in the same way: the same bits.
+//   pairs  : one workgroup of 256 threads per work item.  A thread owns one (i-atom, conformation) and one of JS slices of the j loop
+//            (JS = 256 / (ni * nc): one 50,000-atom molecule with C = 1 keeps all four wavefronts busy, slice s takes j = s, s + JS, ..).
+//            The molecule's j-atoms pass through LDS in ascending blocks of NB_TJ: coordinates per conformation, parameters once for all
+//            conformations.  (With ni * nc < 64 the lanes of one wavefront belong to several slices and read several rows of the LDS
+//            block at once: those reads are not broadcasts.)  A thread walks its atom's sorted exception list in step with j: an
+//            exception REPLACES the pair's parameters, an exclusion (eps = 0 and qq = 0) or j == i is not evaluated at all.  Blocks
+//            in which no thread of a wavefront has an exception or its own atom take a loop without the lookup.
+//            No Newton's third law and no atomics: an atom's gradient is summed by its owner in a fixed j order, the slices are added
+//            in a fixed order through LDS, and the block's half-energies sum_i 1/2 sum_j e_ij are added over i in double.
+//   reduce : one workgroup per molecule adds the blocks' partial energies in double in a fixed order.
+// Same input, same bits.  A non-excluded pair at zero distance gives inf / NaN, as in OpenMM.
+#include <limits.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int NB_T = GRAPPA_NB_IBLOCK;      // i-atoms per work item
+constexpr int NB_TJ = 64;                   // j-atoms per LDS block
+constexpr int NB_NT = 256;                  // threads per workgroup
+constexpr int NB_CW = 16;                   // conformations per work item at most (LDS: NB_TJ * NB_CW float4)
+constexpr int NB_JS = 16;                   // j slices at most
+constexpr float NB_K = (float)(138.93545764438198 * 10.0 / 4.184);      // kcal A / (mol e^2): OpenMM's ONE_4PI_EPS0
+
+// conformations of a block of ni i-atoms are dealt out in nchunks work items of at most ncb
+__host__ __device__ inline void nb_chunks(int ni, int C, int& nchunks, int& ncb) {
+    int cpw = NB_NT / ni;
+    if (cpw > NB_CW) cpw = NB_CW;
+    nchunks = (C + cpw - 1) / cpw;
+    ncb = (C + nchunks - 1) / nchunks;
+}
+
+__device__ inline int nb_clamp(int v, int N) { return v < 0 ? 0 : (v > N ? N : v); }
+
+// ------------------------------------------------------------------------------------------------ setup
+// hdr[0] = number of work items; blk_ptr[b] = first i-block of molecule b (blocks number the rows of the partial energies);
+// items[k] = {molecule, first i-atom, i-block, first conformation}
+__global__ __launch_bounds__(NB_NT) void nb_setup_kernel(int N, int C, int B, const int* __restrict__ molptr, int* __restrict__ hdr,
+                                                         int* __restrict__ blk_ptr, int4* __restrict__ items, int max_blk, int max_items) {
+    __shared__ int sblk[NB_NT], sitem[NB_NT];
+    const int t = threadIdx.x;
+    const int per = (B + NB_NT - 1) / NB_NT;
+    const int b0 = t * per < B ? t * per : B, b1 = b0 + per < B ? b0 + per : B;
+    int nblk = 0, nitem = 0, cf, ncb;
+    nb_chunks(NB_T, C, cf, ncb);
+    for (int b = b0; b < b1; ++b) {
+        const int n = nb_clamp(molptr[b + 1], N) - nb_clamp(molptr[b], N);
+        const int full = n > 0 ? n / NB_T : 0, rem = n > 0 ? n - full * NB_T : 0;
+        int cr = 0;
+        if (rem) nb_chunks(rem, C, cr, ncb);
+        nblk += full + (rem ? 1 : 0);
+        nitem += full * cf + cr;
+    }
+    sblk[t] = nblk;
+    sitem[t] = nitem;
+    __syncthreads();
+    if (t == 0) {
+        int ab = 0, ai = 0;
+        for (int k = 0; k < NB_NT; ++k) {
+            const int vb = sblk[k], vi = sitem[k];
+            sblk[k] = ab;
+            sitem[k] = ai;
+            ab += vb;
+            ai += vi;
+        }
+        hdr[0] = ai < max_items ? ai : max_items;
+        blk_ptr[B] = ab < max_blk ? ab : max_blk;
+    }
+    __syncthreads();
+    int blk = sblk[t], item = sitem[t];
+    for (int b = b0; b < b1; ++b) {
+        blk_ptr[b] = blk < max_blk ? blk : max_blk;
+        const int a0 = nb_clamp(molptr[b], N), a1 = nb_clamp(molptr[b + 1], N);
+        for (int i0 = a0; i0 < a1; i0 += NB_T, ++blk) {
+            const int ni = a1 - i0 < NB_T ? a1 - i0 : NB_T;
+            int nch;
+            nb_chunks(ni, C, nch, ncb);
+            for (int k = 0; k < nch; ++k, ++item)
+                if (item < max_items && blk < max_blk) items[item] = make_int4(b, i0, blk, k * ncb);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pairs
+struct NbArgs {
+    grappa_nb_desc d;
+    const int* hdr;        // hdr[0] = number of work items (the grid is an upper bound), or NULL (the grid is exact)
+    const int4* items;
+    double* part;      // [blocks][C][2]: LJ, Coulomb half-energies of the block's i-atoms
+    float* grad;
+    int max_blk;       // rows of `part`
+};
+
+// one pair: d = x_i - x_j, sij / e4 / kqq = sigma, 4 eps, K q_i q_j of the pair.  v_rsq_f32 is good to 1 ulp and the twelfth power
+// multiplies that by 12: one Newton step brings 1/r to half an ulp.
+__device__ __forceinline__ void nb_pair(float dx, float dy, float dz, float sij, float e4, float kqq, float& elj, float& ec, float& gx,
+                                        float& gy, float& gz) {
+    const float r2 = dx * dx + dy * dy + dz * dz;
+    float y = __builtin_amdgcn_rsqf(r2);
+    y = __builtin_fmaf(0.5f * y, __builtin_fmaf(-r2 * y, y, 1.0f), y);
+    const float y2 = y * y;
+    const float sr2 = sij * sij * y2;
+    const float sr6 = sr2 * sr2 * sr2;
+    const float l6 = e4 * sr6, l12 = l6 * sr6;
+    const float c = kqq * y;
+    elj += l12 - l6;
+    ec += c;
+    const float f = (6.0f * l6 - 12.0f * l12 - c) * y2;      // (dE/dr) / r
+    gx = __builtin_fmaf(f, dx, gx);
+    gy = __builtin_fmaf(f, dy, gy);
+    gz = __builtin_fmaf(f, dz, gz);
+}
+
+__global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
+    __shared__ float4 xs[NB_TJ * NB_CW];      // j coordinates: [jj][conformation of the item]
+    __shared__ float4 ps[NB_TJ];              // j parameters: q, sigma / 2, sqrt(eps)
+    __shared__ float red[5][NB_NT];
+    if (a.hdr && (int)blockIdx.x >= a.hdr[0]) return;
+    const grappa_nb_desc& d = a.d;
+    const int4 it = a.items[blockIdx.x];
+    const int mol = it.x, i0 = it.y, blk = it.z, c0 = it.w;
+    const int C = d.C;
+    if (mol < 0 || mol >= d.B || blk < 0 || blk >= a.max_blk || c0 < 0 || c0 >= C) return;      // (a table made for another batch)
+    const int m0 = nb_clamp(d.atom_molptr[mol], d.N), m1 = nb_clamp(d.atom_molptr[mol + 1], d.N);
+    if (i0 < m0 || i0 >= m1) return;
+    const int ni = m1 - i0 < NB_T ? m1 - i0 : NB_T;
+    int nch, ncb;
+    nb_chunks(ni, C, nch, ncb);
+    const int nc = C - c0 < ncb ? C - c0 : ncb;
+    const int NL = ni * nc;
+    const int JS = NB_NT / NL < NB_JS ? NB_NT / NL : NB_JS;
+    const int t = threadIdx.x, s = t / NL, l = t - s * NL;
+    const bool active = s < JS;
+    const int cl = l / ni, il = l - cl * ni;      // i is the fast index: the lanes of a wavefront share few conformations (LDS broadcasts)
+    const int i = i0 + il, c = c0 + cl;
+
+    float xi = 0.f, yi = 0.f, zi = 0.f, kq = 0.f, hs = 0.f, se = 0.f;
+    int ep = 0, ee = 0, nx = INT_MAX;
+    if (active) {
+        const float* p = d.xyz + ((size_t)i * C + c) * 3;
+        xi = p[0], yi = p[1], zi = p[2];
+        kq = NB_K * d.charge[i];
+        hs = 0.5f * d.sigma[i];
+        se = 4.0f * sqrtf(d.epsilon[i]);
+        ep = d.exc_ptr[i];
+        ee = d.exc_ptr[i + 1];
+        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+    }
+    float elj = 0.f, ec = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
+        const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
+        __syncthreads();
+        for (int idx = t; idx < nj * nc; idx += NB_NT) {
+            const int jj = idx / nc, cc = idx - jj * nc;
+            const float* p = d.xyz + ((size_t)(j0 + jj) * C + c0 + cc) * 3;
+            xs[jj * NB_CW + cc] = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        if (t < nj) ps[t] = make_float4(d.charge[j0 + t], 0.5f * d.sigma[j0 + t], sqrtf(d.epsilon[j0 + t]), 0.f);
+        __syncthreads();
+        const bool lookup = active && ((i >= j0 && i < j0 + nj) || nx < j0 + nj);
+        if (__builtin_amdgcn_ballot_w64(lookup) != 0) {
+            if (active) {
+                for (int jj = s; jj < nj; jj += JS) {
+                    const int j = j0 + jj;
+                    const float4 p = ps[jj];
+                    float sij = hs + p.y, e4 = se * p.z, kqq = kq * p.x;
+                    bool skip = j == i;
+                    while (nx < j) {
+                        ++ep;
+                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                    }
+                    if (nx == j) {
+                        const float q = d.exc_qq[ep], e = d.exc_eps[ep];
+                        sij = d.exc_sigma[ep];
+                        e4 = 4.0f * e;
+                        kqq = NB_K * q;
+                        skip = skip || (q == 0.f && e == 0.f);
+                        ++ep;
+                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                    }
+                    if (!skip) {
+                        const float4 x = xs[jj * NB_CW + cl];
+                        nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                    }
+                }
+                while (nx < j0 + nj) {      // partners that belong to other slices
+                    ++ep;
+                    nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                }
+            }
+        } else if (active) {
+#pragma unroll 4
+            for (int jj = s; jj < nj; jj += JS) {
+                const float4 p = ps[jj];
+                const float4 x = xs[jj * NB_CW + cl];
+                nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
+            }
+        }
+    }
+    // the slices of one (atom, conformation), added in slice order
+    red[0][t] = elj, red[1][t] = ec, red[2][t] = gx, red[3][t] = gy, red[4][t] = gz;
+    __syncthreads();
+    const bool owner = active && s == 0;
+    if (owner) {
+        for (int q = 1; q < JS; ++q) {
+            const int o = q * NL + l;
+            elj += red[0][o], ec += red[1][o], gx += red[2][o], gy += red[3][o], gz += red[4][o];
+        }
+        if (a.grad) {
+            float* g = a.grad + ((size_t)i * C + c) * 3;
+            g[0] = gx, g[1] = gy, g[2] = gz;
+        }
+    }
+    __syncthreads();
+    if (owner) red[0][l] = elj, red[1][l] = ec;
+    __syncthreads();
+    if (owner && il == 0) {
+        double slj = 0.0, sc = 0.0;
+        for (int k = 0; k < ni; ++k) {
+            slj += (double)red[0][cl * ni + k];
+            sc += (double)red[1][cl * ni + k];
+        }
+        double* o = a.part + ((size_t)blk * C + c) * 2;
+        o[0] = 0.5 * slj, o[1] = 0.5 * sc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ reduce
+// one workgroup per molecule; thread (r, conformation) adds the blocks r, r + R, .. and the R rows are added in order
+__global__ __launch_bounds__(NB_NT) void nb_reduce_kernel(int C, int B, const int* __restrict__ blk_ptr, const double* __restrict__ part,
+                                                          float* __restrict__ energy, float* __restrict__ term_energy) {
+    __shared__ double red[2][NB_NT];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int k0 = blk_ptr[b], k1 = blk_ptr[b + 1];
+    const int cs = C < NB_NT ? C : NB_NT, R = NB_NT / cs;
+    const int r = t / cs, cl = t - r * cs;
+    for (int cb = 0; cb < C; cb += cs) {
+        const int c = cb + cl;
+        const bool ok = r < R && c < C;
+        double slj = 0.0, sc = 0.0;
+        if (ok)
+            for (int k = k0 + r; k < k1; k += R) {
+                const double* p = part + ((size_t)k * C + c) * 2;
+                slj += p[0], sc += p[1];
+            }
+        red[0][t] = slj, red[1][t] = sc;
+        __syncthreads();
+        if (ok && r == 0) {
+            for (int q = 1; q < R; ++q) slj += red[0][q * cs + cl], sc += red[1][q * cs + cl];
+            energy[(size_t)b * C + c] = (float)(slj + sc);
+            if (term_energy) {
+                term_energy[(size_t)b * C + c] = (float)slj;
+                term_energy[((size_t)B + b) * C + c] = (float)sc;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+struct NbLayout {
+    size_t blk_ptr, items, part, total;
+    long long max_blk, max_items;
+};
+NbLayout nb_layout(int N, int C, int B) {
+    NbLayout L;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // every molecule ends in at most one short block; a block of ni <= NB_T atoms takes at most ceil(C / (NB_NT / NB_T)) work items
+    L.max_blk = (long long)N / NB_T + B;
+    L.max_items = L.max_blk * ((C + NB_NT / NB_T - 1) / (NB_NT / NB_T));
+    L.blk_ptr = 256;
+    L.items = L.blk_ptr + up(sizeof(int) * ((size_t)B + 1));
+    L.part = L.items + up(sizeof(int4) * (size_t)L.max_items);
+    L.total = L.part + up(sizeof(double) * 2 * (size_t)L.max_blk * (size_t)C);
+    return L;
+}
+
+}  // namespace
+
+extern "C" int grappa_nonbonded_iblock(void) { return NB_T; }
+
+extern "C" size_t grappa_nonbonded_workspace_bytes(int N, int C, int B) {
+    if (N <= 0 || C <= 0 || B <= 0) return 0;
+    return nb_layout(N, C, B).total;
+}
+
+static int nb_check(const grappa_nb_desc* d, const float* energy) {
+    if (!d->xyz || !d->atom_molptr || !d->charge || !d->sigma || !d->epsilon || !d->exc_ptr || !d->exc_atom || !d->exc_qq || !d->exc_sigma ||
+        !d->exc_eps || !energy)
+        return GRAPPA_ERR_ARG;
+    return GRAPPA_OK;
+}
+
+extern "C" int grappa_nonbonded_fwd_f32(void* stream, const grappa_nb_desc* d, float* energy, float* term_energy, float* grad, void* ws,
+                                        size_t ws_bytes) {
+    if (!d || d->N < 0 || d->C < 0 || d->B < 0) return GRAPPA_ERR_ARG;
+    if (d->N == 0 || d->C == 0 || d->B == 0) return GRAPPA_OK;
+    if (nb_check(d, energy) != GRAPPA_OK || !ws) return GRAPPA_ERR_ARG;
+    const NbLayout L = nb_layout(d->N, d->C, d->B);
+    if (L.max_items > INT_MAX) return GRAPPA_ERR_ARG;
+    if (ws_bytes < L.total) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    int* hdr = (int*)w;
+    int* blk_ptr = (int*)(w + L.blk_ptr);
+    int4* items = (int4*)(w + L.items);
+    double* part = (double*)(w + L.part);
+    GRAPPA_LAUNCH(nb_setup_kernel, dim3(1), dim3(NB_NT), 0, st, d->N, d->C, d->B, d->atom_molptr, hdr, blk_ptr, items, (int)L.max_blk,
+                  (int)L.max_items);
+    NbArgs a{*d, hdr, items, part, grad, (int)L.max_blk};
+    GRAPPA_LAUNCH(nb_pairs_kernel, dim3((unsigned)L.max_items), dim3(NB_NT), 0, st, a);
+    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, part, energy, term_energy);
+    return grappa_launch_status();
+}
+
+// the table of the planned path, as ints: [n_items, n_blocks, 0, 0 | blk_ptr[B+1], padded to a multiple of 4 | items: 4 per item]
+extern "C" long long grappa_nonbonded_plan(int N, int C, int B, const int* atom_molptr_host, int* table, long long table_ints) {
+    if (N < 0 || C < 1 || B < 1 || !atom_molptr_host) return GRAPPA_ERR_ARG;
+    const long long items0 = 4 + (((long long)B + 1 + 3) & ~3LL);
+    long long blk = 0, item = 0;
+    for (int pass = 0; pass < (table ? 2 : 1); ++pass) {      // count, then (with a table of the counted size) fill
+        if (pass == 1) {
+            if (table_ints < items0 + 4 * item) return GRAPPA_ERR_WORKSPACE;
+            table[0] = (int)item, table[1] = (int)blk, table[2] = table[3] = 0;
+            for (long long k = 4 + B + 1; k < items0; ++k) table[k] = 0;
+            blk = item = 0;
+        }
+        for (int b = 0; b < B; ++b) {
+            const int a0 = atom_molptr_host[b], a1 = atom_molptr_host[b + 1];
+            if (a0 < 0 || a1 < a0 || a1 > N) return GRAPPA_ERR_ARG;
+            if (pass == 1) table[4 + b] = (int)blk;
+            for (int i0 = a0; i0 < a1; i0 += NB_T, ++blk) {
+                int nch, ncb;
+                nb_chunks(a1 - i0 < NB_T ? a1 - i0 : NB_T, C, nch, ncb);
+                if (pass == 1)
+                    for (int k = 0; k < nch; ++k) {
+                        int* it = table + items0 + 4 * (item + k);
+                        it[0] = b, it[1] = i0, it[2] = (int)blk, it[3] = k * ncb;
+                    }
+                item += nch;
+            }
+        }
+        if (item > INT_MAX / 4 || blk > INT_MAX) return GRAPPA_ERR_ARG;
+        if (pass == 1) table[4 + B] = (int)blk;
+    }
+    return items0 + 4 * item;
+}
+
+extern "C" int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_desc* d, const int* table_dev, int n_items, int n_blocks,
+                                                float* energy, float* term_energy, float* grad, void* ws, size_t ws_bytes) {
+    if (!d || d->N < 0 || d->C < 0 || d->B < 0 || n_items < 0 || n_blocks < 0) return GRAPPA_ERR_ARG;
+    if (d->N == 0 || d->C == 0 || d->B == 0) return GRAPPA_OK;
+    if (nb_check(d, energy) != GRAPPA_OK || !table_dev || (n_blocks > 0 && !ws)) return GRAPPA_ERR_ARG;
+    if (n_blocks > (long long)d->N / NB_T + d->B) return GRAPPA_ERR_ARG;
+    if (ws_bytes < sizeof(double) * 2 * (size_t)n_blocks * (size_t)d->C) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int* blk_ptr = table_dev + 4;
+    const int4* items = (const int4*)(table_dev + 4 + (((size_t)d->B + 1 + 3) & ~(size_t)3));
+    NbArgs a{*d, nullptr, items, (double*)ws, grad, n_blocks};
+    if (n_items > 0) GRAPPA_LAUNCH(nb_pairs_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
+    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, (const double*)ws, energy, term_energy);
+    return grappa_launch_status();
+}

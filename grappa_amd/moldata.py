@@ -5,7 +5,9 @@ Mirrors the reference's data/MolData.py: `to_dict` :200-258 / `from_dict` :262-3
 allow_pickle) and `to_dgl` :155-197 (xyz (N,C,3), energy_ref (1,C) centred, gradient_ref (N,C,3), `energy_<ff>` /
 `gradient_<ff>` per stored force field) plus data/Parameters.py:458-511 `write_to_dgl` (k_ref / eq_ref; torsion
 (|k|, phase in {0, pi, 2pi}) -> signed k, zero-padded / truncated to N_PERIODICITY_* columns).
-Only reading and graph construction are in scope; creation from OpenMM / OpenFF / QM data is not.
+Records are read, turned into graphs, and made from QM arrays plus a nonbonded contribution (`from_arrays`, data/MolData.py:105-151);
+where the reference asks OpenMM for that contribution, `with_nonbonded` computes it on the device (grappa_amd.nonbonded).  Creation
+from OpenMM systems or OpenFF molecules is not in scope.
 """
 from dataclasses import dataclass, field
 from typing import Dict, Optional
@@ -58,6 +60,48 @@ class MolData:
         self.ff_gradient.setdefault("qm", self.gradient)
         for k, v in self.ff_energy.items():
             assert v.shape == self.energy.shape, f"Shape of ff_energy {k} does not match energy: {v.shape} vs {self.energy.shape}"
+
+    # ------------------------------------------------------------------ from QM arrays
+    @classmethod
+    def from_arrays(cls, molecule: Molecule, xyz: np.ndarray, energy: np.ndarray, nonbonded_energy: np.ndarray, gradient: np.ndarray = None,
+                    nonbonded_gradient: np.ndarray = None, smiles: str = None, sequence: str = None, mol_id: str = None,
+                    ff_energy: np.ndarray = None, ff_gradient: np.ndarray = None) -> "MolData":
+        """a record from 'raw' arrays (data/MolData.py:105-151): energy_ref = energy - nonbonded_energy, centred over the conformations;
+        gradient_ref = gradient - nonbonded_gradient, zeros when no gradient is given; mol_id falls back to smiles, then sequence, then ''.
+        The nonbonded contribution is kept as extras['nonbonded_energy_reference_ff'] / extras['nonbonded_gradient_reference_ff']."""
+        xyz, energy, nonbonded_energy = np.asarray(xyz), np.asarray(energy), np.asarray(nonbonded_energy)
+        energy_ref = energy - nonbonded_energy
+        energy_ref = energy_ref - energy_ref.mean()
+        if gradient is not None:
+            assert nonbonded_gradient is not None, "If gradient is provided, nonbonded_gradient must be provided as well."
+        if gradient is None:
+            gradient = np.zeros_like(xyz)
+            nonbonded_gradient = np.zeros_like(xyz)
+        gradient, nonbonded_gradient = np.asarray(gradient), np.asarray(nonbonded_gradient)
+        if mol_id is None:
+            mol_id = smiles if smiles is not None else (sequence if sequence is not None else "")
+        extras = {"nonbonded_energy_reference_ff": nonbonded_energy, "nonbonded_gradient_reference_ff": nonbonded_gradient}
+        if smiles is not None:
+            extras["smiles"] = np.array(str(smiles))
+        if sequence is not None:
+            extras["sequence"] = np.array(str(sequence))
+        return cls(molecule=molecule, xyz=xyz, energy=energy, gradient=gradient, energy_ref=energy_ref, gradient_ref=gradient - nonbonded_gradient,
+                   mol_id=mol_id, ff_energy={} if ff_energy is None else {"reference_ff": np.asarray(ff_energy)},
+                   ff_gradient={} if ff_gradient is None else {"reference_ff": np.asarray(ff_gradient)}, extras=extras)
+
+    def with_nonbonded(self, params, ff_name: str = "reference_ff", device="cuda") -> "MolData":
+        """a copy of the record whose nonbonded contribution is the Lennard-Jones + Coulomb energy and gradient of `params`
+        (grappa_amd.nonbonded.NonbondedParameters) at self.xyz, computed on `device`: energy_ref (centred), gradient_ref and
+        extras['nonbonded_energy_<ff_name>'] / extras['nonbonded_gradient_<ff_name>'] are recomputed from self.energy / self.gradient"""
+        import dataclasses
+
+        from .nonbonded import nonbonded_energy
+        e_nb, g_nb = nonbonded_energy(params, self.xyz, device=device)
+        energy_ref = self.energy - e_nb
+        extras = dict(self.extras)
+        extras[f"nonbonded_energy_{ff_name}"], extras[f"nonbonded_gradient_{ff_name}"] = e_nb, g_nb
+        return dataclasses.replace(self, energy_ref=energy_ref - energy_ref.mean(), gradient_ref=self.gradient - g_nb, extras=extras,
+                                   ff_energy=dict(self.ff_energy), ff_gradient=dict(self.ff_gradient), params=dict(self.params))
 
     # ------------------------------------------------------------------ npz schema
     @classmethod

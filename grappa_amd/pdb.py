@@ -20,6 +20,8 @@ from typing import Dict, List, NamedTuple, Tuple
 
 import numpy as np
 
+from .constants import KJ_TO_KCAL, NM_TO_ANGSTROM
+
 _ELEMENT_Z = {"H": 1, "C": 6, "N": 7, "O": 8, "F": 9, "Na": 11, "Mg": 12, "P": 15, "S": 16, "Cl": 17, "K": 19, "Ca": 20, "Zn": 30, "Br": 35, "I": 53}
 _VARIANTS = {"HIS": ["HIS", "HID", "HIE", "HIP"], "CYS": ["CYS", "CYX", "CYM"], "ASP": ["ASP", "ASH"], "GLU": ["GLU", "GLH"],
              "LYS": ["LYS", "LYN"]}
@@ -37,10 +39,22 @@ class ForceFieldTemplates:
         root = ET.parse(xml_path).getroot()
         self.element = {t.get("name"): t.get("element") for t in root.iter("Type")}
         self.charge = {}
+        # Lennard-Jones parameters per atom type in this project's units (the XML holds nm and kJ/mol), and the block's 1-4 scale factors
+        # (grappa_amd.nonbonded.from_pdb)
+        self.sigma, self.epsilon = {}, {}
+        self.coulomb14scale, self.lj14scale = 1 / 1.2, 0.5
         for nb in root.iter("NonbondedForce"):
+            if nb.get("coulomb14scale") is not None:
+                self.coulomb14scale = float(nb.get("coulomb14scale"))
+            if nb.get("lj14scale") is not None:
+                self.lj14scale = float(nb.get("lj14scale"))
             for a in nb.iter("Atom"):
                 if a.get("type") is not None and a.get("charge") is not None:
                     self.charge[a.get("type")] = float(a.get("charge"))
+                if a.get("type") is not None and a.get("sigma") is not None:
+                    self.sigma[a.get("type")] = float(a.get("sigma")) * NM_TO_ANGSTROM
+                if a.get("type") is not None and a.get("epsilon") is not None:
+                    self.epsilon[a.get("type")] = float(a.get("epsilon")) * KJ_TO_KCAL
         self.residues: Dict[str, Template] = {}
         for r in root.iter("Residue"):
             atoms = r.findall("Atom")
@@ -97,9 +111,13 @@ def read_pdb_atoms(pdb_path: str):
 def graph_from_pdb(pdb_path: str, ffxml_path: str):
     """-> dict(z (n,) int64, bonds (m,2) int64 atom indices in file order, charges (n,) float32, xyz (n,3) float32 in Angstrom,
     residue_ptr (R+1,), residue_templates [R])"""
-    ff = ForceFieldTemplates(ffxml_path)
+    return typed_graph_from_pdb(pdb_path, ForceFieldTemplates(ffxml_path))[0]
+
+
+def typed_graph_from_pdb(pdb_path: str, ff: ForceFieldTemplates):
+    """-> (the dict of graph_from_pdb, the force-field atom type of every atom in file order)"""
     residues = read_pdb_atoms(pdb_path)
-    z, q, xyz, bonds, ptr, tnames = [], [], [], [], [0], []
+    z, q, xyz, bonds, ptr, tnames, types = [], [], [], [], [0], [], []
     ext_atoms = []           # per residue: {atom name: global index} of the atoms that carry an external bond
     for ri, (chain, resname, atoms) in enumerate(residues):
         first = ri == 0 or residues[ri - 1][0] != chain
@@ -108,12 +126,14 @@ def graph_from_pdb(pdb_path: str, ffxml_path: str):
         t = ff.residues[tname]
         base = ptr[-1]
         glob = [base + p for p in perm]                                       # template atom i -> global atom index
-        zr, qr = [0] * len(atoms), [0.0] * len(atoms)
+        zr, qr, tr = [0] * len(atoms), [0.0] * len(atoms), [None] * len(atoms)
         for i, ty in enumerate(t.types):
             zr[perm[i]] = _ELEMENT_Z[ff.element[ty]]
             qr[perm[i]] = ff.charge[ty]
+            tr[perm[i]] = ty
         z += zr
         q += qr
+        types += tr
         xyz += [a[1] for a in atoms]
         bonds += [(glob[a], glob[b]) for a, b in t.bonds]
         ext_atoms.append({t.names[i]: glob[i] for i in t.external})
@@ -131,4 +151,4 @@ def graph_from_pdb(pdb_path: str, ffxml_path: str):
                 bonds.append((a, b))
                 used.update((a, b))
     return {"z": np.asarray(z, dtype=np.int64), "bonds": np.asarray(bonds, dtype=np.int64).reshape(-1, 2), "charges": np.asarray(q, dtype=np.float32),
-            "xyz": xyz, "residue_ptr": np.asarray(ptr, dtype=np.int64), "residue_templates": tnames}
+            "xyz": xyz, "residue_ptr": np.asarray(ptr, dtype=np.int64), "residue_templates": tnames}, types

@@ -462,6 +462,44 @@ int grappa_mm_bwd_f32(void* stream, const grappa_mm_desc* d, const float* gE, co
                       float* const gk[4], float* const geq[4]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nonbonded energy and gradient (additions to ABI 11): OpenMM's NonbondedForce with NoCutoff, in Angstrom, kcal/mol and elementary
+ * charges.  For every molecule b (atoms atom_molptr[b] .. atom_molptr[b+1]-1, atom_molptr[B] == N) and conformation c:
+ *   E[b,c] = sum_{i<j, (i,j) no exception} 4 eps_ij ((s_ij/r)^12 - (s_ij/r)^6) + K q_i q_j / r
+ *          + sum_{exceptions p=(i,j)}      4 eps_p  ((s_p /r)^12 - (s_p /r)^6) + K qq_p / r
+ *   s_ij = (sigma_i + sigma_j)/2, eps_ij = sqrt(eps_i eps_j), K = 138.93545764438198 * 10 / 4.184;  G[a,c,:] = +dE/dxyz[a,c,:].
+ * Atoms of different molecules never interact.  An exception REPLACES the pair's interaction; with eps_p == 0 and qq_p == 0 it is an
+ * exclusion, which is not evaluated (two excluded atoms may coincide).  A non-excluded pair at zero distance gives inf / NaN.
+ * The exception table is a CSR over the atoms with batch-global partner indices, ascending per atom, every exception stored on both
+ * of its atoms (partners outside the atom's molecule are ignored).  The five exc_* arrays must be non-NULL (one unused element when
+ * the table is empty).  term_energy[2,B,C] = the Lennard-Jones and the Coulomb part (NULL: not written); grad NULL: not written.
+ * Fixed-order sums, no atomics: same input, same bits, and a molecule's results do not depend on its place in the batch.
+ * No gradients with respect to charge / sigma / epsilon; no cutoff, periodic box or PME.
+ * GRAPPA_ERR_ARG: a NULL required pointer or a negative size; N == 0, C == 0 or B == 0: returns 0 without a launch. */
+#define GRAPPA_NB_IBLOCK 64      /* i-atoms per workgroup: molecule sizes around its multiples are the kernel's edges */
+typedef struct grappa_nb_desc {
+    int N, C, B;
+    const float* xyz;            /* [N,C,3] */
+    const int*   atom_molptr;    /* [B+1] */
+    const float *charge, *sigma, *epsilon;   /* [N] */
+    const int*   exc_ptr;        /* [N+1]: exceptions of atom a = exc_*[exc_ptr[a] .. exc_ptr[a+1]) */
+    const int*   exc_atom;       /* partner, batch-global index, ascending per atom; every exception is stored on both of its atoms */
+    const float *exc_qq, *exc_sigma, *exc_eps;
+} grappa_nb_desc;
+int grappa_nonbonded_iblock(void);       /* GRAPPA_NB_IBLOCK of the library that is loaded */
+size_t grappa_nonbonded_workspace_bytes(int N, int C, int B);
+int grappa_nonbonded_fwd_f32(void* stream, const grappa_nb_desc* d, float* energy /*[B,C]*/, float* term_energy /*[2,B,C] LJ, Coulomb; may be NULL*/,
+                             float* grad /*[N,C,3]; may be NULL*/, void* ws, size_t ws_bytes);
+/* The same with the work-item list built on the HOST, once per (batch, C), instead of by a setup launch per call (the entry point above
+ * cannot read atom_molptr, which is device memory).  grappa_nonbonded_plan reads a HOST copy of atom_molptr and writes the table as ints:
+ * [n_items, n_blocks, 0, 0 | blk_ptr[B+1] padded to a multiple of 4 | 4 ints per item]; it returns the table's length in ints (table ==
+ * NULL: only that), GRAPPA_ERR_ARG for C < 1, B < 1 or ranges that do not ascend inside [0, N], GRAPPA_ERR_WORKSPACE for a table that is too
+ * short.  The caller copies the table to 16-byte aligned device memory and passes it with table[0] and table[1]; the pairs grid is then
+ * exactly n_items and the workspace holds only the partial energies (16 * n_blocks * C bytes).  Same items, same bits as the entry point above. */
+long long grappa_nonbonded_plan(int N, int C, int B, const int* atom_molptr_host, int* table, long long table_ints);
+int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_desc* d, const int* table_dev, int n_items, int n_blocks, float* energy,
+                                     float* term_energy, float* grad, void* ws, size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:
  *  l_m = wE*mean_c((E-<E>)-(Eref-<Eref>))^2 + wG*mean_{a,c,xyz}(G-Gref)^2   over real conformations
  *  loss_mol[b] = l_m ; gE = d(sum_m l_m * inv_B)/dE ; gG likewise.  is_dummy may be NULL. */

@@ -1,0 +1,188 @@
+"""Time the nonbonded kernel (csrc/nonbonded.hip through HipBackend.nonbonded) with device events, after warm-up, at two shapes:
+
+  pool    256 molecules of the pool x 32 conformations (a training batch)
+  chain   one synthetic 50,046-atom chain, 1 conformation (BASELINE configs[4]'s size: 2.5e9 ordered pairs)
+
+and, at the first shape only (N^2 memory rules out the second), a plain torch broadcast implementation of the same sums on the same GPU.
+Rows per shape: the kernel alone (HipBackend.nonbonded into preallocated outputs, work-item list built once on the host), the same call
+without the gradient output, with the list built on the device by every call, and NonbondedBatch.evaluate (which also allocates its outputs).
+Prints microseconds per call and pair interactions per second; a pair interaction is one evaluated ordered pair (i, j) of one
+conformation, sum_b n_b (n_b - 1) C per call -- the kernel evaluates every unordered pair twice, once for each owner, and both count.
+The share of the fp32 vector peak uses FLOP_PER_PAIR below (counted from the kernel's inner loop) and 157.3 TFLOP/s.
+
+    python tools/nonbonded_bench.py [--out profiles/nonbonded_bench.txt] [--seconds 1.0]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from grappa_amd.constants import COULOMB_CONSTANT      # noqa: E402
+from grappa_amd.nonbonded import NonbondedBatch, NonbondedParameters      # noqa: E402
+
+# fp32 operations of one pair in the kernel's loop without the exception lookup (an fma counts 2): 3 sub, r^2 5, rsq 1, Newton step 7,
+# y^2 1, sigma / eps / qq of the pair 3, (s/r)^2 .. l12 6, Coulomb 1, two energy sums 3, (dE/dr)/r 6, gradient 6
+FLOP_PER_PAIR = 42
+PEAK_FP32_VECTOR = 157.3e12
+
+
+def pool_batch(n_mols, n_confs, seed=0):
+    from grappa_amd.datasets import pool_molecule, pool_size
+    rng = np.random.default_rng(seed)
+    params, xs = [], []
+    for k in range(n_mols):
+        z, bonds, xyz0 = pool_molecule(k % pool_size())
+        n = len(z)
+        q = rng.normal(0, 0.3, n)
+        params.append(NonbondedParameters.from_bonds(bonds, q - q.mean(), np.where(z == 1, 1.1, 3.3), np.where(z == 1, 0.016, 0.1)))
+        xs.append(xyz0[:, None, :] + rng.normal(0, 0.05, size=(n, n_confs, 3)))
+    return params, np.concatenate(xs, axis=0).astype(np.float32)
+
+
+def chain(n_atoms, seed=1):
+    """a self-avoiding zigzag on a cubic lattice of 1.5 A, bonded along the chain"""
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(n_atoms ** (1 / 3)))
+    k = np.arange(n_atoms)
+    x, y, zc = k % side, (k // side) % side, k // (side * side)
+    y = np.where(zc % 2 == 1, side - 1 - y, y)
+    x = np.where((k // side) % 2 == 1, side - 1 - x, x)      # boustrophedon: consecutive atoms are lattice neighbours
+    xyz = 1.5 * np.stack([x, y, zc], axis=1) + rng.uniform(-0.1, 0.1, size=(n_atoms, 3))
+    bonds = np.stack([k[:-1], k[1:]], axis=1)
+    q = rng.normal(0, 0.3, n_atoms)
+    p = NonbondedParameters.from_bonds(bonds, q - q.mean(), rng.uniform(1.0, 2.0, n_atoms), rng.uniform(0.01, 0.1, n_atoms))
+    return [p], xyz[:, None, :].astype(np.float32)
+
+
+def torch_broadcast(nb, pad_idx, pad_mask, xyz):
+    """the same sums as padded (B, n, n, C) broadcasts in stock torch ops (exceptions as dense override tables built once, outside the
+    timed region)"""
+    x = xyz[pad_idx] * pad_mask[:, :, None, None]                      # (B, n, C, 3)
+    d = x[:, :, None] - x[:, None, :]                                  # (B, n, n, C, 3)
+    m = nb["mask"][..., None]
+    r2 = torch.where(m, (d * d).sum(-1), torch.ones((), device=x.device))
+    inv = torch.rsqrt(r2)
+    sr6 = (nb["sij"][..., None] * inv) ** 6
+    l6 = nb["e4"][..., None] * sr6
+    l12 = l6 * sr6
+    co = nb["kqq"][..., None] * inv
+    zero = torch.zeros((), device=x.device)
+    energy = 0.5 * torch.where(m, l12 - l6 + co, zero).sum((1, 2))
+    f = torch.where(m, (6 * l6 - 12 * l12 - co) * inv * inv, zero)
+    grad = (f[..., None] * d).sum(2)
+    return energy, grad
+
+
+def dense_tables(params, device):
+    B, n = len(params), max(p.n_atoms for p in params)
+    sij, e4, kqq = np.zeros((B, n, n), np.float32), np.zeros((B, n, n), np.float32), np.zeros((B, n, n), np.float32)
+    mask = np.zeros((B, n, n), bool)
+    pad_idx, pad_mask, o = np.zeros((B, n), np.int64), np.zeros((B, n), np.float32), 0
+    for b, p in enumerate(params):
+        k = p.n_atoms
+        sij[b, :k, :k] = 0.5 * (p.sigma[:, None] + p.sigma[None, :])
+        e4[b, :k, :k] = 4 * np.sqrt(p.epsilon[:, None] * p.epsilon[None, :])
+        kqq[b, :k, :k] = COULOMB_CONSTANT * p.charge[:, None] * p.charge[None, :]
+        mask[b, :k, :k] = ~np.eye(k, dtype=bool)
+        i, j = p.exception_idx[:, 0], p.exception_idx[:, 1]
+        for a, c in ((i, j), (j, i)):
+            sij[b, a, c], e4[b, a, c], kqq[b, a, c] = p.exception_sigma, 4 * p.exception_epsilon, COULOMB_CONSTANT * p.exception_chargeprod
+            mask[b, a, c] = ~((p.exception_epsilon == 0) & (p.exception_chargeprod == 0))
+        pad_idx[b, :k], pad_mask[b, :k] = np.arange(o, o + k), 1.0
+        o += k
+    t = lambda a: torch.from_numpy(a).to(device)      # noqa: E731
+    return {"sij": t(sij), "e4": t(e4), "kqq": t(kqq), "mask": t(mask)}, t(pad_idx), t(pad_mask)
+
+
+def time_events(fn, seconds):
+    """median and minimum over device-event timings of single calls, after warm-up, for about `seconds` of device time"""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(), fn(), b.record()
+    torch.cuda.synchronize()
+    reps = int(min(max(seconds * 1e3 / max(a.elapsed_time(b), 1e-3), 5), 2000))
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s, e in ev:
+        s.record()
+        fn()
+        e.record()
+    torch.cuda.synchronize()
+    us = np.array([s.elapsed_time(e) * 1e3 for s, e in ev])
+    return float(np.median(us)), float(us.min()), reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--mols", type=int, default=256)
+    ap.add_argument("--confs", type=int, default=32)
+    ap.add_argument("--chain-atoms", type=int, default=50046)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("nonbonded_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    import datetime
+    prop = torch.cuda.get_device_properties(0)
+    be = get_backend()
+    # (the marketing name comes from the driver's id table and may be a generic one; the architecture and the CU count identify the chip)
+    lines = [f"# command: python {' '.join(sys.argv)}",
+             f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}",
+             f"# device: {prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, {prop.total_memory / 2 ** 30:.0f} GiB; "
+             f"library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}",
+             "# device events around single calls, median (min) after warm-up; this file is the tool's output, unedited"]
+    print("\n".join(lines), flush=True)
+
+    def report(name, what, pairs, med, mn, reps):
+        rate = pairs / (med * 1e-6)
+        lines.append(f"{name:6s} {what:18s} {med:12.1f} us (min {mn:10.1f}, {reps:4d} calls)  {rate:10.3e} pair interactions/s  "
+                     f"{100 * rate * FLOP_PER_PAIR / PEAK_FP32_VECTOR:5.1f} % of {PEAK_FP32_VECTOR / 1e12:.1f} TFLOP/s at {FLOP_PER_PAIR} flop/pair")
+        print(lines[-1], flush=True)
+        return rate
+
+    for name, (params, xyz) in (("pool", pool_batch(args.mols, args.confs)), ("chain", chain(args.chain_atoms))):
+        nb = NonbondedBatch(params).to("cuda")
+        x = torch.from_numpy(xyz).to("cuda")
+        n = np.array([p.n_atoms for p in params], dtype=np.float64)
+        pairs = float((n * (n - 1)).sum() * x.shape[1])
+        lines.append(f"{name}: {len(params)} molecules, {int(n.sum())} atoms ({int(n.min())}..{int(n.max())} per molecule), C = {x.shape[1]}, "
+                     f"{nb.n_exceptions} exceptions, {pairs:.4g} pair interactions per call")
+        print(lines[-1], flush=True)
+        # the kernel alone: HipBackend.nonbonded into preallocated outputs, work-item list built once on the host (two launches) ...
+        e_o, t_o, g_o = torch.empty(nb.B, x.shape[1], device="cuda"), torch.empty(2, nb.B, x.shape[1], device="cuda"), torch.empty_like(x)
+        tabs = (x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps)
+        plan = be.nonbonded_plan(nb.atom_molptr.cpu(), nb.N, x.shape[1], "cuda")
+        k_rate = report(name, "kernel", pairs, *time_events(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan), args.seconds))
+        # ... the same call without the gradient output, with the list built on the device by every call (three launches, upper-bound
+        # grid), and NonbondedBatch.evaluate, which also allocates and zeroes its three outputs
+        report(name, "kernel, grad=NULL", pairs, *time_events(lambda: be.nonbonded(*tabs, e_o, t_o, None, plan=plan), args.seconds))
+        report(name, "device-built list", pairs, *time_events(lambda: be.nonbonded(*tabs, e_o, t_o, g_o), args.seconds))
+        report(name, "evaluate()", pairs, *time_events(lambda: nb.evaluate(x, terms=True), args.seconds))
+        if name == "pool":
+            dtabs, pad_idx, pad_mask = dense_tables(params, "cuda")
+            e, g = nb.evaluate(x)
+            te, tg = torch_broadcast(dtabs, pad_idx, pad_mask, x)
+            ptr = nb.atom_molptr.tolist()
+            tg_flat = torch.cat([tg[b, :ptr[b + 1] - ptr[b]] for b in range(nb.B)])
+            lines.append(f"pool   agreement with the torch broadcast: energy {float((e - te).abs().max() / te.abs().max()):.2e}, "
+                         f"gradient {float((g - tg_flat).abs().max() / tg_flat.abs().max()):.2e} (largest difference / largest magnitude)")
+            print(lines[-1], flush=True)
+            t_rate = report(name, "torch broadcast", pairs, *time_events(lambda: torch_broadcast(dtabs, pad_idx, pad_mask, x), args.seconds))
+            lines.append(f"pool   kernel / torch broadcast = {k_rate / t_rate:.1f}x")
+            print(lines[-1], flush=True)
+            del dtabs, te, tg
+            torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
