@@ -685,6 +685,8 @@ int grappa_writer_head_fwd(void* stream, const grappa_writer_layer_desc* d);
  *     dz2 = mask2(dout);  dz1 = (dz2 W_2) * ELU'(u);  dx3 = dz1 W_1 + dout;  dx2 = LN'(dx3; x2, nf);  dzo = mask1(dx2);  datt = dzo W_o;
  *     dqkv = attention'(qkv, datt);  dx1 = dqkv W_in + dx2;  dx = LN'(dx1; x, n1)
  * (the derivative of models/network_utils.py:112-133 with :44-54; mask1 / mask2: the forward's dropout masks, regenerated from seed1 / seed2).
+ * Rounded to bf16 where the unfused kernels store a tensor: the five outputs dz2, dz1, dzo, dqkv, dx AND the intermediates dx3, dx2, datt, dx1,
+ * which the unfused sequence writes to memory and this kernel keeps in registers / LDS (the LayerNorm partials sum the rounded dx3 / dx1).
  * The four weight (and bias) gradients are ordinary grouped weight-gradient products (grappa_gemm_f32_grouped) over the operands this kernel
  * writes as by-products -- dz2, dz1, dzo (s*T, F), dqkv (s*T, 3F) -- and the activations the forward saved (u, x3, att, x1).  LayerNorm parameter
  * gradients: per-tile partial sums, ln*_part[tile][0][F] = dgamma, [tile][1][F] = dbeta, grappa_writer_head_tiles(s, T) tiles (the layout
