@@ -84,6 +84,12 @@ class NbDesc(C.Structure):
                 ("exc_qq", C.c_void_p), ("exc_sigma", C.c_void_p), ("exc_eps", C.c_void_p)]
 
 
+class RelaxOpts(C.Structure):
+    """grappa_relax_opts (additions to ABI 11): the options of the fused FIRE minimiser, per call"""
+    _fields_ = [("tolerance", C.c_float), ("max_steps", C.c_int), ("dt_start", C.c_float), ("dt_max", C.c_float), ("max_disp", C.c_float),
+                ("n_min", C.c_int), ("f_inc", C.c_float), ("f_dec", C.c_float), ("alpha_start", C.c_float), ("f_alpha", C.c_float)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -200,6 +206,9 @@ SIGNATURES = {
     "grappa_nonbonded_fwd_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _vp, _vp, _vp, _sz]),
     "grappa_nonbonded_plan": (C.c_longlong, [_i, _i, _i, _vp, _vp, C.c_longlong]),
     "grappa_nonbonded_fwd_planned_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    # relaxation under the full force field (additions to ABI 11)
+    "grappa_relax_max_atoms": (_i, []),
+    "grappa_relax_fire_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -258,3 +267,8 @@ def load():
 def nonbonded_iblock() -> int:
     """i-atoms per workgroup of the nonbonded kernel (GRAPPA_NB_IBLOCK of the loaded library): its tests put molecule sizes around it"""
     return int(load().grappa_nonbonded_iblock())
+
+
+def relax_max_atoms() -> int:
+    """atoms per molecule the fused minimiser takes at most (grappa_relax_max_atoms of the loaded library)"""
+    return int(load().grappa_relax_max_atoms())

@@ -1919,6 +1919,76 @@ class HipBackend:
         _chk(self.lib.grappa_nonbonded_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()),
              "grappa_nonbonded_fwd_f32")
 
+    # ------------------------------------------------------------------ relaxation
+    def relax_max_atoms(self) -> int:
+        return int(self.lib.grappa_relax_max_atoms())
+
+    def relax_fire(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
+                   atom_counts_host=None) -> None:
+        """the fused FIRE minimiser (include/grappa_hip.h grappa_relax_fire_f32): one launch relaxes every (molecule, conformation) of
+        the batch under the bonded terms (plan, ks, eqs, n_per, offset_torsion as for mm_energy_fwd; xyz (N,C,3) is the start) plus,
+        if nb is not None, Lennard-Jones + Coulomb (nb: the device tables of a NonbondedBatch: atom_molptr, charge, sigma, epsilon,
+        exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps).  opts: the ten fields of grappa_relax_opts by name, all of them.
+        -> xyz_out (N,C,3), energy / gmax (B,C) float32, steps / status (B,C) int32; term_energy (6,B,C) and grad (N,C,3) or None.
+        status: 0 = max_steps reached, 1 = converged, 2 = non-finite gradient, 3 = above relax_max_atoms() (nothing else written).
+        atom_counts_host: atoms per molecule as the caller knows them on the host; with it a molecule above the limit raises here,
+        before the launch and without a device sync (without it such a molecule comes back with status 3)."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"relax_fire: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        N, Cc, B = d.N, d.C, d.B
+        for t, n, dt in ((xyz_out, "xyz_out", torch.float32), (energy, "energy", torch.float32), (gmax, "gmax", torch.float32),
+                         (steps, "steps", torch.int32), (status, "status", torch.int32), (term_energy, "term_energy", torch.float32),
+                         (grad, "grad", torch.float32)):
+            if t is None and n in ("term_energy", "grad"):
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
+            _flat(t, n, dev, dt)
+        if xyz_out.shape != xyz.shape or (grad is not None and grad.shape != xyz.shape) or any(t.numel() != B * Cc for t in (energy, gmax, steps, status)) \
+                or (term_energy is not None and term_energy.numel() != 6 * B * Cc):
+            raise ValueError("relax_fire: expected xyz_out / grad (N,C,3), energy / gmax / steps / status (B,C), term_energy (6,B,C)")
+        if xyz_out.data_ptr() == xyz.data_ptr() and xyz.numel():
+            raise ValueError("relax_fire: xyz_out must not be the start coordinates")
+        if atom_counts_host is not None:
+            counts = [int(c) for c in atom_counts_host]
+            if len(counts) != B or sum(counts) != N:
+                raise ValueError(f"relax_fire: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
+            if counts and max(counts) > self.relax_max_atoms():
+                raise ValueError(f"relax_fire: a molecule of {max(counts)} atoms is above the limit of {self.relax_max_atoms()} atoms per molecule")
+        nd = None
+        if nb is not None:
+            for n in ("atom_molptr", "exc_ptr", "exc_atom"):
+                t = getattr(nb, n)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
+                _flat(t, "nb." + n, dev, torch.int32)
+            for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
+                t = getattr(nb, n)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
+                _flat(t, "nb." + n, dev)
+            if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
+                raise ValueError(f"relax_fire: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
+            if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
+                raise ValueError("relax_fire: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+            nd = _lib.NbDesc()
+            nd.N, nd.C, nd.B = N, Cc, B
+            nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
+            nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
+            nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
+            nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
+        o = _lib.RelaxOpts()
+        names = [f[0] for f in _lib.RelaxOpts._fields_]
+        if sorted(opts) != sorted(names):
+            raise ValueError(f"relax_fire: opts must hold exactly {names}, got {sorted(opts)}")
+        for k in names:
+            setattr(o, k, int(opts[k]) if k in ("max_steps", "n_min") else float(opts[k]))
+        _chk(self.lib.grappa_relax_fire_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), xyz_out.data_ptr(),
+                                            energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
+             "grappa_relax_fire_f32")
+
     # ------------------------------------------------------------------ loss
     def loss_ef(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B, loss_mol, gE, gG) -> None:
         dev = loss_mol.device

@@ -278,6 +278,10 @@ class MolBatch:
     def batch_num_nodes(self, ntype: str) -> torch.Tensor:
         return torch.from_numpy(self._bnn[ntype].copy()).to(self.device)
 
+    def batch_num_nodes_host(self, ntype: str) -> np.ndarray:
+        """the same counts as a host array (a copy): no transfer, so reading them never waits for the device"""
+        return self._bnn[ntype].copy()
+
     @property
     def batch_size(self) -> int:
         return len(self._bnn["g"])

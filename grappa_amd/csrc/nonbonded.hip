@@ -20,6 +20,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "nb_pair.h"
 
 namespace {
 
@@ -28,7 +29,6 @@ constexpr int NB_TJ = 64;                   // j-atoms per LDS block
 constexpr int NB_NT = 256;                  // threads per workgroup
 constexpr int NB_CW = 16;                   // conformations per work item at most (LDS: NB_TJ * NB_CW float4)
 constexpr int NB_JS = 16;                   // j slices at most
-constexpr float NB_K = (float)(138.93545764438198 * 10.0 / 4.184);      // kcal A / (mol e^2): OpenMM's ONE_4PI_EPS0
 
 // conformations of a block of ni i-atoms are dealt out in nchunks work items of at most ncb
 __host__ __device__ inline void nb_chunks(int ni, int C, int& nchunks, int& ncb) {
@@ -98,26 +98,6 @@ struct NbArgs {
     float* grad;
     int max_blk;       // rows of `part`
 };
-
-// one pair: d = x_i - x_j, sij / e4 / kqq = sigma, 4 eps, K q_i q_j of the pair.  v_rsq_f32 is good to 1 ulp and the twelfth power
-// multiplies that by 12: one Newton step brings 1/r to half an ulp.
-__device__ __forceinline__ void nb_pair(float dx, float dy, float dz, float sij, float e4, float kqq, float& elj, float& ec, float& gx,
-                                        float& gy, float& gz) {
-    const float r2 = dx * dx + dy * dy + dz * dz;
-    float y = __builtin_amdgcn_rsqf(r2);
-    y = __builtin_fmaf(0.5f * y, __builtin_fmaf(-r2 * y, y, 1.0f), y);
-    const float y2 = y * y;
-    const float sr2 = sij * sij * y2;
-    const float sr6 = sr2 * sr2 * sr2;
-    const float l6 = e4 * sr6, l12 = l6 * sr6;
-    const float c = kqq * y;
-    elj += l12 - l6;
-    ec += c;
-    const float f = (6.0f * l6 - 12.0f * l12 - c) * y2;      // (dE/dr) / r
-    gx = __builtin_fmaf(f, dx, gx);
-    gy = __builtin_fmaf(f, dy, gy);
-    gz = __builtin_fmaf(f, dz, gz);
-}
 
 __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
     __shared__ float4 xs[NB_TJ * NB_CW];      // j coordinates: [jj][conformation of the item]

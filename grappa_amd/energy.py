@@ -17,6 +17,33 @@ from . import ops
 from .constants import TUPLE_LEVELS
 
 
+def mm_tables(g, plan, terms, suffix: str, dev):
+    """the force-field tables of a parametrised graph as the MM kernels read them: k per level ((T,) bonds / angles, (T, n_per) torsions),
+    eq per level (None for torsions) and n_per; a level that is not in `terms` gets zero force constants"""
+    ks, eqs, n_per = [], [], [0, 0, 1, 1]
+    for l, term in enumerate(TUPLE_LEVELS):
+        T = plan.T[term]
+        d = g.nodes[term].data
+        if term in terms:
+            if term not in g.ntypes:
+                raise ValueError(f"term {term} not in g.ntypes")
+            if "k" + suffix not in d:
+                raise RuntimeError(f"{term} has no k{suffix} attribute")
+            k = d["k" + suffix].float()
+            if l < 2 and k.dim() != 1:
+                raise ValueError(f"k must be a 1d tensor, but has shape {k.shape}")
+            eq = d["eq" + suffix].float() if l < 2 else None
+        else:       # term switched off: zero force constants
+            k = torch.zeros((T,) if l < 2 else (T, 1), dtype=torch.float32, device=dev)
+            eq = torch.zeros((T,), dtype=torch.float32, device=dev) if l < 2 else None
+        if l >= 2:
+            k = k.reshape(T, -1) if T else k.reshape(0, max(k.shape[-1] if k.dim() == 2 else 1, 1))
+            n_per[l] = max(int(k.shape[1]), 1)
+        ks.append(k)
+        eqs.append(eq)
+    return ks, eqs, n_per
+
+
 class Energy(torch.nn.Module):
     def __init__(self, terms: list = ["n2", "n3", "n4", "n4_improper"], suffix: str = "", offset_torsion: bool = False,
                  write_suffix=None, gradients: bool = True):
@@ -40,27 +67,7 @@ class Energy(torch.nn.Module):
         plan = g.plan()
         dev = xyz.device
         Cc = xyz.shape[1]
-        ks, eqs, n_per = [], [], [0, 0, 1, 1]
-        for l, term in enumerate(TUPLE_LEVELS):
-            T = plan.T[term]
-            d = g.nodes[term].data
-            if term in self.terms:
-                if term not in g.ntypes:
-                    raise ValueError(f"term {term} not in g.ntypes")
-                if "k" + self.suffix not in d:
-                    raise RuntimeError(f"{term} has no k{self.suffix} attribute")
-                k = d["k" + self.suffix].float()
-                if l < 2 and k.dim() != 1:
-                    raise ValueError(f"k must be a 1d tensor, but has shape {k.shape}")
-                eq = d["eq" + self.suffix].float() if l < 2 else None
-            else:       # term switched off: zero force constants
-                k = torch.zeros((T,) if l < 2 else (T, 1), dtype=torch.float32, device=dev)
-                eq = torch.zeros((T,), dtype=torch.float32, device=dev) if l < 2 else None
-            if l >= 2:
-                k = k.reshape(T, -1) if T else k.reshape(0, max(k.shape[-1] if k.dim() == 2 else 1, 1))
-                n_per[l] = max(int(k.shape[1]), 1)
-            ks.append(k)
-            eqs.append(eq)
+        ks, eqs, n_per = mm_tables(g, plan, self.terms, self.suffix, dev)
         te = [torch.empty((plan.T[t], Cc), dtype=torch.float32, device=dev) for t in TUPLE_LEVELS]
         tx = [torch.empty((plan.T[t], Cc), dtype=torch.float32, device=dev) for t in TUPLE_LEVELS]
         energy, terms, grad = ops.MMEnergyFn.apply(xyz, plan, n_per, bool(self.offset_torsion), bool(self.gradients), (te, tx),

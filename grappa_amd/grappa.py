@@ -55,3 +55,9 @@ class Grappa:
             g = self.model(g)
         g = g.to("cpu")
         return Parameters.from_dgl(g)
+
+    def relax(self, molecule: Molecule, xyz, nonbonded=None, **opts):
+        """`predict` followed by `grappa_amd.relax.relax`: the conformations xyz (n_confs, n_atoms, 3) of `molecule` minimised on the
+        device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in the molecule's atom order) -> RelaxResult"""
+        from .relax import relax
+        return relax(self.predict(molecule), xyz, nonbonded, device=self.device, **opts)

@@ -148,6 +148,11 @@ class NonbondedBatch:
         self._molptr_host = self.atom_molptr          # stays on the host: the kernel's work-item lists are built from it
         self._plans = {}                              # C -> HipBackend.nonbonded_plan(...), on the batch's device
 
+    @property
+    def atom_molptr_host(self) -> torch.Tensor:
+        """atom_molptr as the int32 host tensor the batch was built with, wherever `.to` has put the tables"""
+        return self._molptr_host
+
     def to(self, device) -> "NonbondedBatch":
         for k in self._TENSORS:
             setattr(self, k, getattr(self, k).to(device))

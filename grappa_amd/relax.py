@@ -1,0 +1,183 @@
+"""Relaxation (energy minimisation) of molecules on the device under the full MM force field: the bonded terms Grappa predicts plus,
+optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`).  The reference hands this step to OpenMM / GROMACS; here one launch of
+csrc/relax.hip (`grappa_relax_fire_f32` through `HipBackend.relax_fire`) runs the whole minimisation of every (molecule, conformation):
+one workgroup each, coordinates in LDS, no host round trip per step.
+
+The minimiser is FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201 (2006)) with unit masses and semi-implicit Euler; the loop is stated
+in include/grappa_hip.h.  Units: Angstrom, kcal/mol, kcal/mol/A.  An item stops with a status:
+    0  max_steps reached        1  converged: the largest atomic gradient norm <= tolerance
+    2  non-finite gradient (for example two non-excluded atoms on one point): stopped at once, the coordinates are those it held
+    3  the molecule has more than `relax_max_atoms()` atoms: not run
+The defaults (`RELAX_DEFAULTS`; tolerance = 10 kJ/mol/nm, OpenMM's `minimizeEnergy` default) were checked on small chain molecules only
+and are not tuned.  Molecules above `relax_max_atoms()` atoms are refused: a stepwise path for them is out of scope.
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .constants import TUPLE_LEVELS
+from .energy import mm_tables
+from .nonbonded import NonbondedBatch, NonbondedParameters
+from .parameters import Parameters
+
+RELAX_DEFAULTS = {"tolerance": 10.0 / 4.184 / 10.0, "max_steps": 1000, "dt_start": 0.002, "dt_max": 0.02, "max_disp": 0.1, "n_min": 5,
+                  "f_inc": 1.1, "f_dec": 0.5, "alpha_start": 0.1, "f_alpha": 0.99}
+MAX_STEPS_CAP = 1000000
+
+
+def relax_max_atoms() -> int:
+    """atoms per molecule the fused minimiser takes at most"""
+    from . import _lib
+    return _lib.relax_max_atoms()
+
+
+def relax_options(**opts) -> dict:
+    """the ten options of a call: RELAX_DEFAULTS overridden by `opts`, checked (the library checks them again)"""
+    unknown = sorted(set(opts) - set(RELAX_DEFAULTS))
+    if unknown:
+        raise TypeError(f"unknown relaxation option(s) {unknown}; the options are {sorted(RELAX_DEFAULTS)}")
+    o = {**RELAX_DEFAULTS, **opts}
+    for k in ("max_steps", "n_min"):
+        if int(o[k]) != o[k] or o[k] < 0:
+            raise ValueError(f"{k} must be a non-negative integer, got {o[k]}")
+        o[k] = int(o[k])
+    if o["max_steps"] > MAX_STEPS_CAP:
+        raise ValueError(f"max_steps must not exceed {MAX_STEPS_CAP}, got {o['max_steps']}")
+    for k in ("dt_start", "dt_max", "max_disp", "f_inc", "f_dec", "f_alpha"):
+        if not (np.isfinite(o[k]) and o[k] > 0):
+            raise ValueError(f"{k} must be positive and finite, got {o[k]}")
+    if not (np.isfinite(o["tolerance"]) and o["tolerance"] >= 0):
+        raise ValueError(f"tolerance must be non-negative and finite, got {o['tolerance']}")
+    if not 0 <= o["alpha_start"] <= 1:
+        raise ValueError(f"alpha_start must lie in [0, 1], got {o['alpha_start']}")
+    return o
+
+
+@dataclass
+class RelaxResult:
+    """xyz: the relaxed coordinates; energy: the total energy there; gradient_max: the largest atomic gradient norm there; steps;
+    status (see the module text).  From `relax_graph`: tensors on the graph's device, xyz (N, C, 3), the others (B, C).  From `relax`:
+    numpy arrays of one molecule, xyz (n_confs, n_atoms, 3), the others (n_confs,)."""
+    xyz: object
+    energy: object
+    gradient_max: object
+    steps: object
+    status: object
+
+    @property
+    def converged(self):
+        return self.status == 1
+
+
+def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
+                offset_torsion: bool = False, **opts) -> RelaxResult:
+    """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
+    exactly what `Energy` reads, through the same plan.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded
+    terms only).  **opts: see RELAX_DEFAULTS.  One launch, no host sync; the graph is not modified."""
+    from .backend import get_backend
+    o = relax_options(**opts)
+    terms = list(terms)
+    for t in terms:
+        if t not in TUPLE_LEVELS:
+            raise ValueError(f"term {t} not in {TUPLE_LEVELS}")
+    n1 = g.nodes["n1"].data
+    if "xyz" not in n1:
+        raise ValueError("xyz coordinates must be stored in g.nodes['n1'].data['xyz']")
+    xyz = n1["xyz"].detach()
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (N, C, 3), got {tuple(xyz.shape)}")
+    xyz = xyz.float().contiguous()
+    dev = xyz.device
+    plan = g.plan()
+    counts = [int(c) for c in g.batch_num_nodes_host("n1")]          # (host numbers: no device sync)
+    limit = get_backend().relax_max_atoms()
+    if counts and max(counts) > limit:
+        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule "
+                         f"(larger molecules are out of scope of the fused minimiser)")
+    if nonbonded is not None:
+        if not isinstance(nonbonded, NonbondedBatch):
+            raise TypeError(f"nonbonded must be a NonbondedBatch or None, got {type(nonbonded).__name__}")
+        if nonbonded.N != plan.N or nonbonded.B != plan.B or nonbonded.atom_molptr_host.tolist() != np.concatenate([[0], np.cumsum(counts)]).tolist():
+            raise ValueError(f"the nonbonded batch ({nonbonded.B} molecules, {nonbonded.N} atoms) does not describe the graph's molecules "
+                             f"({plan.B} molecules, {plan.N} atoms)")
+        if nonbonded.charge.device != dev:
+            raise ValueError(f"the nonbonded batch is on {nonbonded.charge.device}, the graph on {dev}")
+    ks, eqs, n_per = mm_tables(g, plan, terms, suffix, dev)
+    ks = [k.detach().contiguous() for k in ks]
+    eqs = [None if q is None else q.detach().contiguous() for q in eqs]
+    B, C = plan.B, xyz.shape[1]
+    out = torch.empty_like(xyz)
+    energy, gmax = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(B, C, dtype=torch.float32, device=dev)
+    steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
+    get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
+                             atom_counts_host=counts)
+    return RelaxResult(out, energy, gmax, steps, status)
+
+
+def graph_from_parameters(parameters: Parameters, xyz):
+    """one molecule's `Parameters` (atom-id space, torsions as magnitude and phase) and its conformations (n_confs, n_atoms, 3) -> the
+    parametrised single-molecule graph `relax_graph` and `Energy` read: atom ids mapped to indices, signed torsion constants rebuilt
+    (phase pi = a negative constant)"""
+    from .batch import single_graph
+    atoms = np.asarray(parameters.atoms).reshape(-1)
+    n = atoms.shape[0]
+    if np.unique(atoms).shape[0] != n:
+        raise ValueError("Parameters.atoms holds an atom id twice")
+    x = np.asarray(xyz)
+    if x.ndim != 3 or x.shape[1:] != (n, 3):
+        raise ValueError(f"xyz must be (n_confs, {n}, 3), got {x.shape}")
+    order = np.argsort(atoms, kind="stable")
+
+    def index_of(ids, arity, name):
+        ids = np.asarray(ids if ids is not None else np.zeros((0, arity)), dtype=np.int64).reshape(-1, arity)
+        pos = np.searchsorted(atoms[order], ids)
+        if ids.size and (pos.max() >= n or not np.array_equal(atoms[order][np.minimum(pos, n - 1)], ids)):
+            raise ValueError(f"Parameters.{name} names an atom id that is not in Parameters.atoms")
+        return order[pos].reshape(-1, arity)
+
+    idxs = {"n2": index_of(parameters.bonds, 2, "bonds"), "n3": index_of(parameters.angles, 3, "angles"),
+            "n4": index_of(parameters.propers, 4, "propers"), "n4_improper": index_of(parameters.impropers, 4, "impropers")}
+    f32 = lambda a, shape: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape)))      # noqa: E731
+
+    def signed(ks, phases, T, name):
+        if ks is None or phases is None:
+            ks, phases = np.zeros((T, 1)), np.zeros((T, 1))
+        ks, phases = np.asarray(ks, dtype=np.float64), np.asarray(phases, dtype=np.float64)
+        if ks.shape != phases.shape or ks.shape[0] != T:
+            raise ValueError(f"Parameters.{name}_ks {ks.shape} and {name}_phases {phases.shape} must share a shape with {T} rows")
+        ks = ks.reshape(T, -1) if T else ks.reshape(0, max(ks.shape[-1] if ks.ndim == 2 else 1, 1))
+        return f32(np.where(np.cos(phases.reshape(ks.shape)) >= 0, ks, -ks), ks.shape)
+
+    for (lvl, name) in (("n2", "bond"), ("n3", "angle")):
+        T = idxs[lvl].shape[0]
+        for key in ("k", "eq"):
+            if np.asarray(getattr(parameters, f"{name}_{key}")).reshape(-1).shape[0] != T:
+                raise ValueError(f"Parameters.{name}_{key} must hold {T} values")
+    g = single_graph(n, idxs["n2"], idxs, {"xyz": f32(x.transpose(1, 0, 2), (n, x.shape[0], 3))}, ids=atoms)
+    for lvl, name in (("n2", "bond"), ("n3", "angle")):
+        T = idxs[lvl].shape[0]
+        g.nodes[lvl].data["k"] = f32(getattr(parameters, name + "_k"), (T,))
+        g.nodes[lvl].data["eq"] = f32(getattr(parameters, name + "_eq"), (T,))
+    for lvl, name in (("n4", "proper"), ("n4_improper", "improper")):
+        g.nodes[lvl].data["k"] = signed(getattr(parameters, name + "_ks"), getattr(parameters, name + "_phases"), idxs[lvl].shape[0], name)
+    return g
+
+
+def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", **opts) -> RelaxResult:
+    """Relax the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`, whose atoms are in the
+    order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom -> RelaxResult with xyz of the same shape
+    (float64) and energy / gradient_max / steps / status of shape (n_confs,)."""
+    relax_options(**opts)
+    g = graph_from_parameters(parameters, xyz)
+    nb = None
+    if nonbonded is not None:
+        if not isinstance(nonbonded, NonbondedParameters):
+            raise TypeError(f"nonbonded must be NonbondedParameters or None, got {type(nonbonded).__name__}")
+        if nonbonded.n_atoms != g.num_nodes("n1"):
+            raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {g.num_nodes('n1')}")
+        nb = NonbondedBatch([nonbonded]).to(device)
+    r = relax_graph(g.to(device), nb, **opts)
+    return RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
+                       r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])

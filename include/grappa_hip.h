@@ -500,6 +500,37 @@ int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_desc* d, cons
                                      float* term_energy, float* grad, void* ws, size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Relaxation under the full MM force field (additions to ABI 11): FIRE (Bitzek et al. 2006) with unit masses and semi-implicit Euler,
+ * one workgroup per (molecule b, conformation c), the whole minimisation in one launch.  E = the bonded energy of
+ * grappa_mm_energy_fwd_f32 (+ the energy of grappa_nonbonded_fwd_f32 if nb != NULL; nb->xyz is ignored), g = +dE/dxyz, start = mm->xyz:
+ *   x = start; v = 0; h = dt_start; a = alpha_start; npos = 0; steps = 0; g = grad E(x)
+ *   loop: gmax = max_i |g_i|_2;  not finite: status 2, stop;  gmax <= tolerance: status 1, stop;  steps == max_steps: status 0, stop
+ *         F = -g; P = sum F.v; Fn = |F|; vn = |v|
+ *         P > 0: v = (1-a) v + a (vn/Fn) F; then, if npos >= n_min: h = min(h f_inc, dt_max), a = a f_alpha;  npos += 1
+ *         else : v = 0; h = h f_dec; a = alpha_start; npos = 0
+ *         v += h F; d = h v; s = min(1, max_disp / max_i |d_i|_2) (1 if that maximum is 0); x += s d; v = s v; steps += 1; g = grad E(x)
+ * Outputs per item: xyz_out[N,C,3] (the coordinates held when the item stopped), energy[B,C] (total, at xyz_out), gmax[B,C] (inf for
+ * status 2), steps[B,C], status[B,C]; optional (NULL: not written) grad[N,C,3] at xyz_out and term_energy[6,B,C] = bonds, angles,
+ * propers, impropers, Lennard-Jones, Coulomb.  A molecule without atoms writes nothing; a single atom stops at step 0 with status 1 and
+ * xyz_out bit-equal to its input.  A molecule of more than grappa_relax_max_atoms() atoms gets status 3 and NOTHING else is written for
+ * it (the limit is checked by the kernel on atom_molptr, which is device memory; a caller with a host copy refuses before the launch,
+ * as HipBackend.relax_fire does).  Fixed-order sums, no atomics, no communication between workgroups: same input, same bits, and an
+ * item's results depend neither on its place in the batch nor on how long its neighbours run.  max_steps bounds the loop.
+ * GRAPPA_ERR_ARG: a NULL required pointer or a negative size; nb disagreeing with mm in N, C or B; B * C >= 2^31; dt_start, dt_max,
+ * max_disp, f_inc, f_dec or f_alpha not positive and finite; alpha_start outside [0, 1]; tolerance negative or not finite; n_min < 0;
+ * max_steps < 0 or > 1,000,000.  N == 0, C == 0 or B == 0: returns 0 without a launch. */
+typedef struct grappa_relax_opts {
+    float tolerance;             /* kcal/mol/A, on the largest atomic gradient norm */
+    int   max_steps;
+    float dt_start, dt_max, max_disp;      /* max_disp: Angstrom, the largest displacement of an atom in one step */
+    int   n_min;
+    float f_inc, f_dec, alpha_start, f_alpha;
+} grappa_relax_opts;
+int grappa_relax_max_atoms(void);        /* atoms per molecule at most (>= 512) */
+int grappa_relax_fire_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o, float* xyz_out,
+                          float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status);
+
+/* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:
  *  l_m = wE*mean_c((E-<E>)-(Eref-<Eref>))^2 + wG*mean_{a,c,xyz}(G-Gref)^2   over real conformations
  *  loss_mol[b] = l_m ; gE = d(sum_m l_m * inv_B)/dE ; gG likewise.  is_dummy may be NULL. */
