@@ -209,6 +209,12 @@ SIGNATURES = {
     # relaxation under the full force field (additions to ABI 11)
     "grappa_relax_max_atoms": (_i, []),
     "grappa_relax_fire_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise minimiser for molecules of any size (additions to ABI 11)
+    "grappa_relax_steps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "grappa_relax_steps_init_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz, _vp]),
+    "grappa_relax_steps_run_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz, _i, _vp]),
+    "grappa_relax_steps_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1989,6 +1989,97 @@ class HipBackend:
                                             energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
              "grappa_relax_fire_f32")
 
+    def relax_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
+                    atom_counts_host=None, check_every: int = 32, workspace=None) -> None:
+        """the stepwise FIRE minimiser for molecules of any size (include/grappa_hip.h grappa_relax_steps_*_f32): the loop, the
+        arguments and the outputs of `relax_fire`, but a molecule spans many workgroups, the state lives in device memory and a step
+        is four launches.  atom_counts_host (required): atoms per molecule on the host; the work-item table is the nonbonded plan
+        built from it (reused from nb's cache of plans where nb keeps one).  check_every: steps enqueued between two looks at the
+        device's count of running items.  The host SYNCS with the device once per chunk (one `.item()`), never per step; the loop
+        ends when no item runs or max_steps steps are enqueued.  Status 3 does not occur.  workspace: a uint8 tensor of at least
+        `grappa_relax_steps_workspace_bytes` to use instead of the backend's own."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"relax_steps: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
+        if isinstance(check_every, bool) or int(check_every) != check_every or check_every < 1:
+            raise ValueError(f"relax_steps: check_every must be an integer >= 1, got {check_every}")
+        check_every = int(check_every)
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        N, Cc, B = d.N, d.C, d.B
+        for t, n, dt in ((xyz_out, "xyz_out", torch.float32), (energy, "energy", torch.float32), (gmax, "gmax", torch.float32),
+                         (steps, "steps", torch.int32), (status, "status", torch.int32), (term_energy, "term_energy", torch.float32),
+                         (grad, "grad", torch.float32)):
+            if t is None and n in ("term_energy", "grad"):
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
+            _flat(t, n, dev, dt)
+        if xyz_out.shape != xyz.shape or (grad is not None and grad.shape != xyz.shape) or any(t.numel() != B * Cc for t in (energy, gmax, steps, status)) \
+                or (term_energy is not None and term_energy.numel() != 6 * B * Cc):
+            raise ValueError("relax_steps: expected xyz_out / grad (N,C,3), energy / gmax / steps / status (B,C), term_energy (6,B,C)")
+        if atom_counts_host is None:
+            raise ValueError("relax_steps: atom_counts_host is required (the work-item table is built from it)")
+        counts = [int(c) for c in atom_counts_host]
+        if len(counts) != B or sum(counts) != N or (counts and min(counts) < 0):
+            raise ValueError(f"relax_steps: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
+        nd = None
+        if nb is not None:
+            for n in ("atom_molptr", "exc_ptr", "exc_atom"):
+                t = getattr(nb, n)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
+                _flat(t, "nb." + n, dev, torch.int32)
+            for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
+                t = getattr(nb, n)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
+                _flat(t, "nb." + n, dev)
+            if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
+                raise ValueError(f"relax_steps: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
+            if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
+                raise ValueError("relax_steps: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+            nd = _lib.NbDesc()
+            nd.N, nd.C, nd.B = N, Cc, B
+            nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
+            nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
+            nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
+            nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
+        o = _lib.RelaxOpts()
+        names = [f[0] for f in _lib.RelaxOpts._fields_]
+        if sorted(opts) != sorted(names):
+            raise ValueError(f"relax_steps: opts must hold exactly {names}, got {sorted(opts)}")
+        for k in names:
+            setattr(o, k, int(opts[k]) if k in ("max_steps", "n_min") else float(opts[k]))
+        if N == 0 or Cc == 0 or B == 0:
+            return
+        # the work-item table: the nonbonded plan of these molecules for this C (it is about atoms: it also serves nb = None)
+        cache = getattr(nb, "_plans", None) if nb is not None else None
+        table = cache.get(Cc) if isinstance(cache, dict) else None
+        if table is None or table[0] is None or table[0].device != dev:
+            molptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64).cumsum(0)]).to(torch.int32)
+            table = self.nonbonded_plan(molptr, N, Cc, dev)
+            if isinstance(cache, dict) and nb.charge.device == dev:
+                cache[Cc] = table
+        table_dev, n_items, n_blocks, _ = table
+        need = int(self.lib.grappa_relax_steps_workspace_bytes(N, Cc, B, n_blocks))
+        if workspace is None:
+            workspace = self._workspace(need, dev, "relax_steps")
+        else:
+            _flat(workspace, "workspace", dev, torch.uint8)
+        n_running = torch.zeros(1, dtype=torch.int32, device=dev)
+        st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
+        common = (st, C.byref(d), ndp, C.byref(o), table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
+        _chk(self.lib.grappa_relax_steps_init_f32(*common, n_running.data_ptr()), "grappa_relax_steps_init_f32")
+        left = o.max_steps
+        while left > 0:
+            n = min(check_every, left)
+            _chk(self.lib.grappa_relax_steps_run_f32(*common, n, n_running.data_ptr()), "grappa_relax_steps_run_f32")
+            left -= n
+            if int(n_running.item()) <= 0:          # the one host sync per chunk
+                break
+        _chk(self.lib.grappa_relax_steps_finish_f32(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
+                                                    steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
+
     # ------------------------------------------------------------------ loss
     def loss_ef(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B, loss_mol, gE, gG) -> None:
         dev = loss_mol.device

@@ -21,24 +21,9 @@
 
 #include "common.h"
 #include "nb_pair.h"
+#include "nb_plan.h"      // NB_T, NB_TJ, NB_NT, NB_CW, NB_JS, nb_chunks, nb_clamp
 
 namespace {
-
-constexpr int NB_T = GRAPPA_NB_IBLOCK;      // i-atoms per work item
-constexpr int NB_TJ = 64;                   // j-atoms per LDS block
-constexpr int NB_NT = 256;                  // threads per workgroup
-constexpr int NB_CW = 16;                   // conformations per work item at most (LDS: NB_TJ * NB_CW float4)
-constexpr int NB_JS = 16;                   // j slices at most
-
-// conformations of a block of ni i-atoms are dealt out in nchunks work items of at most ncb
-__host__ __device__ inline void nb_chunks(int ni, int C, int& nchunks, int& ncb) {
-    int cpw = NB_NT / ni;
-    if (cpw > NB_CW) cpw = NB_CW;
-    nchunks = (C + cpw - 1) / cpw;
-    ncb = (C + nchunks - 1) / nchunks;
-}
-
-__device__ inline int nb_clamp(int v, int N) { return v < 0 ? 0 : (v > N ? N : v); }
 
 // ------------------------------------------------------------------------------------------------ setup
 // hdr[0] = number of work items; blk_ptr[b] = first i-block of molecule b (blocks number the rows of the partial energies);

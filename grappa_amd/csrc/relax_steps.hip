@@ -1,0 +1,657 @@
+// Stepwise FIRE minimiser for molecules of any size under the full MM force field, fp32 (include/grappa_hip.h
+// grappa_relax_steps_*_f32): the loop of csrc/relax.hip with a molecule spread over many workgroups and a step made of four launches.
+//   items  : the nonbonded plan's (csrc/nb_plan.h): (molecule, block of ni <= 64 i-atoms, nc conformations), one workgroup of 256 threads
+//            each; the plan is about atoms, so it also serves a call without nonbonded parameters.
+//   state  : in the caller's workspace: x, v, g [N,C,3]; per (molecule, conformation) h, a, npos, steps, status and the scalars of the
+//            step in flight (mix, keep, downhill, gmax); per (block, conformation) the partials P, |F|^2, |v|^2, max |g_i| (double) and
+//            max |d_i| (float).
+//   step   : decide  one workgroup of 64 threads per (molecule, conformation): adds the item's block partials in ascending block
+//                    order in double (as nb_reduce_kernel does), applies the loop's stop tests and FIRE's decisions and writes the item's
+//                    new scalars.  It is the ONLY writer of the per-item state, and it runs in a launch of its own: no workgroup
+//                    reads a scalar that a sibling writes in the same launch.
+//            vel     v = keep v + mix F + h F per atom, the block's max |h v_i|
+//            move    max over the item's blocks, s = min(1, max_disp / max), x += s h v, v = s v
+//            force   g at the new x: the bonded gather of mm_gradient_kernel (the thread's slice of the atom's incidences, neighbours
+//                    read from global memory) plus the j loop of nb_pairs_kernel (j-atoms through LDS in ascending blocks of 64, the
+//                    sorted exception row walked in step with j, an exception replaces the pair, an exclusion or j == i is skipped, no
+//                    pair energy kept), slices added in slice order; then the block's partials.
+//            Launch boundaries are the only synchronisation between workgroups: no cooperative launch, no flag, no float atomics.
+//            The one atomic is the integer decrement of the count of running items by the thread that stops an item.
+//   stopped: every launch leaves a (molecule, conformation) whose status is final alone, so the result depends neither on the number of
+//            steps enqueued after it stopped nor on the chunk size.
+//   finish : one more decide (stop tests only), the six energy terms by the library's own energy kernels (mm_energy_kernel,
+//            nb_pairs_kernel + nb_reduce_kernel through their entry points: no second energy code path) at the held coordinates, and a
+//            copy kernel.
+// Same input, same bits; a molecule's bits do not depend on its place in the batch.
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+#include "mm_geom.h"
+#include "nb_pair.h"
+#include "nb_plan.h"
+
+namespace {
+
+constexpr int RS_STEP_CAP = 1000000;
+constexpr int RS_DNT = 64;               // threads of a decide workgroup
+constexpr int RS_NW = NB_NT / GRAPPA_WAVE;
+constexpr int RS_RUNNING = -1;           // status in the workspace while an item runs
+
+struct RsState {                         // per (molecule, conformation): [B*C] each
+    float *h, *al, *mix, *keep, *gmax;
+    int *npos, *steps, *status, *downhill;
+};
+
+struct RsWs {
+    float *x, *v, *g;                    // [N,C,3]
+    RsState s;
+    double* part;                        // [n_blocks][C][4]: P, |F|^2, |v|^2, max |g_i| (inf: a non-finite gradient)
+    float* dpart;                        // [n_blocks][C]: max |h v_i|
+    float *e_mm, *e_nb, *terms;          // finish: [B,C], [B,C], [6,B,C]
+    double* nbpart;                      // finish: the nonbonded kernel's partial energies [n_blocks][C][2]
+    size_t total;
+};
+
+RsWs rs_layout(char* base, int N, int C, int B, int n_blocks) {
+    RsWs w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base + off;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
+    w.x = (float*)take(4 * n3), w.v = (float*)take(4 * n3), w.g = (float*)take(4 * n3);
+    w.s.h = (float*)take(4 * bc), w.s.al = (float*)take(4 * bc), w.s.mix = (float*)take(4 * bc), w.s.keep = (float*)take(4 * bc);
+    w.s.gmax = (float*)take(4 * bc);
+    w.s.npos = (int*)take(4 * bc), w.s.steps = (int*)take(4 * bc), w.s.status = (int*)take(4 * bc), w.s.downhill = (int*)take(4 * bc);
+    w.part = (double*)take(8 * 4 * kc);
+    w.dpart = (float*)take(4 * kc);
+    w.e_mm = (float*)take(4 * bc), w.e_nb = (float*)take(4 * bc), w.terms = (float*)take(4 * 6 * bc);
+    w.nbpart = (double*)take(8 * 2 * kc);
+    w.total = off;
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------ work items
+struct RsGeom {                          // what every per-block kernel needs of the batch
+    int N, C, B, n_blocks;
+    const int* atom_molptr;
+    const int* blk_ptr;                  // [B+1]
+    const int4* items;
+};
+
+struct RsItem {
+    int mol, i0, blk, c0, m0, m1, ni, nc;
+};
+
+// the workgroup's item, checked as nb_pairs_kernel checks it (a table made for another batch is walked away from, not followed)
+__device__ inline bool rs_item(const RsGeom& q, RsItem& r) {
+    const int4 it = q.items[blockIdx.x];
+    r.mol = it.x, r.i0 = it.y, r.blk = it.z, r.c0 = it.w;
+    if (r.mol < 0 || r.mol >= q.B || r.blk < 0 || r.blk >= q.n_blocks || r.c0 < 0 || r.c0 >= q.C) return false;
+    r.m0 = nb_clamp(q.atom_molptr[r.mol], q.N), r.m1 = nb_clamp(q.atom_molptr[r.mol + 1], q.N);
+    if (r.i0 < r.m0 || r.i0 >= r.m1) return false;
+    r.ni = r.m1 - r.i0 < NB_T ? r.m1 - r.i0 : NB_T;
+    int nch, ncb;
+    nb_chunks(r.ni, q.C, nch, ncb);
+    r.nc = q.C - r.c0 < ncb ? q.C - r.c0 : ncb;      // (ni * nc <= NB_NT and nc <= NB_CW by nb_chunks)
+    return true;
+}
+
+// which of the item's conformations still run -> run[0 .. nc); false if none does.  One barrier.
+__device__ inline bool rs_running(const RsItem& r, int C, const int* __restrict__ status, int* run) {
+    if ((int)threadIdx.x < r.nc) run[threadIdx.x] = status[(size_t)r.mol * C + r.c0 + threadIdx.x] == RS_RUNNING;
+    __syncthreads();
+    int any = 0;
+    for (int cc = 0; cc < r.nc; ++cc) any |= run[cc];
+    return any != 0;
+}
+
+// ------------------------------------------------------------------------------------------------ init
+struct RsInitArgs {
+    int N, C, B;
+    const int* atom_molptr;
+    const float* start;
+    float *x, *v;
+    RsState s;
+    float dt_start, alpha_start;
+    int* n_running;
+};
+
+__global__ __launch_bounds__(256) void rs_init_kernel(RsInitArgs a) {
+    __shared__ int cnt[256];
+    const int t = threadIdx.x;
+    const size_t gid = (size_t)blockIdx.x * 256 + t;
+    if (gid < (size_t)a.N * a.C * 3) {
+        a.x[gid] = a.start[gid];
+        a.v[gid] = 0.f;
+    }
+    if (gid < (size_t)a.B * a.C) {
+        const int b = (int)(gid / a.C);
+        const bool some = nb_clamp(a.atom_molptr[b + 1], a.N) > nb_clamp(a.atom_molptr[b], a.N);
+        a.s.h[gid] = a.dt_start, a.s.al[gid] = a.alpha_start, a.s.mix[gid] = 0.f, a.s.keep[gid] = 0.f, a.s.gmax[gid] = 0.f;
+        a.s.npos[gid] = 0, a.s.steps[gid] = 0, a.s.downhill[gid] = 0;
+        a.s.status[gid] = some ? RS_RUNNING : 0;      // a molecule without atoms never runs (and the finish writes nothing for it)
+    }
+    if (blockIdx.x == 0) {      // the count of running items: molecules with atoms, times C (integers: any order gives the same number)
+        int n = 0;
+        for (int b = t; b < a.B; b += 256) n += nb_clamp(a.atom_molptr[b + 1], a.N) > nb_clamp(a.atom_molptr[b], a.N) ? 1 : 0;
+        cnt[t] = n;
+        __syncthreads();
+        if (t == 0) {
+            long long sum = 0;
+            for (int k = 0; k < 256; ++k) sum += cnt[k];
+            a.n_running[0] = (int)(sum * a.C);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ force
+struct RsForceArgs {
+    grappa_mm_desc mm;       // tables only: mm.xyz is not read
+    grappa_nb_desc nb;       // tables only
+    int has_nb;
+    RsGeom q;
+    const float *x, *v;
+    float* g;
+    const int* status;
+    double* part;
+};
+
+__device__ inline V3 rs_ld(const float* __restrict__ x, int atom, int N, int C, int c) {      // (an index outside the batch reads atom 0)
+    return ldv(x, (unsigned)atom < (unsigned)N ? atom : 0, C, c);
+}
+
+// slice s of the bonded gradient of atom i in conformation c (the gather of mm_gradient_kernel / rx_bonded)
+__device__ inline V3 rs_bonded(const grappa_mm_desc& d, const float* __restrict__ x, int i, int s, int JS, int c) {
+    V3 g = {0.f, 0.f, 0.f};
+    const int N = d.N, C = d.C;
+    const int q0 = d.inc_ptr[i], q1 = d.inc_ptr[i + 1];
+    for (int q = q0 + s; q < q1; q += JS) {
+        const int code = d.inc_code[q];
+        const int pos = code & 3, l = (code >> 2) & 3, t = code >> 4;
+        if (l == 0) {
+            V3 u;
+            const float r = bond_geom(rs_ld(x, d.idx[0][2 * t], N, C, c), rs_ld(x, d.idx[0][2 * t + 1], N, C, c), u);
+            const float coef = d.k[0][t] * (r - d.eq[0][t]);
+            g = g + (pos == 0 ? coef : -coef) * u;
+        } else if (l == 1) {
+            V3 e0, e2;
+            const float th = angle_geom(rs_ld(x, d.idx[1][3 * t], N, C, c), rs_ld(x, d.idx[1][3 * t + 1], N, C, c),
+                                        rs_ld(x, d.idx[1][3 * t + 2], N, C, c), e0, e2);
+            const float coef = d.k[1][t] * (th - d.eq[1][t]);
+            const V3 dv = pos == 0 ? e0 : (pos == 2 ? e2 : (-1.0f) * (e0 + e2));
+            g = g + coef * dv;
+        } else {
+            V3 d0, d1, d2, d3;
+            const int* id = d.idx[l] + 4 * (size_t)t;
+            const float phi = dihedral_geom(rs_ld(x, id[0], N, C, c), rs_ld(x, id[1], N, C, c), rs_ld(x, id[2], N, C, c), rs_ld(x, id[3], N, C, c),
+                                            d0, d1, d2, d3);
+            const float coef = torsion_dcoef(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], phi);
+            const V3 dv = pos == 0 ? d0 : (pos == 1 ? d1 : (pos == 2 ? d2 : d3));
+            g = g + coef * dv;
+        }
+    }
+    return g;
+}
+
+__global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
+    __shared__ float4 xs[NB_TJ * NB_CW];      // j coordinates: [jj][conformation of the item]
+    __shared__ float4 ps[NB_TJ];              // j parameters: q, sigma / 2, sqrt(eps)
+    __shared__ float red[4][NB_NT];
+    __shared__ int run[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C;
+    if (!rs_running(r, C, a.status, run)) return;      // every conformation of the item has stopped: nothing of it is touched
+    const int ni = r.ni, nc = r.nc, i0 = r.i0, c0 = r.c0, m0 = r.m0, m1 = r.m1;
+    const int NL = ni * nc;
+    const int JS = NB_NT / NL < NB_JS ? NB_NT / NL : NB_JS;
+    const int t = threadIdx.x, s = t / NL, l = t - s * NL;
+    const int cl = l / ni, il = l - cl * ni;      // (l < NL: cl < nc)
+    const int i = i0 + il, c = c0 + cl;
+    const bool active = s < JS && run[cl] != 0;
+
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (active) {
+        const V3 p = rs_bonded(a.mm, a.x, i, s, JS, c);
+        gx = p.x, gy = p.y, gz = p.z;
+    }
+    if (a.has_nb) {
+        const grappa_nb_desc& d = a.nb;
+        float xi = 0.f, yi = 0.f, zi = 0.f, kq = 0.f, hs = 0.f, se = 0.f;
+        int ep = 0, ee = 0, nx = INT_MAX;
+        if (active) {
+            const float* p = a.x + ((size_t)i * C + c) * 3;
+            xi = p[0], yi = p[1], zi = p[2];
+            kq = NB_K * d.charge[i];
+            hs = 0.5f * d.sigma[i];
+            se = 4.0f * sqrtf(d.epsilon[i]);
+            ep = d.exc_ptr[i];
+            ee = d.exc_ptr[i + 1];
+            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+        }
+        float elj = 0.f, ec = 0.f;      // (no pair energy is kept: dead code to the compiler)
+        for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
+            const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
+            __syncthreads();
+            for (int idx = t; idx < nj * nc; idx += NB_NT) {
+                const int jj = idx / nc, cc = idx - jj * nc;
+                if (run[cc]) {
+                    const float* p = a.x + ((size_t)(j0 + jj) * C + c0 + cc) * 3;
+                    xs[jj * NB_CW + cc] = make_float4(p[0], p[1], p[2], 0.f);
+                }
+            }
+            if (t < nj) ps[t] = make_float4(d.charge[j0 + t], 0.5f * d.sigma[j0 + t], sqrtf(d.epsilon[j0 + t]), 0.f);
+            __syncthreads();
+            const bool lookup = active && ((i >= j0 && i < j0 + nj) || nx < j0 + nj);
+            if (__builtin_amdgcn_ballot_w64(lookup) != 0) {
+                if (active) {
+                    for (int jj = s; jj < nj; jj += JS) {
+                        const int j = j0 + jj;
+                        const float4 p = ps[jj];
+                        float sij = hs + p.y, e4 = se * p.z, kqq = kq * p.x;
+                        bool skip = j == i;
+                        while (nx < j) {
+                            ++ep;
+                            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                        }
+                        if (nx == j) {
+                            const float q = d.exc_qq[ep], e = d.exc_eps[ep];
+                            sij = d.exc_sigma[ep];
+                            e4 = 4.0f * e;
+                            kqq = NB_K * q;
+                            skip = skip || (q == 0.f && e == 0.f);
+                            ++ep;
+                            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                        }
+                        if (!skip) {
+                            const float4 x = xs[jj * NB_CW + cl];
+                            nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                        }
+                    }
+                    while (nx < j0 + nj) {      // partners that belong to other slices
+                        ++ep;
+                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+                    }
+                }
+            } else if (active) {
+#pragma unroll 4
+                for (int jj = s; jj < nj; jj += JS) {
+                    const float4 p = ps[jj];
+                    const float4 x = xs[jj * NB_CW + cl];
+                    nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
+                }
+            }
+        }
+    }
+    // the slices of one (atom, conformation), added in slice order
+    red[0][t] = gx, red[1][t] = gy, red[2][t] = gz;
+    __syncthreads();
+    const bool owner = active && s == 0;
+    float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
+    if (owner) {
+        for (int q = 1; q < JS; ++q) {
+            const int o = q * NL + l;
+            gx += red[0][o], gy += red[1][o], gz += red[2][o];
+        }
+        const size_t off = ((size_t)i * C + c) * 3;
+        a.g[off] = gx, a.g[off + 1] = gy, a.g[off + 2] = gz;
+        const V3 gi = {gx, gy, gz}, vi = {a.v[off], a.v[off + 1], a.v[off + 2]};
+        const float g2 = dot(gi, gi), gn = sqrtf(g2);
+        pP = -dot(gi, vi);          // F = -g
+        pF = g2;
+        pv = dot(vi, vi);
+        pg = gn <= FLT_MAX ? gn : INFINITY;      // (written so that a NaN counts as non-finite)
+    }
+    __syncthreads();
+    if (owner) red[0][l] = pP, red[1][l] = pF, red[2][l] = pv, red[3][l] = pg;
+    __syncthreads();
+    if (owner && il == 0) {      // the block's partials of one conformation: over its atoms in ascending order, in double
+        double sP = 0.0, sF = 0.0, sv = 0.0;
+        float mg = 0.f;
+        for (int k = 0; k < ni; ++k) {
+            const int o = cl * ni + k;
+            sP += (double)red[0][o], sF += (double)red[1][o], sv += (double)red[2][o];
+            mg = fmaxf(mg, red[3][o]);
+        }
+        double* o = a.part + ((size_t)r.blk * C + c) * 4;
+        o[0] = sP, o[1] = sF, o[2] = sv, o[3] = (double)mg;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ decide
+struct RsDecideArgs {
+    grappa_relax_opts o;
+    int C, n_blocks;
+    const int* blk_ptr;
+    const double* part;
+    RsState s;
+    int* n_running;      // NULL: not counted (the finish)
+    int final;           // the finish: stop tests only, a running item ends with status 0
+};
+
+__global__ __launch_bounds__(RS_DNT) void rs_decide_kernel(RsDecideArgs a) {
+    __shared__ double red[4][RS_DNT];
+    const size_t item = blockIdx.x;
+    if (a.s.status[item] != RS_RUNNING) return;
+    const int C = a.C, t = threadIdx.x;
+    const int b = (int)(item / (unsigned)C), c = (int)(item - (size_t)b * C);
+    const int k0 = nb_clamp(a.blk_ptr[b], a.n_blocks), k1 = nb_clamp(a.blk_ptr[b + 1], a.n_blocks);
+    double P = 0.0, F2 = 0.0, v2 = 0.0, gm = 0.0;
+    for (int k = k0 + t; k < k1; k += RS_DNT) {      // thread t adds the blocks t, t + 64, .. ascending; the 64 rows are added in order
+        const double* p = a.part + ((size_t)k * C + c) * 4;
+        P += p[0], F2 += p[1], v2 += p[2];
+        gm = fmax(gm, p[3]);
+    }
+    red[0][t] = P, red[1][t] = F2, red[2][t] = v2, red[3][t] = gm;
+    __syncthreads();
+    if (t != 0) return;
+#pragma unroll 4
+    for (int q = 1; q < RS_DNT; ++q) {
+        P += red[0][q], F2 += red[1][q], v2 += red[2][q];
+        gm = fmax(gm, red[3][q]);
+    }
+    const grappa_relax_opts& o = a.o;
+    float gmf = (float)gm;
+    const int steps = a.s.steps[item];
+    int status = RS_RUNNING;
+    if (!(gmf <= FLT_MAX)) {
+        gmf = INFINITY;
+        status = 2;
+    } else if (gmf <= o.tolerance) {
+        status = 1;
+    } else if (steps >= o.max_steps || a.final) {
+        status = 0;
+    }
+    if (status != RS_RUNNING) {
+        a.s.gmax[item] = gmf;
+        a.s.status[item] = status;
+        if (a.n_running) atomicSub(a.n_running, 1);
+        return;
+    }
+    // FIRE: mix the velocity towards the force (or stop it); the new time step
+    const float Pf = (float)P, F2f = (float)F2, v2f = (float)v2;
+    float h = a.s.h[item], al = a.s.al[item];
+    int npos = a.s.npos[item];
+    const bool downhill = Pf > 0.f;
+    float mix = 0.f, keep = 0.f;
+    if (downhill) {
+        mix = al * (sqrtf(v2f) / sqrtf(F2f));
+        keep = 1.0f - al;
+        if (npos >= o.n_min) {
+            h = fminf(h * o.f_inc, o.dt_max);
+            al = al * o.f_alpha;
+        }
+        ++npos;
+    } else {
+        h = h * o.f_dec;
+        al = o.alpha_start;
+        npos = 0;
+    }
+    a.s.h[item] = h, a.s.al[item] = al, a.s.mix[item] = mix, a.s.keep[item] = keep;
+    a.s.npos[item] = npos, a.s.downhill[item] = downhill ? 1 : 0, a.s.steps[item] = steps + 1;
+}
+
+// ------------------------------------------------------------------------------------------------ vel, move
+struct RsUpdArgs {
+    RsGeom q;
+    float *x, *v;
+    const float* g;
+    RsState s;
+    float* dpart;
+    float max_disp;
+};
+
+__global__ __launch_bounds__(NB_NT) void rs_vel_kernel(RsUpdArgs a) {
+    __shared__ float red[NB_NT];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    const bool in = t < ni * r.nc;
+    const int cl = in ? t / ni : 0, il = in ? t - cl * ni : 0;
+    const int c = r.c0 + cl;
+    const size_t item = (size_t)r.mol * C + c;
+    const bool on = in && a.s.status[item] == RS_RUNNING;
+    float dm = 0.f;
+    if (on) {
+        const size_t off = ((size_t)(r.i0 + il) * C + c) * 3;
+        const float h = a.s.h[item];
+        const V3 gi = {a.g[off], a.g[off + 1], a.g[off + 2]};
+        V3 vk = {0.f, 0.f, 0.f};                   // P <= 0: the velocity is dropped, whatever it held
+        if (a.s.downhill[item]) {
+            const V3 vi = {a.v[off], a.v[off + 1], a.v[off + 2]};
+            vk = a.s.keep[item] * vi - a.s.mix[item] * gi;      // F = -g
+        }
+        vk = vk - h * gi;
+        a.v[off] = vk.x, a.v[off + 1] = vk.y, a.v[off + 2] = vk.z;
+        dm = h * sqrtf(dot(vk, vk));
+    }
+    red[t] = dm;
+    __syncthreads();
+    if (on && il == 0) {
+        for (int k = 1; k < ni; ++k) dm = fmaxf(dm, red[cl * ni + k]);
+        a.dpart[(size_t)r.blk * C + c] = dm;
+    }
+}
+
+__global__ __launch_bounds__(NB_NT) void rs_move_kernel(RsUpdArgs a) {
+    __shared__ float sdm[NB_CW];
+    __shared__ int run[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    if (!rs_running(r, C, a.s.status, run)) return;
+    // the largest displacement of each running conformation over ALL blocks of the molecule (every workgroup of the molecule forms the
+    // same maximum from the same partials): wavefront w takes the conformations w, w + 4, .., its lanes the blocks
+    const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
+    const int wave = t / GRAPPA_WAVE, lane = t & (GRAPPA_WAVE - 1);
+    for (int cc = wave; cc < r.nc; cc += RS_NW) {
+        if (!run[cc]) continue;
+        float m = 0.f;
+        for (int k = k0 + lane; k < k1; k += GRAPPA_WAVE) m = fmaxf(m, a.dpart[(size_t)k * C + r.c0 + cc]);
+#pragma unroll
+        for (int o = GRAPPA_WAVE / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, GRAPPA_WAVE));
+        if (lane == 0) sdm[cc] = m;
+    }
+    __syncthreads();
+    if (t >= ni * r.nc) return;
+    const int cl = t / ni, il = t - cl * ni;
+    if (!run[cl]) return;
+    const int c = r.c0 + cl;
+    const float dm = sdm[cl], h = a.s.h[(size_t)r.mol * C + c];
+    const float sc = dm > 0.f ? fminf(1.0f, a.max_disp / dm) : 1.0f;
+    const float hs = sc * h;
+    const size_t off = ((size_t)(r.i0 + il) * C + c) * 3;
+    const V3 vk = {a.v[off], a.v[off + 1], a.v[off + 2]};
+    a.x[off] += hs * vk.x, a.x[off + 1] += hs * vk.y, a.x[off + 2] += hs * vk.z;
+    a.v[off] = sc * vk.x, a.v[off + 1] = sc * vk.y, a.v[off + 2] = sc * vk.z;
+}
+
+// ------------------------------------------------------------------------------------------------ finish
+struct RsOutArgs {
+    int N, C, B, has_nb;
+    const int* atom_molptr;
+    const float *x, *g, *terms;      // terms [6,B,C] in the workspace (rows 4, 5 only with has_nb)
+    RsState s;
+    float *xyz_out, *energy, *term_energy, *grad, *gmax;
+    int *steps, *status;
+};
+
+__global__ __launch_bounds__(256) void rs_out_kernel(RsOutArgs a) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid < (size_t)a.N * a.C * 3) {
+        a.xyz_out[gid] = a.x[gid];
+        if (a.grad) a.grad[gid] = a.g[gid];
+    }
+    const size_t bc = (size_t)a.B * a.C;
+    if (gid < bc) {
+        const int b = (int)(gid / a.C);
+        if (nb_clamp(a.atom_molptr[b + 1], a.N) <= nb_clamp(a.atom_molptr[b], a.N)) return;      // a molecule without atoms writes nothing
+        double tot = 0.0;
+        for (int q = 0; q < 6; ++q) {
+            const float e = (q < 4 || a.has_nb) ? a.terms[q * bc + gid] : 0.f;
+            if (a.term_energy) a.term_energy[q * bc + gid] = e;
+            tot += (double)e;
+        }
+        a.energy[gid] = (float)tot;
+        a.gmax[gid] = a.s.gmax[gid];
+        a.steps[gid] = a.s.steps[gid];
+        a.status[gid] = a.s.status[gid];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// the argument checks of grappa_relax_fire_f32, without its output pointers; 1: nothing to do (an empty batch)
+int rs_check(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
+             const void* ws) {
+    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0 || n_items < 0 || n_blocks < 0) return GRAPPA_ERR_ARG;
+    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
+    // (comparisons written so that a NaN is refused)
+    if (!(o->tolerance >= 0.f) || o->max_steps < 0 || o->max_steps > RS_STEP_CAP || !(o->dt_start > 0.f) || !(o->dt_max > 0.f) ||
+        !(o->max_disp > 0.f) || o->n_min < 0 || !(o->f_inc > 0.f) || !(o->f_dec > 0.f) || !(o->f_alpha > 0.f) ||
+        !(o->alpha_start >= 0.f && o->alpha_start <= 1.f))
+        return GRAPPA_ERR_ARG;
+    if (!(o->dt_start <= FLT_MAX && o->dt_max <= FLT_MAX && o->max_disp <= FLT_MAX && o->f_inc <= FLT_MAX && o->f_dec <= FLT_MAX &&
+          o->f_alpha <= FLT_MAX && o->tolerance <= FLT_MAX))
+        return GRAPPA_ERR_ARG;
+    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return 1;
+    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !table_dev || !ws) return GRAPPA_ERR_ARG;
+    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)table_dev & 15) != 0) return GRAPPA_ERR_ARG;      // (doubles in the workspace, int4 items in the table)
+    long long tuples = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (mm->T[l] < 0 || mm->T[l] >= (1 << 27) || !mm->mol_ptr[l]) return GRAPPA_ERR_ARG;
+        if (mm->T[l] > 0 && (!mm->idx[l] || !mm->k[l])) return GRAPPA_ERR_ARG;
+        if (l < 2 && mm->T[l] > 0 && !mm->eq[l]) return GRAPPA_ERR_ARG;
+        if (l >= 2 && (mm->n_per[l] < 1 || mm->n_per[l] > 8)) return GRAPPA_ERR_ARG;
+        tuples += mm->T[l];
+    }
+    if (tuples > 0 && !mm->inc_code) return GRAPPA_ERR_ARG;
+    if (nb && (!nb->charge || !nb->sigma || !nb->epsilon || !nb->exc_ptr || !nb->exc_atom || !nb->exc_qq || !nb->exc_sigma || !nb->exc_eps))
+        return GRAPPA_ERR_ARG;
+    if ((long long)mm->B * mm->C > INT_MAX || (long long)mm->N * mm->C * 3 > INT_MAX || (long long)n_blocks * mm->C > INT_MAX)
+        return GRAPPA_ERR_ARG;
+    if (n_blocks > (long long)mm->N / NB_T + mm->B) return GRAPPA_ERR_ARG;
+    return GRAPPA_OK;
+}
+
+RsGeom rs_geom(const grappa_mm_desc* mm, const int* table_dev, int n_blocks) {
+    RsGeom q;
+    q.N = mm->N, q.C = mm->C, q.B = mm->B, q.n_blocks = n_blocks;
+    q.atom_molptr = mm->atom_molptr;
+    q.blk_ptr = table_dev + 4;
+    q.items = (const int4*)(table_dev + 4 + (((size_t)mm->B + 1 + 3) & ~(size_t)3));
+    return q;
+}
+
+void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const RsWs& w, int n_items) {
+    RsForceArgs f;
+    f.mm = *mm;
+    f.mm.xyz = nullptr;
+    f.has_nb = nb != nullptr;
+    if (nb) f.nb = *nb; else f.nb = grappa_nb_desc{};
+    f.nb.xyz = nullptr;
+    f.q = q;
+    f.x = w.x, f.v = w.v, f.g = w.g, f.status = w.s.status, f.part = w.part;
+    GRAPPA_LAUNCH(rs_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
+}
+
+}  // namespace
+
+extern "C" size_t grappa_relax_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return rs_layout(nullptr, N, C, B, n_blocks).total;
+}
+
+extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
+    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
+    if (!n_running_dev) return GRAPPA_ERR_ARG;
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    RsInitArgs a;
+    a.N = mm->N, a.C = mm->C, a.B = mm->B;
+    a.atom_molptr = mm->atom_molptr, a.start = mm->xyz;
+    a.x = w.x, a.v = w.v, a.s = w.s;
+    a.dt_start = o->dt_start, a.alpha_start = o->alpha_start;
+    a.n_running = n_running_dev;
+    const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
+    GRAPPA_LAUNCH(rs_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    if (n_items > 0) rs_launch_force(st, mm, nb, rs_geom(mm, table_dev, n_blocks), w, n_items);
+    return grappa_launch_status();
+}
+
+extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                          const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps,
+                                          int* n_running_dev) {
+    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    if (rc < 0) return rc;
+    if (n_steps < 1) return GRAPPA_ERR_ARG;
+    if (rc != GRAPPA_OK) return GRAPPA_OK;
+    if (!n_running_dev) return GRAPPA_ERR_ARG;
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    RsDecideArgs dc;
+    dc.o = *o;
+    dc.C = mm->C, dc.n_blocks = n_blocks, dc.blk_ptr = q.blk_ptr, dc.part = w.part, dc.s = w.s;
+    dc.n_running = n_running_dev, dc.final = 0;
+    RsUpdArgs u;
+    u.q = q, u.x = w.x, u.v = w.v, u.g = w.g, u.s = w.s, u.dpart = w.dpart, u.max_disp = o->max_disp;
+    const unsigned items = (unsigned)n_items, bc = (unsigned)(mm->B * mm->C);
+    for (int k = 0; k < n_steps; ++k) {
+        GRAPPA_LAUNCH(rs_decide_kernel, dim3(bc), dim3(RS_DNT), 0, st, dc);
+        if (n_items > 0) {
+            GRAPPA_LAUNCH(rs_vel_kernel, dim3(items), dim3(NB_NT), 0, st, u);
+            GRAPPA_LAUNCH(rs_move_kernel, dim3(items), dim3(NB_NT), 0, st, u);
+            rs_launch_force(st, mm, nb, q, w, n_items);
+        }
+    }
+    return grappa_launch_status();
+}
+
+extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
+                                             float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status) {
+    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
+    if (!xyz_out || !energy || !gmax || !steps || !status) return GRAPPA_ERR_ARG;
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    const size_t bc = (size_t)mm->B * mm->C;
+    RsDecideArgs dc;
+    dc.o = *o;
+    dc.C = mm->C, dc.n_blocks = n_blocks, dc.blk_ptr = q.blk_ptr, dc.part = w.part, dc.s = w.s;
+    dc.n_running = nullptr, dc.final = 1;
+    GRAPPA_LAUNCH(rs_decide_kernel, dim3((unsigned)bc), dim3(RS_DNT), 0, st, dc);
+    // the six terms at the held coordinates by the library's own energy kernels: the bits of grappa_mm_energy_fwd_f32 and
+    // grappa_nonbonded_fwd_planned_f32 there
+    grappa_mm_desc me = *mm;
+    me.xyz = w.x;
+    int erc = grappa_mm_energy_fwd_f32(stream, &me, w.e_mm, w.terms, nullptr, nullptr);
+    if (erc != GRAPPA_OK) return erc;
+    if (nb) {
+        grappa_nb_desc ne = *nb;
+        ne.xyz = w.x;
+        ne.atom_molptr = mm->atom_molptr;
+        erc = grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, w.nbpart,
+                                               sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
+        if (erc != GRAPPA_OK) return erc;
+    }
+    RsOutArgs a;
+    a.N = mm->N, a.C = mm->C, a.B = mm->B, a.has_nb = nb != nullptr;
+    a.atom_molptr = mm->atom_molptr;
+    a.x = w.x, a.g = w.g, a.terms = w.terms, a.s = w.s;
+    a.xyz_out = xyz_out, a.energy = energy, a.term_energy = term_energy, a.grad = grad, a.gmax = gmax, a.steps = steps, a.status = status;
+    const size_t n3 = (size_t)mm->N * mm->C * 3, n = n3 > bc ? n3 : bc;
+    GRAPPA_LAUNCH(rs_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    return grappa_launch_status();
+}

@@ -56,8 +56,10 @@ class Grappa:
         g = g.to("cpu")
         return Parameters.from_dgl(g)
 
-    def relax(self, molecule: Molecule, xyz, nonbonded=None, **opts):
+    def relax(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, check_every: int = 32, **opts):
         """`predict` followed by `grappa_amd.relax.relax`: the conformations xyz (n_confs, n_atoms, 3) of `molecule` minimised on the
-        device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in the molecule's atom order) -> RelaxResult"""
+        device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in the molecule's atom order) -> RelaxResult.
+        stepwise=False: the fused kernel (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules
+        of any size, which syncs with the host once per chunk of `check_every` steps (see `grappa_amd.relax.relax_graph`)"""
         from .relax import relax
-        return relax(self.predict(molecule), xyz, nonbonded, device=self.device, **opts)
+        return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)

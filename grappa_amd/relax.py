@@ -1,15 +1,19 @@
 """Relaxation (energy minimisation) of molecules on the device under the full MM force field: the bonded terms Grappa predicts plus,
 optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`).  The reference hands this step to OpenMM / GROMACS; here one launch of
 csrc/relax.hip (`grappa_relax_fire_f32` through `HipBackend.relax_fire`) runs the whole minimisation of every (molecule, conformation):
-one workgroup each, coordinates in LDS, no host round trip per step.
+one workgroup each, coordinates in LDS, no host round trip per step.  That fused kernel takes molecules of up to `relax_max_atoms()`
+atoms.  Larger ones -- a protein -- go through the stepwise path (`stepwise=True` or `"auto"`; csrc/relax_steps.hip,
+`grappa_relax_steps_*_f32` through `HipBackend.relax_steps`): the same loop with a molecule spread over many workgroups, the state in
+device memory and four launches per step; the host syncs with the device once per chunk of `check_every` steps, never per step.
 
 The minimiser is FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201 (2006)) with unit masses and semi-implicit Euler; the loop is stated
 in include/grappa_hip.h.  Units: Angstrom, kcal/mol, kcal/mol/A.  An item stops with a status:
     0  max_steps reached        1  converged: the largest atomic gradient norm <= tolerance
     2  non-finite gradient (for example two non-excluded atoms on one point): stopped at once, the coordinates are those it held
-    3  the molecule has more than `relax_max_atoms()` atoms: not run
+    3  the molecule has more than `relax_max_atoms()` atoms: not run (the fused kernel only)
 The defaults (`RELAX_DEFAULTS`; tolerance = 10 kJ/mol/nm, OpenMM's `minimizeEnergy` default) were checked on small chain molecules only
-and are not tuned.  Molecules above `relax_max_atoms()` atoms are refused: a stepwise path for them is out of scope.
+and are not tuned.  With `stepwise=False` (the default) a molecule above `relax_max_atoms()` atoms is refused; `stepwise="auto"` takes
+the stepwise path for a batch that holds one.  The two paths add in different orders: the same trajectory within rounding, not the same bits.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -25,6 +29,7 @@ from .parameters import Parameters
 RELAX_DEFAULTS = {"tolerance": 10.0 / 4.184 / 10.0, "max_steps": 1000, "dt_start": 0.002, "dt_max": 0.02, "max_disp": 0.1, "n_min": 5,
                   "f_inc": 1.1, "f_dec": 0.5, "alpha_start": 0.1, "f_alpha": 0.99}
 MAX_STEPS_CAP = 1000000
+CHECK_EVERY_DEFAULT = 32          # steps the stepwise path enqueues between two host syncs.  Untuned: nobody has measured another value.
 
 
 def relax_max_atoms() -> int:
@@ -71,13 +76,27 @@ class RelaxResult:
         return self.status == 1
 
 
+def _stepwise_options(stepwise, check_every):
+    if not (stepwise is True or stepwise is False or stepwise == "auto"):
+        raise ValueError(f"stepwise must be False, True or 'auto', got {stepwise!r}")
+    if isinstance(check_every, bool) or not isinstance(check_every, (int, np.integer)) or check_every < 1:
+        raise ValueError(f"check_every must be an integer >= 1, got {check_every!r}")
+    return stepwise, int(check_every)
+
+
 def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                offset_torsion: bool = False, **opts) -> RelaxResult:
+                offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, **opts) -> RelaxResult:
     """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
     exactly what `Energy` reads, through the same plan.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded
-    terms only).  **opts: see RELAX_DEFAULTS.  One launch, no host sync; the graph is not modified."""
+    terms only).  **opts: see RELAX_DEFAULTS.  The graph is not modified.
+    stepwise=False (the default): the fused kernel, one launch, no host sync; a molecule above `relax_max_atoms()` atoms is refused.
+    stepwise=True: the whole batch through the stepwise path, which takes molecules of any size: four launches per step, and the host
+    SYNCS with the device once per chunk of `check_every` steps (an integer >= 1; the default 32 is untuned) to see whether any item
+    still runs.  stepwise="auto": the fused kernel if every molecule is within the limit, else the whole batch stepwise -- a batch is
+    never split between the two paths (one batch, one decomposition, one set of bits)."""
     from .backend import get_backend
     o = relax_options(**opts)
+    stepwise, check_every = _stepwise_options(stepwise, check_every)
     terms = list(terms)
     for t in terms:
         if t not in TUPLE_LEVELS:
@@ -93,9 +112,11 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     plan = g.plan()
     counts = [int(c) for c in g.batch_num_nodes_host("n1")]          # (host numbers: no device sync)
     limit = get_backend().relax_max_atoms()
-    if counts and max(counts) > limit:
-        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule "
-                         f"(larger molecules are out of scope of the fused minimiser)")
+    above = bool(counts) and max(counts) > limit
+    if above and stepwise is False:
+        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
+                         f"minimiser (stepwise=True or stepwise='auto' relaxes molecules of any size)")
+    use_steps = stepwise is True or (stepwise == "auto" and above)
     if nonbonded is not None:
         if not isinstance(nonbonded, NonbondedBatch):
             raise TypeError(f"nonbonded must be a NonbondedBatch or None, got {type(nonbonded).__name__}")
@@ -111,8 +132,12 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     out = torch.empty_like(xyz)
     energy, gmax = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(B, C, dtype=torch.float32, device=dev)
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
-    get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
-                             atom_counts_host=counts)
+    if use_steps:
+        get_backend().relax_steps(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
+                                  atom_counts_host=counts, check_every=check_every)
+    else:
+        get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
+                                 atom_counts_host=counts)
     return RelaxResult(out, energy, gmax, steps, status)
 
 
@@ -165,11 +190,14 @@ def graph_from_parameters(parameters: Parameters, xyz):
     return g
 
 
-def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", **opts) -> RelaxResult:
+def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, stepwise=False,
+          check_every: int = CHECK_EVERY_DEFAULT, **opts) -> RelaxResult:
     """Relax the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`, whose atoms are in the
     order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom -> RelaxResult with xyz of the same shape
-    (float64) and energy / gradient_max / steps / status of shape (n_confs,)."""
+    (float64) and energy / gradient_max / steps / status of shape (n_confs,).  stepwise, check_every: see `relax_graph` (the stepwise
+    path takes a molecule of any size and syncs with the host once per chunk of `check_every` steps)."""
     relax_options(**opts)
+    _stepwise_options(stepwise, check_every)
     g = graph_from_parameters(parameters, xyz)
     nb = None
     if nonbonded is not None:
@@ -178,6 +206,6 @@ def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] 
         if nonbonded.n_atoms != g.num_nodes("n1"):
             raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {g.num_nodes('n1')}")
         nb = NonbondedBatch([nonbonded]).to(device)
-    r = relax_graph(g.to(device), nb, **opts)
+    r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, **opts)
     return RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
                        r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])

@@ -531,6 +531,46 @@ int grappa_relax_fire_f32(void* stream, const grappa_mm_desc* mm, const grappa_n
                           float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same relaxation for molecules of ANY size, stepwise (additions to ABI 11): the loop, the energy, the options and the outputs are
+ * those of grappa_relax_fire_f32 above, but a molecule spans many workgroups, the minimiser's state lives in a caller-owned workspace
+ * and a step is a fixed sequence of four launches.  The decomposition is grappa_nonbonded_plan's (a work item = molecule, block of at
+ * most GRAPPA_NB_IBLOCK i-atoms, nc conformations): the caller passes that table (device memory, 16-byte aligned) with table[0] =
+ * n_items and table[1] = n_blocks to all three calls, also when nb == NULL (the plan is about atoms, not about parameters).
+ *   init   : x = mm->xyz, v = 0, h = dt_start, a = alpha_start, npos = 0, steps = 0; n_running_dev[0] = the number of (molecule,
+ *            conformation) items with at least one atom; g = grad E(x) and the block partials of P, |F|^2, |v|^2, max |g_i|.  2 launches.
+ *   run    : enqueues exactly n_steps iterations of the loop, 4 launches each and nothing else: no sync, no allocation, safe to capture.
+ *            decide (one workgroup per item: adds the block partials in ascending block order in double, takes the stop tests and FIRE's
+ *            decisions, writes the item's scalars; the thread that stops an item subtracts 1 from n_running_dev[0]), vel (v and the
+ *            blocks' largest |h v_i|), move (the maximum over the item's blocks, x += s h v, v = s v), force (g and the partials at the
+ *            new x in ONE launch: the bonded gather and the Lennard-Jones / Coulomb pair loop).  The host reads n_running_dev[0]
+ *            whenever it likes -- typically once per chunk of steps -- and stops enqueueing when it is 0.
+ *   finish : applies the stop tests once more (an item still running ends with status 0), then writes xyz_out, energy, gmax, steps,
+ *            status and the optional grad and term_energy[6,B,C] as grappa_relax_fire_f32 defines them.  The six terms come from the
+ *            kernels of grappa_mm_energy_fwd_f32 and grappa_nonbonded_fwd_planned_f32 at xyz_out: the same bits as those entry points
+ *            give there; energy is their sum, added in double in term order.  A workspace that was finished is not run again.
+ * Hazards.  Workgroups of one molecule exchange data only across launch boundaries: partials are written by one launch and read by
+ * the next, and the per-item scalars (h, a, npos, steps, status, the step's mixing factors) have ONE writer, the decide launch, which no
+ * other launch overlaps.  No cooperative launch, no flag that is waited on, no float atomics; the only atomic is the integer count.
+ * Every launch leaves an item whose status is final alone before touching its x, v, g or state: the outputs do not depend on how many
+ * steps were enqueued after an item stopped, nor on n_steps per call.  A non-finite gradient stops an item at once with status 2,
+ * gmax = inf and the coordinates it held.  A molecule without atoms writes nothing; a single atom stops at step 0 with status 1 and
+ * xyz_out bit-equal to its input.  Fixed-order sums: same input, same bits, and a molecule's bits do not depend on its place in the batch
+ * (they differ from grappa_relax_fire_f32's, which adds in another order).  With max_steps == 0 (init, finish) xyz_out is the input
+ * bit for bit with energy, grad and gmax at it.
+ * Limits.  N * C * 3, n_blocks * C and B * C below 2^31 and n_blocks <= N / GRAPPA_NB_IBLOCK + B, GRAPPA_ERR_ARG otherwise; the other
+ * GRAPPA_ERR_ARG cases are those of grappa_relax_fire_f32, plus a NULL table_dev, ws or n_running_dev, a table or workspace that is not 16-byte
+ * aligned, a negative n_items or n_blocks and n_steps < 1.  ws_bytes below grappa_relax_steps_workspace_bytes(N, C, B, n_blocks): GRAPPA_ERR_WORKSPACE, nothing launched.
+ * N == 0, C == 0 or B == 0: returns 0 without a launch.  The workspace holds about 36 N C + 68 B C + 52 n_blocks C bytes. */
+size_t grappa_relax_steps_workspace_bytes(int N, int C, int B, int n_blocks);
+int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev);
+int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                               const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps, int* n_running_dev);
+int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                  const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* energy,
+                                  float* term_energy, float* grad, float* gmax, int* steps, int* status);
+
+/* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:
  *  l_m = wE*mean_c((E-<E>)-(Eref-<Eref>))^2 + wG*mean_{a,c,xyz}(G-Gref)^2   over real conformations
  *  loss_mol[b] = l_m ; gE = d(sum_m l_m * inv_B)/dE ; gG likewise.  is_dummy may be NULL. */

@@ -1,0 +1,183 @@
+"""Time the stepwise FIRE minimiser (csrc/relax_steps.hip through relax_graph(stepwise=True)) with device events, after warm-up, with
+tolerance 0 and a fixed step count, so that all sides do equal work; milliseconds per step at three sizes:
+
+  (a) pool    256 molecules of the pool x 32 conformations: the fused kernel against the stepwise path -- what stepwise=True costs where
+              it is not needed, and the case for stepwise="auto"
+  (b) chain   one synthetic chain of 2,600 atoms, 1 conformation: stepwise against the same loop composed from the entry points that
+              existed before it (mm_gradient_fwd, the planned nonbonded kernel and a FIRE update in stock torch ops: tools/relax_bench.py's
+              Composed, tables built outside the timed region), and a sweep of check_every over 1, 8, 32, 128
+  (c) chain   the 50,046-atom chain of tools/nonbonded_bench.py: stepwise against composed
+
+The sides of a size are timed alternately, `--reps` times each after one warm-up run each; every row gives the median, the minimum and
+the maximum.  The chains carry bonds, angles and proper torsions along the chain (k_bond 500, k_angle 100, three periodicities) with the
+lattice geometry as equilibrium, and the nonbonded parameters of tools/nonbonded_bench.py.
+
+    python tools/relax_steps_bench.py [--out profiles/relax_steps_bench.txt] [--steps 128] [--big-steps 16] [--reps 5]
+    python tools/relax_steps_bench.py --dry          # build the inputs on the CPU and stop (a rehearsal: nothing is timed)
+"""
+import argparse
+import datetime
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from nonbonded_bench import chain      # noqa: E402
+from relax_bench import Composed, pool_batch      # noqa: E402
+from grappa_amd.relax import RELAX_DEFAULTS      # noqa: E402
+
+
+def chain_graph(n_atoms):
+    """-> (single-molecule graph with k / eq at the tuple levels and xyz (n, 1, 3), NonbondedParameters), on the host"""
+    from grappa_amd import _hostlib
+    from grappa_amd.parameters import Parameters
+    from grappa_amd.relax import graph_from_parameters
+    (nbp,), xyz = chain(n_atoms)
+    x = torch.from_numpy(xyz[:, 0, :]).double()
+    k = np.arange(n_atoms)
+    bonds = np.stack([k[:-1], k[1:]], axis=1)
+    angles, propers = (np.asarray(a, dtype=np.int64) for a in _hostlib.enumerate_tuples(bonds))
+    angles, propers = angles.reshape(-1, 3), propers.reshape(-1, 4)
+    d = x[bonds[:, 0]] - x[bonds[:, 1]]
+    u, v = x[angles[:, 0]] - x[angles[:, 1]], x[angles[:, 2]] - x[angles[:, 1]]
+    theta = torch.atan2(torch.cross(u, v, dim=-1).norm(dim=-1), (u * v).sum(-1))
+    rng = np.random.default_rng(2)
+    ks = rng.uniform(-1, 1, size=(propers.shape[0], 3)) * np.array([1.0, 0.5, 0.3])
+    p = Parameters(atoms=k, bonds=bonds, bond_k=np.full(len(bonds), 500.0), bond_eq=d.norm(dim=-1).numpy(), angles=angles,
+                   angle_k=np.full(len(angles), 100.0), angle_eq=theta.numpy(), propers=propers, proper_ks=np.abs(ks),
+                   proper_phases=np.where(ks >= 0, 0.0, np.pi), impropers=None, improper_ks=None, improper_phases=None)
+    # start a little off the equilibrium geometry, so that the bonded terms pull as well
+    start = xyz + np.random.default_rng(3).normal(0, 0.03, size=xyz.shape).astype(np.float32)
+    return graph_from_parameters(p, start.transpose(1, 0, 2)), nbp
+
+
+def timed_alternately(fns, reps):
+    """fns: name -> callable.  One warm-up run each, then `reps` rounds in which every side runs once, each between device events
+    -> name -> list of milliseconds"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--mols", type=int, default=256)
+    ap.add_argument("--confs", type=int, default=32)
+    ap.add_argument("--mid-atoms", type=int, default=2600)
+    ap.add_argument("--big-atoms", type=int, default=50046)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--big-steps", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dry", action="store_true")
+    args = ap.parse_args()
+    if args.dry:
+        for n in (args.mid_atoms, args.big_atoms):
+            g, nbp = chain_graph(n)
+            print(f"chain of {n} atoms: {', '.join(f'{lv} {g.num_nodes(lv)}' for lv in ('n2', 'n3', 'n4', 'n4_improper'))}; "
+                  f"{nbp.exception_idx.shape[0]} exceptions")
+        return
+    if not torch.cuda.is_available():
+        sys.exit("relax_steps_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    from grappa_amd.nonbonded import NonbondedBatch
+    from grappa_amd.relax import CHECK_EVERY_DEFAULT, relax_graph
+    be = get_backend()
+    prop = torch.cuda.get_device_properties(0)
+    lines = [f"# command: python {' '.join(sys.argv)}",
+             f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}",
+             f"# device: {prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, {prop.total_memory / 2 ** 30:.0f} GiB; "
+             f"library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}",
+             f"# device events around whole runs of a fixed step count (tolerance 0), the sides of a size timed alternately, {args.reps} runs each "
+             "after one warm-up run each: ms per step = run time / steps, median (min .. max); this file is the tool's output, unedited"]
+    print("\n".join(lines), flush=True)
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def report(size, what, steps, ms, launches=None):
+        per = np.array(ms) / steps
+        say(f"{size:6s} {what:24s} {steps:4d} steps  {np.median(per):9.4f} ms/step (min {per.min():9.4f} .. max {per.max():9.4f})  "
+            f"run {np.median(ms):9.2f} ms" + (f"  {launches} library launches per run" if launches is not None else ""))
+        return float(np.median(per))
+
+    def launches_of(fn):
+        n0 = be.lib.grappa_launch_count(0)
+        fn()
+        torch.cuda.synchronize()
+        return int(be.lib.grappa_launch_count(0) - n0)
+
+    def ran(r, steps):
+        return f"all items ran {steps} steps: {bool((r.steps == steps).all()) and bool((r.status == 0).all())}"
+
+    opts = {**RELAX_DEFAULTS, "tolerance": 0.0}
+
+    # ---- (a) the pool: fused against stepwise
+    g, nb = pool_batch(args.mols, args.confs)
+    counts = g.batch_num_nodes_host("n1")
+    S = args.steps
+    say(f"(a) pool: {args.mols} molecules, {int(counts.sum())} atoms ({int(counts.min())}..{int(counts.max())} per molecule), C = {args.confs}, "
+        f"bonded + nonbonded, check_every = {CHECK_EVERY_DEFAULT}")
+    sides = {"fused": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=S),
+             "stepwise": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True)}
+    rf, rs_ = sides["fused"](), sides["stepwise"]()
+    say(f"pool   fused: {ran(rf, S)}; stepwise: {ran(rs_, S)}; largest |x_fused - x_stepwise| = {float((rf.xyz - rs_.xyz).abs().max()):.3e} A")
+    n = {k: launches_of(fn) for k, fn in sides.items()}
+    ms = timed_alternately(sides, args.reps)
+    pf, ps = report("pool", "fused", S, ms["fused"], n["fused"]), report("pool", "stepwise", S, ms["stepwise"], n["stepwise"])
+    say(f"pool   stepwise / fused = {ps / pf:.2f}x ms per step")
+    del g, nb
+
+    # ---- (b), (c) the chains: stepwise against composed
+    for tag, n_atoms, S, sweep in (("(b)", args.mid_atoms, args.steps, (1, 8, 32, 128)), ("(c)", args.big_atoms, args.big_steps, ())):
+        gh, nbp = chain_graph(n_atoms)
+        g, nb = gh.to("cuda"), NonbondedBatch([nbp]).to("cuda")
+        size = f"{n_atoms}"
+        say(f"{tag} chain: 1 molecule, {n_atoms} atoms, C = 1, {', '.join(f'{lv} {g.num_nodes(lv)}' for lv in ('n2', 'n3', 'n4'))}, "
+            f"{nb.n_exceptions} exceptions, bonded + nonbonded")
+        c = Composed(be, g, nb, opts)          # tables, clones and the nonbonded work-item list: built once, outside the timed region
+
+        def composed(S=S, c=c):
+            c.reset()
+            for _ in range(S):
+                c.step()
+        sides = {"stepwise": lambda S=S, g=g, nb=nb: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True), "composed": composed}
+        r = sides["stepwise"]()
+        composed()
+        say(f"{size:6s} stepwise: {ran(r, S)}; largest |x_stepwise - x_composed| after {S} steps = {float((r.xyz - c.x).abs().max()):.3e} A")
+        n = {k: launches_of(fn) for k, fn in sides.items()}
+        ms = timed_alternately(sides, args.reps)
+        ps = report(size, f"stepwise, check_every {CHECK_EVERY_DEFAULT}", S, ms["stepwise"], n["stepwise"])
+        pc = report(size, "composed", S, ms["composed"], n["composed"])
+        say(f"{size:6s} composed / stepwise = {pc / ps:.2f}x ms per step (the composed loop also issues its torch ops: not counted as library launches)")
+        if sweep:
+            sw = {f"check_every {ce}": (lambda ce=ce, S=S, g=g, nb=nb: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True, check_every=ce))
+                  for ce in sweep}
+            ms = timed_alternately(sw, args.reps)
+            for k in sw:
+                report(size, "stepwise, " + k, S, ms[k])
+        del g, nb, c
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
