@@ -90,6 +90,12 @@ class RelaxOpts(C.Structure):
                 ("n_min", C.c_int), ("f_inc", C.c_float), ("f_dec", C.c_float), ("alpha_start", C.c_float), ("f_alpha", C.c_float)]
 
 
+class MdOpts(C.Structure):
+    """grappa_md_opts (additions to ABI 11): the options of the fused Langevin dynamics, per call"""
+    _fields_ = [("dt", C.c_float), ("temperature", C.c_float), ("friction", C.c_float), ("init_temperature", C.c_float),
+                ("n_steps", C.c_int), ("save_every", C.c_int), ("first_step", C.c_uint)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -215,6 +221,11 @@ SIGNATURES = {
     "grappa_relax_steps_run_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz, _i, _vp]),
     "grappa_relax_steps_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # Langevin dynamics under the full force field (additions to ABI 11)
+    "grappa_md_langevin_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
+    "grappa_md_philox": (None, [_u64, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint * 4)]),
+    "grappa_md_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -278,3 +289,10 @@ def nonbonded_iblock() -> int:
 def relax_max_atoms() -> int:
     """atoms per molecule the fused minimiser takes at most (grappa_relax_max_atoms of the loaded library)"""
     return int(load().grappa_relax_max_atoms())
+
+
+def md_philox(key: int, c0: int, c1: int, c2: int, c3: int):
+    """Philox4x32-10 of the loaded library on the host (grappa_md_philox): the four output words"""
+    out = (C.c_uint * 4)()
+    load().grappa_md_philox(key, c0, c1, c2, c3, C.byref(out))
+    return tuple(int(w) for w in out)

@@ -91,6 +91,34 @@ def _flat(t: torch.Tensor, name: str, dev, dtype=torch.float32) -> None:
         raise ValueError(f"{name}: expected a contiguous {dtype} tensor on {dev}")
 
 
+def _nb_tables_desc(nb, N, Cc, B, dev, who):
+    """grappa_nb_desc of the device tables of a NonbondedBatch (atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma,
+    exc_eps) for the kernels that take their coordinates from the MM descriptor (xyz = NULL); None for nb = None"""
+    if nb is None:
+        return None
+    for n in ("atom_molptr", "exc_ptr", "exc_atom"):
+        t = getattr(nb, n)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
+        _flat(t, "nb." + n, dev, torch.int32)
+    for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
+        t = getattr(nb, n)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
+        _flat(t, "nb." + n, dev)
+    if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
+        raise ValueError(f"{who}: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
+    if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
+        raise ValueError(f"{who}: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+    nd = _lib.NbDesc()
+    nd.N, nd.C, nd.B = N, Cc, B
+    nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
+    nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
+    nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
+    nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
+    return nd
+
+
 DEFAULT_GEMM_PRECISION = "f32_f16x3"
 _P_F32, _P_BF16, _P_F16X3 = (_lib.GEMM_PRECISIONS[k] for k in ("f32", "bf16", "f32_f16x3"))
 
@@ -1957,28 +1985,7 @@ class HipBackend:
                 raise ValueError(f"relax_fire: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
             if counts and max(counts) > self.relax_max_atoms():
                 raise ValueError(f"relax_fire: a molecule of {max(counts)} atoms is above the limit of {self.relax_max_atoms()} atoms per molecule")
-        nd = None
-        if nb is not None:
-            for n in ("atom_molptr", "exc_ptr", "exc_atom"):
-                t = getattr(nb, n)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
-                _flat(t, "nb." + n, dev, torch.int32)
-            for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
-                t = getattr(nb, n)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
-                _flat(t, "nb." + n, dev)
-            if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
-                raise ValueError(f"relax_fire: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
-            if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
-                raise ValueError("relax_fire: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
-            nd = _lib.NbDesc()
-            nd.N, nd.C, nd.B = N, Cc, B
-            nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
-            nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
-            nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
-            nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_fire")
         o = _lib.RelaxOpts()
         names = [f[0] for f in _lib.RelaxOpts._fields_]
         if sorted(opts) != sorted(names):
@@ -2022,28 +2029,7 @@ class HipBackend:
         counts = [int(c) for c in atom_counts_host]
         if len(counts) != B or sum(counts) != N or (counts and min(counts) < 0):
             raise ValueError(f"relax_steps: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
-        nd = None
-        if nb is not None:
-            for n in ("atom_molptr", "exc_ptr", "exc_atom"):
-                t = getattr(nb, n)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
-                _flat(t, "nb." + n, dev, torch.int32)
-            for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
-                t = getattr(nb, n)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
-                _flat(t, "nb." + n, dev)
-            if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
-                raise ValueError(f"relax_steps: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
-            if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
-                raise ValueError("relax_steps: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
-            nd = _lib.NbDesc()
-            nd.N, nd.C, nd.B = N, Cc, B
-            nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
-            nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
-            nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
-            nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_steps")
         o = _lib.RelaxOpts()
         names = [f[0] for f in _lib.RelaxOpts._fields_]
         if sorted(opts) != sorted(names):
@@ -2079,6 +2065,75 @@ class HipBackend:
                 break
         _chk(self.lib.grappa_relax_steps_finish_f32(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
                                                     steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
+
+    # ------------------------------------------------------------------ dynamics
+    def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
+        """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
+        (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
+        as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
+        atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
+        init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
+        n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
+        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
+        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"md_langevin: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        N, Cc, B = d.N, d.C, d.B
+        o = _lib.MdOpts()
+        names = [f[0] for f in _lib.MdOpts._fields_]
+        if sorted(opts) != sorted(names):
+            raise ValueError(f"md_langevin: opts must hold exactly {names}, got {sorted(opts)}")
+        for k in names:
+            setattr(o, k, int(opts[k]) if k in ("n_steps", "save_every", "first_step") else float(opts[k]))
+        F = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
+        optional = ("vel_in", "frames_xyz", "frames_epot", "frames_ekin")
+        for t, n, dt in ((mass, "mass", torch.float32), (mol_key, "mol_key", torch.int64), (vel_in, "vel_in", torch.float32),
+                         (xyz_out, "xyz_out", torch.float32), (vel_out, "vel_out", torch.float32), (epot, "epot", torch.float32),
+                         (ekin, "ekin", torch.float32), (steps, "steps", torch.int32), (status, "status", torch.int32),
+                         (frames_xyz, "frames_xyz", torch.float32), (frames_epot, "frames_epot", torch.float32),
+                         (frames_ekin, "frames_ekin", torch.float32)):
+            if t is None and n in optional:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
+            _flat(t, n, dev, dt)
+        if mass.numel() != N or mol_key.numel() != B or any(t is not None and t.shape != xyz.shape for t in (vel_in, xyz_out, vel_out)) \
+                or any(t.numel() != B * Cc for t in (epot, ekin, steps, status)) \
+                or (frames_xyz is not None and frames_xyz.numel() != F * N * Cc * 3) \
+                or any(t is not None and t.numel() != F * B * Cc for t in (frames_epot, frames_ekin)):
+            raise ValueError(f"md_langevin: expected mass (N,), mol_key (B,), vel_in / xyz_out / vel_out (N,C,3), epot / ekin / steps / status "
+                             f"(B,C), frames_xyz ({F},N,C,3), frames_epot / frames_ekin ({F},B,C)")
+        if xyz.numel() and (xyz_out.data_ptr() == xyz.data_ptr() or (vel_in is not None and vel_out.data_ptr() == vel_in.data_ptr())):
+            raise ValueError("md_langevin: xyz_out / vel_out must not be the start coordinates / velocities")
+        if atom_counts_host is not None:
+            counts = [int(c) for c in atom_counts_host]
+            if len(counts) != B or sum(counts) != N:
+                raise ValueError(f"md_langevin: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
+            if counts and max(counts) > self.relax_max_atoms():
+                raise ValueError(f"md_langevin: a molecule of {max(counts)} atoms is above the limit of {self.relax_max_atoms()} atoms per molecule")
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
+        _chk(self.lib.grappa_md_langevin_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), mass.data_ptr(),
+                                             mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
+                                             ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),
+                                             _ptr(frames_ekin)), "grappa_md_langevin_f32")
+
+    def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
+        """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,
+        atom_molptr (B+1,) int32, C_ conformations, step = the global step index, purpose 0 (thermostat) or 1 (start velocities)
+        -> out (N, C_, 3) float32"""
+        for t, n, dt in ((mol_key, "mol_key", torch.int64), (atom_molptr, "atom_molptr", torch.int32), (out, "out", torch.float32)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{n}: expected a contiguous {dt} tensor")
+            _flat(t, n, out.device, dt)
+        B = mol_key.numel()
+        if atom_molptr.numel() != B + 1 or out.dim() != 3 or out.shape[1] != C_ or out.shape[2] != 3:
+            raise ValueError("md_noise: expected mol_key (B,), atom_molptr (B+1,), out (N,C,3)")
+        if not (0 <= int(step) < 2 ** 32 and 0 <= int(purpose) < 2 ** 32):
+            raise ValueError(f"md_noise: step and purpose must lie in [0, 2^32), got {step}, {purpose}")
+        _chk(self.lib.grappa_md_noise_f32(self._stream(), mol_key.data_ptr(), atom_molptr.data_ptr(), out.shape[0], int(C_), B, int(step),
+                                          int(purpose), out.data_ptr()), "grappa_md_noise_f32")
 
     # ------------------------------------------------------------------ loss
     def loss_ef(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B, loss_mol, gE, gG) -> None:

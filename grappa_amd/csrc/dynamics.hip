@@ -1,0 +1,364 @@
+// Fused Langevin molecular dynamics (BAOAB, Leimkuhler and Matthews 2013) under the full MM force field (bonded terms of
+// csrc/mm_energy.hip + Lennard-Jones / Coulomb of csrc/nonbonded.hip), fp32, xyz[N,C,3] (include/grappa_hip.h grappa_md_langevin_f32).
+//   item   : one workgroup of 256 threads per (molecule, conformation), as in csrc/relax.hip: it loads the molecule once, runs n_steps
+//            steps and writes its results.  Workgroups never talk to each other: an item's bits depend on its own input only.
+//   LDS    : the image of csrc/rx_force.h (x, y, z, q, sigma / 2, sqrt(eps), the partial gradients of one step, the reduction words)
+//            plus 256 floats and a double for the kinetic energy: 19.6 KB at any molecule size up to RX_MAX atoms.  Velocities,
+//            gradients, the mass and the two per-atom factors (dt / 2 ACC / m, c2 sqrt(ACC kB T / m)) stay in the registers of the
+//            atom's owner (thread a % 256).
+//   step   : the owner kicks, drifts, draws the thermostat's noise and drifts again (its own atoms only: no barrier in between),
+//            barrier; the partial gradients of rx_bonded / rx_pairs per (atom, slice), barrier; the owner adds the slices in slice
+//            order and the flag of a non-finite gradient is reduced (one barrier); the closing kick.  Three barriers per step.
+//   frame  : every save_every steps the coordinates and, if asked for, the energies: the six potential terms as thread partials in
+//            sh.part (its readers of this step passed the reduction's barrier), barrier, seven threads add them and the kinetic partials
+//            in double in thread order, barrier.  The next step's partial gradients are written after that barrier and the one that
+//            follows its drift, so they cannot overwrite what the seven threads read.  Two barriers per frame with energies.
+//   noise  : Philox4x32-10 (csrc/md_philox.h), key = mol_key[b], counter = (atom in molecule, conformation, global step, purpose);
+//            nothing is kept between steps or launches, so a run can be cut anywhere and continued with first_step advanced.
+// The loop runs n_steps (<= MD_STEP_CAP) iterations: the kernel always terminates.
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+#include "md_philox.h"
+#include "rx_force.h"
+
+namespace {
+
+constexpr int MD_STEP_CAP = 1000000;
+constexpr double MD_ACC = 418.4;               // 1 kcal/mol = 418.4 amu A^2 / ps^2
+constexpr double MD_KB = 0.0019872041;         // kcal/mol/K
+
+struct MdArgs {
+    grappa_mm_desc mm;
+    grappa_nb_desc nb;
+    int has_nb;
+    float h2, hk;                // dt / 2, dt / 2 ACC
+    float c1, c2;                // exp(-friction dt), sqrt(1 - c1^2)
+    float kt, kt0;               // ACC kB temperature, ACC kB init_temperature
+    int thermostat;              // friction > 0
+    int n_steps, save_every;
+    unsigned first_step;
+    const float* mass;
+    const unsigned long long* mol_key;
+    const float* vel_in;
+    float *xyz_out, *vel_out, *epot, *ekin;
+    int *steps, *status;
+    float *frames_xyz, *frames_epot, *frames_ekin;
+};
+
+// sqrt(-2 ln u) for u = ((w >> 8) + 0.5) 2^-24.  Both logarithms get an argument that fp32 holds exactly: n + 0.5 has at most 24
+// bits below 2^23, and above it 1 - u = ((2^24 - 1 - n) + 0.5) 2^-24 has.  u > 0 always.
+__device__ inline float md_radius(uint32_t w) {
+    const uint32_t n = w >> 8;
+    const float l = n < (1u << 23) ? logf(((float)n + 0.5f) * 0x1p-24f) : log1pf(-(((float)(0xFFFFFFu - n) + 0.5f) * 0x1p-24f));
+    return sqrtf(-2.0f * l);
+}
+
+// the three normal deviates of (key, atom in molecule, conformation, step, purpose): Box-Muller on 24-bit uniforms of one Philox call
+__device__ inline V3 md_normal3(unsigned long long key, unsigned atom, unsigned conf, unsigned step, unsigned purpose) {
+    uint32_t w[4];
+    grappa_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), atom, conf, step, purpose, w);
+    float sn, cs;
+    sincospif((float)(w[1] >> 8) * 0x1p-23f, &sn, &cs);          // the angle 2 pi (w >> 8) 2^-24 in half turns: exact in fp32
+    const float cz = cospif((float)(w[3] >> 8) * 0x1p-23f);
+    const float r0 = md_radius(w[0]), r2 = md_radius(w[2]);
+    return {r0 * cs, r0 * sn, r2 * cz};
+}
+
+// g = grad E at the coordinates in LDS, into the owners' registers; true (in every thread) if a gradient is not finite.  Two barriers.
+__device__ __forceinline__ bool md_force(const MdArgs& a, RxShared& sh, int m0, int n, int s, int JS, int il0, bool active, V3 (&g)[RX_APT]) {
+    const int t = threadIdx.x;
+    if (active)
+        for (int il = il0; il < n; il += RX_NT) {
+            V3 p = rx_bonded(a.mm, sh, m0 + il, s, JS, m0, n);
+            if (a.has_nb) {
+                float elj = 0.f, ec = 0.f;
+                rx_pairs(a.nb, sh, il, s, JS, m0, n, elj, ec, p.x, p.y, p.z);
+            }
+            const int u = s * n + il;
+            sh.part[u] = p.x, sh.part[RX_MAX + u] = p.y, sh.part[2 * RX_MAX + u] = p.z;
+        }
+    __syncthreads();
+    float bad = 0.f;
+#pragma unroll
+    for (int k = 0; k < RX_APT; ++k) {
+        const int il = t + k * RX_NT;
+        if (il < n) {
+            V3 gi = {sh.part[il], sh.part[RX_MAX + il], sh.part[2 * RX_MAX + il]};
+            for (int q = 1; q < JS; ++q) {
+                const int u = q * n + il;
+                gi.x += sh.part[u], gi.y += sh.part[RX_MAX + u], gi.z += sh.part[2 * RX_MAX + u];
+            }
+            g[k] = gi;
+            if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;
+        }
+    }
+    return rx_reduce_max(bad, sh.wmax) != 0.f;
+}
+
+// the potential energy (six terms: thread partials in fp32, added in double in thread order, as at the end of relax_fire_kernel) and
+// the kinetic energy 0.5 / ACC sum m v^2 (the owners' partials, added the same way) of the state held -> (epot, ekin) in thread 0.
+// sh.part must be free: every reader of the last partial gradients has passed a barrier.  Two barriers.
+__device__ __forceinline__ float2 md_energies(const MdArgs& a, RxShared& sh, float* kin, double* ksum, int b, int m0, int n, int s, int JS,
+                                              int il0, bool active, const V3 (&v)[RX_APT], const float (&ms)[RX_APT]) {
+    const grappa_mm_desc& d = a.mm;
+    const int t = threadIdx.x;
+    float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int tt = d.mol_ptr[0][b] + t; tt < d.mol_ptr[0][b + 1]; tt += RX_NT) {
+        V3 u;
+        const float dx = bond_geom(rx_ld(sh, d.idx[0][2 * tt], m0, n), rx_ld(sh, d.idx[0][2 * tt + 1], m0, n), u) - d.eq[0][tt];
+        e[0] += 0.5f * d.k[0][tt] * dx * dx;
+    }
+    for (int tt = d.mol_ptr[1][b] + t; tt < d.mol_ptr[1][b + 1]; tt += RX_NT) {
+        V3 e0, e2;
+        const float dx = angle_geom(rx_ld(sh, d.idx[1][3 * tt], m0, n), rx_ld(sh, d.idx[1][3 * tt + 1], m0, n),
+                                    rx_ld(sh, d.idx[1][3 * tt + 2], m0, n), e0, e2) - d.eq[1][tt];
+        e[1] += 0.5f * d.k[1][tt] * dx * dx;
+    }
+    for (int l = 2; l < 4; ++l)
+        for (int tt = d.mol_ptr[l][b] + t; tt < d.mol_ptr[l][b + 1]; tt += RX_NT) {
+            V3 d0, d1, d2, d3;
+            const int* id = d.idx[l] + 4 * (size_t)tt;
+            const float phi = dihedral_geom(rx_ld(sh, id[0], m0, n), rx_ld(sh, id[1], m0, n), rx_ld(sh, id[2], m0, n), rx_ld(sh, id[3], m0, n),
+                                            d0, d1, d2, d3);
+            e[l] += torsion_energy(d.k[l] + (size_t)tt * d.n_per[l], d.n_per[l], phi, d.offset_torsion);
+        }
+    if (a.has_nb && active)
+        for (int il = il0; il < n; il += RX_NT) {
+            float gx = 0.f, gy = 0.f, gz = 0.f;
+            rx_pairs(a.nb, sh, il, s, JS, m0, n, e[4], e[5], gx, gy, gz);
+        }
+    float mv2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < RX_APT; ++k)
+        if (t + k * RX_NT < n) mv2 += ms[k] * dot(v[k], v[k]);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) sh.part[q * RX_NT + t] = e[q];
+    kin[t] = mv2;
+    __syncthreads();
+    if (t < 6) {
+        double sum = 0.0;
+        for (int k = 0; k < RX_NT; ++k) sum += (double)sh.part[t * RX_NT + k];
+        sh.esum[t] = t < 4 ? sum : 0.5 * sum;          // every pair was counted from both of its atoms
+    } else if (t == 6) {
+        double sum = 0.0;
+        for (int k = 0; k < RX_NT; ++k) sum += (double)kin[k];
+        *ksum = (0.5 / MD_ACC) * sum;
+    }
+    __syncthreads();
+    float2 out = make_float2(0.f, 0.f);
+    if (t == 0) {
+        double tot = 0.0;
+        for (int q = 0; q < 6; ++q) tot += sh.esum[q];
+        out = make_float2((float)tot, (float)*ksum);
+    }
+    return out;
+}
+
+__global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
+    __shared__ RxShared sh;
+    __shared__ float kin[RX_NT];
+    __shared__ double ksum;
+    const grappa_mm_desc& d = a.mm;
+    const int C = d.C, t = threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)C), c = (int)(blockIdx.x - (unsigned)b * (unsigned)C);
+    const size_t item = (size_t)b * C + c;
+    const int m0 = rx_clamp(d.atom_molptr[b], d.N), m1 = rx_clamp(d.atom_molptr[b + 1], d.N);
+    const int n = m1 - m0;
+    if (n <= 0) return;
+    if (n > RX_MAX) {          // above the size limit: status 3 and nothing else
+        if (t == 0) a.status[item] = 3;
+        return;
+    }
+    for (int il = t; il < n; il += RX_NT) {
+        const float* p = d.xyz + ((size_t)(m0 + il) * C + c) * 3;
+        sh.xs[il] = make_float4(p[0], p[1], p[2], a.has_nb ? a.nb.charge[m0 + il] : 0.f);
+        sh.ps[il] = a.has_nb ? make_float2(0.5f * a.nb.sigma[m0 + il], sqrtf(a.nb.epsilon[m0 + il])) : make_float2(0.f, 0.f);
+    }
+    // the thread's (atom, slice), as in relax_fire_kernel
+    const int JS = n > RX_NT ? 1 : (RX_NT / n < RX_JS ? RX_NT / n : RX_JS);
+    const int s = n > RX_NT ? 0 : t / n;
+    const int il0 = t - s * n;
+    const bool active = s < JS;
+    const unsigned long long key = a.mol_key[b];
+
+    // the owner's atoms: mass (0: frozen), the kick and noise factors, the start velocity
+    V3 v[RX_APT], g[RX_APT];
+    float ms[RX_APT], kw[RX_APT], sg[RX_APT];
+#pragma unroll
+    for (int k = 0; k < RX_APT; ++k) {
+        const int il = t + k * RX_NT;
+        v[k] = {0.f, 0.f, 0.f}, g[k] = {0.f, 0.f, 0.f};
+        ms[k] = 0.f, kw[k] = 0.f, sg[k] = 0.f;
+        if (il < n) {
+            const float m = a.mass[m0 + il];
+            if (m > 0.f) {          // (a mass that is zero, negative or NaN: a frozen atom, v = 0)
+                const float w = 1.0f / m;
+                ms[k] = m, kw[k] = a.hk * w, sg[k] = a.c2 * sqrtf(a.kt * w);
+                if (a.vel_in) {
+                    const float* p = a.vel_in + ((size_t)(m0 + il) * C + c) * 3;
+                    v[k] = {p[0], p[1], p[2]};
+                } else if (a.kt0 > 0.f) {
+                    v[k] = sqrtf(a.kt0 * w) * md_normal3(key, (unsigned)il, (unsigned)c, a.first_step, 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // one force evaluation per pass: the pass closes step `steps` (none on the first pass), tests the gradient and opens the next step
+    bool bad;
+    int steps = 0, since = 0, frame = 0;
+    for (;;) {
+        bad = md_force(a, sh, m0, n, s, JS, il0, active, g);
+        bool due = false;
+        if (steps > 0) {
+            // ---- the closing B of the step, and its frame's coordinates
+#pragma unroll
+            for (int kk = 0; kk < RX_APT; ++kk)
+                if (t + kk * RX_NT < n && kw[kk] > 0.f) v[kk] = v[kk] - kw[kk] * g[kk];
+            if (a.save_every > 0 && ++since == a.save_every) {
+                since = 0;
+                due = true;
+                if (a.frames_xyz) {
+                    float* fx = a.frames_xyz + (size_t)frame * d.N * C * 3;
+#pragma unroll
+                    for (int kk = 0; kk < RX_APT; ++kk) {
+                        const int il = t + kk * RX_NT;
+                        if (il < n) {
+                            const size_t off = ((size_t)(m0 + il) * C + c) * 3;
+                            const float4 x = sh.xs[il];
+                            fx[off] = x.x, fx[off + 1] = x.y, fx[off + 2] = x.z;
+                        }
+                    }
+                }
+            }
+        }
+        // ---- the energies: of a frame that asks for them, and of the state the run ends with
+        const bool last = bad || steps >= a.n_steps;
+        if (last || (due && (a.frames_epot || a.frames_ekin))) {
+            const float2 e = md_energies(a, sh, kin, &ksum, b, m0, n, s, JS, il0, active, v, ms);
+            if (t == 0) {
+                const size_t fo = (size_t)frame * d.B * C + item;
+                if (due && a.frames_epot) a.frames_epot[fo] = e.x;
+                if (due && a.frames_ekin) a.frames_ekin[fo] = e.y;
+                if (last) a.epot[item] = e.x, a.ekin[item] = e.y;
+            }
+        }
+        if (due) ++frame;
+        if (last) break;
+        // ---- B, A, O, A on the owner's atoms (a frozen atom is not touched)
+#pragma unroll
+        for (int kk = 0; kk < RX_APT; ++kk) {
+            const int il = t + kk * RX_NT;
+            if (il < n && kw[kk] > 0.f) {
+                V3 vk = v[kk] - kw[kk] * g[kk];
+                float4 x = sh.xs[il];
+                x.x += a.h2 * vk.x, x.y += a.h2 * vk.y, x.z += a.h2 * vk.z;
+                if (a.thermostat) vk = a.c1 * vk + sg[kk] * md_normal3(key, (unsigned)il, (unsigned)c, a.first_step + (unsigned)steps, 0u);
+                x.x += a.h2 * vk.x, x.y += a.h2 * vk.y, x.z += a.h2 * vk.z;
+                sh.xs[il] = x;
+                v[kk] = vk;
+            }
+        }
+        ++steps;
+        __syncthreads();
+    }
+
+    // ---- results: the state held and its energies
+#pragma unroll
+    for (int k = 0; k < RX_APT; ++k) {
+        const int il = t + k * RX_NT;
+        if (il < n) {
+            const size_t off = ((size_t)(m0 + il) * C + c) * 3;
+            const float4 x = sh.xs[il];
+            a.xyz_out[off] = x.x, a.xyz_out[off + 1] = x.y, a.xyz_out[off + 2] = x.z;
+            a.vel_out[off] = v[k].x, a.vel_out[off + 1] = v[k].y, a.vel_out[off + 2] = v[k].z;
+        }
+    }
+    if (t == 0) {
+        a.steps[item] = steps;
+        a.status[item] = bad ? 2 : 0;
+    }
+}
+
+// z of (atom, conformation) for one step and purpose, as md_langevin_kernel draws it: a thread per (atom, conformation)
+__global__ __launch_bounds__(256) void md_noise_kernel(const unsigned long long* __restrict__ mol_key, const int* __restrict__ atom_molptr, int N,
+                                                       int C, int B, unsigned step, unsigned purpose, float* __restrict__ out) {
+    const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= (size_t)N * C) return;
+    const int atom = (int)(u / (unsigned)C), c = (int)(u - (size_t)atom * C);
+    int lo = 0, hi = B - 1;          // the last molecule that starts at or before the atom
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rx_clamp(atom_molptr[mid], N) <= atom) lo = mid; else hi = mid - 1;
+    }
+    const int m0 = rx_clamp(atom_molptr[lo], N), m1 = rx_clamp(atom_molptr[lo + 1], N);
+    V3 z = {0.f, 0.f, 0.f};          // (an atom that no molecule holds)
+    if (atom >= m0 && atom < m1) z = md_normal3(mol_key[lo], (unsigned)(atom - m0), (unsigned)c, step, purpose);
+    out[3 * u] = z.x, out[3 * u + 1] = z.y, out[3 * u + 2] = z.z;
+}
+
+}  // namespace
+
+extern "C" void grappa_md_philox(unsigned long long key, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned out[4]) {
+    uint32_t w[4];
+    grappa_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), c0, c1, c2, c3, w);
+    for (int k = 0; k < 4; ++k) out[k] = w[k];
+}
+
+extern "C" int grappa_md_noise_f32(void* stream, const unsigned long long* mol_key, const int* atom_molptr, int N, int C, int B, unsigned step,
+                                   unsigned purpose, float* out) {
+    if (N < 0 || C < 0 || B < 0) return GRAPPA_ERR_ARG;
+    if (N == 0 || C == 0 || B == 0) return GRAPPA_OK;
+    if (!mol_key || !atom_molptr || !out || (long long)N * C > INT_MAX) return GRAPPA_ERR_ARG;
+    const unsigned blocks = (unsigned)(((long long)N * C + 255) / 256);
+    GRAPPA_LAUNCH(md_noise_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), mol_key, atom_molptr, N, C, B, step, purpose, out);
+    return grappa_launch_status();
+}
+
+extern "C" int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const float* mass,
+                                      const unsigned long long* mol_key, const float* vel_in, float* xyz_out, float* vel_out, float* epot,
+                                      float* ekin, int* steps, int* status, float* frames_xyz, float* frames_epot, float* frames_ekin) {
+    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0) return GRAPPA_ERR_ARG;
+    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
+    // (comparisons written so that a NaN is refused)
+    if (!(o->dt > 0.f && o->dt <= FLT_MAX) || !(o->temperature >= 0.f && o->temperature <= FLT_MAX) ||
+        !(o->friction >= 0.f && o->friction <= FLT_MAX) || !(o->init_temperature >= 0.f && o->init_temperature <= FLT_MAX))
+        return GRAPPA_ERR_ARG;
+    if (o->n_steps < 0 || o->n_steps > MD_STEP_CAP || o->save_every < 0) return GRAPPA_ERR_ARG;
+    if ((unsigned long long)o->first_step + (unsigned long long)o->n_steps >= (1ull << 32)) return GRAPPA_ERR_ARG;
+    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return GRAPPA_OK;
+    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status)
+        return GRAPPA_ERR_ARG;
+    long long tuples = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (mm->T[l] < 0 || mm->T[l] >= (1 << 27) || !mm->mol_ptr[l]) return GRAPPA_ERR_ARG;
+        if (mm->T[l] > 0 && (!mm->idx[l] || !mm->k[l])) return GRAPPA_ERR_ARG;
+        if (l < 2 && mm->T[l] > 0 && !mm->eq[l]) return GRAPPA_ERR_ARG;
+        if (l >= 2 && (mm->n_per[l] < 1 || mm->n_per[l] > 8)) return GRAPPA_ERR_ARG;
+        tuples += mm->T[l];
+    }
+    if (tuples > 0 && !mm->inc_code) return GRAPPA_ERR_ARG;
+    if (nb && (!nb->charge || !nb->sigma || !nb->epsilon || !nb->exc_ptr || !nb->exc_atom || !nb->exc_qq || !nb->exc_sigma || !nb->exc_eps))
+        return GRAPPA_ERR_ARG;
+    if ((long long)mm->B * mm->C > INT_MAX) return GRAPPA_ERR_ARG;
+    MdArgs a;
+    a.mm = *mm;
+    a.has_nb = nb != nullptr;
+    if (nb) a.nb = *nb; else a.nb = grappa_nb_desc{};
+    // the step's constants, formed in double and rounded once
+    const double dt = (double)o->dt, c1 = exp(-(double)o->friction * dt);
+    a.h2 = (float)(0.5 * dt), a.hk = (float)(0.5 * dt * MD_ACC);
+    a.c1 = (float)c1, a.c2 = (float)sqrt(1.0 - c1 * c1);
+    a.kt = (float)(MD_ACC * MD_KB * (double)o->temperature), a.kt0 = (float)(MD_ACC * MD_KB * (double)o->init_temperature);
+    a.thermostat = o->friction > 0.f;
+    a.n_steps = o->n_steps, a.save_every = o->save_every, a.first_step = o->first_step;
+    a.mass = mass, a.mol_key = mol_key, a.vel_in = vel_in;
+    a.xyz_out = xyz_out, a.vel_out = vel_out, a.epot = epot, a.ekin = ekin, a.steps = steps, a.status = status;
+    a.frames_xyz = frames_xyz, a.frames_epot = frames_epot, a.frames_ekin = frames_ekin;
+    GRAPPA_LAUNCH(md_langevin_kernel, dim3((unsigned)(mm->B * mm->C)), dim3(RX_NT), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return grappa_launch_status();
+}

@@ -1,0 +1,212 @@
+"""Langevin molecular dynamics of molecules on the device under the full MM force field: the bonded terms Grappa predicts plus,
+optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all pairs.  One launch of csrc/dynamics.hip
+(`grappa_md_langevin_f32` through `HipBackend.md_langevin`) runs many steps of every (molecule, conformation): one workgroup each,
+coordinates in LDS, velocities in registers, no host round trip per step.  Molecules of up to `relax_max_atoms()` atoms; constraints,
+cutoffs, periodic boxes, PME and larger molecules are out of scope (OpenMM / GROMACS).
+
+The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
+stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
+mass 0 is frozen.  The random stream has no state: an atom's noise is a function of its molecule's 64-bit key (`mol_keys`), its index
+in the molecule, the conformation and the global step, so a molecule's trajectory does not depend on its place in a batch, and a run can
+be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An item stops with a status:
+    0  ran n_steps steps
+    2  non-finite gradient (for example two non-excluded atoms on one point): stopped, the state is the one it held
+    3  the molecule has more than `relax_max_atoms()` atoms: not run (`simulate_graph` refuses such a batch before the launch)
+The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
+has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .nonbonded import NonbondedBatch, NonbondedParameters
+from .parameters import Parameters
+from .relax import graph_coordinates, graph_force_field, graph_from_parameters
+
+MD_DEFAULTS = {"dt": 0.001, "temperature": 300.0, "friction": 1.0, "init_temperature": None, "n_steps": 1000, "save_every": 0}
+MAX_STEPS_PER_LAUNCH = 1000000      # the library's cap on n_steps of one call
+STEPS_PER_LAUNCH_DEFAULT = 10000    # untuned: it only keeps one launch short
+KB = 0.0019872041                   # kcal/mol/K (the library's value)
+
+
+def md_options(**opts) -> dict:
+    """the six options of a run: MD_DEFAULTS overridden by `opts`, checked (the library checks them again, per launch).
+    init_temperature None (the default): the thermostat's temperature"""
+    unknown = sorted(set(opts) - set(MD_DEFAULTS))
+    if unknown:
+        raise TypeError(f"unknown dynamics option(s) {unknown}; the options are {sorted(MD_DEFAULTS)}")
+    o = {**MD_DEFAULTS, **opts}
+    if o["init_temperature"] is None:
+        o["init_temperature"] = o["temperature"]
+    for k in ("n_steps", "save_every"):
+        if isinstance(o[k], bool) or int(o[k]) != o[k] or o[k] < 0:
+            raise ValueError(f"{k} must be a non-negative integer, got {o[k]}")
+        o[k] = int(o[k])
+    for k in ("dt", "temperature", "friction", "init_temperature"):
+        if isinstance(o[k], bool) or not isinstance(o[k], (int, float, np.integer, np.floating)):
+            raise ValueError(f"{k} must be a number, got {o[k]!r}")
+    if not (np.isfinite(o["dt"]) and o["dt"] > 0):
+        raise ValueError(f"dt must be positive and finite, got {o['dt']}")
+    for k in ("temperature", "friction", "init_temperature"):
+        if not (np.isfinite(o[k]) and o[k] >= 0):
+            raise ValueError(f"{k} must be non-negative and finite, got {o[k]}")
+    return o
+
+
+def mol_keys(seed: int, B: int) -> np.ndarray:
+    """(B,) uint64: the key of molecule b is output b of splitmix64 seeded with `seed` -- distinct molecules of a batch get distinct
+    streams, and the same (seed, b) the same one"""
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    m = (1 << 64) - 1
+    out = np.empty(B, dtype=np.uint64)
+    for b in range(B):
+        z = (int(seed) + (b + 1) * 0x9E3779B97F4A7C15) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        out[b] = z ^ (z >> 31)
+    return out
+
+
+@dataclass
+class MDResult:
+    """xyz, velocities: the state after the last step; potential_energy, kinetic_energy (kcal/mol) and temperature
+    (2 ekin / (3 n_moving kB), n_moving = the molecule's atoms of non-zero mass; no degrees of freedom are removed) there; steps;
+    status (see the module text); frames, frame_potential_energy, frame_kinetic_energy: one entry per `save_every` steps, or None.
+    From `simulate_graph`: tensors on the graph's device, xyz / velocities (N, C, 3), frames (F, N, C, 3), frame energies (F, B, C),
+    the others (B, C); a frame that was not reached (status 2) is NaN.  From `simulate`: numpy arrays of one molecule, xyz / velocities
+    (n_confs, n_atoms, 3), frames (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames), the others (n_confs,)."""
+    xyz: object
+    velocities: object
+    potential_energy: object
+    kinetic_energy: object
+    temperature: object
+    steps: object
+    status: object
+    frames: object = None
+    frame_potential_energy: object = None
+    frame_kinetic_energy: object = None
+
+
+def _host_masses(masses, N):
+    """(N,) float32 on the host, checked: finite and >= 0"""
+    if isinstance(masses, torch.Tensor):
+        masses = masses.detach().cpu().numpy()
+    m = np.asarray(masses, dtype=np.float64).reshape(-1)
+    if m.shape[0] != N:
+        raise ValueError(f"masses must hold one value per atom ({N}), got {m.shape[0]}")
+    if not (np.isfinite(m).all() and (m >= 0).all()):
+        raise ValueError("masses must be finite and >= 0 (0: a frozen atom)")
+    return m.astype(np.float32)
+
+
+def _host_keys(keys, seed, B):
+    if keys is None:
+        return mol_keys(seed, B)
+    k = np.asarray(keys)
+    if k.dtype.kind not in "ui" or k.reshape(-1).shape[0] != B:
+        raise ValueError(f"keys must hold one 64-bit integer per molecule ({B})")
+    return k.reshape(-1).astype(np.uint64)
+
+
+def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
+                   steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
+                   offset_torsion: bool = False, **opts) -> MDResult:
+    """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
+    `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
+    checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
+    velocities: (N, C, 3) on the graph's device, or None: drawn at `init_temperature`.  keys: one 64-bit key per molecule (default
+    `mol_keys(seed, B)`).  first_step: the global index of the first step -- to continue a run, pass its xyz, its velocities and
+    first_step + the steps it ran.  steps_per_launch: a run is cut into launches of at most this many steps (rounded down to a
+    multiple of `save_every`); the result does not depend on it, it only keeps one launch short.  **opts: see MD_DEFAULTS.
+    No device sync; a molecule above `relax_max_atoms()` atoms is refused here, on the host.  The graph is not modified."""
+    from .backend import get_backend
+    o = md_options(**opts)
+    if isinstance(steps_per_launch, bool) or not isinstance(steps_per_launch, (int, np.integer)) or steps_per_launch < 1:
+        raise ValueError(f"steps_per_launch must be an integer >= 1, got {steps_per_launch!r}")
+    if isinstance(first_step, bool) or int(first_step) != first_step or first_step < 0 or int(first_step) + o["n_steps"] >= 2 ** 32:
+        raise ValueError(f"first_step must be a non-negative integer with first_step + n_steps < 2^32, got {first_step!r}")
+    terms = list(terms)
+    xyz, plan, counts = graph_coordinates(g, terms)
+    dev = xyz.device
+    limit = get_backend().relax_max_atoms()
+    if counts and max(counts) > limit:
+        raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics")
+    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
+    N, B, C = plan.N, plan.B, xyz.shape[1]
+    m_host = _host_masses(masses, N)
+    k_host = _host_keys(keys, seed, B)
+    mass = torch.from_numpy(m_host).to(dev)
+    key = torch.from_numpy(k_host.view(np.int64).copy()).to(dev)
+    n_moving = torch.tensor([[max(int((m_host[p0:p0 + n] > 0).sum()), 1)] for p0, n in zip(np.cumsum([0] + counts[:-1]), counts)],
+                            dtype=torch.float32).reshape(B, 1).to(dev)
+    vel = None
+    if velocities is not None:
+        if not isinstance(velocities, torch.Tensor) or velocities.shape != xyz.shape or velocities.device != dev:
+            raise ValueError(f"velocities must be a {tuple(xyz.shape)} tensor on {dev}")
+        vel = velocities.detach().float().contiguous()
+    n_steps, every = o["n_steps"], o["save_every"]
+    chunk = min(int(steps_per_launch), MAX_STEPS_PER_LAUNCH)
+    if every > 0:
+        chunk = max(chunk // every, 1) * every
+        if chunk > MAX_STEPS_PER_LAUNCH:
+            raise ValueError(f"save_every must not exceed {MAX_STEPS_PER_LAUNCH}, got {every}")
+    F = n_steps // every if every > 0 else 0
+    f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+    frames = fe = fk = None
+    if F:
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)      # noqa: E731
+        frames, fe, fk = nan(F, N, C, 3), nan(F, B, C), nan(F, B, C)
+    bufs = [(torch.empty_like(xyz), torch.empty_like(xyz)) for _ in range(2 if n_steps > chunk else 1)]
+    epot, ekin = f32(B, C), f32(B, C)
+    steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
+    total = torch.zeros(B, C, dtype=torch.int32, device=dev)
+    x_in, v_in, done, launch = xyz, vel, 0, 0
+    while True:
+        n = min(chunk, n_steps - done)
+        f0, f1 = (done // every, (done + n) // every) if every > 0 else (0, 0)
+        x_out, v_out = bufs[launch % len(bufs)]
+        call = {"dt": o["dt"], "temperature": o["temperature"], "friction": o["friction"], "init_temperature": o["init_temperature"],
+                "n_steps": n, "save_every": every, "first_step": int(first_step) + done}
+        get_backend().md_langevin(plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin,
+                                  steps, status, frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
+                                  frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
+        total += steps
+        x_in, v_in, done, launch = x_out, v_out, done + n, launch + 1
+        if done >= n_steps:
+            break
+    return MDResult(x_in, v_in, epot, ekin, 2.0 * ekin / (3.0 * KB * n_moving), total, status, frames, fe, fk)
+
+
+def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
+             seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, **opts) -> MDResult:
+    """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
+    velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
+    velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
+    (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  See `simulate_graph`."""
+    md_options(**opts)
+    g = graph_from_parameters(parameters, xyz)
+    n = g.num_nodes("n1")
+    nb = None
+    if nonbonded is not None:
+        if not isinstance(nonbonded, NonbondedParameters):
+            raise TypeError(f"nonbonded must be NonbondedParameters or None, got {type(nonbonded).__name__}")
+        if nonbonded.n_atoms != n:
+            raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {n}")
+        nb = NonbondedBatch([nonbonded]).to(device)
+    m_host = _host_masses(masses, n)
+    vel = None
+    if velocities is not None:
+        v = np.asarray(velocities, dtype=np.float32)
+        if v.shape != np.asarray(xyz).shape:
+            raise ValueError(f"velocities must have the shape of xyz {np.asarray(xyz).shape}, got {v.shape}")
+        vel = torch.from_numpy(np.ascontiguousarray(v.transpose(1, 0, 2))).to(device)
+    r = simulate_graph(g.to(device), m_host, nb, velocities=vel, seed=seed, keys=keys, first_step=first_step, steps_per_launch=steps_per_launch, **opts)
+    np64 = lambda t: t.cpu().numpy().astype(np.float64)      # noqa: E731
+    confs = lambda t: np64(t).transpose(1, 0, 2)      # noqa: E731  (N, C, 3) -> (C, N, 3)
+    has = r.frames is not None
+    return MDResult(confs(r.xyz), confs(r.velocities), np64(r.potential_energy)[0], np64(r.kinetic_energy)[0], np64(r.temperature)[0],
+                    r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0], np64(r.frames).transpose(2, 0, 1, 3) if has else None,
+                    np64(r.frame_potential_energy)[:, 0].T if has else None, np64(r.frame_kinetic_energy)[:, 0].T if has else None)

@@ -84,6 +84,35 @@ def _stepwise_options(stepwise, check_every):
     return stepwise, int(check_every)
 
 
+def graph_coordinates(g, terms):
+    """what the fused kernels read of a parametrised batched graph before anything is checked against it: -> xyz (N, C, 3) float32
+    contiguous on the graph's device, the graph's plan and the atoms per molecule as host numbers (no device sync)"""
+    for t in terms:
+        if t not in TUPLE_LEVELS:
+            raise ValueError(f"term {t} not in {TUPLE_LEVELS}")
+    n1 = g.nodes["n1"].data
+    if "xyz" not in n1:
+        raise ValueError("xyz coordinates must be stored in g.nodes['n1'].data['xyz']")
+    xyz = n1["xyz"].detach()
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (N, C, 3), got {tuple(xyz.shape)}")
+    return xyz.float().contiguous(), g.plan(), [int(c) for c in g.batch_num_nodes_host("n1")]
+
+
+def graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev):
+    """checks that `nonbonded` (a NonbondedBatch or None) describes the graph's molecules on its device -> the MM tables ks, eqs, n_per"""
+    if nonbonded is not None:
+        if not isinstance(nonbonded, NonbondedBatch):
+            raise TypeError(f"nonbonded must be a NonbondedBatch or None, got {type(nonbonded).__name__}")
+        if nonbonded.N != plan.N or nonbonded.B != plan.B or nonbonded.atom_molptr_host.tolist() != np.concatenate([[0], np.cumsum(counts)]).tolist():
+            raise ValueError(f"the nonbonded batch ({nonbonded.B} molecules, {nonbonded.N} atoms) does not describe the graph's molecules "
+                             f"({plan.B} molecules, {plan.N} atoms)")
+        if nonbonded.charge.device != dev:
+            raise ValueError(f"the nonbonded batch is on {nonbonded.charge.device}, the graph on {dev}")
+    ks, eqs, n_per = mm_tables(g, plan, list(terms), suffix, dev)
+    return [k.detach().contiguous() for k in ks], [None if q is None else q.detach().contiguous() for q in eqs], n_per
+
+
 def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
                 offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, **opts) -> RelaxResult:
     """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
@@ -98,36 +127,15 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     o = relax_options(**opts)
     stepwise, check_every = _stepwise_options(stepwise, check_every)
     terms = list(terms)
-    for t in terms:
-        if t not in TUPLE_LEVELS:
-            raise ValueError(f"term {t} not in {TUPLE_LEVELS}")
-    n1 = g.nodes["n1"].data
-    if "xyz" not in n1:
-        raise ValueError("xyz coordinates must be stored in g.nodes['n1'].data['xyz']")
-    xyz = n1["xyz"].detach()
-    if xyz.dim() != 3 or xyz.shape[2] != 3:
-        raise ValueError(f"xyz must be (N, C, 3), got {tuple(xyz.shape)}")
-    xyz = xyz.float().contiguous()
+    xyz, plan, counts = graph_coordinates(g, terms)
     dev = xyz.device
-    plan = g.plan()
-    counts = [int(c) for c in g.batch_num_nodes_host("n1")]          # (host numbers: no device sync)
     limit = get_backend().relax_max_atoms()
     above = bool(counts) and max(counts) > limit
     if above and stepwise is False:
         raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
                          f"minimiser (stepwise=True or stepwise='auto' relaxes molecules of any size)")
     use_steps = stepwise is True or (stepwise == "auto" and above)
-    if nonbonded is not None:
-        if not isinstance(nonbonded, NonbondedBatch):
-            raise TypeError(f"nonbonded must be a NonbondedBatch or None, got {type(nonbonded).__name__}")
-        if nonbonded.N != plan.N or nonbonded.B != plan.B or nonbonded.atom_molptr_host.tolist() != np.concatenate([[0], np.cumsum(counts)]).tolist():
-            raise ValueError(f"the nonbonded batch ({nonbonded.B} molecules, {nonbonded.N} atoms) does not describe the graph's molecules "
-                             f"({plan.B} molecules, {plan.N} atoms)")
-        if nonbonded.charge.device != dev:
-            raise ValueError(f"the nonbonded batch is on {nonbonded.charge.device}, the graph on {dev}")
-    ks, eqs, n_per = mm_tables(g, plan, terms, suffix, dev)
-    ks = [k.detach().contiguous() for k in ks]
-    eqs = [None if q is None else q.detach().contiguous() for q in eqs]
+    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     B, C = plan.B, xyz.shape[1]
     out = torch.empty_like(xyz)
     energy, gmax = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(B, C, dtype=torch.float32, device=dev)

@@ -571,6 +571,65 @@ int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const 
                                   float* term_energy, float* grad, float* gmax, int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * Langevin molecular dynamics under the full MM force field (additions to ABI 11): BAOAB (Leimkuhler and Matthews 2013; on-step
+ * velocities, one force evaluation per step), one workgroup per (molecule b, conformation c), n_steps steps in one launch.  The energy,
+ * the gradient g = +dE/dxyz, the descriptors and the size limit are those of grappa_relax_fire_f32 (start = mm->xyz, nb->xyz ignored, nb
+ * == NULL: bonded terms only).  Units: Angstrom, kcal/mol, amu, ps, K; ACC = 418.4 (1 kcal/mol = 418.4 amu A^2 / ps^2), kB = 0.0019872041
+ * kcal/mol/K.  mass[N] in amu; w_i = 1 / m_i, and a mass that is not positive makes a FROZEN atom (OpenMM's convention for mass 0): w_i =
+ * 0, its coordinates come back bit for bit and its velocity is 0, whatever vel_in holds for it.
+ *   c1 = exp(-friction dt); c2 = sqrt(1 - c1^2); s_i = sqrt(ACC kB temperature w_i); g = grad E(x)
+ *   v = vel_in, or, if vel_in == NULL, v_i = sqrt(ACC kB init_temperature w_i) z(first_step, purpose 1) (0 for init_temperature == 0)
+ *   repeat n_steps times, t = first_step + k, k = 0, 1, ..:
+ *       g not finite: status 2, stop with the x and v held and steps = k
+ *       v -= (dt/2) ACC w_i g;  x += (dt/2) v
+ *       if friction > 0: v = c1 v + c2 s_i z(t, purpose 0)
+ *       x += (dt/2) v;  g = grad E(x);  v -= (dt/2) ACC w_i g
+ *       if save_every > 0 and (k + 1) % save_every == 0: write frame (k + 1) / save_every - 1
+ *   g not finite: status 2 (the gradient that closes the last step is tested too; with n_steps == 0 the one at the start)
+ * With friction == 0 this is velocity Verlet and no random number is drawn.  dt/2, (dt/2) ACC, c1, c2, ACC kB temperature and ACC kB
+ * init_temperature are formed in double on the host and rounded once.  A gradient is "not finite" by the test of grappa_relax_fire_f32.
+ * The step that found it has been completed with it (frozen atoms excepted, its velocities are then not finite either), and a frame
+ * that fell on that step has been written; no later frame is.
+ * Random numbers have no state: z(t, purpose) of atom i (its index WITHIN the molecule) and conformation c is a function of
+ * (mol_key[b], i, c, t, purpose) alone.  Philox4x32-10 (Salmon et al. 2011, Random123's constants) with key = (low, high half of
+ * mol_key[b]) and counter = (i, c, t, purpose) gives w0..w3; with u(w) = ((w >> 8) + 0.5) 2^-24, r(w) = sqrt(-2 ln u(w)) and
+ * a(w) = 2 pi (w >> 8) 2^-24:  z = (r(w0) cos a(w1), r(w0) sin a(w1), r(w2) cos a(w3)).  u is never 0; the logarithm is taken of an
+ * argument fp32 holds exactly (u below 1/2, 1 - u through log1p above).  A molecule's trajectory therefore depends on its key, not on
+ * its place in the batch, and a run of a + b steps gives the same bits of x, v and frames as a run of a steps (a a multiple of
+ * save_every) followed by one of b steps with mm->xyz = xyz_out, vel_in = vel_out and first_step + a: the gradient recomputed at the
+ * start is the one that was held.  first_step + n_steps must stay below 2^32.
+ * Outputs per item: xyz_out, vel_out [N,C,3]; epot[B,C] (total potential energy at xyz_out: thread partials in fp32, added in double in
+ * a fixed order, the code path of grappa_relax_fire_f32's energy); ekin[B,C] = 0.5 / ACC sum m_i v_i^2, added the same way; steps[B,C];
+ * status[B,C]: 0 = ran n_steps steps, 2 = non-finite gradient, 3 = more than grappa_relax_max_atoms() atoms and NOTHING else written.
+ * Optional (NULL: not written): frames_xyz[F,N,C,3] with F = n_steps / save_every, each frame in the layout of mm->xyz;
+ * frames_epot[F,B,C] and frames_ekin[F,B,C], the bits epot and ekin of a run that ended there would have.  The potential energy is
+ * computed at frames and at the end only.  A molecule without atoms writes nothing.  n_steps == 0 returns the input bit for bit (the
+ * velocities of frozen atoms zeroed) with epot and ekin at it.  No atomics, no communication between workgroups: same input, same bits,
+ * and an item's bits depend neither on its place in the batch nor on its neighbours.
+ * GRAPPA_ERR_ARG, nothing written: a NULL required pointer or a negative size; nb disagreeing with mm in N, C or B; B * C >= 2^31; dt not
+ * positive and finite; temperature, friction or init_temperature negative or not finite; n_steps < 0 or > 1,000,000; save_every < 0;
+ * first_step + n_steps >= 2^32.  N == 0, C == 0 or B == 0: returns 0 without a launch.  Constraints, cutoffs, periodic boxes and
+ * molecules above the limit are not supported.
+ * grappa_md_philox: the generator itself on the host (no device, no launch).  grappa_md_noise_f32: one small launch that writes
+ * out[N,C,3] = z(step, purpose) of every (atom, conformation) exactly as grappa_md_langevin_f32 draws it (atom_molptr[B+1] and
+ * mol_key[B] are device memory; N * C < 2^31). */
+typedef struct grappa_md_opts {
+    float dt;                    /* ps */
+    float temperature;           /* K, of the thermostat */
+    float friction;              /* 1/ps; 0: no thermostat (velocity Verlet) */
+    float init_temperature;      /* K, of the start velocities when vel_in == NULL */
+    int   n_steps, save_every;   /* save_every == 0: no frames */
+    unsigned first_step;         /* the global index of this call's first step: the random stream's position */
+} grappa_md_opts;
+int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                           const float* mass /*[N]*/, const unsigned long long* mol_key /*[B]*/, const float* vel_in /*[N,C,3] or NULL*/,
+                           float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status,
+                           float* frames_xyz, float* frames_epot, float* frames_ekin);
+void grappa_md_philox(unsigned long long key, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned out[4]);
+int grappa_md_noise_f32(void* stream, const unsigned long long* mol_key, const int* atom_molptr, int N, int C, int B, unsigned step,
+                        unsigned purpose, float* out /*[N,C,3]*/);
+
+/* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:
  *  l_m = wE*mean_c((E-<E>)-(Eref-<Eref>))^2 + wG*mean_{a,c,xyz}(G-Gref)^2   over real conformations
  *  loss_mol[b] = l_m ; gE = d(sum_m l_m * inv_B)/dE ; gG likewise.  is_dummy may be NULL. */
