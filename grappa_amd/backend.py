@@ -394,7 +394,10 @@ class HipBackend:
         if not live:
             return
         for e in live:                                  # the maxima first (one batched launch of their own when stale)
-            e.amax = self._amax_of_weight(e.ref())
+            am = self._amax_of_weight(e.ref())
+            if am is not e.amax:                        # registered again (aged out of the maxima, or moved): the table names the old arrays
+                e.amax = am
+                self._wptable = None
         if self._wptable is None:
             dt = np.dtype([("x", "<u8"), ("amax", "<u8"), ("pairs", "<u8"), ("R", "<i4"), ("C", "<i4"), ("ldx", "<i4"), ("ldp", "<i4"),
                            ("transpose", "<i4"), ("tile_begin", "<i4")])
@@ -512,7 +515,9 @@ class HipBackend:
 
     def _amax_of_weight(self, w: torch.Tensor) -> "Amax":
         """row and column maxima of a weight matrix, refreshed when the weight changed (as _planes_of_weight).  Entries keep their
-        weight alive, so its address cannot be handed to another tensor while the entry exists.  After an optimiser step the first
+        weight alive, so its storage is not freed under the entry -- but a parameter can be re-homed (`p.data = ...`: FlatParams, module.to()):
+        the object lives on at a new address and the old one is handed to another tensor.  An entry whose tensor no longer lives at the
+        key's address is therefore dead (views of one storage still share an entry).  After an optimiser step the first
         stale weight refreshes EVERY registered weight in one launch (grappa_amax_f32_batched: one workgroup per weight).
         That refresh rewrites all maxima arrays (zero, then atomic max) on the CALLING stream: it is safe because parameters change between
         steps, so the first stale use is the GNN's on the main stream, before the writer heads fork.  Never hand this function a tensor
@@ -522,6 +527,10 @@ class HipBackend:
         key = (w.data_ptr(), R, Cc, w.stride(0))
         ver = (w._version, self._wepoch)
         hit = self._wamax.get(key)
+        if hit is not None and hit.w.data_ptr() != w.data_ptr():      # its tensor moved away: the device table holds the old address too
+            del self._wamax[key]
+            self._wtable = None
+            hit = None
         if hit is not None:
             hit.epoch = self._wepoch
             if hit.ver == ver:
