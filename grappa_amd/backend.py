@@ -17,6 +17,8 @@ from typing import List, NamedTuple, Optional, Sequence
 import torch
 
 from . import _lib
+from ._marshal import GrappaHipError, _chk, _flat, _ptr  # noqa: F401
+from .backend_mm import MMBackend
 
 _BACKEND = None
 
@@ -33,28 +35,12 @@ def get_backend():
     return _BACKEND
 
 
-class GrappaHipError(RuntimeError):
-    pass
-
-
-_ERR = {-1: "GRAPPA_ERR_ARG (unsupported shape / null pointer)", -2: "GRAPPA_ERR_LAUNCH", -3: "GRAPPA_ERR_WORKSPACE"}
-
-
-def _chk(rc: int, what: str) -> None:
-    if rc != 0:
-        raise GrappaHipError(f"{what} failed: {_ERR.get(rc, rc)}")
-
-
 def _loss_mols(plan) -> int:
     """molecules the loss runs over: all of the batch, or its leading `n_real_mols` when the batch ends in a padding molecule
     (DeviceDataset.collate(pad_to=...): the kernels are one workgroup per molecule, the gradient arrays are zero-initialised, so rows of the
     padding molecule get exactly 0 from the loss)"""
     n = getattr(plan, "n_real_mols", None)
     return plan.B if n is None else int(n)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 _ACT_DTYPES = (torch.float32, torch.bfloat16)
@@ -84,39 +70,6 @@ def _f32_2d(t: torch.Tensor, name: str, dev, dtype=torch.float32) -> int:
             raise ValueError(f"{name}: overlapping rows (stride {t.stride(0)} < {t.shape[1]} columns)")
         return t.stride(0)
     return max(t.shape[1], 1)
-
-
-def _flat(t: torch.Tensor, name: str, dev, dtype=torch.float32) -> None:
-    if t.dtype != dtype or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{name}: expected a contiguous {dtype} tensor on {dev}")
-
-
-def _nb_tables_desc(nb, N, Cc, B, dev, who):
-    """grappa_nb_desc of the device tables of a NonbondedBatch (atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma,
-    exc_eps) for the kernels that take their coordinates from the MM descriptor (xyz = NULL); None for nb = None"""
-    if nb is None:
-        return None
-    for n in ("atom_molptr", "exc_ptr", "exc_atom"):
-        t = getattr(nb, n)
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"nb.{n}: expected a contiguous {torch.int32} tensor on {dev}")
-        _flat(t, "nb." + n, dev, torch.int32)
-    for n in ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps"):
-        t = getattr(nb, n)
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"nb.{n}: expected a contiguous {torch.float32} tensor on {dev}")
-        _flat(t, "nb." + n, dev)
-    if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (nb.charge, nb.sigma, nb.epsilon)):
-        raise ValueError(f"{who}: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
-    if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
-        raise ValueError(f"{who}: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
-    nd = _lib.NbDesc()
-    nd.N, nd.C, nd.B = N, Cc, B
-    nd.xyz, nd.atom_molptr = None, nb.atom_molptr.data_ptr()
-    nd.charge, nd.sigma, nd.epsilon = nb.charge.data_ptr(), nb.sigma.data_ptr(), nb.epsilon.data_ptr()
-    nd.exc_ptr, nd.exc_atom = nb.exc_ptr.data_ptr(), nb.exc_atom.data_ptr()
-    nd.exc_qq, nd.exc_sigma, nd.exc_eps = nb.exc_qq.data_ptr(), nb.exc_sigma.data_ptr(), nb.exc_eps.data_ptr()
-    return nd
 
 
 DEFAULT_GEMM_PRECISION = "f32_f16x3"
@@ -202,7 +155,7 @@ class _AmaxEntry:                       # _wamax: the row / column maxima of one
         self.ver, self.w, self.amax, self.epoch, self.batchable = ver, w, amax, epoch, batchable
 
 
-class HipBackend:
+class HipBackend(MMBackend):
     name = "hip"
 
     def __init__(self):
@@ -1830,319 +1783,6 @@ class HipBackend:
         _chk(self.lib.grappa_param_out_bwd_stats_f32(self._stream(), kind, T, P, n_per, int(gated), float(cutoff), _ptr(o), o.shape[1] if o.dim() == 2 else 0,
                                                      consts.data_ptr(), _ptr(dk), _ptr(deq), d_consts.data_ptr(), ws.data_ptr(), ws.numel()),
              "grappa_param_out_bwd_stats_f32")
-
-    # ------------------------------------------------------------------ MM energy
-    def _mm_desc(self, plan, xyz, ks, eqs, n_per, offset_torsion):
-        from .constants import TUPLE_LEVELS
-        dev = xyz.device
-        _flat(xyz, "xyz", dev)
-        N, Cc = xyz.shape[0], xyz.shape[1]
-        if N != plan.N or xyz.shape[2] != 3 or plan.indptr.device != dev:
-            raise ValueError("mm: xyz does not match the batch plan")
-        d = _lib.MMDesc()
-        d.N, d.C, d.B = N, Cc, plan.B
-        d.xyz = xyz.data_ptr()
-        for l, lvl in enumerate(TUPLE_LEVELS):
-            T = plan.T[lvl]
-            d.T[l] = T
-            d.idx[l] = plan.idx32[lvl].data_ptr()
-            d.mol_ptr[l] = plan.mol_ptr[lvl].data_ptr()
-            k = ks[l]
-            _flat(k, f"k[{lvl}]", dev)
-            if l < 2:
-                if k.numel() != T:
-                    raise ValueError(f"mm: k[{lvl}] length")
-                _flat(eqs[l], f"eq[{lvl}]", dev)
-                if eqs[l].numel() != T:
-                    raise ValueError(f"mm: eq[{lvl}] length")
-                d.eq[l] = eqs[l].data_ptr()
-                d.n_per[l] = 0
-            else:
-                if k.numel() != T * n_per[l]:
-                    raise ValueError(f"mm: k[{lvl}] must be (T,{n_per[l]})")
-                d.n_per[l] = n_per[l]
-            d.k[l] = k.data_ptr()
-        d.offset_torsion = int(offset_torsion)
-        d.inc_ptr, d.inc_code, d.atom_molptr = plan.inc_ptr.data_ptr(), plan.inc_code.data_ptr(), plan.atom_molptr.data_ptr()
-        return d
-
-    def mm_energy_fwd(self, plan, xyz, ks, eqs, n_per, offset_torsion, energy, term_energy, tuple_e=None, tuple_x=None) -> None:
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        te = _lib.VP4(*[_ptr(t) for t in (tuple_e or [None] * 4)])
-        tx = _lib.VP4(*[_ptr(t) for t in (tuple_x or [None] * 4)])
-        _chk(self.lib.grappa_mm_energy_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), C.byref(te), C.byref(tx)),
-             "grappa_mm_energy_fwd_f32")
-
-    def mm_gradient_fwd(self, plan, xyz, ks, eqs, n_per, grad) -> None:
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, False)
-        _flat(grad, "grad", xyz.device)
-        if grad.shape != xyz.shape:
-            raise ValueError("mm_gradient_fwd: grad shape")
-        _chk(self.lib.grappa_mm_gradient_fwd_f32(self._stream(), C.byref(d), grad.data_ptr()), "grappa_mm_gradient_fwd_f32")
-
-    def mm_bwd(self, plan, xyz, ks, eqs, n_per, offset_torsion, gE, gG, gks, geqs) -> None:
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        for t, n in ((gE, "gE"), (gG, "gG")):
-            if t is not None:
-                _flat(t, n, xyz.device)
-        a = _lib.VP4(*[_ptr(t) for t in gks])
-        b = _lib.VP4(*[_ptr(t) for t in geqs])
-        _chk(self.lib.grappa_mm_bwd_f32(self._stream(), C.byref(d), _ptr(gE), _ptr(gG), C.byref(a), C.byref(b)), "grappa_mm_bwd_f32")
-
-    # ------------------------------------------------------------------ nonbonded
-    def nonbonded_plan(self, atom_molptr_host, N: int, n_confs: int, device) -> "tuple":
-        """the work-item list of the nonbonded kernel for C = n_confs, built on the host from a HOST atom_molptr (int32, (B+1,)) and
-        uploaded: (table on the device, n_items, n_blocks, C) for `nonbonded(..., plan=)` (include/grappa_hip.h grappa_nonbonded_plan)"""
-        _flat(atom_molptr_host, "atom_molptr_host", torch.device("cpu"), torch.int32)
-        B = atom_molptr_host.numel() - 1
-        if B < 1 or n_confs < 1:
-            return (None, 0, 0, int(n_confs))
-        need = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), None, 0)
-        if need < 0:
-            _chk(int(need), "grappa_nonbonded_plan")
-        table = torch.empty(int(need), dtype=torch.int32)
-        rc = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), table.data_ptr(), table.numel())
-        if rc < 0:
-            _chk(int(rc), "grappa_nonbonded_plan")
-        return (table.to(device), int(table[0]), int(table[1]), int(n_confs))
-
-    def nonbonded(self, xyz, atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps, energy, term_energy=None, grad=None,
-                  plan=None) -> None:
-        """Lennard-Jones + Coulomb energy and gradient over all pairs of every molecule (include/grappa_hip.h grappa_nonbonded_fwd_f32):
-        xyz (N,C,3), atom_molptr (B+1,) int32, charge / sigma / epsilon (N,), the symmetric CSR exception table exc_ptr (N+1,) int32,
-        exc_atom int32, exc_qq / exc_sigma / exc_eps (at least one element each) -> energy (B,C), term_energy (2,B,C) or None,
-        grad (N,C,3) or None.  Angstrom, kcal/mol, elementary charges; the gradient is +dE/dxyz.
-        plan: what `nonbonded_plan` returned for this atom_molptr and C (the work-item list built once on the host: one launch less and
-        an exact grid); None: the list is built on the device by every call.  Same bits either way.
-        Out of scope: gradients with respect to charge, sigma or epsilon (no autograd wrapper: the term has no learnable input);
-        cutoffs, periodic boxes, PME."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
-            raise ValueError(f"nonbonded: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
-        dev = xyz.device
-        _flat(xyz, "xyz", dev)
-        for t, n in ((atom_molptr, "atom_molptr"), (exc_ptr, "exc_ptr"), (exc_atom, "exc_atom")):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {torch.int32} tensor on {dev}")
-            _flat(t, n, dev, torch.int32)
-        for t, n in ((charge, "charge"), (sigma, "sigma"), (epsilon, "epsilon"), (exc_qq, "exc_qq"), (exc_sigma, "exc_sigma"), (exc_eps, "exc_eps"),
-                     (energy, "energy"), (term_energy, "term_energy"), (grad, "grad")):
-            if t is None and n in ("term_energy", "grad"):
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {torch.float32} tensor on {dev}")
-            _flat(t, n, dev)
-        N, Cc, B = xyz.shape[0], xyz.shape[1], atom_molptr.numel() - 1
-        if B < 0 or exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (charge, sigma, epsilon)):
-            raise ValueError("nonbonded: atom_molptr must be (B+1,), exc_ptr (N+1,), charge / sigma / epsilon (N,)")
-        if not (exc_atom.numel() == exc_qq.numel() == exc_sigma.numel() == exc_eps.numel() >= 1):
-            raise ValueError("nonbonded: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
-        if energy.numel() != B * Cc or (term_energy is not None and term_energy.numel() != 2 * B * Cc) or (grad is not None and grad.shape != xyz.shape):
-            raise ValueError("nonbonded: expected energy (B,C), term_energy (2,B,C), grad (N,C,3)")
-        d = _lib.NbDesc()
-        d.N, d.C, d.B = N, Cc, B
-        d.xyz, d.atom_molptr = xyz.data_ptr(), atom_molptr.data_ptr()
-        d.charge, d.sigma, d.epsilon = charge.data_ptr(), sigma.data_ptr(), epsilon.data_ptr()
-        d.exc_ptr, d.exc_atom = exc_ptr.data_ptr(), exc_atom.data_ptr()
-        d.exc_qq, d.exc_sigma, d.exc_eps = exc_qq.data_ptr(), exc_sigma.data_ptr(), exc_eps.data_ptr()
-        if plan is not None and plan[0] is not None:
-            table, n_items, n_blocks, plan_c = plan
-            if plan_c != Cc or table.device != dev or table.dtype != torch.int32 or table.numel() < 4 + B + 1 + 4 * n_items:
-                raise ValueError(f"nonbonded: the plan was made for C = {plan_c} on {table.device}, the call has C = {Cc} on {dev}")
-            ws = self._workspace(16 * n_blocks * Cc, dev)
-            _chk(self.lib.grappa_nonbonded_fwd_planned_f32(self._stream(), C.byref(d), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
-                                                           _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()), "grappa_nonbonded_fwd_planned_f32")
-            return
-        ws = self._workspace(self.lib.grappa_nonbonded_workspace_bytes(N, Cc, B), dev)
-        _chk(self.lib.grappa_nonbonded_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()),
-             "grappa_nonbonded_fwd_f32")
-
-    # ------------------------------------------------------------------ relaxation
-    def relax_max_atoms(self) -> int:
-        return int(self.lib.grappa_relax_max_atoms())
-
-    def relax_fire(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
-                   atom_counts_host=None) -> None:
-        """the fused FIRE minimiser (include/grappa_hip.h grappa_relax_fire_f32): one launch relaxes every (molecule, conformation) of
-        the batch under the bonded terms (plan, ks, eqs, n_per, offset_torsion as for mm_energy_fwd; xyz (N,C,3) is the start) plus,
-        if nb is not None, Lennard-Jones + Coulomb (nb: the device tables of a NonbondedBatch: atom_molptr, charge, sigma, epsilon,
-        exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps).  opts: the ten fields of grappa_relax_opts by name, all of them.
-        -> xyz_out (N,C,3), energy / gmax (B,C) float32, steps / status (B,C) int32; term_energy (6,B,C) and grad (N,C,3) or None.
-        status: 0 = max_steps reached, 1 = converged, 2 = non-finite gradient, 3 = above relax_max_atoms() (nothing else written).
-        atom_counts_host: atoms per molecule as the caller knows them on the host; with it a molecule above the limit raises here,
-        before the launch and without a device sync (without it such a molecule comes back with status 3)."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
-            raise ValueError(f"relax_fire: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
-        dev = xyz.device
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        N, Cc, B = d.N, d.C, d.B
-        for t, n, dt in ((xyz_out, "xyz_out", torch.float32), (energy, "energy", torch.float32), (gmax, "gmax", torch.float32),
-                         (steps, "steps", torch.int32), (status, "status", torch.int32), (term_energy, "term_energy", torch.float32),
-                         (grad, "grad", torch.float32)):
-            if t is None and n in ("term_energy", "grad"):
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
-            _flat(t, n, dev, dt)
-        if xyz_out.shape != xyz.shape or (grad is not None and grad.shape != xyz.shape) or any(t.numel() != B * Cc for t in (energy, gmax, steps, status)) \
-                or (term_energy is not None and term_energy.numel() != 6 * B * Cc):
-            raise ValueError("relax_fire: expected xyz_out / grad (N,C,3), energy / gmax / steps / status (B,C), term_energy (6,B,C)")
-        if xyz_out.data_ptr() == xyz.data_ptr() and xyz.numel():
-            raise ValueError("relax_fire: xyz_out must not be the start coordinates")
-        if atom_counts_host is not None:
-            counts = [int(c) for c in atom_counts_host]
-            if len(counts) != B or sum(counts) != N:
-                raise ValueError(f"relax_fire: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
-            if counts and max(counts) > self.relax_max_atoms():
-                raise ValueError(f"relax_fire: a molecule of {max(counts)} atoms is above the limit of {self.relax_max_atoms()} atoms per molecule")
-        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_fire")
-        o = _lib.RelaxOpts()
-        names = [f[0] for f in _lib.RelaxOpts._fields_]
-        if sorted(opts) != sorted(names):
-            raise ValueError(f"relax_fire: opts must hold exactly {names}, got {sorted(opts)}")
-        for k in names:
-            setattr(o, k, int(opts[k]) if k in ("max_steps", "n_min") else float(opts[k]))
-        _chk(self.lib.grappa_relax_fire_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), xyz_out.data_ptr(),
-                                            energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
-             "grappa_relax_fire_f32")
-
-    def relax_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
-                    atom_counts_host=None, check_every: int = 32, workspace=None) -> None:
-        """the stepwise FIRE minimiser for molecules of any size (include/grappa_hip.h grappa_relax_steps_*_f32): the loop, the
-        arguments and the outputs of `relax_fire`, but a molecule spans many workgroups, the state lives in device memory and a step
-        is four launches.  atom_counts_host (required): atoms per molecule on the host; the work-item table is the nonbonded plan
-        built from it (reused from nb's cache of plans where nb keeps one).  check_every: steps enqueued between two looks at the
-        device's count of running items.  The host SYNCS with the device once per chunk (one `.item()`), never per step; the loop
-        ends when no item runs or max_steps steps are enqueued.  Status 3 does not occur.  workspace: a uint8 tensor of at least
-        `grappa_relax_steps_workspace_bytes` to use instead of the backend's own."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
-            raise ValueError(f"relax_steps: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
-        if isinstance(check_every, bool) or int(check_every) != check_every or check_every < 1:
-            raise ValueError(f"relax_steps: check_every must be an integer >= 1, got {check_every}")
-        check_every = int(check_every)
-        dev = xyz.device
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        N, Cc, B = d.N, d.C, d.B
-        for t, n, dt in ((xyz_out, "xyz_out", torch.float32), (energy, "energy", torch.float32), (gmax, "gmax", torch.float32),
-                         (steps, "steps", torch.int32), (status, "status", torch.int32), (term_energy, "term_energy", torch.float32),
-                         (grad, "grad", torch.float32)):
-            if t is None and n in ("term_energy", "grad"):
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
-            _flat(t, n, dev, dt)
-        if xyz_out.shape != xyz.shape or (grad is not None and grad.shape != xyz.shape) or any(t.numel() != B * Cc for t in (energy, gmax, steps, status)) \
-                or (term_energy is not None and term_energy.numel() != 6 * B * Cc):
-            raise ValueError("relax_steps: expected xyz_out / grad (N,C,3), energy / gmax / steps / status (B,C), term_energy (6,B,C)")
-        if atom_counts_host is None:
-            raise ValueError("relax_steps: atom_counts_host is required (the work-item table is built from it)")
-        counts = [int(c) for c in atom_counts_host]
-        if len(counts) != B or sum(counts) != N or (counts and min(counts) < 0):
-            raise ValueError(f"relax_steps: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
-        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_steps")
-        o = _lib.RelaxOpts()
-        names = [f[0] for f in _lib.RelaxOpts._fields_]
-        if sorted(opts) != sorted(names):
-            raise ValueError(f"relax_steps: opts must hold exactly {names}, got {sorted(opts)}")
-        for k in names:
-            setattr(o, k, int(opts[k]) if k in ("max_steps", "n_min") else float(opts[k]))
-        if N == 0 or Cc == 0 or B == 0:
-            return
-        # the work-item table: the nonbonded plan of these molecules for this C (it is about atoms: it also serves nb = None)
-        cache = getattr(nb, "_plans", None) if nb is not None else None
-        table = cache.get(Cc) if isinstance(cache, dict) else None
-        if table is None or table[0] is None or table[0].device != dev:
-            molptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64).cumsum(0)]).to(torch.int32)
-            table = self.nonbonded_plan(molptr, N, Cc, dev)
-            if isinstance(cache, dict) and nb.charge.device == dev:
-                cache[Cc] = table
-        table_dev, n_items, n_blocks, _ = table
-        need = int(self.lib.grappa_relax_steps_workspace_bytes(N, Cc, B, n_blocks))
-        if workspace is None:
-            workspace = self._workspace(need, dev, "relax_steps")
-        else:
-            _flat(workspace, "workspace", dev, torch.uint8)
-        n_running = torch.zeros(1, dtype=torch.int32, device=dev)
-        st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        common = (st, C.byref(d), ndp, C.byref(o), table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
-        _chk(self.lib.grappa_relax_steps_init_f32(*common, n_running.data_ptr()), "grappa_relax_steps_init_f32")
-        left = o.max_steps
-        while left > 0:
-            n = min(check_every, left)
-            _chk(self.lib.grappa_relax_steps_run_f32(*common, n, n_running.data_ptr()), "grappa_relax_steps_run_f32")
-            left -= n
-            if int(n_running.item()) <= 0:          # the one host sync per chunk
-                break
-        _chk(self.lib.grappa_relax_steps_finish_f32(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
-                                                    steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
-
-    # ------------------------------------------------------------------ dynamics
-    def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
-                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
-        """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
-        (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
-        as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
-        atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
-        init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
-        n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
-        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
-        if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
-            raise ValueError(f"md_langevin: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
-        dev = xyz.device
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        N, Cc, B = d.N, d.C, d.B
-        o = _lib.MdOpts()
-        names = [f[0] for f in _lib.MdOpts._fields_]
-        if sorted(opts) != sorted(names):
-            raise ValueError(f"md_langevin: opts must hold exactly {names}, got {sorted(opts)}")
-        for k in names:
-            setattr(o, k, int(opts[k]) if k in ("n_steps", "save_every", "first_step") else float(opts[k]))
-        F = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
-        optional = ("vel_in", "frames_xyz", "frames_epot", "frames_ekin")
-        for t, n, dt in ((mass, "mass", torch.float32), (mol_key, "mol_key", torch.int64), (vel_in, "vel_in", torch.float32),
-                         (xyz_out, "xyz_out", torch.float32), (vel_out, "vel_out", torch.float32), (epot, "epot", torch.float32),
-                         (ekin, "ekin", torch.float32), (steps, "steps", torch.int32), (status, "status", torch.int32),
-                         (frames_xyz, "frames_xyz", torch.float32), (frames_epot, "frames_epot", torch.float32),
-                         (frames_ekin, "frames_ekin", torch.float32)):
-            if t is None and n in optional:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {dt} tensor on {dev}")
-            _flat(t, n, dev, dt)
-        if mass.numel() != N or mol_key.numel() != B or any(t is not None and t.shape != xyz.shape for t in (vel_in, xyz_out, vel_out)) \
-                or any(t.numel() != B * Cc for t in (epot, ekin, steps, status)) \
-                or (frames_xyz is not None and frames_xyz.numel() != F * N * Cc * 3) \
-                or any(t is not None and t.numel() != F * B * Cc for t in (frames_epot, frames_ekin)):
-            raise ValueError(f"md_langevin: expected mass (N,), mol_key (B,), vel_in / xyz_out / vel_out (N,C,3), epot / ekin / steps / status "
-                             f"(B,C), frames_xyz ({F},N,C,3), frames_epot / frames_ekin ({F},B,C)")
-        if xyz.numel() and (xyz_out.data_ptr() == xyz.data_ptr() or (vel_in is not None and vel_out.data_ptr() == vel_in.data_ptr())):
-            raise ValueError("md_langevin: xyz_out / vel_out must not be the start coordinates / velocities")
-        if atom_counts_host is not None:
-            counts = [int(c) for c in atom_counts_host]
-            if len(counts) != B or sum(counts) != N:
-                raise ValueError(f"md_langevin: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
-            if counts and max(counts) > self.relax_max_atoms():
-                raise ValueError(f"md_langevin: a molecule of {max(counts)} atoms is above the limit of {self.relax_max_atoms()} atoms per molecule")
-        nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
-        _chk(self.lib.grappa_md_langevin_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), mass.data_ptr(),
-                                             mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
-                                             ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),
-                                             _ptr(frames_ekin)), "grappa_md_langevin_f32")
-
-    def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
-        """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,
-        atom_molptr (B+1,) int32, C_ conformations, step = the global step index, purpose 0 (thermostat) or 1 (start velocities)
-        -> out (N, C_, 3) float32"""
-        for t, n, dt in ((mol_key, "mol_key", torch.int64), (atom_molptr, "atom_molptr", torch.int32), (out, "out", torch.float32)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{n}: expected a contiguous {dt} tensor")
-            _flat(t, n, out.device, dt)
-        B = mol_key.numel()
-        if atom_molptr.numel() != B + 1 or out.dim() != 3 or out.shape[1] != C_ or out.shape[2] != 3:
-            raise ValueError("md_noise: expected mol_key (B,), atom_molptr (B+1,), out (N,C,3)")
-        if not (0 <= int(step) < 2 ** 32 and 0 <= int(purpose) < 2 ** 32):
-            raise ValueError(f"md_noise: step and purpose must lie in [0, 2^32), got {step}, {purpose}")
-        _chk(self.lib.grappa_md_noise_f32(self._stream(), mol_key.data_ptr(), atom_molptr.data_ptr(), out.shape[0], int(C_), B, int(step),
-                                          int(purpose), out.data_ptr()), "grappa_md_noise_f32")
 
     # ------------------------------------------------------------------ loss
     def loss_ef(self, plan, energy, energy_ref, is_dummy, grad, grad_ref, wE, wG, inv_B, loss_mol, gE, gG) -> None:

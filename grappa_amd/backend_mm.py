@@ -1,0 +1,325 @@
+"""The molecular-mechanics part of `HipBackend` (backend.py inherits it): bonded energy, gradient and backward, nonbonded terms, the
+two FIRE minimisers and Langevin dynamics.  Every method reads as checks, descriptor, call; what several of them check the same way
+is a helper here.  It uses `self.lib`, `self._stream()` and `self._workspace()` of the backend."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._marshal import _chk, _flat, _ptr
+
+_F32, _I32, _I64 = torch.float32, torch.int32, torch.int64
+_NB_INT = ("atom_molptr", "exc_ptr", "exc_atom")
+_NB_F32 = ("charge", "sigma", "epsilon", "exc_qq", "exc_sigma", "exc_eps")
+
+
+def _xyz3(xyz, who):
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"{who}: xyz must be an (N, C, 3) tensor, got {tuple(xyz.shape) if isinstance(xyz, torch.Tensor) else type(xyz)}")
+
+
+def _tensors(dev, specs, optional=(), where=None):
+    """every (tensor, name, dtype) of specs is a contiguous tensor of that type on dev; the ones named in `optional` may be None"""
+    where = f" on {dev}" if where is None else where
+    for t, n, dt in specs:
+        if t is None and n in optional:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{n}: expected a contiguous {dt} tensor{where}")
+        _flat(t, n, dev, dt)
+
+
+def _opts_struct(cls, opts, who):
+    """the ctypes options struct `cls` from a dict that holds exactly its fields"""
+    names = [f[0] for f in cls._fields_]
+    if sorted(opts) != sorted(names):
+        raise ValueError(f"{who}: opts must hold exactly {names}, got {sorted(opts)}")
+    o = cls()
+    for k, ct in cls._fields_:
+        setattr(o, k, float(opts[k]) if ct is C.c_float else int(opts[k]))
+    return o
+
+
+def _atom_counts(atom_counts_host, N, B, who, limit=None):
+    """atoms per molecule as the caller knows them on the host; limit: the size a molecule may have (None: any, none negative)"""
+    counts = [int(c) for c in atom_counts_host]
+    if len(counts) != B or sum(counts) != N or (limit is None and counts and min(counts) < 0):
+        raise ValueError(f"{who}: atom_counts_host names {len(counts)} molecules / {sum(counts)} atoms, the batch has {B} / {N}")
+    if limit is not None and counts and max(counts) > limit:
+        raise ValueError(f"{who}: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule")
+    return counts
+
+
+def _relax_outputs(who, xyz, B, xyz_out, energy, gmax, steps, status, term_energy, grad):
+    """the outputs the two minimisers share"""
+    _tensors(xyz.device, ((xyz_out, "xyz_out", _F32), (energy, "energy", _F32), (gmax, "gmax", _F32), (steps, "steps", _I32),
+                          (status, "status", _I32), (term_energy, "term_energy", _F32), (grad, "grad", _F32)), ("term_energy", "grad"))
+    BC = B * xyz.shape[1]
+    if xyz_out.shape != xyz.shape or (grad is not None and grad.shape != xyz.shape) or any(t.numel() != BC for t in (energy, gmax, steps, status)) \
+            or (term_energy is not None and term_energy.numel() != 6 * BC):
+        raise ValueError(f"{who}: expected xyz_out / grad (N,C,3), energy / gmax / steps / status (B,C), term_energy (6,B,C)")
+
+
+def _nb_desc(N, Cc, B, xyz, tables):
+    d = _lib.NbDesc()
+    d.N, d.C, d.B, d.xyz = N, Cc, B, _ptr(xyz)
+    for n in _NB_INT + _NB_F32:
+        setattr(d, n, tables[n].data_ptr())
+    return d
+
+
+def _nb_tables_desc(nb, N, Cc, B, dev, who):
+    """grappa_nb_desc of the device tables of a NonbondedBatch (atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma,
+    exc_eps) for the kernels that take their coordinates from the MM descriptor (xyz = NULL); None for nb = None"""
+    if nb is None:
+        return None
+    t = {n: getattr(nb, n) for n in _NB_INT + _NB_F32}
+    _tensors(dev, [(t[n], "nb." + n, _I32) for n in _NB_INT] + [(t[n], "nb." + n, _F32) for n in _NB_F32])
+    if nb.atom_molptr.numel() != B + 1 or nb.exc_ptr.numel() != N + 1 or any(t[n].numel() != N for n in ("charge", "sigma", "epsilon")):
+        raise ValueError(f"{who}: the nonbonded tables do not describe the batch's {B} molecules / {N} atoms")
+    if not (nb.exc_atom.numel() == nb.exc_qq.numel() == nb.exc_sigma.numel() == nb.exc_eps.numel() >= 1):
+        raise ValueError(f"{who}: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+    return _nb_desc(N, Cc, B, None, t)
+
+
+class MMBackend:
+    # ------------------------------------------------------------------ MM energy
+    def _mm_desc(self, plan, xyz, ks, eqs, n_per, offset_torsion):
+        from .constants import TUPLE_LEVELS
+        dev = xyz.device
+        _flat(xyz, "xyz", dev)
+        N, Cc = xyz.shape[0], xyz.shape[1]
+        if N != plan.N or xyz.shape[2] != 3 or plan.indptr.device != dev:
+            raise ValueError("mm: xyz does not match the batch plan")
+        d = _lib.MMDesc()
+        d.N, d.C, d.B = N, Cc, plan.B
+        d.xyz = xyz.data_ptr()
+        for l, lvl in enumerate(TUPLE_LEVELS):
+            T = plan.T[lvl]
+            d.T[l] = T
+            d.idx[l] = plan.idx32[lvl].data_ptr()
+            d.mol_ptr[l] = plan.mol_ptr[lvl].data_ptr()
+            k = ks[l]
+            _flat(k, f"k[{lvl}]", dev)
+            if l < 2:
+                if k.numel() != T:
+                    raise ValueError(f"mm: k[{lvl}] length")
+                _flat(eqs[l], f"eq[{lvl}]", dev)
+                if eqs[l].numel() != T:
+                    raise ValueError(f"mm: eq[{lvl}] length")
+                d.eq[l] = eqs[l].data_ptr()
+                d.n_per[l] = 0
+            else:
+                if k.numel() != T * n_per[l]:
+                    raise ValueError(f"mm: k[{lvl}] must be (T,{n_per[l]})")
+                d.n_per[l] = n_per[l]
+            d.k[l] = k.data_ptr()
+        d.offset_torsion = int(offset_torsion)
+        d.inc_ptr, d.inc_code, d.atom_molptr = plan.inc_ptr.data_ptr(), plan.inc_code.data_ptr(), plan.atom_molptr.data_ptr()
+        return d
+
+    def mm_energy_fwd(self, plan, xyz, ks, eqs, n_per, offset_torsion, energy, term_energy, tuple_e=None, tuple_x=None) -> None:
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        te = _lib.VP4(*[_ptr(t) for t in (tuple_e or [None] * 4)])
+        tx = _lib.VP4(*[_ptr(t) for t in (tuple_x or [None] * 4)])
+        _chk(self.lib.grappa_mm_energy_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), C.byref(te), C.byref(tx)),
+             "grappa_mm_energy_fwd_f32")
+
+    def mm_gradient_fwd(self, plan, xyz, ks, eqs, n_per, grad) -> None:
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, False)
+        _flat(grad, "grad", xyz.device)
+        if grad.shape != xyz.shape:
+            raise ValueError("mm_gradient_fwd: grad shape")
+        _chk(self.lib.grappa_mm_gradient_fwd_f32(self._stream(), C.byref(d), grad.data_ptr()), "grappa_mm_gradient_fwd_f32")
+
+    def mm_bwd(self, plan, xyz, ks, eqs, n_per, offset_torsion, gE, gG, gks, geqs) -> None:
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        for t, n in ((gE, "gE"), (gG, "gG")):
+            if t is not None:
+                _flat(t, n, xyz.device)
+        a = _lib.VP4(*[_ptr(t) for t in gks])
+        b = _lib.VP4(*[_ptr(t) for t in geqs])
+        _chk(self.lib.grappa_mm_bwd_f32(self._stream(), C.byref(d), _ptr(gE), _ptr(gG), C.byref(a), C.byref(b)), "grappa_mm_bwd_f32")
+
+    # ------------------------------------------------------------------ nonbonded
+    def nonbonded_plan(self, atom_molptr_host, N: int, n_confs: int, device) -> "tuple":
+        """the work-item list of the nonbonded kernel for C = n_confs, built on the host from a HOST atom_molptr (int32, (B+1,)) and
+        uploaded: (table on the device, n_items, n_blocks, C) for `nonbonded(..., plan=)` (include/grappa_hip.h grappa_nonbonded_plan)"""
+        _flat(atom_molptr_host, "atom_molptr_host", torch.device("cpu"), torch.int32)
+        B = atom_molptr_host.numel() - 1
+        if B < 1 or n_confs < 1:
+            return (None, 0, 0, int(n_confs))
+        need = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), None, 0)
+        if need < 0:
+            _chk(int(need), "grappa_nonbonded_plan")
+        table = torch.empty(int(need), dtype=torch.int32)
+        rc = self.lib.grappa_nonbonded_plan(int(N), int(n_confs), B, atom_molptr_host.data_ptr(), table.data_ptr(), table.numel())
+        if rc < 0:
+            _chk(int(rc), "grappa_nonbonded_plan")
+        return (table.to(device), int(table[0]), int(table[1]), int(n_confs))
+
+    def nonbonded(self, xyz, atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps, energy, term_energy=None, grad=None,
+                  plan=None) -> None:
+        """Lennard-Jones + Coulomb energy and gradient over all pairs of every molecule (include/grappa_hip.h grappa_nonbonded_fwd_f32):
+        xyz (N,C,3), atom_molptr (B+1,) int32, charge / sigma / epsilon (N,), the symmetric CSR exception table exc_ptr (N+1,) int32,
+        exc_atom int32, exc_qq / exc_sigma / exc_eps (at least one element each) -> energy (B,C), term_energy (2,B,C) or None,
+        grad (N,C,3) or None.  Angstrom, kcal/mol, elementary charges; the gradient is +dE/dxyz.
+        plan: what `nonbonded_plan` returned for this atom_molptr and C (the work-item list built once on the host: one launch less and
+        an exact grid); None: the list is built on the device by every call.  Same bits either way.
+        Out of scope: gradients with respect to charge, sigma or epsilon (no autograd wrapper: the term has no learnable input);
+        cutoffs, periodic boxes, PME."""
+        _xyz3(xyz, "nonbonded")
+        dev = xyz.device
+        tb = dict(atom_molptr=atom_molptr, exc_ptr=exc_ptr, exc_atom=exc_atom, charge=charge, sigma=sigma, epsilon=epsilon, exc_qq=exc_qq,
+                 exc_sigma=exc_sigma, exc_eps=exc_eps)
+        _tensors(dev, [(xyz, "xyz", _F32)] + [(tb[n], n, _I32) for n in _NB_INT] + [(tb[n], n, _F32) for n in _NB_F32] +
+                 [(energy, "energy", _F32), (term_energy, "term_energy", _F32), (grad, "grad", _F32)], ("term_energy", "grad"))
+        N, Cc, B = xyz.shape[0], xyz.shape[1], atom_molptr.numel() - 1
+        if B < 0 or exc_ptr.numel() != N + 1 or any(t.numel() != N for t in (charge, sigma, epsilon)):
+            raise ValueError("nonbonded: atom_molptr must be (B+1,), exc_ptr (N+1,), charge / sigma / epsilon (N,)")
+        if not (exc_atom.numel() == exc_qq.numel() == exc_sigma.numel() == exc_eps.numel() >= 1):
+            raise ValueError("nonbonded: exc_atom / exc_qq / exc_sigma / exc_eps must share one length >= 1")
+        if energy.numel() != B * Cc or (term_energy is not None and term_energy.numel() != 2 * B * Cc) or (grad is not None and grad.shape != xyz.shape):
+            raise ValueError("nonbonded: expected energy (B,C), term_energy (2,B,C), grad (N,C,3)")
+        d = _nb_desc(N, Cc, B, xyz, tb)
+        if plan is not None and plan[0] is not None:
+            table, n_items, n_blocks, plan_c = plan
+            if plan_c != Cc or table.device != dev or table.dtype != torch.int32 or table.numel() < 4 + B + 1 + 4 * n_items:
+                raise ValueError(f"nonbonded: the plan was made for C = {plan_c} on {table.device}, the call has C = {Cc} on {dev}")
+            ws = self._workspace(16 * n_blocks * Cc, dev)
+            _chk(self.lib.grappa_nonbonded_fwd_planned_f32(self._stream(), C.byref(d), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
+                                                           _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()), "grappa_nonbonded_fwd_planned_f32")
+            return
+        ws = self._workspace(self.lib.grappa_nonbonded_workspace_bytes(N, Cc, B), dev)
+        _chk(self.lib.grappa_nonbonded_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()),
+             "grappa_nonbonded_fwd_f32")
+
+    # ------------------------------------------------------------------ relaxation
+    def relax_max_atoms(self) -> int:
+        return int(self.lib.grappa_relax_max_atoms())
+
+    def relax_fire(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
+                   atom_counts_host=None) -> None:
+        """the fused FIRE minimiser (include/grappa_hip.h grappa_relax_fire_f32): one launch relaxes every (molecule, conformation) of
+        the batch under the bonded terms (plan, ks, eqs, n_per, offset_torsion as for mm_energy_fwd; xyz (N,C,3) is the start) plus,
+        if nb is not None, Lennard-Jones + Coulomb (nb: the device tables of a NonbondedBatch: atom_molptr, charge, sigma, epsilon,
+        exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps).  opts: the ten fields of grappa_relax_opts by name, all of them.
+        -> xyz_out (N,C,3), energy / gmax (B,C) float32, steps / status (B,C) int32; term_energy (6,B,C) and grad (N,C,3) or None.
+        status: 0 = max_steps reached, 1 = converged, 2 = non-finite gradient, 3 = above relax_max_atoms() (nothing else written).
+        atom_counts_host: atoms per molecule as the caller knows them on the host; with it a molecule above the limit raises here,
+        before the launch and without a device sync (without it such a molecule comes back with status 3)."""
+        _xyz3(xyz, "relax_fire")
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        _relax_outputs("relax_fire", xyz, d.B, xyz_out, energy, gmax, steps, status, term_energy, grad)
+        if xyz_out.data_ptr() == xyz.data_ptr() and xyz.numel():
+            raise ValueError("relax_fire: xyz_out must not be the start coordinates")
+        if atom_counts_host is not None:
+            _atom_counts(atom_counts_host, d.N, d.B, "relax_fire", self.relax_max_atoms())
+        nd = _nb_tables_desc(nb, d.N, d.C, d.B, xyz.device, "relax_fire")
+        o = _opts_struct(_lib.RelaxOpts, opts, "relax_fire")
+        _chk(self.lib.grappa_relax_fire_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), xyz_out.data_ptr(),
+                                            energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
+             "grappa_relax_fire_f32")
+
+    def relax_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
+                    atom_counts_host=None, check_every: int = 32, workspace=None) -> None:
+        """the stepwise FIRE minimiser for molecules of any size (include/grappa_hip.h grappa_relax_steps_*_f32): the loop, the
+        arguments and the outputs of `relax_fire`, but a molecule spans many workgroups, the state lives in device memory and a step
+        is four launches.  atom_counts_host (required): atoms per molecule on the host; the work-item table is the nonbonded plan
+        built from it (reused from nb's cache of plans where nb keeps one).  check_every: steps enqueued between two looks at the
+        device's count of running items.  The host SYNCS with the device once per chunk (one `.item()`), never per step; the loop
+        ends when no item runs or max_steps steps are enqueued.  Status 3 does not occur.  workspace: a uint8 tensor of at least
+        `grappa_relax_steps_workspace_bytes` to use instead of the backend's own."""
+        _xyz3(xyz, "relax_steps")
+        if isinstance(check_every, bool) or int(check_every) != check_every or check_every < 1:
+            raise ValueError(f"relax_steps: check_every must be an integer >= 1, got {check_every}")
+        check_every = int(check_every)
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        N, Cc, B = d.N, d.C, d.B
+        _relax_outputs("relax_steps", xyz, B, xyz_out, energy, gmax, steps, status, term_energy, grad)
+        if atom_counts_host is None:
+            raise ValueError("relax_steps: atom_counts_host is required (the work-item table is built from it)")
+        counts = _atom_counts(atom_counts_host, N, B, "relax_steps")
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_steps")
+        o = _opts_struct(_lib.RelaxOpts, opts, "relax_steps")
+        if N == 0 or Cc == 0 or B == 0:
+            return
+        # the work-item table: the nonbonded plan of these molecules for this C (it is about atoms: it also serves nb = None)
+        cache = getattr(nb, "_plans", None) if nb is not None else None
+        table = cache.get(Cc) if isinstance(cache, dict) else None
+        if table is None or table[0] is None or table[0].device != dev:
+            molptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64).cumsum(0)]).to(torch.int32)
+            table = self.nonbonded_plan(molptr, N, Cc, dev)
+            if isinstance(cache, dict) and nb.charge.device == dev:
+                cache[Cc] = table
+        table_dev, n_items, n_blocks, _ = table
+        need = int(self.lib.grappa_relax_steps_workspace_bytes(N, Cc, B, n_blocks))
+        if workspace is None:
+            workspace = self._workspace(need, dev, "relax_steps")
+        else:
+            _flat(workspace, "workspace", dev, torch.uint8)
+        n_running = torch.zeros(1, dtype=torch.int32, device=dev)
+        st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
+        common = (st, C.byref(d), ndp, C.byref(o), table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
+        _chk(self.lib.grappa_relax_steps_init_f32(*common, n_running.data_ptr()), "grappa_relax_steps_init_f32")
+        left = o.max_steps
+        while left > 0:
+            n = min(check_every, left)
+            _chk(self.lib.grappa_relax_steps_run_f32(*common, n, n_running.data_ptr()), "grappa_relax_steps_run_f32")
+            left -= n
+            if int(n_running.item()) <= 0:          # the one host sync per chunk
+                break
+        _chk(self.lib.grappa_relax_steps_finish_f32(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
+                                                    steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
+
+    # ------------------------------------------------------------------ dynamics
+    def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
+        """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
+        (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
+        as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
+        atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
+        init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
+        n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
+        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
+        _xyz3(xyz, "md_langevin")
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        N, Cc, B = d.N, d.C, d.B
+        o = _opts_struct(_lib.MdOpts, opts, "md_langevin")
+        F = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
+        _tensors(dev, ((mass, "mass", _F32), (mol_key, "mol_key", _I64), (vel_in, "vel_in", _F32), (xyz_out, "xyz_out", _F32),
+                       (vel_out, "vel_out", _F32), (epot, "epot", _F32), (ekin, "ekin", _F32), (steps, "steps", _I32), (status, "status", _I32),
+                       (frames_xyz, "frames_xyz", _F32), (frames_epot, "frames_epot", _F32), (frames_ekin, "frames_ekin", _F32)),
+                 ("vel_in", "frames_xyz", "frames_epot", "frames_ekin"))
+        if mass.numel() != N or mol_key.numel() != B or any(t is not None and t.shape != xyz.shape for t in (vel_in, xyz_out, vel_out)) \
+                or any(t.numel() != B * Cc for t in (epot, ekin, steps, status)) \
+                or (frames_xyz is not None and frames_xyz.numel() != F * N * Cc * 3) \
+                or any(t is not None and t.numel() != F * B * Cc for t in (frames_epot, frames_ekin)):
+            raise ValueError(f"md_langevin: expected mass (N,), mol_key (B,), vel_in / xyz_out / vel_out (N,C,3), epot / ekin / steps / status "
+                             f"(B,C), frames_xyz ({F},N,C,3), frames_epot / frames_ekin ({F},B,C)")
+        if xyz.numel() and (xyz_out.data_ptr() == xyz.data_ptr() or (vel_in is not None and vel_out.data_ptr() == vel_in.data_ptr())):
+            raise ValueError("md_langevin: xyz_out / vel_out must not be the start coordinates / velocities")
+        if atom_counts_host is not None:
+            _atom_counts(atom_counts_host, N, B, "md_langevin", self.relax_max_atoms())
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
+        _chk(self.lib.grappa_md_langevin_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), mass.data_ptr(),
+                                             mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
+                                             ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),
+                                             _ptr(frames_ekin)), "grappa_md_langevin_f32")
+
+    def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
+        """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,
+        atom_molptr (B+1,) int32, C_ conformations, step = the global step index, purpose 0 (thermostat) or 1 (start velocities)
+        -> out (N, C_, 3) float32"""
+        _tensors(out.device, ((mol_key, "mol_key", _I64), (atom_molptr, "atom_molptr", _I32), (out, "out", _F32)), where="")
+        B = mol_key.numel()
+        if atom_molptr.numel() != B + 1 or out.dim() != 3 or out.shape[1] != C_ or out.shape[2] != 3:
+            raise ValueError("md_noise: expected mol_key (B,), atom_molptr (B+1,), out (N,C,3)")
+        if not (0 <= int(step) < 2 ** 32 and 0 <= int(purpose) < 2 ** 32):
+            raise ValueError(f"md_noise: step and purpose must lie in [0, 2^32), got {step}, {purpose}")
+        _chk(self.lib.grappa_md_noise_f32(self._stream(), mol_key.data_ptr(), atom_molptr.data_ptr(), out.shape[0], int(C_), B, int(step),
+                                          int(purpose), out.data_ptr()), "grappa_md_noise_f32")

@@ -7,26 +7,26 @@
 //            gradients, the mass and the two per-atom factors (dt / 2 ACC / m, c2 sqrt(ACC kB T / m)) stay in the registers of the
 //            atom's owner (thread a % 256).
 //   step   : the owner kicks, drifts, draws the thermostat's noise and drifts again (its own atoms only: no barrier in between),
-//            barrier; the partial gradients of rx_bonded / rx_pairs per (atom, slice), barrier; the owner adds the slices in slice
-//            order and the flag of a non-finite gradient is reduced (one barrier); the closing kick.  Three barriers per step.
-//   frame  : every save_every steps the coordinates and, if asked for, the energies: the six potential terms as thread partials in
-//            sh.part (its readers of this step passed the reduction's barrier), barrier, seven threads add them and the kinetic partials
+//            barrier; rx_gradient of csrc/rx_force.h (the partial gradients per (atom, slice), barrier, the owner adds the slices in
+//            slice order) and the flag of a non-finite gradient is reduced (one barrier); the closing kick.  Three barriers per step.
+//   frame  : every save_every steps the coordinates and, if asked for, the energies (rx_energies): the six potential terms as thread
+//            partials in sh.part (its readers of this step passed the reduction's barrier), barrier, seven threads add them and the kinetic partials
 //            in double in thread order, barrier.  The next step's partial gradients are written after that barrier and the one that
 //            follows its drift, so they cannot overwrite what the seven threads read.  Two barriers per frame with energies.
 //   noise  : Philox4x32-10 (csrc/md_philox.h), key = mol_key[b], counter = (atom in molecule, conformation, global step, purpose);
 //            nothing is kept between steps or launches, so a run can be cut anywhere and continued with first_step advanced.
-// The loop runs n_steps (<= MD_STEP_CAP) iterations: the kernel always terminates.
+// The loop runs n_steps (<= GRAPPA_STEP_CAP) iterations: the kernel always terminates.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
 
 #include "common.h"
+#include "desc_check.h"
 #include "md_philox.h"
 #include "rx_force.h"
 
 namespace {
 
-constexpr int MD_STEP_CAP = 1000000;
 constexpr double MD_ACC = 418.4;               // 1 kcal/mol = 418.4 amu A^2 / ps^2
 constexpr double MD_KB = 0.0019872041;         // kcal/mol/K
 
@@ -68,93 +68,24 @@ __device__ inline V3 md_normal3(unsigned long long key, unsigned atom, unsigned 
 }
 
 // g = grad E at the coordinates in LDS, into the owners' registers; true (in every thread) if a gradient is not finite.  Two barriers.
-__device__ __forceinline__ bool md_force(const MdArgs& a, RxShared& sh, int m0, int n, int s, int JS, int il0, bool active, V3 (&g)[RX_APT]) {
-    const int t = threadIdx.x;
-    if (active)
-        for (int il = il0; il < n; il += RX_NT) {
-            V3 p = rx_bonded(a.mm, sh, m0 + il, s, JS, m0, n);
-            if (a.has_nb) {
-                float elj = 0.f, ec = 0.f;
-                rx_pairs(a.nb, sh, il, s, JS, m0, n, elj, ec, p.x, p.y, p.z);
-            }
-            const int u = s * n + il;
-            sh.part[u] = p.x, sh.part[RX_MAX + u] = p.y, sh.part[2 * RX_MAX + u] = p.z;
-        }
-    __syncthreads();
+__device__ __forceinline__ bool md_force(const MdArgs& a, RxShared& sh, const RxItem& w, V3 (&g)[RX_APT]) {
     float bad = 0.f;
-#pragma unroll
-    for (int k = 0; k < RX_APT; ++k) {
-        const int il = t + k * RX_NT;
-        if (il < n) {
-            V3 gi = {sh.part[il], sh.part[RX_MAX + il], sh.part[2 * RX_MAX + il]};
-            for (int q = 1; q < JS; ++q) {
-                const int u = q * n + il;
-                gi.x += sh.part[u], gi.y += sh.part[RX_MAX + u], gi.z += sh.part[2 * RX_MAX + u];
-            }
-            g[k] = gi;
-            if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;
-        }
-    }
+    rx_gradient(a.mm, a.nb, a.has_nb, sh, w, g, [&](int, V3 gi) {
+        if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;
+    });
     return rx_reduce_max(bad, sh.wmax) != 0.f;
 }
 
-// the potential energy (six terms: thread partials in fp32, added in double in thread order, as at the end of relax_fire_kernel) and
-// the kinetic energy 0.5 / ACC sum m v^2 (the owners' partials, added the same way) of the state held -> (epot, ekin) in thread 0.
-// sh.part must be free: every reader of the last partial gradients has passed a barrier.  Two barriers.
-__device__ __forceinline__ float2 md_energies(const MdArgs& a, RxShared& sh, float* kin, double* ksum, int b, int m0, int n, int s, int JS,
-                                              int il0, bool active, const V3 (&v)[RX_APT], const float (&ms)[RX_APT]) {
-    const grappa_mm_desc& d = a.mm;
-    const int t = threadIdx.x;
-    float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int tt = d.mol_ptr[0][b] + t; tt < d.mol_ptr[0][b + 1]; tt += RX_NT) {
-        V3 u;
-        const float dx = bond_geom(rx_ld(sh, d.idx[0][2 * tt], m0, n), rx_ld(sh, d.idx[0][2 * tt + 1], m0, n), u) - d.eq[0][tt];
-        e[0] += 0.5f * d.k[0][tt] * dx * dx;
-    }
-    for (int tt = d.mol_ptr[1][b] + t; tt < d.mol_ptr[1][b + 1]; tt += RX_NT) {
-        V3 e0, e2;
-        const float dx = angle_geom(rx_ld(sh, d.idx[1][3 * tt], m0, n), rx_ld(sh, d.idx[1][3 * tt + 1], m0, n),
-                                    rx_ld(sh, d.idx[1][3 * tt + 2], m0, n), e0, e2) - d.eq[1][tt];
-        e[1] += 0.5f * d.k[1][tt] * dx * dx;
-    }
-    for (int l = 2; l < 4; ++l)
-        for (int tt = d.mol_ptr[l][b] + t; tt < d.mol_ptr[l][b + 1]; tt += RX_NT) {
-            V3 d0, d1, d2, d3;
-            const int* id = d.idx[l] + 4 * (size_t)tt;
-            const float phi = dihedral_geom(rx_ld(sh, id[0], m0, n), rx_ld(sh, id[1], m0, n), rx_ld(sh, id[2], m0, n), rx_ld(sh, id[3], m0, n),
-                                            d0, d1, d2, d3);
-            e[l] += torsion_energy(d.k[l] + (size_t)tt * d.n_per[l], d.n_per[l], phi, d.offset_torsion);
-        }
-    if (a.has_nb && active)
-        for (int il = il0; il < n; il += RX_NT) {
-            float gx = 0.f, gy = 0.f, gz = 0.f;
-            rx_pairs(a.nb, sh, il, s, JS, m0, n, e[4], e[5], gx, gy, gz);
-        }
+// the potential energy (rx_energies) and the kinetic energy 0.5 / ACC sum m v^2 (the owners' partials, added the same way between the same
+// barriers) of the state held -> (epot, ekin) in thread 0.  sh.part must be free.  Two barriers.
+__device__ __forceinline__ float2 md_energies(const MdArgs& a, RxShared& sh, float* kin, double* ksum, const RxItem& w, const V3 (&v)[RX_APT],
+                                              const float (&ms)[RX_APT]) {
     float mv2 = 0.f;
 #pragma unroll
     for (int k = 0; k < RX_APT; ++k)
-        if (t + k * RX_NT < n) mv2 += ms[k] * dot(v[k], v[k]);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) sh.part[q * RX_NT + t] = e[q];
-    kin[t] = mv2;
-    __syncthreads();
-    if (t < 6) {
-        double sum = 0.0;
-        for (int k = 0; k < RX_NT; ++k) sum += (double)sh.part[t * RX_NT + k];
-        sh.esum[t] = t < 4 ? sum : 0.5 * sum;          // every pair was counted from both of its atoms
-    } else if (t == 6) {
-        double sum = 0.0;
-        for (int k = 0; k < RX_NT; ++k) sum += (double)kin[k];
-        *ksum = (0.5 / MD_ACC) * sum;
-    }
-    __syncthreads();
-    float2 out = make_float2(0.f, 0.f);
-    if (t == 0) {
-        double tot = 0.0;
-        for (int q = 0; q < 6; ++q) tot += sh.esum[q];
-        out = make_float2((float)tot, (float)*ksum);
-    }
-    return out;
+        if ((int)threadIdx.x + k * RX_NT < w.n) mv2 += ms[k] * dot(v[k], v[k]);
+    const double tot = rx_energies(a.mm, a.nb, a.has_nb, sh, w, mv2, kin, ksum);
+    return threadIdx.x == 0 ? make_float2((float)tot, (float)((0.5 / MD_ACC) * *ksum)) : make_float2(0.f, 0.f);
 }
 
 __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
@@ -163,6 +94,8 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
     __shared__ double ksum;
     const grappa_mm_desc& d = a.mm;
     const int C = d.C, t = threadIdx.x;
+    // The item's prologue is rx_begin's (csrc/rx_force.h), written out: through rx_begin this kernel came out 0.7 % slower (2000 steps of
+    // 8192 items: 396.7 ms against 393.7 ms, the same arithmetic in another layout), so the two copies must be changed together.
     const int b = (int)(blockIdx.x / (unsigned)C), c = (int)(blockIdx.x - (unsigned)b * (unsigned)C);
     const size_t item = (size_t)b * C + c;
     const int m0 = rx_clamp(d.atom_molptr[b], d.N), m1 = rx_clamp(d.atom_molptr[b + 1], d.N);
@@ -177,11 +110,11 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
         sh.xs[il] = make_float4(p[0], p[1], p[2], a.has_nb ? a.nb.charge[m0 + il] : 0.f);
         sh.ps[il] = a.has_nb ? make_float2(0.5f * a.nb.sigma[m0 + il], sqrtf(a.nb.epsilon[m0 + il])) : make_float2(0.f, 0.f);
     }
-    // the thread's (atom, slice), as in relax_fire_kernel
     const int JS = n > RX_NT ? 1 : (RX_NT / n < RX_JS ? RX_NT / n : RX_JS);
     const int s = n > RX_NT ? 0 : t / n;
     const int il0 = t - s * n;
     const bool active = s < JS;
+    const RxItem w = {b, c, item, m0, n, JS, s, il0, active};
     const unsigned long long key = a.mol_key[b];
 
     // the owner's atoms: mass (0: frozen), the kick and noise factors, the start velocity
@@ -195,13 +128,13 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
         if (il < n) {
             const float m = a.mass[m0 + il];
             if (m > 0.f) {          // (a mass that is zero, negative or NaN: a frozen atom, v = 0)
-                const float w = 1.0f / m;
-                ms[k] = m, kw[k] = a.hk * w, sg[k] = a.c2 * sqrtf(a.kt * w);
+                const float im = 1.0f / m;
+                ms[k] = m, kw[k] = a.hk * im, sg[k] = a.c2 * sqrtf(a.kt * im);
                 if (a.vel_in) {
                     const float* p = a.vel_in + ((size_t)(m0 + il) * C + c) * 3;
                     v[k] = {p[0], p[1], p[2]};
                 } else if (a.kt0 > 0.f) {
-                    v[k] = sqrtf(a.kt0 * w) * md_normal3(key, (unsigned)il, (unsigned)c, a.first_step, 1u);
+                    v[k] = sqrtf(a.kt0 * im) * md_normal3(key, (unsigned)il, (unsigned)c, a.first_step, 1u);
                 }
             }
         }
@@ -212,7 +145,7 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
     bool bad;
     int steps = 0, since = 0, frame = 0;
     for (;;) {
-        bad = md_force(a, sh, m0, n, s, JS, il0, active, g);
+        bad = md_force(a, sh, w, g);
         bool due = false;
         if (steps > 0) {
             // ---- the closing B of the step, and its frame's coordinates
@@ -239,7 +172,7 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_kernel(MdArgs a) {
         // ---- the energies: of a frame that asks for them, and of the state the run ends with
         const bool last = bad || steps >= a.n_steps;
         if (last || (due && (a.frames_epot || a.frames_ekin))) {
-            const float2 e = md_energies(a, sh, kin, &ksum, b, m0, n, s, JS, il0, active, v, ms);
+            const float2 e = md_energies(a, sh, kin, &ksum, w, v, ms);
             if (t == 0) {
                 const size_t fo = (size_t)frame * d.B * C + item;
                 if (due && a.frames_epot) a.frames_epot[fo] = e.x;
@@ -328,22 +261,12 @@ extern "C" int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, co
     if (!(o->dt > 0.f && o->dt <= FLT_MAX) || !(o->temperature >= 0.f && o->temperature <= FLT_MAX) ||
         !(o->friction >= 0.f && o->friction <= FLT_MAX) || !(o->init_temperature >= 0.f && o->init_temperature <= FLT_MAX))
         return GRAPPA_ERR_ARG;
-    if (o->n_steps < 0 || o->n_steps > MD_STEP_CAP || o->save_every < 0) return GRAPPA_ERR_ARG;
+    if (o->n_steps < 0 || o->n_steps > GRAPPA_STEP_CAP || o->save_every < 0) return GRAPPA_ERR_ARG;
     if ((unsigned long long)o->first_step + (unsigned long long)o->n_steps >= (1ull << 32)) return GRAPPA_ERR_ARG;
     if (mm->N == 0 || mm->C == 0 || mm->B == 0) return GRAPPA_OK;
     if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status)
         return GRAPPA_ERR_ARG;
-    long long tuples = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (mm->T[l] < 0 || mm->T[l] >= (1 << 27) || !mm->mol_ptr[l]) return GRAPPA_ERR_ARG;
-        if (mm->T[l] > 0 && (!mm->idx[l] || !mm->k[l])) return GRAPPA_ERR_ARG;
-        if (l < 2 && mm->T[l] > 0 && !mm->eq[l]) return GRAPPA_ERR_ARG;
-        if (l >= 2 && (mm->n_per[l] < 1 || mm->n_per[l] > 8)) return GRAPPA_ERR_ARG;
-        tuples += mm->T[l];
-    }
-    if (tuples > 0 && !mm->inc_code) return GRAPPA_ERR_ARG;
-    if (nb && (!nb->charge || !nb->sigma || !nb->epsilon || !nb->exc_ptr || !nb->exc_atom || !nb->exc_qq || !nb->exc_sigma || !nb->exc_eps))
-        return GRAPPA_ERR_ARG;
+    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
     if ((long long)mm->B * mm->C > INT_MAX) return GRAPPA_ERR_ARG;
     MdArgs a;
     a.mm = *mm;

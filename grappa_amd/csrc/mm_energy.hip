@@ -12,6 +12,7 @@
 // the reference's random dihedral noise; conformations are the fast axis of xyz[N,C,3] so lanes read 12-byte
 // strided but contiguous segments.
 #include "common.h"
+#include "desc_check.h"
 #include "mm_geom.h"
 
 namespace {
@@ -45,25 +46,8 @@ __global__ __launch_bounds__(MME_NT) void mm_energy_kernel(MMArgs a) {
             const int t0 = d.mol_ptr[l][b], t1 = d.mol_ptr[l][b + 1];
             if (cok) {
                 for (int t = t0 + j; t < t1; t += tpb) {
-                    float e, x;
-                    if (l == 0) {
-                        V3 u;
-                        x = bond_geom(ldv(d.xyz, d.idx[0][2 * t], C, c), ldv(d.xyz, d.idx[0][2 * t + 1], C, c), u);
-                        const float dx = x - d.eq[0][t];
-                        e = 0.5f * d.k[0][t] * dx * dx;
-                    } else if (l == 1) {
-                        V3 e0, e2;
-                        x = angle_geom(ldv(d.xyz, d.idx[1][3 * t], C, c), ldv(d.xyz, d.idx[1][3 * t + 1], C, c),
-                                       ldv(d.xyz, d.idx[1][3 * t + 2], C, c), e0, e2);
-                        const float dx = x - d.eq[1][t];
-                        e = 0.5f * d.k[1][t] * dx * dx;
-                    } else {
-                        V3 d0, d1, d2, d3;
-                        const int* id = d.idx[l] + 4 * (size_t)t;
-                        x = dihedral_geom(ldv(d.xyz, id[0], C, c), ldv(d.xyz, id[1], C, c), ldv(d.xyz, id[2], C, c), ldv(d.xyz, id[3], C, c),
-                                          d0, d1, d2, d3);
-                        e = torsion_energy(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], x, d.offset_torsion);
-                    }
+                    float x;
+                    const float e = bonded_tuple_energy(d, l, t, [&](int atom) { return ldv(d.xyz, atom, C, c); }, x);
                     if (a.tuple_e[l]) a.tuple_e[l][(size_t)t * C + c] = e;
                     if (a.tuple_x[l]) a.tuple_x[l][(size_t)t * C + c] = x;
                     acc += e;
@@ -95,34 +79,8 @@ __global__ __launch_bounds__(256) void mm_gradient_kernel(grappa_mm_desc d, floa
     const int C = d.C;
     const bool ok = gid < (size_t)d.N * C;                         // (whole groups of MMG_SUB lanes are in or out: 256 % MMG_SUB == 0)
     const int atom = ok ? (int)(gid / C) : 0, c = ok ? (int)(gid % C) : 0;
-    V3 g = {0.f, 0.f, 0.f};
     const int i0 = ok ? d.inc_ptr[atom] : 0, i1 = ok ? d.inc_ptr[atom + 1] : 0;
-    for (int i = i0 + sub; i < i1; i += MMG_SUB) {
-        const int code = d.inc_code[i];
-        const int pos = code & 3, l = (code >> 2) & 3, t = code >> 4;
-        if (l == 0) {
-            V3 u;
-            const float r = bond_geom(ldv(d.xyz, d.idx[0][2 * t], C, c), ldv(d.xyz, d.idx[0][2 * t + 1], C, c), u);
-            const float coef = d.k[0][t] * (r - d.eq[0][t]);
-            g = g + (pos == 0 ? coef : -coef) * u;
-        } else if (l == 1) {
-            V3 e0, e2;
-            const float th = angle_geom(ldv(d.xyz, d.idx[1][3 * t], C, c), ldv(d.xyz, d.idx[1][3 * t + 1], C, c),
-                                        ldv(d.xyz, d.idx[1][3 * t + 2], C, c), e0, e2);
-            const float coef = d.k[1][t] * (th - d.eq[1][t]);
-            const V3 dv = pos == 0 ? e0 : (pos == 2 ? e2 : (-1.0f) * (e0 + e2));
-            g = g + coef * dv;
-        } else {
-            V3 d0, d1, d2, d3;
-            const int* id = d.idx[l] + 4 * (size_t)t;
-            const float phi = dihedral_geom(ldv(d.xyz, id[0], C, c), ldv(d.xyz, id[1], C, c), ldv(d.xyz, id[2], C, c), ldv(d.xyz, id[3], C, c),
-                                            d0, d1, d2, d3);
-            const float* k = d.k[l] + (size_t)t * d.n_per[l];
-            const float coef = torsion_dcoef(k, d.n_per[l], phi);
-            const V3 dv = pos == 0 ? d0 : (pos == 1 ? d1 : (pos == 2 ? d2 : d3));
-            g = g + coef * dv;
-        }
-    }
+    V3 g = bonded_gather(d, i0 + sub, i1, MMG_SUB, [&](int at) { return ldv(d.xyz, at, C, c); });
 #pragma unroll
     for (int m = 1; m < MMG_SUB; m <<= 1) {
         g.x += __shfl_xor(g.x, m);
@@ -242,15 +200,8 @@ inline int lanes_per_tuple(int C) { return C > 32 ? 64 : C > 16 ? 32 : C > 8 ? 1
 
 int validate(const grappa_mm_desc* d, bool need_inc) {
     if (!d || d->N < 0 || d->C <= 0 || d->B <= 0 || !d->xyz) return GRAPPA_ERR_ARG;
-    for (int l = 0; l < 4; ++l) {
-        if (d->T[l] < 0 || !d->mol_ptr[l]) return GRAPPA_ERR_ARG;
-        if (d->T[l] > 0 && (!d->idx[l] || !d->k[l])) return GRAPPA_ERR_ARG;
-        if (l < 2 && d->T[l] > 0 && !d->eq[l]) return GRAPPA_ERR_ARG;
-        if (l >= 2 && (d->n_per[l] < 1 || d->n_per[l] > 8)) return GRAPPA_ERR_ARG;
-        if (d->T[l] >= (1 << 27)) return GRAPPA_ERR_ARG;
-    }
-    if (need_inc && (!d->inc_ptr || (!d->inc_code && (d->T[0] + d->T[1] + d->T[2] + d->T[3]) > 0))) return GRAPPA_ERR_ARG;
-    return GRAPPA_OK;
+    if (need_inc && !d->inc_ptr) return GRAPPA_ERR_ARG;
+    return mm_desc_tables_ok(d, need_inc) ? GRAPPA_OK : GRAPPA_ERR_ARG;
 }
 
 }  // namespace

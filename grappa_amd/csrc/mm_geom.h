@@ -1,5 +1,6 @@
 // Internal coordinates of the molecular-mechanics terms and their derivatives (fp32), shared by csrc/mm_energy.hip (energy, gradient
-// and backward over a batch) and csrc/relax.hip (the fused minimiser): ONE definition of the geometry, its guards and the torsion series.
+// and backward over a batch), csrc/rx_force.h (the fused minimiser and dynamics) and csrc/relax_steps.hip: ONE definition of the
+// geometry, its guards, the torsion series, the bonded gather of an atom and the energy of a tuple.
 // Geometry follows models/internal_coordinates.py:150-210 (distance, atan2 angle, timemachine dihedral) without the reference's random
 // dihedral noise.
 #pragma once
@@ -74,6 +75,58 @@ __device__ inline float torsion_dcoef(const float* __restrict__ k, int n_per, fl
     float coef = 0.f;
     for (int n = 1; n <= n_per; ++n) coef -= (float)n * k[n - 1] * sinf((float)n * phi);
     return coef;
+}
+
+// The bonded gradient of one atom over its incidences q = first, first + stride, .. < last (inc_code[q] = tuple << 4 | level << 2 | position
+// of the atom in the tuple): coefficient times d(internal coordinate)/dx in closed form.  ld maps an atom index to its coordinates.
+template <class Ld>
+__device__ inline V3 bonded_gather(const grappa_mm_desc& d, int first, int last, int stride, Ld ld) {
+    V3 g = {0.f, 0.f, 0.f};
+    for (int q = first; q < last; q += stride) {
+        const int code = d.inc_code[q];
+        const int pos = code & 3, l = (code >> 2) & 3, t = code >> 4;
+        if (l == 0) {
+            V3 u;
+            const float r = bond_geom(ld(d.idx[0][2 * t]), ld(d.idx[0][2 * t + 1]), u);
+            const float coef = d.k[0][t] * (r - d.eq[0][t]);
+            g = g + (pos == 0 ? coef : -coef) * u;
+        } else if (l == 1) {
+            V3 e0, e2;
+            const float th = angle_geom(ld(d.idx[1][3 * t]), ld(d.idx[1][3 * t + 1]), ld(d.idx[1][3 * t + 2]), e0, e2);
+            const float coef = d.k[1][t] * (th - d.eq[1][t]);
+            const V3 dv = pos == 0 ? e0 : (pos == 2 ? e2 : (-1.0f) * (e0 + e2));
+            g = g + coef * dv;
+        } else {
+            V3 d0, d1, d2, d3;
+            const int* id = d.idx[l] + 4 * (size_t)t;
+            const float phi = dihedral_geom(ld(id[0]), ld(id[1]), ld(id[2]), ld(id[3]), d0, d1, d2, d3);
+            const float coef = torsion_dcoef(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], phi);
+            const V3 dv = pos == 0 ? d0 : (pos == 1 ? d1 : (pos == 2 ? d2 : d3));
+            g = g + coef * dv;
+        }
+    }
+    return g;
+}
+
+// The energy of tuple t of level l (0 bond, 1 angle, 2 proper, 3 improper); x: its internal coordinate.  ld as for bonded_gather.
+template <class Ld>
+__device__ inline float bonded_tuple_energy(const grappa_mm_desc& d, int l, int t, Ld ld, float& x) {
+    if (l == 0) {
+        V3 u;
+        x = bond_geom(ld(d.idx[0][2 * t]), ld(d.idx[0][2 * t + 1]), u);
+        const float dx = x - d.eq[0][t];
+        return 0.5f * d.k[0][t] * dx * dx;
+    }
+    if (l == 1) {
+        V3 e0, e2;
+        x = angle_geom(ld(d.idx[1][3 * t]), ld(d.idx[1][3 * t + 1]), ld(d.idx[1][3 * t + 2]), e0, e2);
+        const float dx = x - d.eq[1][t];
+        return 0.5f * d.k[1][t] * dx * dx;
+    }
+    V3 d0, d1, d2, d3;
+    const int* id = d.idx[l] + 4 * (size_t)t;
+    x = dihedral_geom(ld(id[0]), ld(id[1]), ld(id[2]), ld(id[3]), d0, d1, d2, d3);
+    return torsion_energy(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], x, d.offset_torsion);
 }
 
 }  // namespace

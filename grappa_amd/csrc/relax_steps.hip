@@ -6,13 +6,13 @@
 //            step in flight (mix, keep, downhill, gmax); per (block, conformation) the partials P, |F|^2, |v|^2, max |g_i| (double) and
 //            max |d_i| (float).
 //   step   : decide  one workgroup of 64 threads per (molecule, conformation): adds the item's block partials in ascending block
-//                    order in double (as nb_reduce_kernel does), applies the loop's stop tests and FIRE's decisions and writes the item's
-//                    new scalars.  It is the ONLY writer of the per-item state, and it runs in a launch of its own: no workgroup
+//                    order in double (as nb_reduce_kernel does), applies the loop's stop tests and FIRE's decisions (csrc/fire.h) and
+//                    writes the item's new scalars.  It is the ONLY writer of the per-item state, and it runs in a launch of its own: no workgroup
 //                    reads a scalar that a sibling writes in the same launch.
 //            vel     v = keep v + mix F + h F per atom, the block's max |h v_i|
 //            move    max over the item's blocks, s = min(1, max_disp / max), x += s h v, v = s v
-//            force   g at the new x: the bonded gather of mm_gradient_kernel (the thread's slice of the atom's incidences, neighbours
-//                    read from global memory) plus the j loop of nb_pairs_kernel (j-atoms through LDS in ascending blocks of 64, the
+//            force   g at the new x: bonded_gather of csrc/mm_geom.h, as in mm_gradient_kernel (the thread's slice of the atom's
+//                    incidences, neighbours read from global memory) plus the j loop of nb_pairs_kernel (j-atoms through LDS in ascending blocks of 64, the
 //                    sorted exception row walked in step with j, an exception replaces the pair, an exclusion or j == i is skipped, no
 //                    pair energy kept), slices added in slice order; then the block's partials.
 //            Launch boundaries are the only synchronisation between workgroups: no cooperative launch, no flag, no float atomics.
@@ -28,13 +28,14 @@
 #include <math.h>
 
 #include "common.h"
+#include "desc_check.h"
+#include "fire.h"
 #include "mm_geom.h"
 #include "nb_pair.h"
 #include "nb_plan.h"
 
 namespace {
 
-constexpr int RS_STEP_CAP = 1000000;
 constexpr int RS_DNT = 64;               // threads of a decide workgroup
 constexpr int RS_NW = NB_NT / GRAPPA_WAVE;
 constexpr int RS_RUNNING = -1;           // status in the workspace while an item runs
@@ -165,37 +166,9 @@ __device__ inline V3 rs_ld(const float* __restrict__ x, int atom, int N, int C, 
     return ldv(x, (unsigned)atom < (unsigned)N ? atom : 0, C, c);
 }
 
-// slice s of the bonded gradient of atom i in conformation c (the gather of mm_gradient_kernel / rx_bonded)
+// slice s of the bonded gradient of atom i in conformation c
 __device__ inline V3 rs_bonded(const grappa_mm_desc& d, const float* __restrict__ x, int i, int s, int JS, int c) {
-    V3 g = {0.f, 0.f, 0.f};
-    const int N = d.N, C = d.C;
-    const int q0 = d.inc_ptr[i], q1 = d.inc_ptr[i + 1];
-    for (int q = q0 + s; q < q1; q += JS) {
-        const int code = d.inc_code[q];
-        const int pos = code & 3, l = (code >> 2) & 3, t = code >> 4;
-        if (l == 0) {
-            V3 u;
-            const float r = bond_geom(rs_ld(x, d.idx[0][2 * t], N, C, c), rs_ld(x, d.idx[0][2 * t + 1], N, C, c), u);
-            const float coef = d.k[0][t] * (r - d.eq[0][t]);
-            g = g + (pos == 0 ? coef : -coef) * u;
-        } else if (l == 1) {
-            V3 e0, e2;
-            const float th = angle_geom(rs_ld(x, d.idx[1][3 * t], N, C, c), rs_ld(x, d.idx[1][3 * t + 1], N, C, c),
-                                        rs_ld(x, d.idx[1][3 * t + 2], N, C, c), e0, e2);
-            const float coef = d.k[1][t] * (th - d.eq[1][t]);
-            const V3 dv = pos == 0 ? e0 : (pos == 2 ? e2 : (-1.0f) * (e0 + e2));
-            g = g + coef * dv;
-        } else {
-            V3 d0, d1, d2, d3;
-            const int* id = d.idx[l] + 4 * (size_t)t;
-            const float phi = dihedral_geom(rs_ld(x, id[0], N, C, c), rs_ld(x, id[1], N, C, c), rs_ld(x, id[2], N, C, c), rs_ld(x, id[3], N, C, c),
-                                            d0, d1, d2, d3);
-            const float coef = torsion_dcoef(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], phi);
-            const V3 dv = pos == 0 ? d0 : (pos == 1 ? d1 : (pos == 2 ? d2 : d3));
-            g = g + coef * dv;
-        }
-    }
-    return g;
+    return bonded_gather(d, d.inc_ptr[i] + s, d.inc_ptr[i + 1], JS, [&](int atom) { return rs_ld(x, atom, d.N, d.C, c); });
 }
 
 __global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
@@ -377,21 +350,8 @@ __global__ __launch_bounds__(RS_DNT) void rs_decide_kernel(RsDecideArgs a) {
     const float Pf = (float)P, F2f = (float)F2, v2f = (float)v2;
     float h = a.s.h[item], al = a.s.al[item];
     int npos = a.s.npos[item];
-    const bool downhill = Pf > 0.f;
-    float mix = 0.f, keep = 0.f;
-    if (downhill) {
-        mix = al * (sqrtf(v2f) / sqrtf(F2f));
-        keep = 1.0f - al;
-        if (npos >= o.n_min) {
-            h = fminf(h * o.f_inc, o.dt_max);
-            al = al * o.f_alpha;
-        }
-        ++npos;
-    } else {
-        h = h * o.f_dec;
-        al = o.alpha_start;
-        npos = 0;
-    }
+    float mix, keep;
+    const bool downhill = fire_decide(o, Pf, F2f, v2f, h, al, npos, mix, keep);
     a.s.h[item] = h, a.s.al[item] = al, a.s.mix[item] = mix, a.s.keep[item] = keep;
     a.s.npos[item] = npos, a.s.downhill[item] = downhill ? 1 : 0, a.s.steps[item] = steps + 1;
 }
@@ -505,33 +465,17 @@ __global__ __launch_bounds__(256) void rs_out_kernel(RsOutArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// the argument checks of grappa_relax_fire_f32, without its output pointers; 1: nothing to do (an empty batch)
+// the argument checks of grappa_relax_fire_f32 (the shared ones: csrc/desc_check.h), without its output pointers; 1: nothing to do (an
+// empty batch)
 int rs_check(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
              const void* ws) {
     if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0 || n_items < 0 || n_blocks < 0) return GRAPPA_ERR_ARG;
     if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    // (comparisons written so that a NaN is refused)
-    if (!(o->tolerance >= 0.f) || o->max_steps < 0 || o->max_steps > RS_STEP_CAP || !(o->dt_start > 0.f) || !(o->dt_max > 0.f) ||
-        !(o->max_disp > 0.f) || o->n_min < 0 || !(o->f_inc > 0.f) || !(o->f_dec > 0.f) || !(o->f_alpha > 0.f) ||
-        !(o->alpha_start >= 0.f && o->alpha_start <= 1.f))
-        return GRAPPA_ERR_ARG;
-    if (!(o->dt_start <= FLT_MAX && o->dt_max <= FLT_MAX && o->max_disp <= FLT_MAX && o->f_inc <= FLT_MAX && o->f_dec <= FLT_MAX &&
-          o->f_alpha <= FLT_MAX && o->tolerance <= FLT_MAX))
-        return GRAPPA_ERR_ARG;
+    if (!relax_opts_ok(o)) return GRAPPA_ERR_ARG;
     if (mm->N == 0 || mm->C == 0 || mm->B == 0) return 1;
     if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !table_dev || !ws) return GRAPPA_ERR_ARG;
     if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)table_dev & 15) != 0) return GRAPPA_ERR_ARG;      // (doubles in the workspace, int4 items in the table)
-    long long tuples = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (mm->T[l] < 0 || mm->T[l] >= (1 << 27) || !mm->mol_ptr[l]) return GRAPPA_ERR_ARG;
-        if (mm->T[l] > 0 && (!mm->idx[l] || !mm->k[l])) return GRAPPA_ERR_ARG;
-        if (l < 2 && mm->T[l] > 0 && !mm->eq[l]) return GRAPPA_ERR_ARG;
-        if (l >= 2 && (mm->n_per[l] < 1 || mm->n_per[l] > 8)) return GRAPPA_ERR_ARG;
-        tuples += mm->T[l];
-    }
-    if (tuples > 0 && !mm->inc_code) return GRAPPA_ERR_ARG;
-    if (nb && (!nb->charge || !nb->sigma || !nb->epsilon || !nb->exc_ptr || !nb->exc_atom || !nb->exc_qq || !nb->exc_sigma || !nb->exc_eps))
-        return GRAPPA_ERR_ARG;
+    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
     if ((long long)mm->B * mm->C > INT_MAX || (long long)mm->N * mm->C * 3 > INT_MAX || (long long)n_blocks * mm->C > INT_MAX)
         return GRAPPA_ERR_ARG;
     if (n_blocks > (long long)mm->N / NB_T + mm->B) return GRAPPA_ERR_ARG;

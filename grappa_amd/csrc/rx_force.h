@@ -1,5 +1,6 @@
-// The force evaluation of the fused kernels that keep one molecule in one workgroup (csrc/relax.hip, csrc/dynamics.hip): the LDS image of
-// a molecule, the bonded gather and the pair loop of one (atom, slice), and the fixed-order workgroup reductions.
+// The core of the fused kernels that keep one molecule in one workgroup (csrc/relax.hip, csrc/dynamics.hip): the LDS image of a molecule
+// and the workgroup's item, the gradient of the coordinates held (the bonded gather and the pair loop of one (atom, slice), the owner's
+// sum over the slices), the six energy terms, and the fixed-order workgroup reductions.
 #pragma once
 #include <limits.h>
 
@@ -14,7 +15,6 @@ constexpr int RX_NT = 256;                // threads per workgroup
 constexpr int RX_JS = 16;                 // slices per atom at most
 constexpr int RX_APT = RX_MAX / RX_NT;    // atoms per owner thread at most
 constexpr int RX_NW = RX_NT / GRAPPA_WAVE;
-constexpr int RX_STEP_CAP = 1000000;
 
 struct RxShared {
     float4 xs[RX_MAX];              // x, y, z, q
@@ -36,34 +36,7 @@ __device__ inline V3 rx_ld(const RxShared& sh, int atom, int m0, int n) {
 
 // slice s of the bonded gradient of atom i
 __device__ inline V3 rx_bonded(const grappa_mm_desc& d, const RxShared& sh, int i, int s, int JS, int m0, int n) {
-    V3 g = {0.f, 0.f, 0.f};
-    const int i0 = d.inc_ptr[i], i1 = d.inc_ptr[i + 1];
-    for (int q = i0 + s; q < i1; q += JS) {
-        const int code = d.inc_code[q];
-        const int pos = code & 3, l = (code >> 2) & 3, t = code >> 4;
-        if (l == 0) {
-            V3 u;
-            const float r = bond_geom(rx_ld(sh, d.idx[0][2 * t], m0, n), rx_ld(sh, d.idx[0][2 * t + 1], m0, n), u);
-            const float coef = d.k[0][t] * (r - d.eq[0][t]);
-            g = g + (pos == 0 ? coef : -coef) * u;
-        } else if (l == 1) {
-            V3 e0, e2;
-            const float th = angle_geom(rx_ld(sh, d.idx[1][3 * t], m0, n), rx_ld(sh, d.idx[1][3 * t + 1], m0, n),
-                                        rx_ld(sh, d.idx[1][3 * t + 2], m0, n), e0, e2);
-            const float coef = d.k[1][t] * (th - d.eq[1][t]);
-            const V3 dv = pos == 0 ? e0 : (pos == 2 ? e2 : (-1.0f) * (e0 + e2));
-            g = g + coef * dv;
-        } else {
-            V3 d0, d1, d2, d3;
-            const int* id = d.idx[l] + 4 * (size_t)t;
-            const float phi = dihedral_geom(rx_ld(sh, id[0], m0, n), rx_ld(sh, id[1], m0, n), rx_ld(sh, id[2], m0, n), rx_ld(sh, id[3], m0, n),
-                                            d0, d1, d2, d3);
-            const float coef = torsion_dcoef(d.k[l] + (size_t)t * d.n_per[l], d.n_per[l], phi);
-            const V3 dv = pos == 0 ? d0 : (pos == 1 ? d1 : (pos == 2 ? d2 : d3));
-            g = g + coef * dv;
-        }
-    }
-    return g;
+    return bonded_gather(d, d.inc_ptr[i] + s, d.inc_ptr[i + 1], JS, [&](int atom) { return rx_ld(sh, atom, m0, n); });
 }
 
 // slice s of the pair sums of atom i = m0 + il: j = m0 + s, m0 + s + JS, .. ascending
@@ -95,6 +68,115 @@ __device__ inline void rx_pairs(const grappa_nb_desc& d, const RxShared& sh, int
         }
         if (!skip) nb_pair(pi.x - pj.x, pi.y - pj.y, pi.z - pj.z, sij, e4, kqq, elj, ec, gx, gy, gz);
     }
+}
+
+// the workgroup's item: molecule b in conformation c, its atoms m0 .. m0 + n, and the thread's (atom, slice): up to 256 atoms one unit
+// per thread in JS slices (thread t: slice s of atom il0, active if s < JS), above that one slice and RX_APT atoms per thread
+struct RxItem {
+    int b, c;
+    size_t item;
+    int m0, n, JS, s, il0;
+    bool active;
+};
+
+// fills w and loads the molecule into sh.xs / sh.ps (no barrier: the caller's comes before the first read).  false: nothing to run --
+// a molecule without atoms, or one above the size limit (status 3 and nothing else)
+__device__ inline bool rx_begin(const grappa_mm_desc& d, const grappa_nb_desc& nb, int has_nb, int* status, RxShared& sh, RxItem& w) {
+    const int C = d.C, t = threadIdx.x;
+    w.b = (int)(blockIdx.x / (unsigned)C), w.c = (int)(blockIdx.x - (unsigned)w.b * (unsigned)C);
+    w.item = (size_t)w.b * C + w.c;
+    w.m0 = rx_clamp(d.atom_molptr[w.b], d.N);
+    const int n = rx_clamp(d.atom_molptr[w.b + 1], d.N) - w.m0, m0 = w.m0;
+    w.n = n;
+    if (n <= 0) return false;
+    if (n > RX_MAX) {
+        if (t == 0) status[w.item] = 3;
+        return false;
+    }
+    for (int il = t; il < n; il += RX_NT) {
+        const float* p = d.xyz + ((size_t)(m0 + il) * C + w.c) * 3;
+        sh.xs[il] = make_float4(p[0], p[1], p[2], has_nb ? nb.charge[m0 + il] : 0.f);
+        sh.ps[il] = has_nb ? make_float2(0.5f * nb.sigma[m0 + il], sqrtf(nb.epsilon[m0 + il])) : make_float2(0.f, 0.f);
+    }
+    w.JS = n > RX_NT ? 1 : (RX_NT / n < RX_JS ? RX_NT / n : RX_JS);
+    w.s = n > RX_NT ? 0 : t / n;
+    w.il0 = t - w.s * n;
+    w.active = w.s < w.JS;
+    return true;
+}
+
+// g = grad E at the coordinates in LDS, into the owners' registers: the partial gradient of every (atom, slice), a barrier, the owner adds
+// the slices in slice order and hands each of its atoms' gradients to each(k, g[k]) (what a caller tests or accumulates per atom, in
+// the same pass).  One barrier; sh.part is read after it, so another must pass before it is written again.
+template <class Each>
+__device__ __forceinline__ void rx_gradient(const grappa_mm_desc& d, const grappa_nb_desc& nb, int has_nb, RxShared& sh, const RxItem& w,
+                                            V3 (&g)[RX_APT], Each each) {
+    const int t = threadIdx.x, n = w.n;
+    if (w.active)
+        for (int il = w.il0; il < n; il += RX_NT) {
+            V3 p = rx_bonded(d, sh, w.m0 + il, w.s, w.JS, w.m0, n);
+            if (has_nb) {
+                float elj = 0.f, ec = 0.f;
+                rx_pairs(nb, sh, il, w.s, w.JS, w.m0, n, elj, ec, p.x, p.y, p.z);
+            }
+            const int u = w.s * n + il;
+            sh.part[u] = p.x, sh.part[RX_MAX + u] = p.y, sh.part[2 * RX_MAX + u] = p.z;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < RX_APT; ++k) {
+        const int il = t + k * RX_NT;
+        if (il < n) {
+            V3 gi = {sh.part[il], sh.part[RX_MAX + il], sh.part[2 * RX_MAX + il]};
+            for (int q = 1; q < w.JS; ++q) {
+                const int u = q * n + il;
+                gi.x += sh.part[u], gi.y += sh.part[RX_MAX + u], gi.z += sh.part[2 * RX_MAX + u];
+            }
+            g[k] = gi;
+            each(k, gi);
+        }
+    }
+}
+
+// The potential energy at the coordinates in LDS: the six terms as thread partials in fp32 (a thread's tuples t, t + 256, .. and the pairs
+// of its (atom, slice)), added in double in thread order -> sh.esum (every pair was counted from both of its atoms); their sum in thread 0.
+// A caller with one more sum to form hands it to the same two barriers: its thread partial `extra` goes through extra_part[RX_NT] and
+// thread 6 adds them the same way into *extra_sum (extra_part = NULL: none).
+// (Thread 6 because threads 0 .. 5 each add one of the six terms; *extra_sum holds the plain sum, any scaling is the caller's, and it
+// may be read only after this function returns, that is after the second barrier.)
+// sh.part must be free: every reader of the last partial gradients has passed a barrier.  Two barriers.
+__device__ __forceinline__ double rx_energies(const grappa_mm_desc& d, const grappa_nb_desc& nb, int has_nb, RxShared& sh, const RxItem& w,
+                                              float extra = 0.f, float* extra_part = nullptr, double* extra_sum = nullptr) {
+    const int t = threadIdx.x, b = w.b, n = w.n;
+    const auto ld = [&](int atom) { return rx_ld(sh, atom, w.m0, n); };
+    float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, x;
+    for (int tt = d.mol_ptr[0][b] + t; tt < d.mol_ptr[0][b + 1]; tt += RX_NT) e[0] += bonded_tuple_energy(d, 0, tt, ld, x);
+    for (int tt = d.mol_ptr[1][b] + t; tt < d.mol_ptr[1][b + 1]; tt += RX_NT) e[1] += bonded_tuple_energy(d, 1, tt, ld, x);
+    for (int l = 2; l < 4; ++l)
+        for (int tt = d.mol_ptr[l][b] + t; tt < d.mol_ptr[l][b + 1]; tt += RX_NT) e[l] += bonded_tuple_energy(d, l, tt, ld, x);
+    if (has_nb && w.active)
+        for (int il = w.il0; il < n; il += RX_NT) {
+            float gx = 0.f, gy = 0.f, gz = 0.f;
+            rx_pairs(nb, sh, il, w.s, w.JS, w.m0, n, e[4], e[5], gx, gy, gz);
+        }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) sh.part[q * RX_NT + t] = e[q];
+    if (extra_part) extra_part[t] = extra;
+    __syncthreads();
+    if (t < 6) {
+        double sum = 0.0;
+        for (int k = 0; k < RX_NT; ++k) sum += (double)sh.part[t * RX_NT + k];
+        sh.esum[t] = t < 4 ? sum : 0.5 * sum;
+    } else if (t == 6 && extra_part) {
+        double sum = 0.0;
+        for (int k = 0; k < RX_NT; ++k) sum += (double)extra_part[k];
+        *extra_sum = sum;
+    }
+    __syncthreads();
+    double tot = 0.0;
+    if (t == 0)
+        for (int q = 0; q < 6; ++q) tot += sh.esum[q];
+    return tot;
 }
 
 // two maxima and three sums over the workgroup, in a fixed order; every thread gets the same bits.  One barrier.

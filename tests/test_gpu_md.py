@@ -190,6 +190,23 @@ def test_step_zero(hip, name):
     assert bool(((got["ekin"].double() - want).abs() <= 8 * kr.U32 * want).all()), (got["ekin"].tolist(), want.tolist())
 
 
+@pytest.mark.parametrize("name", ["mixed", "edge256", "max"])
+def test_step_zero_potential_energy_has_the_minimiser_s_bits(hip, name):
+    """n_steps = 0 against relax_fire at max_steps = 0 on the same coordinates: both kernels take the energy from the one sum of
+    csrc/rx_force.h (rx_energies), so epot and energy are the same bits, with the nonbonded tables and without them"""
+    from grappa_amd.relax import RELAX_DEFAULTS
+    b, m = md.case(name), md.masses(name)
+    plan, x = b.plan("cuda"), b.xyz.to("cuda")
+    ks, eqs = [k.to("cuda") for k in b.ks], [None if q is None else q.to("cuda") for q in b.eqs]
+    for nb in ("full", None):
+        got = _run(hip, b, m, md.keys(name), vel=md.thermal_velocities(name), nb=nb, n_steps=0)
+        xo, e, gm = torch.empty_like(x), torch.zeros(b.B, x.shape[1], device="cuda"), torch.zeros(b.B, x.shape[1], device="cuda")
+        st, ss = torch.zeros_like(e, dtype=torch.int32), torch.zeros_like(e, dtype=torch.int32)
+        hip.relax_fire(plan, x, ks, eqs, b.n_per, False, None if nb is None else b.nonbonded().to("cuda"),
+                       {**RELAX_DEFAULTS, "max_steps": 0, "tolerance": 0.0}, xo, e, gm, st, ss)
+        assert torch.equal(_bits(got["epot"]), _bits(e.cpu())), f"{name} nb={nb}: epot {got['epot'].tolist()} energy {e.cpu().tolist()}"
+
+
 # ------------------------------------------------------------------------------------------------ 3. trajectories, no thermostat
 TRAJ = [(n, s) for n in md.CASES for s in md.TRAJ_STEPS]
 
