@@ -197,6 +197,10 @@ SIGNATURES = {
     "grappa_seqattn_bwd_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "grappa_seqattn_fwd_amax_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "grappa_seqattn_bwd_amax_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "grappa_seqattn_fwd_idx_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "grappa_seqattn_fwd_pairs_idx_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "grappa_seqattn_bwd_idx_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_tuple_gather_bwd2_f32": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "grappa_perm_concat_fwd_f32": (_i, [_vp, _i, _i, _i, _i, c_int_p, _vp, _vp]),
     "grappa_perm_concat_bwd_f32": (_i, [_vp, _i, _i, _i, _i, c_int_p, _vp, _vp]),
     "grappa_param_out_fwd_f32": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp]),

@@ -235,6 +235,11 @@ class HipBackend(MMBackend):
         # ... and the first layer of the angle / proper heads (ops.ProjFirstLayerFn: LayerNorm + q | k | v on (atom, position) rows) through the same
         # kernels in their gather mode; 0: the unfused sequence behind the table-level products
         self.fused_first_layer = os.environ.get("GRAPPA_FUSED_FIRST_LAYER", "1") not in ("0", "")
+        # the unfused fp32 first layer (ops.ProjFirstLayerFn) keeps q | k | v on the table: the attention kernels read a token's row through the
+        # table index (grappa_seqattn_*_idx_f32), and the token sums of the backward pass run with several rows in flight and write the row maxima
+        # of what they sum (grappa_tuple_gather_bwd2_f32).  GRAPPA_FIRST_LAYER_INDEXED=0: the token-level copy of q | k | v and the one-row-at-a-time
+        # sums -- the reference of the equality tests and the other leg of tools/first_layer_ab.sh
+        self.first_layer_indexed = os.environ.get("GRAPPA_FIRST_LAYER_INDEXED", "1") not in ("0", "")
         self._wplanes = {}     # (data_ptr, rows, cols, transposed) -> _PlanesEntry
         self._wpairs = {}      # (data_ptr, rows, cols, "pairs" | "pairsT") -> _PairsEntry
         self._wptable = None   # _PairsTable of the registered pairs
@@ -1519,7 +1524,11 @@ class HipBackend(MMBackend):
         _chk(fn(self._stream(), T, s, W, a.data_ptr(), _f32_2d(a, "a", dev, dt), idx.data_ptr(), _ptr(pe),
                 x.data_ptr(), _f32_2d(x, "x", dev, dt)), "grappa_tuple_gather_fwd")
 
-    def tuple_gather_bwd(self, inv_ptr, inv_rows, dx, da, has_pe: bool, accumulate=False) -> None:
+    def tuple_gather_bwd(self, inv_ptr, inv_rows, dx, da, has_pe: bool, accumulate=False, amax=False, second=None):
+        """da[n] = sum of the rows dx[inv_rows[inv_ptr[n] : inv_ptr[n + 1]]] (+ da[n] with accumulate), in list order.  fp32 with
+        `first_layer_indexed`: the launch that keeps several rows in flight (same bits), which can also write da's row maxima (amax: True,
+        or None = where the backward products read them; -> Amax record of da) and sum a second table over the same incidence
+        (second = (dx2, da2))."""
         dev = da.device
         N, W = da.shape[0], dx.shape[1]
         if inv_ptr.dtype != torch.int32 or inv_ptr.numel() != N + 1 or inv_ptr.device != dev or inv_rows.dtype != torch.int32:
@@ -1527,21 +1536,50 @@ class HipBackend(MMBackend):
         if da.shape[1] < W or inv_rows.numel() != dx.shape[0]:
             raise ValueError("tuple_gather_bwd: shapes")
         dt = _same_dtype(dx, da)
+        if self.first_layer_indexed and da.dtype == torch.float32:
+            row = self._new_row_amax(da, True, None if amax is None else bool(amax))
+            W2 = ld2x = ld2a = 0
+            dx2 = da2 = None
+            if second is not None:
+                dx2, da2 = second
+                W2 = dx2.shape[1]
+                if da2.shape[0] != N or da2.shape[1] < W2 or dx2.shape[0] != dx.shape[0] or _same_dtype(dx2, da2) != dt:
+                    raise ValueError("tuple_gather_bwd: shapes of the second table")
+                ld2x, ld2a = _f32_2d(dx2, "dx2", dev, dt), _f32_2d(da2, "da2", dev, dt)
+            _chk(self.lib.grappa_tuple_gather_bwd2_f32(self._stream(), N, inv_ptr.data_ptr(), inv_rows.data_ptr(), int(has_pe), int(accumulate),
+                                                       W, dx.data_ptr(), _f32_2d(dx, "dx", dev, dt), da.data_ptr(), _f32_2d(da, "da", dev, dt), _ptr(row),
+                                                       W2, _ptr(dx2), ld2x, _ptr(da2), ld2a, None), "grappa_tuple_gather_bwd2_f32")
+            return Amax(row=row) if row is not None else None
         fn = getattr(self.lib, f"grappa_tuple_gather_bwd_{_sfx(da)}")
-        _chk(fn(self._stream(), N, W, inv_ptr.data_ptr(), inv_rows.data_ptr(), dx.data_ptr(),
-                _f32_2d(dx, "dx", dev, dt), da.data_ptr(), _f32_2d(da, "da", dev, dt), int(has_pe), int(accumulate)),
-             "grappa_tuple_gather_bwd")
+        for x_, a_ in ((dx, da),) + ((second,) if second is not None else ()):
+            _chk(fn(self._stream(), N, x_.shape[1], inv_ptr.data_ptr(), inv_rows.data_ptr(), x_.data_ptr(),
+                    _f32_2d(x_, "dx", dev, dt), a_.data_ptr(), _f32_2d(a_, "da", dev, dt), int(has_pe), int(accumulate)),
+                 "grappa_tuple_gather_bwd")
+        return None
 
-    def seqattn_fwd(self, qkv, s, T, nheads, out, amax=None, pairs=False):
+    def _row_index(self, row_idx, s, T, qkv, table_rows, who):
+        """the checks tuple_gather_fwd applies to its index, for the attention kernels that read q | k | v rows of a table through it"""
+        if row_idx.dtype != torch.int32 or row_idx.device != qkv.device or not row_idx.is_contiguous() or tuple(row_idx.shape) != (T, s):
+            raise ValueError(f"{who}: row_idx must be contiguous int32 (T,s)")
+        if qkv.dtype != torch.float32 or (table_rows is not None and qkv.shape[0] != table_rows):
+            raise ValueError(f"{who}: the indexed q | k | v table must be float32 of table_rows rows")
+
+    def seqattn_fwd(self, qkv, s, T, nheads, out, amax=None, pairs=False, row_idx=None, table_rows=None):
+        """row_idx (int32 (T, s)): qkv is a TABLE and the q | k | v row of token (pos, t) is qkv[row_idx[t, pos]]; outputs stay token-level"""
+        if row_idx is not None:
+            self._row_index(row_idx, s, T, qkv, table_rows, "seqattn_fwd")
         if pairs:               # the output in the pair format ONLY (`out` is not written and may be None): inference
             dev = qkv.device
             F = qkv.shape[1] // 3
-            if qkv.dtype != torch.float32 or qkv.shape != (s * T, 3 * F) or F % nheads or F % 32 or F > 512:
+            if qkv.dtype != torch.float32 or qkv.shape[1] != 3 * F or (row_idx is None and qkv.shape[0] != s * T) or F % nheads or F % 32 or F > 512:
                 raise ValueError("seqattn_fwd: the pair format needs float32 q, k, v of F % 32 == 0, F <= 512 columns each")
             _flat(qkv, "qkv", dev)
             row = torch.empty(s * T, dtype=torch.int32, device=dev)
             pr = torch.empty((s * T, 2 * F), dtype=torch.float16, device=dev)
-            if T:
+            if T and row_idx is not None:
+                _chk(self.lib.grappa_seqattn_fwd_pairs_idx_f32(self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), row_idx.data_ptr(), pr.data_ptr(),
+                                                               pr.stride(0), row.data_ptr()), "grappa_seqattn_fwd_pairs_idx_f32")
+            elif T:
                 _chk(self.lib.grappa_seqattn_fwd_pairs_f32(self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), pr.data_ptr(), pr.stride(0),
                                                            row.data_ptr()), "grappa_seqattn_fwd_pairs_f32")
             return Amax(row=row, pairs=pr)
@@ -1549,9 +1587,13 @@ class HipBackend(MMBackend):
         dt = _same_dtype(qkv, out)
         _flat(qkv, "qkv", dev, dt), _flat(out, "out", dev, dt)
         F = out.shape[1]
-        if qkv.shape != (s * T, 3 * F) or out.shape[0] != s * T or F % nheads:
+        if qkv.shape[1] != 3 * F or (row_idx is None and qkv.shape[0] != s * T) or out.shape[0] != s * T or F % nheads:
             raise ValueError("seqattn_fwd: shapes")
         row = self._new_row_amax(out, False, amax)
+        if row_idx is not None:
+            _chk(self.lib.grappa_seqattn_fwd_idx_f32(self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), row_idx.data_ptr(), out.data_ptr(),
+                                                     _ptr(row)), "grappa_seqattn_fwd_idx_f32")
+            return Amax(row=row) if row is not None else None
         args = (self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), out.data_ptr())
         if row is not None:
             _chk(self.lib.grappa_seqattn_fwd_amax_f32(*args, row.data_ptr()), "grappa_seqattn_fwd_amax_f32")
@@ -1715,14 +1757,21 @@ class HipBackend(MMBackend):
         a.part, a.nrows, a.n, a.out, a.out2, a.n_first, a.accumulate = part.data_ptr(), nrows, 2 * W, dg.data_ptr(), db.data_ptr(), W, 1
         _chk(self.lib.grappa_colsum_partials_batched(self._stream(), arr, 1), "grappa_colsum_partials_batched")
 
-    def seqattn_bwd(self, qkv, dout, s, T, nheads, dqkv, amax=None):
+    def seqattn_bwd(self, qkv, dout, s, T, nheads, dqkv, amax=None, row_idx=None):
+        """row_idx: as seqattn_fwd (qkv is the table; dqkv stays token-level)"""
         dev = dqkv.device
         dt = _same_dtype(qkv, dout, dqkv)
         _flat(qkv, "qkv", dev, dt), _flat(dout, "dout", dev, dt), _flat(dqkv, "dqkv", dev, dt)
         F = dout.shape[1]
-        if qkv.shape != (s * T, 3 * F) or dqkv.shape != qkv.shape or dout.shape[0] != s * T:
+        if row_idx is not None:
+            self._row_index(row_idx, s, T, qkv, None, "seqattn_bwd")
+        if qkv.shape[1] != 3 * F or (row_idx is None and qkv.shape[0] != s * T) or tuple(dqkv.shape) != (s * T, 3 * F) or dout.shape[0] != s * T:
             raise ValueError("seqattn_bwd: shapes")
         row = self._new_row_amax(dqkv, True, amax)
+        if row_idx is not None:
+            _chk(self.lib.grappa_seqattn_bwd_idx_f32(self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), row_idx.data_ptr(), dout.data_ptr(),
+                                                     dqkv.data_ptr(), _ptr(row)), "grappa_seqattn_bwd_idx_f32")
+            return Amax(row=row) if row is not None else None
         args = (self._stream(), s, T, nheads, F // nheads, qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr())
         if row is not None:
             _chk(self.lib.grappa_seqattn_bwd_amax_f32(*args, row.data_ptr()), "grappa_seqattn_bwd_amax_f32")

@@ -364,7 +364,7 @@ class CapturedForward:
         if ps is None:
             ps = self._params = list(self.model.parameters())
         return (be.gemm_precision_name, getattr(be, "gemm_precision_bwd", None), be.inference_pairs, be.training_pairs, be._tails, be.plan_override,
-                be.splitk_reduce, be.weight_pairs_min_rows, be.pairs_min_rows, tuple(p.data_ptr() for p in ps))
+                be.splitk_reduce, be.weight_pairs_min_rows, be.pairs_min_rows, getattr(be, "first_layer_indexed", None), tuple(p.data_ptr() for p in ps))
 
     def valid(self) -> bool:
         """the per-weight caches (maxima, pair splits) were filled OUTSIDE the graph: a graph captured before the weights changed must not be

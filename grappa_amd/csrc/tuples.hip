@@ -70,13 +70,139 @@ __device__ inline unsigned wave_umax(unsigned v) {
     return v;
 }
 
+// tuple_gather_bwd with several incident rows in flight (grappa_tuple_gather_bwd2_f32).  One wavefront per destination row, as above, but a
+// lane holds NC column chunks of a row and the loads of FOUR incident rows (their indices first, then 4 * NC 16-byte loads) are issued
+// before the first add: 4 - 24 KB in flight per wave instead of one 1-KB load.  Every element is still acc += v over j = r0 .. r1-1 in
+// ascending order from 0 (or from dst): the bits of tuple_gather_bwd_kernel.  -> the largest magnitude of the columns written
+// (the zeroed last column of has_pe left out).
+template <int NC>
+__device__ __forceinline__ unsigned gather_sum_cols(int lane, int r0, int r1, const int* __restrict__ inv_rows, const float* __restrict__ dx, int lddx,
+                                                    float* __restrict__ dst, int c0, int nvec, int has_pe, int accumulate) {
+    // a lane past the row's end reads the row's last chunk instead (no branch around any load) and stores nothing
+    float4 acc[NC];
+    int cc[NC];
+    bool ok[NC], last[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const int c = c0 + k * 64 + lane;
+        ok[k] = c < nvec;
+        cc[k] = min(c, nvec - 1);
+        last[k] = has_pe && cc[k] == nvec - 1;
+        acc[k] = accumulate ? ld4(dst, cc[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    int j = r0;
+    for (; j + 4 <= r1; j += 4) {
+        int r[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) r[u] = inv_rows[j + u];
+        float4 v[4][NC];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float* src = dx + (size_t)r[u] * lddx;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) v[u][k] = ld4(src, cc[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);       // every load above is issued before the first add below: 4 * NC KB in flight per wave
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                if (last[k]) v[u][k].w = 0.f;
+                acc[k].x += v[u][k].x; acc[k].y += v[u][k].y; acc[k].z += v[u][k].z; acc[k].w += v[u][k].w;
+            }
+        }
+    }
+    const int cnt = r1 - j;                      // 0 .. 3 rows left (wave-uniform)
+    if (cnt > 0) {
+        int r[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) r[u] = inv_rows[u < cnt ? j + u : j];
+        float4 v[3][NC];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            if (u < cnt) {
+                const float* src = dx + (size_t)r[u] * lddx;
+#pragma unroll
+                for (int k = 0; k < NC; ++k) v[u][k] = ld4(src, cc[k]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            if (u < cnt) {                       // (a row that is not there is not added as zeros either: -0 + 0 = +0)
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    if (last[k]) v[u][k].w = 0.f;
+                    acc[k].x += v[u][k].x; acc[k].y += v[u][k].y; acc[k].z += v[u][k].z; acc[k].w += v[u][k].w;
+                }
+            }
+        }
+    }
+    unsigned am = 0u;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        if (ok[k]) {
+            st4(dst, c0 + k * 64 + lane, acc[k]);
+            if (last[k]) acc[k].w = 0.f;
+            am = max(am, mag4(acc[k]));
+        }
+    }
+    return am;
+}
+
+template <int NC>
+__device__ __forceinline__ void gather_sum_row(int lane, int n, int r0, int r1, const int* __restrict__ inv_rows, int W, const float* __restrict__ dx,
+                                               int lddx, float* __restrict__ da, int ldda, unsigned* __restrict__ row_amax, int has_pe, int accumulate) {
+    const int nvec = W >> 2;
+    float* dst = da + (size_t)n * ldda;
+    unsigned am = 0u;
+    for (int c0 = 0; c0 < nvec; c0 += NC * 64) am = max(am, gather_sum_cols<NC>(lane, r0, r1, inv_rows, dx, lddx, dst, c0, nvec, has_pe, accumulate));
+    if (row_amax) {
+        am = wave_umax(am);
+        if (lane == 0) row_amax[n] = am;
+    }
+}
+
+// NC / NC2: column chunks per lane of the first / the second table (NC2 = 0: no second table)
+template <int NC, int NC2>
+__global__ __launch_bounds__(256) void tuple_gather_bwd2_kernel(int N, const int* __restrict__ inv_ptr, const int* __restrict__ inv_rows, int has_pe,
+                                                                int accumulate, int W, const float* __restrict__ dx, int lddx, float* __restrict__ da,
+                                                                int ldda, unsigned* __restrict__ da_amax, int W2, const float* __restrict__ dx2, int lddx2,
+                                                                float* __restrict__ da2, int ldda2, unsigned* __restrict__ da2_amax) {
+    const int lane = threadIdx.x & 63;
+    const int n = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);      // (wave-uniform: the list and its loops stay scalar)
+    if (n >= N) return;
+    const int r0 = inv_ptr[n], r1 = inv_ptr[n + 1];
+    gather_sum_row<NC>(lane, n, r0, r1, inv_rows, W, dx, lddx, da, ldda, da_amax, has_pe, accumulate);
+    if constexpr (NC2 > 0) gather_sum_row<NC2>(lane, n, r0, r1, inv_rows, W2, dx2, lddx2, da2, ldda2, da2_amax, has_pe, accumulate);
+}
+
+// the q | k | v rows of tuple t's S tokens: token-level rows pos*T + t, or (IDX) rows of a table through row_idx (T, S) -- the first layer
+// of a head on (atom, position) rows (ops.ProjFirstLayerFn), whose q | k | v are never copied to the tokens.  The S indices are wave-uniform
+// and read before the first row load.
+template <int S, bool IDX, typename TE>
+__device__ __forceinline__ void qkv_rows(const TE* __restrict__ qkv, const int* __restrict__ row_idx, int T, int t, int F, const TE* (&rows)[S]) {
+    if constexpr (IDX) {
+        int r[S];
+#pragma unroll
+        for (int i = 0; i < S; ++i) r[i] = __builtin_amdgcn_readfirstlane(row_idx[(size_t)t * S + i]);
+#pragma unroll
+        for (int i = 0; i < S; ++i) rows[i] = qkv + (size_t)r[i] * 3 * F;
+    } else {
+#pragma unroll
+        for (int i = 0; i < S; ++i) rows[i] = qkv + ((size_t)i * T + t) * 3 * F;
+    }
+}
+
 // row_amax (optional): largest |out| of each of the tuple's S token rows
-template <int S, typename TE>
+template <int S, typename TE, bool IDX = false>
 __device__ __forceinline__ void seqattn_fwd_body(int T, int F, int dh, const TE* __restrict__ qkv, TE* __restrict__ out,
-                                                 unsigned* __restrict__ row_amax, int vblock) {
+                                                 unsigned* __restrict__ row_amax, int vblock, const int* __restrict__ row_idx = nullptr) {
     const int lane = threadIdx.x & 63;
     const int t = (vblock * blockDim.x + threadIdx.x) >> 6;
     if (t >= T) return;
+    const TE* rows[S];
+    qkv_rows<S, IDX, TE>(qkv, row_idx, T, t, F, rows);
     const int nvec = F >> 2, lph = dh >> 2;
     const float scale = 1.0f / sqrtf((float)dh);
     unsigned am[S];
@@ -88,7 +214,7 @@ __device__ __forceinline__ void seqattn_fwd_body(int T, int F, int dh, const TE*
         float4 q[S], k[S], v[S];
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-            const TE* row = qkv + ((size_t)i * T + t) * 3 * F;
+            const TE* row = rows[i];
             q[i] = ok ? ld4(row, c) : make_float4(0.f, 0.f, 0.f, 0.f);
             k[i] = ok ? ld4(row, nvec + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             v[i] = ok ? ld4(row, 2 * nvec + c) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -134,6 +260,11 @@ __global__ __launch_bounds__(256) void seqattn_fwd_kernel(int T, int F, int dh, 
                                                           unsigned* __restrict__ row_amax) {
     seqattn_fwd_body<S, TE>(T, F, dh, qkv, out, row_amax, blockIdx.x);
 }
+template <int S>
+__global__ __launch_bounds__(256) void seqattn_fwd_idx_kernel(int T, int F, int dh, const float* __restrict__ qkv_tab, const int* __restrict__ row_idx,
+                                                              float* __restrict__ out, unsigned* __restrict__ row_amax) {
+    seqattn_fwd_body<S, float, true>(T, F, dh, qkv_tab, out, row_amax, blockIdx.x, row_idx);
+}
 
 // the attention of several heads (different s, T) in ONE launch: C ABI 8 grappa_seqattn_fwd_batched_f32 / _bwd_
 struct SeqAttnBatch {
@@ -156,12 +287,14 @@ __global__ __launch_bounds__(256) void seqattn_fwd_batched_kernel(SeqAttnBatch b
 
 // The attention output straight in the PAIR format (common.h st_pairs4): in inference nothing but the out-projection product reads it.
 // The S x F outputs of a tuple stay in registers until their rows' maxima are known (F <= 512: two trips of 64 lanes x 4 columns).
-template <int S>
+template <int S, bool IDX = false>
 __global__ __launch_bounds__(256) void seqattn_fwd_pairs_kernel(int T, int F, int dh, const float* __restrict__ qkv, uint16_t* __restrict__ pairs, int ldp,
-                                                                unsigned* __restrict__ row_amax) {
+                                                                unsigned* __restrict__ row_amax, const int* __restrict__ row_idx) {
     const int lane = threadIdx.x & 63;
     const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (t >= T) return;
+    const float* rows[S];
+    qkv_rows<S, IDX, float>(qkv, row_idx, T, t, F, rows);
     const int nvec = F >> 2, lph = dh >> 2;
     const float scale = 1.0f / sqrtf((float)dh);
     unsigned am[S];
@@ -175,7 +308,7 @@ __global__ __launch_bounds__(256) void seqattn_fwd_pairs_kernel(int T, int F, in
         float4 q[S], k[S], v[S];
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-            const float* row = qkv + ((size_t)i * T + t) * 3 * F;
+            const float* row = rows[i];
             q[i] = ok ? ld4(row, c) : make_float4(0.f, 0.f, 0.f, 0.f);
             k[i] = ok ? ld4(row, nvec + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             v[i] = ok ? ld4(row, 2 * nvec + c) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -219,12 +352,15 @@ __global__ __launch_bounds__(256) void seqattn_fwd_pairs_kernel(int T, int F, in
     }
 }
 
-template <int S, typename TE>
+template <int S, typename TE, bool IDX = false>
 __device__ __forceinline__ void seqattn_bwd_body(int T, int F, int dh, const TE* __restrict__ qkv, const TE* __restrict__ dout,
-                                                 TE* __restrict__ dqkv, unsigned* __restrict__ row_amax, int vblock) {
+                                                 TE* __restrict__ dqkv, unsigned* __restrict__ row_amax, int vblock,
+                                                 const int* __restrict__ row_idx = nullptr) {
     const int lane = threadIdx.x & 63;
     const int t = (vblock * blockDim.x + threadIdx.x) >> 6;
     if (t >= T) return;
+    const TE* rows[S];
+    qkv_rows<S, IDX, TE>(qkv, row_idx, T, t, F, rows);
     const int nvec = F >> 2, lph = dh >> 2;
     const float scale = 1.0f / sqrtf((float)dh);
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -237,7 +373,7 @@ __device__ __forceinline__ void seqattn_bwd_body(int T, int F, int dh, const TE*
         float4 q[S], k[S], v[S], go[S], dq[S], dk[S], dv[S];
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-            const TE* row = qkv + ((size_t)i * T + t) * 3 * F;
+            const TE* row = rows[i];
             q[i] = ok ? ld4(row, c) : zero;
             k[i] = ok ? ld4(row, nvec + c) : zero;
             v[i] = ok ? ld4(row, 2 * nvec + c) : zero;
@@ -298,6 +434,11 @@ template <int S, typename TE>
 __global__ __launch_bounds__(256) void seqattn_bwd_kernel(int T, int F, int dh, const TE* __restrict__ qkv, const TE* __restrict__ dout,
                                                           TE* __restrict__ dqkv, unsigned* __restrict__ row_amax) {
     seqattn_bwd_body<S, TE>(T, F, dh, qkv, dout, dqkv, row_amax, blockIdx.x);
+}
+template <int S>
+__global__ __launch_bounds__(256) void seqattn_bwd_idx_kernel(int T, int F, int dh, const float* __restrict__ qkv_tab, const int* __restrict__ row_idx,
+                                                              const float* __restrict__ dout, float* __restrict__ dqkv, unsigned* __restrict__ row_amax) {
+    seqattn_bwd_body<S, float, true>(T, F, dh, qkv_tab, dout, dqkv, row_amax, blockIdx.x, row_idx);
 }
 
 __global__ __launch_bounds__(256) void seqattn_bwd_batched_kernel(SeqAttnBatch b) {
@@ -776,20 +917,116 @@ extern "C" int grappa_seqattn_bwd_amax_f32(void* stream, int s, int T, int nhead
                                            uint32_t* dqkv_amax) {
     return seqattn_bwd_impl<float>(stream, s, T, nheads, dh, qkv, dout, dqkv, dqkv_amax);
 }
-extern "C" int grappa_seqattn_fwd_pairs_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv, uint16_t* pairs, int ldp,
-                                            uint32_t* out_amax) {
+namespace {
+int seqattn_fwd_pairs_impl(void* stream, int s, int T, int nheads, int dh, const float* qkv, const int* row_idx, bool indexed, uint16_t* pairs, int ldp,
+                           uint32_t* out_amax) {
     const int F = nheads * dh;
     if (s < 1 || s > 4 || T < 0 || nheads <= 0 || dh <= 0 || (dh & 3) || !pow2(dh / 4) || dh / 4 > 64 || F > 512 || (F & 31) || ldp < 2 * F || (ldp & 7))
         return GRAPPA_ERR_ARG;
+    if (indexed && !row_idx) return GRAPPA_ERR_ARG;
     if (T == 0) return GRAPPA_OK;
     if (!qkv || !pairs || !out_amax || !aligned_el<float>(qkv) || (reinterpret_cast<uintptr_t>(pairs) & 15)) return GRAPPA_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((T + 3) / 4);
+    if (indexed) {
+        switch (s) {
+            case 1: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<1, true>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, row_idx); break;
+            case 2: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<2, true>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, row_idx); break;
+            case 3: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<3, true>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, row_idx); break;
+            default: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<4, true>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, row_idx); break;
+        }
+        return grappa_launch_status();
+    }
     switch (s) {
-        case 1: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<1>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax); break;
-        case 2: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<2>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax); break;
-        case 3: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<3>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax); break;
-        default: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<4>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax); break;
+        case 1: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<1>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, (const int*)nullptr); break;
+        case 2: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<2>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, (const int*)nullptr); break;
+        case 3: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<3>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, (const int*)nullptr); break;
+        default: GRAPPA_LAUNCH((seqattn_fwd_pairs_kernel<4>), grid, dim3(256), 0, st, T, F, dh, qkv, pairs, ldp, out_amax, (const int*)nullptr); break;
+    }
+    return grappa_launch_status();
+}
+
+bool seqattn_shape_ok(int s, int T, int nheads, int dh) {
+    return !(s < 1 || s > 4 || T < 0 || nheads <= 0 || dh <= 0 || (dh & 3) || !pow2(dh / 4) || dh / 4 > 64 || nheads * dh > 1024);
+}
+
+// chunks per lane of the multi-row gather sum: the whole row of a lane in registers up to 6 chunks (1536 columns), wider rows in groups of 6
+inline int gather_chunks(int W) {
+    const int n = ((W >> 2) + 63) / 64;
+    return n <= 4 ? n : 6;
+}
+template <int NC>
+void launch_gather_bwd2(hipStream_t st, int N, const int* inv_ptr, const int* inv_rows, int has_pe, int accumulate, int W, const float* dx, int lddx,
+                        float* da, int ldda, uint32_t* da_amax, int W2, const float* dx2, int lddx2, float* da2, int ldda2, uint32_t* da2_amax) {
+    const dim3 grid((N + 3) / 4);
+#define GRAPPA_GB2(NC2)                                                                                                                           \
+    GRAPPA_LAUNCH((tuple_gather_bwd2_kernel<NC, NC2>), grid, dim3(256), 0, st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, \
+                  da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax)
+    switch (W2 > 0 ? gather_chunks(W2) : 0) {      // (the second table: 2 or 6 chunks per lane)
+        case 0: GRAPPA_GB2(0); break;
+        case 1:
+        case 2: GRAPPA_GB2(2); break;
+        default: GRAPPA_GB2(6); break;
+    }
+#undef GRAPPA_GB2
+}
+}  // namespace
+
+extern "C" int grappa_seqattn_fwd_pairs_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv, uint16_t* pairs, int ldp,
+                                            uint32_t* out_amax) {
+    return seqattn_fwd_pairs_impl(stream, s, T, nheads, dh, qkv, nullptr, false, pairs, ldp, out_amax);
+}
+extern "C" int grappa_seqattn_fwd_pairs_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx,
+                                                uint16_t* pairs, int ldp, uint32_t* out_amax) {
+    return seqattn_fwd_pairs_impl(stream, s, T, nheads, dh, qkv_tab, row_idx, true, pairs, ldp, out_amax);
+}
+extern "C" int grappa_seqattn_fwd_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx, float* out,
+                                          uint32_t* out_amax) {
+    if (!seqattn_shape_ok(s, T, nheads, dh) || !row_idx) return GRAPPA_ERR_ARG;
+    if (T == 0) return GRAPPA_OK;
+    if (!qkv_tab || !out || !aligned_el<float>(qkv_tab) || !aligned_el<float>(out)) return GRAPPA_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((T + 3) / 4);
+    const int F = nheads * dh;
+    switch (s) {
+        case 1: GRAPPA_LAUNCH((seqattn_fwd_idx_kernel<1>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, out, out_amax); break;
+        case 2: GRAPPA_LAUNCH((seqattn_fwd_idx_kernel<2>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, out, out_amax); break;
+        case 3: GRAPPA_LAUNCH((seqattn_fwd_idx_kernel<3>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, out, out_amax); break;
+        default: GRAPPA_LAUNCH((seqattn_fwd_idx_kernel<4>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, out, out_amax); break;
+    }
+    return grappa_launch_status();
+}
+extern "C" int grappa_seqattn_bwd_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx, const float* dout,
+                                          float* dqkv, uint32_t* dqkv_amax) {
+    if (!seqattn_shape_ok(s, T, nheads, dh) || !row_idx) return GRAPPA_ERR_ARG;
+    if (T == 0) return GRAPPA_OK;
+    if (!qkv_tab || !dout || !dqkv || !aligned_el<float>(qkv_tab) || !aligned_el<float>(dout) || !aligned_el<float>(dqkv)) return GRAPPA_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((T + 3) / 4);
+    const int F = nheads * dh;
+    switch (s) {
+        case 1: GRAPPA_LAUNCH((seqattn_bwd_idx_kernel<1>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, dout, dqkv, dqkv_amax); break;
+        case 2: GRAPPA_LAUNCH((seqattn_bwd_idx_kernel<2>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, dout, dqkv, dqkv_amax); break;
+        case 3: GRAPPA_LAUNCH((seqattn_bwd_idx_kernel<3>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, dout, dqkv, dqkv_amax); break;
+        default: GRAPPA_LAUNCH((seqattn_bwd_idx_kernel<4>), grid, dim3(256), 0, st, T, F, dh, qkv_tab, row_idx, dout, dqkv, dqkv_amax); break;
+    }
+    return grappa_launch_status();
+}
+extern "C" int grappa_tuple_gather_bwd2_f32(void* stream, int N, const int* inv_ptr, const int* inv_rows, int has_pe, int accumulate, int W,
+                                            const float* dx, int lddx, float* da, int ldda, uint32_t* da_amax, int W2, const float* dx2, int lddx2,
+                                            float* da2, int ldda2, uint32_t* da2_amax) {
+    if (N < 0 || W <= 0 || (W & 3) || (lddx & 3) || (ldda & 3) || lddx < W || ldda < W) return GRAPPA_ERR_ARG;
+    if (W2 < 0 || (W2 > 0 && ((W2 & 3) || (lddx2 & 3) || (ldda2 & 3) || lddx2 < W2 || ldda2 < W2))) return GRAPPA_ERR_ARG;
+    if (N == 0) return GRAPPA_OK;
+    if (!inv_ptr || !da || !aligned_el<float>(da) || (dx && !aligned_el<float>(dx))) return GRAPPA_ERR_ARG;
+    if (W2 > 0 && (!da2 || !aligned_el<float>(da2) || (dx2 && !aligned_el<float>(dx2)))) return GRAPPA_ERR_ARG;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (gather_chunks(W)) {
+        case 1: launch_gather_bwd2<1>(st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax); break;
+        case 2: launch_gather_bwd2<2>(st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax); break;
+        case 3: launch_gather_bwd2<3>(st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax); break;
+        case 4: launch_gather_bwd2<4>(st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax); break;
+        default: launch_gather_bwd2<6>(st, N, inv_ptr, inv_rows, has_pe, accumulate, W, dx, lddx, da, ldda, da_amax, W2, dx2, lddx2, da2, ldda2, da2_amax); break;
     }
     return grappa_launch_status();
 }

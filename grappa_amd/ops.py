@@ -498,16 +498,19 @@ class SplitHeadsFn(Function):
         return acc, None
 
 
-def _attention(be, qkv, s, T, nheads, like, infer):
+def _attention(be, qkv, s, T, nheads, like, infer, row_idx=None):
     """-> (att or None, record of att's row maxima): the s <= 4 tokens of every tuple attend to each other.  Inference on the HIP
-    backend: the output is written in the pair format only (the record's .pairs) -- nothing but the out-projection reads it."""
-    M, Fd = qkv.shape[0], qkv.shape[1] // 3
+    backend: the output is written in the pair format only (the record's .pairs) -- nothing but the out-projection reads it.
+    row_idx (T, s): qkv is a table and token (pos, t) reads its row row_idx[t, pos] (ProjFirstLayerFn); att stays token-level."""
+    M, Fd = qkv.shape[0] if row_idx is None else s * T, qkv.shape[1] // 3
     if not T:
         return _new((M, Fd), like), None
-    if infer and hasattr(be, "pairs_ok") and be.pairs_ok(qkv, Fd, training=infer == 2) and 32 < Fd <= 512 and M > 32:        # (the out-projection must be able to read pairs: M, N > 32)
-        return None, be.seqattn_fwd(qkv, s, T, nheads, None, pairs=True)
+    kw = {} if row_idx is None else dict(row_idx=row_idx, table_rows=qkv.shape[0])
+    tok = qkv if row_idx is None else qkv[:1].expand(M, -1)       # (what decides the format is the token table's shape, not the table's)
+    if infer and hasattr(be, "pairs_ok") and be.pairs_ok(tok, Fd, training=infer == 2) and 32 < Fd <= 512 and M > 32:        # (the out-projection must be able to read pairs: M, N > 32)
+        return None, be.seqattn_fwd(qkv, s, T, nheads, None, pairs=True, **kw)
     att = _new((M, Fd), like)
-    return att, be.seqattn_fwd(qkv, s, T, nheads, att)
+    return att, be.seqattn_fwd(qkv, s, T, nheads, att, **kw)
 
 
 class ProjGatherFn(Function):
@@ -641,9 +644,10 @@ class ProjFirstLayerFn(Function):
     """ProjGatherFn followed by the first TransformerLayerFn, with that layer's LayerNorm and QKV product done once per
     (atom, position) row instead of once per token: a token x[pos*T + t] = [a[idx[t, pos]], pe[pos]] depends on its tuple only through
     (idx[t, pos], pos), and so do LN(x) and LN(x) W_in^T + b_in -- s*N table rows instead of s*T tokens (propers: 32,932 instead of
-    83,328 on the C2 batch).  The normed rows and their q, k, v are gathered to the tokens behind the product; backward sums the
-    token gradients into the table rows first (inverse incidence of the table) and runs the dgrad / wgrad products and the
-    LayerNorm backward on the table.  Same arithmetic per row as the two functions it replaces (reference
+    83,328 on the C2 batch).  The normed rows are gathered to the tokens behind the product (the out-projection's residual); q, k, v
+    stay on the table where the backend's attention kernels read a token's row through idx_tab (HipBackend.first_layer_indexed, fp32),
+    else they are gathered too.  Backward sums the token gradients into the table rows first (inverse incidence of the table) and
+    runs the dgrad / wgrad products and the LayerNorm backward on the table.  Same arithmetic per row as the two functions it replaces (reference
     models/interaction_parameters.py:155-180, perm_equiv_transformer.py:127-151, network_utils.py:112-133).
     tabs = batch.BatchPlan.position_tables(level)."""
 
@@ -691,11 +695,19 @@ class ProjFirstLayerFn(Function):
                 out._grappa_drop = (drop_p, seed2)
             return out
         ctx.fused_gather = False
-        x1, qkv = _new((M, Fd), tab), _new((M, 3 * Fd), tab)
+        # q | k | v stay on the table where the attention kernels read a token's row through idx_tab (HipBackend.first_layer_indexed, fp32):
+        # no token-level copy is written, and the backward pass keeps the table
+        ctx.indexed = indexed = bool(getattr(be, "first_layer_indexed", False)) and qkv_tab.dtype == F32 and T > 0
+        x1 = _new((M, Fd), tab)
         be.tuple_gather_fwd(x1_tab, idx_tab, s, None, x1)          # x1[pos*T + t] = x1_tab[pos*N + idx[t, pos]]
-        be.tuple_gather_fwd(qkv_tab, idx_tab, s, None, qkv)
+        if indexed:
+            qkv = qkv_tab
+            att, satt = _attention(be, qkv_tab, s, T, nheads, tab, infer, row_idx=idx_tab)
+        else:
+            qkv = _new((M, 3 * Fd), tab)
+            be.tuple_gather_fwd(qkv_tab, idx_tab, s, None, qkv)
+            att, satt = _attention(be, qkv, s, T, nheads, tab, infer)
         del qkv_tab
-        att, satt = _attention(be, qkv, s, T, nheads, tab, infer)
         x2 = _new((M, Fd), tab)
         satt = be.gemm(att, w_o, x2, M=M, N=Fd, K=Fd, bias=b_o, drop_p=drop_p, drop_seed=seed1, res=x1, a_scales=satt)
         del x1
@@ -703,7 +715,7 @@ class ProjFirstLayerFn(Function):
         ctx.cfg, ctx.scales = (s, T, N, Wp, pe is not None, nheads, drop_p, seed1, seed2), (sh, sx1, satt)
         ctx.ff_saved = ff_saved
         ctx.save_for_backward(h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows,
-                              w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2)
+                              w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, *((idx_tab,) if indexed else ()))
         if drop_p > 0:
             out._grappa_drop = (drop_p, seed2)            # (TransformerLayerFn.forward)
         return out
@@ -712,7 +724,7 @@ class ProjFirstLayerFn(Function):
     def backward(ctx, dout):
         be = get_backend()
         idx_tab = None
-        if getattr(ctx, "fused_gather", False):
+        if getattr(ctx, "fused_gather", False) or getattr(ctx, "indexed", False):
             (h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows,
              w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, idx_tab) = ctx.saved_tensors      # (qkv: the TABLE here)
         else:
@@ -733,7 +745,10 @@ class ProjFirstLayerFn(Function):
             _linear_bwd_params(be, dz1, sv["x3"], w1, b1, None, None)
             _linear_bwd_params(be, dzo, att, w_o, b_o, None, None)
         else:
-            if idx_tab is not None:                 # fused forward, unfused backward (A/B switch): the token-level q | k | v the unfused attention backward reads
+            row_idx = None
+            if idx_tab is not None and getattr(be, "first_layer_indexed", False) and qkv.dtype == F32:
+                row_idx = idx_tab                   # qkv is the table: the attention backward reads its rows through the index
+            elif idx_tab is not None:               # fused forward, unfused backward (A/B switch): the token-level q | k | v the unfused attention backward reads
                 qkv_tok = _new((M, 3 * Fd), tab)
                 be.tuple_gather_fwd(qkv, idx_tab, s, None, qkv_tok)
                 qkv = qkv_tok
@@ -743,14 +758,22 @@ class ProjFirstLayerFn(Function):
             sz = _linear_bwd_params(be, dzo, att, w_o, b_o, satt, sz)
             datt = _new((M, Fd), qkv)
             be.gemm(dzo, w_o, datt, M=M, N=Fd, K=Fd, b_kcontig=False, a_scales=sz)
-            dqkv = _new(qkv.shape, qkv)
-            be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv)                      # (its rows are summed into the table before any product reads them)
+            dqkv = _new((M, 3 * Fd), qkv)
+            if row_idx is not None:
+                be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv, amax=False, row_idx=row_idx)
+            else:
+                be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv)                  # (its rows are summed into the table before any product reads them)
         # token gradients -> table rows (pos*N + n): the q, k, v gradients and the skip branch of x1
         dqkv_tab, dres_tab = _new((s * N, 3 * Fd), qkv), _new((s * N, Fd), qkv)
-        be.tuple_gather_bwd(invtab_ptr, invtab_rows, dqkv, dqkv_tab, False, False)
-        be.tuple_gather_bwd(invtab_ptr, invtab_rows, dx2, dres_tab, False, False)
+        if getattr(be, "first_layer_indexed", False) and dqkv.dtype == F32:
+            # one launch over the incidence for both tables, which also writes the row maxima of dqkv_tab the two products below read
+            sz = be.tuple_gather_bwd(invtab_ptr, invtab_rows, dqkv, dqkv_tab, False, False, amax=None, second=(dx2, dres_tab))
+        else:
+            be.tuple_gather_bwd(invtab_ptr, invtab_rows, dqkv, dqkv_tab, False, False)
+            be.tuple_gather_bwd(invtab_ptr, invtab_rows, dx2, dres_tab, False, False)
+            sz = None
         del dqkv
-        sz = _linear_bwd_params(be, dqkv_tab, x1_tab, w_in, b_in, sx1, None)
+        sz = _linear_bwd_params(be, dqkv_tab, x1_tab, w_in, b_in, sx1, sz)
         if hasattr(be, "credit"):
             be.credit("gemm_saved", 2.0 * 2.0 * (M - s * N) * 3 * Fd * Fd)
         dx1_tab = _new(x1_tab.shape, x1_tab)

@@ -157,7 +157,7 @@ class Trainer:
         # activation storage, fused layer switches -- a setting changed in the middle of a run means new graphs, not stale ones
         backend_cfg = tuple(getattr(be, k, None) for k in ("gemm_precision_name", "gemm_precision_bwd_name", "inference_pairs", "training_pairs", "backward_pairs",
                                                             "_tails", "plan_override", "splitk_reduce", "weight_pairs_min_rows", "pairs_min_rows",
-                                                            "fused_writer_layer", "fused_writer_layer_bwd", "group_launches", "wgrads_aside"))
+                                                            "fused_writer_layer", "fused_writer_layer_bwd", "first_layer_indexed", "group_launches", "wgrads_aside"))
         return (float(lf.gradient_weight), float(lf.energy_weight), float(lf.param_weight), float(lf.tuplewise_weight), float(lf.proper_regularisation),
                 float(lf.improper_regularisation), tuple(sorted(lf.weights.items())), tuple(sorted(lf.param_weights_by_dataset.items())),
                 tuple(o.betas), float(o.eps), float(o.weight_decay), o.max_grad_norm, bool(self.model.training), backend_cfg,

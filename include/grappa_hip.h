@@ -401,6 +401,24 @@ int grappa_seqattn_fwd_amax_f32(void* stream, int s, int T, int nheads, int dh, 
 int grappa_seqattn_fwd_pairs_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv, uint16_t* pairs, int ldp, uint32_t* out_amax);
 int grappa_seqattn_bwd_amax_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv, const float* dout, float* dqkv,
                                 uint32_t* dqkv_amax);
+/* The same attention kernels reading q | k | v through a row index (the first layer of a head computed on (atom, position) table rows):
+ * the q | k | v row of token (pos, t) is qkv_tab[row_idx[t*s + pos]] (row_idx: int32 (T, s), required) instead of qkv[pos*T + t]; every
+ * output (out / pairs / dqkv and the row maxima) stays token-level at pos*T + t.  Same limits and the same bits as the entry points above
+ * run on the gathered copy; out_amax / dqkv_amax may be NULL except for the pair format. */
+int grappa_seqattn_fwd_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx, float* out,
+                               uint32_t* out_amax);
+int grappa_seqattn_fwd_pairs_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx, uint16_t* pairs,
+                                     int ldp, uint32_t* out_amax);
+int grappa_seqattn_bwd_idx_f32(void* stream, int s, int T, int nheads, int dh, const float* qkv_tab, const int* row_idx, const float* dout,
+                               float* dqkv, uint32_t* dqkv_amax);
+/* gather_bwd with several incident rows in flight per wavefront (each element is still summed over its list in ascending order: the bits
+ * of grappa_tuple_gather_bwd_f32), optionally writing the largest magnitude of every destination row (da_amax: N fp32 bit patterns with
+ * the sign cleared, as grappa_amax_f32's row maxima; the zeroed column W-1 of has_pe does not enter it; NULL: not wanted), and optionally
+ * summing a second table of another width over the SAME incidence in the same launch (W2 > 0: dx2 -> da2, da2_amax; has_pe and
+ * accumulate apply to both). */
+int grappa_tuple_gather_bwd2_f32(void* stream, int N, const int* inv_ptr, const int* inv_rows, int has_pe, int accumulate,
+                                 int W, const float* dx, int lddx, float* da, int ldda, uint32_t* da_amax,
+                                 int W2, const float* dx2, int lddx2, float* da2, int ldda2, uint32_t* da2_amax);
 
 /* Symmetriser input (perm_equiv_transformer.py:248-261): z[p*T+t, j*F+f] = x[perm[p*s+j]*T+t, f].
  * bwd: dx[i*T+t, f] = sum_p dz[p*T+t, inv_p(i)*F+f].  h_perm is a HOST array (P*s ints). */
