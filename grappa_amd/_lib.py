@@ -230,6 +230,13 @@ SIGNATURES = {
                                     _vp, _vp, _vp]),
     "grappa_md_philox": (None, [_u64, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint * 4)]),
     "grappa_md_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
+    # the same dynamics for molecules of any size, stepwise (additions to ABI 11)
+    "grappa_md_steps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "grappa_md_steps_init_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _i, _i, _vp, _sz]),
+    "grappa_md_steps_run_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i,
+                                     _vp, _vp, _vp]),
+    "grappa_md_steps_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _i, _i, _vp, _sz,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,5 +1,5 @@
 """The molecular-mechanics part of `HipBackend` (backend.py inherits it): bonded energy, gradient and backward, nonbonded terms, the
-two FIRE minimisers and Langevin dynamics.  Every method reads as checks, descriptor, call; what several of them check the same way
+two FIRE minimisers and the two Langevin dynamics.  Every method reads as checks, descriptor, call; what several of them check the same way
 is a helper here.  It uses `self.lib`, `self._stream()` and `self._workspace()` of the backend."""
 from __future__ import annotations
 
@@ -223,6 +223,18 @@ class MMBackend:
                                             energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
              "grappa_relax_fire_f32")
 
+    def _item_table(self, nb, counts, N, Cc, dev):
+        """the work-item table of the stepwise paths: the nonbonded plan of these molecules for this C (it is about atoms: it also serves
+        nb = None), reused from nb's cache of plans where nb keeps one"""
+        cache = getattr(nb, "_plans", None) if nb is not None else None
+        table = cache.get(Cc) if isinstance(cache, dict) else None
+        if table is None or table[0] is None or table[0].device != dev:
+            molptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64).cumsum(0)]).to(torch.int32)
+            table = self.nonbonded_plan(molptr, N, Cc, dev)
+            if isinstance(cache, dict) and nb.charge.device == dev:
+                cache[Cc] = table
+        return table
+
     def relax_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
                     atom_counts_host=None, check_every: int = 32, workspace=None) -> None:
         """the stepwise FIRE minimiser for molecules of any size (include/grappa_hip.h grappa_relax_steps_*_f32): the loop, the
@@ -247,14 +259,7 @@ class MMBackend:
         o = _opts_struct(_lib.RelaxOpts, opts, "relax_steps")
         if N == 0 or Cc == 0 or B == 0:
             return
-        # the work-item table: the nonbonded plan of these molecules for this C (it is about atoms: it also serves nb = None)
-        cache = getattr(nb, "_plans", None) if nb is not None else None
-        table = cache.get(Cc) if isinstance(cache, dict) else None
-        if table is None or table[0] is None or table[0].device != dev:
-            molptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(counts, dtype=torch.int64).cumsum(0)]).to(torch.int32)
-            table = self.nonbonded_plan(molptr, N, Cc, dev)
-            if isinstance(cache, dict) and nb.charge.device == dev:
-                cache[Cc] = table
+        table = self._item_table(nb, counts, N, Cc, dev)
         table_dev, n_items, n_blocks, _ = table
         need = int(self.lib.grappa_relax_steps_workspace_bytes(N, Cc, B, n_blocks))
         if workspace is None:
@@ -276,20 +281,14 @@ class MMBackend:
                                                     steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
 
     # ------------------------------------------------------------------ dynamics
-    def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
-                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
-        """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
-        (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
-        as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
-        atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
-        init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
-        n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
-        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
-        _xyz3(xyz, "md_langevin")
+    def _md_call(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                 frames_xyz, frames_epot, frames_ekin):
+        """the checks the two dynamics seams share -> (grappa_mm_desc, grappa_md_opts)"""
+        _xyz3(xyz, who)
         dev = xyz.device
         d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
         N, Cc, B = d.N, d.C, d.B
-        o = _opts_struct(_lib.MdOpts, opts, "md_langevin")
+        o = _opts_struct(_lib.MdOpts, opts, who)
         F = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
         _tensors(dev, ((mass, "mass", _F32), (mol_key, "mol_key", _I64), (vel_in, "vel_in", _F32), (xyz_out, "xyz_out", _F32),
                        (vel_out, "vel_out", _F32), (epot, "epot", _F32), (ekin, "ekin", _F32), (steps, "steps", _I32), (status, "status", _I32),
@@ -299,10 +298,24 @@ class MMBackend:
                 or any(t.numel() != B * Cc for t in (epot, ekin, steps, status)) \
                 or (frames_xyz is not None and frames_xyz.numel() != F * N * Cc * 3) \
                 or any(t is not None and t.numel() != F * B * Cc for t in (frames_epot, frames_ekin)):
-            raise ValueError(f"md_langevin: expected mass (N,), mol_key (B,), vel_in / xyz_out / vel_out (N,C,3), epot / ekin / steps / status "
+            raise ValueError(f"{who}: expected mass (N,), mol_key (B,), vel_in / xyz_out / vel_out (N,C,3), epot / ekin / steps / status "
                              f"(B,C), frames_xyz ({F},N,C,3), frames_epot / frames_ekin ({F},B,C)")
         if xyz.numel() and (xyz_out.data_ptr() == xyz.data_ptr() or (vel_in is not None and vel_out.data_ptr() == vel_in.data_ptr())):
-            raise ValueError("md_langevin: xyz_out / vel_out must not be the start coordinates / velocities")
+            raise ValueError(f"{who}: xyz_out / vel_out must not be the start coordinates / velocities")
+        return d, o
+
+    def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
+        """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
+        (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
+        as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
+        atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
+        init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
+        n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
+        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
+        d, o = self._md_call("md_langevin", plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
+                             steps, status, frames_xyz, frames_epot, frames_ekin)
+        dev, N, Cc, B = xyz.device, d.N, d.C, d.B
         if atom_counts_host is not None:
             _atom_counts(atom_counts_host, N, B, "md_langevin", self.relax_max_atoms())
         nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
@@ -310,6 +323,52 @@ class MMBackend:
                                              mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
                                              ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),
                                              _ptr(frames_ekin)), "grappa_md_langevin_f32")
+
+    def md_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                 frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None) -> None:
+        """stepwise Langevin dynamics for molecules of any size (include/grappa_hip.h grappa_md_steps_*_f32): the loop, the arguments
+        and the outputs of `md_langevin`, but a molecule spans many workgroups, the state lives in device memory and a step is two
+        launches.  opts: the whole run's (n_steps its total).  atom_counts_host (required): atoms per molecule on the host; the
+        work-item table is the nonbonded plan built from it (reused from nb's cache of plans where nb keeps one).  steps_per_call:
+        steps enqueued per run call at most (rounded down to a multiple of save_every when frames are written); the result does not
+        depend on it.  There is NO device sync anywhere in it: init, the run calls and finish are only enqueued.  Status 3 does not
+        occur.  workspace: a uint8 tensor of at least `grappa_md_steps_workspace_bytes` to use instead of the backend's own."""
+        if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
+            raise ValueError(f"md_steps: steps_per_call must be an integer >= 1, got {steps_per_call}")
+        d, o = self._md_call("md_steps", plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
+                             steps, status, frames_xyz, frames_epot, frames_ekin)
+        dev, N, Cc, B = xyz.device, d.N, d.C, d.B
+        if atom_counts_host is None:
+            raise ValueError("md_steps: atom_counts_host is required (the work-item table is built from it)")
+        counts = _atom_counts(atom_counts_host, N, B, "md_steps")
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_steps")
+        if N == 0 or Cc == 0 or B == 0:
+            return
+        table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
+        need = int(self.lib.grappa_md_steps_workspace_bytes(N, Cc, B, n_blocks))
+        if workspace is None:
+            workspace = self._workspace(need, dev, "md_steps")
+        else:
+            _flat(workspace, "workspace", dev, torch.uint8)
+        st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
+        head = (st, C.byref(d), ndp, C.byref(o))
+        tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
+        _chk(self.lib.grappa_md_steps_init_f32(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), "grappa_md_steps_init_f32")
+        F = o.n_steps // o.save_every if o.save_every > 0 else 0
+        every = o.save_every if F > 0 and any(t is not None for t in (frames_xyz, frames_epot, frames_ekin)) else 0
+        chunk = int(steps_per_call)
+        if every > 0:
+            chunk = max(chunk // every, 1) * every
+        done = 0
+        while done < o.n_steps:
+            n = min(chunk, o.n_steps - done)
+            f0 = done // every if every > 0 else 0
+            fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size()
+                  for t in (frames_xyz, frames_epot, frames_ekin)]
+            _chk(self.lib.grappa_md_steps_run_f32(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), "grappa_md_steps_run_f32")
+            done += n
+        _chk(self.lib.grappa_md_steps_finish_f32(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(),
+                                                 steps.data_ptr(), status.data_ptr()), "grappa_md_steps_finish_f32")
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

@@ -1,5 +1,5 @@
 // Host-side checks of the descriptors of include/grappa_hip.h that several entry points take (csrc/mm_energy.hip, csrc/relax.hip,
-// csrc/relax_steps.hip, csrc/dynamics.hip): ONE definition of what a usable table is.  The heads of the entries differ (which sizes may be
+// csrc/relax_steps.hip, csrc/dynamics.hip, csrc/dynamics_steps.hip): ONE definition of what a usable table is.  The heads of the entries differ (which sizes may be
 // zero, which outputs are required) and stay with them.
 #pragma once
 #include <float.h>

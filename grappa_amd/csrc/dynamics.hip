@@ -13,7 +13,7 @@
 //            partials in sh.part (its readers of this step passed the reduction's barrier), barrier, seven threads add them and the kinetic partials
 //            in double in thread order, barrier.  The next step's partial gradients are written after that barrier and the one that
 //            follows its drift, so they cannot overwrite what the seven threads read.  Two barriers per frame with energies.
-//   noise  : Philox4x32-10 (csrc/md_philox.h), key = mol_key[b], counter = (atom in molecule, conformation, global step, purpose);
+//   noise  : Philox4x32-10 (csrc/md_philox.h, csrc/md_noise.h), key = mol_key[b], counter = (atom in molecule, conformation, global step, purpose);
 //            nothing is kept between steps or launches, so a run can be cut anywhere and continued with first_step advanced.
 // The loop runs n_steps (<= GRAPPA_STEP_CAP) iterations: the kernel always terminates.
 #include <float.h>
@@ -22,13 +22,10 @@
 
 #include "common.h"
 #include "desc_check.h"
-#include "md_philox.h"
+#include "md_noise.h"
 #include "rx_force.h"
 
 namespace {
-
-constexpr double MD_ACC = 418.4;               // 1 kcal/mol = 418.4 amu A^2 / ps^2
-constexpr double MD_KB = 0.0019872041;         // kcal/mol/K
 
 struct MdArgs {
     grappa_mm_desc mm;
@@ -47,25 +44,6 @@ struct MdArgs {
     int *steps, *status;
     float *frames_xyz, *frames_epot, *frames_ekin;
 };
-
-// sqrt(-2 ln u) for u = ((w >> 8) + 0.5) 2^-24.  Both logarithms get an argument that fp32 holds exactly: n + 0.5 has at most 24
-// bits below 2^23, and above it 1 - u = ((2^24 - 1 - n) + 0.5) 2^-24 has.  u > 0 always.
-__device__ inline float md_radius(uint32_t w) {
-    const uint32_t n = w >> 8;
-    const float l = n < (1u << 23) ? logf(((float)n + 0.5f) * 0x1p-24f) : log1pf(-(((float)(0xFFFFFFu - n) + 0.5f) * 0x1p-24f));
-    return sqrtf(-2.0f * l);
-}
-
-// the three normal deviates of (key, atom in molecule, conformation, step, purpose): Box-Muller on 24-bit uniforms of one Philox call
-__device__ inline V3 md_normal3(unsigned long long key, unsigned atom, unsigned conf, unsigned step, unsigned purpose) {
-    uint32_t w[4];
-    grappa_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), atom, conf, step, purpose, w);
-    float sn, cs;
-    sincospif((float)(w[1] >> 8) * 0x1p-23f, &sn, &cs);          // the angle 2 pi (w >> 8) 2^-24 in half turns: exact in fp32
-    const float cz = cospif((float)(w[3] >> 8) * 0x1p-23f);
-    const float r0 = md_radius(w[0]), r2 = md_radius(w[2]);
-    return {r0 * cs, r0 * sn, r2 * cz};
-}
 
 // g = grad E at the coordinates in LDS, into the owners' registers; true (in every thread) if a gradient is not finite.  Two barriers.
 __device__ __forceinline__ bool md_force(const MdArgs& a, RxShared& sh, const RxItem& w, V3 (&g)[RX_APT]) {
@@ -257,12 +235,7 @@ extern "C" int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, co
                                       float* ekin, int* steps, int* status, float* frames_xyz, float* frames_epot, float* frames_ekin) {
     if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0) return GRAPPA_ERR_ARG;
     if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    // (comparisons written so that a NaN is refused)
-    if (!(o->dt > 0.f && o->dt <= FLT_MAX) || !(o->temperature >= 0.f && o->temperature <= FLT_MAX) ||
-        !(o->friction >= 0.f && o->friction <= FLT_MAX) || !(o->init_temperature >= 0.f && o->init_temperature <= FLT_MAX))
-        return GRAPPA_ERR_ARG;
-    if (o->n_steps < 0 || o->n_steps > GRAPPA_STEP_CAP || o->save_every < 0) return GRAPPA_ERR_ARG;
-    if ((unsigned long long)o->first_step + (unsigned long long)o->n_steps >= (1ull << 32)) return GRAPPA_ERR_ARG;
+    if (!md_opts_ok(o)) return GRAPPA_ERR_ARG;
     if (mm->N == 0 || mm->C == 0 || mm->B == 0) return GRAPPA_OK;
     if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status)
         return GRAPPA_ERR_ARG;
@@ -272,12 +245,8 @@ extern "C" int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, co
     a.mm = *mm;
     a.has_nb = nb != nullptr;
     if (nb) a.nb = *nb; else a.nb = grappa_nb_desc{};
-    // the step's constants, formed in double and rounded once
-    const double dt = (double)o->dt, c1 = exp(-(double)o->friction * dt);
-    a.h2 = (float)(0.5 * dt), a.hk = (float)(0.5 * dt * MD_ACC);
-    a.c1 = (float)c1, a.c2 = (float)sqrt(1.0 - c1 * c1);
-    a.kt = (float)(MD_ACC * MD_KB * (double)o->temperature), a.kt0 = (float)(MD_ACC * MD_KB * (double)o->init_temperature);
-    a.thermostat = o->friction > 0.f;
+    const MdConsts k = md_consts(o);
+    a.h2 = k.h2, a.hk = k.hk, a.c1 = k.c1, a.c2 = k.c2, a.kt = k.kt, a.kt0 = k.kt0, a.thermostat = k.thermostat;
     a.n_steps = o->n_steps, a.save_every = o->save_every, a.first_step = o->first_step;
     a.mass = mass, a.mol_key = mol_key, a.vel_in = vel_in;
     a.xyz_out = xyz_out, a.vel_out = vel_out, a.epot = epot, a.ekin = ekin, a.steps = steps, a.status = status;

@@ -30,15 +30,12 @@
 #include "common.h"
 #include "desc_check.h"
 #include "fire.h"
-#include "mm_geom.h"
-#include "nb_pair.h"
-#include "nb_plan.h"
+#include "rs_force.h"
 
 namespace {
 
 constexpr int RS_DNT = 64;               // threads of a decide workgroup
 constexpr int RS_NW = NB_NT / GRAPPA_WAVE;
-constexpr int RS_RUNNING = -1;           // status in the workspace while an item runs
 
 struct RsState {                         // per (molecule, conformation): [B*C] each
     float *h, *al, *mix, *keep, *gmax;
@@ -74,41 +71,6 @@ RsWs rs_layout(char* base, int N, int C, int B, int n_blocks) {
     w.nbpart = (double*)take(8 * 2 * kc);
     w.total = off;
     return w;
-}
-
-// ------------------------------------------------------------------------------------------------ work items
-struct RsGeom {                          // what every per-block kernel needs of the batch
-    int N, C, B, n_blocks;
-    const int* atom_molptr;
-    const int* blk_ptr;                  // [B+1]
-    const int4* items;
-};
-
-struct RsItem {
-    int mol, i0, blk, c0, m0, m1, ni, nc;
-};
-
-// the workgroup's item, checked as nb_pairs_kernel checks it (a table made for another batch is walked away from, not followed)
-__device__ inline bool rs_item(const RsGeom& q, RsItem& r) {
-    const int4 it = q.items[blockIdx.x];
-    r.mol = it.x, r.i0 = it.y, r.blk = it.z, r.c0 = it.w;
-    if (r.mol < 0 || r.mol >= q.B || r.blk < 0 || r.blk >= q.n_blocks || r.c0 < 0 || r.c0 >= q.C) return false;
-    r.m0 = nb_clamp(q.atom_molptr[r.mol], q.N), r.m1 = nb_clamp(q.atom_molptr[r.mol + 1], q.N);
-    if (r.i0 < r.m0 || r.i0 >= r.m1) return false;
-    r.ni = r.m1 - r.i0 < NB_T ? r.m1 - r.i0 : NB_T;
-    int nch, ncb;
-    nb_chunks(r.ni, q.C, nch, ncb);
-    r.nc = q.C - r.c0 < ncb ? q.C - r.c0 : ncb;      // (ni * nc <= NB_NT and nc <= NB_CW by nb_chunks)
-    return true;
-}
-
-// which of the item's conformations still run -> run[0 .. nc); false if none does.  One barrier.
-__device__ inline bool rs_running(const RsItem& r, int C, const int* __restrict__ status, int* run) {
-    if ((int)threadIdx.x < r.nc) run[threadIdx.x] = status[(size_t)r.mol * C + r.c0 + threadIdx.x] == RS_RUNNING;
-    __syncthreads();
-    int any = 0;
-    for (int cc = 0; cc < r.nc; ++cc) any |= run[cc];
-    return any != 0;
 }
 
 // ------------------------------------------------------------------------------------------------ init
@@ -152,148 +114,42 @@ __global__ __launch_bounds__(256) void rs_init_kernel(RsInitArgs a) {
 
 // ------------------------------------------------------------------------------------------------ force
 struct RsForceArgs {
-    grappa_mm_desc mm;       // tables only: mm.xyz is not read
-    grappa_nb_desc nb;       // tables only
-    int has_nb;
-    RsGeom q;
-    const float *x, *v;
+    RsForceIn f;             // the force of csrc/rs_force.h
+    const float* v;
     float* g;
-    const int* status;
     double* part;
 };
 
-__device__ inline V3 rs_ld(const float* __restrict__ x, int atom, int N, int C, int c) {      // (an index outside the batch reads atom 0)
-    return ldv(x, (unsigned)atom < (unsigned)N ? atom : 0, C, c);
-}
-
-// slice s of the bonded gradient of atom i in conformation c
-__device__ inline V3 rs_bonded(const grappa_mm_desc& d, const float* __restrict__ x, int i, int s, int JS, int c) {
-    return bonded_gather(d, d.inc_ptr[i] + s, d.inc_ptr[i + 1], JS, [&](int atom) { return rs_ld(x, atom, d.N, d.C, c); });
-}
-
 __global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
-    __shared__ float4 xs[NB_TJ * NB_CW];      // j coordinates: [jj][conformation of the item]
-    __shared__ float4 ps[NB_TJ];              // j parameters: q, sigma / 2, sqrt(eps)
-    __shared__ float red[4][NB_NT];
-    __shared__ int run[NB_CW];
-    RsItem r;
-    if (!rs_item(a.q, r)) return;
-    const int C = a.q.C;
-    if (!rs_running(r, C, a.status, run)) return;      // every conformation of the item has stopped: nothing of it is touched
-    const int ni = r.ni, nc = r.nc, i0 = r.i0, c0 = r.c0, m0 = r.m0, m1 = r.m1;
-    const int NL = ni * nc;
-    const int JS = NB_NT / NL < NB_JS ? NB_NT / NL : NB_JS;
-    const int t = threadIdx.x, s = t / NL, l = t - s * NL;
-    const int cl = l / ni, il = l - cl * ni;      // (l < NL: cl < nc)
-    const int i = i0 + il, c = c0 + cl;
-    const bool active = s < JS && run[cl] != 0;
-
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-    if (active) {
-        const V3 p = rs_bonded(a.mm, a.x, i, s, JS, c);
-        gx = p.x, gy = p.y, gz = p.z;
-    }
-    if (a.has_nb) {
-        const grappa_nb_desc& d = a.nb;
-        float xi = 0.f, yi = 0.f, zi = 0.f, kq = 0.f, hs = 0.f, se = 0.f;
-        int ep = 0, ee = 0, nx = INT_MAX;
-        if (active) {
-            const float* p = a.x + ((size_t)i * C + c) * 3;
-            xi = p[0], yi = p[1], zi = p[2];
-            kq = NB_K * d.charge[i];
-            hs = 0.5f * d.sigma[i];
-            se = 4.0f * sqrtf(d.epsilon[i]);
-            ep = d.exc_ptr[i];
-            ee = d.exc_ptr[i + 1];
-            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
+    __shared__ RsShared sh;
+    rs_force(a.f, sh, [&](const RsItem& r, const RsLane& w, V3 gi) {
+        const int C = a.f.q.C, ni = r.ni;
+        float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
+        if (w.owner) {
+            const size_t off = ((size_t)w.i * C + w.c) * 3;
+            a.g[off] = gi.x, a.g[off + 1] = gi.y, a.g[off + 2] = gi.z;
+            const V3 vi = {a.v[off], a.v[off + 1], a.v[off + 2]};
+            const float g2 = dot(gi, gi), gn = sqrtf(g2);
+            pP = -dot(gi, vi);          // F = -g
+            pF = g2;
+            pv = dot(vi, vi);
+            pg = gn <= FLT_MAX ? gn : INFINITY;      // (written so that a NaN counts as non-finite)
         }
-        float elj = 0.f, ec = 0.f;      // (no pair energy is kept: dead code to the compiler)
-        for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
-            const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
-            __syncthreads();
-            for (int idx = t; idx < nj * nc; idx += NB_NT) {
-                const int jj = idx / nc, cc = idx - jj * nc;
-                if (run[cc]) {
-                    const float* p = a.x + ((size_t)(j0 + jj) * C + c0 + cc) * 3;
-                    xs[jj * NB_CW + cc] = make_float4(p[0], p[1], p[2], 0.f);
-                }
+        __syncthreads();
+        if (w.owner) sh.red[0][w.l] = pP, sh.red[1][w.l] = pF, sh.red[2][w.l] = pv, sh.red[3][w.l] = pg;
+        __syncthreads();
+        if (w.owner && w.il == 0) {      // the block's partials of one conformation: over its atoms in ascending order, in double
+            double sP = 0.0, sF = 0.0, sv = 0.0;
+            float mg = 0.f;
+            for (int k = 0; k < ni; ++k) {
+                const int o = w.cl * ni + k;
+                sP += (double)sh.red[0][o], sF += (double)sh.red[1][o], sv += (double)sh.red[2][o];
+                mg = fmaxf(mg, sh.red[3][o]);
             }
-            if (t < nj) ps[t] = make_float4(d.charge[j0 + t], 0.5f * d.sigma[j0 + t], sqrtf(d.epsilon[j0 + t]), 0.f);
-            __syncthreads();
-            const bool lookup = active && ((i >= j0 && i < j0 + nj) || nx < j0 + nj);
-            if (__builtin_amdgcn_ballot_w64(lookup) != 0) {
-                if (active) {
-                    for (int jj = s; jj < nj; jj += JS) {
-                        const int j = j0 + jj;
-                        const float4 p = ps[jj];
-                        float sij = hs + p.y, e4 = se * p.z, kqq = kq * p.x;
-                        bool skip = j == i;
-                        while (nx < j) {
-                            ++ep;
-                            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                        }
-                        if (nx == j) {
-                            const float q = d.exc_qq[ep], e = d.exc_eps[ep];
-                            sij = d.exc_sigma[ep];
-                            e4 = 4.0f * e;
-                            kqq = NB_K * q;
-                            skip = skip || (q == 0.f && e == 0.f);
-                            ++ep;
-                            nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                        }
-                        if (!skip) {
-                            const float4 x = xs[jj * NB_CW + cl];
-                            nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
-                        }
-                    }
-                    while (nx < j0 + nj) {      // partners that belong to other slices
-                        ++ep;
-                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                    }
-                }
-            } else if (active) {
-#pragma unroll 4
-                for (int jj = s; jj < nj; jj += JS) {
-                    const float4 p = ps[jj];
-                    const float4 x = xs[jj * NB_CW + cl];
-                    nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
-                }
-            }
+            double* o = a.part + ((size_t)r.blk * C + w.c) * 4;
+            o[0] = sP, o[1] = sF, o[2] = sv, o[3] = (double)mg;
         }
-    }
-    // the slices of one (atom, conformation), added in slice order
-    red[0][t] = gx, red[1][t] = gy, red[2][t] = gz;
-    __syncthreads();
-    const bool owner = active && s == 0;
-    float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
-    if (owner) {
-        for (int q = 1; q < JS; ++q) {
-            const int o = q * NL + l;
-            gx += red[0][o], gy += red[1][o], gz += red[2][o];
-        }
-        const size_t off = ((size_t)i * C + c) * 3;
-        a.g[off] = gx, a.g[off + 1] = gy, a.g[off + 2] = gz;
-        const V3 gi = {gx, gy, gz}, vi = {a.v[off], a.v[off + 1], a.v[off + 2]};
-        const float g2 = dot(gi, gi), gn = sqrtf(g2);
-        pP = -dot(gi, vi);          // F = -g
-        pF = g2;
-        pv = dot(vi, vi);
-        pg = gn <= FLT_MAX ? gn : INFINITY;      // (written so that a NaN counts as non-finite)
-    }
-    __syncthreads();
-    if (owner) red[0][l] = pP, red[1][l] = pF, red[2][l] = pv, red[3][l] = pg;
-    __syncthreads();
-    if (owner && il == 0) {      // the block's partials of one conformation: over its atoms in ascending order, in double
-        double sP = 0.0, sF = 0.0, sv = 0.0;
-        float mg = 0.f;
-        for (int k = 0; k < ni; ++k) {
-            const int o = cl * ni + k;
-            sP += (double)red[0][o], sF += (double)red[1][o], sv += (double)red[2][o];
-            mg = fmaxf(mg, red[3][o]);
-        }
-        double* o = a.part + ((size_t)r.blk * C + c) * 4;
-        o[0] = sP, o[1] = sF, o[2] = sv, o[3] = (double)mg;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ decide
@@ -482,24 +338,10 @@ int rs_check(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_re
     return GRAPPA_OK;
 }
 
-RsGeom rs_geom(const grappa_mm_desc* mm, const int* table_dev, int n_blocks) {
-    RsGeom q;
-    q.N = mm->N, q.C = mm->C, q.B = mm->B, q.n_blocks = n_blocks;
-    q.atom_molptr = mm->atom_molptr;
-    q.blk_ptr = table_dev + 4;
-    q.items = (const int4*)(table_dev + 4 + (((size_t)mm->B + 1 + 3) & ~(size_t)3));
-    return q;
-}
-
 void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const RsWs& w, int n_items) {
     RsForceArgs f;
-    f.mm = *mm;
-    f.mm.xyz = nullptr;
-    f.has_nb = nb != nullptr;
-    if (nb) f.nb = *nb; else f.nb = grappa_nb_desc{};
-    f.nb.xyz = nullptr;
-    f.q = q;
-    f.x = w.x, f.v = w.v, f.g = w.g, f.status = w.s.status, f.part = w.part;
+    f.f = rs_force_in(mm, nb, q, w.x, w.s.status);
+    f.v = w.v, f.g = w.g, f.part = w.part;
     GRAPPA_LAUNCH(rs_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
 }
 

@@ -1,8 +1,15 @@
 """Langevin molecular dynamics of molecules on the device under the full MM force field: the bonded terms Grappa predicts plus,
-optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all pairs.  One launch of csrc/dynamics.hip
-(`grappa_md_langevin_f32` through `HipBackend.md_langevin`) runs many steps of every (molecule, conformation): one workgroup each,
-coordinates in LDS, velocities in registers, no host round trip per step.  Molecules of up to `relax_max_atoms()` atoms; constraints,
-cutoffs, periodic boxes, PME and larger molecules are out of scope (OpenMM / GROMACS).
+optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all pairs.  Two paths run the same loop:
+  fused     one launch of csrc/dynamics.hip (`grappa_md_langevin_f32` through `HipBackend.md_langevin`) runs many steps of every
+            (molecule, conformation): one workgroup each, coordinates in LDS, velocities in registers, no host round trip per step.
+            Molecules of up to `relax_max_atoms()` atoms.  `stepwise=False` (the default) takes it and refuses a larger molecule.
+  stepwise  csrc/dynamics_steps.hip (`grappa_md_steps_*_f32` through `HipBackend.md_steps`): a molecule of ANY size -- a protein --
+            spread over many workgroups, the state in device memory, two launches per step, all of them only enqueued: the host never
+            waits for the device.  `stepwise=True` takes it for the whole batch, `stepwise="auto"` for a batch that holds a molecule
+            above the limit (a batch is never split between the two paths).
+The two paths add in different orders: the same trajectory within rounding, not the same bits.  Which of them is faster for a batch
+that both take has not been decided here (tools/md_steps_bench.py measures it).  Constraints, cutoffs, periodic boxes and PME are out
+of scope (OpenMM / GROMACS).
 
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
@@ -11,7 +18,8 @@ in the molecule, the conformation and the global step, so a molecule's trajector
 be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An item stops with a status:
     0  ran n_steps steps
     2  non-finite gradient (for example two non-excluded atoms on one point): stopped, the state is the one it held
-    3  the molecule has more than `relax_max_atoms()` atoms: not run (`simulate_graph` refuses such a batch before the launch)
+    3  the molecule has more than `relax_max_atoms()` atoms: not run by the fused path (`simulate_graph` refuses such a batch before
+       the launch); it cannot occur on the stepwise path
 The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
 has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
 """
@@ -23,7 +31,7 @@ import torch
 
 from .nonbonded import NonbondedBatch, NonbondedParameters
 from .parameters import Parameters
-from .relax import graph_coordinates, graph_force_field, graph_from_parameters
+from .relax import _stepwise_options, graph_coordinates, graph_force_field, graph_from_parameters
 
 MD_DEFAULTS = {"dt": 0.001, "temperature": 300.0, "friction": 1.0, "init_temperature": None, "n_steps": 1000, "save_every": 0}
 MAX_STEPS_PER_LAUNCH = 1000000      # the library's cap on n_steps of one call
@@ -74,7 +82,7 @@ def mol_keys(seed: int, B: int) -> np.ndarray:
 class MDResult:
     """xyz, velocities: the state after the last step; potential_energy, kinetic_energy (kcal/mol) and temperature
     (2 ekin / (3 n_moving kB), n_moving = the molecule's atoms of non-zero mass; no degrees of freedom are removed) there; steps;
-    status (see the module text); frames, frame_potential_energy, frame_kinetic_energy: one entry per `save_every` steps, or None.
+    status (see the module text; 3 cannot occur on the stepwise path); frames, frame_potential_energy, frame_kinetic_energy: one entry per `save_every` steps, or None.
     From `simulate_graph`: tensors on the graph's device, xyz / velocities (N, C, 3), frames (F, N, C, 3), frame energies (F, B, C),
     the others (B, C); a frame that was not reached (status 2) is NaN.  From `simulate`: numpy arrays of one molecule, xyz / velocities
     (n_confs, n_atoms, 3), frames (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames), the others (n_confs,)."""
@@ -113,7 +121,7 @@ def _host_keys(keys, seed, B):
 
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                   offset_torsion: bool = False, **opts) -> MDResult:
+                   offset_torsion: bool = False, stepwise=False, **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -121,9 +129,14 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     `mol_keys(seed, B)`).  first_step: the global index of the first step -- to continue a run, pass its xyz, its velocities and
     first_step + the steps it ran.  steps_per_launch: a run is cut into launches of at most this many steps (rounded down to a
     multiple of `save_every`); the result does not depend on it, it only keeps one launch short.  **opts: see MD_DEFAULTS.
-    No device sync; a molecule above `relax_max_atoms()` atoms is refused here, on the host.  The graph is not modified."""
+    stepwise=False (the default): the fused kernel; a molecule above `relax_max_atoms()` atoms is refused here, on the host.
+    stepwise=True: the whole batch through the stepwise path, which takes molecules of any size, two launches per step;
+    `steps_per_launch` then bounds the steps one run call enqueues.  stepwise="auto": the fused kernel if every molecule is within the
+    limit, else the whole batch stepwise -- a batch is never split between the two paths (one batch, one decomposition, one set of
+    bits).  No device sync on either path.  The graph is not modified."""
     from .backend import get_backend
     o = md_options(**opts)
+    stepwise, _ = _stepwise_options(stepwise, 1)
     if isinstance(steps_per_launch, bool) or not isinstance(steps_per_launch, (int, np.integer)) or steps_per_launch < 1:
         raise ValueError(f"steps_per_launch must be an integer >= 1, got {steps_per_launch!r}")
     if isinstance(first_step, bool) or int(first_step) != first_step or first_step < 0 or int(first_step) + o["n_steps"] >= 2 ** 32:
@@ -132,8 +145,11 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     xyz, plan, counts = graph_coordinates(g, terms)
     dev = xyz.device
     limit = get_backend().relax_max_atoms()
-    if counts and max(counts) > limit:
-        raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics")
+    above = bool(counts) and max(counts) > limit
+    if above and stepwise is False:
+        raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
+                         f"(stepwise=True or stepwise='auto' runs molecules of any size)")
+    use_steps = stepwise is True or (stepwise == "auto" and above)
     ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     N, B, C = plan.N, plan.B, xyz.shape[1]
     m_host = _host_masses(masses, N)
@@ -159,20 +175,27 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if F:
         nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)      # noqa: E731
         frames, fe, fk = nan(F, N, C, 3), nan(F, B, C), nan(F, B, C)
-    bufs = [(torch.empty_like(xyz), torch.empty_like(xyz)) for _ in range(2 if n_steps > chunk else 1)]
+    # one call of a seam runs `seg` steps: a launch of the fused kernel, or init / run calls of at most `chunk` steps / finish of the
+    # stepwise path, whose options carry the library's cap on n_steps too; calls continue one another bit for bit
+    seg = chunk if not use_steps else (MAX_STEPS_PER_LAUNCH // every * every if every > 0 else MAX_STEPS_PER_LAUNCH)
+    bufs = [(torch.empty_like(xyz), torch.empty_like(xyz)) for _ in range(2 if n_steps > seg else 1)]
     epot, ekin = f32(B, C), f32(B, C)
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
     total = torch.zeros(B, C, dtype=torch.int32, device=dev)
     x_in, v_in, done, launch = xyz, vel, 0, 0
     while True:
-        n = min(chunk, n_steps - done)
+        n = min(seg, n_steps - done)
         f0, f1 = (done // every, (done + n) // every) if every > 0 else (0, 0)
         x_out, v_out = bufs[launch % len(bufs)]
         call = {"dt": o["dt"], "temperature": o["temperature"], "friction": o["friction"], "init_temperature": o["init_temperature"],
                 "n_steps": n, "save_every": every, "first_step": int(first_step) + done}
-        get_backend().md_langevin(plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin,
-                                  steps, status, frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
-                                  frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
+        args = (plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin, steps, status)
+        kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
+                  frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
+        if use_steps:
+            get_backend().md_steps(*args, steps_per_call=chunk, **kw)
+        else:
+            get_backend().md_langevin(*args, **kw)
         total += steps
         x_in, v_in, done, launch = x_out, v_out, done + n, launch + 1
         if done >= n_steps:
@@ -181,12 +204,14 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
 
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
-             seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, **opts) -> MDResult:
+             seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
-    (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  See `simulate_graph`."""
+    (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  stepwise: see `simulate_graph`
+    (the stepwise path takes a molecule of any size)."""
     md_options(**opts)
+    _stepwise_options(stepwise, 1)
     g = graph_from_parameters(parameters, xyz)
     n = g.num_nodes("n1")
     nb = None
@@ -203,7 +228,8 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
         if v.shape != np.asarray(xyz).shape:
             raise ValueError(f"velocities must have the shape of xyz {np.asarray(xyz).shape}, got {v.shape}")
         vel = torch.from_numpy(np.ascontiguousarray(v.transpose(1, 0, 2))).to(device)
-    r = simulate_graph(g.to(device), m_host, nb, velocities=vel, seed=seed, keys=keys, first_step=first_step, steps_per_launch=steps_per_launch, **opts)
+    r = simulate_graph(g.to(device), m_host, nb, velocities=vel, seed=seed, keys=keys, first_step=first_step, steps_per_launch=steps_per_launch,
+                       stepwise=stepwise, **opts)
     np64 = lambda t: t.cpu().numpy().astype(np.float64)      # noqa: E731
     confs = lambda t: np64(t).transpose(1, 0, 2)      # noqa: E731  (N, C, 3) -> (C, N, 3)
     has = r.frames is not None

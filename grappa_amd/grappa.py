@@ -64,11 +64,12 @@ class Grappa:
         from .relax import relax
         return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)
 
-    def simulate(self, molecule: Molecule, xyz, nonbonded=None, **kw):
+    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
-        the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  **kw: velocities, seed, keys,
-        first_step, steps_per_launch and the options of `MD_DEFAULTS` (see `grappa_amd.dynamics.simulate_graph`)"""
+        the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
+        (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules of any size.  **kw: velocities,
+        seed, keys, first_step, steps_per_launch and the options of `MD_DEFAULTS` (see `grappa_amd.dynamics.simulate_graph`)"""
         from .dynamics import simulate
         masses = [constants.ATOMIC_MASSES[int(z)] for z in molecule.atomic_numbers]
-        return simulate(self.predict(molecule), xyz, masses, nonbonded, device=self.device, **kw)
+        return simulate(self.predict(molecule), xyz, masses, nonbonded, device=self.device, stepwise=stepwise, **kw)

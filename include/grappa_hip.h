@@ -626,8 +626,8 @@ int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const 
  * and an item's bits depend neither on its place in the batch nor on its neighbours.
  * GRAPPA_ERR_ARG, nothing written: a NULL required pointer or a negative size; nb disagreeing with mm in N, C or B; B * C >= 2^31; dt not
  * positive and finite; temperature, friction or init_temperature negative or not finite; n_steps < 0 or > 1,000,000; save_every < 0;
- * first_step + n_steps >= 2^32.  N == 0, C == 0 or B == 0: returns 0 without a launch.  Constraints, cutoffs, periodic boxes and
- * molecules above the limit are not supported.
+ * first_step + n_steps >= 2^32.  N == 0, C == 0 or B == 0: returns 0 without a launch.  Constraints, cutoffs and periodic boxes are
+ * not supported; molecules above the limit go through grappa_md_steps_*_f32 below.
  * grappa_md_philox: the generator itself on the host (no device, no launch).  grappa_md_noise_f32: one small launch that writes
  * out[N,C,3] = z(step, purpose) of every (atom, conformation) exactly as grappa_md_langevin_f32 draws it (atom_molptr[B+1] and
  * mol_key[B] are device memory; N * C < 2^31). */
@@ -646,6 +646,65 @@ int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, const grappa_
 void grappa_md_philox(unsigned long long key, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned out[4]);
 int grappa_md_noise_f32(void* stream, const unsigned long long* mol_key, const int* atom_molptr, int N, int C, int B, unsigned step,
                         unsigned purpose, float* out /*[N,C,3]*/);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same dynamics for molecules of ANY size, stepwise (additions to ABI 11): the loop, the units, the frozen-atom rule, the random
+ * stream, the options and the outputs are, word for word, those of grappa_md_langevin_f32 above, but a molecule spans many workgroups,
+ * the integrator's state lives in a caller-owned workspace and a step is a fixed sequence of TWO launches, whatever the shape.  The
+ * decomposition is grappa_nonbonded_plan's, exactly as grappa_relax_steps_*_f32 use it: the caller passes that table (device memory,
+ * 16-byte aligned) with n_items and n_blocks to all three calls, also when nb == NULL; a table made for another batch is walked away
+ * from, not followed.  opts is the run's: opts->n_steps its total number of steps, opts->save_every its frame period, opts->first_step
+ * the global index of its first step; pass the same opts to all three calls.
+ *   init   : x = mm->xyz; v = vel_in with frozen atoms zeroed, or, if vel_in == NULL, the draw at init_temperature (purpose 1 at
+ *            first_step); every (molecule, conformation) with atoms is running, steps = 0; g = grad E(x) with the blocks' flags of a
+ *            non-finite gradient and kinetic partials at it.  2 launches.
+ *   run    : enqueues the steps step0 .. step0 + n_steps - 1 of the run (the noise of step k is z(first_step + step0 + k, purpose 0)), 2
+ *            launches each and nothing else: no sync, no allocation, safe to capture.  The caller advances step0.
+ *            move  (a thread per (atom, conformation); every workgroup of a molecule ORs the flags of all the molecule's blocks and
+ *                  leaves a flagged conformation untouched, otherwise v -= (dt/2) ACC w g; x += (dt/2) v; the thermostat; x += (dt/2) v
+ *                  on its atoms of positive mass.  The workgroup of the molecule's first block writes the item's status and steps.)
+ *            force (g at the new x in ONE launch: the bonded gather and the Lennard-Jones / Coulomb pair loop of the stepwise
+ *                  minimiser, slices added in slice order; then per atom the closing kick v -= (dt/2) ACC w g and the non-finite test, per
+ *                  (block, conformation) the flag and sum m v^2 over the block's atoms in ascending order in double, and on a frame step
+ *                  the frame's coordinates.  It leaves an item alone whose status, written by the move launch before it, is final.)
+ *            Frames: this call's frame pointers address the frames step0 / save_every .. (each NULL or the slice for this call's
+ *            frames, in the layouts of grappa_md_langevin_f32); step0 must be a multiple of save_every when one is given.  Only on a
+ *            frame step, and only if frames_epot or frames_ekin is given, the energy launches are added: without frames a call adds
+ *            exactly 2 n_steps launches.
+ *   finish : takes the stop decision once more (the gradient that closed the last step), then writes xyz_out, vel_out, epot, ekin, steps
+ *            and status as grappa_md_langevin_f32 defines them: steps = the steps completed, status 0 or 2; status 3 does not occur.
+ * Energies.  epot and frames_epot come from the kernels of grappa_mm_energy_fwd_f32 and grappa_nonbonded_fwd_planned_f32 at the
+ * coordinates held: the six terms those entry points give there, added in double in term order -- the arrangement and the bits of
+ * grappa_relax_steps_finish_f32's energy.  ekin and frames_ekin are 0.5 / ACC times the blocks' partials, added in ascending block
+ * order in double.  frames_*[f] are the bits xyz_out, epot and ekin of a run that ended at that step would have.
+ * Stopping.  A non-finite gradient (the test of grappa_relax_fire_f32) stops an item with status 2, the x and v it held and steps =
+ * the steps completed, the one that found it included; a frame that fell on that step has been written, no later one is; steps
+ * enqueued after an item stopped do not touch it.
+ * Hazards.  Workgroups of one molecule exchange data only across launch boundaries, every word has one writer per launch, and no
+ * workgroup reads in a launch what a sibling writes in it: move reads the flags and writes status, force reads status and writes the
+ * flags.  No cooperative launch, no flag that is waited on, no atomics.
+ * Bits.  Same input, same bits.  A molecule's bits depend on its key and its own input, not on its place in the batch nor on its
+ * neighbours, and not on how the steps are dealt out to run calls.  They differ from grappa_md_langevin_f32's, which adds in another
+ * order.  A run of a + b steps equals a run of a steps (a a multiple of save_every) followed by init / run / finish of b steps from
+ * its outputs with first_step + a.  n_steps == 0 (init, finish): the input back bit for bit (the velocities of frozen atoms zeroed)
+ * with epot and ekin at it.  A molecule without atoms writes nothing.
+ * GRAPPA_ERR_ARG, nothing launched and nothing written: the cases of grappa_md_langevin_f32 (a NULL required pointer -- mass and mol_key
+ * for init and run, the six outputs for finish --, bad options, nb disagreeing with mm) and of grappa_relax_steps_*_f32 (a NULL
+ * table_dev or ws, a table or workspace that is not 16-byte aligned, a negative n_items or n_blocks, n_blocks > N / GRAPPA_NB_IBLOCK + B;
+ * N * C * 3, n_blocks * C or B * C at or above 2^31); on run also n_steps < 1, step0 < 0, step0 + n_steps > opts->n_steps and a step0
+ * that is no multiple of save_every with a frame pointer given.  first_step + opts->n_steps must stay below 2^32.  ws_bytes below
+ * grappa_md_steps_workspace_bytes(N, C, B, n_blocks): GRAPPA_ERR_WORKSPACE, nothing launched.  N == 0, C == 0 or B == 0: returns 0
+ * without a launch.  The workspace holds about 36 N C + 40 B C + 28 n_blocks C bytes. */
+size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks);
+int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                             const float* mass /*[N]*/, const unsigned long long* mol_key /*[B]*/, const float* vel_in /*[N,C,3] or NULL*/,
+                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                            const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
+                            size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin);
+int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                               const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out,
+                               float* epot, float* ekin, int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

@@ -1,0 +1,177 @@
+"""Time the stepwise Langevin dynamics (csrc/dynamics_steps.hip through simulate_graph(stepwise=True)) with device events, after
+warm-up, in steps per second, against (a) the fused kernel (csrc/dynamics.hip) where it applies and (c) the same BAOAB step composed
+from the entry points that existed before either (tools/md_bench.py Composed: mm_gradient_fwd, the planned nonbonded kernel and an
+update in stock torch ops), at three workloads:
+
+  pool    256 molecules of the pool x 32 conformations (tools/relax_bench.py pool_batch): fused, stepwise and composed -- what
+          stepwise=True costs where it is not needed; also the coordinate difference between fused and stepwise after 50 steps
+          without thermostat (per item the farthest atom: median, 99th percentile, largest)
+  513     one synthetic chain of 513 atoms (tools/relax_steps_bench.py chain_graph), 1 conformation -- one atom above the fused limit:
+          stepwise and composed
+  50046   the 50,046-atom chain of tools/nonbonded_bench.py, 1 conformation: stepwise and composed
+
+No rate is fixed here: the tool reports stepwise against fused and composed of the same run.  Every stage that touches the GPU is a
+child process of its own under a time limit; the parent never initialises the GPU, stops at the first stage that fails and starts
+nothing after it; at most one GPU process runs at a time.
+
+    python tools/md_steps_bench.py [--out profiles/md_steps_bench.txt] [--steps 500] [--big-steps 20] [--composed-steps 50]
+"""
+import argparse
+import datetime
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from md_bench import OPTS, Composed, _batch, _timed      # noqa: E402
+
+WORKLOADS = ("pool", "mid", "big")
+SIDES = {"pool": ("fused", "stepwise", "composed", "agreement"), "mid": ("stepwise", "composed"), "big": ("stepwise", "composed")}
+STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w]]
+STAGE_LIMIT = 300      # seconds, every stage
+AGREEMENT_STEPS = 50
+CARBON = 12.011
+
+
+def _workload(args, which):
+    """-> (graph on the device, NonbondedBatch on the device, masses (N,) float32 on the host, conformations, steps of a timed run)"""
+    import numpy as np
+    if which == "pool":
+        g, nb, masses = _batch(args)
+        return g, nb, masses, args.confs, args.steps
+    from relax_steps_bench import chain_graph
+    from grappa_amd.nonbonded import NonbondedBatch
+    n = args.mid_atoms if which == "mid" else args.big_atoms
+    gh, nbp = chain_graph(n)
+    return gh.to("cuda"), NonbondedBatch([nbp]).to("cuda"), np.full(n, CARBON, dtype=np.float32), 1, args.steps if which == "mid" else args.big_steps
+
+
+def stage(args):
+    """one GPU stage in this (child) process -> a JSON line on stdout"""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("md_steps_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    from grappa_amd.dynamics import simulate_graph
+    be = get_backend()
+    if args.stage == "device":
+        prop = torch.cuda.get_device_properties(0)
+        print(json.dumps({"device": f"{prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, "
+                                    f"{prop.total_memory / 2 ** 30:.0f} GiB; library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}"}))
+        return
+    which, side = args.stage.split(":")
+    g, nb, masses, confs, steps = _workload(args, which)
+    counts = g.batch_num_nodes_host("n1")
+    out = {"molecules": len(counts), "atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max()), "confs": confs}
+    sim = lambda n, stepwise, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, stepwise=stepwise,      # noqa: E731
+                                                   **{**OPTS, **kw})
+    if side in ("fused", "stepwise"):
+        sw = side == "stepwise"
+        n0 = be.lib.grappa_launch_count(0)
+        r = sim(steps, sw)
+        torch.cuda.synchronize()
+        out["launches"], out["steps"] = int(be.lib.grappa_launch_count(0) - n0), steps
+        # (an item that meets a non-finite gradient stops early: the rate counts the steps that were run)
+        out["item_steps"], out["stopped"] = int(r.steps.sum()), int((r.status != 0).sum())
+        out["median_us"], out["min_us"] = _timed(lambda: sim(steps, sw), args.reps)
+    elif side == "composed":
+        c = Composed(be, g, nb, masses, OPTS["friction"])          # tables, clones and the nonbonded work-item list: outside the timed region
+        v0 = sim(0, True).velocities
+
+        def composed():
+            c.reset(v0)
+            for _ in range(args.composed_steps):
+                c.step()
+        n0 = be.lib.grappa_launch_count(0)
+        composed()
+        torch.cuda.synchronize()
+        out["launches"], out["steps"] = int(be.lib.grappa_launch_count(0) - n0), args.composed_steps
+        out["item_steps"], out["stopped"] = len(counts) * confs * args.composed_steps, 0
+        out["median_us"], out["min_us"] = _timed(composed, args.reps)
+    else:          # agreement without a thermostat (with one the two paths would still draw the same noise, but diverge faster)
+        v0 = sim(0, True, friction=0.0).velocities
+        a, b = (sim(AGREEMENT_STEPS, s, velocities=v0, friction=0.0) for s in (False, True))
+        atom_mol = torch.repeat_interleave(torch.arange(len(counts)), torch.as_tensor(counts, dtype=torch.long)).to(a.xyz.device)
+        both = (a.status == 0) & (b.status == 0)          # (B, C): items that ran all steps on both paths
+        d = torch.zeros_like(a.potential_energy).index_reduce_(0, atom_mol, (a.xyz - b.xyz).abs().amax(-1), "amax", include_self=True)[both]
+        # per item, the farthest atom.  The synthetic charges pull some items towards a singularity, where a trajectory amplifies
+        # rounding without bound: the largest value describes those items, the quantiles the batch
+        q = torch.quantile(d.double(), torch.tensor([0.5, 0.99], dtype=torch.float64, device=d.device))
+        out["items"], out["median_dx"], out["p99_dx"], out["max_dx"] = int(d.numel()), float(q[0]), float(q[1]), float(d.max())
+        out["above"] = int((d > 1e-3).sum())
+        out["steps"], out["differ"] = AGREEMENT_STEPS, int(((a.steps != b.steps) | (a.status != b.status)).sum())
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--mols", type=int, default=256)
+    ap.add_argument("--confs", type=int, default=32)
+    ap.add_argument("--mid-atoms", type=int, default=513)
+    ap.add_argument("--big-atoms", type=int, default=50046)
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--big-steps", type=int, default=20)
+    ap.add_argument("--steps-per-launch", type=int, default=10000)
+    ap.add_argument("--composed-steps", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--stage", default=None, choices=STAGES)
+    args = ap.parse_args()
+    if args.stage:
+        return stage(args)
+    lines = [f"# command: python {' '.join(sys.argv)}",
+             f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}"]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def run(name):
+        cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
+              [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
+                                                                      "composed_steps", "reps")]
+        p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout + p.stderr)
+            sys.exit(f"md_steps_bench: stage {name} ended with status {p.returncode}; nothing more is started")
+        return json.loads(p.stdout.strip().splitlines()[-1])
+
+    def report(what, r):
+        steps_s = r["steps"] / (r["median_us"] * 1e-6)
+        say(f"  {what:10s} {r['steps']:6d} steps {r['median_us'] / 1e3:10.2f} ms (min {r['min_us'] / 1e3:10.2f})  {steps_s:10.1f} steps/s  "
+            f"{r['item_steps'] / (r['median_us'] * 1e-6):10.3e} item steps/s  {r['launches']:6d} library launches"
+            + (f"  ({r['stopped']} items stopped early)" if r["stopped"] else ""))
+        return steps_s
+
+    say(f"# device: {run('device')['device']}")
+    say("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; steps/s = steps of the run / "
+        "run time, whatever the batch holds; this file is the tool's output, unedited")
+    for w in WORKLOADS:
+        rate, head = {}, None
+        for side in SIDES[w]:
+            r = run(f"{w}:{side}")
+            if head is None:
+                head = (f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms ({r['smallest']}..{r['largest']} per molecule), C = {r['confs']}, "
+                        f"bonded + nonbonded, dt {OPTS['dt']} ps, {OPTS['temperature']} K, friction {OPTS['friction']} / ps")
+                say(head)
+            if side == "agreement":
+                say(f"  after {r['steps']} steps without thermostat, per item the farthest atom |x_fused - x_stepwise| over the {r['items']} items that ran all "
+                    f"steps on both paths: median {r['median_dx']:.3e}, 99th percentile {r['p99_dx']:.3e}, largest {r['max_dx']:.3e} A; {r['above']} items "
+                    f"above 1e-3 A; {r['differ']} items differ in steps or status")
+            else:
+                rate[side] = report(side, r)
+        if "fused" in rate:
+            say(f"  stepwise / fused = {rate['stepwise'] / rate['fused']:.3f}x steps/s")
+        say(f"  stepwise / composed = {rate['stepwise'] / rate['composed']:.2f}x steps/s (the composed loop also issues its torch ops: not counted as library launches)")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
