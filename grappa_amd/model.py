@@ -541,11 +541,19 @@ class WriteParameters(nn.Module):
     def _writers_largest_first(self):
         return [self.proper_writer, self.angle_writer, self.improper_writer, self.bond_writer]
 
-    def forward(self, g):
+    def forward(self, g, heads_done=None):
         h = g.nodes["n1"].data["h"]
         writers = self._writers_largest_first()
         # every head reads an alias of h of its own, so that its gradient of h arrives alone at the node that adds the four
-        aliases = ops.SplitHeadsFn.apply(h, len(writers)) if (torch.is_grad_enabled() and h.requires_grad) else (h,) * len(writers)
+        if torch.is_grad_enabled() and h.requires_grad:
+            aliases = ops.SplitHeadsFn.apply(h, len(writers))
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            # h takes no gradient (a frozen GNN) but the heads train: the node that ends their backward passes is still needed
+            # (heads_done: the model's on_heads_backward_done, which a hook on h cannot deliver here)
+            token = torch.zeros(0, dtype=h.dtype, device=h.device, requires_grad=True)
+            aliases = ops.JoinHeadsFn.apply(h, token, len(writers), (lambda: self._streams or ()) if h.is_cuda else None, heads_done)
+        else:
+            aliases = (h,) * len(writers)
         try:
             if self._use_merged(g, h):
                 return self._forward_merged(g, writers, aliases)
@@ -686,9 +694,12 @@ class GrappaModel(nn.Module):
         if hasattr(be, "set_tail_launches") and getattr(be, "gnn_tails", False):
             be.set_tail_launches(not (self.parameter_writer.head_streams > 1 and plan.device.type == "cuda"))
         h = g.nodes["n1"].data["h"]
-        if self.on_heads_backward_done is not None and h.requires_grad:
+        cb = self.on_heads_backward_done
+        if cb is None:
+            return self.parameter_writer(g)
+        if h.requires_grad:
             # fires when the gradient of the atom embedding is complete = every writer head has finished its backward pass
-            cb = self.on_heads_backward_done
             h.register_hook(lambda grad: (cb(), None)[1])
-        g = self.parameter_writer(g)
-        return g
+            return self.parameter_writer(g)
+        # an embedding that takes no gradient (a frozen GNN) has no such hook: the node that joins the heads calls back instead (ops.JoinHeadsFn)
+        return self.parameter_writer(g, heads_done=cb)

@@ -302,6 +302,17 @@ def _drop_bwd(be, dy, drop_p, seed, w):
     return dz, be.act_dropout_bwd(dy, None, drop_p, seed, dz)
 
 
+def _first_pass(ctx) -> None:
+    """the block functions release what they keep on `ctx` (activations, the backend's records of them) as their backward pass goes, so
+    that a step's peak memory falls with the pass; a second pass over a graph kept with retain_graph=True would find nothing (an
+    attention block would even take its missing feed-forward part for self_interaction=False and return a wrong sum).  Said here, at the
+    first such node, instead"""
+    if getattr(ctx, "_grappa_ran", False):
+        raise RuntimeError("grappa_amd: a second backward pass over the same graph (retain_graph=True) is not supported: the blocks release "
+                           "their saved activations during the first one; run the forward pass again (gradients accumulate across passes)")
+    ctx._grappa_ran = True
+
+
 # ------------------------------------------------------------------------------------------------
 class LinearFn(Function):
     """y = drop(act(x W^T + b))   (pre_dense / post_dense)."""
@@ -372,6 +383,7 @@ class AttBlockFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _first_pass(ctx)
         be = get_backend()
         h, mean1, rstd1, h1, ft, m, alpha, ln_w, ln_b, w_fc, w_r, b_r, ln2_w, ln2_b, w1, b1, w2, b2 = ctx.saved_tensors
         heads, drop_p, seed1, seed2 = ctx.cfg
@@ -469,6 +481,13 @@ class ConvBlockFn(Function):
         return (dh,) + (None,) * 13
 
 
+def _heads_done(be) -> None:
+    """every writer head has finished its backward pass (SplitHeadsFn / JoinHeadsFn, on the caller's stream)"""
+    if getattr(be, "gnn_tails", False):
+        be.set_tail_launches(True)               # the GNN's backward pass has the chip to itself (model.GrappaModel.forward switches back)
+    _wgrads_aside(be, all_streams=True)          # every head is done: what they left queued runs beside the GNN's backward pass
+
+
 class SplitHeadsFn(Function):
     """h -> one alias of the atom embedding per writer head.  The four heads read the same h (reference models/interaction_parameters.py:
     125-135) and, with GRAPPA_HEAD_STREAMS > 1, run forward and backward on HIP streams of their own.  Each head's backward pass delivers
@@ -484,9 +503,7 @@ class SplitHeadsFn(Function):
     @staticmethod
     def backward(ctx, *gs):
         be = get_backend()
-        if getattr(be, "gnn_tails", False):
-            be.set_tail_launches(True)               # the GNN's backward pass has the chip to itself (model.GrappaModel.forward switches back)
-        _wgrads_aside(be, all_streams=True)          # every head is done: what they left queued runs beside the GNN's backward pass
+        _heads_done(be)
         gs = [_c(g) for g in gs if g is not None]
         if not gs:
             return None, None
@@ -496,6 +513,36 @@ class SplitHeadsFn(Function):
             be.add(acc.reshape(-1), g.reshape(-1), out.reshape(-1))
             acc = out
         return acc, None
+
+
+class JoinHeadsFn(Function):
+    """SplitHeadsFn for an atom embedding that takes NO gradient (a frozen GNN under trainable heads): without it nothing runs behind
+    the heads' backward passes -- no node joins their streams, nothing sends their queued weight gradients aside, nobody hears that
+    they are done.  `token` is an empty tensor that asks for a gradient, so that the aliases do and every head reports back here; the
+    node runs on the caller's stream, puts it behind the side streams the heads ran on (`lanes()`: their kernels write `p.grad`
+    themselves, so this is the only place where the caller's stream learns of them -- autograd's own joins order gradients it
+    carries, and it carries none for the parameters), does what SplitHeadsFn does besides adding, and calls `done` (the model's
+    `on_heads_backward_done`).  The heads' gradients of h are dropped."""
+
+    @staticmethod
+    def forward(ctx, h, token, n, lanes, done):
+        ctx.set_materialize_grads(False)
+        ctx.lanes, ctx.done = lanes, done
+        return tuple(h.view_as(h) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        be = get_backend()
+        side = ctx.lanes() if ctx.lanes is not None else ()
+        if side:
+            cur = torch.cuda.current_stream(side[0].device)
+            for s in side:
+                if s != cur:
+                    cur.wait_stream(s)
+        _heads_done(be)
+        if ctx.done is not None:
+            ctx.done()
+        return None, None, None, None, None
 
 
 def _attention(be, qkv, s, T, nheads, like, infer, row_idx=None):
@@ -607,6 +654,7 @@ class TransformerLayerFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _first_pass(ctx)
         be = get_backend()
         x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2 = ctx.saved_tensors
         s, T, nheads, drop_p, seed1, seed2 = ctx.cfg
@@ -722,6 +770,7 @@ class ProjFirstLayerFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _first_pass(ctx)
         be = get_backend()
         idx_tab = None
         if getattr(ctx, "fused_gather", False) or getattr(ctx, "indexed", False):
@@ -816,6 +865,7 @@ class SymmetriserFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
+        _first_pass(ctx)
         be = get_backend()
         s, T, perms, n_layers, xshape, xdtype = ctx.cfg
         nret = 5 + 6 * n_layers
@@ -1153,6 +1203,7 @@ class MultiTransformerLayerFn(Function):
 
     @staticmethod
     def backward(ctx, *douts):
+        _first_pass(ctx)
         be = get_backend()
         n, cfgs = ctx.n, ctx.cfgs
         sv = ctx.saved_tensors
@@ -1227,6 +1278,7 @@ class MultiSymmetriserFn(Function):
 
     @staticmethod
     def backward(ctx, *douts):
+        _first_pass(ctx)
         be = get_backend()
         cfgs, n = ctx.cfgs, len(ctx.cfgs)
         g, sg = [_c(d) for d in douts], [None] * n
