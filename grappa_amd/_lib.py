@@ -7,8 +7,10 @@ path raises (tests on a CPU-only box use a test-only backend, see tests/).
 import ctypes as C
 import os
 
+from . import settings
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("GRAPPA_HIP_LIB") or os.path.join(_HERE, "libgrappa_hip.so")   # override: kernel A/B builds (tools/)
+LIB_PATH = settings.read("LIB_PATH") or os.path.join(_HERE, "libgrappa_hip.so")   # override: kernel A/B builds (tools/)
 
 ABI_VERSION = 11
 # grappa_gemm_desc.precision (include/grappa_hip.h GRAPPA_GEMM_*)

@@ -9,14 +9,13 @@ a test-only backend through `set_backend()` (tests/conftest.py) to exercise the 
 from __future__ import annotations
 
 import ctypes as C
-import os
 import weakref
 from collections import namedtuple
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, settings
 from ._marshal import GrappaHipError, _chk, _flat, _ptr  # noqa: F401
 from .backend_mm import MMBackend
 
@@ -72,7 +71,7 @@ def _f32_2d(t: torch.Tensor, name: str, dev, dtype=torch.float32) -> int:
     return max(t.shape[1], 1)
 
 
-DEFAULT_GEMM_PRECISION = "f32_f16x3"
+DEFAULT_GEMM_PRECISION = settings.BY_NAME["gemm_precision_name"].default
 _P_F32, _P_BF16, _P_F16X3 = (_lib.GEMM_PRECISIONS[k] for k in ("f32", "bf16", "f32_f16x3"))
 
 
@@ -164,82 +163,20 @@ class HipBackend(MMBackend):
         self.lib = _lib.load()
         self._ws = {}
         self._ws_need = {}             # (M, N, K) -> workspace bytes of a product of that shape (any tail / reduction setting)
-        # arithmetic of the dense products (include/grappa_hip.h GRAPPA_GEMM_*): "f32_f16x3" = fp32 operands, every row scaled by a
-        # power of two, split into two fp16 pieces (3 partial products on the fp16 matrix cores, fp32 accumulation); "f32_bf16x6" =
-        # three bf16 pieces, 6 products (the default until round 2).  Both are at least as close to the exact product as the native
-        # fp32 MFMA (tests/test_gpu_ops.py::test_gemm_precision_modes) at ~2.3x / ~1.7x its speed; "f32" = native fp32 MFMA
-        self.set_gemm_precision(os.environ.get("GRAPPA_GEMM_PRECISION", DEFAULT_GEMM_PRECISION))
-        # optional, OFF by default: a separate arithmetic for the products of the BACKWARD pass (dgrad / wgrad layouts), e.g.
-        # "bf16x3" (two bf16 pieces per operand, 2^-16 per product).  The forward pass -- parameters, energies, forces, loss -- is
-        # untouched by it; the reference itself trains with torch.set_float32_matmul_precision('medium') (training/trainrun.py:3).
-        self.set_gemm_precision_bwd(os.environ.get("GRAPPA_GEMM_PRECISION_BWD") or None)
+        # the switches, thresholds and arithmetic: plain attributes, named, explained and defaulted by the `backend` entries of settings.TABLE
+        for e in settings.of("backend"):
+            if e.setter:
+                getattr(self, e.setter)(settings.read(e.name))
+            else:
+                setattr(self, e.name, settings.read(e.name))
         self._prof = None      # list of (kernel family, algorithmic flops, algorithmic bytes, start event, end event) when profiling
-        # opt-in (GRAPPA_WEIGHT_PLANES=1): forward and dgrad products read the weight matrix from its bf16 planes (split once per
-        # optimiser step, both orientations) through LDS-DMA instead of re-splitting it in every workgroup of every launch
-        # (csrc/gemm_planes.hip gemm_wplanes_kernel).  Results are bit-identical to the default; measured speed is the same within
-        # +-3 %, which is why it is not the default.
-        # weight-gradient products of a backward pass are queued and launched together (grappa_gemm_f32_grouped): alone, each must
-        # cut its K (= tokens) 10 - 32 ways to fill the chip and pays for that many partial tiles per output tile
-        self.defer_wgrads = os.environ.get("GRAPPA_DEFER_WGRADS", "1") not in ("0", "")
         self._wq = {}                  # (autograd graph task id, stream handle) -> (stream, [_WgradItem kept alive until the launch])
-        self.defer_ln = os.environ.get("GRAPPA_DEFER_LN_REDUCTIONS", "1") not in ("0", "")      # tuning: 0 = reduce every LayerNorm's parameter gradients at once
         self._lnq = []                 # deferred LayerNorm parameter gradients (_LnItem)
         self._tasks = set()            # autograd graph task ids (backward passes) that have an end-of-pass callback registered and not yet run
-        self.wgrad_queue_bytes = int(float(os.environ.get("GRAPPA_WGRAD_QUEUE_GB", "12")) * 2 ** 30)
-        # inference (no gradient asked for): LayerNorm and the tuple attention write the A operand of the product behind them in the pair
-        # format and the product reads operands split once (csrc/gemm_pairs.hip) -- same bits as the fp32-operand product of the same K cuts
-        self.inference_pairs = os.environ.get("GRAPPA_INFERENCE_PAIRS", "1") not in ("0", "")
-        # training (round 4): the same producers write pairs ONLY, the dropout backward too, and the weight-gradient products read pairs
-        # (C ABI 8: token rows moved onto the tensor's scale inside the kernel) -- no fp32 copy of a normalised activation exists any more
-        self.training_pairs = os.environ.get("GRAPPA_TRAINING_PAIRS", "1") not in ("0", "")
-        # the same product of the four writer heads as ONE launch (gemm_group); GRAPPA_GROUP_LAUNCHES=0: one by one
-        self.group_launches = os.environ.get("GRAPPA_GROUP_LAUNCHES", "1") not in ("0", "")
-        # opt-in (GRAPPA_AMAX_PARTS=1): the row maxima of a product's output stay the per-segment partials its epilogue writes and the
-        # products that read the tensor combine them (C ABI 8 out_amax_parts / a_amax_nseg: 62 combine launches per C2 step gone).  Measured
-        # SLOWER: 37.4 against 35.9 ms per C2 step -- every workgroup of the consumer re-reads 16 partials per row in its prologue and
-        # epilogue, which costs more than the one small launch it replaces (profiles/r4_amax_parts_ab.txt) -- hence not the default
-        self.amax_parts = os.environ.get("GRAPPA_AMAX_PARTS", "0") not in ("0", "")
-        # the dropout backward of a layer's two dropouts written by the LayerNorm backward that produces their input (C ABI 9): 30 of the
-        # 40 act_dropout_bwd launches of a C2 step gone with the read of the gradient they made.  GRAPPA_FUSE_LN_DROP=0: launches of their own
-        self.fuse_ln_drop = os.environ.get("GRAPPA_FUSE_LN_DROP", "1") not in ("0", "")
-        self.pairs_min_rows = int(os.environ.get("GRAPPA_PAIRS_MIN_ROWS", "12288"))
-        # the dropout backward writing ITS rows (gradients) as pairs too: the input-gradient products behind gain (pair kernel), the weight-
-        # gradient products lose a little (a pair-format A operand costs 3 - 5 %, a pair-format B operand gains 9 %: tools/wgrad_pairs_bench.py)
-        # Measured on the C2 step: 34.9 ms with the forward producers' pairs only, 35.0 - 35.1 with the backward producers' too, 35.35 without
-        # pairs (profiles/r4_backward_pairs_ab.txt) -- hence off by default
-        self.backward_pairs = os.environ.get("GRAPPA_BACKWARD_PAIRS", "0") not in ("0", "")
-        # round 5: forward / input-gradient products whose A operand reaches them as fp32 rows (the second product of a feed-forward, every
-        # input-gradient product) read the WEIGHT from its pairs and split A's fragments in registers (csrc/gemm_wpairs_il.hip: the pinned
-        # pipeline, two workgroups per CU) where that beats the fp32-operand kernel: tables of at least `wpairs_min_rows` rows (on the C2 shapes
-        # 1.08 - 1.12 x at >= 28 k rows, slower than the 512-thread kernel on one round of tiles: profiles/r5_pairs_lab_v4.txt)
-        self.weight_pairs_min_rows = int(os.environ.get("GRAPPA_WPAIRS_MIN_ROWS", "24000"))
-        self._tails = None             # tail launches of the products: True / False, None = the library's default (grappa_gemm_desc.plan_tail)
         self._salt = None
         self._salt_ptr = None          # address of the dropout salt word while enabled (enable_dropout_salt)
-        self.plan_override = None      # tuning / tests: (cfg or -1, nsplit or 0, tail: -1 model, 0 never, 1 forced) applied to every product
-        self.splitk_reduce = 0         # tests: 0 library default, 1 a reduction launch, 2 inside the product's launch
-        self._tails_pinned = False
-        if os.environ.get("GRAPPA_PLAN_TAILS", "") != "":
-            self.pin_tail_launches(os.environ["GRAPPA_PLAN_TAILS"] != "0")
-        self.gnn_tails = os.environ.get("GRAPPA_GNN_TAILS", "0") not in ("0", "")      # tuning: tail launches for the GNN's products while the heads run without
-        self.wgrads_aside = os.environ.get("GRAPPA_WGRADS_ASIDE", "1") not in ("0", "")      # tuning: 0 = every queued product waits for the end of the pass
         self._side_streams = {}        # (device, caller's stream handle) -> the side stream of launch_wgrads_aside
         self._aside = []               # (side stream, items kept alive) since the last flush
-        self.weight_planes = os.environ.get("GRAPPA_WEIGHT_PLANES", "0") not in ("0", "")
-        # round 6: a transformer layer of a writer head as ONE kernel (csrc/writer_layer.hip, grappa_writer_head_fwd) where its shape allows:
-        # bf16 storage configuration, 512 features, 8 heads.  GRAPPA_FUSED_WRITER_LAYER=0: the unfused sequence (A/B, tests)
-        self.fused_writer_layer = os.environ.get("GRAPPA_FUSED_WRITER_LAYER", "1") not in ("0", "")
-        # ... and its backward pass: the input-gradient chain as one kernel (grappa_writer_head_bwd); 0: the unfused backward over the tensors
-        # the fused forward saved
-        self.fused_writer_layer_bwd = os.environ.get("GRAPPA_FUSED_WRITER_LAYER_BWD", "1") not in ("0", "")
-        # ... and the first layer of the angle / proper heads (ops.ProjFirstLayerFn: LayerNorm + q | k | v on (atom, position) rows) through the same
-        # kernels in their gather mode; 0: the unfused sequence behind the table-level products
-        self.fused_first_layer = os.environ.get("GRAPPA_FUSED_FIRST_LAYER", "1") not in ("0", "")
-        # the unfused fp32 first layer (ops.ProjFirstLayerFn) keeps q | k | v on the table: the attention kernels read a token's row through the
-        # table index (grappa_seqattn_*_idx_f32), and the token sums of the backward pass run with several rows in flight and write the row maxima
-        # of what they sum (grappa_tuple_gather_bwd2_f32).  GRAPPA_FIRST_LAYER_INDEXED=0: the token-level copy of q | k | v and the one-row-at-a-time
-        # sums -- the reference of the equality tests and the other leg of tools/first_layer_ab.sh
-        self.first_layer_indexed = os.environ.get("GRAPPA_FIRST_LAYER_INDEXED", "1") not in ("0", "")
         self._wplanes = {}     # (data_ptr, rows, cols, transposed) -> _PlanesEntry
         self._wpairs = {}      # (data_ptr, rows, cols, "pairs" | "pairsT") -> _PairsEntry
         self._wptable = None   # _PairsTable of the registered pairs
@@ -250,10 +187,6 @@ class HipBackend(MMBackend):
         # products receive it), anything missing is computed by one pass over the tensor
         self._wamax = {}       # (data_ptr, rows, cols, ld) -> _AmaxEntry
         self._wtable = None    # _AmaxTable of the batchable entries
-        # weight-gradient products reduce over the tokens, so each operand gets ONE scale (its largest magnitude): columns more than
-        # 2^16 below it lose relative precision gradually.  GRAPPA_WGRAD_COLUMN_MAXIMA=1 gives every column its own scale instead,
-        # at the price of one extra pass over both operands of every weight-gradient product (rigorous, ~15 % slower steps)
-        self.wgrad_column_maxima = os.environ.get("GRAPPA_WGRAD_COLUMN_MAXIMA", "0") not in ("0", "")
 
     def set_gemm_precision(self, name: str) -> None:
         if name not in _lib.GEMM_PRECISIONS:

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import settings
 from .constants import LEVEL_ARITY, TUPLE_LEVELS
 
 NTYPES = ["g", "n1", "n2", "n3", "n4", "n4_improper"]
@@ -64,7 +65,7 @@ class BatchPlan:
                     f"Encountered idxs up to {idx.max()} at the level g.nodes[{lvl}].data[\"idxs\"], "
                     f"but there are only {N} atom-level-nodes in the graph")
             idx_np.append(idx.astype(np.int32))
-        arrays = _plan_arrays_native(N, src, dst, idx_np) if _NATIVE_PLAN else None
+        arrays = _plan_arrays_native(N, src, dst, idx_np) if settings.read("host_plan") else None
         if arrays is None:
             arrays = _plan_arrays_numpy(N, src, dst, idx_np)
         self.N, self.E = N, E
@@ -98,11 +99,6 @@ class BatchPlan:
         self._idx_host = dict(zip(TUPLE_LEVELS, idx_np))      # (position_tables builds its tables from these on the host: no device sync)
 
 
-import os as _os
-
-_NATIVE_PLAN = _os.environ.get("GRAPPA_HOST_PLAN", "1") not in ("0", "")
-
-
 def _plan_arrays_native(N, src, dst, idx_np):
     """the index structures from libgrappa_host.so (include/grappa_host.h grappa_plan_build); None if the library is not built"""
     try:
@@ -121,7 +117,7 @@ def _plan_arrays_native(N, src, dst, idx_np):
 
 
 def _plan_arrays_numpy(N, src, dst, idx_np):
-    """the same in numpy (GRAPPA_HOST_PLAN=0, or the host library missing): the definition the native builder is tested against"""
+    """the same in numpy (GRAPPA_HOST_PLAN=numpy or 0, or the host library missing): the definition the native builder is tested against"""
     E = len(src)
     # CSR by destination, neighbours ascending by source id (deterministic)
     order = np.lexsort((src, dst))
@@ -191,7 +187,7 @@ def _position_tables(plan: "BatchPlan", lvl: str):
     s, N, T = LEVEL_ARITY[lvl], plan.N, plan.T[lvl]
     dev = plan.idx32[lvl].device
     host = getattr(plan, "_idx_host", None)
-    if host is not None and _os.environ.get("GRAPPA_HOST_PLAN", "native") != "numpy":
+    if host is not None and settings.read("host_plan"):
         # natively (libgrappa_host.so grappa_position_tables): 5 us instead of the 40 us of the numpy expressions below, per level
         try:
             from . import _hostlib

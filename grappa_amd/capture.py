@@ -25,6 +25,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from .backend import get_backend
+from .settings import launch_stamp
 
 
 def _pinned_by_graph(be):
@@ -356,15 +357,13 @@ class CapturedForward:
         return (self.be._wepoch, sum(p._version for p in ps))
 
     def _config_stamp(self):
-        """what is baked into the recorded launches besides the weights' values: the backend settings a product's plan and arithmetic
-        depend on, and WHICH tensors the parameters are (model.to(), load_state_dict(assign=True), p.data = ... replace them: the graph
+        """what is baked into the recorded launches besides the weights' values: every setting of the engine (settings.launch_stamp),
+        and WHICH tensors the parameters are (model.to(), load_state_dict(assign=True), p.data = ... replace them: the graph
         would go on reading the old storage, which its pinned caches keep alive)"""
-        be = self.be
         ps = self.__dict__.get("_params")
         if ps is None:
             ps = self._params = list(self.model.parameters())
-        return (be.gemm_precision_name, getattr(be, "gemm_precision_bwd", None), be.inference_pairs, be.training_pairs, be._tails, be.plan_override,
-                be.splitk_reduce, be.weight_pairs_min_rows, be.pairs_min_rows, getattr(be, "first_layer_indexed", None), tuple(p.data_ptr() for p in ps))
+        return launch_stamp(self.be, self.model) + (tuple(p.data_ptr() for p in ps),)
 
     def valid(self) -> bool:
         """the per-weight caches (maxima, pair splits) were filled OUTSIDE the graph: a graph captured before the weights changed must not be

@@ -562,7 +562,7 @@ __device__ inline void splitk_reduce_body(const GemmParams& p, int nblocks, int 
 // the grid drains whatever the order of arrival.  s_last: one word of LDS no wavefront uses any more.
 template <int NT>
 #ifndef SK_EXP
-#define SK_EXP 0          // timing experiments (tools/splitk_ab.sh): 1 = no fences (results not guaranteed), 2 = fences + ticket only (no sum: wrong results)
+#define SK_EXP 0          // timing experiments (-D builds): 1 = no fences (results not guaranteed), 2 = fences + ticket only (no sum: wrong results)
 #endif
 __device__ __forceinline__ void splitk_finish_tile(const GemmParams& p, int tile_local, volatile int* s_last) {
     if (SK_EXP != 1) __threadfence();

@@ -388,7 +388,7 @@ constexpr int pairs_cfg() { return 6; }                   // the 256 x 128 tile 
 // (tests/gemm_routes.py restates the rules below for a forced tile and a forced split -- the ladder of split factors, the rounding of
 //  k_per_split, the tail launch -- to name the kernel every case of the route sweep reaches: change the two together)
 Plan make_plan(int M, int N, int K, const PlanOpts& opt, bool vec = true, bool bf16x = false, bool planes = false, bool pairs = false, bool pairs_small = false,
-               int planes_tile = 0) {      // 256 / 128: the bf16 pinned-pipeline kernel's other tiles (GRAPPA_BF16_TILE)
+               int planes_tile = 0) {      // 256 / 128: the bf16 pinned-pipeline kernel's other tiles (experiments: the launch passes 0)
     Plan best;
     best.cfg = 1;
     best.nsplit = 1;

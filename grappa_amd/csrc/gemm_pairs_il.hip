@@ -246,7 +246,7 @@ int grappa_launch_gemm_pairs_il(hipStream_t st, GemmParams& p) {
 // (the caller checks): the bf16 storage configuration's forward / input-gradient products
 int grappa_launch_gemm_bf16_il(hipStream_t st, GemmParams& p) {
     static bool a0 = false, a1 = false, a2 = false;
-    if (p.bm == 128) return launch_il<128, 128>(st, p, gemm_bf16_il_small_kernel, a2);      // experiment (GRAPPA_BF16_TILE=128)
+    if (p.bm == 128) return launch_il<128, 128>(st, p, gemm_bf16_il_small_kernel, a2);      // experiment (make_plan planes_tile = 128)
     if (p.bn == 256) return launch_il<256, QBM>(st, p, gemm_bf16_il_kernel<256>, a1);
     return launch_il<128, QBM>(st, p, gemm_bf16_il_kernel<128>, a0);
 }

@@ -12,6 +12,8 @@ from typing import List, Sequence
 import torch
 import torch.distributed as dist
 
+from . import settings
+
 
 def init_process_group_from_env(backend: str = None) -> int:
     """torchrun-style env (RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT, LOCAL_RANK) -> world size."""
@@ -62,7 +64,7 @@ class BucketedGradReducer:
         # while MFMA wavefronts of another queue share the SIMD.  This library is compiled without packed fp32; librccl is not ours to
         # compile, and no run on two or more GPUs has compared overlapped and post-backward reductions bit for bit yet
         # (bench.py --gpus N reports `allreduce_bit_check` when both orders are run: see there).
-        self.overlap = (os.environ.get("GRAPPA_OVERLAP_ALLREDUCE", "0") not in ("0", "")) if overlap is None else bool(overlap)
+        self.overlap = settings.read("overlap") if overlap is None else bool(overlap)
         model.on_heads_backward_done = self._on_heads_done if self.overlap else None
 
     @staticmethod

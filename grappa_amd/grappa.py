@@ -1,9 +1,7 @@
 """`Grappa`: inference wrapper, `predict(Molecule) -> Parameters` (reference grappa.py:14-57)."""
-import os
-
 import torch
 
-from . import constants
+from . import constants, settings
 from .batch import check_disconnected_graphs
 from .model import GrappaModel
 from .molecule import Molecule
@@ -22,7 +20,7 @@ class Grappa:
         self.field_of_view = model.field_of_view
         # repeated shapes replay a recorded hipGraph instead of issuing ~450 launches from Python (grappa_amd/capture.py; GRAPPA_PREDICT_GRAPHS=0: never)
         self._graphs = None
-        if str(device).startswith("cuda") and os.environ.get("GRAPPA_PREDICT_GRAPHS", "1") not in ("0", ""):
+        if str(device).startswith("cuda") and settings.read("predict_graphs"):
             from .capture import ForwardCache
             self._graphs = ForwardCache(self.model, device)
 

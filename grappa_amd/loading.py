@@ -7,12 +7,12 @@ The reference's containers load unchanged -- the state-dict keys of `GrappaModel
     `Sequential(GrappaModel, Energy)` held as `.model`; the hyper-parameters sit in `grappa_config.yaml` of the run directory.
 Release files are looked up in a local directory first ($GRAPPA_MODELS_DIR, then `<repository>/models`); only when the file is not
 there is the release asset fetched (torch.hub), which needs a network."""
-import os
 from pathlib import Path
 from typing import Dict, Optional, Union
 
 import torch
 
+from . import settings
 from .deploy import model_from_dict
 
 RELEASE_URL = "https://github.com/hits-mbm-dev/grappa/releases/download"
@@ -28,7 +28,7 @@ RELEASES = {
 def models_dir(directory: Union[str, Path, None] = None) -> Path:
     if directory is not None:
         return Path(directory)
-    env = os.environ.get("GRAPPA_MODELS_DIR")
+    env = settings.read("models_dir")
     return Path(env) if env else Path(__file__).resolve().parent.parent / "models"
 
 
@@ -55,7 +55,7 @@ def _torch_load(path: Union[str, Path], trusted: Optional[bool] = None):
         return torch.load(path, map_location="cpu", weights_only=True)
     except Exception as e:       # noqa: BLE001
         if trusted is None:
-            trusted = os.environ.get("GRAPPA_TRUST_CHECKPOINTS", "0") not in ("0", "")
+            trusted = settings.read("trust_checkpoints")
         if not trusted:
             raise RuntimeError(f"{path} does not load with weights_only=True ({type(e).__name__}: {e}); if the file is yours, pass trusted=True "
                                "or set GRAPPA_TRUST_CHECKPOINTS=1 to unpickle it in full") from e

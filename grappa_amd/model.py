@@ -15,13 +15,12 @@ reference drops, learnable_statistics=True turns the same statistics into parame
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict, List, Optional, Union
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, settings
 from .backend import get_backend
 from .constants import CHARGE_ENCODING_DIM, DEFAULT_FEAT_DIMS, get_default_statistics
 
@@ -519,24 +518,10 @@ class WriteParameters(nn.Module):
                                                       cfg["gated_torsion"], cfg["wrong_symmetry"], cfg["torsion_cutoff"],
                                                       layer_norm=cfg.get("layer_norm", True), learnable_statistics=cfg.get("learnable_statistics", False))
 
-        # The four writers read the same atom embedding and write disjoint tuple levels: on the GPU each runs on its own HIP stream
-        # (largest first), so that the tail rounds and launch gaps of one head's kernels are filled by another head's; autograd replays
-        # every backward node on the stream of its forward, which gives the same overlap in the backward pass (-1.7 .. -2.0 ms of a 38 ms
-        # C2 step).  Default since round 3 (GRAPPA_HEAD_STREAMS=1 puts everything back on one stream).  History: a
-        # since-removed LayerNorm kernel computed deviating rows beside MFMA wavefronts of another queue; the trigger -- packed fp32
-        # instructions -- is compiled out of this library, and the gradients of h are joined by the library's own kernel
-        # (ops.SplitHeadsFn), so no torch arithmetic kernel runs on a side stream.
-        self.head_streams = int(os.environ.get("GRAPPA_HEAD_STREAMS", "4"))
+        # how the four heads share the GPU -- streams of their own, or layer-locked on one: the `writer` entries of settings.TABLE
+        for e in settings.of("writer"):
+            setattr(self, e.name, settings.read(e.name))
         self._streams = None
-        # round 4: the heads LAYER-LOCKED on one stream -- every product of a transformer / symmetriser layer is ONE grouped launch over the
-        # heads (ops.MultiTransformerLayerFn, backend.gemm_group): what the four streams approximated, without their launch count.
-        # GRAPPA_MERGED_HEADS: "0" (default) never, "1" always, "auto" = when a head's tokens would not fill the chip by themselves (fewer
-        # than `merged_heads_max_tokens` tokens in the largest head).  Measured (round 4): the layer-locked heads cut
-        # the launches per batch-32 step from 681 to 487 and the products' time on one queue by 6 %, but lose to four streams on the wall
-        # clock in every regime tried -- C2 37.2 against 35.8 ms, batch 32 eager 18.4 against 16.4 ms (the Python that builds the grouped
-        # calls costs more than the launches it saves), recorded 9.5 against 9.0 ms, recorded predict 3.5 against 3.0 ms -- hence opt-in
-        self.merged_heads = os.environ.get("GRAPPA_MERGED_HEADS", "0")
-        self.merged_heads_max_tokens = int(os.environ.get("GRAPPA_MERGED_HEADS_MAX_TOKENS", "40000"))
 
     def _writers_largest_first(self):
         return [self.proper_writer, self.angle_writer, self.improper_writer, self.bond_writer]

@@ -20,12 +20,12 @@ Reference blocks restated (file:line under /root/reference/src/grappa/):
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional, Sequence
 
 import torch
 from torch.autograd import Function
 
+from . import settings
 from .backend import get_backend
 from .constants import TUPLE_LEVELS
 
@@ -33,9 +33,7 @@ ELU = 1
 _SEED = {"base": 0x5DEECE66D, "counter": 0}
 
 
-# the first transformer layer of a writer on (atom, position) rows instead of tokens where those are far fewer (ProjFirstLayerFn);
-# GRAPPA_FIRST_LAYER_ROWS=0: always the token formulation (ProjGatherFn + TransformerLayerFn)
-FIRST_LAYER_ON_ATOM_ROWS = os.environ.get("GRAPPA_FIRST_LAYER_ROWS", "1") not in ("0", "")
+FIRST_LAYER_ON_ATOM_ROWS = settings.read("FIRST_LAYER_ON_ATOM_ROWS")      # (settings.TABLE says what it switches)
 
 
 def manual_seed(seed: int) -> None:
@@ -50,7 +48,7 @@ def next_seed() -> int:
 
 
 F32 = torch.float32
-_ACT = {"dtype": torch.bfloat16 if os.environ.get("GRAPPA_ACT_DTYPE", "f32") == "bf16" else None}
+_ACT = {"dtype": torch.bfloat16 if settings.read("act_dtype") == "bf16" else None}
 
 
 def set_activation_dtype(name) -> None:

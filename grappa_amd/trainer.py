@@ -25,6 +25,7 @@ from .evaluation import Evaluator, FastEvaluator
 from .loss import MolwiseLoss
 from .optim import FlatParams, FusedAdam
 from .schedule import TrainSchedule
+from .settings import launch_stamp
 
 
 def epoch_batches(names: List[str], batch_size: int, shuffle: bool = True, weights: Dict[str, float] = {}, balance_factor: float = 0.,
@@ -149,19 +150,17 @@ class Trainer:
     def _step_stamp(self) -> tuple:
         """what a recorded step has baked in besides the batch's shape: the loss weights the schedule moves, the optimiser's constants"""
         lf, o = self.loss_fn, self.opt
-        from . import ops
         from .backend import get_backend
-        be = get_backend()
-        pw = getattr(self.model, "parameter_writer", None)
-        # (ADVICE r5) ... and the backend settings baked into the recorded launches: arithmetic, operand formats, plan options, head streams,
-        # activation storage, fused layer switches -- a setting changed in the middle of a run means new graphs, not stale ones
-        backend_cfg = tuple(getattr(be, k, None) for k in ("gemm_precision_name", "gemm_precision_bwd_name", "inference_pairs", "training_pairs", "backward_pairs",
-                                                            "_tails", "plan_override", "splitk_reduce", "weight_pairs_min_rows", "pairs_min_rows",
-                                                            "fused_writer_layer", "fused_writer_layer_bwd", "first_layer_indexed", "group_launches", "wgrads_aside"))
+        # (ADVICE r5) ... and every setting of the engine baked into the recorded launches (settings.launch_stamp)
         return (float(lf.gradient_weight), float(lf.energy_weight), float(lf.param_weight), float(lf.tuplewise_weight), float(lf.proper_regularisation),
                 float(lf.improper_regularisation), tuple(sorted(lf.weights.items())), tuple(sorted(lf.param_weights_by_dataset.items())),
-                tuple(o.betas), float(o.eps), float(o.weight_decay), o.max_grad_norm, bool(self.model.training), backend_cfg,
-                str(ops.act_dtype()), getattr(pw, "head_streams", None), getattr(pw, "merged_heads", None))
+                tuple(o.betas), float(o.eps), float(o.weight_decay), o.max_grad_norm, bool(self.model.training)) + launch_stamp(get_backend(), self.model)
+
+    def _step_key(self, g) -> tuple:
+        """what a recorded step is stored under: the batch's shape, the stamp, and the loss's 1 / B_global (data parallelism, VERDICT r5 item
+        7a: a constant of the recorded step)"""
+        from .capture import train_signature
+        return (train_signature(g), self._step_stamp(), self.loss_fn.global_batch_size)
 
     def calibrate_buckets(self, batches: Sequence[np.ndarray]) -> ShapeBuckets:
         self._buckets = ShapeBuckets(self.train_set, batches, n_buckets=self.shape_buckets)
@@ -207,7 +206,7 @@ class Trainer:
         """prepared: the result of `_prepare(ids)` if the caller made it ahead; after_load: called once this batch is in the graph's inputs and before
         the graph is launched (pipelined epochs start the next batch's preparation there: launching a hipGraph of ~650 kernel nodes keeps the
         launching thread in the runtime for ~5 ms -- with the interpreter lock released)"""
-        from .capture import CapturedTrainStep, train_signature
+        from .capture import CapturedTrainStep
         ids = np.asarray(ids)
         if isinstance(prepared, str):
             prepared = self._prepare(ids)
@@ -224,11 +223,10 @@ class Trainer:
         g, names, ready, tot, caps = prepared
         main = torch.cuda.current_stream(self.train_set.device)
         main.wait_event(ready)
-        # data parallelism: the loss's 1 / B_global is a constant of the recorded step, so it is part of the key; the step is
-        # two graphs with the eager all-reduce between them (capture.CapturedTrainStep reducer=)
+        # data parallelism: the step is two graphs with the eager all-reduce between them (capture.CapturedTrainStep reducer=)
         self.loss_fn.global_batch_size = len(ids) if self.world > 1 else None
         reducer = self.reducer if self.world > 1 else None
-        key = (train_signature(g), self._step_stamp(), self.loss_fn.global_batch_size)
+        key = self._step_key(g)
         step = self._steps.pop(key, None) if key not in self._unrecordable else None
         if step is None and key not in self._unrecordable:
             if len(self._steps) >= self.max_recorded_steps:

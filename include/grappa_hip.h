@@ -9,8 +9,8 @@
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, nothing synchronises;
  *   - no allocation, no mutable global state, re-entrant per stream and per host thread: every option of a call travels in its arguments
  *     (ABI 10 removed the four process-wide setters: plan override, tail launches, split-K reduction, dropout salt); scratch comes from the
- *     caller (`ws`, `ws_bytes`; sizes from the *_workspace_bytes() queries).  Environment variables read once at first use (GRAPPA_PLAN_TAILS,
- *     GRAPPA_PAIRS_TILE ...) only choose DEFAULTS and never change afterwards;
+ *     caller (`ws`, `ws_bytes`; sizes from the *_workspace_bytes() queries).  The library reads no environment variable: what used to be one
+ *     is a constant of the build;
  *   - return 0 on success, a negative GRAPPA_ERR_* otherwise (never throws / aborts);
  *   - fp32 activations, int32 indices, row-major, leading dimensions in ELEMENTS.
  */
@@ -165,11 +165,11 @@ typedef struct grappa_gemm_desc {
     /* ---- ABI 10: the options that used to be process-wide setters, per call (all 0 / NULL = the library's defaults).
      * plan_cfg: tuning and tests -- force the tile configuration index plan_cfg - 1 (0: the plan's own choice); plan_nsplit: force the split-K
      * factor (0: own choice).  plan_tail: the "tail launch" (when the tile grid is 256 q + rem workgroups, the rem tiles run as a second launch
-     * with their K range cut): 0 = allowed unless the environment says GRAPPA_PLAN_TAILS=0, 1 = allowed, 2 = never (a caller that keeps several
+     * with their K range cut): 0 = the default (allowed), 1 = allowed, 2 = never (a caller that keeps several
      * streams busy: the partial last round then runs beside another stream's kernels), 3 = forced where possible (tests).  Results differ only
      * in the summation order of the tail tiles' K slices.
      * splitk_reduce: where a split-K product of the fp32-operand split kernels sums its K slices -- 0 = default (a launch of the reduction kernel
-     * behind the product, unless the environment says GRAPPA_SPLITK_IN_KERNEL=1), 1 = the reduction launch, 2 = inside the product's own launch
+     * behind the product), 1 = the reduction launch, 2 = inside the product's own launch
      * (the last workgroup of a tile to arrive adds the slabs in the fixed order 0, 1, ...).  Same bits either way.
      * drop_salt: one uint64 in DEVICE memory (or NULL: none) mixed into drop_seed when the kernel runs: seed + word * 0x9E3779B97F4A7C15.  A
      * train step captured in a hipGraph increments the word inside the graph: every replay draws fresh masks while forward and backward of

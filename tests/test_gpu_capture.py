@@ -216,6 +216,24 @@ def test_predict_cache_follows_backend_settings_and_replaced_parameters():
         assert ent not in gr._graphs.entries.values() and not gr._graphs.refresh_weights
     finally:
         be.inference_pairs = old
+    # ... and the settings that live outside the backend (the stamp is settings.launch_stamp: every owner's): the activations' storage type,
+    # the writer heads' streams
+    from grappa_amd import ops
+    pw = model.parameter_writer
+    streams = pw.head_streams
+    for flip, restore in ((lambda: ops.set_activation_dtype("bf16"), lambda: ops.set_activation_dtype("f32")),
+                          (lambda: setattr(pw, "head_streams", 1), lambda: setattr(pw, "head_streams", streams))):
+        for _ in range(3):
+            gr.predict(mol)
+        ent = next(iter(gr._graphs.entries.values()))
+        assert ent.valid()
+        try:
+            flip()
+            assert not ent.valid()
+            same(gr.predict(mol), eager())
+            assert ent not in gr._graphs.entries.values()
+        finally:
+            restore()
     for _ in range(3):
         gr.predict(mol)
     ent = next(iter(gr._graphs.entries.values()))
@@ -276,3 +294,38 @@ def test_split_recorded_step_equals_the_single_graph_step(preserve):
         be._salt.zero_()
     (la, pa, ca), (lb, pb, cb) = res
     assert la == lb and ca == cb and torch.equal(pa, pb)
+
+
+def test_a_backend_setting_flipped_between_two_steps_records_another_graph():
+    """the trainer files its recorded steps under `_step_key`, whose stamp holds every setting of the engine: the same batch shape after
+    `defer_wgrads` changed (a setting the hand-written stamp did not name) is recorded again, not replayed from the graph of the other setting"""
+    from test_host_train import TINY
+    from grappa_amd import GrappaModel, ops
+    from grappa_amd.backend import get_backend
+    from grappa_amd.datasets import graph_from_pool
+    from grappa_amd.device_dataset import DeviceDataset
+    from grappa_amd.trainer import Trainer
+    be = get_backend()
+    items = [(graph_from_pool(300 + i, n_confs=4, seed=2), "ds") for i in range(8)]
+    torch.manual_seed(0)
+    ops.manual_seed(5)
+    model = GrappaModel(**TINY).to("cuda")
+    tr = Trainer(model, DeviceDataset(items, device="cuda"), None, batch_size=8, conf_strategy=4, lr=1e-3, start_qm_epochs=0, warmup_steps=2,
+                 energy_weight=1.0, gradient_weight=0.8, param_weight=0.0, recorded=True, shape_buckets=1)
+    tr.model.train()
+    ids = np.arange(8)
+    tr.calibrate_buckets([ids])
+    tr.train_step(ids)             # (eagerly first: the model's forward chooses the products' tail launches, `be._tails`, itself a part of the stamp)
+    losses = [float(tr.train_step_recorded(ids)) for _ in range(2)]
+    assert tr.recorded_stats["graphs_recorded"] == 1 and tr.recorded_stats["replayed"] == 2 and len(tr._steps) == 1
+    first = next(iter(tr._steps))
+    old = be.defer_wgrads
+    try:
+        be.defer_wgrads = not old
+        losses.append(float(tr.train_step_recorded(ids)))
+        assert tr.recorded_stats["graphs_recorded"] == 2 and len(tr._steps) == 2 and first in tr._steps
+    finally:
+        be.defer_wgrads = old
+    losses.append(float(tr.train_step_recorded(ids)))                    # back under the first setting: its graph, replayed
+    assert tr.recorded_stats["graphs_recorded"] == 2 and tr.recorded_stats["replayed"] == 4 and tr.recorded_stats["eager"] == 0
+    assert list(tr._steps)[-1] == first and all(np.isfinite(losses))

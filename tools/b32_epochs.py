@@ -46,7 +46,6 @@ def main():
             from grappa_amd.trainer import epoch_batches
             batches = [b for b in epoch_batches(ds.names, 32, generator=torch.Generator().manual_seed(9)) if len(b) == 32][:20]
             ph = {"collate+pad": 0.0, "signature+lookup": 0.0, "load": 0.0, "replay": 0.0}
-            from grappa_amd.capture import train_signature
             for b in batches:
                 tot = ds.totals(b)
                 caps = tr._buckets.choose(tot)
@@ -56,8 +55,7 @@ def main():
                 g, names = ds.collate(b, 32, pad_to=caps)
                 g.plan().param_weight_rows = tr.loss_fn.param_weights_of(list(names), g.plan().B).to("cuda")
                 torch.cuda.synchronize(); ph["collate+pad"] += time.perf_counter() - t; t = time.perf_counter()
-                key = (train_signature(g), tr._step_stamp())
-                step = tr._steps.get(key)
+                step = tr._steps.get(tr._step_key(g))
                 torch.cuda.synchronize(); ph["signature+lookup"] += time.perf_counter() - t; t = time.perf_counter()
                 if step is None:
                     continue
@@ -81,7 +79,7 @@ def main():
                 hp["collate"] += time.perf_counter() - t; t = time.perf_counter()
                 g.plan().param_weight_rows = tr.loss_fn.param_weights_of(list(names), g.plan().B).pin_memory().to("cuda", non_blocking=True)
                 hp["pw"] += time.perf_counter() - t; t = time.perf_counter()
-                step = tr._steps.get((train_signature(g), tr._step_stamp()))
+                step = tr._steps.get(tr._step_key(g))
                 hp["signature"] += time.perf_counter() - t; t = time.perf_counter()
                 step.load(g)
                 hp["load"] += time.perf_counter() - t; t = time.perf_counter()

@@ -36,7 +36,7 @@ def record_shapes():
     model = model_from_config(get_default_model_config())
     model.load_state_dict(gu.keyed_state_dict(model))
     model = model.to(DEV).train()
-    n_mols = int(os.environ.get("GRAPPA_TUNE_MOLECULES", "0"))
+    n_mols = int(os.environ.get("TUNE_MOLECULES", "0"))
     if n_mols:                               # the first molecules of the workload only (e.g. 32: the reference's own batch size)
         from grappa_amd.datasets import build_batch_from_pool, workload_molecule_ids
         g = build_batch_from_pool(workload_molecule_ids(WORKLOAD, seed=0)[:n_mols], n_confs=32, seed=0).to(DEV)

@@ -1,7 +1,7 @@
-"""GPU: the pair-format GEMM under whatever GRAPPA_PAIRS_* environment the process was started with -- correctness of the multi-tile
+"""GPU: the pair-format GEMM of whatever library the process was started with (GRAPPA_HIP_LIB: a lab build) -- correctness of the multi-tile
 (persistent) walk against the fp32-operand fp16-split kernel (bit for bit) on shapes with several tiles per workgroup, every straight-line
 epilogue class, ragged edges and short K; then the timing of the C2 / C3 product shapes (pairs kernel only).
-    GRAPPA_PAIRS_PERSIST=0 python tools/pairs_lab.py --tag base ; GRAPPA_PAIRS_STAGGER=0 python tools/pairs_lab.py --tag persist ..."""
+    python tools/pairs_lab.py --tag base ; GRAPPA_HIP_LIB=<lab build> python tools/pairs_lab.py --tag lab ..."""
 import os
 import sys
 

@@ -1,7 +1,7 @@
 """GPU, diagnostic build only (csrc compiled with -DGQ_STAMP=1, see tools/pairs_stamps.sh): the timeline of the one-tile pair-format GEMM
 kernel, workgroup by workgroup -- where a tile's time goes (first slab's arrival, main loop, of which waiting for LDS-DMA + barrier, scale-back,
 epilogue) and how the grid's phases line up on the chip.
-    GRAPPA_HIP_LIB=build/variants/libgrappa_stamp.so python tools/pairs_stamps.py 83328 512 512"""
+    GRAPPA_HIP_LIB=build/variants/libgrappa_stamp.so python tools/pairs_stamps.py 83328x512x512 [--round3: read the stamps of the round-3 loop (gemm_pairs.hip), for shapes the plan sends there]"""
 import ctypes as C
 import os
 import sys
@@ -22,7 +22,7 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     lib = g.lib
-    il = not (os.environ.get("GRAPPA_PAIRS_IL", "1") == "0")
+    il = "--round3" not in sys.argv
     read_stamps = lib.grappa_debug_pairs_il_stamps if il else lib.grappa_debug_pairs_stamps
     read_stamps.argtypes = [C.c_void_p, C.c_int]
     for (M, N, K) in shapes:

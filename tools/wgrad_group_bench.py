@@ -1,5 +1,5 @@
 """GPU: the weight gradients of one transformer layer of the four writer heads (C2 token counts), launched one by one
-(grappa_gemm_f32, each with its own split-K + reduce) and as one group (grappa_gemm_f32_grouped); GRAPPA_GROUP_KPS forces the K chunk."""
+(grappa_gemm_f32, each with its own split-K + reduce) and as one group (grappa_gemm_f32_grouped)."""
 import os
 import sys
 import time
@@ -46,4 +46,4 @@ for defer in (False, True):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
-    print(f"{'grouped' if defer else 'single '} kps={os.environ.get('GRAPPA_GROUP_KPS', 'auto'):>6s}: {ms:7.3f} ms  {flops / ms / 1e9:6.1f} TF", flush=True)
+    print(f"{'grouped' if defer else 'single '}: {ms:7.3f} ms  {flops / ms / 1e9:6.1f} TF", flush=True)
