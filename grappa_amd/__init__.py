@@ -17,7 +17,9 @@ from .moldata import MolData
 from .trainer import Trainer
 from .relax import RelaxResult, relax, relax_graph
 from .dynamics import MDResult, simulate, simulate_graph
+from .constraints import ConstraintBatch, Constraints, hydrogen_constraints
 
 __all__ = ["MolBatch", "batch", "unbatch", "set_number_confs", "delete_dummy_confs", "Molecule", "Parameters", "GrappaModel",
            "Energy", "MolwiseLoss", "get_default_model_config", "model_from_config", "model_from_dict", "model_from_tag", "model_from_path", "Grappa", "FastEvaluator", "Evaluator", "eval_model",
-           "TrainSchedule", "DeviceDataset", "Dataset", "MolData", "Trainer", "RelaxResult", "relax", "relax_graph", "MDResult", "simulate", "simulate_graph"]
+           "TrainSchedule", "DeviceDataset", "Dataset", "MolData", "Trainer", "RelaxResult", "relax", "relax_graph", "MDResult", "simulate", "simulate_graph",
+           "Constraints", "ConstraintBatch", "hydrogen_constraints"]

@@ -98,6 +98,12 @@ class MdOpts(C.Structure):
                 ("n_steps", C.c_int), ("save_every", C.c_int), ("first_step", C.c_uint)]
 
 
+class MdCons(C.Structure):
+    """grappa_md_cons (additions to ABI 11): the X-H bond constraints of the fused Langevin dynamics, per call"""
+    _fields_ = [("cluster_molptr", C.c_void_p), ("cluster_atoms", C.c_void_p), ("cluster_d", C.c_void_p), ("K", C.c_int),
+                ("tolerance", C.c_float), ("constrain_start", C.c_int)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -230,6 +236,10 @@ SIGNATURES = {
     # Langevin dynamics under the full force field (additions to ABI 11)
     "grappa_md_langevin_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp]),
+    "grappa_md_cons_max_leaves": (_i, []),
+    "grappa_md_cons_max_iter": (_i, []),
+    "grappa_md_langevin_cons_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), C.POINTER(MdCons), _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_md_philox": (None, [_u64, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint * 4)]),
     "grappa_md_noise_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
     # the same dynamics for molecules of any size, stepwise (additions to ABI 11)
@@ -309,3 +319,9 @@ def md_philox(key: int, c0: int, c1: int, c2: int, c3: int):
     out = (C.c_uint * 4)()
     load().grappa_md_philox(key, c0, c1, c2, c3, C.byref(out))
     return tuple(int(w) for w in out)
+
+
+def md_cons_limits():
+    """(leaves per cluster at most, Newton updates at most) of the constrained dynamics of the loaded library"""
+    lib = load()
+    return int(lib.grappa_md_cons_max_leaves()), int(lib.grappa_md_cons_max_iter())

@@ -304,21 +304,45 @@ class MMBackend:
             raise ValueError(f"{who}: xyz_out / vel_out must not be the start coordinates / velocities")
         return d, o
 
+    @staticmethod
+    def _md_cons(constraints, B, dev, constrain_start):
+        """grappa_md_cons from a ConstraintBatch on `dev`"""
+        from .constraints import MAX_LEAVES, ConstraintBatch
+        if not isinstance(constraints, ConstraintBatch):
+            raise TypeError(f"md_langevin: constraints must be a ConstraintBatch or None, got {type(constraints).__name__}")
+        ptr, atoms, dd = constraints.cluster_molptr, constraints.cluster_atoms, constraints.cluster_d
+        _tensors(dev, ((ptr, "cluster_molptr", _I32), (atoms, "cluster_atoms", _I32), (dd, "cluster_d", _F32)))
+        K = int(atoms.shape[0])
+        if ptr.numel() != B + 1 or atoms.shape != (K, MAX_LEAVES + 1) or dd.shape != (K, MAX_LEAVES):
+            raise ValueError(f"md_langevin: expected cluster_molptr ({B + 1},), cluster_atoms (K,{MAX_LEAVES + 1}), cluster_d (K,{MAX_LEAVES})")
+        return _lib.MdCons(cluster_molptr=ptr.data_ptr(), cluster_atoms=atoms.data_ptr() if K else None, cluster_d=dd.data_ptr() if K else None,
+                           K=K, tolerance=float(constraints.tolerance), constrain_start=int(bool(constrain_start)))
+
     def md_langevin(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
-                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None) -> None:
+                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, constraints=None, constrain_start=True) -> None:
         """fused Langevin dynamics (include/grappa_hip.h grappa_md_langevin_f32): one launch runs opts["n_steps"] BAOAB steps of every
         (molecule, conformation) of the batch.  plan, xyz (N,C,3: the start), ks, eqs, n_per, offset_torsion, nb and atom_counts_host
         as for `relax_fire`.  opts: the seven fields of grappa_md_opts by name, all of them.  mass (N,) float32 in amu (0: a frozen
         atom); mol_key (B,) int64 holding the molecules' 64-bit keys bit for bit; vel_in (N,C,3) or None (velocities drawn at
         init_temperature).  -> xyz_out, vel_out (N,C,3), epot / ekin (B,C) float32, steps / status (B,C) int32 (status 0 = ran
         n_steps steps, 2 = non-finite gradient, 3 = above relax_max_atoms(), nothing else written); frames_xyz (F,N,C,3), frames_epot /
-        frames_ekin (F,B,C) with F = n_steps // save_every, or None."""
+        frames_ekin (F,B,C) with F = n_steps // save_every, or None.
+        constraints: a `grappa_amd.constraints.ConstraintBatch` on xyz's device (None: the call above, unchanged) -- the X-H bond
+        constraints of grappa_md_langevin_cons_f32, which adds status 4 = a position constraint did not converge and 5 = the item's
+        constraint tables are refused, nothing else written; constrain_start: True constrains the input first, False continues a run."""
         d, o = self._md_call("md_langevin", plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
                              steps, status, frames_xyz, frames_epot, frames_ekin)
         dev, N, Cc, B = xyz.device, d.N, d.C, d.B
         if atom_counts_host is not None:
             _atom_counts(atom_counts_host, N, B, "md_langevin", self.relax_max_atoms())
         nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
+        if constraints is not None:
+            cons = self._md_cons(constraints, B, dev, constrain_start)
+            _chk(self.lib.grappa_md_langevin_cons_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), C.byref(cons),
+                                                      mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(),
+                                                      epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz),
+                                                      _ptr(frames_epot), _ptr(frames_ekin)), "grappa_md_langevin_cons_f32")
+            return
         _chk(self.lib.grappa_md_langevin_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), mass.data_ptr(),
                                              mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
                                              ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),

@@ -8,8 +8,13 @@ optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all
             waits for the device.  `stepwise=True` takes it for the whole batch, `stepwise="auto"` for a batch that holds a molecule
             above the limit (a batch is never split between the two paths).
 The two paths add in different orders: the same trajectory within rounding, not the same bits.  Which of them is faster for a batch
-that both take has not been decided here (tools/md_steps_bench.py measures it).  Constraints, cutoffs, periodic boxes and PME are out
-of scope (OpenMM / GROMACS).
+that both take has not been decided here (tools/md_steps_bench.py measures it).  Cutoffs, periodic boxes and PME are out of scope
+(OpenMM / GROMACS).
+
+Constraints (`constraints=`, `grappa_amd.constraints`): X-H bonds held at fixed lengths, on the fused path only.  The loop is then
+g-BAOAB (Leimkuhler and Matthews, Proc. R. Soc. A 472, 20160138 (2016)) with one geodesic sub-step, csrc/dynamics_cons.hip
+(`grappa_md_langevin_cons_f32`): positions by a cluster-wise Newton iteration (M-SHAKE) of at most eight updates, velocities by a
+direct projection.  An atom draws the same noise with and without constraints.  Rigid water and the stepwise path are out of scope.
 
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
@@ -20,6 +25,10 @@ be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An i
     2  non-finite gradient (for example two non-excluded atoms on one point): stopped, the state is the one it held
     3  the molecule has more than `relax_max_atoms()` atoms: not run by the fused path (`simulate_graph` refuses such a batch before
        the launch); it cannot occur on the stepwise path
+    4  (with constraints) a position constraint did not converge within its eight updates: stopped, the state is the one it held;
+       `steps` counts the steps before the one that failed
+    5  (with constraints) the molecule's constraint tables were refused on the device (an index outside the molecule, an atom in two
+       clusters, a length that is not positive and finite, more than 256 clusters): nothing else was written for the item
 The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
 has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
 """
@@ -81,8 +90,9 @@ def mol_keys(seed: int, B: int) -> np.ndarray:
 @dataclass
 class MDResult:
     """xyz, velocities: the state after the last step; potential_energy, kinetic_energy (kcal/mol) and temperature
-    (2 ekin / (3 n_moving kB), n_moving = the molecule's atoms of non-zero mass; no degrees of freedom are removed) there; steps;
-    status (see the module text; 3 cannot occur on the stepwise path); frames, frame_potential_energy, frame_kinetic_energy: one entry per `save_every` steps, or None.
+    (2 ekin / (3 n_moving kB), n_moving = the molecule's atoms of non-zero mass; no degrees of freedom are removed -- except with
+    constraints: 2 ekin / ((3 n_moving - n_constraints) kB), n_constraints = the constrained bonds with a moving end, the divisor
+    floored at 1) there; steps; status (see the module text: 0, 2, 3, and with constraints 4 and 5; 3 cannot occur on the stepwise path); frames, frame_potential_energy, frame_kinetic_energy: one entry per `save_every` steps, or None.
     From `simulate_graph`: tensors on the graph's device, xyz / velocities (N, C, 3), frames (F, N, C, 3), frame energies (F, B, C),
     the others (B, C); a frame that was not reached (status 2) is NaN.  From `simulate`: numpy arrays of one molecule, xyz / velocities
     (n_confs, n_atoms, 3), frames (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames), the others (n_confs,)."""
@@ -121,7 +131,7 @@ def _host_keys(keys, seed, B):
 
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                   offset_torsion: bool = False, stepwise=False, **opts) -> MDResult:
+                   offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -133,7 +143,14 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     stepwise=True: the whole batch through the stepwise path, which takes molecules of any size, two launches per step;
     `steps_per_launch` then bounds the steps one run call enqueues.  stepwise="auto": the fused kernel if every molecule is within the
     limit, else the whole batch stepwise -- a batch is never split between the two paths (one batch, one decomposition, one set of
-    bits).  No device sync on either path.  The graph is not modified."""
+    bits).  No device sync on either path.  The graph is not modified.
+    constraints: a `grappa_amd.constraints.ConstraintBatch` holding the batch's molecules in order (None: unconstrained, the calls
+    made are exactly those without this argument).  The fused path only: with constraints stepwise=True is refused, and so is "auto"
+    for a batch above the size limit.  constrain_start=True: the start coordinates are brought to the constraint lengths and the start
+    velocities projected first; False continues a run (with its xyz, velocities and first_step) bit for bit.  The first launch of
+    a run gets the caller's constrain_start, later launches continue.  Statuses 4 and 5: see the module text; an item that ends with
+    either in one launch of a run keeps that launch's results: later launches add no steps and no frames (NaN) for it.  A moving centre
+    whose frozen leaves alone number four is refused (ValueError): they over-determine it."""
     from .backend import get_backend
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
@@ -150,6 +167,14 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
                          f"(stepwise=True or stepwise='auto' runs molecules of any size)")
     use_steps = stepwise is True or (stepwise == "auto" and above)
+    if constraints is not None:
+        from .constraints import ConstraintBatch
+        if not isinstance(constraints, ConstraintBatch):
+            raise TypeError(f"constraints must be a ConstraintBatch or None, got {type(constraints).__name__}")
+        if use_steps:
+            raise ValueError("simulate: constraints run on the fused path only (stepwise=False, or 'auto' with every molecule within the limit)")
+        if constraints.B != len(counts):
+            raise ValueError(f"the constraints describe {constraints.B} molecules, the batch has {len(counts)}")
     ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     N, B, C = plan.N, plan.B, xyz.shape[1]
     m_host = _host_masses(masses, N)
@@ -158,6 +183,12 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     key = torch.from_numpy(k_host.view(np.int64).copy()).to(dev)
     n_moving = torch.tensor([[max(int((m_host[p0:p0 + n] > 0).sum()), 1)] for p0, n in zip(np.cumsum([0] + counts[:-1]), counts)],
                             dtype=torch.float32).reshape(B, 1).to(dev)
+    if constraints is not None:
+        constraints.check_masses(m_host, counts)
+        dof = 3.0 * n_moving - torch.from_numpy(constraints.n_constraints_host(m_host, counts).astype(np.float32)).reshape(B, 1).to(dev)
+        constraints = constraints.to(dev)
+    else:
+        dof = 3.0 * n_moving
     vel = None
     if velocities is not None:
         if not isinstance(velocities, torch.Tensor) or velocities.shape != xyz.shape or velocities.device != dev:
@@ -183,6 +214,10 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
     total = torch.zeros(B, C, dtype=torch.int32, device=dev)
     x_in, v_in, done, launch = xyz, vel, 0, 0
+    held = None          # with constraints and more than one launch: the items that have ended, and what they ended with
+    if constraints is not None and n_steps > seg:
+        held = {"dead": torch.zeros(B, C, dtype=torch.bool, device=dev)}
+        atom_item = torch.repeat_interleave(torch.arange(B), torch.tensor(counts, dtype=torch.long)).to(dev)
     while True:
         n = min(seg, n_steps - done)
         f0, f1 = (done // every, (done + n) // every) if every > 0 else (0, 0)
@@ -194,24 +229,52 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
         if use_steps:
             get_backend().md_steps(*args, steps_per_call=chunk, **kw)
+        elif constraints is not None:
+            get_backend().md_langevin(*args, **kw, constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
         else:
             get_backend().md_langevin(*args, **kw)
-        total += steps
+        if held is None:
+            total += steps
+        else:
+            # A non-finite state (status 2) is found again by every later launch; a constraint failure (4) is not: the next launch
+            # would constrain the broken geometry afresh and run on.  So an item that has ended with 4 or 5 keeps the results of the
+            # launch that ended it, and nothing a later launch writes for it counts: no steps, NaN frames.  Tensor ops only, no sync.
+            alive = ~held["dead"]
+            atoms = alive[atom_item][:, :, None]
+            total += torch.where(alive, steps, torch.zeros_like(steps))
+            for name, new, mask in (("x", x_out, atoms), ("v", v_out, atoms), ("epot", epot, alive), ("ekin", ekin, alive), ("status", status, alive)):
+                held[name] = torch.where(mask, new, held[name]) if name in held else new.clone()
+            if f1 > f0 and launch > 0:
+                nanf = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+                frames[f0:f1] = torch.where(atoms[None], frames[f0:f1], nanf)
+                fe[f0:f1], fk[f0:f1] = torch.where(alive[None], fe[f0:f1], nanf), torch.where(alive[None], fk[f0:f1], nanf)
+            held["dead"] = held["dead"] | (alive & (status >= 4))
         x_in, v_in, done, launch = x_out, v_out, done + n, launch + 1
         if done >= n_steps:
             break
-    return MDResult(x_in, v_in, epot, ekin, 2.0 * ekin / (3.0 * KB * n_moving), total, status, frames, fe, fk)
+    if held is not None:
+        x_in, v_in, epot, ekin, status = held["x"], held["v"], held["epot"], held["ekin"], held["status"]
+    temperature = 2.0 * ekin / (3.0 * KB * n_moving) if constraints is None else 2.0 * ekin / (KB * dof.clamp_min(1.0))
+    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk)
 
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
-             seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, **opts) -> MDResult:
+             seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, constraints=None,
+             constrain_start: bool = True, **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
     (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  stepwise: see `simulate_graph`
-    (the stepwise path takes a molecule of any size)."""
+    (the stepwise path takes a molecule of any size).  constraints: the molecule's `grappa_amd.constraints.Constraints` in the order of
+    `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`."""
     md_options(**opts)
     _stepwise_options(stepwise, 1)
+    extra = {}
+    if constraints is not None:
+        from .constraints import ConstraintBatch, Constraints
+        if not isinstance(constraints, Constraints):
+            raise TypeError(f"constraints must be a Constraints or None, got {type(constraints).__name__}")
+        extra = dict(constraints=ConstraintBatch([constraints]), constrain_start=constrain_start)
     g = graph_from_parameters(parameters, xyz)
     n = g.num_nodes("n1")
     nb = None
@@ -229,7 +292,7 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
             raise ValueError(f"velocities must have the shape of xyz {np.asarray(xyz).shape}, got {v.shape}")
         vel = torch.from_numpy(np.ascontiguousarray(v.transpose(1, 0, 2))).to(device)
     r = simulate_graph(g.to(device), m_host, nb, velocities=vel, seed=seed, keys=keys, first_step=first_step, steps_per_launch=steps_per_launch,
-                       stepwise=stepwise, **opts)
+                       stepwise=stepwise, **extra, **opts)
     np64 = lambda t: t.cpu().numpy().astype(np.float64)      # noqa: E731
     confs = lambda t: np64(t).transpose(1, 0, 2)      # noqa: E731  (N, C, 3) -> (C, N, 3)
     has = r.frames is not None

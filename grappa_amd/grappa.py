@@ -62,12 +62,22 @@ class Grappa:
         from .relax import relax
         return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)
 
-    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, **kw):
+    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
         the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
         (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules of any size.  **kw: velocities,
-        seed, keys, first_step, steps_per_launch and the options of `MD_DEFAULTS` (see `grappa_amd.dynamics.simulate_graph`)"""
+        seed, keys, first_step, steps_per_launch, constrain_start and the options of `MD_DEFAULTS` (see
+        `grappa_amd.dynamics.simulate_graph`).  constraints: None, "h-bonds" (every X-H bond held at its predicted equilibrium length:
+        `grappa_amd.constraints.hydrogen_constraints`) or a `Constraints` in the molecule's atom order; the fused path only"""
         from .dynamics import simulate
         masses = [constants.ATOMIC_MASSES[int(z)] for z in molecule.atomic_numbers]
-        return simulate(self.predict(molecule), xyz, masses, nonbonded, device=self.device, stepwise=stepwise, **kw)
+        parameters = self.predict(molecule)
+        if isinstance(constraints, str):
+            if constraints != "h-bonds":
+                raise ValueError(f"constraints must be None, 'h-bonds' or a Constraints, got {constraints!r}")
+            from .constraints import hydrogen_constraints
+            constraints = hydrogen_constraints(parameters, molecule.atomic_numbers)
+        if constraints is None:
+            return simulate(parameters, xyz, masses, nonbonded, device=self.device, stepwise=stepwise, **kw)
+        return simulate(parameters, xyz, masses, nonbonded, device=self.device, stepwise=stepwise, constraints=constraints, **kw)

@@ -626,8 +626,8 @@ int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const 
  * and an item's bits depend neither on its place in the batch nor on its neighbours.
  * GRAPPA_ERR_ARG, nothing written: a NULL required pointer or a negative size; nb disagreeing with mm in N, C or B; B * C >= 2^31; dt not
  * positive and finite; temperature, friction or init_temperature negative or not finite; n_steps < 0 or > 1,000,000; save_every < 0;
- * first_step + n_steps >= 2^32.  N == 0, C == 0 or B == 0: returns 0 without a launch.  Constraints, cutoffs and periodic boxes are
- * not supported; molecules above the limit go through grappa_md_steps_*_f32 below.
+ * first_step + n_steps >= 2^32.  N == 0, C == 0 or B == 0: returns 0 without a launch.  Cutoffs and periodic boxes are
+ * not supported; X-H bond constraints are grappa_md_langevin_cons_f32's below; molecules above the limit go through grappa_md_steps_*_f32.
  * grappa_md_philox: the generator itself on the host (no device, no launch).  grappa_md_noise_f32: one small launch that writes
  * out[N,C,3] = z(step, purpose) of every (atom, conformation) exactly as grappa_md_langevin_f32 draws it (atom_molptr[B+1] and
  * mol_key[B] are device memory; N * C < 2^31). */
@@ -646,6 +646,66 @@ int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, const grappa_
 void grappa_md_philox(unsigned long long key, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned out[4]);
 int grappa_md_noise_f32(void* stream, const unsigned long long* mol_key, const int* atom_molptr, int N, int C, int B, unsigned step,
                         unsigned purpose, float* out /*[N,C,3]*/);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same dynamics with X-H bond constraints (additions to ABI 11): g-BAOAB (Leimkuhler and Matthews 2016) with one geodesic
+ * sub-step.  Everything that grappa_md_langevin_f32 states holds (units, frozen atoms, c1, c2, s_i, z and its counters -- the noise an
+ * atom draws does not depend on whether it is constrained --, the outputs, the frames, the size limit), except the loop.
+ * Constraints come as STAR CLUSTERS: a centre atom 0 and L leaves 1..L, 1 <= L <= GRAPPA_MD_CONS_MAX_LEAVES = 4, with one length d_k > 0
+ * per leaf (X-H, XH2, XH3, XH4).  Every atom belongs to at most one cluster, so a molecule has at most 256 clusters.  cluster_molptr[B+1]:
+ * the clusters of molecule b; cluster_atoms[K,5]: the centre, then the leaves, as atom indices WITHIN the molecule, -1 = no leaf;
+ * cluster_d[K,4] in Angstrom.  h2 = dt/2, hk = (dt/2) ACC.  A leaf with w_0 + w_k == 0 (both ends frozen) is treated as absent.
+ *   P(x, v), the velocity projection, direct:  r_k = x_k - x_0;  solve sum_l A_kl mu_l = r_k . (v_k - v_0) with
+ *       A_kl = w_0 (r_k . r_l) + delta_kl w_k (r_k . r_k);  v_k -= w_k mu_k r_k;  v_0 += w_0 sum_l mu_l r_l.
+ *   S(xref, x, v), the position constraint, cluster-wise Newton on the multipliers (M-SHAKE), on vectors relative to the centre:
+ *       rref_k = xref_k - xref_0;  rt_k = x_k - x_0;  lambda = 0;  repeat:
+ *           r_k = rt_k - w_k lambda_k rref_k - w_0 sum_l lambda_l rref_l;  sigma_k = r_k . r_k - d_k^2
+ *           converged when every |sigma_k| <= 2 tolerance d_k^2 (a sigma that is not finite: not converged)
+ *           else lambda -= J^-1 sigma with J_kl = -2 r_k . (delta_kl w_k rref_k + w_0 rref_l),
+ *       at most GRAPPA_MD_CONS_MAX_ITER = 8 updates.  Then x_0 += w_0 sum_l lambda_l rref_l;  x_k = x_0 (new) + r_k;
+ *       v_k -= w_k lambda_k rref_k / h2;  v_0 += w_0 sum_l lambda_l rref_l / h2 (a frozen atom is not touched).  Without convergence
+ *       the same updates are made with the last lambda, if it is finite, and the item's constraint-failure flag is set.
+ *   start:  if constrain_start: S(x, x, -) (the velocities are set afterwards);  v = vel_in or drawn;  P
+ *           else: x and vel_in are taken as they are (a continued run); drawn velocities are projected in either case
+ *           g = grad E(x)
+ *   repeat n_steps times:
+ *           g not finite or the flag set: stop
+ *           v -= hk w g;  P
+ *           xr = x;  x += h2 v;  S(xr, x, v);  P
+ *           if friction > 0: v = c1 v + c2 s z(t, purpose 0);  P
+ *           xr = x;  x += h2 v;  S(xr, x, v);  P
+ *           g = grad E(x);  v -= hk w g;  P
+ *           frame if due
+ * An atom in no cluster moves exactly as in grappa_md_langevin_f32.  The potential energy is unchanged: the constrained bonds' terms are
+ * still evaluated.  The flag is reduced with the non-finite-gradient flag at the next force evaluation, so the step that found either
+ * has been completed with it and its frame, if due, written.  status 4 = a position constraint did not converge (it wins over 2): the
+ * state is the one held after that step, and steps = the steps completed BEFORE it (0 when the start's S failed) -- the steps whose
+ * constraints held; status 2 counts as in grappa_md_langevin_f32.  status 5 = the item's tables are refused and NOTHING else is written
+ * for it: the tables are device memory, so the kernel checks, before it writes anything, that a cluster's indices lie in [0, n) and are
+ * distinct, that it has at least one leaf, that no atom is in two clusters, that every used d is finite and positive and that the
+ * molecule has at most 256 clusters.  NOT checked: a cluster that its frozen atoms over-determine (a moving centre with four frozen
+ * leaves: the projection's system is singular) is unsupported; its item ends with status 2 or 4.  grappa_amd's front ends refuse it.
+ * A run of a + b steps gives the bits of a run of a steps followed by one of b steps with constrain_start = 0, mm->xyz = xyz_out,
+ * vel_in = vel_out and first_step + a.  Same input, same bits; an item's bits depend neither on its place nor on its neighbours.
+ * GRAPPA_ERR_ARG: the cases of grappa_md_langevin_f32, plus K < 0, a NULL table with K > 0, and a tolerance that is not finite, below
+ * 2^-20 or above 2^-7.  cons == NULL or K == 0: the launch of grappa_md_langevin_f32 itself, hence its bits.  Constraints other than
+ * these stars (rigid water, SETTLE), and constraints on the stepwise path, are not supported. */
+#define GRAPPA_MD_CONS_MAX_LEAVES 4
+#define GRAPPA_MD_CONS_MAX_ITER 8
+typedef struct grappa_md_cons {
+    const int*   cluster_molptr;   /* [B+1] device: clusters of molecule b */
+    const int*   cluster_atoms;    /* [K,5] device: centre, leaves; atom index WITHIN the molecule; -1 = no leaf */
+    const float* cluster_d;        /* [K,4] device: A */
+    int   K;
+    float tolerance;               /* relative, on d: converged when |r^2 - d^2| <= 2 tol d^2 */
+    int   constrain_start;         /* 1: constrain the input first; 0: a continued run */
+} grappa_md_cons;
+int grappa_md_cons_max_leaves(void);   /* 4 */
+int grappa_md_cons_max_iter(void);     /* 8 */
+int grappa_md_langevin_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                                const grappa_md_cons* cons, const float* mass /*[N]*/, const unsigned long long* mol_key /*[B]*/,
+                                const float* vel_in /*[N,C,3] or NULL*/, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+                                int* status, float* frames_xyz, float* frames_epot, float* frames_ekin);
 
 /* ------------------------------------------------------------------------------------------------
  * The same dynamics for molecules of ANY size, stepwise (additions to ABI 11): the loop, the units, the frozen-atom rule, the random

@@ -9,6 +9,14 @@ process of its own under a time limit; the parent never initialises the GPU, sto
 after it.
 
     python tools/md_bench.py [--out profiles/md_bench.txt] [--steps 2000] [--composed-steps 50]
+
+--constraints times the constrained kernel (csrc/dynamics_cons.hip) next to the unconstrained one instead: the same batch with every
+X-H bond of the pool molecules held at its start length (`Constraints.from_bonds`), both kernels in one child process, the
+unconstrained one at 1 fs and the constrained one at 2 fs and at 1 fs, with the workload's charges and again with them quartered (the
+full charges pull atoms onto each other, which ends items early).  What constraints have to earn is a per-step cost below twice the
+unconstrained kernel's: then a picosecond at 2 fs costs less wall time than at 1 fs without them.
+
+    python tools/md_bench.py --constraints [--out profiles/md_cons_bench.txt] [--steps 2000]
 """
 import argparse
 import datetime
@@ -23,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 OPTS = dict(dt=0.001, temperature=300.0, friction=1.0, init_temperature=300.0)
 ACC, KB = 418.4, 0.0019872041
-STAGE_LIMIT = {"device": 300, "fused": 300, "composed": 300, "agreement": 300}      # seconds
+STAGE_LIMIT = {"device": 300, "fused": 300, "composed": 300, "agreement": 300, "cons": 300}      # seconds
 
 
 def _batch(args):
@@ -34,6 +42,18 @@ def _batch(args):
     g, nb = pool_batch(args.mols, args.confs)
     masses = np.concatenate([[ATOMIC_MASSES[int(z)] for z in pool_molecule(k % pool_size())[0]] for k in range(args.mols)]).astype(np.float32)
     return g, nb, masses
+
+
+def _constraints(args):
+    """every bond between a hydrogen and a heavy atom of the batch's molecules, at its length in the pool's geometry"""
+    import numpy as np
+    from grappa_amd.constraints import ConstraintBatch, Constraints
+    from grappa_amd.datasets import pool_molecule, pool_size
+    items = []
+    for k in range(args.mols):
+        z, bonds, xyz0 = pool_molecule(k % pool_size())
+        items.append(Constraints.from_bonds(bonds, z == 1, np.linalg.norm(xyz0[bonds[:, 0]] - xyz0[bonds[:, 1]], axis=-1)))
+    return ConstraintBatch(items)
 
 
 def _timed(fn, reps):
@@ -113,8 +133,24 @@ def stage(args):
     g, nb, masses = _batch(args)
     counts = g.batch_num_nodes_host("n1")
     out = {"atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max())}
-    fused = lambda n, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, **{**OPTS, **kw})      # noqa: E731
-    if args.stage == "fused":
+    def fused(n, constraints=None, **kw):
+        extra = {} if constraints is None else {"constraints": constraints}
+        return simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, **extra, **{**OPTS, **kw})
+
+    if args.stage == "cons":
+        cb = _constraints(args).to("cuda")
+        out["constraints"], out["clusters"] = int(sum(c.n_constraints for c in cb.items)), cb.K
+        # twice: with the workload's charges, which pull some atoms onto each other (items then stop early, and a workgroup that leaves
+        # early skews the time per step run), and with the charges quartered, where items are meant to survive
+        for tag, scale in (("", 1.0), ("_calm", 0.25)):
+            nb.charge.mul_(scale)
+            nb.exc_qq.mul_(scale * scale)
+            for name, kw in (("free_1fs", dict(dt=0.001)), ("cons_2fs", dict(dt=0.002, constraints=cb)), ("cons_1fs", dict(dt=0.001, constraints=cb))):
+                r = fused(args.steps, **kw)
+                med, low = _timed(lambda: fused(args.steps, **kw), args.reps)
+                out[name + tag] = {"item_steps": int(r.steps.sum()), "status": {int(k): int((r.status == k).sum()) for k in r.status.unique()},
+                                   "median_us": med, "min_us": low, "temperature": float(r.temperature[r.status == 0].mean())}
+    elif args.stage == "fused":
         n0 = be.lib.grappa_launch_count(0)
         r = fused(args.steps)
         out["launches"] = int(be.lib.grappa_launch_count(0) - n0)
@@ -153,6 +189,7 @@ def main():
     ap.add_argument("--steps-per-launch", type=int, default=10000)
     ap.add_argument("--composed-steps", type=int, default=50)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--constraints", action="store_true", help="time the constrained kernel next to the unconstrained one")
     ap.add_argument("--stage", default=None, choices=sorted(STAGE_LIMIT))
     args = ap.parse_args()
     if args.stage:
@@ -179,6 +216,28 @@ def main():
 
     lines.append(f"# device: {run('device')['device']}")
     lines.append("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; this file is the tool's output, unedited")
+    if args.constraints:
+        c = run("cons")
+        lines.append(f"pool: {args.mols} molecules, {c['atoms']} atoms ({c['smallest']}..{c['largest']} per molecule), C = {args.confs}, {items} items, "
+                     f"bonded + nonbonded, {OPTS['temperature']} K, friction {OPTS['friction']} / ps; {c['constraints']} X-H constraints in "
+                     f"{c['clusters']} clusters per conformation; the three runs in one process")
+        for tag, title in (("", "the workload's charges"), ("_calm", "charges x 0.25")):
+            per = {}
+            lines.append(f"-- {title}")
+            for name, what in (("free_1fs", "unconstrained, 1 fs"), ("cons_2fs", "constrained, 2 fs"), ("cons_1fs", "constrained, 1 fs")):
+                r = c[name + tag]
+                per[name] = r["median_us"] / max(r["item_steps"], 1)
+                lines.append(f"{what:20s} {args.steps:6d} steps {r['median_us'] / 1e3:10.2f} ms (min {r['min_us'] / 1e3:10.2f})  "
+                             f"{r['item_steps'] / (r['median_us'] * 1e-6):10.3e} item steps/s  {r['item_steps']} item steps run, items by status "
+                             f"{r['status']}, mean kinetic temperature of the status-0 items at the end {r['temperature']:.1f} K")
+            lines.append(f"time per item step, constrained 2 fs / unconstrained 1 fs = {per['cons_2fs'] / per['free_1fs']:.3f} (below 2: a picosecond "
+                         f"costs less wall time constrained); constrained 1 fs / unconstrained 1 fs = {per['cons_1fs'] / per['free_1fs']:.3f}")
+        print("\n".join(lines), flush=True)
+        out = args.out or os.path.join(ROOT, "profiles", "md_cons_bench.txt")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        return
     f = run("fused")
     lines.append(f"pool: {args.mols} molecules, {f['atoms']} atoms ({f['smallest']}..{f['largest']} per molecule), C = {args.confs}, {items} items, "
                  f"bonded + nonbonded, dt {OPTS['dt']} ps, {OPTS['temperature']} K, friction {OPTS['friction']} / ps")
