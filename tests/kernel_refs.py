@@ -292,6 +292,296 @@ def loss_ef_ref64(atom_counts, energy, energy_ref, is_dummy, grad, grad_ref, wE,
     return loss.detach(), gE, gG, se
 
 
+def loss_param_ref64(mol_ptrs, params, refs, fac, reg, pw, inv_B):
+    """the parameter MSE + torsion regularisers of one batch, per molecule, in float64 (training/loss.py:80-132 as grappa_amd.loss hands
+    it to the kernel: six levels n2_k, n2_eq, n3_k, n3_eq, n4_k, n4_improper_k; fac and reg per level, pw per molecule or None):
+        den_b  = sum over the levels with a table and a reference of tuples_b * width          (NaN references still count)
+        mse_b  = pw_b * sum_l fac_l^2 sum (p - ref)^2 over the non-NaN references / den_b      (ref zero-padded / cut to p's width;
+                 0 where pw_b == 0 or den_b == 0 -- the documented deviation: the reference loop gives NaN for den_b == 0)
+        reg_b  = sum_l reg_l * mean over the molecule's elements of p^2                        (0 for a molecule without tuples on l)
+    -> (mse + reg per molecule (B,), [d(inv_B * sum_b loss_b)/d params[l] by autograd, None where params[l] is None])"""
+    B = int(mol_ptrs[0].numel()) - 1
+    ps = [None if p is None else p.detach().cpu().double().clone().requires_grad_(True) for p in params]
+    cnts = [mp.detach().cpu().long()[1:] - mp.detach().cpu().long()[:-1] for mp in mol_ptrs]
+    tables = []
+    for l in range(6):
+        if ps[l] is None:
+            tables.append(None)
+            continue
+        T = int(cnts[l].sum())
+        tables.append(ps[l].reshape(T, -1) if T else ps[l].reshape(0, ps[l].shape[1] if ps[l].dim() == 2 else 1))
+    den = torch.zeros(B, dtype=torch.float64)
+    for l in range(6):
+        if tables[l] is not None and refs[l] is not None:
+            den = den + cnts[l].double() * tables[l].shape[1]
+    pwv = torch.zeros(B, dtype=torch.float64) if pw is None else pw.detach().cpu().double()
+    num, regsum = torch.zeros(B, dtype=torch.float64), torch.zeros(B, dtype=torch.float64)
+    for l in range(6):
+        pv = tables[l]
+        if pv is None or pv.shape[0] == 0:
+            continue
+        T, w = pv.shape
+        seg = torch.repeat_interleave(torch.arange(B), cnts[l])
+        if refs[l] is not None:
+            r = _ref_table64(refs[l], T, w)
+            ok = ~torch.isnan(r)
+            diff = torch.where(ok, pv - torch.where(ok, r, torch.zeros_like(r)), torch.zeros_like(pv))
+            num = num + torch.zeros(B, dtype=torch.float64).index_add(0, seg, float(fac[l]) ** 2 * (diff * diff).sum(1))
+        if reg[l] > 0:
+            n_el = cnts[l].double() * w
+            sq = torch.zeros(B, dtype=torch.float64).index_add(0, seg, (pv * pv).sum(1))
+            regsum = regsum + torch.where(n_el > 0, float(reg[l]) * sq / n_el.clamp(min=1), torch.zeros_like(sq))
+    loss = regsum + torch.where((pwv != 0) & (den > 0), pwv * num / den.clamp(min=1), torch.zeros_like(num))
+    live = [p for p in ps if p is not None]
+    if loss.requires_grad:
+        g = list(torch.autograd.grad(inv_B * loss.sum(), live, allow_unused=True))
+    else:
+        g = [None] * len(live)
+    g = [torch.zeros_like(p) if gi is None else gi for gi, p in zip(g, live)]
+    it = iter(g)
+    return loss.detach(), [None if p is None else next(it).reshape(p.shape) for p in ps]
+
+
+def _ref_table64(ref, T, w):
+    """a reference table (T, rw) as float64 (T, w): zero-padded where narrower than the parameters, cut where wider"""
+    r = ref.detach().cpu().double().reshape(T, -1)
+    if r.shape[1] < w:
+        r = torch.cat([r, torch.zeros(T, w - r.shape[1], dtype=torch.float64)], 1)
+    return r[:, :w]
+
+
+def loss_param_grad_scales(mol_ptrs, params, refs, fac, reg, pw, inv_B):
+    """per element of params[l], the magnitude its gradient's gate is relative to (float64):
+    inv_B * (pw * fac^2 * 2 * (|p| + |ref|) / den  [where the element has an MSE term]  +  reg / n_el * 2 * |p|  [a regulariser term]);
+    0 for an element with neither: its gradient must be exactly 0.  -> list of tensors shaped like params[l] (None where that is None)"""
+    B = int(mol_ptrs[0].numel()) - 1
+    cnts = [mp.detach().cpu().long()[1:] - mp.detach().cpu().long()[:-1] for mp in mol_ptrs]
+    widths = [None if p is None else (p.numel() // int(c.sum()) if int(c.sum()) else 1) for p, c in zip(params, cnts)]
+    den = torch.zeros(B, dtype=torch.float64)
+    for l in range(6):
+        if params[l] is not None and refs[l] is not None:
+            den = den + cnts[l].double() * widths[l]
+    pwv = torch.zeros(B, dtype=torch.float64) if pw is None else pw.detach().cpu().double()
+    out = []
+    for l in range(6):
+        if params[l] is None:
+            out.append(None)
+            continue
+        T, w = int(cnts[l].sum()), widths[l]
+        pv = params[l].detach().cpu().double().reshape(T, w).abs()
+        seg = torch.repeat_interleave(torch.arange(B), cnts[l])
+        s = torch.zeros_like(pv)
+        if refs[l] is not None and T:
+            r = _ref_table64(refs[l], T, w)
+            term = (~torch.isnan(r)) & (pwv != 0)[seg][:, None]
+            mse = (pwv * float(fac[l]) ** 2 * 2.0 / den.clamp(min=1))[seg][:, None] * (pv + torch.nan_to_num(r, nan=0.0).abs())
+            s = s + torch.where(term, mse, torch.zeros_like(mse))
+        if reg[l] > 0 and T:
+            s = s + (float(reg[l]) / (cnts[l].double() * w).clamp(min=1))[seg][:, None] * 2.0 * pv
+        out.append((inv_B * s).reshape(params[l].shape))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- output maps
+OUT_BOND, OUT_ANGLE, OUT_TORSION = 0, 1, 2
+BOND_CONSTS = [6.3, 0.1953, 0.0, 4.7, 161.2, 0.0]             # [mos_eq, std_eq, min_eq, mos_k, std_k, min_k]: production-like statistics
+ANGLE_CONSTS = [0.0292, math.pi, 0.0, 3.97, 26.6, 0.0]        # [std_over_max, max, -, mos_k, std_k, min_k]
+Z_POINTS = [0.0, 2.0 ** -20, -2.0 ** -20, -1.0, -20.0, -104.0, -200.0, 50.0]      # the ELU argument z = mos + c - 1: the kink, expm1f / expf underflow
+X_POINTS = [0.0, 1.0, -1.0, 20.0, -20.0, 88.0, -88.0, 100.0, -100.0, 1000.0, -1000.0]   # the angle sigmoid's argument s * c0: expf overflow, sg (1 - sg) = 0
+
+
+def _to_positive64(c, mos, std, mn):
+    """models/final_layer.py ToPositive: std * (elu(mean_over_std + x - 1) + 1) + min"""
+    return std * (F.elu(mos + c - 1.0) + 1.0) + mn
+
+
+def param_out_forward64(kind, c, cst, n_per, gated, cutoff):
+    """the output maps on the per-tuple sums c (T, nout) and the statistics cst, in the dtype of c -> (k, eq or None):
+    bond k, eq = ToPositive; angle k = ToPositive, eq = ToRange: max * sigmoid(std_over_max * x); torsion k = x k_std + k_mean or, gated,
+    x sigmoid(gate) k_std, with the hard cutoff k = 0 unless |k| > cutoff"""
+    if kind == OUT_TORSION:
+        if gated:
+            v = c[:, :n_per] * torch.sigmoid(c[:, n_per:2 * n_per]) * cst[:n_per]
+        else:
+            v = c[:, :n_per] * cst[:n_per] + cst[n_per:2 * n_per]
+        if cutoff > 0:
+            v = torch.where(v.abs() > float(np.float32(cutoff)), v, torch.zeros_like(v))
+        return v, None
+    eq = _to_positive64(c[:, 0], cst[0], cst[1], cst[2]) if kind == OUT_BOND else cst[1] * torch.sigmoid(cst[0] * c[:, 0])
+    return _to_positive64(c[:, 1], cst[3], cst[4], cst[5]), eq
+
+
+def param_out_ref64(kind, o, T, P, n_per, gated, cutoff, consts, dk, deq):
+    """-> (k, eq, d_o, d_consts) in float64: the forward stated directly, d_o and d_consts = the gradients of <dk, k> + <deq, eq> by
+    torch.autograd (dk / deq = None: no upstream gradient on that output).  eq is None for torsions.  T = 0: zeros."""
+    nout, ncst = o.shape[1], consts.numel()
+    if T == 0:
+        k = torch.zeros((0, n_per) if kind == OUT_TORSION else (0,), dtype=torch.float64)
+        return k, (None if kind == OUT_TORSION else torch.zeros(0, dtype=torch.float64)), torch.zeros(0, nout, dtype=torch.float64), \
+            torch.zeros(ncst, dtype=torch.float64)
+    od = o.detach().cpu().double().clone().requires_grad_(True)
+    cst = consts.detach().cpu().double().clone().requires_grad_(True)
+    k, eq = param_out_forward64(kind, od.view(P, T, nout).sum(0), cst, n_per, gated, cutoff)
+    loss = (od * 0.0).sum() + (cst * 0.0).sum()
+    if dk is not None:
+        loss = loss + (k * dk.detach().cpu().double().reshape(k.shape)).sum()
+    if deq is not None and eq is not None:
+        loss = loss + (eq * deq.detach().cpu().double()).sum()
+    d_o, d_c = torch.autograd.grad(loss, (od, cst))
+    return k.detach(), (None if eq is None else eq.detach()), d_o, d_c
+
+
+def param_out_scales(kind, o, T, P, consts):
+    """bond / angle: per tuple, the magnitude the outputs' gates are relative to -> (k scale, eq scale), float64 (T,):
+    ToPositive  std * (|mos| + sum_p |o_p| + 1) + |min|;   angle eq  max * (1 + |s| * sum_p |o_p|)"""
+    a = o.detach().cpu().double().abs().view(P, T, -1).sum(0)
+    c = [abs(float(v)) for v in consts.detach().cpu().double()]
+    sk = c[4] * (c[3] + a[:, 1] + 1.0) + c[5]
+    seq = c[1] * (c[0] + a[:, 0] + 1.0) + c[2] if kind == OUT_BOND else c[1] * (1.0 + c[0] * a[:, 0])
+    return sk, seq
+
+
+def param_out_grad_scale(kind, o, T, P, consts, dk, deq):
+    """the scale of d_o (P*T, nout): column 0 |deq| x the eq scale, column 1 |dk| x the k scale (0 without that upstream gradient),
+    further columns 0 (they must come back exactly 0)"""
+    sk, seq = param_out_scales(kind, o, T, P, consts)
+    s = torch.zeros(T, o.shape[1], dtype=torch.float64)
+    if deq is not None:
+        s[:, 0] = deq.detach().cpu().double().abs() * seq
+    if dk is not None:
+        s[:, 1] = dk.detach().cpu().double().abs() * sk
+    return s.repeat(P, 1)
+
+
+def param_out_stat_terms64(kind, o, T, P, n_per, gated, cutoff, consts, dk, deq):
+    """(T, ncst) float64: tuple t's term of d_consts[i] (its closed form; the rows' sum is param_out_ref64's d_consts, which
+    tests/test_kernel_domain_refs.py checks) -- sum_t |term| is the magnitude the statistics gradients' gate is relative to"""
+    ncst = consts.numel()
+    terms = torch.zeros(T, ncst, dtype=torch.float64)
+    if T == 0:
+        return terms
+    c = o.detach().cpu().double().view(P, T, -1).sum(0)
+    cst = consts.detach().cpu().double()
+    d = lambda t, shape: torch.zeros(shape, dtype=torch.float64) if t is None else t.detach().cpu().double().reshape(shape)      # noqa: E731
+    if kind == OUT_TORSION:
+        up = d(dk, (T, n_per))
+        v, _ = param_out_forward64(kind, c, cst, n_per, gated, cutoff)
+        if cutoff > 0:
+            up = torch.where(v != 0, up, torch.zeros_like(up))
+        if gated:
+            terms[:, :n_per] = up * c[:, :n_per] * torch.sigmoid(c[:, n_per:2 * n_per])
+        else:
+            terms[:, :n_per] = up * c[:, :n_per]
+            terms[:, n_per:] = up
+        return terms
+
+    def pos(x, mos, std, u):          # d/d mos, d/d std, d/d min of u * ToPositive
+        z = mos + x - 1.0
+        return u * std * torch.where(z > 0, torch.ones_like(z), torch.exp(z)), u * (F.elu(z) + 1.0), u
+    ueq, uk = d(deq, (T,)), d(dk, (T,))
+    if kind == OUT_BOND:
+        terms[:, 0], terms[:, 1], terms[:, 2] = pos(c[:, 0], cst[0], cst[1], ueq)
+    else:
+        sg = torch.sigmoid(cst[0] * c[:, 0])
+        terms[:, 0] = ueq * cst[1] * sg * (1.0 - sg) * c[:, 0]
+        terms[:, 1] = ueq * sg
+    terms[:, 3], terms[:, 4], terms[:, 5] = pos(c[:, 1], cst[3], cst[4], uk)
+    return terms
+
+
+def param_out_stats_c(T):
+    """the constant of the statistics gradients' gate |gpu - f64| <= c u32 sum_t |term_t|: the longest chain of fp32 additions an element
+    goes through in param_out_stats_kernel + param_out_stats_final_kernel (csrc/tuples.hip) -- a thread's serial sum over its
+    ceil(T / 65536) tuples (256 blocks x 256 threads at the most), the final serial sum over the min(256, ceil(T / 256)) blocks, the
+    six butterfly steps of a wave plus the two additions of the four waves (8) -- and 16 for each term's own arithmetic"""
+    return -(-T // 65536) + min(256, -(-T // 256)) + 8 + 16
+
+
+def param_out_case(kind, T, P, nout, consts, seed, n_per=0, gated=False):
+    """inputs of one output-map case (fp32, CPU): o (P*T, nout) randn, dk, deq.  Bond / angle: the leading tuples (as many as T holds)
+    sit on the named points -- tuple t has z = mos + c - 1 = Z_POINTS[(t + P) % 8] in BOTH ToPositive columns (bond) and the angle
+    sigmoid's argument s * c0 = X_POINTS[(t + P) % 11]; the sum over the P rows is exact (row 0 carries c - (P - 1) / 2, the others 1/2).
+    Torsion: randn, with the gate columns of the leading tuples at +-20, +-88, +-100 (sigmoid saturated both ways)."""
+    gen = torch.Generator().manual_seed(seed)
+    o = torch.randn(P * T, nout, generator=gen)
+    cst = [float(np.float32(v)) for v in consts]
+
+    def put(t, col, c):
+        o[t, col] = c - 0.5 * (P - 1)
+        for p in range(1, P):
+            o[p * T + t, col] = 0.5
+    if kind == OUT_TORSION:
+        if gated:
+            for t in range(min(T, 12)):
+                g = [20.0, -20.0, 88.0, -88.0, 100.0, -100.0][t % 6]
+                for n in range(n_per):
+                    put(t, n_per + n, g)
+        dk, deq = torch.randn(T, n_per, generator=gen), None
+    else:
+        for t in range(min(T, 3 * len(X_POINTS))):
+            put(t, 1, 1.0 - cst[3] + Z_POINTS[(t + P) % len(Z_POINTS)])
+            if kind == OUT_BOND:
+                put(t, 0, 1.0 - cst[0] + Z_POINTS[(t + P + t // len(Z_POINTS)) % len(Z_POINTS)])
+            else:
+                put(t, 0, X_POINTS[(t + P) % len(X_POINTS)] / cst[0])
+        dk, deq = torch.randn(T, generator=gen), torch.randn(T, generator=gen)
+    return o, dk, deq
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- column sums, charges
+def colsum_chain(M):
+    """grappa_colsum_f32 (csrc/rowwise.hip) -> (rows per block, additions of the partials' reduction, blocks used).
+    colsum_partial_kernel: min(512, ceil(M / 64)) blocks, each a serial sum over rows_per_block = ceil(M / blocks) rows.  reduce_rows:
+    up to 64 partials in one stage, more in two (32 groups of rpg = ceil(blocks / 32), then the groups); a stage over n values keeps four
+    interleaved accumulators of n // 4 additions, adds the n % 4 left-over values to the first and combines the four pairwise (2):
+    n // 4 + n % 4 + 2 additions on the longest path.  (The last stage's `out + s` and slack are the gate's + 8.)"""
+    blocks = min(512, max(1, -(-M // 64)))
+    rpb = -(-M // blocks)
+    used = -(-M // rpb)
+    stage = lambda n: n // 4 + n % 4 + 2          # noqa: E731
+    if used <= 64:
+        return rpb, stage(used), used
+    rpg = -(-used // 32)
+    return rpb, stage(rpg) + stage(-(-used // rpg)), used
+
+
+def charge_encoding_ref64(q, dim, lo, hi):
+    """the reference encoder (models/graph_attention.py via oracle/cpu_ref.charge_encoding) in float64, its scaling quirk included:
+    v = clamp(q, lo, hi); s = (v + hi) / (hi - lo)  [not (v - lo)]; out[:, 2j] = sin(s f_j), out[:, 2j+1] = cos(s f_j), f_j = 10000^(-j / (dim/2))"""
+    v = torch.clamp(q.detach().cpu().double(), lo, hi)
+    s = (v + hi) / (hi - lo)
+    half = dim // 2
+    f = torch.exp(torch.arange(half, dtype=torch.float64) * (-math.log(10000.0) / half))
+    out = torch.zeros(q.numel(), dim, dtype=torch.float64)
+    out[:, 0::2] = torch.sin(s[:, None] * f)
+    out[:, 1::2] = torch.cos(s[:, None] * f)
+    return out
+
+
+def assert_sum(got, want64, c, abs_sum, what):
+    """a sum of terms, per element: |got - f64| <= c * u32 * sum |term|  (abs_sum, float64) -> the largest error / bound"""
+    got, want64 = got.detach().cpu().double(), want64.detach().cpu().double()
+    abs_sum = torch.as_tensor(abs_sum, dtype=torch.float64).expand(want64.shape)
+    assert got.shape == want64.shape, (what, got.shape, want64.shape)
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
+    d, bound = (got - want64).abs(), c * U32 * abs_sum
+    bad = d > bound
+    if bool(bad.any()):
+        i = int(torch.argmax((d / bound.clamp_min(1e-300)).reshape(-1)))
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} sums outside c={c} u32 sum|term|; worst at flat index {i}: got "
+                             f"{float(got.reshape(-1)[i]):.9g} f64 {float(want64.reshape(-1)[i]):.9g} ({float(d.reshape(-1)[i] / bound.reshape(-1)[i]):.3g}x the bound)")
+    ok = bound > 0
+    return float((d[ok] / bound[ok]).max()) if bool(ok.any()) else 0.0
+
+
+def el_ratio(got, want64, c, scale):
+    """the largest |got - f64| / (c u32 (|f64| + scale)) of assert_el (the figure the test files' docstrings record)"""
+    got, want64 = got.detach().cpu().double(), want64.detach().cpu().double()
+    bound = c * U32 * (want64.abs() + torch.as_tensor(scale, dtype=torch.float64))
+    ok = bound > 0
+    return float(((got - want64).abs() / bound.clamp_min(1e-300))[ok].max()) if bool(ok.any()) else 0.0
+
+
 # ----------------------------------------------------------------------------------------------------------------------------- dense products
 GOLDEN64 = 0x9E3779B97F4A7C15      # include/grappa_hip.h, drop_salt: seed + word * 0x9E3779B97F4A7C15 (mod 2^64)
 FP32_GRADE = ("f32", "f32_bf16x9", "f32_bf16x6", "f32_f16x3")

@@ -330,3 +330,165 @@ def test_c_acc_is_twice_the_cpu_references_error():
     r_mm, r_ch = gr.calibrate()
     assert gr.R_CHAIN - 0.01 <= r_ch <= gr.R_CHAIN, r_ch
     assert r_mm <= gr.C_ACC, r_mm
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- output maps, parameter loss
+import head_loss_cases as hc  # noqa: E402
+
+
+@pytest.mark.parametrize("name,kind,n_per,gated,cutoff", [("bond", 0, 0, False, 0.0), ("angle", 1, 0, False, 0.0), ("torsion", 2, 3, False, 1e-4),
+                                                           ("torsion-gated", 2, 3, True, 1e-4)])
+def test_param_out_reference(ref, name, kind, n_per, gated, cutoff):
+    """kernel_refs.param_out_ref64 (forward stated directly, gradients by autograd) = RefBackend's forward, closed-form backward and
+    statistics gradient on float64 inputs; the closed-form terms whose magnitudes scale the statistics gate sum to that gradient"""
+    T, P = 40, 3
+    nout = 2 if kind != 2 else (2 if gated else 1) * n_per
+    gen = torch.Generator().manual_seed(kind + 5)
+    consts = torch.tensor(kr.BOND_CONSTS if kind == 0 else kr.ANGLE_CONSTS) if kind != 2 else torch.cat([0.1 + torch.rand(n_per, generator=gen), torch.randn(n_per, generator=gen)])
+    o, dk, deq = kr.param_out_case(kind, T, P, nout, consts.tolist(), 3, n_per, gated)
+    if kind == 2:
+        consts[n_per:] *= torch.tensor([0.0, 1.0, 1.0])          # (no k_mean on the first periodicity ...)
+        o.view(P, T, nout)[:, :5] *= 1e-6                        # (... where these tuples take the cutoff branch)
+    o, consts, dk, deq = o.double(), consts.double(), dk.double(), None if deq is None else deq.double()
+    k64, eq64, do64, dc64 = kr.param_out_ref64(kind, o, T, P, n_per, gated, cutoff, consts, dk, deq)
+    k = torch.empty(k64.shape, dtype=D64)
+    eq = None if kind == 2 else torch.empty(T, dtype=D64)
+    d_o, d_c = torch.empty(P * T, nout, dtype=D64), torch.empty(consts.numel(), dtype=D64)
+    cut = float(np.float32(cutoff))
+    ref.param_out_fwd(kind, o, T, P, n_per, gated, cut, consts, k, eq)
+    ref.param_out_bwd(kind, o, T, P, n_per, gated, cut, consts, dk, deq, d_o)
+    ref.param_out_bwd_stats(kind, o, T, P, n_per, gated, cut, consts, dk, deq, d_c)
+    _close(k64, k, name + " k"), _close(do64, d_o, name + " d_o"), _close(dc64, d_c, name + " d_consts")
+    if eq is not None:
+        _close(eq64, eq, name + " eq")
+    terms = kr.param_out_stat_terms64(kind, o, T, P, n_per, gated, cutoff, consts, dk, deq)
+    assert float((terms.sum(0) - dc64).abs().max()) <= 1e-12 * float(terms.abs().sum(0).max()), name + ": the terms do not sum to d_consts"
+    if kind == 2:
+        assert bool((k64 == 0).any()) and bool((k64 != 0).any())
+    # no upstream gradient, no tuples
+    z = kr.param_out_ref64(kind, o, T, P, n_per, gated, cutoff, consts, None, None)
+    assert bool((z[2] == 0).all()) and bool((z[3] == 0).all())
+    e = kr.param_out_ref64(kind, o[:0], 0, P, n_per, gated, cutoff, consts, dk[:0], None)
+    assert e[0].numel() == 0 and e[2].shape == (0, nout) and bool((e[3] == 0).all())
+
+
+def test_loss_param_reference_against_ref_molwise_loss():
+    """kernel_refs.loss_param_ref64 = cpu_ref.RefMolwiseLoss run in float64 with param_weight, param_weights_by_dataset and both
+    regularisers, per molecule and through autograd; k_ref / eq_ref tables with NaN entries and an n4 reference narrower than k.  A
+    molecule without a single tuple (den == 0) is the documented deviation: 0 here, NaN in the reference loop."""
+    from grappa_amd.batch import batch, single_graph
+    from grappa_amd.datasets import graph_from_pool
+    from oracle.cpu_ref import RefMolwiseLoss
+    empty = lambda s: np.zeros((0, s), dtype=np.int64)          # noqa: E731
+    bare = single_graph(2, np.array([[0, 1]]), {"n2": empty(2), "n3": empty(3), "n4": empty(4), "n4_improper": empty(4)}, {"partial_charge": torch.zeros(2)})
+    g = batch([bare] + [graph_from_pool(i, 1, 0) for i in (300, 301, 302)])
+    B = g.batch_size
+    gen = torch.Generator().manual_seed(21)
+    T = {l: g.num_nodes(l) for l in ("n2", "n3", "n4", "n4_improper")}
+    rn = lambda *s: torch.randn(*s, generator=gen, dtype=D64)          # noqa: E731
+    params = [700 + 100 * rn(T["n2"]), 1.2 + 0.1 * rn(T["n2"]), 100 + 20 * rn(T["n3"]), 1.9 + 0.1 * rn(T["n3"]), rn(T["n4"], 6), rn(T["n4_improper"], 3)]
+    refs = [p * (1 + 0.01 * rn(*p.shape)) for p in params[:4]] + [rn(T["n4"], 4), rn(T["n4_improper"], 3)]
+    refs[2][:7] = float("nan")
+    refs[1][3] = float("nan")
+    refs[4][2, 1] = float("nan")
+    live = [p.clone().requires_grad_(True) for p in params]
+    for (lvl, name), p, r in zip(hc_levels(), live, refs):
+        g.nodes[lvl].data[name], g.nodes[lvl].data[name + "_ref"] = p, r
+    dsnames = ["x", "a", "b", "x"]
+    lf = RefMolwiseLoss(gradient_weight=0.0, energy_weight=0.0, param_weight=1e-3, param_weights_by_dataset={"a": 0.0, "b": 5e-3},
+                        proper_regularisation=1e-3, improper_regularisation=2e-3)
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(D64)          # (RefMolwiseLoss makes its sums and weights with the default dtype)
+    try:
+        total = lf(g, dsnames)
+    finally:
+        torch.set_default_dtype(old)
+    grads = torch.autograd.grad(total, live)
+    pw = torch.tensor([1e-3, 0.0, 5e-3, 1e-3], dtype=D64)
+    ptrs = [g.plan().mol_ptr[l] for l in hc.LV6]
+    fac, reg = hc.FAC, [0, 0, 0, 0, 1e-3, 2 * 2e-3]          # (the reference adds the improper regulariser twice)
+    loss, gp = kr.loss_param_ref64(ptrs, params, refs[:5] + [None], fac, reg, pw, 1.0 / B)
+    per_mol = lf.last_per_molecule
+    assert bool(torch.isnan(per_mol[0])) and float(loss[0]) == 0.0, "den == 0: the reference loop's NaN is 0 here"
+    _close(loss[1:], per_mol[1:], "parameter loss per molecule")
+    assert float(loss[1]) > 0 and float(loss[2]) > float(loss[3]) * 0.1
+    for l in range(6):
+        assert bool(torch.isfinite(grads[l]).all())
+        _close(gp[l], grads[l], f"d/d params[{l}]")
+    # the scale of the gradients' gate bounds the gradient itself, and is 0 exactly where there is no term
+    sc = kr.loss_param_grad_scales(ptrs, params, refs[:5] + [None], fac, reg, pw, 1.0 / B)
+    for l in range(6):
+        assert bool((gp[l].abs() <= sc[l] * (1 + 1e-12)).all()), l
+    assert bool((sc[2][:7] == 0).all()) and bool((gp[2][:7] == 0).all())
+
+
+def hc_levels():
+    return [("n2", "k"), ("n2", "eq"), ("n3", "k"), ("n3", "eq"), ("n4", "k"), ("n4_improper", "k")]
+
+
+def test_colsum_chain_and_charge_reference(ref):
+    assert kr.colsum_chain(1) == (1, 3, 1) and kr.colsum_chain(64) == (64, 3, 1) and kr.colsum_chain(65) == (33, 2 + 2, 2)
+    assert kr.colsum_chain(4096) == (64, 16 + 2, 64) and kr.colsum_chain(4097) == (64, (3 + 2) + (5 + 2 + 2), 65)
+    assert kr.colsum_chain(32768) == (64, (4 + 2) + (8 + 2), 512) and kr.colsum_chain(40000)[::2] == (79, 507)
+    from oracle.cpu_ref import charge_encoding
+    q = torch.linspace(-4, 4, 33, dtype=D64)
+    for lo, hi, dim in ((-2.0, 2.0, 16), (-1.0, 3.0, 2), (0.0, 1.0, 16)):
+        old = torch.get_default_dtype()
+        torch.set_default_dtype(D64)          # (cpu_ref.charge_encoding allocates with the default dtype)
+        try:
+            want = charge_encoding(q, dim, lo, hi)
+        finally:
+            torch.set_default_dtype(old)
+        assert float((kr.charge_encoding_ref64(q, dim, lo, hi) - want).abs().max()) < 1e-6          # (its frequencies are made in fp32)
+
+
+# every gate of tests/test_gpu_head_and_loss_domains.py is reachable by a correct fp32 implementation: the same checks on RefBackend, CPU
+@pytest.mark.parametrize("name", list(hc.MAP_CONSTS))
+def test_fp32_ref_backend_passes_the_map_gates(ref, name):
+    base = name.split("-")[0]
+    for T in (1, 255, 256, 257):
+        for P in (1, 2, 3, 6):
+            hc.check_param_out_map(ref, "cpu", name, T, P, 2 + (P % 2))
+    for drop in ("dk", "deq", "both"):
+        hc.check_param_out_map(ref, "cpu", base, 257, 2, 2, drop)
+    hc.check_param_out_map(ref, "cpu", base, 0, 2, 2)
+
+
+@pytest.mark.parametrize("gated", [False, True])
+def test_fp32_ref_backend_passes_the_cutoff_checks(ref, gated):
+    hc.check_torsion_cutoff(ref, "cpu", gated)
+
+
+@pytest.mark.parametrize("name", list(hc.STATS_KINDS))
+def test_fp32_ref_backend_passes_the_statistics_gate(ref, name):
+    for T, P in ((1, 2), (257, 6), (1003, 2), (65537, 2)):
+        hc.check_param_out_stats(ref, "cpu", name, T, P)
+
+
+@pytest.mark.parametrize("name", hc.LOSS_PARAM_CASES)
+def test_fp32_ref_backend_passes_the_loss_param_gates(ref, name):
+    hc.check_loss_param(ref, ref, "cpu", name)
+
+
+def test_fp32_ref_backend_passes_the_loss_ef_colsum_and_charge_gates(ref):
+    for C in (1, 6):
+        for wE, wG in ((1.0, 0.0), (0.0, 0.8), (1.0, 0.8)):
+            hc.check_loss_ef_off(ref, ref, "cpu", C, wE, wG)
+    for shape in hc.COLSUM_SHAPES + [(0, 12, 12)]:
+        for acc in (False, True):
+            hc.check_colsum(ref, "cpu", *shape, acc)
+    for lo, hi in ((-2.0, 2.0), (-1.0, 3.0), (0.0, 1.0)):
+        for dim in (2, 16):
+            for N, col0 in ((0, 0), (1, 0), (257, 0), (257, 5)):
+                hc.check_charge_encoding(ref, "cpu", lo, hi, dim, N, col0)
+
+
+def test_the_new_gates_reject_what_they_must():
+    """a statistics sum that lost one block's partial, a loss increment divided by the wrong count, a gradient off by 1e-3 relative"""
+    kind, n_per, gated, cutoff, consts, o, dk, deq, want, scale = hc.stats_case("bond", 1003, 2)
+    terms = kr.param_out_stat_terms64(kind, o, 1003, 2, n_per, gated, cutoff, consts, dk, deq)
+    kr.assert_sum(want.float(), want, kr.param_out_stats_c(1003), scale, "fp32 rounding of the sums")
+    with pytest.raises(AssertionError):
+        kr.assert_sum(terms[256:].sum(0), want, kr.param_out_stats_c(1003), scale, "the first block's partial left out")
+    with pytest.raises(AssertionError):
+        kr.assert_sum(want * (1 + 1e-3), want, kr.param_out_stats_c(1003), scale, "off by 1e-3")
