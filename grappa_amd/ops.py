@@ -7,6 +7,13 @@ epilogues (`res=`), parameter gradients are accumulated by the kernels straight 
 (flat-buffer friendly: one RCCL all-reduce / one fused Adam over all of them), and dropout masks are
 regenerated from a counter-based hash instead of being stored.
 
+The writer heads' sequences -- feed-forward, dropout / activation backward, the unfused attention layer body, the glue around the fused
+layer, the symmetriser -- are each stated once, as plain functions over lists with one entry per head (`_ff_fwd` / `_ff_bwd`, `_drop_bwd`,
+`_layer_fwd` / `_layer_bwd` with `_transformer_fwd` / `_transformer_bwd` around them, `_fused_*`, `_sym_fwd` / `_sym_bwd`).  The
+head-by-head Functions (TransformerLayerFn, ProjFirstLayerFn, SymmetriserFn, and AttBlockFn for its feed-forward part) call them with lists
+of one, the layer-locked ones (MultiTransformerLayerFn, MultiSymmetriserFn) with every head that has the layer; what still differs between
+the two paths is an argument at the call site.  tests/test_ops_trace.py pins every library call of both.
+
 Reference blocks restated (file:line under /root/reference/src/grappa/):
   LinearFn            models/graph_attention.py:98-101, :125-127 (pre_dense / post_dense)
   AttBlockFn          models/graph_attention.py:276-310  (ResidualAttentionBlock + DGL DotGatConv)
@@ -20,7 +27,7 @@ Reference blocks restated (file:line under /root/reference/src/grappa/):
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -177,10 +184,11 @@ def mark_mode() -> None:
     _INFERENCE["on"] = not torch.is_grad_enabled()
 
 
-def _infer(ctx) -> int:
+def _infer(ctx, inputs=(0,)) -> int:
     """-> 1: inference (no node will run backward); 2: training on a backend whose products read the pair format (HipBackend.training_pairs);
-    0: neither.  (Second condition of 1: whatever the flag says, an input activation that asks for a gradient means a backward pass will come.)"""
-    if _INFERENCE["on"] and not ctx.needs_input_grad[0]:
+    0: neither.  (Second condition of 1: whatever the flag says, an input activation -- the Function's arguments `inputs` -- that asks for a
+    gradient means a backward pass will come.)"""
+    if _INFERENCE["on"] and not any(ctx.needs_input_grad[i] for i in inputs):
         return 1
     return 2 if getattr(get_backend(), "training_pairs", False) else 0
 
@@ -232,72 +240,131 @@ def _masked_grad(dy, drop_p, seed):
     return m[0], m[1]
 
 
-def _ff_fwd(be, x, norm_w, norm_b, w1, b1, w2, b2, act2, drop_p, seed, skip, infer=False):
-    """FeedForward: xn = LN(x); u = ELU(xn W1^T + b1); y = act2(u W2^T + b2); out = drop(y) (+ xn)."""
-    M = x.shape[0]
-    Hd, Nout = w1.shape[0], w2.shape[0]
-    narrow = Nout <= 32                       # the output maps' last product (2 .. 12 columns): fp32 kernels, fp32 operands and result
-    # inference through the pair format: the normalised rows are written as pairs only when the product that adds them back (skip) can
-    # recompute them in its epilogue -- or nobody adds them back
-    lean = _pairs(be, x, infer) and norm_w is not None and Hd > 32 and M > 32 and (not skip or not narrow)
-    xn, mean, rstd, sxn = _ln_fwd(be, x, norm_w, norm_b, infer, need_y=not lean)
-    u = _new((M, Hd), x, F32 if narrow else None)
-    # u feeds the next product: its row maxima come out of this product's epilogue -- where a product will read them (ADVICE r2)
-    sxn, su = be.gemm(xn, w1, u, M=M, N=Hd, K=x.shape[1], bias=b1, act=ELU, a_scales=sxn, out_amax=_wants_amax(be, False))
-    out = _new((M, Nout), x, F32 if narrow else None)
-    res = xn if skip else None
-    pre = None
-    ln_res = (mean, rstd, norm_w, norm_b) if (skip and xn is None) else None      # (lean) the residual = LayerNorm(x), recomputed by the epilogue from x
-    if act2:
-        pre = _new((M, Nout), x)
-        kw = dict(res=x, res_ln=ln_res) if ln_res else dict(res=res)
-        su = be.gemm(u, w2, pre, M=M, N=Nout, K=Hd, bias=b2, act=ELU, drop_p=drop_p, drop_seed=seed, out2=out, a_scales=su, **kw)
-    elif skip and xn is None:                  # (lean) the residual = LayerNorm(x), recomputed by the epilogue from x
-        su = be.gemm(u, w2, out, M=M, N=Nout, K=Hd, bias=b2, drop_p=drop_p, drop_seed=seed, res=x, res_ln=(mean, rstd, norm_w, norm_b), a_scales=su)
-    else:
-        su = be.gemm(u, w2, out, M=M, N=Nout, K=Hd, bias=b2, drop_p=drop_p, drop_seed=seed, res=res, a_scales=su)
-    return out, (x, mean, rstd, xn, u, pre, sxn, su)
+# ------------------------------------------------------------------------------------------------
+# The writer heads' sequences, stated once over LISTS with one entry per head.  The four heads (bond / angle / proper / improper) have the
+# same architecture and read the same atom embedding; head by head, each of their products leaves most of the chip idle at small batches
+# (batch 32: 44 .. 176 workgroups of one tile time each on 256 CUs) and costs a launch.  Layer-locked (model._forward_merged), one autograd
+# node runs ONE transformer layer (or the symmetrisers) of all heads: row-wise kernels head by head or batched, every product of the layer
+# as ONE grouped launch (backend.gemm_group).  Head by head, the same functions run on lists of one: `_gemm_group` falls back to `be.gemm`
+# below two calls and every batched row-wise launch needs two heads, so a list of one emits the single-head calls -- the two paths cannot
+# drift apart, and tests/test_ops_trace.py pins what both emit.
+def _gemm_group(be, calls):
+    f = getattr(be, "gemm_group", None)
+    if f is None or len(calls) < 2:
+        return [be.gemm(*a, **k) for a, k in calls]
+    return f(calls)
 
 
-def _ff_bwd(be, saved, dout, norm_w, norm_b, w1, b1, w2, b2, act2, drop_p, seed, skip, sdout=None, then_drop=None):
-    """-> (dx, record of dx's row maxima or None); sdout: the record for dout when the kernel that produced it wrote one; then_drop: (p, seed)
-    of the dropout whose backward reads dx next (_ln_bwd)"""
-    x, mean, rstd, xn, u, pre, sxn, su = saved          # (xn is None where the forward pass wrote the normalised rows as pairs only: sxn.pairs)
-    M = x.shape[0]
-    if not dout.is_contiguous():
-        dout, sdout = dout.contiguous(), None
-    ready = _masked_grad(dout, drop_p, seed) if (drop_p > 0 and not act2) else None
-    if ready is not None:
-        dz2, sz = ready
-    elif act2 or drop_p > 0:
-        if dout.dtype == F32 and _bwd_pairs(be, M, dout.shape[1], w2):
-            dz2, sz = None, be.act_dropout_bwd(dout, pre if act2 else None, drop_p, seed, None, pairs=True)      # pairs only: both products behind read them
+def _ln_fwd_heads(be, xs, ws, bs, infer, need_y):
+    """_ln_fwd of every head: ONE batched launch where the backend has it, for two or more heads none of which writes the pair format"""
+    f = getattr(be, "layernorm_fwd_batched", None)
+    if f is not None and len(xs) >= 2 and all(w is not None for w in ws) and not any(_pairs(be, x, infer) for x in xs):
+        r = f(xs, ws, bs)
+        if r is not None:
+            return r
+    return [_ln_fwd(be, x, w, b, infer, need_y=ny) for x, w, b, ny in zip(xs, ws, bs, need_y)]
+
+
+def _ln_bwd_heads(be, dys, xs, means, rstds, ws, bs, drops=None):
+    """_ln_bwd of every head -> [(dx, record)]: ONE batched launch for two or more heads with every affine pair trainable (and no dropout
+    backward to write with it: drops, per head as _ln_bwd's drop)"""
+    f = getattr(be, "layernorm_bwd_batched", None)
+    if f is not None and len(xs) >= 2 and drops is None and all(w is not None and w.requires_grad and b.requires_grad for w, b in zip(ws, bs)):
+        r = f([(dy, x, m, r_, w, _pgrad(w), _pgrad(b)) for dy, x, m, r_, w, b in zip(dys, xs, means, rstds, ws, bs)])
+        if r is not None:
+            return r
+    return [_ln_bwd(be, dy, x, m, r_, w, b, drop=d) for dy, x, m, r_, w, b, d in zip(dys, xs, means, rstds, ws, bs, drops or [None] * len(xs))]
+
+
+def _drop_bwd(be, dys, drops, ws, ys=None):
+    """dropout (p, seed) backward of every head's dy, with ELU' where ys holds the saved ELU outputs -> [(dz or None, record)].  Per head, in
+    this order: dy itself with no record where there is neither dropout nor activation; what the kernel that produced dy wrote already
+    (_masked_grad); the pair format only (dz None) where both products behind it (weight w) read pairs; else fp32 rows.  Two or more heads
+    that all take the last way: ONE batched launch."""
+    n = len(dys)
+    ys = ys or [None] * n
+    ready = [_masked_grad(dy, p, sd) if (p > 0 and y is None) else None for dy, (p, sd), y in zip(dys, drops, ys)]
+    f = getattr(be, "act_dropout_bwd_batched", None)
+    if f is not None and n >= 2 and all((p > 0 or y is not None) for (p, _s), y in zip(drops, ys)) and not any(r is not None for r in ready) and \
+            not any(dy.dtype == F32 and _bwd_pairs(be, dy.shape[0], dy.shape[1], w) for dy, w in zip(dys, ws)):
+        r = f([(dy, y, p, sd) for dy, y, (p, sd) in zip(dys, ys, drops)])
+        if r is not None:
+            return r
+    out = []
+    for dy, (p, sd), w, y, rd in zip(dys, drops, ws, ys, ready):
+        if p <= 0 and y is None:
+            out.append((dy, None))
+        elif rd is not None:
+            out.append(rd)
+        elif dy.dtype == F32 and _bwd_pairs(be, dy.shape[0], dy.shape[1], w):
+            out.append((None, be.act_dropout_bwd(dy, y, p, sd, None, pairs=True)))      # pairs only: both products behind read them
         else:
-            dz2 = _new(dout.shape, dout)
-            sz = be.act_dropout_bwd(dout, pre if act2 else None, drop_p, seed, dz2)
-    else:
-        dz2, sz = dout, sdout
-    sz = _linear_bwd_params(be, dz2, u, w2, b2, su, sz)
-    dz1 = _new(u.shape, x)                                         # (u is fp32 in front of a narrow output product, x never)
-    _, sz = be.gemm(dz2, w2, dz1, M=M, N=u.shape[1], K=w2.shape[0], b_kcontig=False, aux=u, a_scales=sz, out_amax=_wants_amax(be, True))   # fused ELU'(u)
-    sz = _linear_bwd_params(be, dz1, xn, w1, b1, sxn, sz)
-    dxn = _new(x.shape, x)
-    be.gemm(dz1, w1, dxn, M=M, N=x.shape[1], K=u.shape[1], b_kcontig=False, res=dout if skip else None, a_scales=sz)
-    return _ln_bwd(be, dxn, x, mean, rstd, norm_w, norm_b, drop=then_drop)
+            dz = _new(dy.shape, dy)
+            out.append((dz, be.act_dropout_bwd(dy, y, p, sd, dz)))
+    return out
 
 
-def _drop_bwd(be, dy, drop_p, seed, w):
-    """dz = dropout mask of the forward pass applied to dy (no activation) -> (dz or None, record): in the pair format only where both
-    products behind it read pairs; dy itself without dropout"""
-    if drop_p <= 0:
-        return dy, None
-    ready = _masked_grad(dy, drop_p, seed)
-    if ready is not None:
-        return ready
-    if dy.dtype == F32 and _bwd_pairs(be, dy.shape[0], dy.shape[1], w):
-        return None, be.act_dropout_bwd(dy, None, drop_p, seed, None, pairs=True)
-    dz = _new(dy.shape, dy)
-    return dz, be.act_dropout_bwd(dy, None, drop_p, seed, dz)
+def _ff_fwd(be, xs, params, drops, skips, infer, act2=False):
+    """FeedForward of every head: xn = LN(x); u = ELU(xn W1^T + b1); y = act2(u W2^T + b2); out = drop(y) (+ xn).
+    xs [x], params [(norm_w, norm_b, w1, b1, w2, b2)], drops [(drop_p, seed)], skips [bool] -> ([out], [saved])"""
+    # inference through the pair format: the normalised rows are written as pairs only when the product that adds them back (skip) can
+    # recompute them in its epilogue -- or nobody adds them back.  (narrow = w2.shape[0] <= 32, the output maps' last product, 2 .. 12 columns:
+    # fp32 kernels, fp32 operands and result)
+    leans = [_pairs(be, x, infer) and p[0] is not None and p[2].shape[0] > 32 and x.shape[0] > 32 and (not sk or not p[4].shape[0] <= 32)
+             for x, p, sk in zip(xs, params, skips)]
+    lns = _ln_fwd_heads(be, xs, [p[0] for p in params], [p[1] for p in params], infer, [not l for l in leans])
+    us, calls = [], []
+    for x, (norm_w, norm_b, w1, b1, w2, b2), (xn, mean, rstd, sxn) in zip(xs, params, lns):
+        M, Hd = x.shape[0], w1.shape[0]
+        u = _new((M, Hd), x, F32 if w2.shape[0] <= 32 else None)
+        us.append(u)
+        # u feeds the next product: its row maxima come out of this product's epilogue -- where a product will read them (ADVICE r2)
+        calls.append(((xn, w1, u), dict(M=M, N=Hd, K=x.shape[1], bias=b1, act=ELU, a_scales=sxn, out_amax=_wants_amax(be, False))))
+    r1 = _gemm_group(be, calls)
+    outs, saved, calls = [], [], []
+    for x, (norm_w, norm_b, w1, b1, w2, b2), (drop_p, seed), skip, (xn, mean, rstd, _), u, (sxn, su) in zip(xs, params, drops, skips, lns, us, r1):
+        M, Hd, Nout = x.shape[0], w1.shape[0], w2.shape[0]
+        out = _new((M, Nout), x, F32 if Nout <= 32 else None)
+        ln_res = (mean, rstd, norm_w, norm_b) if (skip and xn is None) else None      # (lean) the residual = LayerNorm(x), recomputed by the epilogue from x
+        kw = dict(res=x, res_ln=ln_res) if ln_res else dict(res=xn if skip else None)
+        pre = None
+        if act2:
+            pre = _new((M, Nout), x)
+            calls.append(((u, w2, pre), dict(M=M, N=Nout, K=Hd, bias=b2, act=ELU, drop_p=drop_p, drop_seed=seed, out2=out, a_scales=su, **kw)))
+        else:
+            calls.append(((u, w2, out), dict(M=M, N=Nout, K=Hd, bias=b2, drop_p=drop_p, drop_seed=seed, a_scales=su, **kw)))
+        outs.append(out)
+        saved.append((x, mean, rstd, xn, u, pre, sxn))
+    return outs, [sv + (su,) for sv, su in zip(saved, _gemm_group(be, calls))]
+
+
+def _ff_bwd(be, saved, douts, params, drops, skips, act2=False, sdouts=None, then_drops=None):
+    """-> ([dx], [record of dx's row maxima or None]); sdouts: per head the record for dout when the kernel that produced it wrote one;
+    then_drops: per head (p, seed) of the dropout whose backward reads dx next (_ln_bwd)"""
+    n = len(saved)
+    douts, sdouts = list(douts), list(sdouts or [None] * n)
+    for i in range(n):
+        if not douts[i].is_contiguous():
+            douts[i], sdouts[i] = douts[i].contiguous(), None
+    dzs = _drop_bwd(be, douts, drops, [p[4] for p in params], [sv[5] for sv in saved] if act2 else None)
+    dz1s, calls = [], []
+    for (x, mean, rstd, xn, u, pre, sxn, su), (norm_w, norm_b, w1, b1, w2, b2), (dz2, sz), dout, sdout in zip(saved, params, dzs, douts, sdouts):
+        if dz2 is dout:                          # (no dropout, no activation: the incoming gradient itself, with its producer's record)
+            sz = sdout
+        sz = _linear_bwd_params(be, dz2, u, w2, b2, su, sz)       # (xn is None where the forward pass wrote the normalised rows as pairs only: sxn.pairs)
+        dz1 = _new(u.shape, x)                                    # (u is fp32 in front of a narrow output product, x never)
+        dz1s.append(dz1)
+        calls.append(((dz2, w2, dz1), dict(M=x.shape[0], N=u.shape[1], K=w2.shape[0], b_kcontig=False, aux=u, a_scales=sz, out_amax=_wants_amax(be, True))))   # fused ELU'(u)
+    r = _gemm_group(be, calls)
+    dxns, calls = [], []
+    for (x, mean, rstd, xn, u, pre, sxn, su), (norm_w, norm_b, w1, b1, w2, b2), dz1, (_, sz), dout, skip in zip(saved, params, dz1s, r, douts, skips):
+        sz = _linear_bwd_params(be, dz1, xn, w1, b1, sxn, sz)
+        dxn = _new(x.shape, x)
+        dxns.append(dxn)
+        calls.append(((dz1, w1, dxn), dict(M=x.shape[0], N=x.shape[1], K=u.shape[1], b_kcontig=False, res=dout if skip else None, a_scales=sz)))
+    _gemm_group(be, calls)
+    out = _ln_bwd_heads(be, dxns, [sv[0] for sv in saved], [sv[1] for sv in saved], [sv[2] for sv in saved], [p[0] for p in params], [p[1] for p in params], then_drops)
+    return [o[0] for o in out], [o[1] for o in out]
 
 
 def _first_pass(ctx) -> None:
@@ -373,7 +440,7 @@ class AttBlockFn(Function):
         if w1 is None:                              # self_interaction=False: attention + head reducer + skip only
             out, ff_saved = h3, None
         else:
-            out, ff_saved = _ff_fwd(be, h3, ln2_w, ln2_b, w1, b1, w2, b2, True, drop_p, seed2, True, infer)
+            (out,), (ff_saved,) = _ff_fwd(be, [h3], [(ln2_w, ln2_b, w1, b1, w2, b2)], [(drop_p, seed2)], [True], infer, act2=True)
         ctx.plan, ctx.cfg, ctx.scales = plan, (heads, drop_p, seed1, seed2), (sh1, sm)
         ctx.ff_saved = ff_saved
         ctx.save_for_backward(h, mean1, rstd1, h1, ft, m, alpha, ln_w, ln_b, w_fc, w_r, b_r, ln2_w, ln2_b, w1, b1, w2, b2)
@@ -390,7 +457,7 @@ class AttBlockFn(Function):
         if ctx.ff_saved is None:
             dh3, sz = _c(dout), None
         else:
-            dh3, sz = _ff_bwd(be, ctx.ff_saved, dout, ln2_w, ln2_b, w1, b1, w2, b2, True, drop_p, seed2, True)
+            (dh3,), (sz,) = _ff_bwd(be, [ctx.ff_saved], [dout], [(ln2_w, ln2_b, w1, b1, w2, b2)], [(drop_p, seed2)], [True], act2=True)
         ctx.ff_saved = None
         if drop_p > 0 and dh3.dtype == F32 and _bwd_pairs(be, N, Fd, w_r):
             dzr, sz = None, be.act_dropout_bwd(dh3, None, drop_p, seed1, None, pairs=True)
@@ -543,19 +610,180 @@ class JoinHeadsFn(Function):
         return None, None, None, None, None
 
 
-def _attention(be, qkv, s, T, nheads, like, infer, row_idx=None):
-    """-> (att or None, record of att's row maxima): the s <= 4 tokens of every tuple attend to each other.  Inference on the HIP
-    backend: the output is written in the pair format only (the record's .pairs) -- nothing but the out-projection reads it.
-    row_idx (T, s): qkv is a table and token (pos, t) reads its row row_idx[t, pos] (ProjFirstLayerFn); att stays token-level."""
-    M, Fd = qkv.shape[0] if row_idx is None else s * T, qkv.shape[1] // 3
-    if not T:
-        return _new((M, Fd), like), None
-    kw = {} if row_idx is None else dict(row_idx=row_idx, table_rows=qkv.shape[0])
-    tok = qkv if row_idx is None else qkv[:1].expand(M, -1)       # (what decides the format is the token table's shape, not the table's)
-    if infer and hasattr(be, "pairs_ok") and be.pairs_ok(tok, Fd, training=infer == 2) and 32 < Fd <= 512 and M > 32:        # (the out-projection must be able to read pairs: M, N > 32)
-        return None, be.seqattn_fwd(qkv, s, T, nheads, None, pairs=True, **kw)
-    att = _new((M, Fd), like)
-    return att, be.seqattn_fwd(qkv, s, T, nheads, att, **kw)
+class _Head(NamedTuple):
+    """one head's side of the unfused attention layer body (_layer_fwd / _layer_bwd): what differs between its callers"""
+    s: int
+    T: int
+    nheads: int
+    drop_p: float
+    seed1: int
+    seed2: int
+    qkv: torch.Tensor                          # q | k | v of the tokens -- or, with row_idx, the (atom, position) table they are read from
+    row_idx: Optional[torch.Tensor]            # (T, s): token (pos, t) reads table row row_idx[t, pos] (ProjFirstLayerFn)
+    w_o: torch.Tensor
+    b_o: Optional[torch.Tensor]
+    ff: tuple                                  # nf_w, nf_b, w1, b1, w2, b2
+    x1: Optional[torch.Tensor] = None          # forward: the normalised rows = the out-projection's residual; None: its epilogue recomputes them ...
+    res_ln: Optional[tuple] = None             # ... from (x, mean1, rstd1, n1_w, n1_b)
+    then_drop: Optional[tuple] = None          # backward: (p, seed) of the dropout whose backward the FF's LayerNorm backward writes too (_ln_bwd)
+    ln_record: bool = False                    # backward, drop_p <= 0: hand that LayerNorm backward's record of dx2 to the out-projection's products?
+
+
+def _attention(be, heads, infer):
+    """-> per head (att or None, record of att's row maxima): the s <= 4 tokens of every tuple attend to each other.  With `infer` on the HIP
+    backend the output is written in the pair format only (the record's .pairs) -- nothing but the out-projection reads it; two or more
+    heads none of which does: ONE batched launch.  With row_idx, q | k | v is a table and att stays token-level."""
+    def pairs(h, M, Fd):                       # (what decides the format is the token table's shape, not the table's; the out-projection must be able to read pairs: M, N > 32)
+        tok = h.qkv if h.row_idx is None else h.qkv[:1].expand(M, -1)
+        return infer and hasattr(be, "pairs_ok") and be.pairs_ok(tok, Fd, training=infer == 2) and 32 < Fd <= 512 and M > 32
+    dims = [(h.qkv.shape[0] if h.row_idx is None else h.s * h.T, h.qkv.shape[1] // 3) for h in heads]
+    f = getattr(be, "seqattn_batched", None)
+    if f is not None and len(heads) >= 2 and not any(h.row_idx is not None or pairs(h, M, Fd) for h, (M, Fd) in zip(heads, dims)):
+        r = f([(h.qkv, h.s, h.T, h.nheads) for h in heads], False)
+        if r is not None:
+            return r
+    out = []
+    for h, (M, Fd) in zip(heads, dims):
+        kw = {} if h.row_idx is None else dict(row_idx=h.row_idx, table_rows=h.qkv.shape[0])
+        if not h.T:
+            out.append((_new((M, Fd), h.qkv), None))
+        elif pairs(h, M, Fd):
+            out.append((None, be.seqattn_fwd(h.qkv, h.s, h.T, h.nheads, None, pairs=True, **kw)))
+        else:
+            att = _new((M, Fd), h.qkv)
+            out.append((att, be.seqattn_fwd(h.qkv, h.s, h.T, h.nheads, att, **kw)))
+    return out
+
+
+def _attention_bwd(be, heads, datts):
+    """-> per head (dqkv, record): token-level, also where q | k | v was read from a table (its rows are then summed into the table before any
+    product reads them: no maxima)"""
+    f = getattr(be, "seqattn_batched", None)
+    if f is not None and len(heads) >= 2 and all(h.row_idx is None for h in heads):
+        r = f([(h.qkv, d, h.s, h.T, h.nheads) for h, d in zip(heads, datts)], True)
+        if r is not None:
+            return r
+    out = []
+    for h, d in zip(heads, datts):
+        dqkv = _new((d.shape[0], h.qkv.shape[1]), h.qkv)
+        kw = {} if h.row_idx is None else dict(amax=False, row_idx=h.row_idx)
+        out.append((dqkv, be.seqattn_bwd(h.qkv, d, h.s, h.T, h.nheads, dqkv, **kw)))
+    return out
+
+
+def _layer_fwd(be, heads, infer):
+    """the unfused transformer layer of every head from the normalised rows and q | k | v on: a = MHA(q, k, v); x2 = drop(a Wo^T + bo) + x1;
+    out = FF(x2) (skip on the normed input) -> ([out], [att], [satt], [ff_saved]).  Empties `heads`: the references it holds (x1, a table)
+    go before the feed-forward allocates, where the caller keeps none"""
+    atts = _attention(be, heads, infer)
+    x2s, calls = [], []
+    for h, (att, satt) in zip(heads, atts):
+        M, Fd = h.s * h.T, h.qkv.shape[1] // 3
+        x2 = _new((M, Fd), h.qkv)
+        x2s.append(x2)
+        kw = dict(res=h.x1) if h.x1 is not None else dict(res=h.res_ln[0], res_ln=h.res_ln[1:])
+        calls.append(((att, h.w_o, x2), dict(M=M, N=Fd, K=Fd, bias=h.b_o, drop_p=h.drop_p, drop_seed=h.seed1, a_scales=satt, **kw)))
+    satts = _gemm_group(be, calls)
+    params, drops = [h.ff for h in heads], [(h.drop_p, h.seed2) for h in heads]
+    del calls, kw, h, heads[:]
+    outs, ff_saved = _ff_fwd(be, x2s, params, drops, [True] * len(x2s), infer)
+    return outs, [a for a, _ in atts], satts, ff_saved
+
+
+def _layer_bwd(be, heads, atts, satts, ff_saved, douts):
+    """the backward pass of _layer_fwd from dout to the attention's input -> ([dqkv], [record of dqkv], [dx2 = the skip branch's gradient]);
+    atts / satts: what the forward pass returned (att is None where the attention wrote pairs only: satt.pairs).  Empties `ff_saved`, which
+    is released as the pass goes (_first_pass)"""
+    n = len(heads)
+    dx2s, sdx2s = _ff_bwd(be, ff_saved, douts, [h.ff for h in heads], [(h.drop_p, h.seed2) for h in heads], [True] * n,
+                          then_drops=None if all(h.then_drop is None for h in heads) else [h.then_drop for h in heads])
+    del ff_saved[:]
+    dzos = _drop_bwd(be, dx2s, [(h.drop_p, h.seed1) for h in heads], [h.w_o for h in heads])
+    datts, calls = [], []
+    for h, att, satt, dx2, sdx2, (dzo, sz) in zip(heads, atts, satts, dx2s, sdx2s, dzos):
+        if h.ln_record and h.drop_p <= 0:
+            sz = sdx2
+        sz = _linear_bwd_params(be, dzo, att, h.w_o, h.b_o, satt, sz)
+        M, Fd = dx2.shape
+        datt = _new((M, Fd), h.qkv)
+        datts.append(datt)
+        calls.append(((dzo, h.w_o, datt), dict(M=M, N=Fd, K=Fd, b_kcontig=False, a_scales=sz)))
+    _gemm_group(be, calls)
+    dq = _attention_bwd(be, heads, datts)
+    return [d for d, _ in dq], [r for _, r in dq], dx2s
+
+
+def _transformer_fwd(be, xs, cfgs, params, infer):
+    """x1 = LN(x); q | k | v = x1 W_in^T + b_in; _layer_fwd -- of every head.  cfgs [(s, T, nheads, drop_p, seed1, seed2)], params [the twelve
+    tensors n1_w .. b2] -> ([out], [the six activations a head saves: x, mean1, rstd1, x1, qkv, att], [(sx1, satt)], [ff_saved])"""
+    # x1 as pairs only; the out-projection recomputes it as its residual
+    leans = [_pairs(be, x, infer) and p[0] is not None and x.shape[0] > 32 and x.shape[1] > 32 for x, p in zip(xs, params)]
+    lns = _ln_fwd_heads(be, xs, [p[0] for p in params], [p[1] for p in params], infer, [not l for l in leans])
+    heads, calls = [], []
+    for x, cfg, (n1_w, n1_b, w_in, b_in, w_o, b_o, *ff), (x1, mean1, rstd1, sx1) in zip(xs, cfgs, params, lns):
+        M, Fd = x.shape
+        qkv = _new((M, 3 * Fd), x)
+        calls.append(((x1, w_in, qkv), dict(M=M, N=3 * Fd, K=Fd, bias=b_in, a_scales=sx1)))
+        heads.append(_Head(*cfg, qkv, None, w_o, b_o, tuple(ff), x1=x1, res_ln=None if x1 is not None else (x, mean1, rstd1, n1_w, n1_b)))
+    sx1s = _gemm_group(be, calls)
+    kept = [(x, mean1, rstd1, x1, h.qkv) for x, (x1, mean1, rstd1, _), h in zip(xs, lns, heads)]
+    outs, atts, satts, ff_saved = _layer_fwd(be, heads, infer)
+    return outs, [k + (att,) for k, att in zip(kept, atts)], list(zip(sx1s, satts)), ff_saved
+
+
+def _transformer_bwd(be, saved, cfgs, scales, ff_saved, douts, then_drop, ln_record, up_drops=None):
+    """the backward pass of _transformer_fwd -> [(dx, record)].  saved: per head the eighteen tensors x, mean1, rstd1, x1, qkv, att, n1_w .. b2;
+    then_drop / ln_record: _Head; up_drops: per head (p, seed) of the dropout that produced x (the layer in front), for the last _ln_bwd"""
+    heads = [_Head(*cfg, qkv, None, w_o, b_o, tuple(ff), then_drop=(cfg[3], cfg[4]) if then_drop else None, ln_record=ln_record)
+             for cfg, (x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o, *ff) in zip(cfgs, saved)]
+    dqkvs, szs, dx2s = _layer_bwd(be, heads, [sv[5] for sv in saved], [sc[1] for sc in scales], ff_saved, douts)
+    dx1s, calls = [], []
+    for (x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, *_), (sx1, _satt), dqkv, sz, dx2 in zip(saved, scales, dqkvs, szs, dx2s):
+        M, Fd = x.shape
+        sz = _linear_bwd_params(be, dqkv, x1, w_in, b_in, sx1, sz)
+        dx1 = _new(x.shape, x)
+        dx1s.append(dx1)
+        calls.append(((dqkv, w_in, dx1), dict(M=M, N=Fd, K=3 * Fd, b_kcontig=False, res=dx2, a_scales=sz)))
+    _gemm_group(be, calls)
+    return _ln_bwd_heads(be, dx1s, [sv[0] for sv in saved], [sv[1] for sv in saved], [sv[2] for sv in saved], [sv[6] for sv in saved],
+                         [sv[7] for sv in saved], up_drops)
+
+
+# the whole layer as ONE launch (C ABI 11 grappa_writer_head_fwd / _bwd, csrc/writer_layer.hip; bf16 storage, the single-head Functions only)
+def _fused_save(be, like, s, T, M, Fd, gather=False):
+    """the by-products of the fused forward launch that the backward pass reads (training).  gather: the layer reads x1 and q | k | v of a
+    token from table rows -- no token-level copy of either, nor of the first LayerNorm's statistics, exists"""
+    # x2 is read by the LayerNorm backward only: with the fused backward kernel it is kept in that kernel's tile order
+    tiled = bool(getattr(be, "fused_writer_layer_bwd", False))
+    rows2 = be.lib.grappa_writer_head_tiles(s, T) * 64 if tiled else M
+    sv = dict(meanf=_new((M,), like, F32), rstdf=_new((M,), like, F32), att=_new((M, Fd), like), x2=_new((rows2, Fd), like), x3=_new((M, Fd), like),
+              u=_new((M, Fd), like), x2_tiled=tiled)
+    if not gather:
+        sv.update(mean1=_new((M,), like, F32), rstd1=_new((M,), like, F32), x1=_new((M, Fd), like), qkv=_new((M, 3 * Fd), like))
+    return sv
+
+
+def _fused_done(ctx, sv, out, drop_p, seed2):
+    """what a Function keeps of a fused forward launch; sv None: inference"""
+    ctx.fused_saved = sv if (sv is not None and sv["x2_tiled"]) else None          # (tiled x2 <=> the fused backward kernel runs this layer's backward)
+    ctx.ff_saved = [(sv["x2"], sv["meanf"], sv["rstdf"], sv["x3"], sv["u"], None, None, None)] if sv is not None else None
+    if drop_p > 0:
+        out._grappa_drop = (drop_p, seed2)            # (TransformerLayerFn.forward)
+    return out
+
+
+def _fused_bwd(be, sv, dout, x, cfg, params, att, x1=None, gather=None):
+    """the input-gradient chain as ONE launch (grappa_writer_head_bwd); the weight gradients = the grouped products of the pass over the operands
+    it leaves behind -> (dx, dqkv).  gather = (idx_tab, q | k | v table): the chain ends at the attention -- the token-level gradient of the
+    skip branch comes back in place of dx, and q | k | v's weight gradient is the caller's, on the table"""
+    n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2 = params
+    dx, dz2, dz1, dzo, dqkv = be.writer_layer_bwd(_c(dout), x, *cfg, sv, n1_w, n1_b, w_in, w_o, nf_w, nf_b, w1, w2, gather=gather)
+    _linear_bwd_params(be, dz2, sv["u"], w2, b2, None, None)
+    _linear_bwd_params(be, dz1, sv["x3"], w1, b1, None, None)
+    _linear_bwd_params(be, dzo, att, w_o, b_o, None, None)
+    if gather is None:
+        _linear_bwd_params(be, dqkv, x1, w_in, b_in, None, None)
+    return dx, dqkv
 
 
 class ProjGatherFn(Function):
@@ -601,50 +829,25 @@ class TransformerLayerFn(Function):
     """x1 = LN(x); a = MHA(x1); x2 = drop(a Wo^T + bo) + x1; out = FF(x2) (skip on the normed input)."""
 
     @staticmethod
-    def forward(ctx, x, s, T, nheads, drop_p, seed1, seed2, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2):
+    def forward(ctx, x, s, T, nheads, drop_p, seed1, seed2, *params):          # params: n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2
         be = get_backend()
         ctx.up_drop = getattr(x, "_grappa_drop", None)       # (p, seed) of the dropout that produced x: the layer in front (see below)
         x = _c(x)
         M, Fd = x.shape
         infer = _infer(ctx)
+        ctx.cfg = (s, T, nheads, drop_p, seed1, seed2)
         fused = getattr(be, "writer_layer_ok", None)
-        if fused is not None and T and fused(x, s, nheads, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2):
-            # the whole layer as ONE launch (C ABI 11 grappa_writer_head_fwd, csrc/writer_layer.hip); training: the tensors the backward pass
-            # below reads are by-products of that launch
+        if fused is not None and T and fused(x, s, nheads, *params):
+            # training: the tensors the backward pass below reads are by-products of the launch
             out = _new((M, Fd), x)
-            sv = None
-            if infer != 1:
-                # x2 is read by the LayerNorm backward only: with the fused backward kernel it is kept in that kernel's tile order
-                tiled = bool(getattr(be, "fused_writer_layer_bwd", False))
-                rows2 = be.lib.grappa_writer_head_tiles(s, T) * 64 if tiled else M
-                sv = dict(mean1=_new((M,), x, F32), rstd1=_new((M,), x, F32), meanf=_new((M,), x, F32), rstdf=_new((M,), x, F32),
-                          x1=_new((M, Fd), x), qkv=_new((M, 3 * Fd), x), att=_new((M, Fd), x), x2=_new((rows2, Fd), x), x3=_new((M, Fd), x),
-                          u=_new((M, Fd), x), x2_tiled=tiled)
-            be.writer_layer_fwd(x, s, T, nheads, drop_p, seed1, seed2, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, out, save=sv)
-            ctx.cfg, ctx.scales = (s, T, nheads, drop_p, seed1, seed2), (None, None)
-            ctx.fused_saved = sv if (sv is not None and sv.get("x2_tiled")) else None        # (tiled x2 <=> the fused backward kernel runs this layer's backward)
+            sv = _fused_save(be, x, s, T, M, Fd) if infer != 1 else None
+            be.writer_layer_fwd(x, s, T, nheads, drop_p, seed1, seed2, *params, out, save=sv)
+            ctx.scales = [(None, None)]
             if sv is not None:
-                ctx.ff_saved = (sv["x2"], sv["meanf"], sv["rstdf"], sv["x3"], sv["u"], None, None, None)
-                ctx.save_for_backward(x, sv["mean1"], sv["rstd1"], sv["x1"], sv["qkv"], sv["att"], n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2)
-            else:
-                ctx.ff_saved = None
-            if drop_p > 0:
-                out._grappa_drop = (drop_p, seed2)
-            return out
-        lean = _pairs(be, x, infer) and n1_w is not None and M > 32 and Fd > 32      # x1 as pairs only; the out-projection recomputes it as its residual
-        x1, mean1, rstd1, sx1 = _ln_fwd(be, x, n1_w, n1_b, infer, need_y=not lean)
-        qkv = _new((M, 3 * Fd), x)
-        sx1 = be.gemm(x1, w_in, qkv, M=M, N=3 * Fd, K=Fd, bias=b_in, a_scales=sx1)
-        att, satt = _attention(be, qkv, s, T, nheads, x, infer)
-        x2 = _new((M, Fd), x)
-        if x1 is None:
-            satt = be.gemm(att, w_o, x2, M=M, N=Fd, K=Fd, bias=b_o, drop_p=drop_p, drop_seed=seed1, res=x, res_ln=(mean1, rstd1, n1_w, n1_b), a_scales=satt)
-        else:
-            satt = be.gemm(att, w_o, x2, M=M, N=Fd, K=Fd, bias=b_o, drop_p=drop_p, drop_seed=seed1, res=x1, a_scales=satt)
-        out, ff_saved = _ff_fwd(be, x2, nf_w, nf_b, w1, b1, w2, b2, False, drop_p, seed2, True, infer)
-        ctx.cfg, ctx.scales = (s, T, nheads, drop_p, seed1, seed2), (sx1, satt)
-        ctx.ff_saved = ff_saved
-        ctx.save_for_backward(x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2)
+                ctx.save_for_backward(x, sv["mean1"], sv["rstd1"], sv["x1"], sv["qkv"], sv["att"], *params)
+            return _fused_done(ctx, sv, out, drop_p, seed2)
+        (out,), (kept,), ctx.scales, ctx.ff_saved = _transformer_fwd(be, [x], [ctx.cfg], [params], infer)
+        ctx.save_for_backward(*kept, *params)
         if drop_p > 0:
             # the layer behind reads this: its LayerNorm backward then writes the backward of THIS layer's last dropout with its result
             out._grappa_drop = (drop_p, seed2)
@@ -654,35 +857,19 @@ class TransformerLayerFn(Function):
     def backward(ctx, dout):
         _first_pass(ctx)
         be = get_backend()
-        x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2 = ctx.saved_tensors
-        s, T, nheads, drop_p, seed1, seed2 = ctx.cfg
-        M, Fd = x.shape
-        if M == 0:
+        saved = ctx.saved_tensors
+        x, x1, att = saved[0], saved[3], saved[5]
+        if x.shape[0] == 0:                                  # (an empty level; the layer-locked path never sees one)
             return (torch.zeros_like(x),) + (None,) * 18
         sv = getattr(ctx, "fused_saved", None)
         if sv is not None:
-            # the input-gradient chain as ONE launch (grappa_writer_head_bwd); the four weight gradients = the grouped products of the pass over
-            # the operands it leaves behind
             ctx.fused_saved = ctx.ff_saved = None
-            dx, dz2, dz1, dzo, dqkv = be.writer_layer_bwd(_c(dout), x, s, T, nheads, drop_p, seed1, seed2, sv, n1_w, n1_b, w_in, w_o, nf_w, nf_b, w1, w2)
-            _linear_bwd_params(be, dz2, sv["u"], w2, b2, None, None)
-            _linear_bwd_params(be, dz1, sv["x3"], w1, b1, None, None)
-            _linear_bwd_params(be, dzo, att, w_o, b_o, None, None)
-            _linear_bwd_params(be, dqkv, x1, w_in, b_in, None, None)
+            dx, _ = _fused_bwd(be, sv, dout, x, ctx.cfg, saved[6:], att, x1=x1)
             return (dx,) + (None,) * 18
-        dx2, sz = _ff_bwd(be, ctx.ff_saved, dout, nf_w, nf_b, w1, b1, w2, b2, False, drop_p, seed2, True, then_drop=(drop_p, seed1))
+        # head by head, the feed-forward's LayerNorm backward also writes the backward of the out-projection's dropout (then_drop), the first
+        # one that of the layer in front (up_drop), and at drop_p <= 0 the out-projection's products get no record for their operand
+        (dx, _), = _transformer_bwd(be, [saved], [ctx.cfg], ctx.scales, ctx.ff_saved, [dout], then_drop=True, ln_record=False, up_drops=[ctx.up_drop])
         ctx.ff_saved = None
-        dzo, sz = _drop_bwd(be, dx2, drop_p, seed1, w_o)
-        sx1, satt = ctx.scales
-        sz = _linear_bwd_params(be, dzo, att, w_o, b_o, satt, sz)           # (att is None where the attention wrote pairs only: satt.pairs)
-        datt = _new((M, Fd), x)
-        be.gemm(dzo, w_o, datt, M=M, N=Fd, K=Fd, b_kcontig=False, a_scales=sz)
-        dqkv = _new(qkv.shape, qkv)
-        sz = be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv)
-        sz = _linear_bwd_params(be, dqkv, x1, w_in, b_in, sx1, sz)
-        dx1 = _new(x.shape, x)
-        be.gemm(dqkv, w_in, dx1, M=M, N=Fd, K=3 * Fd, b_kcontig=False, res=dx2, a_scales=sz)
-        dx, _ = _ln_bwd(be, dx1, x, mean1, rstd1, n1_w, n1_b, drop=ctx.up_drop)
         return (dx,) + (None,) * 18
 
 
@@ -698,8 +885,9 @@ class ProjFirstLayerFn(Function):
     tabs = batch.BatchPlan.position_tables(level)."""
 
     @staticmethod
-    def forward(ctx, h, w, b, tabs, s, T, pe, out_dtype, nheads, drop_p, seed1, seed2, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2):
+    def forward(ctx, h, w, b, tabs, s, T, pe, out_dtype, nheads, drop_p, seed1, seed2, *params):      # params: as TransformerLayerFn's
         be = get_backend()
+        n1_w, n1_b, w_in, b_in, w_o, b_o, *ff = params
         idx_id, invid_ptr, invid_rows, idx_tab, invtab_ptr, invtab_rows = tabs
         h = _c(h)
         N, R = h.shape
@@ -710,58 +898,42 @@ class ProjFirstLayerFn(Function):
         tab = _new((s * N, Fd), a)
         be.tuple_gather_fwd(a, idx_id, s, pe, tab)                 # tab[pos*N + n] = [a[n], pe[pos]]
         infer = _infer(ctx)
-        # (training with pairs: the table's normalised rows are gathered to the tokens as the out-projection's residual, so they stay fp32)
+        # (training with pairs: the table's normalised rows are gathered to the tokens as the out-projection's residual, so they stay fp32 --
+        # where TransformerLayerFn may leave x1 to the out-projection's epilogue, this LayerNorm always writes it)
         x1_tab, mean1, rstd1, sx1 = _ln_fwd(be, tab, n1_w, n1_b, infer if infer == 1 else 0)
         qkv_tab = _new((s * N, 3 * Fd), tab)
         sx1 = be.gemm(x1_tab, w_in, qkv_tab, M=s * N, N=3 * Fd, K=Fd, bias=b_in, a_scales=sx1)
         M = s * T
         if hasattr(be, "credit"):                 # profiling: the per-token count of this product (and of its two backward products below)
             be.credit("gemm_saved", 2.0 * (M - s * N) * 3 * Fd * Fd)
+        ctx.cfg = (s, T, N, Wp, pe is not None, nheads, drop_p, seed1, seed2)
+        tables = (invid_ptr, invid_rows, invtab_ptr, invtab_rows, w, b, *params)
         fused = getattr(be, "writer_layer_ok", None)
-        if fused is not None and fused(tab, s, nheads, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2) and getattr(be, "fused_first_layer", True):
+        ctx.fused_gather = fused is not None and fused(tab, s, nheads, *params) and getattr(be, "fused_first_layer", True)
+        if ctx.fused_gather:
             # everything behind the table-level LayerNorm and q | k | v product as ONE launch: the fused writer layer in its GATHER mode takes x1 and
             # q | k | v of a token from the table rows (C ABI 11 grappa_writer_layer_desc.gather_idx) -- no token-level copy of either exists
             out = _new((M, Fd), tab)
-            sv = None
-            if infer != 1:
-                tiled = bool(getattr(be, "fused_writer_layer_bwd", False))
-                rows2 = be.lib.grappa_writer_head_tiles(s, T) * 64 if tiled else M
-                sv = dict(meanf=_new((M,), tab, F32), rstdf=_new((M,), tab, F32), att=_new((M, Fd), tab), x2=_new((rows2, Fd), tab), x3=_new((M, Fd), tab),
-                          u=_new((M, Fd), tab), x2_tiled=tiled)
-            be.writer_layer_fwd(None, s, T, nheads, drop_p, seed1, seed2, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, out, save=sv,
-                                gather=(idx_tab, x1_tab, qkv_tab))
-            ctx.cfg, ctx.scales = (s, T, N, Wp, pe is not None, nheads, drop_p, seed1, seed2), (sh, sx1, None)
-            ctx.fused_saved = sv if (sv is not None and sv["x2_tiled"]) else None
-            ctx.fused_gather = True
+            sv = _fused_save(be, tab, s, T, M, Fd, gather=True) if infer != 1 else None
+            be.writer_layer_fwd(None, s, T, nheads, drop_p, seed1, seed2, *params, out, save=sv, gather=(idx_tab, x1_tab, qkv_tab))
+            ctx.scales = (sh, sx1, None)
             if sv is not None:
-                ctx.ff_saved = (sv["x2"], sv["meanf"], sv["rstdf"], sv["x3"], sv["u"], None, None, None)
-                ctx.save_for_backward(h, a, tab, mean1, rstd1, x1_tab, qkv_tab, sv["att"], invid_ptr, invid_rows, invtab_ptr, invtab_rows,
-                                      w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, idx_tab)
-            if drop_p > 0:
-                out._grappa_drop = (drop_p, seed2)
-            return out
-        ctx.fused_gather = False
+                ctx.save_for_backward(h, a, tab, mean1, rstd1, x1_tab, qkv_tab, sv["att"], *tables, idx_tab)
+            return _fused_done(ctx, sv, out, drop_p, seed2)
         # q | k | v stay on the table where the attention kernels read a token's row through idx_tab (HipBackend.first_layer_indexed, fp32):
         # no token-level copy is written, and the backward pass keeps the table
         ctx.indexed = indexed = bool(getattr(be, "first_layer_indexed", False)) and qkv_tab.dtype == F32 and T > 0
         x1 = _new((M, Fd), tab)
         be.tuple_gather_fwd(x1_tab, idx_tab, s, None, x1)          # x1[pos*T + t] = x1_tab[pos*N + idx[t, pos]]
-        if indexed:
-            qkv = qkv_tab
-            att, satt = _attention(be, qkv_tab, s, T, nheads, tab, infer, row_idx=idx_tab)
-        else:
+        qkv = qkv_tab
+        if not indexed:
             qkv = _new((M, 3 * Fd), tab)
             be.tuple_gather_fwd(qkv_tab, idx_tab, s, None, qkv)
-            att, satt = _attention(be, qkv, s, T, nheads, tab, infer)
-        del qkv_tab
-        x2 = _new((M, Fd), tab)
-        satt = be.gemm(att, w_o, x2, M=M, N=Fd, K=Fd, bias=b_o, drop_p=drop_p, drop_seed=seed1, res=x1, a_scales=satt)
-        del x1
-        out, ff_saved = _ff_fwd(be, x2, nf_w, nf_b, w1, b1, w2, b2, False, drop_p, seed2, True, infer)
-        ctx.cfg, ctx.scales = (s, T, N, Wp, pe is not None, nheads, drop_p, seed1, seed2), (sh, sx1, satt)
-        ctx.ff_saved = ff_saved
-        ctx.save_for_backward(h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows,
-                              w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, *((idx_tab,) if indexed else ()))
+        heads = [_Head(s, T, nheads, drop_p, seed1, seed2, qkv, idx_tab if indexed else None, w_o, b_o, tuple(ff), x1=x1)]
+        del qkv_tab, x1
+        (out,), (att,), (satt,), ctx.ff_saved = _layer_fwd(be, heads, infer)
+        ctx.scales = (sh, sx1, satt)
+        ctx.save_for_backward(h, a, tab, mean1, rstd1, x1_tab, qkv, att, *tables, *((idx_tab,) if indexed else ()))
         if drop_p > 0:
             out._grappa_drop = (drop_p, seed2)            # (TransformerLayerFn.forward)
         return out
@@ -770,27 +942,19 @@ class ProjFirstLayerFn(Function):
     def backward(ctx, dout):
         _first_pass(ctx)
         be = get_backend()
-        idx_tab = None
-        if getattr(ctx, "fused_gather", False) or getattr(ctx, "indexed", False):
-            (h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows,
-             w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2, idx_tab) = ctx.saved_tensors      # (qkv: the TABLE here)
-        else:
-            (h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows,
-             w, b, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2) = ctx.saved_tensors
+        # (qkv: the TABLE where idx_tab was saved -- the fused gather mode, or the indexed attention)
+        h, a, tab, mean1, rstd1, x1_tab, qkv, att, invid_ptr, invid_rows, invtab_ptr, invtab_rows, w, b, *rest = ctx.saved_tensors
+        params, idx_tab = rest[:12], (rest[12] if len(rest) > 12 else None)
+        n1_w, n1_b, w_in, b_in, w_o, b_o, *ff = params
         s, T, N, Wp, has_pe, nheads, drop_p, seed1, seed2 = ctx.cfg
         sh, sx1, satt = ctx.scales
         M, Fd = s * T, qkv.shape[1] // 3
         R = h.shape[1]
         sv = getattr(ctx, "fused_saved", None)
         if idx_tab is not None and sv is not None:
-            # the input-gradient chain down to the attention as ONE launch (grappa_writer_head_bwd in its gather mode): the token-level gradients of
-            # q | k | v and of the skip branch come back, the table-level part below is unchanged
+            # down to the attention: the token-level gradients of q | k | v and of the skip branch come back, the table-level part below is unchanged
             ctx.fused_saved = ctx.ff_saved = None
-            dx2, dz2, dz1, dzo, dqkv = be.writer_layer_bwd(_c(dout), None, s, T, nheads, drop_p, seed1, seed2, sv, n1_w, n1_b, w_in, w_o, nf_w, nf_b, w1, w2,
-                                                           gather=(idx_tab, qkv))
-            _linear_bwd_params(be, dz2, sv["u"], w2, b2, None, None)
-            _linear_bwd_params(be, dz1, sv["x3"], w1, b1, None, None)
-            _linear_bwd_params(be, dzo, att, w_o, b_o, None, None)
+            dx2, dqkv = _fused_bwd(be, sv, dout, None, (s, T, nheads, drop_p, seed1, seed2), params, att, gather=(idx_tab, qkv))
         else:
             row_idx = None
             if idx_tab is not None and getattr(be, "first_layer_indexed", False) and qkv.dtype == F32:
@@ -799,17 +963,10 @@ class ProjFirstLayerFn(Function):
                 qkv_tok = _new((M, 3 * Fd), tab)
                 be.tuple_gather_fwd(qkv, idx_tab, s, None, qkv_tok)
                 qkv = qkv_tok
-            dx2, sz = _ff_bwd(be, ctx.ff_saved, dout, nf_w, nf_b, w1, b1, w2, b2, False, drop_p, seed2, True, then_drop=(drop_p, seed1))
+            # (then_drop / ln_record: as TransformerLayerFn.backward)
+            head = _Head(s, T, nheads, drop_p, seed1, seed2, qkv, row_idx, w_o, b_o, tuple(ff), then_drop=(drop_p, seed1))
+            (dqkv,), _, (dx2,) = _layer_bwd(be, [head], [att], [satt], ctx.ff_saved, [dout])
             ctx.ff_saved = None
-            dzo, sz = _drop_bwd(be, dx2, drop_p, seed1, w_o)
-            sz = _linear_bwd_params(be, dzo, att, w_o, b_o, satt, sz)
-            datt = _new((M, Fd), qkv)
-            be.gemm(dzo, w_o, datt, M=M, N=Fd, K=Fd, b_kcontig=False, a_scales=sz)
-            dqkv = _new((M, 3 * Fd), qkv)
-            if row_idx is not None:
-                be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv, amax=False, row_idx=row_idx)
-            else:
-                be.seqattn_bwd(qkv, datt, s, T, nheads, dqkv)                  # (its rows are summed into the table before any product reads them)
         # token gradients -> table rows (pos*N + n): the q, k, v gradients and the skip branch of x1
         dqkv_tab, dres_tab = _new((s * N, 3 * Fd), qkv), _new((s * N, Fd), qkv)
         if getattr(be, "first_layer_indexed", False) and dqkv.dtype == F32:
@@ -836,47 +993,68 @@ class ProjFirstLayerFn(Function):
         return (dh,) + (None,) * 23
 
 
+def _sym_fwd(be, cfgs, xs, layers, infer):
+    """o[p*T+t] = mlp(concat_j x[perm_p[j]*T + t]) for every permutation p, of every head.  cfgs [(s, T, perms, n_layers)], layers: per head
+    and layer (norm_w, norm_b, w1, b1, w2, b2); layer li runs for the heads that are that deep -> ([o], per head its layers' saved)"""
+    n = len(cfgs)
+    cur, saved = [], [[] for _ in range(n)]
+    for (s, T, perms, nl), x in zip(cfgs, xs):
+        z = _new((len(perms) * T, s * x.shape[1]), x)
+        if T:
+            be.perm_concat_fwd(x, s, T, perms, z)
+        cur.append(z)
+    for li in range(max(c[3] for c in cfgs)):
+        act = [i for i in range(n) if li < cfgs[i][3]]
+        outs, sv = _ff_fwd(be, [cur[i] for i in act], [layers[i][li] for i in act], [(0.0, 0)] * len(act),
+                           [(li != 0) and (li != cfgs[i][3] - 1) for i in act], infer)
+        for j, i in enumerate(act):
+            cur[i] = outs[j]
+            saved[i].append(sv[j])
+    return cur, saved
+
+
+def _sym_bwd(be, cfgs, saved, layers, douts, xmeta):
+    """-> [dx]; xmeta: per head the shape and element type of x"""
+    n = len(cfgs)
+    g, sg = [_c(d) for d in douts], [None] * n
+    for li in reversed(range(max(c[3] for c in cfgs))):
+        act = [i for i in range(n) if li < cfgs[i][3]]
+        dxs, sdx = _ff_bwd(be, [saved[i][li] for i in act], [g[i] for i in act], [layers[i][li] for i in act], [(0.0, 0)] * len(act),
+                           [(li != 0) and (li != cfgs[i][3] - 1) for i in act], sdouts=[sg[i] for i in act])
+        for j, i in enumerate(act):
+            g[i], sg[i] = dxs[j], sdx[j]
+    out = []
+    for (s, T, perms, nl), gi, (shape, dtype) in zip(cfgs, g, xmeta):
+        dx = torch.empty(shape, dtype=dtype, device=gi.device)
+        be.perm_concat_bwd(gi, s, T, perms, dx)
+        out.append(dx)
+    return out
+
+
+def _chunks(t, n):
+    return [t[i:i + n] for i in range(0, len(t), n)]
+
+
 class SymmetriserFn(Function):
     """o[p*T+t] = mlp(concat_j x[perm_p[j]*T + t]) for every permutation p (the sum over p is taken by ParamOutFn).
-    layers: list of (norm_w, norm_b, w1, b1, w2, b2, skip)."""
+    params: per layer norm_w, norm_b, w1, b1, w2, b2."""
 
     @staticmethod
     def forward(ctx, x, s, T, perms, n_layers, *params):
-        be = get_backend()
         x = _c(x)
-        Fd = x.shape[1]
-        P = len(perms)
-        layers = [params[6 * i:6 * i + 6] for i in range(n_layers)]
-        z = _new((P * T, s * Fd), x)
-        if T:
-            be.perm_concat_fwd(x, s, T, perms, z)
-        saved = []
-        cur = z
-        for i, (nw, nb, w1, b1, w2, b2) in enumerate(layers):
-            skip = (i != 0) and (i != n_layers - 1)
-            cur, sv = _ff_fwd(be, cur, nw, nb, w1, b1, w2, b2, False, 0.0, 0, skip, _infer(ctx))
-            saved.append(sv)
-        ctx.cfg = (s, T, perms, n_layers, tuple(x.shape), x.dtype)
-        ctx.saved_layers = saved
-        ctx.layers = layers
-        return cur
+        ctx.cfg, ctx.layers, ctx.xmeta = (s, T, perms, n_layers), _chunks(params, 6), (tuple(x.shape), x.dtype)
+        (out,), (ctx.saved_layers,) = _sym_fwd(get_backend(), [ctx.cfg], [x], [ctx.layers], _infer(ctx))
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         _first_pass(ctx)
-        be = get_backend()
-        s, T, perms, n_layers, xshape, xdtype = ctx.cfg
+        s, T, perms, n_layers = ctx.cfg
         nret = 5 + 6 * n_layers
-        if T == 0:
-            return (torch.zeros(xshape, dtype=xdtype, device=dout.device),) + (None,) * (nret - 1)
-        g, sg = _c(dout), None
-        for i in reversed(range(n_layers)):
-            nw, nb, w1, b1, w2, b2 = ctx.layers[i]
-            skip = (i != 0) and (i != n_layers - 1)
-            g, sg = _ff_bwd(be, ctx.saved_layers[i], g, nw, nb, w1, b1, w2, b2, False, 0.0, 0, skip, sg)
+        if T == 0:                                           # (an empty level; the layer-locked path never sees one)
+            return (torch.zeros(ctx.xmeta[0], dtype=ctx.xmeta[1], device=dout.device),) + (None,) * (nret - 1)
+        dx, = _sym_bwd(get_backend(), [ctx.cfg], [ctx.saved_layers], [ctx.layers], [dout], [ctx.xmeta])
         ctx.saved_layers = None
-        dx = torch.empty(xshape, dtype=xdtype, device=dout.device)
-        be.perm_concat_bwd(g, s, T, perms, dx)
         return (dx,) + (None,) * (nret - 1)
 
 
@@ -999,161 +1177,11 @@ class MolwiseLossFn(Function):
 
 
 # ------------------------------------------------------------------------------------------------
-# The writer heads layer-locked (round 4).  The four heads (bond / angle / proper / improper) have the same architecture and read the
-# same atom embedding; head by head, each of their products leaves most of the chip idle at small batches (batch 32: 44 .. 176
-# workgroups of one tile time each on 256 CUs) and costs a launch.  Here one autograd node runs ONE transformer layer (or the
-# symmetrisers) of all heads: row-wise kernels head by head, every product of the layer as ONE grouped launch (backend.gemm_group).
-# Same arithmetic per head as TransformerLayerFn / SymmetriserFn above (same kernels, same K cuts: the same bits).
-def _gemm_group(be, calls):
-    f = getattr(be, "gemm_group", None)
-    if f is None or len(calls) < 2:
-        return [be.gemm(*a, **k) for a, k in calls]
-    return f(calls)
-
-
-def _ln_fwd_multi(be, xs, ws, bs, infer, need_y):
-    """_ln_fwd for several heads: one batched launch where the backend has it and no head writes the pair format"""
-    f = getattr(be, "layernorm_fwd_batched", None)
-    if f is not None and len(xs) >= 2 and all(w is not None for w in ws) and not any(_pairs(be, x, infer) for x in xs):
-        r = f(xs, ws, bs)
-        if r is not None:
-            return r
-    return [_ln_fwd(be, x, w, b, infer, need_y=ny) for x, w, b, ny in zip(xs, ws, bs, need_y)]
-
-
-def _ln_bwd_multi(be, dys, xs, means, rstds, ws, bs):
-    f = getattr(be, "layernorm_bwd_batched", None)
-    if f is not None and len(xs) >= 2 and all(w is not None and w.requires_grad and b.requires_grad for w, b in zip(ws, bs)):
-        r = f([(dy, x, m, r_, w, _pgrad(w), _pgrad(b)) for dy, x, m, r_, w, b in zip(dys, xs, means, rstds, ws, bs)])
-        if r is not None:
-            return r
-    return [_ln_bwd(be, dy, x, m, r_, w, b) for dy, x, m, r_, w, b in zip(dys, xs, means, rstds, ws, bs)]
-
-
-def _drop_bwd_multi(be, dys, drops, ws, ys=None):
-    """dropout (and ELU') backward of several heads -> [(dz or None, record)]; ys: the saved ELU outputs (act2) or None"""
-    n = len(dys)
-    ys = ys or [None] * n
-    f = getattr(be, "act_dropout_bwd_batched", None)
-    plain = all((p > 0 or y is not None) for (p, _s), y in zip(drops, ys)) and not any(dy.dtype == F32 and _bwd_pairs(be, dy.shape[0], dy.shape[1], w) for dy, w in zip(dys, ws))
-    if f is not None and n >= 2 and plain:
-        r = f([(dy, y, p, sd) for dy, y, (p, sd) in zip(dys, ys, drops)])
-        if r is not None:
-            return r
-    out = []
-    for dy, (p, sd), w, y in zip(dys, drops, ws, ys):
-        if p <= 0 and y is None:
-            out.append((dy, None))
-        elif dy.dtype == F32 and _bwd_pairs(be, dy.shape[0], dy.shape[1], w):
-            out.append((None, be.act_dropout_bwd(dy, y, p, sd, None, pairs=True)))
-        else:
-            dz = _new(dy.shape, dy)
-            out.append((dz, be.act_dropout_bwd(dy, y, p, sd, dz)))
-    return out
-
-
-def _attention_multi(be, qkvs, cfgs, likes, infer):
-    """_attention for several heads (cfgs: (s, T, nheads)): one batched launch unless a head writes the pair format"""
-    f = getattr(be, "seqattn_batched", None)
-    def wants_pairs(qkv):
-        Fd = qkv.shape[1] // 3
-        return infer and hasattr(be, "pairs_ok") and be.pairs_ok(qkv, Fd, training=infer == 2) and 32 < Fd <= 512 and qkv.shape[0] > 32
-    if f is not None and len(qkvs) >= 2 and not any(wants_pairs(q) for q in qkvs):
-        r = f([(q, s, T, nh) for q, (s, T, nh) in zip(qkvs, cfgs)], False)
-        if r is not None:
-            return r
-    return [_attention(be, q, s, T, nh, like, infer) for q, (s, T, nh), like in zip(qkvs, cfgs, likes)]
-
-
-def _attention_bwd_multi(be, qkvs, datts, cfgs):
-    f = getattr(be, "seqattn_batched", None)
-    if f is not None and len(qkvs) >= 2:
-        r = f([(q, d, s, T, nh) for q, d, (s, T, nh) in zip(qkvs, datts, cfgs)], True)
-        if r is not None:
-            return r
-    out = []
-    for q, d, (s, T, nh) in zip(qkvs, datts, cfgs):
-        dqkv = _new(q.shape, q)
-        out.append((dqkv, be.seqattn_bwd(q, d, s, T, nh, dqkv)))
-    return out
-
-
-def _ff_fwd_multi(be, xs, params, act2, drops, skip, infer):
-    """_ff_fwd for several heads at once: xs [x], params [(norm_w, norm_b, w1, b1, w2, b2)], drops [(drop_p, seed)], skip [bool] -> ([out], [saved])"""
-    n = len(xs)
-    pre1, calls1 = [], []
-    leans = []
-    for x, (norm_w, norm_b, w1, b1, w2, b2), sk in zip(xs, params, skip):
-        leans.append(_pairs(be, x, infer) and norm_w is not None and w1.shape[0] > 32 and x.shape[0] > 32 and (not sk or not w2.shape[0] <= 32))
-    lns = _ln_fwd_multi(be, xs, [p[0] for p in params], [p[1] for p in params], infer, [not l for l in leans])
-    for x, (norm_w, norm_b, w1, b1, w2, b2), sk, (xn, mean, rstd, sxn) in zip(xs, params, skip, lns):
-        M, Hd, Nout = x.shape[0], w1.shape[0], w2.shape[0]
-        narrow = Nout <= 32
-        u = _new((M, Hd), x, F32 if narrow else None)
-        pre1.append((xn, mean, rstd, u, narrow))
-        calls1.append(((xn, w1, u), dict(M=M, N=Hd, K=x.shape[1], bias=b1, act=ELU, a_scales=sxn, out_amax=_wants_amax(be, False))))
-    r1 = _gemm_group(be, calls1)
-    outs, saved, calls2 = [], [], []
-    for i in range(n):
-        x, (norm_w, norm_b, w1, b1, w2, b2), (drop_p, seed) = xs[i], params[i], drops[i]
-        xn, mean, rstd, u, narrow = pre1[i]
-        sxn, su = r1[i]
-        M, Hd, Nout = x.shape[0], w1.shape[0], w2.shape[0]
-        out = _new((M, Nout), x, F32 if narrow else None)
-        ln_res = (mean, rstd, norm_w, norm_b) if (skip[i] and xn is None) else None
-        pre = None
-        if act2:
-            pre = _new((M, Nout), x)
-            kw = dict(res=x, res_ln=ln_res) if ln_res else dict(res=xn if skip[i] else None)
-            calls2.append(((u, w2, pre), dict(M=M, N=Nout, K=Hd, bias=b2, act=ELU, drop_p=drop_p, drop_seed=seed, out2=out, a_scales=su, **kw)))
-        elif ln_res:
-            calls2.append(((u, w2, out), dict(M=M, N=Nout, K=Hd, bias=b2, drop_p=drop_p, drop_seed=seed, res=x, res_ln=ln_res, a_scales=su)))
-        else:
-            calls2.append(((u, w2, out), dict(M=M, N=Nout, K=Hd, bias=b2, drop_p=drop_p, drop_seed=seed, res=xn if skip[i] else None, a_scales=su)))
-        outs.append(out)
-        saved.append([x, mean, rstd, xn, u, pre, sxn, None])
-    r2 = _gemm_group(be, calls2)
-    for sv, su in zip(saved, r2):
-        sv[7] = su
-    return outs, [tuple(sv) for sv in saved]
-
-
-def _ff_bwd_multi(be, saved, douts, params, act2, drops, skip, sdouts=None):
-    """_ff_bwd for several heads at once -> ([dx], [record of dx or None])"""
-    n = len(saved)
-    sdouts = sdouts or [None] * n
-    dz2s, szs, calls = [], [], []
-    douts, sdouts = list(douts), list(sdouts)
-    for i in range(n):
-        if not douts[i].is_contiguous():
-            douts[i], sdouts[i] = douts[i].contiguous(), None
-    dzs = _drop_bwd_multi(be, douts, drops, [p[4] for p in params], [sv[5] for sv in saved] if act2 else None)
-    for i in range(n):
-        x, mean, rstd, xn, u, pre, sxn, su = saved[i]
-        norm_w, norm_b, w1, b1, w2, b2 = params[i]
-        M = x.shape[0]
-        dz2, sz = dzs[i]
-        if dz2 is douts[i]:                      # (no dropout, no activation: the incoming gradient itself, with its producer's record)
-            sz = sdouts[i]
-        sz = _linear_bwd_params(be, dz2, u, w2, b2, su, sz)
-        dz1 = _new(u.shape, x)
-        dz2s.append(dz1)
-        calls.append(((dz2, w2, dz1), dict(M=M, N=u.shape[1], K=w2.shape[0], b_kcontig=False, aux=u, a_scales=sz, out_amax=_wants_amax(be, True))))
-    r = _gemm_group(be, calls)
-    calls, dxns = [], []
-    for i in range(n):
-        x, mean, rstd, xn, u, pre, sxn, su = saved[i]
-        norm_w, norm_b, w1, b1, w2, b2 = params[i]
-        dz1 = dz2s[i]
-        sz = _linear_bwd_params(be, dz1, xn, w1, b1, sxn, r[i][1])
-        dxn = _new(x.shape, x)
-        dxns.append(dxn)
-        calls.append(((dz1, w1, dxn), dict(M=x.shape[0], N=x.shape[1], K=u.shape[1], b_kcontig=False, res=douts[i] if skip[i] else None, a_scales=sz)))
-    _gemm_group(be, calls)
-    out = _ln_bwd_multi(be, dxns, [sv[0] for sv in saved], [sv[1] for sv in saved], [sv[2] for sv in saved], [p[0] for p in params], [p[1] for p in params])
-    return [o[0] for o in out], [o[1] for o in out]
-
-
+# The writer heads layer-locked (round 4): the list functions above over all heads that have a layer li, one autograd node per layer.  What these
+# nodes do NOT do that the head-by-head Functions do (each kept as it was, to be measured on its own): `infer` looks at every head's x; no
+# LayerNorm backward writes a dropout backward with its result (no then_drop / up_drop, no `_grappa_drop` on the outputs); at drop_p <= 0 the
+# out-projection's backward products get the LayerNorm backward's record of their operand (ln_record); an empty level never comes here
+# (model._forward_merged sends it head by head); the fused layer is not reachable (merged heads are off in the bf16 storage configuration).
 _NP_LAYER = 13        # tensors per head of MultiTransformerLayerFn: x, n1_w, n1_b, w_in, b_in, w_o, b_o, nf_w, nf_b, w1, b1, w2, b2
 
 
@@ -1162,86 +1190,20 @@ class MultiTransformerLayerFn(Function):
 
     @staticmethod
     def forward(ctx, cfgs, *t):
-        be = get_backend()
-        n = len(cfgs)
-        heads = [t[_NP_LAYER * i:_NP_LAYER * (i + 1)] for i in range(n)]
-        infer = 1 if (_INFERENCE["on"] and not any(ctx.needs_input_grad[1 + _NP_LAYER * i] for i in range(n))) else \
-            (2 if getattr(be, "training_pairs", False) else 0)
-        xs = [_c(h[0]) for h in heads]
-        st, calls = [], []
-        leans = [_pairs(be, x, infer) and h[1] is not None and x.shape[0] > 32 and x.shape[1] > 32 for x, h in zip(xs, heads)]
-        lns = _ln_fwd_multi(be, xs, [h[1] for h in heads], [h[2] for h in heads], infer, [not l for l in leans])
-        for x, (_, n1_w, n1_b, w_in, b_in, *_r), (x1, mean1, rstd1, sx1) in zip(xs, heads, lns):
-            M, Fd = x.shape
-            qkv = _new((M, 3 * Fd), x)
-            st.append([x1, mean1, rstd1, qkv])
-            calls.append(((x1, w_in, qkv), dict(M=M, N=3 * Fd, K=Fd, bias=b_in, a_scales=sx1)))
-        sx1s = _gemm_group(be, calls)
-        calls, x2s, atts = [], [], []
-        att_r = _attention_multi(be, [q[3] for q in st], [(c[0], c[1], c[2]) for c in cfgs], xs, infer)
-        for i, (x, hp) in enumerate(zip(xs, heads)):
-            s, T, nheads, drop_p, seed1, seed2 = cfgs[i]
-            _, n1_w, n1_b, w_in, b_in, w_o, b_o = hp[:7]
-            x1, mean1, rstd1, qkv = st[i]
-            M, Fd = x.shape
-            att, satt = att_r[i]
-            x2 = _new((M, Fd), x)
-            kw = dict(res=x, res_ln=(mean1, rstd1, n1_w, n1_b)) if x1 is None else dict(res=x1)
-            calls.append(((att, w_o, x2), dict(M=M, N=Fd, K=Fd, bias=b_o, drop_p=drop_p, drop_seed=seed1, a_scales=satt, **kw)))
-            x2s.append(x2)
-            atts.append(att)
-        satts = _gemm_group(be, calls)
-        outs, ff_saved = _ff_fwd_multi(be, x2s, [hp[7:13] for hp in heads], False, [(c[3], c[5]) for c in cfgs], [True] * n, infer)
-        ctx.cfgs, ctx.scales, ctx.ff_saved, ctx.n = cfgs, list(zip(sx1s, satts)), ff_saved, n
-        flat = []
-        for i in range(n):
-            flat += [xs[i], st[i][1], st[i][2], st[i][0], st[i][3], atts[i]] + list(heads[i][1:])
-        ctx.save_for_backward(*flat)
+        heads = _chunks(t, _NP_LAYER)
+        ctx.cfgs, params = cfgs, [h[1:] for h in heads]
+        infer = _infer(ctx, range(1, len(t), _NP_LAYER))      # (every head's x)
+        outs, kept, ctx.scales, ctx.ff_saved = _transformer_fwd(get_backend(), [_c(h[0]) for h in heads], cfgs, params, infer)
+        ctx.save_for_backward(*[a for k, p in zip(kept, params) for a in k + p])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *douts):
         _first_pass(ctx)
-        be = get_backend()
-        n, cfgs = ctx.n, ctx.cfgs
-        sv = ctx.saved_tensors
-        per = 6 + (_NP_LAYER - 1)
-        H = [sv[per * i:per * (i + 1)] for i in range(n)]
-        params = [h[6 + 6:6 + 12] for h in H]                       # nf_w, nf_b, w1, b1, w2, b2
-        dx2s, szs = _ff_bwd_multi(be, ctx.ff_saved, douts, params, False, [(c[3], c[5]) for c in cfgs], [True] * n)
+        # (no LayerNorm backward writes a dropout backward here, and at drop_p <= 0 the out-projection's products get the record of dx2: see above)
+        dxs = _transformer_bwd(get_backend(), _chunks(ctx.saved_tensors, 6 + _NP_LAYER - 1), ctx.cfgs, ctx.scales, ctx.ff_saved, douts, then_drop=False, ln_record=True)
         ctx.ff_saved = None
-        calls, datts = [], []
-        dzos = _drop_bwd_multi(be, dx2s, [(c[3], c[4]) for c in cfgs], [H[i][10] for i in range(n)])
-        for i in range(n):
-            x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o = H[i][:12]
-            s, T, nheads, drop_p, seed1, seed2 = cfgs[i]
-            M, Fd = x.shape
-            dzo, sz = dzos[i]
-            sz = sz if drop_p > 0 else szs[i]
-            sx1, satt = ctx.scales[i]
-            sz = _linear_bwd_params(be, dzo, att, w_o, b_o, satt, sz)
-            datt = _new((M, Fd), x)
-            datts.append(datt)
-            calls.append(((dzo, w_o, datt), dict(M=M, N=Fd, K=Fd, b_kcontig=False, a_scales=sz)))
-        _gemm_group(be, calls)
-        calls, dx1s = [], []
-        dq = _attention_bwd_multi(be, [H[i][4] for i in range(n)], datts, [(c[0], c[1], c[2]) for c in cfgs])
-        for i in range(n):
-            x, mean1, rstd1, x1, qkv, att, n1_w, n1_b, w_in, b_in, w_o, b_o = H[i][:12]
-            s, T, nheads, drop_p, seed1, seed2 = cfgs[i]
-            M, Fd = x.shape
-            dqkv, sz = dq[i]
-            sz = _linear_bwd_params(be, dqkv, x1, w_in, b_in, ctx.scales[i][0], sz)
-            dx1 = _new(x.shape, x)
-            dx1s.append(dx1)
-            calls.append(((dqkv, w_in, dx1), dict(M=M, N=Fd, K=3 * Fd, b_kcontig=False, res=dx2s[i], a_scales=sz)))
-        _gemm_group(be, calls)
-        grads = [None]
-        dxs = _ln_bwd_multi(be, dx1s, [H[i][0] for i in range(n)], [H[i][1] for i in range(n)], [H[i][2] for i in range(n)],
-                            [H[i][6] for i in range(n)], [H[i][7] for i in range(n)])
-        for i in range(n):
-            grads += [dxs[i][0]] + [None] * (_NP_LAYER - 1)
-        return tuple(grads)
+        return (None,) + tuple(g for dx, _ in dxs for g in (dx,) + (None,) * (_NP_LAYER - 1))
 
 
 class MultiSymmetriserFn(Function):
@@ -1249,48 +1211,20 @@ class MultiSymmetriserFn(Function):
 
     @staticmethod
     def forward(ctx, cfgs, *t):
-        be = get_backend()
-        n = len(cfgs)
-        heads, pos, xpos = [], 0, []
+        xpos, pos = [], 0
         for (s, T, perms, nl) in cfgs:
             xpos.append(pos)
-            heads.append((t[pos], [t[pos + 1 + 6 * i:pos + 7 + 6 * i] for i in range(nl)]))
             pos += 1 + 6 * nl
-        infer = 1 if (_INFERENCE["on"] and not any(ctx.needs_input_grad[1 + p] for p in xpos)) else (2 if getattr(be, "training_pairs", False) else 0)
-        cur, saved = [], [[] for _ in range(n)]
-        for (s, T, perms, nl), (x, layers) in zip(cfgs, heads):
-            x = _c(x)
-            z = _new((len(perms) * T, s * x.shape[1]), x)
-            be.perm_concat_fwd(x, s, T, perms, z)
-            cur.append(z)
-        for li in range(max(c[3] for c in cfgs)):
-            act = [i for i in range(n) if li < cfgs[i][3]]
-            outs, sv = _ff_fwd_multi(be, [cur[i] for i in act], [heads[i][1][li] for i in act], False, [(0.0, 0)] * len(act),
-                                     [(li != 0) and (li != cfgs[i][3] - 1) for i in act], infer)
-            for j, i in enumerate(act):
-                cur[i] = outs[j]
-                saved[i].append(sv[j])
-        ctx.cfgs, ctx.saved_layers, ctx.layers = cfgs, saved, [h[1] for h in heads]
-        ctx.xmeta = [(tuple(h[0].shape), h[0].dtype) for h in heads]
-        return tuple(cur)
+        xs = [_c(t[p]) for p in xpos]
+        ctx.cfgs, ctx.layers = cfgs, [_chunks(t[p + 1:p + 1 + 6 * c[3]], 6) for p, c in zip(xpos, cfgs)]
+        ctx.xmeta = [(tuple(x.shape), x.dtype) for x in xs]
+        outs, ctx.saved_layers = _sym_fwd(get_backend(), cfgs, xs, ctx.layers, _infer(ctx, [1 + p for p in xpos]))      # (every head's x)
+        return tuple(outs)
 
     @staticmethod
     def backward(ctx, *douts):
         _first_pass(ctx)
-        be = get_backend()
-        cfgs, n = ctx.cfgs, len(ctx.cfgs)
-        g, sg = [_c(d) for d in douts], [None] * n
-        for li in reversed(range(max(c[3] for c in cfgs))):
-            act = [i for i in range(n) if li < cfgs[i][3]]
-            dxs, sdx = _ff_bwd_multi(be, [ctx.saved_layers[i][li] for i in act], [g[i] for i in act], [ctx.layers[i][li] for i in act], False,
-                                     [(0.0, 0)] * len(act), [(li != 0) and (li != cfgs[i][3] - 1) for i in act], [sg[i] for i in act])
-            for j, i in enumerate(act):
-                g[i], sg[i] = dxs[j], sdx[j]
+        dxs = _sym_bwd(get_backend(), ctx.cfgs, ctx.saved_layers, ctx.layers, douts, ctx.xmeta)
         ctx.saved_layers = None
-        grads = [None]
-        for i, (s, T, perms, nl) in enumerate(cfgs):
-            shape, dtype = ctx.xmeta[i]
-            dx = torch.empty(shape, dtype=dtype, device=g[i].device)
-            be.perm_concat_bwd(g[i], s, T, perms, dx)
-            grads += [dx] + [None] * (6 * nl)
-        return tuple(grads)
+        return (None,) + tuple(g for dx, (s, T, perms, nl) in zip(dxs, ctx.cfgs) for g in (dx,) + (None,) * (6 * nl))
+
