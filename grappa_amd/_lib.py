@@ -92,6 +92,12 @@ class RelaxOpts(C.Structure):
                 ("n_min", C.c_int), ("f_inc", C.c_float), ("f_dec", C.c_float), ("alpha_start", C.c_float), ("f_alpha", C.c_float)]
 
 
+class RelaxRestr(C.Structure):
+    """grappa_relax_restr (additions to ABI 11): frozen atoms, tethers and dihedral restraints of the fused FIRE minimiser, per call"""
+    _fields_ = [("frozen", C.c_void_p), ("pos_k", C.c_void_p), ("dih_molptr", C.c_void_p), ("dih_atoms", C.c_void_p), ("dih_k", C.c_void_p),
+                ("dih_target", C.c_void_p), ("R", C.c_int)]
+
+
 class MdOpts(C.Structure):
     """grappa_md_opts (additions to ABI 11): the options of the fused Langevin dynamics, per call"""
     _fields_ = [("dt", C.c_float), ("temperature", C.c_float), ("friction", C.c_float), ("init_temperature", C.c_float),
@@ -227,6 +233,9 @@ SIGNATURES = {
     # relaxation under the full force field (additions to ABI 11)
     "grappa_relax_max_atoms": (_i, []),
     "grappa_relax_fire_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_relax_max_dihedrals": (_i, []),
+    "grappa_relax_fire_restr_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), C.POINTER(RelaxRestr), _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
     # the stepwise minimiser for molecules of any size (additions to ABI 11)
     "grappa_relax_steps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "grappa_relax_steps_init_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz, _vp]),
@@ -312,6 +321,11 @@ def nonbonded_iblock() -> int:
 def relax_max_atoms() -> int:
     """atoms per molecule the fused minimiser takes at most (grappa_relax_max_atoms of the loaded library)"""
     return int(load().grappa_relax_max_atoms())
+
+
+def relax_max_dihedrals() -> int:
+    """restrained dihedrals per molecule the fused minimiser takes at most (grappa_relax_max_dihedrals of the loaded library)"""
+    return int(load().grappa_relax_max_dihedrals())
 
 
 def md_philox(key: int, c0: int, c1: int, c2: int, c3: int):

@@ -201,7 +201,7 @@ class MMBackend:
         return int(self.lib.grappa_relax_max_atoms())
 
     def relax_fire(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
-                   atom_counts_host=None) -> None:
+                   atom_counts_host=None, restraints=None, restraint_energy=None, dihedral_out=None) -> None:
         """the fused FIRE minimiser (include/grappa_hip.h grappa_relax_fire_f32): one launch relaxes every (molecule, conformation) of
         the batch under the bonded terms (plan, ks, eqs, n_per, offset_torsion as for mm_energy_fwd; xyz (N,C,3) is the start) plus,
         if nb is not None, Lennard-Jones + Coulomb (nb: the device tables of a NonbondedBatch: atom_molptr, charge, sigma, epsilon,
@@ -209,7 +209,16 @@ class MMBackend:
         -> xyz_out (N,C,3), energy / gmax (B,C) float32, steps / status (B,C) int32; term_energy (6,B,C) and grad (N,C,3) or None.
         status: 0 = max_steps reached, 1 = converged, 2 = non-finite gradient, 3 = above relax_max_atoms() (nothing else written).
         atom_counts_host: atoms per molecule as the caller knows them on the host; with it a molecule above the limit raises here,
-        before the launch and without a device sync (without it such a molecule comes back with status 3)."""
+        before the launch and without a device sync (without it such a molecule comes back with status 3).
+        restraints: a `grappa_amd.restraints.RestraintBatch` on xyz's device (None: the call above, unchanged) -- the frozen atoms,
+        tethers and dihedral restraints of grappa_relax_fire_restr_f32, which minimises E + E_r, keeps energy / term_energy the force
+        field's, writes restraint_energy (B,C) float32 (required with restraints) = E_r at xyz_out and dihedral_out (R,C) float32 or
+        None = the restrained dihedrals there, and adds status 5 = the item's restraint tables are refused, nothing else written."""
+        if restraints is not None:
+            return self._relax_fire_restr(plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy,
+                                          grad, atom_counts_host, restraints, restraint_energy, dihedral_out)
+        if restraint_energy is not None or dihedral_out is not None:
+            raise ValueError("relax_fire: restraint_energy and dihedral_out need restraints")
         _xyz3(xyz, "relax_fire")
         d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
         _relax_outputs("relax_fire", xyz, d.B, xyz_out, energy, gmax, steps, status, term_energy, grad)
@@ -222,6 +231,40 @@ class MMBackend:
         _chk(self.lib.grappa_relax_fire_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), xyz_out.data_ptr(),
                                             energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
              "grappa_relax_fire_f32")
+
+    def _relax_fire_restr(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy, grad,
+                          atom_counts_host, restraints, restraint_energy, dihedral_out) -> None:
+        """`relax_fire` with a RestraintBatch: the same checks, then grappa_relax_fire_restr_f32"""
+        from .restraints import RestraintBatch
+        if not isinstance(restraints, RestraintBatch):
+            raise TypeError(f"relax_fire: restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
+        _xyz3(xyz, "relax_fire")
+        dev = xyz.device
+        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
+        _relax_outputs("relax_fire", xyz, d.B, xyz_out, energy, gmax, steps, status, term_energy, grad)
+        if xyz_out.data_ptr() == xyz.data_ptr() and xyz.numel():
+            raise ValueError("relax_fire: xyz_out must not be the start coordinates")
+        if atom_counts_host is not None:
+            _atom_counts(atom_counts_host, d.N, d.B, "relax_fire", self.relax_max_atoms())
+        r = restraints
+        R = int(r.dih_atoms.shape[0])
+        _tensors(dev, ((r.dih_molptr, "dih_molptr", _I32), (r.dih_atoms, "dih_atoms", _I32), (r.dih_k, "dih_k", _F32), (r.dih_target, "dih_target", _F32),
+                       (r.frozen, "frozen", _I32), (r.pos_k, "pos_k", _F32), (restraint_energy, "restraint_energy", _F32),
+                       (dihedral_out, "dihedral_out", _F32)), ("frozen", "pos_k", "dihedral_out"))
+        if r.dih_molptr.numel() != d.B + 1 or r.dih_atoms.shape != (R, 4) or r.dih_k.numel() != R or r.dih_target.numel() != R * d.C \
+                or any(t is not None and t.numel() != d.N for t in (r.frozen, r.pos_k)):
+            raise ValueError(f"relax_fire: expected dih_molptr ({d.B + 1},), dih_atoms (R,4), dih_k (R,), dih_target (R,{d.C}), frozen / pos_k ({d.N},)")
+        if restraint_energy.numel() != d.B * d.C or (dihedral_out is not None and dihedral_out.numel() != R * d.C):
+            raise ValueError(f"relax_fire: expected restraint_energy (B,C), dihedral_out ({R},{d.C})")
+        nd = _nb_tables_desc(nb, d.N, d.C, d.B, dev, "relax_fire")
+        o = _opts_struct(_lib.RelaxOpts, opts, "relax_fire")
+        rr = _lib.RelaxRestr(frozen=_ptr(r.frozen), pos_k=_ptr(r.pos_k), dih_molptr=r.dih_molptr.data_ptr() if R else None,
+                             dih_atoms=r.dih_atoms.data_ptr() if R else None, dih_k=r.dih_k.data_ptr() if R else None,
+                             dih_target=r.dih_target.data_ptr() if R else None, R=R)
+        _chk(self.lib.grappa_relax_fire_restr_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), C.byref(rr),
+                                                  xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
+                                                  steps.data_ptr(), status.data_ptr(), restraint_energy.data_ptr(), _ptr(dihedral_out)),
+             "grappa_relax_fire_restr_f32")
 
     def _item_table(self, nb, counts, N, Cc, dev):
         """the work-item table of the stepwise paths: the nonbonded plan of these molecules for this C (it is about atoms: it also serves

@@ -62,6 +62,13 @@ class Grappa:
         from .relax import relax
         return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)
 
+    def torsion_scan(self, molecule: Molecule, xyz, dihedral, angles=None, nonbonded=None, **kw):
+        """`predict` followed by `grappa_amd.relax.torsion_scan`: a relaxed scan of the dihedral (four atom ids of the molecule) from the
+        conformation xyz (n_atoms, 3) under the predicted bonded parameters (+ `nonbonded`) -> ScanResult.  All grid points run in one
+        launch and are independent of each other.  **kw: k and the options of `relax`"""
+        from .relax import torsion_scan
+        return torsion_scan(self.predict(molecule), xyz, dihedral, angles, nonbonded, device=self.device, **kw)
+
     def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in

@@ -70,6 +70,8 @@ class RelaxResult:
     gradient_max: object
     steps: object
     status: object
+    restraint_energy: object = None          # with restraints: E_r at xyz (energy stays the force field's), else None
+    dihedrals: object = None                 # with restraints: the restrained dihedrals at xyz, (R, C) / (R, n_confs) in radians, else None
 
     @property
     def converged(self):
@@ -114,7 +116,7 @@ def graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev):
 
 
 def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, **opts) -> RelaxResult:
+                offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, restraints=None, **opts) -> RelaxResult:
     """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
     exactly what `Energy` reads, through the same plan.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded
     terms only).  **opts: see RELAX_DEFAULTS.  The graph is not modified.
@@ -122,10 +124,16 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     stepwise=True: the whole batch through the stepwise path, which takes molecules of any size: four launches per step, and the host
     SYNCS with the device once per chunk of `check_every` steps (an integer >= 1; the default 32 is untuned) to see whether any item
     still runs.  stepwise="auto": the fused kernel if every molecule is within the limit, else the whole batch stepwise -- a batch is
-    never split between the two paths (one batch, one decomposition, one set of bits)."""
+    never split between the two paths (one batch, one decomposition, one set of bits).
+    restraints: a `grappa_amd.restraints.RestraintBatch` for the graph's molecules and C on the graph's device (None: no restraints,
+    the call as it always was).  The minimiser then works on E + E_r; `energy` stays the force field's, and the result carries
+    `restraint_energy` (B, C) and `dihedrals` (R, C).  An item whose tables the kernel refuses comes back with status 5.  The fused
+    path only: with restraints stepwise=True raises, and "auto" raises for a batch that holds a molecule above the limit."""
     from .backend import get_backend
     o = relax_options(**opts)
     stepwise, check_every = _stepwise_options(stepwise, check_every)
+    if restraints is not None:
+        return _relax_graph_restrained(g, nonbonded, list(terms), suffix, offset_torsion, stepwise, restraints, o)
     terms = list(terms)
     xyz, plan, counts = graph_coordinates(g, terms)
     dev = xyz.device
@@ -147,6 +155,40 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
         get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
                                  atom_counts_host=counts)
     return RelaxResult(out, energy, gmax, steps, status)
+
+
+def _relax_graph_restrained(g, nonbonded, terms, suffix, offset_torsion, stepwise, restraints, o) -> RelaxResult:
+    """`relax_graph` with a RestraintBatch: the fused kernel of csrc/relax_restr.hip"""
+    from .backend import get_backend
+    from .restraints import RestraintBatch
+    if not isinstance(restraints, RestraintBatch):
+        raise TypeError(f"restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
+    if stepwise is True:
+        raise ValueError("relax: restraints are taken by the fused minimiser only (stepwise=False or 'auto')")
+    xyz, plan, counts = graph_coordinates(g, terms)
+    dev = xyz.device
+    limit = get_backend().relax_max_atoms()
+    if counts and max(counts) > limit:
+        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
+                         f"minimiser, and restraints are not available on the stepwise path")
+    B, C = plan.B, xyz.shape[1]
+    if restraints.B != B or restraints.C != C:
+        raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
+    if restraints.atom_counts is not None and list(restraints.atom_counts) != counts:
+        raise ValueError("the restraint batch does not describe the graph's molecules (atoms per molecule differ)")
+    for b, r in enumerate(restraints.items):
+        if r is not None and r.n_dihedrals and int(r.dihedrals.max()) >= counts[b]:
+            raise ValueError(f"molecule {b}: a restrained dihedral names atom {int(r.dihedrals.max())}, the molecule has {counts[b]} atoms")
+    if restraints.dih_molptr.device != dev:
+        raise ValueError(f"the restraint batch is on {restraints.dih_molptr.device}, the graph on {dev}")
+    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
+    out = torch.empty_like(xyz)
+    energy, gmax, er = (torch.zeros(B, C, dtype=torch.float32, device=dev) for _ in range(3))
+    steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
+    phi = torch.zeros(restraints.R, C, dtype=torch.float32, device=dev)
+    get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
+                             atom_counts_host=counts, restraints=restraints, restraint_energy=er, dihedral_out=phi)
+    return RelaxResult(out, energy, gmax, steps, status, er, phi)
 
 
 def graph_from_parameters(parameters: Parameters, xyz):
@@ -199,14 +241,24 @@ def graph_from_parameters(parameters: Parameters, xyz):
 
 
 def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, stepwise=False,
-          check_every: int = CHECK_EVERY_DEFAULT, **opts) -> RelaxResult:
+          check_every: int = CHECK_EVERY_DEFAULT, restraints=None, **opts) -> RelaxResult:
     """Relax the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`, whose atoms are in the
     order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom -> RelaxResult with xyz of the same shape
     (float64) and energy / gradient_max / steps / status of shape (n_confs,).  stepwise, check_every: see `relax_graph` (the stepwise
-    path takes a molecule of any size and syncs with the host once per chunk of `check_every` steps)."""
+    path takes a molecule of any size and syncs with the host once per chunk of `check_every` steps).
+    restraints: a `grappa_amd.restraints.Restraints` whose indices are in the order of `parameters.atoms` (None: none); the result
+    then carries restraint_energy (n_confs,) and dihedrals (R, n_confs), and `energy` stays the force field's.  The fused path only."""
     relax_options(**opts)
     _stepwise_options(stepwise, check_every)
     g = graph_from_parameters(parameters, xyz)
+    batch = None
+    if restraints is not None:
+        from .restraints import RestraintBatch, Restraints
+        if not isinstance(restraints, Restraints):
+            raise TypeError(f"restraints must be Restraints or None, got {type(restraints).__name__}")
+        if stepwise is True:
+            raise ValueError("relax: restraints are taken by the fused minimiser only (stepwise=False or 'auto')")
+        batch = RestraintBatch([restraints], int(np.asarray(xyz).shape[0]), atom_counts=[g.num_nodes("n1")])
     nb = None
     if nonbonded is not None:
         if not isinstance(nonbonded, NonbondedParameters):
@@ -214,6 +266,74 @@ def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] 
         if nonbonded.n_atoms != g.num_nodes("n1"):
             raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {g.num_nodes('n1')}")
         nb = NonbondedBatch([nonbonded]).to(device)
-    r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, **opts)
-    return RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
-                       r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])
+    if batch is None:
+        r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, **opts)
+    else:
+        r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, restraints=batch.to(device), **opts)
+    res = RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
+                      r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])
+    if batch is not None:
+        res.restraint_energy, res.dihedrals = r.restraint_energy.cpu().numpy()[0].astype(np.float64), r.dihedrals.cpu().numpy().astype(np.float64)
+    return res
+
+
+SCAN_K_DEFAULT = 239.0          # kcal/mol: 1000 kJ/mol, the usual stiffness of a torsion restraint.  A default, not a tuned value.
+
+
+@dataclass
+class ScanResult:
+    """angles (P,): the targets; dihedrals (P,): the dihedral achieved at each; energy (P,): the FORCE FIELD's energy there (what a scan
+    plots); restraint_energy (P,); xyz (P, n_atoms, 3); steps, status (P,) as for `relax`.  numpy, radians, kcal/mol, Angstrom."""
+    angles: object
+    dihedrals: object
+    energy: object
+    restraint_energy: object
+    xyz: object
+    steps: object
+    status: object
+
+
+def scan_starts(parameters: Parameters, xyz, dihedral, angles):
+    """-> (the start coordinates of a torsion scan, (P, n_atoms, 3) float64; the dihedral as four atom indices): for each angle the
+    input with the l-side of the j-k bond rotated rigidly about that bond so that the dihedral equals the angle
+    (`grappa_amd.restraints.set_dihedral`, on the bond graph of `parameters.bonds`); if j-k lies in a ring nothing is rotated and every
+    point starts from the input"""
+    from .restraints import set_dihedral
+    atoms = np.asarray(parameters.atoms).reshape(-1)
+    pos = {int(a): k for k, a in enumerate(atoms.tolist())}
+    x = np.asarray(xyz, dtype=np.float64)
+    if x.shape != (atoms.shape[0], 3):
+        raise ValueError(f"xyz must be one conformation ({atoms.shape[0]}, 3), got {x.shape}")
+    ids = [int(a) for a in np.asarray(dihedral).reshape(-1)]
+    if len(ids) != 4 or any(a not in pos for a in ids) or len(set(ids)) != 4:
+        raise ValueError(f"dihedral must name four distinct atom ids of parameters.atoms, got {ids}")
+    idx = [pos[a] for a in ids]
+    bonds = np.array([[pos[int(a)], pos[int(b)]] for a, b in np.asarray(parameters.bonds).reshape(-1, 2).tolist()], dtype=np.int64).reshape(-1, 2)
+    return np.stack([set_dihedral(x, bonds, idx, float(a)) for a in angles]), idx
+
+
+def torsion_scan(parameters: Parameters, xyz, dihedral, angles=None, nonbonded: Optional[NonbondedParameters] = None, k: float = SCAN_K_DEFAULT,
+                 device="cuda", **opts) -> ScanResult:
+    """A relaxed torsion scan of ONE molecule: the dihedral (four atom ids of `parameters.atoms`) is held near each of `angles`
+    (radians; default 24 points from -pi in steps of 15 degrees) by the restraint k (1 - cos(phi - angle)), k in kcal/mol, and everything
+    else is relaxed.  xyz: one conformation (n_atoms, 3).  The grid points are the conformations of ONE restrained `relax` call: one
+    launch, one workgroup per point.  The points are INDEPENDENT: each starts from the input with one side of the bond rotated to its
+    angle (`scan_starts`), nothing is propagated from a neighbouring point -- so a point can end in another basin than its neighbours.
+    **opts: the options of `relax` (RELAX_DEFAULTS).  With the default k FIRE's defaults are stable (the restraint is softer than
+    every bond); whether a point reached the tolerance is in `status`."""
+    from .restraints import Restraints
+    if angles is None:
+        angles = -np.pi + np.deg2rad(15.0) * np.arange(24)
+    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+    if not np.isfinite(angles).all():
+        raise ValueError("angles must be finite")
+    if not (np.isfinite(k) and k >= 0):
+        raise ValueError(f"k must be finite and non-negative, got {k}")
+    starts, idx = scan_starts(parameters, xyz, dihedral, angles)
+    P = angles.shape[0]
+    if P == 0:
+        z = np.zeros(0)
+        return ScanResult(angles, z, z, z, starts.reshape(0, np.asarray(xyz).shape[0], 3), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    r = relax(parameters, starts, nonbonded, device=device,
+              restraints=Restraints(dihedrals=[idx], dihedral_k=[float(k)], dihedral_targets=angles[None, :]), **opts)
+    return ScanResult(angles, r.dihedrals[0], r.energy, r.restraint_energy, r.xyz, r.steps, r.status)

@@ -549,6 +549,45 @@ int grappa_relax_fire_f32(void* stream, const grappa_mm_desc* mm, const grappa_n
                           float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same relaxation with restraints (additions to ABI 11): frozen atoms, harmonic tethers to the start coordinates and periodic
+ * dihedral restraints with one target per conformation -- what a relaxed torsion scan needs (the grid points are the conformations of
+ * one molecule, one workgroup each, one launch).  The loop, the options, the item and the size limit are those of grappa_relax_fire_f32,
+ * word for word, on the objective E_ff + E_r with E_ff the energy above and
+ *   E_r = sum_r dih_k_r (1 - cos(phi_r - dih_target_r,c)) + sum_i 0.5 pos_k_i |x_i - start_i|^2        (start = mm->xyz)
+ * phi: the dihedral of grappa_mm_energy_fwd_f32 (the reference's sign convention), radians; the restraint is periodic and smooth (no
+ * wrap-around case) and about 0.5 k dphi^2 near its target.  Units: dih_k kcal/mol, pos_k kcal/mol/A^2, targets rad.  The gradient the
+ * loop sees is formed per atom in a fixed order: g = grad E_ff as grappa_relax_fire_f32 forms it; + dih_k_r sin(phi_r - target) dphi_r/dx
+ * for the atom's restraints in ascending r; + pos_k_i (x_i - start_i); then replaced by 0 for a frozen atom before anything reads it
+ * (gmax, the non-finite test, P, |F|^2, the velocity).  A frozen atom keeps the bits of its input coordinates; a molecule frozen
+ * entirely stops at step 0 with status 1.
+ * Outputs: xyz_out, steps, status as above; energy and term_energy are the FORCE FIELD's six terms only (what a scan plots);
+ * restraint_energy[B,C] = E_r at xyz_out, thread partials added in double in thread order like the six terms; grad and gmax are those of
+ * the objective; dih_phi[R,C] (NULL: not written) the restrained dihedrals at xyz_out.
+ * The tables are device memory: the kernel vets an item's before it writes anything for it.  An atom index outside [0, n), a dihedral
+ * whose four atoms are not distinct, a dih_k that is negative or not finite, a target of the item's conformation that is not finite, a
+ * pos_k that is negative or not finite, or more than GRAPPA_RELAX_MAX_DIHEDRALS restrained dihedrals on the molecule: status 5 = the
+ * item's tables are refused and NOTHING else is written for it (as for grappa_md_langevin_cons_f32).  Statuses 0 to 3 are unchanged;
+ * a molecule above grappa_relax_max_atoms() gets status 3.  Same input, same bits, whatever the neighbours do.
+ * r == NULL, or R == 0 with frozen == NULL and pos_k == NULL: the launch of grappa_relax_fire_f32 itself, hence its bits, and
+ * restraint_energy = 0 for every molecule that has atoms and is within the size limit.
+ * GRAPPA_ERR_ARG: the cases of grappa_relax_fire_f32; R < 0; a NULL dih_molptr, dih_atoms, dih_k or dih_target with R > 0; a NULL
+ * restraint_energy; R * C >= 2^31. */
+#define GRAPPA_RELAX_MAX_DIHEDRALS 16        /* restrained dihedrals per molecule at most */
+typedef struct grappa_relax_restr {
+    const int*   frozen;       /* [N] or NULL: nonzero = the atom is frozen */
+    const float* pos_k;        /* [N] or NULL: kcal/mol/A^2, 0 = none; tethers the atom to its START position mm->xyz */
+    const int*   dih_molptr;   /* [B+1]: the restrained dihedrals of molecule b (NULL iff R == 0) */
+    const int*   dih_atoms;    /* [R,4]: atom indices WITHIN the molecule */
+    const float* dih_k;        /* [R] kcal/mol */
+    const float* dih_target;   /* [R,C] rad: one target per conformation */
+    int R;
+} grappa_relax_restr;
+int grappa_relax_max_dihedrals(void);    /* 16 */
+int grappa_relax_fire_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                const grappa_relax_restr* r, float* xyz_out, float* energy, float* term_energy, float* grad, float* gmax,
+                                int* steps, int* status, float* restraint_energy /*[B,C]*/, float* dih_phi /*[R,C] or NULL*/);
+
+/* ------------------------------------------------------------------------------------------------
  * The same relaxation for molecules of ANY size, stepwise (additions to ABI 11): the loop, the energy, the options and the outputs are
  * those of grappa_relax_fire_f32 above, but a molecule spans many workgroups, the minimiser's state lives in a caller-owned workspace
  * and a step is a fixed sequence of four launches.  The decomposition is grappa_nonbonded_plan's (a work item = molecule, block of at

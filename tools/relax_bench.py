@@ -9,6 +9,12 @@ Both run a fixed number of steps (tolerance 0), so a step is the same work in bo
 proper and two improper periodicities), equilibrium values are those of the pool geometry, conformations are jittered by 0.05 A.
 
     python tools/relax_bench.py [--out profiles/relax_bench.txt] [--steps 200] [--composed-steps 50]
+
+--restraints times something else on the same pool workload: the restrained kernel (csrc/relax_restr.hip, one restrained dihedral,
+k = 239 kcal/mol, target 0.5 rad from the start, on every molecule that has a proper) against the unrestrained one, both in this
+process, device events, median of --reps runs of the same fixed number of steps.
+
+    python tools/relax_bench.py --restraints [--out profiles/relax_restr_bench.txt]
 """
 import argparse
 import datetime
@@ -49,6 +55,26 @@ def pool_batch(n_mols, n_confs, seed=0):
     g.nodes["n4"].data["k"] = (torch.rand(len(idx["n4"]), 3, generator=gen) * 2 - 1) * torch.tensor([1.0, 0.5, 0.3])
     g.nodes["n4_improper"].data["k"] = (torch.rand(len(idx["n4_improper"]), 2, generator=gen) * 2 - 1) * torch.tensor([1.0, 0.5])
     return g.to("cuda"), NonbondedBatch(params).to("cuda")
+
+
+def pool_restraints(g, n_confs):
+    """one restrained dihedral per molecule of the batch that has a proper (its first), in every conformation 0.5 rad from the start
+    dihedral of conformation 0 -> (RestraintBatch on the device, molecules restrained)"""
+    from grappa_amd.restraints import RestraintBatch, Restraints, dihedral_angle
+    counts = [int(c) for c in g.batch_num_nodes_host("n1")]
+    ptr = np.concatenate([[0], np.cumsum(counts)])
+    idx = g.nodes["n4"].data["idxs"].long().cpu().numpy()
+    first = g.plan().mol_ptr["n4"].cpu().numpy()
+    x = g.nodes["n1"].data["xyz"][:, 0].double().cpu().numpy()
+    items = []
+    for b in range(len(counts)):
+        if first[b + 1] == first[b]:
+            items.append(None)
+            continue
+        row = idx[first[b]] - ptr[b]
+        phi = dihedral_angle(x[ptr[b]:ptr[b + 1]], *row)
+        items.append(Restraints(dihedrals=[row], dihedral_k=239.0, dihedral_targets=[(phi + 0.5 + np.pi) % (2 * np.pi) - np.pi]))
+    return RestraintBatch(items, n_confs, atom_counts=counts).to("cuda"), sum(r is not None for r in items)
 
 
 class Composed:
@@ -128,6 +154,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--composed-steps", type=int, default=50)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--restraints", action="store_true", help="time the restrained kernel against the unrestrained one instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("relax_bench: needs a GPU (there is nothing to time without one)")
@@ -148,11 +175,30 @@ def main():
     print("\n".join(lines), flush=True)
 
     def report(what, steps, med, mn, launches):
-        lines.append(f"{what:10s} {steps:5d} steps {med / 1e3:10.2f} ms (min {mn / 1e3:10.2f})  {items * steps / (med * 1e-6):10.3e} item steps/s  "
+        lines.append(f"{what:12s} {steps:5d} steps {med / 1e3:10.2f} ms (min {mn / 1e3:10.2f})  {items * steps / (med * 1e-6):10.3e} item steps/s  "
                      f"{args.mols / (med * 1e-6):10.3e} molecules/s at {steps} steps x {args.confs} conformations  {launches:6d} library launches")
         print(lines[-1], flush=True)
         return items * steps / (med * 1e-6)
 
+    if args.restraints:
+        rb, n_restr = pool_restraints(g, args.confs)
+        lines.append(f"restraints: one dihedral (k = 239 kcal/mol, target 0.5 rad from the start) on {n_restr} of {args.mols} molecules")
+        run = {"unrestrained": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=args.steps),
+               "restrained": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=args.steps, restraints=rb)}
+        rate = {}
+        for what, fn in run.items():
+            n0 = be.lib.grappa_launch_count(0)
+            r = fn()
+            n1 = be.lib.grappa_launch_count(0)
+            assert bool((r.steps == args.steps).all()) and bool((r.status == 0).all())
+            rate[what] = report(what, args.steps, *timed(fn, args.reps), n1 - n0)
+        lines.append(f"restrained / unrestrained = {rate['restrained'] / rate['unrestrained']:.3f}x item steps/s")
+        print(lines[-1], flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     opts = {**RELAX_DEFAULTS, "tolerance": 0.0}
     n0 = be.lib.grappa_launch_count(0)
     r = relax_graph(g, nb, tolerance=0.0, max_steps=args.steps)
