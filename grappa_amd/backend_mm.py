@@ -214,30 +214,13 @@ class MMBackend:
         tethers and dihedral restraints of grappa_relax_fire_restr_f32, which minimises E + E_r, keeps energy / term_energy the force
         field's, writes restraint_energy (B,C) float32 (required with restraints) = E_r at xyz_out and dihedral_out (R,C) float32 or
         None = the restrained dihedrals there, and adds status 5 = the item's restraint tables are refused, nothing else written."""
-        if restraints is not None:
-            return self._relax_fire_restr(plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy,
-                                          grad, atom_counts_host, restraints, restraint_energy, dihedral_out)
-        if restraint_energy is not None or dihedral_out is not None:
+        r = restraints
+        if r is not None:
+            from .restraints import RestraintBatch
+            if not isinstance(r, RestraintBatch):
+                raise TypeError(f"relax_fire: restraints must be a RestraintBatch or None, got {type(r).__name__}")
+        elif restraint_energy is not None or dihedral_out is not None:
             raise ValueError("relax_fire: restraint_energy and dihedral_out need restraints")
-        _xyz3(xyz, "relax_fire")
-        d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
-        _relax_outputs("relax_fire", xyz, d.B, xyz_out, energy, gmax, steps, status, term_energy, grad)
-        if xyz_out.data_ptr() == xyz.data_ptr() and xyz.numel():
-            raise ValueError("relax_fire: xyz_out must not be the start coordinates")
-        if atom_counts_host is not None:
-            _atom_counts(atom_counts_host, d.N, d.B, "relax_fire", self.relax_max_atoms())
-        nd = _nb_tables_desc(nb, d.N, d.C, d.B, xyz.device, "relax_fire")
-        o = _opts_struct(_lib.RelaxOpts, opts, "relax_fire")
-        _chk(self.lib.grappa_relax_fire_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), xyz_out.data_ptr(),
-                                            energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr()),
-             "grappa_relax_fire_f32")
-
-    def _relax_fire_restr(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy, grad,
-                          atom_counts_host, restraints, restraint_energy, dihedral_out) -> None:
-        """`relax_fire` with a RestraintBatch: the same checks, then grappa_relax_fire_restr_f32"""
-        from .restraints import RestraintBatch
-        if not isinstance(restraints, RestraintBatch):
-            raise TypeError(f"relax_fire: restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
         _xyz3(xyz, "relax_fire")
         dev = xyz.device
         d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
@@ -246,24 +229,27 @@ class MMBackend:
             raise ValueError("relax_fire: xyz_out must not be the start coordinates")
         if atom_counts_host is not None:
             _atom_counts(atom_counts_host, d.N, d.B, "relax_fire", self.relax_max_atoms())
-        r = restraints
-        R = int(r.dih_atoms.shape[0])
-        _tensors(dev, ((r.dih_molptr, "dih_molptr", _I32), (r.dih_atoms, "dih_atoms", _I32), (r.dih_k, "dih_k", _F32), (r.dih_target, "dih_target", _F32),
-                       (r.frozen, "frozen", _I32), (r.pos_k, "pos_k", _F32), (restraint_energy, "restraint_energy", _F32),
-                       (dihedral_out, "dihedral_out", _F32)), ("frozen", "pos_k", "dihedral_out"))
-        if r.dih_molptr.numel() != d.B + 1 or r.dih_atoms.shape != (R, 4) or r.dih_k.numel() != R or r.dih_target.numel() != R * d.C \
-                or any(t is not None and t.numel() != d.N for t in (r.frozen, r.pos_k)):
-            raise ValueError(f"relax_fire: expected dih_molptr ({d.B + 1},), dih_atoms (R,4), dih_k (R,), dih_target (R,{d.C}), frozen / pos_k ({d.N},)")
-        if restraint_energy.numel() != d.B * d.C or (dihedral_out is not None and dihedral_out.numel() != R * d.C):
-            raise ValueError(f"relax_fire: expected restraint_energy (B,C), dihedral_out ({R},{d.C})")
+        if r is not None:
+            R = int(r.dih_atoms.shape[0])
+            _tensors(dev, ((r.dih_molptr, "dih_molptr", _I32), (r.dih_atoms, "dih_atoms", _I32), (r.dih_k, "dih_k", _F32), (r.dih_target, "dih_target", _F32),
+                           (r.frozen, "frozen", _I32), (r.pos_k, "pos_k", _F32), (restraint_energy, "restraint_energy", _F32),
+                           (dihedral_out, "dihedral_out", _F32)), ("frozen", "pos_k", "dihedral_out"))
+            if r.dih_molptr.numel() != d.B + 1 or r.dih_atoms.shape != (R, 4) or r.dih_k.numel() != R or r.dih_target.numel() != R * d.C \
+                    or any(t is not None and t.numel() != d.N for t in (r.frozen, r.pos_k)):
+                raise ValueError(f"relax_fire: expected dih_molptr ({d.B + 1},), dih_atoms (R,4), dih_k (R,), dih_target (R,{d.C}), frozen / pos_k ({d.N},)")
+            if restraint_energy.numel() != d.B * d.C or (dihedral_out is not None and dihedral_out.numel() != R * d.C):
+                raise ValueError(f"relax_fire: expected restraint_energy (B,C), dihedral_out ({R},{d.C})")
         nd = _nb_tables_desc(nb, d.N, d.C, d.B, dev, "relax_fire")
         o = _opts_struct(_lib.RelaxOpts, opts, "relax_fire")
+        head = (self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o))
+        outs = (xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(), status.data_ptr())
+        if r is None:
+            _chk(self.lib.grappa_relax_fire_f32(*head, *outs), "grappa_relax_fire_f32")
+            return
         rr = _lib.RelaxRestr(frozen=_ptr(r.frozen), pos_k=_ptr(r.pos_k), dih_molptr=r.dih_molptr.data_ptr() if R else None,
                              dih_atoms=r.dih_atoms.data_ptr() if R else None, dih_k=r.dih_k.data_ptr() if R else None,
                              dih_target=r.dih_target.data_ptr() if R else None, R=R)
-        _chk(self.lib.grappa_relax_fire_restr_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), C.byref(rr),
-                                                  xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
-                                                  steps.data_ptr(), status.data_ptr(), restraint_energy.data_ptr(), _ptr(dihedral_out)),
+        _chk(self.lib.grappa_relax_fire_restr_f32(*head, C.byref(rr), *outs, restraint_energy.data_ptr(), _ptr(dihedral_out)),
              "grappa_relax_fire_restr_f32")
 
     def _item_table(self, nb, counts, N, Cc, dev):
@@ -379,17 +365,14 @@ class MMBackend:
         if atom_counts_host is not None:
             _atom_counts(atom_counts_host, N, B, "md_langevin", self.relax_max_atoms())
         nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_langevin")
+        head = (self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o))
+        tail = (mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(),
+                steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot), _ptr(frames_ekin))
         if constraints is not None:
             cons = self._md_cons(constraints, B, dev, constrain_start)
-            _chk(self.lib.grappa_md_langevin_cons_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), C.byref(cons),
-                                                      mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(),
-                                                      epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz),
-                                                      _ptr(frames_epot), _ptr(frames_ekin)), "grappa_md_langevin_cons_f32")
+            _chk(self.lib.grappa_md_langevin_cons_f32(*head, C.byref(cons), *tail), "grappa_md_langevin_cons_f32")
             return
-        _chk(self.lib.grappa_md_langevin_f32(self._stream(), C.byref(d), C.byref(nd) if nd is not None else None, C.byref(o), mass.data_ptr(),
-                                             mol_key.data_ptr(), _ptr(vel_in), xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(),
-                                             ekin.data_ptr(), steps.data_ptr(), status.data_ptr(), _ptr(frames_xyz), _ptr(frames_epot),
-                                             _ptr(frames_ekin)), "grappa_md_langevin_f32")
+        _chk(self.lib.grappa_md_langevin_f32(*head, *tail), "grappa_md_langevin_f32")
 
     def md_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                  frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None) -> None:

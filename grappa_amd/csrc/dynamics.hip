@@ -233,14 +233,9 @@ extern "C" int grappa_md_noise_f32(void* stream, const unsigned long long* mol_k
 extern "C" int grappa_md_langevin_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const float* mass,
                                       const unsigned long long* mol_key, const float* vel_in, float* xyz_out, float* vel_out, float* epot,
                                       float* ekin, int* steps, int* status, float* frames_xyz, float* frames_epot, float* frames_ekin) {
-    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0) return GRAPPA_ERR_ARG;
-    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    if (!md_opts_ok(o)) return GRAPPA_ERR_ARG;
-    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return GRAPPA_OK;
-    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status)
-        return GRAPPA_ERR_ARG;
-    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
-    if ((long long)mm->B * mm->C > INT_MAX) return GRAPPA_ERR_ARG;
+    const int rc = mm_seam_check(mm, nb, o && md_opts_ok(o));
+    if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
+    if (!mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
     MdArgs a;
     a.mm = *mm;
     a.has_nb = nb != nullptr;

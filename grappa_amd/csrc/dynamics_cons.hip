@@ -506,14 +506,9 @@ extern "C" int grappa_md_langevin_cons_f32(void* stream, const grappa_mm_desc* m
                                       frames_ekin);
     if (!cons->cluster_molptr || !cons->cluster_atoms || !cons->cluster_d) return GRAPPA_ERR_ARG;
     if (!(cons->tolerance >= 0x1p-20f && cons->tolerance <= 0x1p-7f)) return GRAPPA_ERR_ARG;          // (a NaN is refused)
-    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0) return GRAPPA_ERR_ARG;
-    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    if (!md_opts_ok(o)) return GRAPPA_ERR_ARG;
-    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return GRAPPA_OK;
-    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status)
-        return GRAPPA_ERR_ARG;
-    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
-    if ((long long)mm->B * mm->C > INT_MAX) return GRAPPA_ERR_ARG;
+    const int rc = mm_seam_check(mm, nb, o && md_opts_ok(o));
+    if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
+    if (!mass || !mol_key || !xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
     MdConsArgs a;
     a.mm = *mm;
     a.has_nb = nb != nullptr;

@@ -262,21 +262,7 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// the argument checks the three calls share (csrc/desc_check.h, csrc/md_noise.h); 1: nothing to do (an empty batch)
-int ms_check(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks,
-             const void* ws) {
-    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0 || n_items < 0 || n_blocks < 0) return GRAPPA_ERR_ARG;
-    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    if (!md_opts_ok(o)) return GRAPPA_ERR_ARG;
-    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return 1;
-    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !table_dev || !ws) return GRAPPA_ERR_ARG;
-    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)table_dev & 15) != 0) return GRAPPA_ERR_ARG;      // (doubles in the workspace, int4 items in the table)
-    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
-    if ((long long)mm->B * mm->C > INT_MAX || (long long)mm->N * mm->C * 3 > INT_MAX || (long long)n_blocks * mm->C > INT_MAX)
-        return GRAPPA_ERR_ARG;
-    if (n_blocks > (long long)mm->N / NB_T + mm->B) return GRAPPA_ERR_ARG;
-    return GRAPPA_OK;
-}
+// (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
 void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w, const float* mass,
                      float hk, float* frame_xyz, int n_items) {
@@ -321,7 +307,7 @@ extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blo
 extern "C" int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                         const float* mass, const unsigned long long* mol_key, const float* vel_in, const int* table_dev,
                                         int n_items, int n_blocks, void* ws, size_t ws_bytes) {
-    const int rc = ms_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
@@ -345,7 +331,7 @@ extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, c
                                        const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks,
                                        void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot,
                                        float* frames_ekin) {
-    const int rc = ms_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
     const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin);
@@ -388,7 +374,7 @@ extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, c
 extern "C" int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
                                           float* vel_out, float* epot, float* ekin, int* steps, int* status) {
-    const int rc = ms_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);

@@ -321,22 +321,7 @@ __global__ __launch_bounds__(256) void rs_out_kernel(RsOutArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// the argument checks of grappa_relax_fire_f32 (the shared ones: csrc/desc_check.h), without its output pointers; 1: nothing to do (an
-// empty batch)
-int rs_check(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
-             const void* ws) {
-    if (!mm || !o || mm->N < 0 || mm->C < 0 || mm->B < 0 || n_items < 0 || n_blocks < 0) return GRAPPA_ERR_ARG;
-    if (nb && (nb->N != mm->N || nb->C != mm->C || nb->B != mm->B)) return GRAPPA_ERR_ARG;
-    if (!relax_opts_ok(o)) return GRAPPA_ERR_ARG;
-    if (mm->N == 0 || mm->C == 0 || mm->B == 0) return 1;
-    if (!mm->xyz || !mm->atom_molptr || !mm->inc_ptr || !table_dev || !ws) return GRAPPA_ERR_ARG;
-    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)table_dev & 15) != 0) return GRAPPA_ERR_ARG;      // (doubles in the workspace, int4 items in the table)
-    if (!mm_desc_tables_ok(mm, true) || (nb && !nb_desc_tables_ok(nb))) return GRAPPA_ERR_ARG;
-    if ((long long)mm->B * mm->C > INT_MAX || (long long)mm->N * mm->C * 3 > INT_MAX || (long long)n_blocks * mm->C > INT_MAX)
-        return GRAPPA_ERR_ARG;
-    if (n_blocks > (long long)mm->N / NB_T + mm->B) return GRAPPA_ERR_ARG;
-    return GRAPPA_OK;
-}
+// (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
 void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const RsWs& w, int n_items) {
     RsForceArgs f;
@@ -354,7 +339,7 @@ extern "C" size_t grappa_relax_steps_workspace_bytes(int N, int C, int B, int n_
 
 extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
                                            const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
-    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!n_running_dev) return GRAPPA_ERR_ARG;
     const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
@@ -375,7 +360,7 @@ extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* m
 extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps,
                                           int* n_running_dev) {
-    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
@@ -405,7 +390,7 @@ extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm
 extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
                                              const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
                                              float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status) {
-    const int rc = rs_check(mm, nb, o, table_dev, n_items, n_blocks, ws);
+    const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !energy || !gmax || !steps || !status) return GRAPPA_ERR_ARG;
     const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);

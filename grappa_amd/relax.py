@@ -132,62 +132,49 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     from .backend import get_backend
     o = relax_options(**opts)
     stepwise, check_every = _stepwise_options(stepwise, check_every)
-    if restraints is not None:
-        return _relax_graph_restrained(g, nonbonded, list(terms), suffix, offset_torsion, stepwise, restraints, o)
     terms = list(terms)
+    if restraints is not None:
+        from .restraints import RestraintBatch
+        if not isinstance(restraints, RestraintBatch):
+            raise TypeError(f"restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
+        if stepwise is True:
+            raise ValueError("relax: restraints are taken by the fused minimiser only (stepwise=False or 'auto')")
     xyz, plan, counts = graph_coordinates(g, terms)
     dev = xyz.device
     limit = get_backend().relax_max_atoms()
     above = bool(counts) and max(counts) > limit
+    if above and restraints is not None:
+        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
+                         f"minimiser, and restraints are not available on the stepwise path")
     if above and stepwise is False:
         raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
                          f"minimiser (stepwise=True or stepwise='auto' relaxes molecules of any size)")
     use_steps = stepwise is True or (stepwise == "auto" and above)
-    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     B, C = plan.B, xyz.shape[1]
+    if restraints is not None:
+        if restraints.B != B or restraints.C != C:
+            raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
+        if restraints.atom_counts is not None and list(restraints.atom_counts) != counts:
+            raise ValueError("the restraint batch does not describe the graph's molecules (atoms per molecule differ)")
+        for b, r in enumerate(restraints.items):
+            if r is not None and r.n_dihedrals and int(r.dihedrals.max()) >= counts[b]:
+                raise ValueError(f"molecule {b}: a restrained dihedral names atom {int(r.dihedrals.max())}, the molecule has {counts[b]} atoms")
+        if restraints.dih_molptr.device != dev:
+            raise ValueError(f"the restraint batch is on {restraints.dih_molptr.device}, the graph on {dev}")
+    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     out = torch.empty_like(xyz)
     energy, gmax = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(B, C, dtype=torch.float32, device=dev)
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
+    er, phi, restr = None, None, {}          # (without restraints the backend is called exactly as it always was)
+    if restraints is not None:
+        er, phi = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(restraints.R, C, dtype=torch.float32, device=dev)
+        restr = dict(restraints=restraints, restraint_energy=er, dihedral_out=phi)
     if use_steps:
         get_backend().relax_steps(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
                                   atom_counts_host=counts, check_every=check_every)
     else:
         get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
-                                 atom_counts_host=counts)
-    return RelaxResult(out, energy, gmax, steps, status)
-
-
-def _relax_graph_restrained(g, nonbonded, terms, suffix, offset_torsion, stepwise, restraints, o) -> RelaxResult:
-    """`relax_graph` with a RestraintBatch: the fused kernel of csrc/relax_restr.hip"""
-    from .backend import get_backend
-    from .restraints import RestraintBatch
-    if not isinstance(restraints, RestraintBatch):
-        raise TypeError(f"restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
-    if stepwise is True:
-        raise ValueError("relax: restraints are taken by the fused minimiser only (stepwise=False or 'auto')")
-    xyz, plan, counts = graph_coordinates(g, terms)
-    dev = xyz.device
-    limit = get_backend().relax_max_atoms()
-    if counts and max(counts) > limit:
-        raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
-                         f"minimiser, and restraints are not available on the stepwise path")
-    B, C = plan.B, xyz.shape[1]
-    if restraints.B != B or restraints.C != C:
-        raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
-    if restraints.atom_counts is not None and list(restraints.atom_counts) != counts:
-        raise ValueError("the restraint batch does not describe the graph's molecules (atoms per molecule differ)")
-    for b, r in enumerate(restraints.items):
-        if r is not None and r.n_dihedrals and int(r.dihedrals.max()) >= counts[b]:
-            raise ValueError(f"molecule {b}: a restrained dihedral names atom {int(r.dihedrals.max())}, the molecule has {counts[b]} atoms")
-    if restraints.dih_molptr.device != dev:
-        raise ValueError(f"the restraint batch is on {restraints.dih_molptr.device}, the graph on {dev}")
-    ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
-    out = torch.empty_like(xyz)
-    energy, gmax, er = (torch.zeros(B, C, dtype=torch.float32, device=dev) for _ in range(3))
-    steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
-    phi = torch.zeros(restraints.R, C, dtype=torch.float32, device=dev)
-    get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
-                             atom_counts_host=counts, restraints=restraints, restraint_energy=er, dihedral_out=phi)
+                                 atom_counts_host=counts, **restr)
     return RelaxResult(out, energy, gmax, steps, status, er, phi)
 
 
@@ -266,10 +253,7 @@ def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] 
         if nonbonded.n_atoms != g.num_nodes("n1"):
             raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {g.num_nodes('n1')}")
         nb = NonbondedBatch([nonbonded]).to(device)
-    if batch is None:
-        r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, **opts)
-    else:
-        r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, restraints=batch.to(device), **opts)
+    r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, restraints=None if batch is None else batch.to(device), **opts)
     res = RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
                       r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])
     if batch is not None:

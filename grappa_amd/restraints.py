@@ -1,4 +1,4 @@
-"""Restraints for the fused FIRE minimiser (`grappa_amd.relax`, csrc/relax_restr.hip; the objective is stated in include/grappa_hip.h at
+"""Restraints for the fused FIRE minimiser (`grappa_amd.relax`, csrc/relax.hip; the objective is stated in include/grappa_hip.h at
 grappa_relax_fire_restr_f32): frozen atoms, harmonic tethers to the start coordinates and periodic dihedral restraints
 k (1 - cos(phi - target)) with one target per conformation -- what "optimise the hydrogens only", "relax, but stay near the input" and
 a relaxed torsion scan need.

@@ -307,6 +307,41 @@ def test_bad_options_and_pointers_are_refused(hip):
     assert all(bool((buf[:64] == (FILL_I if buf.dtype == torch.int32 else FILL)).all()) for buf, _ in out.values())
 
 
+def test_an_empty_batch_passes_every_seam_after_its_options_and_counts(hip):
+    """the head the six entry families share (csrc/desc_check.h), in its observable order: with N = C = B = 0 and every output NULL a call
+    returns 0 without a launch, but bad options -- and, on the stepwise paths, a negative n_items -- are refused first"""
+    from grappa_amd import _lib
+    lib, st = hip.lib, hip._stream()
+    d = C.byref(_lib.MMDesc())          # all zero: an empty batch, every pointer NULL
+    some = torch.zeros(4, dtype=torch.int32, device="cuda").data_ptr()          # (a pointer the struct checks accept; nothing reads it)
+    ro = lambda **kw: C.byref(_lib.RelaxOpts(**{k: (int(v) if k in ("max_steps", "n_min") else float(v)) for k, v in {**RELAX_DEFAULTS, **kw}.items()}))      # noqa: E731
+    mo = lambda **kw: C.byref(_lib.MdOpts(**{**dict(dt=0.001, temperature=300.0, friction=1.0, init_temperature=300.0, n_steps=4, save_every=0, first_step=0), **kw}))      # noqa: E731
+    restr = C.byref(_lib.RelaxRestr(frozen=None, pos_k=None, dih_molptr=some, dih_atoms=some, dih_k=some, dih_target=some, R=1))
+    cons = C.byref(_lib.MdCons(cluster_molptr=some, cluster_atoms=some, cluster_d=some, K=1, tolerance=1e-4, constrain_start=1))
+    n7, n12 = [None] * 7, [None] * 12
+    fused = {"relax_fire": lambda o: lib.grappa_relax_fire_f32(st, d, None, o, *n7),
+             "relax_fire_restr": lambda o: lib.grappa_relax_fire_restr_f32(st, d, None, o, restr, *n7, some, None),      # (restraint_energy is required whatever the batch)
+             "md_langevin": lambda o: lib.grappa_md_langevin_f32(st, d, None, o, *n12),
+             "md_langevin_cons": lambda o: lib.grappa_md_langevin_cons_f32(st, d, None, o, cons, *n12)}
+    steps = {"relax_steps_init": lambda o, ni: lib.grappa_relax_steps_init_f32(st, d, None, o, None, ni, 0, None, 0, None),
+             "relax_steps_run": lambda o, ni: lib.grappa_relax_steps_run_f32(st, d, None, o, None, ni, 0, None, 0, 1, None),
+             "relax_steps_finish": lambda o, ni: lib.grappa_relax_steps_finish_f32(st, d, None, o, None, ni, 0, None, 0, *n7),
+             "md_steps_init": lambda o, ni: lib.grappa_md_steps_init_f32(st, d, None, o, None, None, None, None, ni, 0, None, 0),
+             "md_steps_run": lambda o, ni: lib.grappa_md_steps_run_f32(st, d, None, o, None, None, None, ni, 0, None, 0, 0, 1, None, None, None),
+             "md_steps_finish": lambda o, ni: lib.grappa_md_steps_finish_f32(st, d, None, o, None, ni, 0, None, 0, *[None] * 6)}
+    before = lib.grappa_launch_count(0)
+    for name, call in fused.items():
+        good, bad = (mo(), mo(dt=0.0)) if name.startswith("md") else (ro(), ro(dt_start=0.0))
+        assert call(good) == 0, f"{name}: an empty batch"
+        assert call(bad) == -1, f"{name}: bad options with an empty batch"          # GRAPPA_ERR_ARG
+    for name, call in steps.items():
+        good, bad = (mo(), mo(dt=0.0)) if name.startswith("md") else (ro(), ro(dt_start=0.0))
+        assert call(good, 0) == 0, f"{name}: an empty batch"
+        assert call(bad, 0) == -1, f"{name}: bad options with an empty batch"
+        assert call(good, -1) == -1, f"{name}: n_items = -1 with an empty batch"
+    assert lib.grappa_launch_count(0) == before, "a call on an empty batch launched something"
+
+
 # ------------------------------------------------------------------------------------------------ 8. front ends
 def _parameters(mol):
     from grappa_amd.parameters import Parameters

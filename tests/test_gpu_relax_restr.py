@@ -1,4 +1,4 @@
-"""GPU: the restrained fused FIRE minimiser (csrc/relax_restr.hip through HipBackend.relax_fire(restraints=...) and grappa_amd/relax.py)
+"""GPU: the restrained fused FIRE minimiser (csrc/relax.hip through HipBackend.relax_fire(restraints=...) and grappa_amd/relax.py)
 against the float64 restatement of tests/relax_restr_refs.py, inside sentinel-guarded output buffers.
 
 Gates are those of tests/test_gpu_relax.py: the calibrated gate |gpu - f64| <= 2 |fp32 restatement - f64| + 64 u32 scale for what is

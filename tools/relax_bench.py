@@ -10,7 +10,7 @@ proper and two improper periodicities), equilibrium values are those of the pool
 
     python tools/relax_bench.py [--out profiles/relax_bench.txt] [--steps 200] [--composed-steps 50]
 
---restraints times something else on the same pool workload: the restrained kernel (csrc/relax_restr.hip, one restrained dihedral,
+--restraints times something else on the same pool workload: the restrained instantiation of the kernel (csrc/relax.hip, one restrained dihedral,
 k = 239 kcal/mol, target 0.5 rad from the start, on every molecule that has a proper) against the unrestrained one, both in this
 process, device events, median of --reps runs of the same fixed number of steps.
 
