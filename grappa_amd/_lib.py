@@ -86,6 +86,11 @@ class NbDesc(C.Structure):
                 ("exc_qq", C.c_void_p), ("exc_sigma", C.c_void_p), ("exc_eps", C.c_void_p)]
 
 
+class NbCut(C.Structure):
+    """grappa_nb_cut (additions to ABI 11): the nonbonded cutoff, per call"""
+    _fields_ = [("cutoff", C.c_float), ("switch_distance", C.c_float), ("rf_dielectric", C.c_float), ("prune", C.c_int)]
+
+
 class RelaxOpts(C.Structure):
     """grappa_relax_opts (additions to ABI 11): the options of the fused FIRE minimiser, per call"""
     _fields_ = [("tolerance", C.c_float), ("max_steps", C.c_int), ("dt_start", C.c_float), ("dt_max", C.c_float), ("max_disp", C.c_float),
@@ -230,6 +235,9 @@ SIGNATURES = {
     "grappa_nonbonded_fwd_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _vp, _vp, _vp, _sz]),
     "grappa_nonbonded_plan": (C.c_longlong, [_i, _i, _i, _vp, _vp, C.c_longlong]),
     "grappa_nonbonded_fwd_planned_f32": (_i, [_vp, C.POINTER(NbDesc), _vp, _i, _i, _vp, _vp, _vp, _vp, _sz]),
+    # the same with a cutoff, a reaction field and tile pruning (additions to ABI 11)
+    "grappa_nonbonded_cut_workspace_bytes": (_sz, [_i, _i]),
+    "grappa_nonbonded_fwd_cut_f32": (_i, [_vp, C.POINTER(NbDesc), C.POINTER(NbCut), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
     # relaxation under the full force field (additions to ABI 11)
     "grappa_relax_max_atoms": (_i, []),
     "grappa_relax_fire_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -258,6 +266,14 @@ SIGNATURES = {
                                      _vp, _vp, _vp]),
     "grappa_md_steps_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _i, _i, _vp, _sz,
                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise dynamics under a nonbonded cutoff (additions to ABI 11)
+    "grappa_md_steps_cut_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "grappa_md_steps_init_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _i, _i,
+                                          _vp, _sz]),
+    "grappa_md_steps_run_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), _vp, _vp, _vp, _i, _i, _vp,
+                                         _sz, _i, _i, _vp, _vp, _vp]),
+    "grappa_md_steps_finish_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), _vp, _i, _i, _vp, _sz,
+                                            _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

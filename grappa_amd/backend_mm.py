@@ -42,6 +42,12 @@ def _opts_struct(cls, opts, who):
     return o
 
 
+def _cut_struct(cutoff, who):
+    """grappa_nb_cut from a `grappa_amd.nonbonded.Cutoff` (or a plain distance)"""
+    from .nonbonded import as_cutoff
+    return _opts_struct(_lib.NbCut, as_cutoff(cutoff).as_opts(), who)
+
+
 def _atom_counts(atom_counts_host, N, B, who, limit=None):
     """atoms per molecule as the caller knows them on the host; limit: the size a molecule may have (None: any, none negative)"""
     counts = [int(c) for c in atom_counts_host]
@@ -161,16 +167,21 @@ class MMBackend:
         return (table.to(device), int(table[0]), int(table[1]), int(n_confs))
 
     def nonbonded(self, xyz, atom_molptr, charge, sigma, epsilon, exc_ptr, exc_atom, exc_qq, exc_sigma, exc_eps, energy, term_energy=None, grad=None,
-                  plan=None) -> None:
+                  plan=None, cutoff=None, tiles=None) -> None:
         """Lennard-Jones + Coulomb energy and gradient over all pairs of every molecule (include/grappa_hip.h grappa_nonbonded_fwd_f32):
         xyz (N,C,3), atom_molptr (B+1,) int32, charge / sigma / epsilon (N,), the symmetric CSR exception table exc_ptr (N+1,) int32,
         exc_atom int32, exc_qq / exc_sigma / exc_eps (at least one element each) -> energy (B,C), term_energy (2,B,C) or None,
         grad (N,C,3) or None.  Angstrom, kcal/mol, elementary charges; the gradient is +dE/dxyz.
         plan: what `nonbonded_plan` returned for this atom_molptr and C (the work-item list built once on the host: one launch less and
         an exact grid); None: the list is built on the device by every call.  Same bits either way.
+        cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls above) -- grappa_nonbonded_fwd_cut_f32: a
+        reaction field and a switch below the cutoff, exceptions uncut, far tiles skipped; it needs `plan`.  tiles: an int32 tensor of
+        n_items or None -> the tiles each work item evaluated.
         Out of scope: gradients with respect to charge, sigma or epsilon (no autograd wrapper: the term has no learnable input);
-        cutoffs, periodic boxes, PME."""
+        periodic boxes, PME, a long-range Lennard-Jones correction."""
         _xyz3(xyz, "nonbonded")
+        if tiles is not None and cutoff is None:
+            raise ValueError("nonbonded: tiles needs a cutoff")
         dev = xyz.device
         tb = dict(atom_molptr=atom_molptr, exc_ptr=exc_ptr, exc_atom=exc_atom, charge=charge, sigma=sigma, epsilon=epsilon, exc_qq=exc_qq,
                  exc_sigma=exc_sigma, exc_eps=exc_eps)
@@ -184,10 +195,23 @@ class MMBackend:
         if energy.numel() != B * Cc or (term_energy is not None and term_energy.numel() != 2 * B * Cc) or (grad is not None and grad.shape != xyz.shape):
             raise ValueError("nonbonded: expected energy (B,C), term_energy (2,B,C), grad (N,C,3)")
         d = _nb_desc(N, Cc, B, xyz, tb)
+        if cutoff is not None and (plan is None or plan[0] is None) and N and Cc and B:
+            raise ValueError("nonbonded: a cutoff needs the plan of `nonbonded_plan` (the planned form is the only one with a cutoff)")
         if plan is not None and plan[0] is not None:
             table, n_items, n_blocks, plan_c = plan
             if plan_c != Cc or table.device != dev or table.dtype != torch.int32 or table.numel() < 4 + B + 1 + 4 * n_items:
                 raise ValueError(f"nonbonded: the plan was made for C = {plan_c} on {table.device}, the call has C = {Cc} on {dev}")
+            if cutoff is not None:
+                cut = _cut_struct(cutoff, "nonbonded")
+                if tiles is not None:
+                    _tensors(dev, ((tiles, "tiles", _I32),))
+                    if tiles.numel() != n_items:
+                        raise ValueError(f"nonbonded: tiles must hold one int32 per work item ({n_items})")
+                ws = self._workspace(int(self.lib.grappa_nonbonded_cut_workspace_bytes(Cc, n_blocks)), dev)
+                _chk(self.lib.grappa_nonbonded_fwd_cut_f32(self._stream(), C.byref(d), C.byref(cut), table.data_ptr(), n_items, n_blocks,
+                                                           energy.data_ptr(), _ptr(term_energy), _ptr(grad), _ptr(tiles), ws.data_ptr(), ws.numel()),
+                     "grappa_nonbonded_fwd_cut_f32")
+                return
             ws = self._workspace(16 * n_blocks * Cc, dev)
             _chk(self.lib.grappa_nonbonded_fwd_planned_f32(self._stream(), C.byref(d), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
                                                            _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()), "grappa_nonbonded_fwd_planned_f32")
@@ -375,14 +399,18 @@ class MMBackend:
         _chk(self.lib.grappa_md_langevin_f32(*head, *tail), "grappa_md_langevin_f32")
 
     def md_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
-                 frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None) -> None:
+                 frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None,
+                 cutoff=None) -> None:
         """stepwise Langevin dynamics for molecules of any size (include/grappa_hip.h grappa_md_steps_*_f32): the loop, the arguments
         and the outputs of `md_langevin`, but a molecule spans many workgroups, the state lives in device memory and a step is two
         launches.  opts: the whole run's (n_steps its total).  atom_counts_host (required): atoms per molecule on the host; the
         work-item table is the nonbonded plan built from it (reused from nb's cache of plans where nb keeps one).  steps_per_call:
         steps enqueued per run call at most (rounded down to a multiple of save_every when frames are written); the result does not
         depend on it.  There is NO device sync anywhere in it: init, the run calls and finish are only enqueued.  Status 3 does not
-        occur.  workspace: a uint8 tensor of at least `grappa_md_steps_workspace_bytes` to use instead of the backend's own."""
+        occur.  workspace: a uint8 tensor of at least `grappa_md_steps_workspace_bytes` to use instead of the backend's own.
+        cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls above, unchanged) -- the nonbonded force and
+        energies of grappa_md_steps_*_cut_f32: `nonbonded(..., cutoff=)`'s; it needs nb; the workspace is then
+        `grappa_md_steps_cut_workspace_bytes`; a step stays two launches."""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"md_steps: steps_per_call must be an integer >= 1, got {steps_per_call}")
         d, o = self._md_call("md_steps", plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
@@ -392,18 +420,27 @@ class MMBackend:
             raise ValueError("md_steps: atom_counts_host is required (the work-item table is built from it)")
         counts = _atom_counts(atom_counts_host, N, B, "md_steps")
         nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_steps")
+        cut = None
+        if cutoff is not None:
+            if nb is None:
+                raise ValueError("md_steps: a cutoff needs the nonbonded tables (nb)")
+            cut = _cut_struct(cutoff, "md_steps")
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        need = int(self.lib.grappa_md_steps_workspace_bytes(N, Cc, B, n_blocks))
+        need = int((self.lib.grappa_md_steps_workspace_bytes if cut is None else self.lib.grappa_md_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
         if workspace is None:
             workspace = self._workspace(need, dev, "md_steps")
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        head = (st, C.byref(d), ndp, C.byref(o))
+        if cut is None:
+            head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
+        else:
+            head, sfx = (st, C.byref(d), ndp, C.byref(cut), C.byref(o)), "_cut_f32"
+        init, run, finish = (getattr(self.lib, f"grappa_md_steps_{n}{sfx}") for n in ("init", "run", "finish"))
         tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
-        _chk(self.lib.grappa_md_steps_init_f32(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), "grappa_md_steps_init_f32")
+        _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), f"grappa_md_steps_init{sfx}")
         F = o.n_steps // o.save_every if o.save_every > 0 else 0
         every = o.save_every if F > 0 and any(t is not None for t in (frames_xyz, frames_epot, frames_ekin)) else 0
         chunk = int(steps_per_call)
@@ -415,10 +452,10 @@ class MMBackend:
             f0 = done // every if every > 0 else 0
             fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size()
                   for t in (frames_xyz, frames_epot, frames_ekin)]
-            _chk(self.lib.grappa_md_steps_run_f32(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), "grappa_md_steps_run_f32")
+            _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), f"grappa_md_steps_run{sfx}")
             done += n
-        _chk(self.lib.grappa_md_steps_finish_f32(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(),
-                                                 steps.data_ptr(), status.data_ptr()), "grappa_md_steps_finish_f32")
+        _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr()),
+             f"grappa_md_steps_finish{sfx}")
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

@@ -19,6 +19,10 @@
 //   and end  coordinates (mm_energy_kernel, nb_pairs_kernel + nb_reduce_kernel through their entry points: no second energy code path)
 //            and one small launch that adds the six terms in double in term order and the kinetic partials in ascending block order.
 //   noise  : csrc/md_noise.h, keyed by (mol_key, atom WITHIN the molecule, conformation, global step, purpose): the fused kernel's stream.
+//   cutoff : grappa_md_steps_*_cut_f32 (cut == NULL: the calls without).  The force launch is rs_force under the cut policy of
+//            csrc/nb_cut.h; the move launch's item writes the box of its own (block, conformations) after moving -- the box's only
+//            writer -- and the force launch reads all boxes across the launch boundary: a step stays two launches, init gains one (boxes
+//            and exception ranges).  Energies by grappa_nonbonded_fwd_cut_f32 at the held coordinates.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -40,10 +44,15 @@ struct MsWs {
     double* kpart;                       // [n_blocks][C]: sum m v^2 over the block's atoms
     float *e_mm, *e_nb, *terms;          // frames and finish: [B,C], [B,C], [6,B,C]
     double* nbpart;                      // frames and finish: the nonbonded kernel's partial energies [n_blocks][C][2]
+    float4* box;                         // with a cutoff: the blocks' boxes [n_blocks][C][2] and exception ranges [n_blocks] (csrc/nb_cut.h)
+    int2* er;
+    char* nbcut;                         // with a cutoff, frames and finish: the workspace of grappa_nonbonded_fwd_cut_f32
+    size_t nbcut_bytes;
     size_t total;
 };
 
-MsWs ms_layout(char* base, int N, int C, int B, int n_blocks) {
+// (the words of a cutoff lie behind the others: without one the layout is the one it was)
+MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false) {
     MsWs w;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -58,6 +67,12 @@ MsWs ms_layout(char* base, int N, int C, int B, int n_blocks) {
     w.kpart = (double*)take(8 * kc);
     w.e_mm = (float*)take(4 * bc), w.e_nb = (float*)take(4 * bc), w.terms = (float*)take(4 * 6 * bc);
     w.nbpart = (double*)take(8 * 2 * kc);
+    w.box = nullptr, w.er = nullptr, w.nbcut = nullptr, w.nbcut_bytes = 0;
+    if (cut) {
+        w.box = (float4*)take(sizeof(float4) * 2 * kc), w.er = (int2*)take(sizeof(int2) * (size_t)n_blocks);
+        w.nbcut_bytes = grappa_nonbonded_cut_workspace_bytes(C, n_blocks);
+        w.nbcut = take(w.nbcut_bytes);
+    }
     w.total = off;
     return w;
 }
@@ -121,23 +136,10 @@ struct MsMoveArgs {
     unsigned step;           // the global index of the step: the random stream's position
 };
 
-__global__ __launch_bounds__(NB_NT) void ms_move_kernel(MsMoveArgs a) {
-    __shared__ int stop[NB_CW];
-    RsItem r;
-    if (!rs_item(a.q, r)) return;
+// the thread's (atom, conformation) of the item; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
+template <bool CUT>
+__device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& r, int k0, const int* stop, float* bxl) {
     const int C = a.q.C, t = threadIdx.x, ni = r.ni;
-    // has a block of the molecule flagged the conformation?  Every workgroup of the molecule forms the same OR from the same words, which
-    // the force launch before this one wrote: wavefront w takes the conformations w, w + 4, .., its lanes the blocks
-    const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
-    const int wave = t / GRAPPA_WAVE, lane = t & (GRAPPA_WAVE - 1);
-    for (int cc = wave; cc < r.nc; cc += MS_NW) {
-        int f = 0;
-        for (int k = k0 + lane; k < k1; k += GRAPPA_WAVE) f |= a.bad[(size_t)k * C + r.c0 + cc];
-        const bool any = __builtin_amdgcn_ballot_w64(f != 0) != 0;
-        if (lane == 0) stop[cc] = any ? 1 : 0;
-    }
-    __syncthreads();
-    if (t >= ni * r.nc) return;
     const int cl = t / ni, il = t - cl * ni;
     const int i = r.i0 + il, c = r.c0 + cl;
     const size_t item = (size_t)r.mol * C + c;
@@ -160,9 +162,44 @@ __global__ __launch_bounds__(NB_NT) void ms_move_kernel(MsMoveArgs a) {
         xx += a.k.h2 * vk.x, xy += a.k.h2 * vk.y, xz += a.k.h2 * vk.z;
         a.x[off] = xx, a.x[off + 1] = xy, a.x[off + 2] = xz;
         a.v[off] = vk.x, a.v[off + 1] = vk.y, a.v[off + 2] = vk.z;
+        if constexpr (CUT) bxl[0] = xx, bxl[1] = xy, bxl[2] = xz;
+    } else if constexpr (CUT) {
+        const size_t off = ((size_t)i * C + c) * 3;
+        bxl[0] = a.x[off], bxl[1] = a.x[off + 1], bxl[2] = a.x[off + 2];
     }
     if (writer) a.steps[item] += 1;
 }
+
+// CUT: the item also writes the box of its own (block, conformations) at the coordinates it leaves (csrc/nb_cut.h): it is the box's only
+// writer, the force launch after it the reader.  A stopped conformation keeps its box, as it keeps its x.
+template <bool CUT>
+__device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
+    __shared__ int stop[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    // has a block of the molecule flagged the conformation?  Every workgroup of the molecule forms the same OR from the same words, which
+    // the force launch before this one wrote: wavefront w takes the conformations w, w + 4, .., its lanes the blocks
+    const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
+    const int wave = t / GRAPPA_WAVE, lane = t & (GRAPPA_WAVE - 1);
+    for (int cc = wave; cc < r.nc; cc += MS_NW) {
+        int f = 0;
+        for (int k = k0 + lane; k < k1; k += GRAPPA_WAVE) f |= a.bad[(size_t)k * C + r.c0 + cc];
+        const bool any = __builtin_amdgcn_ballot_w64(f != 0) != 0;
+        if (lane == 0) stop[cc] = any ? 1 : 0;
+    }
+    __syncthreads();
+    if constexpr (CUT) {
+        __shared__ float bx[NB_NT * 3];
+        if (t < ni * r.nc) ms_move_lane<true>(a, r, k0, stop, bx + 3 * t);
+        nb_cut_box_write(bx, stop, ni, r.nc, r.blk, C, r.c0, box);
+    } else {
+        if (t < ni * r.nc) ms_move_lane<false>(a, r, k0, stop, nullptr);
+    }
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_move_kernel(MsMoveArgs a) { ms_move_body<false>(a, nullptr); }
+__global__ __launch_bounds__(NB_NT) void ms_move_cut_kernel(MsMoveArgs a, float4* box) { ms_move_body<true>(a, box); }
 
 // ------------------------------------------------------------------------------------------------ force
 struct MsForceArgs {
@@ -175,9 +212,10 @@ struct MsForceArgs {
     float* frame_xyz;        // the frame this step writes, or NULL
 };
 
-__global__ __launch_bounds__(NB_NT) void ms_force_kernel(MsForceArgs a) {
+template <class Cut>
+__device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& cut) {
     __shared__ RsShared sh;
-    rs_force(a.f, sh, [&](const RsItem& r, const RsLane& w, V3 gi) {
+    rs_force(a.f, sh, cut, [&](const RsItem& r, const RsLane& w, V3 gi) {
         const int C = a.f.q.C, ni = r.ni;
         float mv2 = 0.f, bad = 0.f;
         if (w.owner) {
@@ -214,6 +252,38 @@ __global__ __launch_bounds__(NB_NT) void ms_force_kernel(MsForceArgs a) {
             a.bad[o] = fb != 0.f ? 1 : 0;
         }
     });
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_force_kernel(MsForceArgs a) { ms_force_body(a, NbNoCut{}); }
+
+__global__ __launch_bounds__(NB_NT) void ms_force_cut_kernel(MsForceArgs a, NbCutDev c) {
+    __shared__ unsigned char near[NB_NT];
+    ms_force_body(a, NbCut{c, near});
+}
+
+// with a cutoff, the launch of init between ms_init_kernel and the first force: the boxes of the item's (block, conformations) at x and,
+// by the item of the block's first conformations, the block's exception range
+struct MsBoxArgs {
+    RsGeom q;
+    const float* x;
+    const int *exc_ptr, *exc_atom;
+    float4* box;
+    int2* er;
+};
+
+__global__ __launch_bounds__(NB_NT) void ms_box_kernel(MsBoxArgs a) {
+    __shared__ float bx[NB_NT * 3];
+    __shared__ int2 er_s[NB_T];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int t = threadIdx.x;
+    if (t < r.ni * r.nc) {
+        const int cl = t / r.ni, il = t - cl * r.ni;
+        const float* p = a.x + ((size_t)(r.i0 + il) * a.q.C + r.c0 + cl) * 3;
+        bx[3 * t] = p[0], bx[3 * t + 1] = p[1], bx[3 * t + 2] = p[2];
+    }
+    if (r.c0 == 0) nb_cut_range_write(a.exc_ptr, a.exc_atom, r.i0, r.ni, r.m0, r.m1, r.blk, er_s, a.er);
+    nb_cut_box_write(bx, nullptr, r.ni, r.nc, r.blk, a.q.C, r.c0, a.box);
 }
 
 // ------------------------------------------------------------------------------------------------ energies and outputs
@@ -264,19 +334,40 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
-void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w, const float* mass,
-                     float hk, float* frame_xyz, int n_items) {
+// a cutoff as the three calls carry it: the caller's options and the device constants made of them (c == NULL: none)
+struct MsCut {
+    const grappa_nb_cut* opts;
+    NbCutDev dev;
+};
+
+// cut given: false if its options are refused or nb is missing; else the constants (box and er are set once the workspace is laid out)
+bool ms_cut_make(const grappa_nb_cut* cut, const grappa_nb_desc* nb, MsCut& c) {
+    c.opts = cut;
+    c.dev = NbCutDev{};
+    if (!nb || !nb_cut_consts(cut, c.dev.k, c.dev.thr)) return false;
+    c.dev.prune = cut->prune;
+    return true;
+}
+
+void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const RsGeom& q, const MsWs& w,
+                     const float* mass, float hk, float* frame_xyz, int n_items) {
     MsForceArgs f;
     f.f = rs_force_in(mm, nb, q, w.x, w.status);
     f.v = w.v, f.g = w.g, f.mass = mass, f.bad = w.bad, f.kpart = w.kpart;
     f.hk = hk, f.frame_xyz = frame_xyz;
-    GRAPPA_LAUNCH(ms_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
+    if (c) {
+        NbCutDev d = c->dev;
+        d.box = w.box, d.er = w.er;
+        GRAPPA_LAUNCH(ms_force_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d);
+    } else {
+        GRAPPA_LAUNCH(ms_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
+    }
 }
 
 // the six potential terms at the held coordinates by the library's own energy kernels: the bits of grappa_mm_energy_fwd_f32 and
-// grappa_nonbonded_fwd_planned_f32 there
-int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const int* table_dev, int n_items, int n_blocks,
-                    const MsWs& w) {
+// grappa_nonbonded_fwd_planned_f32 (with a cutoff: grappa_nonbonded_fwd_cut_f32) there
+int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const int* table_dev, int n_items,
+                    int n_blocks, const MsWs& w) {
     const size_t bc = (size_t)mm->B * mm->C;
     grappa_mm_desc me = *mm;
     me.xyz = w.x;
@@ -285,6 +376,9 @@ int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc
     grappa_nb_desc ne = *nb;
     ne.xyz = w.x;
     ne.atom_molptr = mm->atom_molptr;
+    if (c)
+        return grappa_nonbonded_fwd_cut_f32(stream, &ne, c->opts, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, nullptr, w.nbcut,
+                                            w.nbcut_bytes);
     return grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, w.nbpart,
                                             sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
 }
@@ -297,20 +391,13 @@ MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const 
     return a;
 }
 
-}  // namespace
-
-extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
-    return ms_layout(nullptr, N, C, B, n_blocks).total;
-}
-
-extern "C" int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
-                                        const float* mass, const unsigned long long* mol_key, const float* vel_in, const int* table_dev,
-                                        int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+// the three calls, with and without a cutoff (c == NULL: none)
+int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const float* mass,
+            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
@@ -323,14 +410,18 @@ extern "C" int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, 
     n = n > bc ? n : bc;
     n = n > kc ? n : kc;
     GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    if (n_items > 0) ms_launch_force(st, mm, nb, rs_geom(mm, table_dev, n_blocks), w, mass, 0.f, nullptr, n_items);
+    const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    if (c && n_items > 0) {
+        const MsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
+        GRAPPA_LAUNCH(ms_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+    }
+    if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
     return grappa_launch_status();
 }
 
-extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
-                                       const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks,
-                                       void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot,
-                                       float* frames_ekin) {
+int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const float* mass,
+           const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
+           float* frames_xyz, float* frames_epot, float* frames_ekin) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
@@ -338,7 +429,7 @@ extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, c
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
@@ -354,12 +445,13 @@ extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, c
         const size_t f = due ? (size_t)(done / o->save_every - 1 - frame0) : 0;
         if (n_items > 0) {
             mv.step = o->first_step + (unsigned)(step0 + s);
-            GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-            ms_launch_force(st, mm, nb, q, w, mass, k.hk, due && frames_xyz ? frames_xyz + f * n3 : nullptr, n_items);
+            if (c) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
+            else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
+            ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, due && frames_xyz ? frames_xyz + f * n3 : nullptr, n_items);
         }
         if (due && (frames_epot || frames_ekin)) {
             if (frames_epot) {
-                const int erc = ms_launch_terms(stream, mm, nb, table_dev, n_items, n_blocks, w);
+                const int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
                 if (erc != GRAPPA_OK) return erc;
             }
             MsOutArgs a = ms_out_args(mm, nb, q, w);
@@ -371,16 +463,16 @@ extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, c
     return grappa_launch_status();
 }
 
-extern "C" int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
-                                          const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
-                                          float* vel_out, float* epot, float* ekin, int* steps, int* status) {
+int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const int* table_dev,
+              int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+              int* status) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int erc = ms_launch_terms(stream, mm, nb, table_dev, n_items, n_blocks, w);
+    const int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
     if (erc != GRAPPA_OK) return erc;
     MsOutArgs a = ms_out_args(mm, nb, rs_geom(mm, table_dev, n_blocks), w);
     a.final = 1, a.with_epot = 1;
@@ -388,4 +480,64 @@ extern "C" int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
     GRAPPA_LAUNCH(ms_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     return grappa_launch_status();
+}
+
+}  // namespace
+
+extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return ms_layout(nullptr, N, C, B, n_blocks).total;
+}
+
+extern "C" int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                                        const float* mass, const unsigned long long* mol_key, const float* vel_in, const int* table_dev,
+                                        int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+    return ms_init(stream, mm, nb, nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+}
+
+extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                                       const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks,
+                                       void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot,
+                                       float* frames_ekin) {
+    return ms_run(stream, mm, nb, nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz, frames_epot,
+                  frames_ekin);
+}
+
+extern "C" int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
+                                          const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
+                                          float* vel_out, float* epot, float* ekin, int* steps, int* status) {
+    return ms_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
+}
+
+// with a cutoff: cut == NULL is the call above; bad options in cut, or a cut without nb, are refused before anything else is looked at
+extern "C" size_t grappa_md_steps_cut_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return ms_layout(nullptr, N, C, B, n_blocks, true).total;
+}
+
+extern "C" int grappa_md_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                            const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const float* vel_in,
+                                            const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+    MsCut c;
+    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+}
+
+extern "C" int grappa_md_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                           const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const int* table_dev,
+                                           int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz,
+                                           float* frames_epot, float* frames_ekin) {
+    MsCut c;
+    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
+                  frames_epot, frames_ekin);
+}
+
+extern "C" int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                              const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                              size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+                                              int* status) {
+    MsCut c;
+    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
 }

@@ -16,10 +16,15 @@
 //            No Newton's third law and no atomics: an atom's gradient is summed by its owner in a fixed j order, the slices are added
 //            in a fixed order through LDS, and the block's half-energies sum_i 1/2 sum_j e_ij are added over i in double.
 //   reduce : one workgroup per molecule adds the blocks' partial energies in double in a fixed order.
+//   cutoff : grappa_nonbonded_fwd_cut_f32 runs the same pairs kernel under the cut policy of csrc/nb_cut.h (OpenMM's CutoffNonPeriodic:
+//            reaction field, switch, exceptions uncut; nb_pair_cut of csrc/nb_pair.h) after one launch that writes the blocks' bounding
+//            boxes and exception ranges; the item then skips the j-blocks the rule of csrc/nb_cut.h calls far -- no neighbour list, no
+//            sort, no atomics, and the same bits as with every tile evaluated.
 // Same input, same bits.  A non-excluded pair at zero distance gives inf / NaN, as in OpenMM.
 #include <limits.h>
 
 #include "common.h"
+#include "nb_cut.h"
 #include "nb_pair.h"
 #include "nb_plan.h"      // NB_T, NB_TJ, NB_NT, NB_CW, NB_JS, nb_chunks, nb_clamp
 
@@ -84,10 +89,17 @@ struct NbArgs {
     int max_blk;       // rows of `part`
 };
 
-__global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
+// Cut: the compile-time cut policy of csrc/nb_cut.h (NbNoCut: all pairs; NbCut: nb_pair_cut for a pair that is no exception, far tiles
+// skipped, tiles[item] = the tiles evaluated)
+template <class Cut>
+__global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a, Cut cut, int* tiles) {
     __shared__ float4 xs[NB_TJ * NB_CW];      // j coordinates: [jj][conformation of the item]
     __shared__ float4 ps[NB_TJ];              // j parameters: q, sigma / 2, sqrt(eps)
     __shared__ float red[5][NB_NT];
+    if constexpr (Cut::on) {
+        __shared__ unsigned char near[NB_NT];
+        cut.near = near;
+    }
     if (a.hdr && (int)blockIdx.x >= a.hdr[0]) return;
     const grappa_nb_desc& d = a.d;
     const int4 it = a.items[blockIdx.x];
@@ -96,6 +108,8 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
     if (mol < 0 || mol >= d.B || blk < 0 || blk >= a.max_blk || c0 < 0 || c0 >= C) return;      // (a table made for another batch)
     const int m0 = nb_clamp(d.atom_molptr[mol], d.N), m1 = nb_clamp(d.atom_molptr[mol + 1], d.N);
     if (i0 < m0 || i0 >= m1) return;
+    const int ntiles = (m1 - m0 + NB_TJ - 1) / NB_TJ, kb0 = blk - (i0 - m0) / NB_T;      // (read by the cut policy only)
+    if (Cut::on && (kb0 < 0 || kb0 + ntiles > a.max_blk)) return;      // the boxes of the molecule's blocks are read
     const int ni = m1 - i0 < NB_T ? m1 - i0 : NB_T;
     int nch, ncb;
     nb_chunks(ni, C, nch, ncb);
@@ -120,7 +134,14 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
         nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
     }
     float elj = 0.f, ec = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    [[maybe_unused]] int count = 0;      // (the cut policy's: the tiles evaluated)
     for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
+        if constexpr (Cut::on) {      // NB_NT verdicts at a time; a far tile loads nothing and passes no barrier of the tile
+            const int jt = (j0 - m0) / NB_TJ, k = jt & (NB_NT - 1);
+            if (k == 0) nb_cut_decide(cut.c, C, blk, kb0, ntiles, jt, c0, nc, nullptr, cut.near);
+            if (!cut.near[k]) continue;
+            ++count;
+        }
         const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
         __syncthreads();
         for (int idx = t; idx < nj * nc; idx += NB_NT) {
@@ -142,8 +163,10 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
                         ++ep;
                         nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
                     }
+                    bool exc = false;      // (read by the cut policy only)
                     if (nx == j) {
                         const float q = d.exc_qq[ep], e = d.exc_eps[ep];
+                        exc = true;
                         sij = d.exc_sigma[ep];
                         e4 = 4.0f * e;
                         kqq = NB_K * q;
@@ -153,7 +176,12 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
                     }
                     if (!skip) {
                         const float4 x = xs[jj * NB_CW + cl];
-                        nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                        if constexpr (Cut::on) {      // an exception is not cut
+                            if (exc) nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                            else nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, cut.c.k, elj, ec, gx, gy, gz);
+                        } else {
+                            nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                        }
                     }
                 }
                 while (nx < j0 + nj) {      // partners that belong to other slices
@@ -166,10 +194,13 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
             for (int jj = s; jj < nj; jj += JS) {
                 const float4 p = ps[jj];
                 const float4 x = xs[jj * NB_CW + cl];
-                nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
+                if constexpr (Cut::on) nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, cut.c.k, elj, ec, gx, gy, gz);
+                else nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
             }
         }
     }
+    if constexpr (Cut::on)
+        if (tiles && t == 0) tiles[blockIdx.x] = count;
     // the slices of one (atom, conformation), added in slice order
     red[0][t] = elj, red[1][t] = ec, red[2][t] = gx, red[3][t] = gy, red[4][t] = gz;
     __syncthreads();
@@ -196,6 +227,32 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a) {
         double* o = a.part + ((size_t)blk * C + c) * 2;
         o[0] = 0.5 * slj, o[1] = 0.5 * sc;
     }
+}
+
+// the boxes of the item's (block, conformations) at d.xyz and, by the item of the block's first conformations, the block's exception
+// range (csrc/nb_cut.h): the launch before nb_pairs_kernel<NbCut>
+__global__ __launch_bounds__(NB_NT) void nb_box_kernel(NbArgs a, float4* box, int2* er) {
+    __shared__ float bx[NB_NT * 3];
+    __shared__ int2 er_s[NB_T];
+    const grappa_nb_desc& d = a.d;
+    const int4 it = a.items[blockIdx.x];
+    const int mol = it.x, i0 = it.y, blk = it.z, c0 = it.w;
+    const int C = d.C;
+    if (mol < 0 || mol >= d.B || blk < 0 || blk >= a.max_blk || c0 < 0 || c0 >= C) return;
+    const int m0 = nb_clamp(d.atom_molptr[mol], d.N), m1 = nb_clamp(d.atom_molptr[mol + 1], d.N);
+    if (i0 < m0 || i0 >= m1) return;
+    const int ni = m1 - i0 < NB_T ? m1 - i0 : NB_T;
+    int nch, ncb;
+    nb_chunks(ni, C, nch, ncb);
+    const int nc = C - c0 < ncb ? C - c0 : ncb;
+    const int t = threadIdx.x;
+    if (t < ni * nc) {
+        const int cl = t / ni, il = t - cl * ni;
+        const float* p = d.xyz + ((size_t)(i0 + il) * C + c0 + cl) * 3;
+        bx[3 * t] = p[0], bx[3 * t + 1] = p[1], bx[3 * t + 2] = p[2];
+    }
+    if (c0 == 0) nb_cut_range_write(d.exc_ptr, d.exc_atom, i0, ni, m0, m1, blk, er_s, er);
+    nb_cut_box_write(bx, nullptr, ni, nc, blk, C, c0, box);
 }
 
 // ------------------------------------------------------------------------------------------------ reduce
@@ -280,7 +337,7 @@ extern "C" int grappa_nonbonded_fwd_f32(void* stream, const grappa_nb_desc* d, f
     GRAPPA_LAUNCH(nb_setup_kernel, dim3(1), dim3(NB_NT), 0, st, d->N, d->C, d->B, d->atom_molptr, hdr, blk_ptr, items, (int)L.max_blk,
                   (int)L.max_items);
     NbArgs a{*d, hdr, items, part, grad, (int)L.max_blk};
-    GRAPPA_LAUNCH(nb_pairs_kernel, dim3((unsigned)L.max_items), dim3(NB_NT), 0, st, a);
+    GRAPPA_LAUNCH(nb_pairs_kernel<NbNoCut>, dim3((unsigned)L.max_items), dim3(NB_NT), 0, st, a, NbNoCut{}, (int*)nullptr);
     GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, part, energy, term_energy);
     return grappa_launch_status();
 }
@@ -329,7 +386,56 @@ extern "C" int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_de
     const int* blk_ptr = table_dev + 4;
     const int4* items = (const int4*)(table_dev + 4 + (((size_t)d->B + 1 + 3) & ~(size_t)3));
     NbArgs a{*d, nullptr, items, (double*)ws, grad, n_blocks};
-    if (n_items > 0) GRAPPA_LAUNCH(nb_pairs_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
+    if (n_items > 0) GRAPPA_LAUNCH(nb_pairs_kernel<NbNoCut>, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, NbNoCut{}, (int*)nullptr);
     GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, (const double*)ws, energy, term_energy);
+    return grappa_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ with a cutoff
+namespace {
+
+struct NbCutLayout {
+    size_t part, box, er, total;
+};
+NbCutLayout nb_cut_layout(int C, int n_blocks) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t kc = (size_t)n_blocks * (size_t)C;
+    NbCutLayout L;
+    L.part = 0;
+    L.box = L.part + up(sizeof(double) * 2 * kc);
+    L.er = L.box + up(sizeof(float4) * 2 * kc);
+    L.total = L.er + up(sizeof(int2) * (size_t)n_blocks);
+    return L;
+}
+
+}  // namespace
+
+extern "C" size_t grappa_nonbonded_cut_workspace_bytes(int C, int n_blocks) {
+    if (C <= 0 || n_blocks <= 0) return 0;
+    return nb_cut_layout(C, n_blocks).total;
+}
+
+extern "C" int grappa_nonbonded_fwd_cut_f32(void* stream, const grappa_nb_desc* d, const grappa_nb_cut* cut, const int* table_dev, int n_items,
+                                            int n_blocks, float* energy, float* term_energy, float* grad, int* tiles, void* ws, size_t ws_bytes) {
+    NbCutDev c;
+    if (!d || d->N < 0 || d->C < 0 || d->B < 0 || n_items < 0 || n_blocks < 0 || !nb_cut_consts(cut, c.k, c.thr)) return GRAPPA_ERR_ARG;
+    if (d->N == 0 || d->C == 0 || d->B == 0) return GRAPPA_OK;
+    if (nb_check(d, energy) != GRAPPA_OK || !table_dev || (n_blocks > 0 && !ws)) return GRAPPA_ERR_ARG;
+    if ((((uintptr_t)ws | (uintptr_t)table_dev) & 15) != 0) return GRAPPA_ERR_ARG;      // (float4 boxes, int4 items)
+    if (n_blocks > (long long)d->N / NB_T + d->B || (long long)n_blocks * d->C > INT_MAX) return GRAPPA_ERR_ARG;
+    const NbCutLayout L = nb_cut_layout(d->C, n_blocks);
+    if (n_blocks > 0 && ws_bytes < L.total) return GRAPPA_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    const int* blk_ptr = table_dev + 4;
+    const int4* items = (const int4*)(table_dev + 4 + (((size_t)d->B + 1 + 3) & ~(size_t)3));
+    NbArgs a{*d, nullptr, items, (double*)(w + L.part), grad, n_blocks};
+    c.prune = cut->prune;
+    c.box = (const float4*)(w + L.box), c.er = (const int2*)(w + L.er);
+    if (n_items > 0) {
+        GRAPPA_LAUNCH(nb_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, (float4*)(w + L.box), (int2*)(w + L.er));
+        GRAPPA_LAUNCH(nb_pairs_kernel<NbCut>, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, NbCut{c, nullptr}, tiles);
+    }
+    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, (const double*)(w + L.part), energy, term_energy);
     return grappa_launch_status();
 }

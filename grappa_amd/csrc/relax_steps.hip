@@ -122,7 +122,7 @@ struct RsForceArgs {
 
 __global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
     __shared__ RsShared sh;
-    rs_force(a.f, sh, [&](const RsItem& r, const RsLane& w, V3 gi) {
+    rs_force(a.f, sh, NbNoCut{}, [&](const RsItem& r, const RsLane& w, V3 gi) {
         const int C = a.f.q.C, ni = r.ni;
         float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
         if (w.owner) {

@@ -7,13 +7,15 @@
 //            nb_pairs_kernel (j-atoms through LDS in ascending blocks of 64, the sorted exception row walked in step with j, an exception
 //            replaces the pair, an exclusion or j == i is skipped, no pair energy kept), slices added in slice order.  What a kernel does
 //            with the gradient of an (atom, conformation) -- the minimiser's partials, the integrator's closing kick -- is its epilogue,
-//            a functor, the way rx_gradient of csrc/rx_force.h takes one.
+//            a functor, the way rx_gradient of csrc/rx_force.h takes one.  A compile-time cut policy (csrc/nb_cut.h) chooses between
+//            all pairs and a cutoff with tile pruning; there is one definition of the loop for both.
 // The workgroup reads x of the whole molecule and the status of its own conformations; it writes nothing itself.
 #pragma once
 #include <limits.h>
 
 #include "common.h"
 #include "mm_geom.h"
+#include "nb_cut.h"
 #include "nb_pair.h"
 #include "nb_plan.h"
 
@@ -106,15 +108,20 @@ __device__ inline V3 rs_bonded(const grappa_mm_desc& d, const float* __restrict_
     return bonded_gather(d, d.inc_ptr[i] + s, d.inc_ptr[i + 1], JS, [&](int atom) { return rs_ld(x, atom, d.N, d.C, c); });
 }
 
-// The item's force.  Every thread of the workgroup calls it; false: the table's item was refused or all of its conformations have
+// The item's force.  Cut is the compile-time cut policy of csrc/nb_cut.h: NbNoCut is the all-pairs force; NbCut evaluates a pair that is
+// no exception with nb_pair_cut and skips the tiles the rule of csrc/nb_cut.h calls far.  Every thread of the workgroup calls it; false: the table's item was refused or all of its conformations have
 // stopped, nothing was done and epi was not called.  Otherwise epi(r, w, g) runs in EVERY thread after the barrier that follows the slices' words in
 // sh.red (g is the gradient only where w.owner); it may use barriers, and must pass one before it writes sh.red.
-template <class Epi>
-__device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, Epi epi) {
+template <class Cut, class Epi>
+__device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, const Cut& cut, Epi epi) {
     RsItem r;
     if (!rs_item(a.q, r)) return false;
     const int C = a.q.C;
     if (!rs_running(r, C, a.status, sh.run)) return false;      // every conformation of the item has stopped: nothing of it is touched
+    if constexpr (Cut::on) {      // the boxes of the molecule's blocks are read: a table whose block numbers do not fit is walked away from
+        const int kb0 = r.blk - (r.i0 - r.m0) / NB_T;
+        if (kb0 < 0 || kb0 + (r.m1 - r.m0 + NB_TJ - 1) / NB_TJ > a.q.n_blocks) return false;
+    }
     const int ni = r.ni, nc = r.nc, i0 = r.i0, c0 = r.c0, m0 = r.m0, m1 = r.m1;
     const int NL = ni * nc;
     const int JS = NB_NT / NL < NB_JS ? NB_NT / NL : NB_JS;
@@ -143,7 +150,13 @@ __device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, Epi e
             nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
         }
         float elj = 0.f, ec = 0.f;      // (no pair energy is kept: dead code to the compiler)
+        [[maybe_unused]] const int ntiles = (m1 - m0 + NB_TJ - 1) / NB_TJ, kb0 = r.blk - (i0 - m0) / NB_T;      // (read by the cut policy only)
         for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
+            if constexpr (Cut::on) {      // NB_NT verdicts at a time; a far tile loads nothing and passes no barrier of the tile
+                const int jt = (j0 - m0) / NB_TJ, k = jt & (NB_NT - 1);
+                if (k == 0) nb_cut_decide(cut.c, C, r.blk, kb0, ntiles, jt, c0, nc, sh.run, cut.near);
+                if (!cut.near[k]) continue;
+            }
             const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
             __syncthreads();
             for (int idx = t; idx < nj * nc; idx += NB_NT) {
@@ -167,8 +180,10 @@ __device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, Epi e
                             ++ep;
                             nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
                         }
+                        bool exc = false;      // (read by the cut policy only)
                         if (nx == j) {
                             const float q = d.exc_qq[ep], e = d.exc_eps[ep];
+                            exc = true;
                             sij = d.exc_sigma[ep];
                             e4 = 4.0f * e;
                             kqq = NB_K * q;
@@ -178,7 +193,12 @@ __device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, Epi e
                         }
                         if (!skip) {
                             const float4 x = sh.xs[jj * NB_CW + cl];
-                            nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                            if constexpr (Cut::on) {      // an exception is not cut
+                                if (exc) nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                                else nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, cut.c.k, elj, ec, gx, gy, gz);
+                            } else {
+                                nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
+                            }
                         }
                     }
                     while (nx < j0 + nj) {      // partners that belong to other slices
@@ -191,7 +211,8 @@ __device__ __forceinline__ bool rs_force(const RsForceIn& a, RsShared& sh, Epi e
                 for (int jj = s; jj < nj; jj += JS) {
                     const float4 p = sh.ps[jj];
                     const float4 x = sh.xs[jj * NB_CW + cl];
-                    nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
+                    if constexpr (Cut::on) nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, cut.c.k, elj, ec, gx, gy, gz);
+                    else nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
                 }
             }
         }

@@ -8,8 +8,13 @@ optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all
             waits for the device.  `stepwise=True` takes it for the whole batch, `stepwise="auto"` for a batch that holds a molecule
             above the limit (a batch is never split between the two paths).
 The two paths add in different orders: the same trajectory within rounding, not the same bits.  Which of them is faster for a batch
-that both take has not been decided here (tools/md_steps_bench.py measures it).  Cutoffs, periodic boxes and PME are out of scope
-(OpenMM / GROMACS).
+that both take has not been decided here (tools/md_steps_bench.py measures it).
+
+Cutoff (`cutoff=`, a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom): the nonbonded term under OpenMM's `CutoffNonPeriodic`
+conventions -- reaction field, optional switch, exceptions uncut (`grappa_amd.nonbonded` states them) -- on the stepwise path only,
+whose force launch then skips the 64 x 64 atom tiles that lie beyond the cutoff; a step stays two launches.  It needs `nonbonded`;
+`stepwise="auto"` goes stepwise whenever a cutoff is given.  The stepwise minimiser, the fused kernels, periodic boxes, PME and a
+long-range Lennard-Jones correction are out of scope (OpenMM / GROMACS).
 
 Constraints (`constraints=`, `grappa_amd.constraints`): X-H bonds held at fixed lengths, on the fused path only.  The loop is then
 g-BAOAB (Leimkuhler and Matthews, Proc. R. Soc. A 472, 20160138 (2016)) with one geodesic sub-step, csrc/dynamics_cons.hip
@@ -38,7 +43,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .nonbonded import NonbondedBatch, NonbondedParameters
+from .nonbonded import NonbondedBatch, NonbondedParameters, as_cutoff
 from .parameters import Parameters
 from .relax import _stepwise_options, graph_coordinates, graph_force_field, graph_from_parameters
 
@@ -131,7 +136,8 @@ def _host_keys(keys, seed, B):
 
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                   offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, **opts) -> MDResult:
+                   offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, cutoff=None,
+                   **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -150,10 +156,21 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     velocities projected first; False continues a run (with its xyz, velocities and first_step) bit for bit.  The first launch of
     a run gets the caller's constrain_start, later launches continue.  Statuses 4 and 5: see the module text; an item that ends with
     either in one launch of a run keeps that launch's results: later launches add no steps and no frames (NaN) for it.  A moving centre
-    whose frozen leaves alone number four is refused (ValueError): they over-determine it."""
+    whose frozen leaves alone number four is refused (ValueError): they over-determine it.
+    cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls made are exactly those without this argument):
+    see the module text.  It needs `nonbonded` and the stepwise path: "auto" then goes stepwise whatever the sizes, stepwise=False and
+    constraints are refused."""
     from .backend import get_backend
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
+    cutoff = as_cutoff(cutoff)
+    if cutoff is not None:
+        if nonbonded is None:
+            raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
+        if stepwise is False:
+            raise ValueError('simulate: a cutoff runs on the stepwise path only: pass stepwise="auto" (or True)')
+        if constraints is not None:
+            raise ValueError("simulate: constraints run on the fused path only, a cutoff on the stepwise path only")
     if isinstance(steps_per_launch, bool) or not isinstance(steps_per_launch, (int, np.integer)) or steps_per_launch < 1:
         raise ValueError(f"steps_per_launch must be an integer >= 1, got {steps_per_launch!r}")
     if isinstance(first_step, bool) or int(first_step) != first_step or first_step < 0 or int(first_step) + o["n_steps"] >= 2 ** 32:
@@ -166,7 +183,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if above and stepwise is False:
         raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
                          f"(stepwise=True or stepwise='auto' runs molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and above)
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None))
     if constraints is not None:
         from .constraints import ConstraintBatch
         if not isinstance(constraints, ConstraintBatch):
@@ -228,7 +245,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
         if use_steps:
-            get_backend().md_steps(*args, steps_per_call=chunk, **kw)
+            get_backend().md_steps(*args, steps_per_call=chunk, **kw, **({} if cutoff is None else {"cutoff": cutoff}))
         elif constraints is not None:
             get_backend().md_langevin(*args, **kw, constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
         else:
@@ -260,21 +277,30 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
              seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, constraints=None,
-             constrain_start: bool = True, **opts) -> MDResult:
+             constrain_start: bool = True, cutoff=None, **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
     (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  stepwise: see `simulate_graph`
     (the stepwise path takes a molecule of any size).  constraints: the molecule's `grappa_amd.constraints.Constraints` in the order of
-    `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`."""
+    `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`.  cutoff: see `simulate_graph`."""
     md_options(**opts)
     _stepwise_options(stepwise, 1)
     extra = {}
+    cutoff = as_cutoff(cutoff)
+    if cutoff is not None:
+        if nonbonded is None:
+            raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
+        if stepwise is False:
+            raise ValueError('simulate: a cutoff runs on the stepwise path only: pass stepwise="auto" (or True)')
+        if constraints is not None:
+            raise ValueError("simulate: constraints run on the fused path only, a cutoff on the stepwise path only")
+        extra["cutoff"] = cutoff
     if constraints is not None:
         from .constraints import ConstraintBatch, Constraints
         if not isinstance(constraints, Constraints):
             raise TypeError(f"constraints must be a Constraints or None, got {type(constraints).__name__}")
-        extra = dict(constraints=ConstraintBatch([constraints]), constrain_start=constrain_start)
+        extra.update(constraints=ConstraintBatch([constraints]), constrain_start=constrain_start)
     g = graph_from_parameters(parameters, xyz)
     n = g.num_nodes("n1")
     nb = None

@@ -69,15 +69,20 @@ class Grappa:
         from .relax import torsion_scan
         return torsion_scan(self.predict(molecule), xyz, dihedral, angles, nonbonded, device=self.device, **kw)
 
-    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, **kw):
+    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
         the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
         (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules of any size.  **kw: velocities,
         seed, keys, first_step, steps_per_launch, constrain_start and the options of `MD_DEFAULTS` (see
         `grappa_amd.dynamics.simulate_graph`).  constraints: None, "h-bonds" (every X-H bond held at its predicted equilibrium length:
-        `grappa_amd.constraints.hydrogen_constraints`) or a `Constraints` in the molecule's atom order; the fused path only"""
+        `grappa_amd.constraints.hydrogen_constraints`) or a `Constraints` in the molecule's atom order; the fused path only.
+        cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom (None: all pairs): the nonbonded term with a cutoff and a
+        reaction field on the stepwise path, which skips the atom tiles beyond it -- what makes a protein fast, not only movable; it
+        needs `nonbonded` and stepwise="auto" (or True), and refuses constraints"""
         from .dynamics import simulate
+        if cutoff is not None:
+            kw = {**kw, "cutoff": cutoff}
         masses = [constants.ATOMIC_MASSES[int(z)] for z in molecule.atomic_numbers]
         parameters = self.predict(molecule)
         if isinstance(constraints, str):

@@ -12,16 +12,59 @@ An exception replaces the pair's interaction; with epsilon 0 and charge product 
 excluded atoms may sit on one point).  A non-excluded pair at zero distance gives inf / NaN, as in OpenMM.  Atoms of different
 molecules of a batch never interact.
 
+With `cutoff=` (a `Cutoff`, or a plain distance) the semantics are those of OpenMM's `CutoffNonPeriodic`: a pair that is no exception
+contributes only below the cutoff rc, its Lennard-Jones energy times the switch S (1 up to `switch_distance` rs, then
+1 - 10 u^3 + 15 u^4 - 6 u^5 with u = (r - rs)/(rc - rs)), its Coulomb energy as the reaction field K q_i q_j (1/r + k_rf r^2 - c_rf) with
+k_rf = (eps - 1)/((2 eps + 1) rc^3), c_rf = 3 eps/((2 eps + 1) rc), which vanishes at rc.  Exceptions are not cut: an exception is
+evaluated at any distance with the plain formulas.  The kernel skips whole tiles of 64 x 64 atoms whose bounding boxes lie farther apart
+than rc (include/grappa_hip.h grappa_nb_cut states the rule); the bits do not depend on it.
+
 The arithmetic runs in csrc/nonbonded.hip through `HipBackend.nonbonded`; there is no CPU evaluator.  Out of scope: gradients with
-respect to charges, sigma or epsilon; cutoffs, periodic boxes, PME.
+respect to charges, sigma or epsilon; periodic boxes, PME, a long-range Lennard-Jones correction.
 """
+import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 _KEYS = ("charge", "sigma", "epsilon", "exception_idx", "exception_chargeprod", "exception_sigma", "exception_epsilon")
+
+
+@dataclass(frozen=True)
+class Cutoff:
+    """a nonbonded cutoff (grappa_nb_cut): distance rc in Angstrom (finite, > 0); switch_distance None or 0 (no switch) or inside
+    (0, distance); rf_dielectric finite and >= 1 (1: no reaction field, a shifted Coulomb).  prune=False evaluates every tile: the same
+    bits, slower -- it is there to measure what the skipped tiles are worth."""
+    distance: float
+    switch_distance: Optional[float] = None
+    rf_dielectric: float = 78.3
+    prune: bool = True
+
+    def __post_init__(self):
+        num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))      # noqa: E731
+        if not num(self.distance) or not (math.isfinite(self.distance) and self.distance > 0):
+            raise ValueError(f"cutoff: distance must be a finite number > 0, got {self.distance!r}")
+        rs = self.switch_distance
+        if rs is not None and (not num(rs) or not (rs == 0 or 0 < rs < self.distance)):
+            raise ValueError(f"cutoff: switch_distance must be None, 0 or inside (0, {self.distance}), got {rs!r}")
+        if not num(self.rf_dielectric) or not (math.isfinite(self.rf_dielectric) and self.rf_dielectric >= 1):
+            raise ValueError(f"cutoff: rf_dielectric must be a finite number >= 1, got {self.rf_dielectric!r}")
+        if not isinstance(self.prune, (bool, np.bool_)):
+            raise ValueError(f"cutoff: prune must be True or False, got {self.prune!r}")
+
+    def as_opts(self) -> dict:
+        """the four fields of grappa_nb_cut by name"""
+        return {"cutoff": float(self.distance), "switch_distance": float(self.switch_distance or 0.0), "rf_dielectric": float(self.rf_dielectric),
+                "prune": int(bool(self.prune))}
+
+
+def as_cutoff(cutoff: Union[None, float, "Cutoff"]) -> Optional["Cutoff"]:
+    """None, a `Cutoff`, or a plain distance (-> Cutoff(distance)), checked"""
+    if cutoff is None or isinstance(cutoff, Cutoff):
+        return cutoff
+    return Cutoff(cutoff)
 
 
 def _f64(x, shape=None):
@@ -172,10 +215,12 @@ class NonbondedBatch:
         col = lambda t: t.cpu().numpy()[lo:hi][keep]      # noqa: E731
         return np.stack([own[keep] - a0, partner[keep] - a0], axis=1).reshape(-1, 2), col(self.exc_qq), col(self.exc_sigma), col(self.exc_eps)
 
-    def evaluate(self, xyz: torch.Tensor, terms: bool = False, gradient: bool = True):
+    def evaluate(self, xyz: torch.Tensor, terms: bool = False, gradient: bool = True, cutoff=None):
         """xyz (N, C, 3) float32 on the batch's device (the layout of g.nodes['n1'].data['xyz']) -> energy (B, C), gradient (N, C, 3)
-        [, term_energy (2, B, C): Lennard-Jones, Coulomb].  gradient=False: (energy, None [, term_energy])."""
+        [, term_energy (2, B, C): Lennard-Jones, Coulomb].  gradient=False: (energy, None [, term_energy]).  cutoff: a `Cutoff` or a
+        distance (None: all pairs, the call it always was)."""
         from .backend import get_backend
+        cutoff = as_cutoff(cutoff)
         if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
             raise ValueError(f"xyz must be a float32 (N, C, 3) tensor, got {getattr(xyz, 'dtype', type(xyz))} {tuple(getattr(xyz, 'shape', ()))}")
         if xyz.shape[0] != self.N or xyz.device != self.charge.device:
@@ -189,16 +234,18 @@ class NonbondedBatch:
         energy = torch.zeros(self.B, C, dtype=torch.float32, device=xyz.device)
         grad = torch.zeros_like(xyz) if gradient else None
         te = torch.zeros(2, self.B, C, dtype=torch.float32, device=xyz.device) if terms else None
+        extra = {} if cutoff is None else {"cutoff": cutoff}
         be.nonbonded(xyz, self.atom_molptr, self.charge, self.sigma, self.epsilon, self.exc_ptr, self.exc_atom, self.exc_qq, self.exc_sigma,
-                     self.exc_eps, energy, te, grad, plan=plan)
+                     self.exc_eps, energy, te, grad, plan=plan, **extra)
         return (energy, grad, te) if terms else (energy, grad)
 
 
-def nonbonded_energy(params, xyz, device="cuda", terms: bool = False):
+def nonbonded_energy(params, xyz, device="cuda", terms: bool = False, cutoff=None):
     """Energies and gradients of one molecule or a list of molecules, numpy in and out.  xyz: (n_confs, n_atoms, 3) in Angstrom (the
     MolData convention), or a list of such arrays sharing n_confs, one per NonbondedParameters.
     -> (energy (n_confs,), gradient (n_confs, n_atoms, 3)) in kcal/mol and kcal/mol/A, with terms=True followed by the Lennard-Jones
-    and the Coulomb part of the energy; for a list, a list of such tuples."""
+    and the Coulomb part of the energy; for a list, a list of such tuples.  cutoff: a `Cutoff` or a distance (None: all pairs)."""
+    cutoff = as_cutoff(cutoff)
     single = isinstance(params, NonbondedParameters)
     plist: List[NonbondedParameters] = [params] if single else list(params)
     xs = [np.asarray(xyz)] if single else [np.asarray(x) for x in xyz]
@@ -209,7 +256,7 @@ def nonbonded_energy(params, xyz, device="cuda", terms: bool = False):
             raise ValueError(f"xyz must be (n_confs, {p.n_atoms}, 3) with one n_confs for all molecules, got {x.shape}")
     nb = NonbondedBatch(plist).to(device)
     flat = np.concatenate([x.transpose(1, 0, 2) for x in xs], axis=0).astype(np.float32)
-    out = nb.evaluate(torch.from_numpy(np.ascontiguousarray(flat)).to(device), terms=terms)
+    out = nb.evaluate(torch.from_numpy(np.ascontiguousarray(flat)).to(device), terms=terms, **({} if cutoff is None else {"cutoff": cutoff}))
     energy, grad = out[0].cpu().numpy(), out[1].cpu().numpy()
     te = out[2].cpu().numpy() if terms else None
     ptr = nb.atom_molptr.cpu().numpy()

@@ -491,7 +491,7 @@ int grappa_mm_bwd_f32(void* stream, const grappa_mm_desc* d, const float* gE, co
  * of its atoms (partners outside the atom's molecule are ignored).  The five exc_* arrays must be non-NULL (one unused element when
  * the table is empty).  term_energy[2,B,C] = the Lennard-Jones and the Coulomb part (NULL: not written); grad NULL: not written.
  * Fixed-order sums, no atomics: same input, same bits, and a molecule's results do not depend on its place in the batch.
- * No gradients with respect to charge / sigma / epsilon; no cutoff, periodic box or PME.
+ * No gradients with respect to charge / sigma / epsilon; no periodic box or PME (a cutoff: grappa_nonbonded_fwd_cut_f32 below).
  * GRAPPA_ERR_ARG: a NULL required pointer or a negative size; N == 0, C == 0 or B == 0: returns 0 without a launch. */
 #define GRAPPA_NB_IBLOCK 64      /* i-atoms per workgroup: molecule sizes around its multiples are the kernel's edges */
 typedef struct grappa_nb_desc {
@@ -516,6 +516,44 @@ int grappa_nonbonded_fwd_f32(void* stream, const grappa_nb_desc* d, float* energ
 long long grappa_nonbonded_plan(int N, int C, int B, const int* atom_molptr_host, int* table, long long table_ints);
 int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_desc* d, const int* table_dev, int n_items, int n_blocks, float* energy,
                                      float* term_energy, float* grad, void* ws, size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same with a cutoff (additions to ABI 11): the conventions of OpenMM's NonbondedForce with CutoffNonPeriodic, stated in full.
+ * With rc = cutoff, rs = switch_distance and eps = rf_dielectric, a pair that is NOT an exception contributes, for r < rc,
+ *   E_lj = S(r) 4 eps_ij ((s_ij/r)^12 - (s_ij/r)^6),  S = 1 for r <= rs or rs == 0, else 1 - 10 u^3 + 15 u^4 - 6 u^5, u = (r - rs)/(rc - rs)
+ *   E_c  = K q_i q_j (1/r + k_rf r^2 - c_rf),  k_rf = (eps - 1) / ((2 eps + 1) rc^3),  c_rf = 3 eps / ((2 eps + 1) rc)   (E_c(rc) = 0)
+ * and the exact derivative of these, the dS/dr term included; for r >= rc nothing, by a branch: the test is r2 < rc2 with r2 the fp32
+ * value the pair code forms and rc2 rounded once from (double)rc * rc (a NaN r2 is evaluated and gives a non-finite gradient, as
+ * today).  EXCEPTIONS ARE NOT CUT: an exception is evaluated at any distance with the plain formulas above, without reaction field and
+ * without switch; an exclusion is skipped.  term_energy[0] = the switched Lennard-Jones part, term_energy[1] = the Coulomb part with
+ * the reaction-field terms.  Planned form only: table_dev, n_items, n_blocks are grappa_nonbonded_plan's (table and ws 16-byte aligned).
+ * Tiles.  The work item of i-block I walks its molecule's atoms in tiles of GRAPPA_NB_IBLOCK j-atoms; tile J of a molecule is its
+ * block J (counted from the molecule's first atom).  With prune == 1 an item skips the tiles that cannot hold a pair within rc:
+ *   boxes  : for each (block, conformation), lo and hi = the exact fp32 minimum and maximum of the block's coordinates per axis.
+ *   range  : for each block I, [e_lo, e_hi] = the first and last tile of the molecule that holds an exception partner of one of the
+ *            block's atoms, taken from the first and last entry of each atom's (ascending) partner list with the partner clamped
+ *            into the molecule; empty if no atom of the block has an entry.
+ *   rule   : tile (I, J) of an item is evaluated iff  prune == 0,  or  e_lo(I) <= J <= e_hi(I),  or  for some conformation of the
+ *            item (in the dynamics: some conformation that still runs)  NOT d2 > thr,  where
+ *            d2 = ((gx * gx) + (gy * gy)) + (gz * gz),  g_axis = max(0, lo_I - hi_J, lo_J - hi_I),  every operation rounded to fp32,
+ *            thr = (float)((double)rc2 * (1 + 2^-18)).  A non-finite box compares as near.
+ * One launch writes boxes and ranges into the workspace, the next reads them; the decision is uniform over the workgroup.  A skipped
+ * tile holds only pairs the branch above rejects (the margin 2^-18 covers the rounding of r2 and of d2: DESIGN.md section 17), so
+ * prune == 0 and prune == 1 give the same bits.  tiles[k] (NULL: not written) = the tiles item k evaluated, written by its thread 0.
+ * GRAPPA_ERR_ARG, nothing launched and nothing written: the cases of grappa_nonbonded_fwd_planned_f32, a NULL cut, a cutoff that is not
+ * finite and > 0, a switch_distance that is neither 0 nor inside (0, cutoff), an rf_dielectric that is not finite and >= 1, a prune
+ * other than 0 or 1, a table or workspace that is not 16-byte aligned.  ws_bytes below grappa_nonbonded_cut_workspace_bytes(C, n_blocks)
+ * (about 56 n_blocks C bytes): GRAPPA_ERR_WORKSPACE.  3 launches.  No periodic box, no PME, no long-range Lennard-Jones correction. */
+typedef struct grappa_nb_cut {
+    float cutoff;           /* A, finite, > 0 */
+    float switch_distance;  /* 0: none; else 0 < switch_distance < cutoff */
+    float rf_dielectric;    /* finite, >= 1 (1: k_rf = 0, a shifted Coulomb) */
+    int   prune;            /* 1: skip far tiles; 0: evaluate every tile -- the same bits */
+} grappa_nb_cut;
+size_t grappa_nonbonded_cut_workspace_bytes(int C, int n_blocks);
+int grappa_nonbonded_fwd_cut_f32(void* stream, const grappa_nb_desc* d, const grappa_nb_cut* cut, const int* table_dev, int n_items,
+                                 int n_blocks, float* energy, float* term_energy, float* grad, int* tiles /*[n_items] or NULL*/, void* ws,
+                                 size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Relaxation under the full MM force field (additions to ABI 11): FIRE (Bitzek et al. 2006) with unit masses and semi-implicit Euler,
@@ -804,6 +842,25 @@ int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa
 int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out,
                                float* epot, float* ekin, int* steps, int* status);
+/* The stepwise dynamics under a nonbonded cutoff (additions to ABI 11): the three calls above with `const grappa_nb_cut* cut` after nb.
+ * cut == NULL forwards to the call above, with its launches and its bits; cut != NULL needs nb (else GRAPPA_ERR_ARG) and bad options in
+ * cut are GRAPPA_ERR_ARG, nothing launched and nothing written.  The force is then that of grappa_nonbonded_fwd_cut_f32 (same formulas,
+ * same skip rule; a conformation that has stopped is not looked at by the rule).  A step stays TWO launches: the move launch's work item
+ * writes the box of its own (block, conformations) after moving -- it is the box's only writer, and a stopped conformation keeps its box
+ * as it keeps its x -- and the force launch reads all boxes across the launch boundary.  init gains one launch (boxes and ranges): 3.
+ * epot and frames_epot come from the kernels of grappa_nonbonded_fwd_cut_f32 at the held coordinates: its bits there.  Pass the same cut
+ * to all three calls.  The workspace is grappa_md_steps_cut_workspace_bytes(N, C, B, n_blocks): the one above plus about 88 n_blocks C. */
+size_t grappa_md_steps_cut_workspace_bytes(int N, int C, int B, int n_blocks);
+int grappa_md_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                 const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const float* vel_in,
+                                 const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const int* table_dev,
+                                int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz,
+                                float* frames_epot, float* frames_ekin);
+int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                   const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+                                   float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

@@ -15,6 +15,14 @@ child process of its own under a time limit; the parent never initialises the GP
 nothing after it; at most one GPU process runs at a time.
 
     python tools/md_steps_bench.py [--out profiles/md_steps_bench.txt] [--steps 500] [--big-steps 20] [--composed-steps 50]
+
+With --cutoff RC [--switch RS] the tool measures the nonbonded cutoff instead (same protocol: device events, one warm-up run, five timed
+runs, every GPU stage a child process under its own time limit).  Per workload, in the same visit: the stepwise path with all pairs,
+with the cutoff and tile pruning (prune = 1), with the cutoff and every tile evaluated (prune = 0: what the per-pair test alone costs),
+and the tiles the cut energy kernel evaluates per work item at the start coordinates against all tiles.  All five times of each side are
+printed: the acceptance on the 50,046-atom graph is "the slowest pruned run is faster than the fastest all-pairs run".
+
+    python tools/md_steps_bench.py --cutoff 10 [--switch 8] [--out profiles/md_steps_cutoff_bench.txt]
 """
 import argparse
 import datetime
@@ -31,7 +39,8 @@ from md_bench import OPTS, Composed, _batch, _timed      # noqa: E402
 
 WORKLOADS = ("pool", "mid", "big")
 SIDES = {"pool": ("fused", "stepwise", "composed", "agreement"), "mid": ("stepwise", "composed"), "big": ("stepwise", "composed")}
-STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w]]
+CUT_SIDES = ("stepwise", "cut", "cut_noprune", "tiles")
+STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:]]
 STAGE_LIMIT = 300      # seconds, every stage
 AGREEMENT_STEPS = 50
 CARBON = 12.011
@@ -48,6 +57,22 @@ def _workload(args, which):
     n = args.mid_atoms if which == "mid" else args.big_atoms
     gh, nbp = chain_graph(n)
     return gh.to("cuda"), NonbondedBatch([nbp]).to("cuda"), np.full(n, CARBON, dtype=np.float32), 1, args.steps if which == "mid" else args.big_steps
+
+
+def _all_timed(fn, reps):
+    """md_bench._timed's protocol (one warm-up run, device events around whole runs), every time kept"""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        us.append(a.elapsed_time(b) * 1e3)
+    return us
 
 
 def stage(args):
@@ -69,8 +94,24 @@ def stage(args):
     out = {"molecules": len(counts), "atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max()), "confs": confs}
     sim = lambda n, stepwise, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, stepwise=stepwise,      # noqa: E731
                                                    **{**OPTS, **kw})
-    if side in ("fused", "stepwise"):
-        sw = side == "stepwise"
+    if side in ("cut", "cut_noprune", "tiles"):
+        from grappa_amd.nonbonded import Cutoff
+        cut = Cutoff(args.cutoff, args.switch or None, prune=side != "cut_noprune")
+    if side == "tiles":          # what the cut energy kernel evaluates at the start coordinates, per work item
+        x = g.nodes["n1"].data["xyz"].contiguous()
+        plan = be.nonbonded_plan(nb.atom_molptr_host, nb.N, x.shape[1], x.device)
+        e = torch.empty(nb.B, x.shape[1], device=x.device)
+        t = {}
+        for prune in (True, False):
+            t[prune] = torch.zeros(plan[1], dtype=torch.int32, device=x.device)
+            be.nonbonded(x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps, e, None, None,
+                         plan=plan, cutoff=Cutoff(args.cutoff, args.switch or None, prune=prune), tiles=t[prune])
+        out["items"], out["tiles"], out["all_tiles"] = int(plan[1]), int(t[True].sum()), int(t[False].sum())
+    elif side in ("fused", "stepwise", "cut", "cut_noprune"):
+        sw = side != "fused"
+        if side.startswith("cut"):
+            plain = sim
+            sim = lambda n, stepwise, **kw: plain(n, stepwise, cutoff=cut, **kw)      # noqa: E731
         n0 = be.lib.grappa_launch_count(0)
         r = sim(steps, sw)
         torch.cuda.synchronize()
@@ -78,6 +119,9 @@ def stage(args):
         # (an item that meets a non-finite gradient stops early: the rate counts the steps that were run)
         out["item_steps"], out["stopped"] = int(r.steps.sum()), int((r.status != 0).sum())
         out["median_us"], out["min_us"] = _timed(lambda: sim(steps, sw), args.reps)
+        if args.cutoff:          # every run of the five: the acceptance compares the slowest of one side with the fastest of another
+            out["all_us"] = _all_timed(lambda: sim(steps, sw), args.reps)
+            out["median_us"], out["min_us"] = float(sorted(out["all_us"])[len(out["all_us"]) // 2]), min(out["all_us"])
     elif side == "composed":
         c = Composed(be, g, nb, masses, OPTS["friction"])          # tables, clones and the nonbonded work-item list: outside the timed region
         v0 = sim(0, True).velocities
@@ -119,6 +163,8 @@ def main():
     ap.add_argument("--steps-per-launch", type=int, default=10000)
     ap.add_argument("--composed-steps", type=int, default=50)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
+    ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -133,7 +179,7 @@ def main():
     def run(name):
         cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
               [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
-                                                                      "composed_steps", "reps")]
+                                                                      "composed_steps", "reps", "cutoff", "switch")]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
             sys.stderr.write(p.stdout + p.stderr)
@@ -150,7 +196,25 @@ def main():
     say(f"# device: {run('device')['device']}")
     say("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; steps/s = steps of the run / "
         "run time, whatever the batch holds; this file is the tool's output, unedited")
-    for w in WORKLOADS:
+    if args.cutoff:
+        say(f"# cutoff {args.cutoff} A, switch {args.switch or 'none'}, reaction field 78.3; all five run times of each side in ms; tiles: evaluated by the cut "
+            "energy kernel at the start coordinates, summed over its work items")
+        for w in WORKLOADS:
+            res = {side: run(f"{w}:{side}") for side in CUT_SIDES}
+            r = res["stepwise"]
+            say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms ({r['smallest']}..{r['largest']} per molecule), C = {r['confs']}, "
+                f"bonded + nonbonded, dt {OPTS['dt']} ps, {OPTS['temperature']} K, friction {OPTS['friction']} / ps")
+            rate = {}
+            for side, what in (("stepwise", "all pairs"), ("cut", "cut, prune=1"), ("cut_noprune", "cut, prune=0")):
+                rate[side] = report(f"{what:12s}", res[side])
+                say(f"               runs: {', '.join(f'{u / 1e3:.2f}' for u in res[side]['all_us'])} ms")
+            t = res["tiles"]
+            say(f"  tiles: {t['tiles']} of {t['all_tiles']} evaluated over {t['items']} work items: mean {t['tiles'] / max(t['items'], 1):.2f} of "
+                f"{t['all_tiles'] / max(t['items'], 1):.2f} per item ({100.0 * t['tiles'] / max(t['all_tiles'], 1):.1f} %)")
+            say(f"  cut, prune=1 / all pairs = {rate['cut'] / rate['stepwise']:.2f}x steps/s; cut, prune=0 / all pairs = {rate['cut_noprune'] / rate['stepwise']:.2f}x; "
+                f"slowest pruned run {max(res['cut']['all_us']) / 1e3:.2f} ms, fastest all-pairs run {min(res['stepwise']['all_us']) / 1e3:.2f} ms: "
+                f"{'faster' if max(res['cut']['all_us']) < min(res['stepwise']['all_us']) else 'NOT faster'}")
+    for w in (() if args.cutoff else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:
             r = run(f"{w}:{side}")

@@ -11,9 +11,19 @@ conformation, sum_b n_b (n_b - 1) C per call -- the kernel evaluates every unord
 The share of the fp32 vector peak uses FLOP_PER_PAIR below (counted from the kernel's inner loop) and 157.3 TFLOP/s.
 
     python tools/nonbonded_bench.py [--out profiles/nonbonded_bench.txt] [--seconds 1.0]
+
+With --cutoff RC [--switch RS] the tool measures the nonbonded cutoff instead: at three workloads (the pool batch, a 513-atom chain, the
+50,046-atom chain) the planned kernel with all pairs, with the cutoff and tile pruning (prune = 1) and with the cutoff and every tile
+evaluated (prune = 0: what the per-pair test alone costs), in calls per second, and the tiles evaluated per work item against all tiles.
+Device events around single calls, one warm-up call, five timed calls (all five printed, the median reported); every workload is a child
+process of its own under a time limit, the parent never initialises the GPU and starts nothing after a stage that fails.
+
+    python tools/nonbonded_bench.py --cutoff 10 [--switch 8] [--out profiles/nb_cutoff_bench.txt]
 """
 import argparse
+import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -117,6 +127,92 @@ def time_events(fn, seconds):
     return float(np.median(us)), float(us.min()), reps
 
 
+CUT_WORKLOADS = ("pool", "mid", "big")
+CUT_STAGE_LIMIT = 300      # seconds, every stage
+
+
+def five(fn):
+    """one warm-up call, then five calls between device events -> the five times in us"""
+    fn()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(), fn(), b.record()
+        torch.cuda.synchronize()
+        us.append(a.elapsed_time(b) * 1e3)
+    return us
+
+
+def cut_stage(args):
+    """one workload of the cutoff measurement in this (child) process -> a JSON line on stdout"""
+    if not torch.cuda.is_available():
+        sys.exit("nonbonded_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    from grappa_amd.nonbonded import Cutoff
+    be = get_backend()
+    if args.stage == "device":
+        prop = torch.cuda.get_device_properties(0)
+        print(json.dumps({"device": f"{prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, "
+                                    f"{prop.total_memory / 2 ** 30:.0f} GiB; library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}"}))
+        return
+    params, xyz = pool_batch(args.mols, args.confs) if args.stage == "pool" else chain(args.mid_atoms if args.stage == "mid" else args.chain_atoms)
+    nb = NonbondedBatch(params).to("cuda")
+    x = torch.from_numpy(xyz).to("cuda")
+    n = np.array([p.n_atoms for p in params], dtype=np.float64)
+    e_o, t_o, g_o = torch.empty(nb.B, x.shape[1], device="cuda"), torch.empty(2, nb.B, x.shape[1], device="cuda"), torch.empty_like(x)
+    tabs = (x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps)
+    plan = be.nonbonded_plan(nb.atom_molptr.cpu(), nb.N, x.shape[1], "cuda")
+    cut = {p: Cutoff(args.cutoff, args.switch or None, prune=p) for p in (True, False)}
+    tiles = {p: torch.zeros(plan[1], dtype=torch.int32, device="cuda") for p in (True, False)}
+    out = {"molecules": len(params), "atoms": int(n.sum()), "smallest": int(n.min()), "largest": int(n.max()), "confs": int(x.shape[1]), "items": int(plan[1])}
+    out["all_pairs"] = five(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan))
+    out["cut"] = five(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan, cutoff=cut[True], tiles=tiles[True]))
+    out["cut_noprune"] = five(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan, cutoff=cut[False], tiles=tiles[False]))
+    out["tiles"], out["all_tiles"] = int(tiles[True].sum()), int(tiles[False].sum())
+    print(json.dumps(out))
+
+
+def cut_main(args):
+    import datetime
+    lines = [f"# command: python {' '.join(sys.argv)}", f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}"]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def run(name):
+        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name, f"--cutoff={args.cutoff}",
+               f"--switch={args.switch}", f"--mols={args.mols}", f"--confs={args.confs}", f"--mid-atoms={args.mid_atoms}", f"--chain-atoms={args.chain_atoms}"]
+        p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout + p.stderr)
+            sys.exit(f"nonbonded_bench: stage {name} ended with status {p.returncode}; nothing more is started")
+        return json.loads(p.stdout.strip().splitlines()[-1])
+
+    say(f"# device: {run('device')['device']}")
+    say(f"# cutoff {args.cutoff} A, switch {args.switch or 'none'}, reaction field 78.3; the planned kernel into preallocated outputs (energy, terms, gradient); "
+        "device events around single calls, one warm-up call, five timed calls: median, all five; every workload a process of its own; "
+        "this file is the tool's output, unedited")
+    for w in CUT_WORKLOADS:
+        r = run(w)
+        say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms ({r['smallest']}..{r['largest']} per molecule), C = {r['confs']}, {r['items']} work items")
+        rate = {}
+        for key, what in (("all_pairs", "all pairs"), ("cut", "cut, prune=1"), ("cut_noprune", "cut, prune=0")):
+            med = float(np.median(r[key]))
+            rate[key] = 1e6 / med
+            say(f"  {what:14s} {med:12.1f} us  {rate[key]:10.1f} calls/s   runs: {', '.join(f'{u:.1f}' for u in r[key])} us")
+        say(f"  tiles: {r['tiles']} of {r['all_tiles']} evaluated: mean {r['tiles'] / max(r['items'], 1):.2f} of {r['all_tiles'] / max(r['items'], 1):.2f} per item "
+            f"({100.0 * r['tiles'] / max(r['all_tiles'], 1):.1f} %)")
+        say(f"  cut, prune=1 / all pairs = {rate['cut'] / rate['all_pairs']:.2f}x; cut, prune=0 / all pairs = {rate['cut_noprune'] / rate['all_pairs']:.2f}x; "
+            f"slowest pruned call {max(r['cut']):.1f} us, fastest all-pairs call {min(r['all_pairs']):.1f} us: "
+            f"{'faster' if max(r['cut']) < min(r['all_pairs']) else 'NOT faster'}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -124,7 +220,15 @@ def main():
     ap.add_argument("--mols", type=int, default=256)
     ap.add_argument("--confs", type=int, default=32)
     ap.add_argument("--chain-atoms", type=int, default=50046)
+    ap.add_argument("--mid-atoms", type=int, default=513)
+    ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
+    ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
+    ap.add_argument("--stage", default=None, choices=("device",) + CUT_WORKLOADS)
     args = ap.parse_args()
+    if args.stage:
+        return cut_stage(args)
+    if args.cutoff:
+        return cut_main(args)
     if not torch.cuda.is_available():
         sys.exit("nonbonded_bench: needs a GPU (there is nothing to time without one)")
     from grappa_amd.backend import get_backend
