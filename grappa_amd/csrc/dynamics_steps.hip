@@ -54,26 +54,21 @@ struct MsWs {
 // (the words of a cutoff lie behind the others: without one the layout is the one it was)
 MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false) {
     MsWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    WsCarve k{base};
     const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
-    w.x = (float*)take(4 * n3), w.v = (float*)take(4 * n3), w.g = (float*)take(4 * n3);
-    w.status = (int*)take(4 * bc), w.steps = (int*)take(4 * bc);
-    w.bad = (int*)take(4 * kc);
-    w.kpart = (double*)take(8 * kc);
-    w.e_mm = (float*)take(4 * bc), w.e_nb = (float*)take(4 * bc), w.terms = (float*)take(4 * 6 * bc);
-    w.nbpart = (double*)take(8 * 2 * kc);
+    w.x = k.take<float>(n3), w.v = k.take<float>(n3), w.g = k.take<float>(n3);
+    w.status = k.take<int>(bc), w.steps = k.take<int>(bc);
+    w.bad = k.take<int>(kc);
+    w.kpart = k.take<double>(kc);
+    w.e_mm = k.take<float>(bc), w.e_nb = k.take<float>(bc), w.terms = k.take<float>(6 * bc);
+    w.nbpart = k.take<double>(2 * kc);
     w.box = nullptr, w.er = nullptr, w.nbcut = nullptr, w.nbcut_bytes = 0;
     if (cut) {
-        w.box = (float4*)take(sizeof(float4) * 2 * kc), w.er = (int2*)take(sizeof(int2) * (size_t)n_blocks);
+        w.box = k.take<float4>(2 * kc), w.er = k.take<int2>((size_t)n_blocks);
         w.nbcut_bytes = grappa_nonbonded_cut_workspace_bytes(C, n_blocks);
-        w.nbcut = take(w.nbcut_bytes);
+        w.nbcut = k.take<char>(w.nbcut_bytes);
     }
-    w.total = off;
+    w.total = k.off;
     return w;
 }
 
@@ -261,8 +256,7 @@ __global__ __launch_bounds__(NB_NT) void ms_force_cut_kernel(MsForceArgs a, NbCu
     ms_force_body(a, NbCut{c, near});
 }
 
-// with a cutoff, the launch of init between ms_init_kernel and the first force: the boxes of the item's (block, conformations) at x and,
-// by the item of the block's first conformations, the block's exception range
+// with a cutoff, the launch of init between ms_init_kernel and the first force: the boxes and exception ranges at x (csrc/nb_cut.h)
 struct MsBoxArgs {
     RsGeom q;
     const float* x;
@@ -272,18 +266,8 @@ struct MsBoxArgs {
 };
 
 __global__ __launch_bounds__(NB_NT) void ms_box_kernel(MsBoxArgs a) {
-    __shared__ float bx[NB_NT * 3];
-    __shared__ int2 er_s[NB_T];
     RsItem r;
-    if (!rs_item(a.q, r)) return;
-    const int t = threadIdx.x;
-    if (t < r.ni * r.nc) {
-        const int cl = t / r.ni, il = t - cl * r.ni;
-        const float* p = a.x + ((size_t)(r.i0 + il) * a.q.C + r.c0 + cl) * 3;
-        bx[3 * t] = p[0], bx[3 * t + 1] = p[1], bx[3 * t + 2] = p[2];
-    }
-    if (r.c0 == 0) nb_cut_range_write(a.exc_ptr, a.exc_atom, r.i0, r.ni, r.m0, r.m1, r.blk, er_s, a.er);
-    nb_cut_box_write(bx, nullptr, r.ni, r.nc, r.blk, a.q.C, r.c0, a.box);
+    if (rs_item(a.q, r)) nb_cut_box_range(r, a.q.C, a.x, a.exc_ptr, a.exc_atom, a.box, a.er);
 }
 
 // ------------------------------------------------------------------------------------------------ energies and outputs
@@ -364,23 +348,12 @@ void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_d
     }
 }
 
-// the six potential terms at the held coordinates by the library's own energy kernels: the bits of grappa_mm_energy_fwd_f32 and
-// grappa_nonbonded_fwd_planned_f32 (with a cutoff: grappa_nonbonded_fwd_cut_f32) there
+// steps_terms_at of csrc/rs_force.h at w.x, in the part of this workspace that the cut or the planned nonbonded call takes
 int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const int* table_dev, int n_items,
                     int n_blocks, const MsWs& w) {
-    const size_t bc = (size_t)mm->B * mm->C;
-    grappa_mm_desc me = *mm;
-    me.xyz = w.x;
-    int rc = grappa_mm_energy_fwd_f32(stream, &me, w.e_mm, w.terms, nullptr, nullptr);
-    if (rc != GRAPPA_OK || !nb) return rc;
-    grappa_nb_desc ne = *nb;
-    ne.xyz = w.x;
-    ne.atom_molptr = mm->atom_molptr;
-    if (c)
-        return grappa_nonbonded_fwd_cut_f32(stream, &ne, c->opts, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, nullptr, w.nbcut,
-                                            w.nbcut_bytes);
-    return grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, w.nbpart,
-                                            sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
+    if (c) return steps_terms_at(stream, mm, nb, c->opts, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbcut, w.nbcut_bytes);
+    return steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
+                          sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
 }
 
 MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w) {

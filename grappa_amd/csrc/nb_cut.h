@@ -32,7 +32,8 @@ struct NbCutDev {
     const int2* er;          // [n_blocks]
 };
 
-// The cut policy of the two pair loops (nb_pairs_body of csrc/nonbonded.hip, rs_force of csrc/rs_force.h), a compile-time choice.
+// The cut policy of the pair loop (nb_pair_loop of csrc/nb_loop.h, called by nb_pairs_kernel of csrc/nonbonded.hip and by rs_force of
+// csrc/rs_force.h), a compile-time choice.
 struct NbNoCut {
     static constexpr bool on = false;
 };
@@ -104,7 +105,29 @@ __device__ inline void nb_cut_range_write(const int* __restrict__ exc_ptr, const
     }
 }
 
+// The launch before the first pair loop under the cut policy: the boxes of the item's (block, conformations) at x [N,C,3] and, by the
+// item of the block's first conformations, the block's exception range.  Every thread of the item's workgroup calls it.
+__device__ inline void nb_cut_box_range(const RsItem& r, int C, const float* __restrict__ x, const int* __restrict__ exc_ptr,
+                                        const int* __restrict__ exc_atom, float4* box, int2* er) {
+    __shared__ float bx[NB_NT * 3];
+    __shared__ int2 er_s[NB_T];
+    const int t = threadIdx.x;
+    if (t < r.ni * r.nc) {
+        const int cl = t / r.ni, il = t - cl * r.ni;
+        const float* p = x + ((size_t)(r.i0 + il) * C + r.c0 + cl) * 3;
+        bx[3 * t] = p[0], bx[3 * t + 1] = p[1], bx[3 * t + 2] = p[2];
+    }
+    if (r.c0 == 0) nb_cut_range_write(exc_ptr, exc_atom, r.i0, r.ni, r.m0, r.m1, r.blk, er_s, er);
+    nb_cut_box_write(bx, nullptr, r.ni, r.nc, r.blk, C, r.c0, box);
+}
+
 // ------------------------------------------------------------------------------------------------ the skip rule
+// the boxes of all blocks of the item's molecule are read: false for a table whose block numbers do not fit, which is walked away from
+__device__ inline bool nb_cut_blocks_ok(const RsItem& r, int n_blocks) {
+    const int kb0 = nb_first_block(r);
+    return kb0 >= 0 && kb0 + nb_tiles(r) <= n_blocks;
+}
+
 __device__ inline float nb_cut_gap2(const float4 lo_i, const float4 hi_i, const float4 lo_j, const float4 hi_j) {
     auto gap = [](float a, float b) {          // max(0, a, b); a NaN gives 0
         float d = a > b ? a : b;

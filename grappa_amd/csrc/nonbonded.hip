@@ -12,7 +12,8 @@
 //            conformations.  (With ni * nc < 64 the lanes of one wavefront belong to several slices and read several rows of the LDS
 //            block at once: those reads are not broadcasts.)  A thread walks its atom's sorted exception list in step with j: an
 //            exception REPLACES the pair's parameters, an exclusion (eps = 0 and qq = 0) or j == i is not evaluated at all.  Blocks
-//            in which no thread of a wavefront has an exception or its own atom take a loop without the lookup.
+//            in which no thread of a wavefront has an exception or its own atom take a loop without the lookup.  (The text of this
+//            loop is nb_pair_loop of csrc/nb_loop.h; the force of the stepwise minimiser and dynamics, csrc/rs_force.h, calls it too.)
 //            No Newton's third law and no atomics: an atom's gradient is summed by its owner in a fixed j order, the slices are added
 //            in a fixed order through LDS, and the block's half-energies sum_i 1/2 sum_j e_ij are added over i in double.
 //   reduce : one workgroup per molecule adds the blocks' partial energies in double in a fixed order.
@@ -25,8 +26,9 @@
 
 #include "common.h"
 #include "nb_cut.h"
+#include "nb_loop.h"
 #include "nb_pair.h"
-#include "nb_plan.h"      // NB_T, NB_TJ, NB_NT, NB_CW, NB_JS, nb_chunks, nb_clamp
+#include "nb_plan.h"
 
 namespace {
 
@@ -88,6 +90,7 @@ struct NbArgs {
     float* grad;
     int max_blk;       // rows of `part`
 };
+__device__ inline RsGeom nb_geom(const NbArgs& a) { return {a.d.N, a.d.C, a.d.B, a.max_blk, a.d.atom_molptr, nullptr, a.items}; }
 
 // Cut: the compile-time cut policy of csrc/nb_cut.h (NbNoCut: all pairs; NbCut: nb_pair_cut for a pair that is no exception, far tiles
 // skipped, tiles[item] = the tiles evaluated)
@@ -102,105 +105,22 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a, Cut cut, int*
     }
     if (a.hdr && (int)blockIdx.x >= a.hdr[0]) return;
     const grappa_nb_desc& d = a.d;
-    const int4 it = a.items[blockIdx.x];
-    const int mol = it.x, i0 = it.y, blk = it.z, c0 = it.w;
     const int C = d.C;
-    if (mol < 0 || mol >= d.B || blk < 0 || blk >= a.max_blk || c0 < 0 || c0 >= C) return;      // (a table made for another batch)
-    const int m0 = nb_clamp(d.atom_molptr[mol], d.N), m1 = nb_clamp(d.atom_molptr[mol + 1], d.N);
-    if (i0 < m0 || i0 >= m1) return;
-    const int ntiles = (m1 - m0 + NB_TJ - 1) / NB_TJ, kb0 = blk - (i0 - m0) / NB_T;      // (read by the cut policy only)
-    if (Cut::on && (kb0 < 0 || kb0 + ntiles > a.max_blk)) return;      // the boxes of the molecule's blocks are read
-    const int ni = m1 - i0 < NB_T ? m1 - i0 : NB_T;
-    int nch, ncb;
-    nb_chunks(ni, C, nch, ncb);
-    const int nc = C - c0 < ncb ? C - c0 : ncb;
-    const int NL = ni * nc;
+    RsItem r;
+    if (!rs_item(nb_geom(a), r)) return;
+    if (Cut::on && !nb_cut_blocks_ok(r, a.max_blk)) return;
+    const int ni = r.ni, blk = r.blk;
+    const int NL = ni * r.nc;
     const int JS = NB_NT / NL < NB_JS ? NB_NT / NL : NB_JS;
     const int t = threadIdx.x, s = t / NL, l = t - s * NL;
     const bool active = s < JS;
     const int cl = l / ni, il = l - cl * ni;      // i is the fast index: the lanes of a wavefront share few conformations (LDS broadcasts)
-    const int i = i0 + il, c = c0 + cl;
+    const int i = r.i0 + il, c = r.c0 + cl;
 
-    float xi = 0.f, yi = 0.f, zi = 0.f, kq = 0.f, hs = 0.f, se = 0.f;
-    int ep = 0, ee = 0, nx = INT_MAX;
-    if (active) {
-        const float* p = d.xyz + ((size_t)i * C + c) * 3;
-        xi = p[0], yi = p[1], zi = p[2];
-        kq = NB_K * d.charge[i];
-        hs = 0.5f * d.sigma[i];
-        se = 4.0f * sqrtf(d.epsilon[i]);
-        ep = d.exc_ptr[i];
-        ee = d.exc_ptr[i + 1];
-        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-    }
-    float elj = 0.f, ec = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
-    [[maybe_unused]] int count = 0;      // (the cut policy's: the tiles evaluated)
-    for (int j0 = m0; j0 < m1; j0 += NB_TJ) {
-        if constexpr (Cut::on) {      // NB_NT verdicts at a time; a far tile loads nothing and passes no barrier of the tile
-            const int jt = (j0 - m0) / NB_TJ, k = jt & (NB_NT - 1);
-            if (k == 0) nb_cut_decide(cut.c, C, blk, kb0, ntiles, jt, c0, nc, nullptr, cut.near);
-            if (!cut.near[k]) continue;
-            ++count;
-        }
-        const int nj = m1 - j0 < NB_TJ ? m1 - j0 : NB_TJ;
-        __syncthreads();
-        for (int idx = t; idx < nj * nc; idx += NB_NT) {
-            const int jj = idx / nc, cc = idx - jj * nc;
-            const float* p = d.xyz + ((size_t)(j0 + jj) * C + c0 + cc) * 3;
-            xs[jj * NB_CW + cc] = make_float4(p[0], p[1], p[2], 0.f);
-        }
-        if (t < nj) ps[t] = make_float4(d.charge[j0 + t], 0.5f * d.sigma[j0 + t], sqrtf(d.epsilon[j0 + t]), 0.f);
-        __syncthreads();
-        const bool lookup = active && ((i >= j0 && i < j0 + nj) || nx < j0 + nj);
-        if (__builtin_amdgcn_ballot_w64(lookup) != 0) {
-            if (active) {
-                for (int jj = s; jj < nj; jj += JS) {
-                    const int j = j0 + jj;
-                    const float4 p = ps[jj];
-                    float sij = hs + p.y, e4 = se * p.z, kqq = kq * p.x;
-                    bool skip = j == i;
-                    while (nx < j) {
-                        ++ep;
-                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                    }
-                    bool exc = false;      // (read by the cut policy only)
-                    if (nx == j) {
-                        const float q = d.exc_qq[ep], e = d.exc_eps[ep];
-                        exc = true;
-                        sij = d.exc_sigma[ep];
-                        e4 = 4.0f * e;
-                        kqq = NB_K * q;
-                        skip = skip || (q == 0.f && e == 0.f);
-                        ++ep;
-                        nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                    }
-                    if (!skip) {
-                        const float4 x = xs[jj * NB_CW + cl];
-                        if constexpr (Cut::on) {      // an exception is not cut
-                            if (exc) nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
-                            else nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, cut.c.k, elj, ec, gx, gy, gz);
-                        } else {
-                            nb_pair(xi - x.x, yi - x.y, zi - x.z, sij, e4, kqq, elj, ec, gx, gy, gz);
-                        }
-                    }
-                }
-                while (nx < j0 + nj) {      // partners that belong to other slices
-                    ++ep;
-                    nx = ep < ee ? d.exc_atom[ep] : INT_MAX;
-                }
-            }
-        } else if (active) {
-#pragma unroll 4
-            for (int jj = s; jj < nj; jj += JS) {
-                const float4 p = ps[jj];
-                const float4 x = xs[jj * NB_CW + cl];
-                if constexpr (Cut::on) nb_pair_cut(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, cut.c.k, elj, ec, gx, gy, gz);
-                else nb_pair(xi - x.x, yi - x.y, zi - x.z, hs + p.y, se * p.z, kq * p.x, elj, ec, gx, gy, gz);
-            }
-        }
-    }
+    const NbSums sum = nb_pair_loop(d, d.xyz, r, C, s, JS, i, c, cl, active, nullptr, cut, xs, ps, NbSums{0.f, 0.f, 0.f, 0.f, 0.f, 0});
+    float elj = sum.elj, ec = sum.ec, gx = sum.gx, gy = sum.gy, gz = sum.gz;
     if constexpr (Cut::on)
-        if (tiles && t == 0) tiles[blockIdx.x] = count;
+        if (tiles && t == 0) tiles[blockIdx.x] = sum.tiles;
     // the slices of one (atom, conformation), added in slice order
     red[0][t] = elj, red[1][t] = ec, red[2][t] = gx, red[3][t] = gy, red[4][t] = gz;
     __syncthreads();
@@ -232,27 +152,8 @@ __global__ __launch_bounds__(NB_NT) void nb_pairs_kernel(NbArgs a, Cut cut, int*
 // the boxes of the item's (block, conformations) at d.xyz and, by the item of the block's first conformations, the block's exception
 // range (csrc/nb_cut.h): the launch before nb_pairs_kernel<NbCut>
 __global__ __launch_bounds__(NB_NT) void nb_box_kernel(NbArgs a, float4* box, int2* er) {
-    __shared__ float bx[NB_NT * 3];
-    __shared__ int2 er_s[NB_T];
-    const grappa_nb_desc& d = a.d;
-    const int4 it = a.items[blockIdx.x];
-    const int mol = it.x, i0 = it.y, blk = it.z, c0 = it.w;
-    const int C = d.C;
-    if (mol < 0 || mol >= d.B || blk < 0 || blk >= a.max_blk || c0 < 0 || c0 >= C) return;
-    const int m0 = nb_clamp(d.atom_molptr[mol], d.N), m1 = nb_clamp(d.atom_molptr[mol + 1], d.N);
-    if (i0 < m0 || i0 >= m1) return;
-    const int ni = m1 - i0 < NB_T ? m1 - i0 : NB_T;
-    int nch, ncb;
-    nb_chunks(ni, C, nch, ncb);
-    const int nc = C - c0 < ncb ? C - c0 : ncb;
-    const int t = threadIdx.x;
-    if (t < ni * nc) {
-        const int cl = t / ni, il = t - cl * ni;
-        const float* p = d.xyz + ((size_t)(i0 + il) * C + c0 + cl) * 3;
-        bx[3 * t] = p[0], bx[3 * t + 1] = p[1], bx[3 * t + 2] = p[2];
-    }
-    if (c0 == 0) nb_cut_range_write(d.exc_ptr, d.exc_atom, i0, ni, m0, m1, blk, er_s, er);
-    nb_cut_box_write(bx, nullptr, ni, nc, blk, C, c0, box);
+    RsItem r;
+    if (rs_item(nb_geom(a), r)) nb_cut_box_range(r, a.d.C, a.d.xyz, a.d.exc_ptr, a.d.exc_atom, box, er);
 }
 
 // ------------------------------------------------------------------------------------------------ reduce
@@ -293,14 +194,15 @@ struct NbLayout {
 };
 NbLayout nb_layout(int N, int C, int B) {
     NbLayout L;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    WsCarve w{nullptr};
     // every molecule ends in at most one short block; a block of ni <= NB_T atoms takes at most ceil(C / (NB_NT / NB_T)) work items
     L.max_blk = (long long)N / NB_T + B;
     L.max_items = L.max_blk * ((C + NB_NT / NB_T - 1) / (NB_NT / NB_T));
-    L.blk_ptr = 256;
-    L.items = L.blk_ptr + up(sizeof(int) * ((size_t)B + 1));
-    L.part = L.items + up(sizeof(int4) * (size_t)L.max_items);
-    L.total = L.part + up(sizeof(double) * 2 * (size_t)L.max_blk * (size_t)C);
+    w.skip(256);      // hdr
+    L.blk_ptr = w.skip(sizeof(int) * ((size_t)B + 1));
+    L.items = w.skip(sizeof(int4) * (size_t)L.max_items);
+    L.part = w.skip(sizeof(double) * 2 * (size_t)L.max_blk * (size_t)C);
+    L.total = w.off;
     return L;
 }
 
@@ -342,10 +244,10 @@ extern "C" int grappa_nonbonded_fwd_f32(void* stream, const grappa_nb_desc* d, f
     return grappa_launch_status();
 }
 
-// the table of the planned path, as ints: [n_items, n_blocks, 0, 0 | blk_ptr[B+1], padded to a multiple of 4 | items: 4 per item]
+// the table of the planned path (csrc/nb_plan.h states its layout, nb_table_view reads it)
 extern "C" long long grappa_nonbonded_plan(int N, int C, int B, const int* atom_molptr_host, int* table, long long table_ints) {
     if (N < 0 || C < 1 || B < 1 || !atom_molptr_host) return GRAPPA_ERR_ARG;
-    const long long items0 = 4 + (((long long)B + 1 + 3) & ~3LL);
+    const long long items0 = nb_table_items0(B);
     long long blk = 0, item = 0;
     for (int pass = 0; pass < (table ? 2 : 1); ++pass) {      // count, then (with a table of the counted size) fill
         if (pass == 1) {
@@ -383,11 +285,10 @@ extern "C" int grappa_nonbonded_fwd_planned_f32(void* stream, const grappa_nb_de
     if (n_blocks > (long long)d->N / NB_T + d->B) return GRAPPA_ERR_ARG;
     if (ws_bytes < sizeof(double) * 2 * (size_t)n_blocks * (size_t)d->C) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int* blk_ptr = table_dev + 4;
-    const int4* items = (const int4*)(table_dev + 4 + (((size_t)d->B + 1 + 3) & ~(size_t)3));
-    NbArgs a{*d, nullptr, items, (double*)ws, grad, n_blocks};
+    const NbTableView tv = nb_table_view(table_dev, d->B);
+    NbArgs a{*d, nullptr, tv.items, (double*)ws, grad, n_blocks};
     if (n_items > 0) GRAPPA_LAUNCH(nb_pairs_kernel<NbNoCut>, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, NbNoCut{}, (int*)nullptr);
-    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, (const double*)ws, energy, term_energy);
+    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, tv.blk_ptr, (const double*)ws, energy, term_energy);
     return grappa_launch_status();
 }
 
@@ -398,13 +299,13 @@ struct NbCutLayout {
     size_t part, box, er, total;
 };
 NbCutLayout nb_cut_layout(int C, int n_blocks) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t kc = (size_t)n_blocks * (size_t)C;
     NbCutLayout L;
-    L.part = 0;
-    L.box = L.part + up(sizeof(double) * 2 * kc);
-    L.er = L.box + up(sizeof(float4) * 2 * kc);
-    L.total = L.er + up(sizeof(int2) * (size_t)n_blocks);
+    WsCarve w{nullptr};
+    L.part = w.skip(sizeof(double) * 2 * kc);
+    L.box = w.skip(sizeof(float4) * 2 * kc);
+    L.er = w.skip(sizeof(int2) * (size_t)n_blocks);
+    L.total = w.off;
     return L;
 }
 
@@ -427,15 +328,14 @@ extern "C" int grappa_nonbonded_fwd_cut_f32(void* stream, const grappa_nb_desc* 
     if (n_blocks > 0 && ws_bytes < L.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
-    const int* blk_ptr = table_dev + 4;
-    const int4* items = (const int4*)(table_dev + 4 + (((size_t)d->B + 1 + 3) & ~(size_t)3));
-    NbArgs a{*d, nullptr, items, (double*)(w + L.part), grad, n_blocks};
+    const NbTableView tv = nb_table_view(table_dev, d->B);
+    NbArgs a{*d, nullptr, tv.items, (double*)(w + L.part), grad, n_blocks};
     c.prune = cut->prune;
     c.box = (const float4*)(w + L.box), c.er = (const int2*)(w + L.er);
     if (n_items > 0) {
         GRAPPA_LAUNCH(nb_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, (float4*)(w + L.box), (int2*)(w + L.er));
         GRAPPA_LAUNCH(nb_pairs_kernel<NbCut>, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a, NbCut{c, nullptr}, tiles);
     }
-    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, blk_ptr, (const double*)(w + L.part), energy, term_energy);
+    GRAPPA_LAUNCH(nb_reduce_kernel, dim3(d->B), dim3(NB_NT), 0, st, d->C, d->B, tv.blk_ptr, (const double*)(w + L.part), energy, term_energy);
     return grappa_launch_status();
 }

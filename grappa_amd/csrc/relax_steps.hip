@@ -11,10 +11,8 @@
 //                    reads a scalar that a sibling writes in the same launch.
 //            vel     v = keep v + mix F + h F per atom, the block's max |h v_i|
 //            move    max over the item's blocks, s = min(1, max_disp / max), x += s h v, v = s v
-//            force   g at the new x: bonded_gather of csrc/mm_geom.h, as in mm_gradient_kernel (the thread's slice of the atom's
-//                    incidences, neighbours read from global memory) plus the j loop of nb_pairs_kernel (j-atoms through LDS in ascending blocks of 64, the
-//                    sorted exception row walked in step with j, an exception replaces the pair, an exclusion or j == i is skipped, no
-//                    pair energy kept), slices added in slice order; then the block's partials.
+//            force   g at the new x (rs_force of csrc/rs_force.h: the bonded gradient plus the pair loop of nb_pairs_kernel itself,
+//                    slices added in slice order); then the block's partials.
 //            Launch boundaries are the only synchronisation between workgroups: no cooperative launch, no flag, no float atomics.
 //            The one atomic is the integer decrement of the count of running items by the thread that stops an item.
 //   stopped: every launch leaves a (molecule, conformation) whose status is final alone, so the result depends neither on the number of
@@ -54,22 +52,17 @@ struct RsWs {
 
 RsWs rs_layout(char* base, int N, int C, int B, int n_blocks) {
     RsWs w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    WsCarve k{base};
     const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
-    w.x = (float*)take(4 * n3), w.v = (float*)take(4 * n3), w.g = (float*)take(4 * n3);
-    w.s.h = (float*)take(4 * bc), w.s.al = (float*)take(4 * bc), w.s.mix = (float*)take(4 * bc), w.s.keep = (float*)take(4 * bc);
-    w.s.gmax = (float*)take(4 * bc);
-    w.s.npos = (int*)take(4 * bc), w.s.steps = (int*)take(4 * bc), w.s.status = (int*)take(4 * bc), w.s.downhill = (int*)take(4 * bc);
-    w.part = (double*)take(8 * 4 * kc);
-    w.dpart = (float*)take(4 * kc);
-    w.e_mm = (float*)take(4 * bc), w.e_nb = (float*)take(4 * bc), w.terms = (float*)take(4 * 6 * bc);
-    w.nbpart = (double*)take(8 * 2 * kc);
-    w.total = off;
+    w.x = k.take<float>(n3), w.v = k.take<float>(n3), w.g = k.take<float>(n3);
+    w.s.h = k.take<float>(bc), w.s.al = k.take<float>(bc), w.s.mix = k.take<float>(bc), w.s.keep = k.take<float>(bc);
+    w.s.gmax = k.take<float>(bc);
+    w.s.npos = k.take<int>(bc), w.s.steps = k.take<int>(bc), w.s.status = k.take<int>(bc), w.s.downhill = k.take<int>(bc);
+    w.part = k.take<double>(4 * kc);
+    w.dpart = k.take<float>(kc);
+    w.e_mm = k.take<float>(bc), w.e_nb = k.take<float>(bc), w.terms = k.take<float>(6 * bc);
+    w.nbpart = k.take<double>(2 * kc);
+    w.total = k.off;
     return w;
 }
 
@@ -403,20 +396,9 @@ extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc*
     dc.C = mm->C, dc.n_blocks = n_blocks, dc.blk_ptr = q.blk_ptr, dc.part = w.part, dc.s = w.s;
     dc.n_running = nullptr, dc.final = 1;
     GRAPPA_LAUNCH(rs_decide_kernel, dim3((unsigned)bc), dim3(RS_DNT), 0, st, dc);
-    // the six terms at the held coordinates by the library's own energy kernels: the bits of grappa_mm_energy_fwd_f32 and
-    // grappa_nonbonded_fwd_planned_f32 there
-    grappa_mm_desc me = *mm;
-    me.xyz = w.x;
-    int erc = grappa_mm_energy_fwd_f32(stream, &me, w.e_mm, w.terms, nullptr, nullptr);
+    const int erc = steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
+                                   sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
     if (erc != GRAPPA_OK) return erc;
-    if (nb) {
-        grappa_nb_desc ne = *nb;
-        ne.xyz = w.x;
-        ne.atom_molptr = mm->atom_molptr;
-        erc = grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, w.e_nb, w.terms + 4 * bc, nullptr, w.nbpart,
-                                               sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
-        if (erc != GRAPPA_OK) return erc;
-    }
     RsOutArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.has_nb = nb != nullptr;
     a.atom_molptr = mm->atom_molptr;

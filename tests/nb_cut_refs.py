@@ -189,8 +189,13 @@ def expected_tiles(params, xyz, cut: Cutoff, T=None, prune=True):
 
 # ------------------------------------------------------------------------------------------------------------------------- cases
 LATTICE = [k for k in nr.case_table() if k != "all_exceptions"]          # nonbonded_refs' cases: nominal cutoffs 2.5 and 4 A
-CHAINS = {"c129_C3": ((129,), 3), "c513_C3": ((513,), 3), "chain_mixed": ((1, 2, 17, 130, 5, 64), 3), "c513_far_exception": ((513,), 3)}
-NOMINAL = {**{k: (2.5, 4.0) for k in LATTICE}, **{k: (6.0, 9.0) for k in CHAINS}}
+# BIG: 257 j-tiles, so that a work item takes its verdicts in two batches (csrc/nb_cut.h nb_cut_decide is called again at tile 256).  Its
+# tiles and the bits with and without pruning are tested, at BIG_CUTOFF as it stands: it has no dense reference, so it is in no entry of
+# NOMINAL / CASES and its cutoff needs no placement.
+BIG, BIG_CUTOFF = "c16448_C1", 9.0
+CHAINS = {"c129_C3": ((129,), 3), "c513_C3": ((513,), 3), "chain_mixed": ((1, 2, 17, 130, 5, 64), 3), "c513_far_exception": ((513,), 3),
+          BIG: ((16448,), 1)}
+NOMINAL = {**{k: (2.5, 4.0) for k in LATTICE}, **{k: (6.0, 9.0) for k in CHAINS if k != BIG}}
 VARIANTS = [(sw, eps) for sw in (False, True) for eps in (78.3, 1.0)]          # with and without a switch at 0.8 rc; eps = 1: no reaction field
 CASES = [(name, nominal) for name in NOMINAL for nominal in NOMINAL[name]]
 

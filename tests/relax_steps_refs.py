@@ -39,6 +39,17 @@ def case(name) -> rr.Batch:
 
 
 @functools.lru_cache(maxsize=None)
+def unbonded(name) -> rr.Batch:
+    """case(name) without its bonded tuples (T = 0 at every level): the coordinates and the nonbonded parameters, exceptions included,
+    stay, so the force of the stepwise paths is the nonbonded term alone.  Computed once and shared: treat as read-only"""
+    b = case(name)
+    idx = [torch.zeros(0, a, dtype=torch.int64) for a in rr.ARITY]
+    mol_ptr = [torch.zeros(b.B + 1, dtype=torch.int32) for _ in rr.ARITY]
+    return rr.Batch.from_tables(b.counts, idx, mol_ptr, [k[:0] for k in b.ks], [None if q is None else q[:0] for q in b.eqs], b.n_per,
+                                b.params, b.xyz)
+
+
+@functools.lru_cache(maxsize=None)
 def forces_of(name, dtype=torch.float64):
     b = case(name)
     return rr.forces(b, b.xyz, dtype, True)

@@ -63,6 +63,23 @@ def test_energy_terms_gradient_and_tiles(hip, name, nominal):
             assert torch.equal(_bits(got[k]), _bits(every[k])), f"{what}: {k} differs between prune = 1 and prune = 0"
 
 
+def test_the_second_batch_of_verdicts(hip):
+    """a molecule of 257 tiles (nb_cut_refs.BIG): a work item decides its tiles 256 at a time, so tile 256 belongs to a second batch.
+    `tiles` equals the host restatement item for item, and energy, terms and gradient have the bits of the call that evaluates every
+    tile (no dense reference at this size: the formulas are gated on the smaller cases)"""
+    params, nb, x = nc.inputs(nc.BIG)
+    nbd = nc.NonbondedBatch(params).to("cuda")
+    cut = nc.Cutoff(nc.BIG_CUTOFF, 0.8 * nc.BIG_CUTOFF)
+    got = _evaluate(hip, nbd, x, cut)
+    want, full, _ = nc.expected_tiles(params, x.numpy(), cut)
+    assert got["tiles"].tolist() == want.tolist(), f"tiles {got['tiles'].tolist()} expected {want.tolist()}"
+    every = _evaluate(hip, nbd, x, nc.Cutoff(nc.BIG_CUTOFF, 0.8 * nc.BIG_CUTOFF, prune=False))
+    assert every["tiles"].tolist() == full.tolist() and full.tolist() == [257] * 257, "prune = 0 skipped a tile"
+    for k in ("energy", "terms", "grad"):
+        assert bool(torch.isfinite(got[k]).all()), k
+        assert torch.equal(_bits(got[k]), _bits(every[k])), f"{k} differs between prune = 1 and prune = 0"
+
+
 def test_the_same_call_twice_gives_the_same_bits(hip):
     params, nb, x = nc.inputs("c513_C3")
     nbd = nc.NonbondedBatch(params).to("cuda")

@@ -223,6 +223,68 @@ def test_a_molecule_of_three_blocks_gives_the_same_bits_behind_another(hip):
     _same_bits(_rows_of(_run(hip, two, max_steps=40, tolerance=0.0), two, 1), alone, "129 atoms behind 65")
 
 
+# ------------------------------------------------------------------------------------------------ 4b. the seam to the energy kernel
+# the sizes of the mixed batch at C = 3; one molecule at C = 17, whose block is dealt out in two conformation chunks, and one of two
+# blocks at C = 17 (five chunks and two)
+SEAM_CASES = [rs.MIXED, "s9_C17", "s65_C17"]
+
+
+def _nonbonded_kernel(hip, b, x):
+    """energy terms and gradient of the nonbonded term alone by the planned energy kernel -> (terms (2,B,C), grad (N,C,3)) on the CPU"""
+    nb, x = b.nonbonded().to("cuda"), x.to("cuda")
+    Cc = x.shape[1]
+    e, te, g = torch.full((b.B, Cc), FILL, device="cuda"), torch.full((2, b.B, Cc), FILL, device="cuda"), torch.full_like(x, FILL)
+    hip.nonbonded(x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps, e, te, g,
+                  plan=hip.nonbonded_plan(nb.atom_molptr_host, nb.N, Cc, x.device))
+    torch.cuda.synchronize()
+    return te.cpu(), g.cpu()
+
+
+@pytest.mark.parametrize("name", SEAM_CASES)
+def test_without_bonded_tuples_the_force_has_the_bits_of_the_nonbonded_kernel(hip, name):
+    """T = 0 at every level: the gradient the stepwise path holds at step zero is that of the one pair loop (csrc/nb_loop.h) and of the
+    same slice reduction, so it has the BITS of `nonbonded(plan=)`'s gradient, and the four bonded terms are zero"""
+    b = rs.unbonded(name)
+    assert all(int(i.shape[0]) == 0 for i in b.idx)
+    got = _run(hip, b, max_steps=0, tolerance=0.0)
+    te, g = _nonbonded_kernel(hip, b, b.xyz)
+    diff = got["grad"].view(torch.int32) != g.view(torch.int32)
+    print(f"{name}: {int(diff.sum())} of {diff.numel()} gradient words differ; largest |difference| {float((got['grad'] - g).abs().max()):.3e}")
+    assert not bool(diff.any()), f"{name}: the stepwise force and the energy kernel's gradient differ in {int(diff.sum())} words"
+    assert not got["terms"][:4].any() and torch.equal(got["terms"][4:].view(torch.int32), te.view(torch.int32))
+
+
+def test_a_conformation_that_starts_at_nan_stops_and_leaves_the_others_their_bits(hip):
+    """one conformation of the 130-atom molecule starts with a NaN coordinate.  At step zero its gradient is non-finite and every other
+    (molecule, conformation) has the bits of the nonbonded kernel at the same coordinates; then it stops with status 2, the force
+    launches of the steps that follow mask it (it is neither loaded nor asked for a verdict), and after three steps every other
+    conformation has the bits it has without the NaN"""
+    clean = rs.unbonded(rs.MIXED)
+    M, cbad = 3, 1
+    p0, p1 = int(clean.ptr[M]), int(clean.ptr[M + 1])
+    x = clean.xyz.clone()
+    x[p0 + 70, cbad, 1] = float("nan")
+    bad = rr.Batch.from_tables(clean.counts, clean.idx, clean.mol_ptr, clean.ks, clean.eqs, clean.n_per, clean.params, x)
+    keep = torch.ones(clean.N, x.shape[1], dtype=torch.bool)
+    keep[p0:p1, cbad] = False
+    item = torch.ones(clean.B, x.shape[1], dtype=torch.bool)
+    item[M, cbad] = False
+    got0 = _run(hip, bad, max_steps=0, tolerance=0.0)
+    _, g = _nonbonded_kernel(hip, bad, x)
+    assert torch.equal(got0["grad"].view(torch.int32)[keep], g.view(torch.int32)[keep]), "step zero: the other conformations' gradient"
+    assert int(got0["status"][M, cbad]) == 2 and bool(torch.isinf(got0["gmax"][M, cbad]))
+    a, c = _run(hip, bad, max_steps=3, tolerance=0.0), _run(hip, clean, max_steps=3, tolerance=0.0)
+    assert int(a["status"][M, cbad]) == 2 and int(a["steps"][M, cbad]) == 0
+    assert torch.equal(a["xyz"][p0:p1, cbad].view(torch.int32), x[p0:p1, cbad].view(torch.int32)), "status 2 returns the coordinates it holds"
+    for k in ("xyz", "grad"):
+        assert torch.equal(a[k].view(torch.int32)[keep], c[k].view(torch.int32)[keep]), f"{k} of the other conformations"
+    for k in ("energy", "gmax", "steps", "status"):
+        va, vc = (t.view(torch.int32) if t.dtype == torch.float32 else t for t in (a[k], c[k]))
+        assert torch.equal(va[item], vc[item]), f"{k} of the other conformations"
+    assert torch.equal(a["terms"].view(torch.int32)[:, item], c["terms"].view(torch.int32)[:, item]), "terms of the other conformations"
+    assert bool((a["steps"][M][item[M]] == 3).all()), "the molecule's other conformations did not run on"
+
+
 # ------------------------------------------------------------------------------------------------ 5. convergence
 @pytest.mark.parametrize("name", rs.CONV_CASES)
 def test_convergence_with_the_defaults(hip, name):

@@ -196,13 +196,25 @@ def test_one_copy_of_the_noise_and_of_the_force():
     """csrc/dynamics.hip and csrc/dynamics_steps.hip include ONE md_normal3; csrc/relax_steps.hip and csrc/dynamics_steps.hip ONE force"""
     src = lambda f: open(os.path.join(ROOT, "grappa_amd", "csrc", f)).read()      # noqa: E731
     files = [f for f in sorted(os.listdir(os.path.join(ROOT, "grappa_amd", "csrc"))) if f.endswith((".h", ".hip"))]
-    defs = lambda name: [f for f in files if re.search(r"\b(float|V3|bool) " + name + r"\(", src(f))]      # noqa: E731
+    defs = lambda name: [f for f in files if re.search(r"\b(float|V3|bool|int|void|NbSums) " + name + r"\(", src(f))]      # noqa: E731
     assert defs("md_normal3") == ["md_noise.h"] and defs("md_radius") == ["md_noise.h"] and defs("rs_force") == ["rs_force.h"]
     for f in ("dynamics.hip", "dynamics_steps.hip"):
         assert '#include "md_noise.h"' in src(f)
     for f in ("relax_steps.hip", "dynamics_steps.hip"):
         assert '#include "rs_force.h"' in src(f) and "rs_force(" in src(f)
     assert "dynamics_steps.hip" in src("Makefile")
+    # under the force: ONE tiled pair loop, called by the energy kernel and by rs_force, and ONE decode of a work item
+    having = lambda text: [f for f in files if text in src(f)]      # noqa: E731
+    assert defs("nb_pair_loop") == ["nb_loop.h"] and defs("rs_item") == ["nb_plan.h"] and defs("nb_cut_box_range") == ["nb_cut.h"]
+    for f in ("nonbonded.hip", "rs_force.h"):
+        assert '#include "nb_loop.h"' in src(f) and src(f).count("nb_pair_loop(") == 1, f
+    assert having("nx = ep < ee ? d.exc_atom[ep] : INT_MAX") == ["nb_loop.h", "rx_force.h"]      # (rx_force.h: the whole molecule in LDS, another loop)
+    assert having("int4 it = ") == ["nb_plan.h"], "a work item is decoded outside rs_item"
+    for f in ("nonbonded.hip", "relax_steps.hip", "dynamics_steps.hip"):
+        assert "rs_item(" in src(f), f
+    # the plan table's layout: stated in csrc/nb_plan.h, read through nb_table_view
+    assert having("+ 1 + 3) & ~") == ["nb_plan.h"] and src("nb_plan.h").count("+ 3) & ~") == 1      # ((B + 1 + 3) & ~3: blk_ptr padded)
+    assert defs("steps_terms_at") == ["rs_force.h"] and "nb_loop.h" in src("Makefile")
 
 
 def test_the_inputs_of_the_gpu_tests_are_finite_and_mostly_steady():

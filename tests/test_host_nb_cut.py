@@ -210,3 +210,14 @@ def test_the_inputs_of_the_gpu_tests_keep_their_distance_from_every_edge():
     assert got.sum() == 7 and full.sum() == 9
     got, full, _ = nc.expected_tiles(nc.inputs("c513_C3")[0], nc.inputs("c513_C3")[2].numpy(), nc.cutoff_of("c513_C3", 6.0, False, 78.3), prune=False)
     assert (got == full).all()
+
+
+def test_the_big_chain_takes_its_verdicts_in_two_batches_and_keeps_its_distance_from_the_threshold():
+    """257 tiles per work item, one more than a batch of verdicts holds; no tile has d2 within a relative 1e-5 (above nb_cut_refs.MARGIN)
+    of the threshold; far fewer tiles than all are expected (every item its own tile at least, so the last item tile 256)"""
+    params, _, x = nc.inputs(nc.BIG)
+    assert (nc.BIG, nc.BIG_CUTOFF) not in nc.CASES and x.shape == (16448, 1, 3)
+    got, full, closest = nc.expected_tiles(params, x.numpy(), Cutoff(nc.BIG_CUTOFF, 0.8 * nc.BIG_CUTOFF))      # (the GPU test's cutoff)
+    assert len(got) == 257 and (full == 257).all() and 257 > nc.NT
+    assert closest >= 1e-5 > nc.MARGIN, closest
+    assert (got >= 2).all() and got.sum() < full.sum() // 16, (got.min(), got.sum())
