@@ -250,6 +250,14 @@ SIGNATURES = {
     "grappa_relax_steps_run_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz, _i, _vp]),
     "grappa_relax_steps_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _i, _i, _vp, _sz,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise minimiser under a nonbonded cutoff (additions to ABI 11)
+    "grappa_relax_steps_cut_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "grappa_relax_steps_init_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(RelaxOpts), _vp, _i, _i, _vp,
+                                             _sz, _vp]),
+    "grappa_relax_steps_run_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(RelaxOpts), _vp, _i, _i, _vp,
+                                            _sz, _i, _vp]),
+    "grappa_relax_steps_finish_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(RelaxOpts), _vp, _i, _i, _vp,
+                                               _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # Langevin dynamics under the full force field (additions to ABI 11)
     "grappa_md_langevin_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp]),

@@ -289,14 +289,17 @@ class MMBackend:
         return table
 
     def relax_steps(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
-                    atom_counts_host=None, check_every: int = 32, workspace=None) -> None:
+                    atom_counts_host=None, check_every: int = 32, workspace=None, cutoff=None) -> None:
         """the stepwise FIRE minimiser for molecules of any size (include/grappa_hip.h grappa_relax_steps_*_f32): the loop, the
         arguments and the outputs of `relax_fire`, but a molecule spans many workgroups, the state lives in device memory and a step
         is four launches.  atom_counts_host (required): atoms per molecule on the host; the work-item table is the nonbonded plan
         built from it (reused from nb's cache of plans where nb keeps one).  check_every: steps enqueued between two looks at the
         device's count of running items.  The host SYNCS with the device once per chunk (one `.item()`), never per step; the loop
         ends when no item runs or max_steps steps are enqueued.  Status 3 does not occur.  workspace: a uint8 tensor of at least
-        `grappa_relax_steps_workspace_bytes` to use instead of the backend's own."""
+        `grappa_relax_steps_workspace_bytes` to use instead of the backend's own.
+        cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls above, unchanged) -- the nonbonded force and
+        energy of grappa_relax_steps_*_cut_f32: `nonbonded(..., cutoff=)`'s; it needs nb; the workspace is then
+        `grappa_relax_steps_cut_workspace_bytes`; a step stays four launches."""
         _xyz3(xyz, "relax_steps")
         if isinstance(check_every, bool) or int(check_every) != check_every or check_every < 1:
             raise ValueError(f"relax_steps: check_every must be an integer >= 1, got {check_every}")
@@ -310,28 +313,38 @@ class MMBackend:
         counts = _atom_counts(atom_counts_host, N, B, "relax_steps")
         nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_steps")
         o = _opts_struct(_lib.RelaxOpts, opts, "relax_steps")
+        cut = None
+        if cutoff is not None:
+            if nb is None:
+                raise ValueError("relax_steps: a cutoff needs the nonbonded tables (nb)")
+            cut = _cut_struct(cutoff, "relax_steps")
         if N == 0 or Cc == 0 or B == 0:
             return
         table = self._item_table(nb, counts, N, Cc, dev)
         table_dev, n_items, n_blocks, _ = table
-        need = int(self.lib.grappa_relax_steps_workspace_bytes(N, Cc, B, n_blocks))
+        need = int((self.lib.grappa_relax_steps_workspace_bytes if cut is None else self.lib.grappa_relax_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
         if workspace is None:
             workspace = self._workspace(need, dev, "relax_steps")
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         n_running = torch.zeros(1, dtype=torch.int32, device=dev)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        common = (st, C.byref(d), ndp, C.byref(o), table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
-        _chk(self.lib.grappa_relax_steps_init_f32(*common, n_running.data_ptr()), "grappa_relax_steps_init_f32")
+        if cut is None:
+            head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
+        else:
+            head, sfx = (st, C.byref(d), ndp, C.byref(cut), C.byref(o)), "_cut_f32"
+        init, run, finish = (getattr(self.lib, f"grappa_relax_steps_{n}{sfx}") for n in ("init", "run", "finish"))
+        common = (*head, table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
+        _chk(init(*common, n_running.data_ptr()), f"grappa_relax_steps_init{sfx}")
         left = o.max_steps
         while left > 0:
             n = min(check_every, left)
-            _chk(self.lib.grappa_relax_steps_run_f32(*common, n, n_running.data_ptr()), "grappa_relax_steps_run_f32")
+            _chk(run(*common, n, n_running.data_ptr()), f"grappa_relax_steps_run{sfx}")
             left -= n
             if int(n_running.item()) <= 0:          # the one host sync per chunk
                 break
-        _chk(self.lib.grappa_relax_steps_finish_f32(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(),
-                                                    steps.data_ptr(), status.data_ptr()), "grappa_relax_steps_finish_f32")
+        _chk(finish(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(),
+                    status.data_ptr()), f"grappa_relax_steps_finish{sfx}")
 
     # ------------------------------------------------------------------ dynamics
     def _md_call(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,

@@ -256,20 +256,6 @@ __global__ __launch_bounds__(NB_NT) void ms_force_cut_kernel(MsForceArgs a, NbCu
     ms_force_body(a, NbCut{c, near});
 }
 
-// with a cutoff, the launch of init between ms_init_kernel and the first force: the boxes and exception ranges at x (csrc/nb_cut.h)
-struct MsBoxArgs {
-    RsGeom q;
-    const float* x;
-    const int *exc_ptr, *exc_atom;
-    float4* box;
-    int2* er;
-};
-
-__global__ __launch_bounds__(NB_NT) void ms_box_kernel(MsBoxArgs a) {
-    RsItem r;
-    if (rs_item(a.q, r)) nb_cut_box_range(r, a.q.C, a.x, a.exc_ptr, a.exc_atom, a.box, a.er);
-}
-
 // ------------------------------------------------------------------------------------------------ energies and outputs
 struct MsOutArgs {
     int N, C, B, n_blocks, has_nb;
@@ -318,22 +304,8 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
-// a cutoff as the three calls carry it: the caller's options and the device constants made of them (c == NULL: none)
-struct MsCut {
-    const grappa_nb_cut* opts;
-    NbCutDev dev;
-};
-
-// cut given: false if its options are refused or nb is missing; else the constants (box and er are set once the workspace is laid out)
-bool ms_cut_make(const grappa_nb_cut* cut, const grappa_nb_desc* nb, MsCut& c) {
-    c.opts = cut;
-    c.dev = NbCutDev{};
-    if (!nb || !nb_cut_consts(cut, c.dev.k, c.dev.thr)) return false;
-    c.dev.prune = cut->prune;
-    return true;
-}
-
-void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const RsGeom& q, const MsWs& w,
+// (a cutoff as the three calls carry it: RsCut / rs_cut_make of csrc/rs_force.h; c == NULL: none)
+void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const MsWs& w,
                      const float* mass, float hk, float* frame_xyz, int n_items) {
     MsForceArgs f;
     f.f = rs_force_in(mm, nb, q, w.x, w.status);
@@ -349,7 +321,7 @@ void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_d
 }
 
 // steps_terms_at of csrc/rs_force.h at w.x, in the part of this workspace that the cut or the planned nonbonded call takes
-int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const int* table_dev, int n_items,
+int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const int* table_dev, int n_items,
                     int n_blocks, const MsWs& w) {
     if (c) return steps_terms_at(stream, mm, nb, c->opts, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbcut, w.nbcut_bytes);
     return steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
@@ -365,7 +337,7 @@ MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const 
 }
 
 // the three calls, with and without a cutoff (c == NULL: none)
-int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const float* mass,
+int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
             const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
@@ -385,14 +357,14 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     if (c && n_items > 0) {
-        const MsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
-        GRAPPA_LAUNCH(ms_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+        const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
+        GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
     }
     if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
     return grappa_launch_status();
 }
 
-int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const float* mass,
+int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
            float* frames_xyz, float* frames_epot, float* frames_ekin) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
@@ -436,7 +408,7 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     return grappa_launch_status();
 }
 
-int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsCut* c, const grappa_md_opts* o, const int* table_dev,
+int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const int* table_dev,
               int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
               int* status) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
@@ -491,8 +463,8 @@ extern "C" size_t grappa_md_steps_cut_workspace_bytes(int N, int C, int B, int n
 extern "C" int grappa_md_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                             const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const float* vel_in,
                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
-    MsCut c;
-    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
@@ -500,8 +472,8 @@ extern "C" int grappa_md_steps_run_cut_f32(void* stream, const grappa_mm_desc* m
                                            const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const int* table_dev,
                                            int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz,
                                            float* frames_epot, float* frames_ekin) {
-    MsCut c;
-    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
                   frames_epot, frames_ekin);
 }
@@ -510,7 +482,7 @@ extern "C" int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc
                                               const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
                                               size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
                                               int* status) {
-    MsCut c;
-    if (cut && !ms_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
 }

@@ -20,6 +20,10 @@
 //   finish : one more decide (stop tests only), the six energy terms by the library's own energy kernels (mm_energy_kernel,
 //            nb_pairs_kernel + nb_reduce_kernel through their entry points: no second energy code path) at the held coordinates, and a
 //            copy kernel.
+//   cutoff : grappa_relax_steps_*_cut_f32 (cut == NULL: the calls without).  The force launch is rs_force under the cut policy of
+//            csrc/nb_cut.h; the move launch's item writes the box of its own (block, conformations) after moving -- the box's only
+//            writer -- and the force launch reads all boxes across the launch boundary: a step stays four launches, init gains one (boxes
+//            and exception ranges).  The finish's nonbonded energy by grappa_nonbonded_fwd_cut_f32 at the held coordinates.
 // Same input, same bits; a molecule's bits do not depend on its place in the batch.
 #include <float.h>
 #include <limits.h>
@@ -47,10 +51,15 @@ struct RsWs {
     float* dpart;                        // [n_blocks][C]: max |h v_i|
     float *e_mm, *e_nb, *terms;          // finish: [B,C], [B,C], [6,B,C]
     double* nbpart;                      // finish: the nonbonded kernel's partial energies [n_blocks][C][2]
+    float4* box;                         // with a cutoff: the blocks' boxes [n_blocks][C][2] and exception ranges [n_blocks] (csrc/nb_cut.h)
+    int2* er;
+    char* nbcut;                         // with a cutoff, finish: the workspace of grappa_nonbonded_fwd_cut_f32
+    size_t nbcut_bytes;
     size_t total;
 };
 
-RsWs rs_layout(char* base, int N, int C, int B, int n_blocks) {
+// (the words of a cutoff lie behind the others: without one the layout is the one it was)
+RsWs rs_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false) {
     RsWs w;
     WsCarve k{base};
     const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
@@ -62,6 +71,12 @@ RsWs rs_layout(char* base, int N, int C, int B, int n_blocks) {
     w.dpart = k.take<float>(kc);
     w.e_mm = k.take<float>(bc), w.e_nb = k.take<float>(bc), w.terms = k.take<float>(6 * bc);
     w.nbpart = k.take<double>(2 * kc);
+    w.box = nullptr, w.er = nullptr, w.nbcut = nullptr, w.nbcut_bytes = 0;
+    if (cut) {
+        w.box = k.take<float4>(2 * kc), w.er = k.take<int2>((size_t)n_blocks);
+        w.nbcut_bytes = grappa_nonbonded_cut_workspace_bytes(C, n_blocks);
+        w.nbcut = k.take<char>(w.nbcut_bytes);
+    }
     w.total = k.off;
     return w;
 }
@@ -113,9 +128,10 @@ struct RsForceArgs {
     double* part;
 };
 
-__global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
+template <class Cut>
+__device__ __forceinline__ void rs_force_body(const RsForceArgs& a, const Cut& cut) {
     __shared__ RsShared sh;
-    rs_force(a.f, sh, NbNoCut{}, [&](const RsItem& r, const RsLane& w, V3 gi) {
+    rs_force(a.f, sh, cut, [&](const RsItem& r, const RsLane& w, V3 gi) {
         const int C = a.f.q.C, ni = r.ni;
         float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
         if (w.owner) {
@@ -143,6 +159,14 @@ __global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) {
             o[0] = sP, o[1] = sF, o[2] = sv, o[3] = (double)mg;
         }
     });
+}
+
+__global__ __launch_bounds__(NB_NT) void rs_force_kernel(RsForceArgs a) { rs_force_body(a, NbNoCut{}); }
+
+// (the rule looks only at the item's running conformations: a.f.status is the minimiser's, RS_RUNNING while an item runs)
+__global__ __launch_bounds__(NB_NT) void rs_force_cut_kernel(RsForceArgs a, NbCutDev c) {
+    __shared__ unsigned char near[NB_NT];
+    rs_force_body(a, NbCut{c, near});
 }
 
 // ------------------------------------------------------------------------------------------------ decide
@@ -247,7 +271,30 @@ __global__ __launch_bounds__(NB_NT) void rs_vel_kernel(RsUpdArgs a) {
     }
 }
 
-__global__ __launch_bounds__(NB_NT) void rs_move_kernel(RsUpdArgs a) {
+// the thread's (atom, conformation) of the item, t < ni * nc; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
+template <bool CUT>
+__device__ __forceinline__ void rs_move_lane(const RsUpdArgs& a, const RsItem& r, int C, int t, int ni, const float* sdm, const int* run,
+                                             float* bxl) {
+    const int cl = t / ni, il = t - cl * ni;
+    if (!run[cl]) return;
+    const int c = r.c0 + cl;
+    const float dm = sdm[cl], h = a.s.h[(size_t)r.mol * C + c];
+    const float sc = dm > 0.f ? fminf(1.0f, a.max_disp / dm) : 1.0f;
+    const float hs = sc * h;
+    const size_t off = ((size_t)(r.i0 + il) * C + c) * 3;
+    const V3 vk = {a.v[off], a.v[off + 1], a.v[off + 2]};
+    const float xx = a.x[off] + hs * vk.x, xy = a.x[off + 1] + hs * vk.y, xz = a.x[off + 2] + hs * vk.z;
+    a.x[off] = xx, a.x[off + 1] = xy, a.x[off + 2] = xz;
+    a.v[off] = sc * vk.x, a.v[off + 1] = sc * vk.y, a.v[off + 2] = sc * vk.z;
+    if constexpr (CUT) bxl[0] = xx, bxl[1] = xy, bxl[2] = xz;
+}
+
+// CUT: the item also writes the box of its own (block, conformations) at the coordinates it leaves (csrc/nb_cut.h): it is the box's only
+// writer, the force launch after it the reader.  A stopped conformation keeps its box, as it keeps its x.  Only the uniform returns of
+// rs_item and rs_running come before the barriers of nb_cut_box_write: the whole workgroup reaches them.  (a by value: through a reference
+// the all-pairs instantiation's index arithmetic compiles to other instructions than rs_move_kernel had.)
+template <bool CUT>
+__device__ __forceinline__ void rs_move_body(const RsUpdArgs a, float4* box) {
     __shared__ float sdm[NB_CW];
     __shared__ int run[NB_CW];
     RsItem r;
@@ -266,19 +313,21 @@ __global__ __launch_bounds__(NB_NT) void rs_move_kernel(RsUpdArgs a) {
         for (int o = GRAPPA_WAVE / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, GRAPPA_WAVE));
         if (lane == 0) sdm[cc] = m;
     }
-    __syncthreads();
-    if (t >= ni * r.nc) return;
-    const int cl = t / ni, il = t - cl * ni;
-    if (!run[cl]) return;
-    const int c = r.c0 + cl;
-    const float dm = sdm[cl], h = a.s.h[(size_t)r.mol * C + c];
-    const float sc = dm > 0.f ? fminf(1.0f, a.max_disp / dm) : 1.0f;
-    const float hs = sc * h;
-    const size_t off = ((size_t)(r.i0 + il) * C + c) * 3;
-    const V3 vk = {a.v[off], a.v[off + 1], a.v[off + 2]};
-    a.x[off] += hs * vk.x, a.x[off + 1] += hs * vk.y, a.x[off + 2] += hs * vk.z;
-    a.v[off] = sc * vk.x, a.v[off + 1] = sc * vk.y, a.v[off + 2] = sc * vk.z;
+    if constexpr (CUT) {
+        __shared__ float bx[NB_NT * 3];
+        __shared__ int keep[NB_CW];
+        if (t < r.nc) keep[t] = !run[t];
+        __syncthreads();
+        if (t < ni * r.nc) rs_move_lane<true>(a, r, C, t, ni, sdm, run, bx + 3 * t);
+        nb_cut_box_write(bx, keep, ni, r.nc, r.blk, C, r.c0, box);
+    } else {
+        __syncthreads();
+        if (t < ni * r.nc) rs_move_lane<false>(a, r, C, t, ni, sdm, run, nullptr);
+    }
 }
+
+__global__ __launch_bounds__(NB_NT) void rs_move_kernel(RsUpdArgs a) { rs_move_body<false>(a, nullptr); }
+__global__ __launch_bounds__(NB_NT) void rs_move_cut_kernel(RsUpdArgs a, float4* box) { rs_move_body<true>(a, box); }
 
 // ------------------------------------------------------------------------------------------------ finish
 struct RsOutArgs {
@@ -316,26 +365,29 @@ __global__ __launch_bounds__(256) void rs_out_kernel(RsOutArgs a) {
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
-void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const RsWs& w, int n_items) {
+// (a cutoff as the three calls carry it: RsCut / rs_cut_make of csrc/rs_force.h; c == NULL: none)
+
+void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const RsWs& w,
+                     int n_items) {
     RsForceArgs f;
     f.f = rs_force_in(mm, nb, q, w.x, w.s.status);
     f.v = w.v, f.g = w.g, f.part = w.part;
-    GRAPPA_LAUNCH(rs_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
+    if (c) {
+        NbCutDev d = c->dev;
+        d.box = w.box, d.er = w.er;
+        GRAPPA_LAUNCH(rs_force_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d);
+    } else {
+        GRAPPA_LAUNCH(rs_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
+    }
 }
 
-}  // namespace
-
-extern "C" size_t grappa_relax_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
-    return rs_layout(nullptr, N, C, B, n_blocks).total;
-}
-
-extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
-                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
+// the three calls, with and without a cutoff (c == NULL: none)
+int rs_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o, const int* table_dev,
+            int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!n_running_dev) return GRAPPA_ERR_ARG;
-    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     RsInitArgs a;
@@ -346,19 +398,23 @@ extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* m
     a.n_running = n_running_dev;
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
     GRAPPA_LAUNCH(rs_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    if (n_items > 0) rs_launch_force(st, mm, nb, rs_geom(mm, table_dev, n_blocks), w, n_items);
+    const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    if (c && n_items > 0) {
+        const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
+        GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+    }
+    if (n_items > 0) rs_launch_force(st, mm, nb, c, q, w, n_items);
     return grappa_launch_status();
 }
 
-extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
-                                          const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps,
-                                          int* n_running_dev) {
+int rs_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o, const int* table_dev,
+           int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps, int* n_running_dev) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!n_running_dev) return GRAPPA_ERR_ARG;
-    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
@@ -373,20 +429,21 @@ extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm
         GRAPPA_LAUNCH(rs_decide_kernel, dim3(bc), dim3(RS_DNT), 0, st, dc);
         if (n_items > 0) {
             GRAPPA_LAUNCH(rs_vel_kernel, dim3(items), dim3(NB_NT), 0, st, u);
-            GRAPPA_LAUNCH(rs_move_kernel, dim3(items), dim3(NB_NT), 0, st, u);
-            rs_launch_force(st, mm, nb, q, w, n_items);
+            if (c) GRAPPA_LAUNCH(rs_move_cut_kernel, dim3(items), dim3(NB_NT), 0, st, u, w.box);
+            else GRAPPA_LAUNCH(rs_move_kernel, dim3(items), dim3(NB_NT), 0, st, u);
+            rs_launch_force(st, mm, nb, c, q, w, n_items);
         }
     }
     return grappa_launch_status();
 }
 
-extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
-                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
-                                             float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status) {
+int rs_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o,
+              const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* energy, float* term_energy,
+              float* grad, float* gmax, int* steps, int* status) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !energy || !gmax || !steps || !status) return GRAPPA_ERR_ARG;
-    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks);
+    const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
@@ -396,8 +453,10 @@ extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc*
     dc.C = mm->C, dc.n_blocks = n_blocks, dc.blk_ptr = q.blk_ptr, dc.part = w.part, dc.s = w.s;
     dc.n_running = nullptr, dc.final = 1;
     GRAPPA_LAUNCH(rs_decide_kernel, dim3((unsigned)bc), dim3(RS_DNT), 0, st, dc);
-    const int erc = steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
-                                   sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
+    // (steps_terms_at of csrc/rs_force.h at w.x, in the part of this workspace that the cut or the planned nonbonded call takes)
+    const int erc = c ? steps_terms_at(stream, mm, nb, c->opts, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbcut, w.nbcut_bytes)
+                      : steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
+                                       sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
     if (erc != GRAPPA_OK) return erc;
     RsOutArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.has_nb = nb != nullptr;
@@ -407,4 +466,61 @@ extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc*
     const size_t n3 = (size_t)mm->N * mm->C * 3, n = n3 > bc ? n3 : bc;
     GRAPPA_LAUNCH(rs_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     return grappa_launch_status();
+}
+
+}  // namespace
+
+extern "C" size_t grappa_relax_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return rs_layout(nullptr, N, C, B, n_blocks).total;
+}
+
+extern "C" int grappa_relax_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
+    return rs_init(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_running_dev);
+}
+
+extern "C" int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                          const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps,
+                                          int* n_running_dev) {
+    return rs_run(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_steps, n_running_dev);
+}
+
+extern "C" int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
+                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
+                                             float* energy, float* term_energy, float* grad, float* gmax, int* steps, int* status) {
+    return rs_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy, term_energy, grad, gmax, steps,
+                     status);
+}
+
+// with a cutoff: cut == NULL is the call above; bad options in cut, or a cut without nb, are refused before anything else is looked at
+extern "C" size_t grappa_relax_steps_cut_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return rs_layout(nullptr, N, C, B, n_blocks, true).total;
+}
+
+extern "C" int grappa_relax_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                               const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                               size_t ws_bytes, int* n_running_dev) {
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return rs_init(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_running_dev);
+}
+
+extern "C" int grappa_relax_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                              const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                              size_t ws_bytes, int n_steps, int* n_running_dev) {
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return rs_run(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_steps, n_running_dev);
+}
+
+extern "C" int grappa_relax_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                                 const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                                 size_t ws_bytes, float* xyz_out, float* energy, float* term_energy, float* grad, float* gmax,
+                                                 int* steps, int* status) {
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return rs_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy, term_energy, grad,
+                     gmax, steps, status);
 }

@@ -140,4 +140,34 @@ inline int steps_terms_at(void* stream, const grappa_mm_desc* mm, const grappa_n
     return grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, e_nb, te, nullptr, nbws, nbws_bytes);
 }
 
+// ------------------------------------------------------------------------------------------------ a cutoff on the stepwise paths
+// a cutoff as the three calls of a stepwise path carry it: the caller's options and the device constants made of them
+struct RsCut {
+    const grappa_nb_cut* opts;
+    NbCutDev dev;
+};
+
+// cut given: false if its options are refused or nb is missing; else the constants (box and er are set once the workspace is laid out)
+inline bool rs_cut_make(const grappa_nb_cut* cut, const grappa_nb_desc* nb, RsCut& c) {
+    c.opts = cut;
+    c.dev = NbCutDev{};
+    if (!nb || !nb_cut_consts(cut, c.dev.k, c.dev.thr)) return false;
+    c.dev.prune = cut->prune;
+    return true;
+}
+
+// with a cutoff, the launch of init between the init kernel and the first force: the boxes and exception ranges at x (csrc/nb_cut.h)
+struct RsBoxArgs {
+    RsGeom q;
+    const float* x;
+    const int *exc_ptr, *exc_atom;
+    float4* box;
+    int2* er;
+};
+
+__global__ __launch_bounds__(NB_NT) void rs_box_kernel(RsBoxArgs a) {
+    RsItem r;
+    if (rs_item(a.q, r)) nb_cut_box_range(r, a.q.C, a.x, a.exc_ptr, a.exc_atom, a.box, a.er);
+}
+
 }  // namespace

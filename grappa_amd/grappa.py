@@ -54,12 +54,17 @@ class Grappa:
         g = g.to("cpu")
         return Parameters.from_dgl(g)
 
-    def relax(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, check_every: int = 32, **opts):
+    def relax(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, check_every: int = 32, cutoff=None, **opts):
         """`predict` followed by `grappa_amd.relax.relax`: the conformations xyz (n_confs, n_atoms, 3) of `molecule` minimised on the
         device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in the molecule's atom order) -> RelaxResult.
         stepwise=False: the fused kernel (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules
-        of any size, which syncs with the host once per chunk of `check_every` steps (see `grappa_amd.relax.relax_graph`)"""
+        of any size, which syncs with the host once per chunk of `check_every` steps (see `grappa_amd.relax.relax_graph`).
+        cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom (None: all pairs): the minimisation under the nonbonded
+        cutoff that `simulate(..., cutoff=)` runs under, on the stepwise path; the result's energy is then the sum of the cut terms;
+        it needs `nonbonded` and stepwise="auto" (or True)"""
         from .relax import relax
+        if cutoff is not None:
+            opts = {**opts, "cutoff": cutoff}
         return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)
 
     def torsion_scan(self, molecule: Molecule, xyz, dihedral, angles=None, nonbonded=None, **kw):

@@ -14,6 +14,14 @@ in include/grappa_hip.h.  Units: Angstrom, kcal/mol, kcal/mol/A.  An item stops 
 The defaults (`RELAX_DEFAULTS`; tolerance = 10 kJ/mol/nm, OpenMM's `minimizeEnergy` default) were checked on small chain molecules only
 and are not tuned.  With `stepwise=False` (the default) a molecule above `relax_max_atoms()` atoms is refused; `stepwise="auto"` takes
 the stepwise path for a batch that holds one.  The two paths add in different orders: the same trajectory within rounding, not the same bits.
+
+Cutoff (`cutoff=`, a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom): the nonbonded term under OpenMM's `CutoffNonPeriodic`
+conventions, as `grappa_amd.nonbonded` states them and `simulate(..., cutoff=)` moves under them, on the stepwise path
+(`grappa_relax_steps_*_cut_f32`), whose force launch then skips the 64 x 64 atom tiles that lie beyond the cutoff; a step stays four
+launches.  The minimiser then works on that energy: `RelaxResult.energy` (and the backend's `term_energy`) are the CUT terms, the
+Hamiltonian a `simulate` with the same cutoff starts under.  It needs `nonbonded`; `stepwise="auto"` goes stepwise whenever a cutoff
+is given, `stepwise=False` is refused.  The fused kernels, restraints (and so `torsion_scan`), periodic boxes, PME and a long-range
+Lennard-Jones correction have no cutoff.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -23,7 +31,7 @@ import torch
 
 from .constants import TUPLE_LEVELS
 from .energy import mm_tables
-from .nonbonded import NonbondedBatch, NonbondedParameters
+from .nonbonded import NonbondedBatch, NonbondedParameters, as_cutoff
 from .parameters import Parameters
 
 RELAX_DEFAULTS = {"tolerance": 10.0 / 4.184 / 10.0, "max_steps": 1000, "dt_start": 0.002, "dt_max": 0.02, "max_disp": 0.1, "n_min": 5,
@@ -62,7 +70,7 @@ def relax_options(**opts) -> dict:
 
 @dataclass
 class RelaxResult:
-    """xyz: the relaxed coordinates; energy: the total energy there; gradient_max: the largest atomic gradient norm there; steps;
+    """xyz: the relaxed coordinates; energy: the total energy there (under a cutoff: the sum of the cut terms); gradient_max: the largest atomic gradient norm there; steps;
     status (see the module text).  From `relax_graph`: tensors on the graph's device, xyz (N, C, 3), the others (B, C).  From `relax`:
     numpy arrays of one molecule, xyz (n_confs, n_atoms, 3), the others (n_confs,)."""
     xyz: object
@@ -84,6 +92,19 @@ def _stepwise_options(stepwise, check_every):
     if isinstance(check_every, bool) or not isinstance(check_every, (int, np.integer)) or check_every < 1:
         raise ValueError(f"check_every must be an integer >= 1, got {check_every!r}")
     return stepwise, int(check_every)
+
+
+def _cutoff_options(cutoff, nonbonded, stepwise, restraints):
+    """the rules of a cutoff (those of `simulate`), decided on the host before anything is built -> a `Cutoff` or None"""
+    cutoff = as_cutoff(cutoff)
+    if cutoff is not None:
+        if nonbonded is None:
+            raise ValueError("relax: a cutoff needs the nonbonded parameters (nonbonded=)")
+        if stepwise is False:
+            raise ValueError('relax: a cutoff runs on the stepwise path only: pass stepwise="auto" (or True)')
+        if restraints is not None:
+            raise ValueError("relax: restraints are taken by the fused minimiser only, a cutoff on the stepwise path only")
+    return cutoff
 
 
 def graph_coordinates(g, terms):
@@ -116,7 +137,8 @@ def graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev):
 
 
 def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
-                offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, restraints=None, **opts) -> RelaxResult:
+                offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, restraints=None, cutoff=None,
+                **opts) -> RelaxResult:
     """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
     exactly what `Energy` reads, through the same plan.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded
     terms only).  **opts: see RELAX_DEFAULTS.  The graph is not modified.
@@ -128,10 +150,14 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     restraints: a `grappa_amd.restraints.RestraintBatch` for the graph's molecules and C on the graph's device (None: no restraints,
     the call as it always was).  The minimiser then works on E + E_r; `energy` stays the force field's, and the result carries
     `restraint_energy` (B, C) and `dihedrals` (R, C).  An item whose tables the kernel refuses comes back with status 5.  The fused
-    path only: with restraints stepwise=True raises, and "auto" raises for a batch that holds a molecule above the limit."""
+    path only: with restraints stepwise=True raises, and "auto" raises for a batch that holds a molecule above the limit.
+    cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls made are exactly those without this argument):
+    see the module text.  `energy` is then the sum of the cut terms.  It needs `nonbonded` and the stepwise path: "auto" then goes
+    stepwise whatever the sizes, stepwise=False and restraints are refused."""
     from .backend import get_backend
     o = relax_options(**opts)
     stepwise, check_every = _stepwise_options(stepwise, check_every)
+    cutoff = _cutoff_options(cutoff, nonbonded, stepwise, restraints)
     terms = list(terms)
     if restraints is not None:
         from .restraints import RestraintBatch
@@ -149,7 +175,7 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     if above and stepwise is False:
         raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
                          f"minimiser (stepwise=True or stepwise='auto' relaxes molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and above)
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None))
     B, C = plan.B, xyz.shape[1]
     if restraints is not None:
         if restraints.B != B or restraints.C != C:
@@ -171,7 +197,7 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
         restr = dict(restraints=restraints, restraint_energy=er, dihedral_out=phi)
     if use_steps:
         get_backend().relax_steps(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
-                                  atom_counts_host=counts, check_every=check_every)
+                                  atom_counts_host=counts, check_every=check_every, **({} if cutoff is None else {"cutoff": cutoff}))
     else:
         get_backend().relax_fire(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
                                  atom_counts_host=counts, **restr)
@@ -228,15 +254,19 @@ def graph_from_parameters(parameters: Parameters, xyz):
 
 
 def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, stepwise=False,
-          check_every: int = CHECK_EVERY_DEFAULT, restraints=None, **opts) -> RelaxResult:
+          check_every: int = CHECK_EVERY_DEFAULT, restraints=None, cutoff=None, **opts) -> RelaxResult:
     """Relax the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`, whose atoms are in the
     order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom -> RelaxResult with xyz of the same shape
     (float64) and energy / gradient_max / steps / status of shape (n_confs,).  stepwise, check_every: see `relax_graph` (the stepwise
     path takes a molecule of any size and syncs with the host once per chunk of `check_every` steps).
     restraints: a `grappa_amd.restraints.Restraints` whose indices are in the order of `parameters.atoms` (None: none); the result
-    then carries restraint_energy (n_confs,) and dihedrals (R, n_confs), and `energy` stays the force field's.  The fused path only."""
+    then carries restraint_energy (n_confs,) and dihedrals (R, n_confs), and `energy` stays the force field's.  The fused path only.
+    cutoff: see `relax_graph` (`energy` is then the sum of the cut terms; the stepwise path only, no restraints)."""
     relax_options(**opts)
     _stepwise_options(stepwise, check_every)
+    extra = {}
+    if _cutoff_options(cutoff, nonbonded, stepwise, restraints) is not None:
+        extra["cutoff"] = as_cutoff(cutoff)
     g = graph_from_parameters(parameters, xyz)
     batch = None
     if restraints is not None:
@@ -253,7 +283,8 @@ def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] 
         if nonbonded.n_atoms != g.num_nodes("n1"):
             raise ValueError(f"the nonbonded parameters describe {nonbonded.n_atoms} atoms, the molecule has {g.num_nodes('n1')}")
         nb = NonbondedBatch([nonbonded]).to(device)
-    r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, restraints=None if batch is None else batch.to(device), **opts)
+    r = relax_graph(g.to(device), nb, stepwise=stepwise, check_every=check_every, restraints=None if batch is None else batch.to(device), **extra,
+                    **opts)
     res = RelaxResult(r.xyz.cpu().numpy().transpose(1, 0, 2).astype(np.float64), r.energy.cpu().numpy()[0].astype(np.float64),
                       r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])
     if batch is not None:
@@ -304,8 +335,10 @@ def torsion_scan(parameters: Parameters, xyz, dihedral, angles=None, nonbonded: 
     launch, one workgroup per point.  The points are INDEPENDENT: each starts from the input with one side of the bond rotated to its
     angle (`scan_starts`), nothing is propagated from a neighbouring point -- so a point can end in another basin than its neighbours.
     **opts: the options of `relax` (RELAX_DEFAULTS).  With the default k FIRE's defaults are stable (the restraint is softer than
-    every bond); whether a point reached the tolerance is in `status`."""
+    every bond); whether a point reached the tolerance is in `status`.  It takes no cutoff: restraints are the fused minimiser's."""
     from .restraints import Restraints
+    if "cutoff" in opts:
+        raise ValueError("torsion_scan: takes no cutoff (restraints are taken by the fused minimiser only, a cutoff runs on the stepwise path only)")
     if angles is None:
         angles = -np.pi + np.deg2rad(15.0) * np.arange(24)
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)

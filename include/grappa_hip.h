@@ -664,6 +664,27 @@ int grappa_relax_steps_run_f32(void* stream, const grappa_mm_desc* mm, const gra
 int grappa_relax_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_relax_opts* o,
                                   const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* energy,
                                   float* term_energy, float* grad, float* gmax, int* steps, int* status);
+/* The stepwise minimiser under a nonbonded cutoff (additions to ABI 11): the three calls above with `const grappa_nb_cut* cut` after nb.
+ * cut == NULL forwards to the call above, with its launches and its bits; cut != NULL needs nb (else GRAPPA_ERR_ARG) and bad options in
+ * cut are GRAPPA_ERR_ARG, nothing launched and nothing written.  The conventions are grappa_nb_cut's, stated there: the nonbonded force
+ * is that of grappa_nonbonded_fwd_cut_f32 (same formulas, same skip rule; a conformation that has stopped is not looked at by the rule),
+ * and the loop minimises that energy.  A step stays FOUR launches: the move launch's work item writes the box of its own (block,
+ * conformations) after moving -- it is the box's only writer, and a stopped conformation keeps its box as it keeps its x -- and the force
+ * launch reads all boxes across the launch boundary.  init gains one launch (boxes and ranges at the start coordinates): 3.  finish's
+ * terms 4 and 5 come from the kernels of grappa_nonbonded_fwd_cut_f32 at xyz_out: its bits there.  Pass the same cut to all three
+ * calls.  The workspace is grappa_relax_steps_cut_workspace_bytes(N, C, B, n_blocks): the one above plus about 88 n_blocks C; ws_bytes
+ * below it is GRAPPA_ERR_WORKSPACE, nothing launched. */
+size_t grappa_relax_steps_cut_workspace_bytes(int N, int C, int B, int n_blocks);
+int grappa_relax_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                    const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+                                    int* n_running_dev);
+int grappa_relax_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                   const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+                                   int n_steps, int* n_running_dev);
+int grappa_relax_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                      const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                      size_t ws_bytes, float* xyz_out, float* energy, float* term_energy, float* grad, float* gmax,
+                                      int* steps, int* status);
 
 /* ------------------------------------------------------------------------------------------------
  * Langevin molecular dynamics under the full MM force field (additions to ABI 11): BAOAB (Leimkuhler and Matthews 2013; on-step

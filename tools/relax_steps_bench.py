@@ -12,12 +12,20 @@ The sides of a size are timed alternately, `--reps` times each after one warm-up
 the maximum.  The chains carry bonds, angles and proper torsions along the chain (k_bond 500, k_angle 100, three periodicities) with the
 lattice geometry as equilibrium, and the nonbonded parameters of tools/nonbonded_bench.py.
 
+With --cutoff RC [--switch RS] the tool measures the nonbonded cutoff of relax(..., cutoff=) instead: at the two chains three sides --
+all pairs, the cutoff with prune = 1 and with prune = 0 -- timed alternately by the same protocol (device events, one warm-up run, `--reps`
+runs each), all run times printed, with the tiles the cut energy kernel evaluates at the start coordinates.  Every size is a child
+process of its own under `timeout`; after one that fails nothing more is started.
+
     python tools/relax_steps_bench.py [--out profiles/relax_steps_bench.txt] [--steps 128] [--big-steps 16] [--reps 5]
+    python tools/relax_steps_bench.py --cutoff 10 [--switch 8] [--out profiles/relax_steps_cutoff_bench.txt]
     python tools/relax_steps_bench.py --dry          # build the inputs on the CPU and stop (a rehearsal: nothing is timed)
 """
 import argparse
 import datetime
+import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -73,6 +81,103 @@ def timed_alternately(fns, reps):
     return ms
 
 
+CUT_STAGES = ("device", "mid", "big")
+CUT_STAGE_LIMIT = 300          # seconds a stage may take
+CUT_SIDES = ("all pairs", "cut, prune=1", "cut, prune=0")
+
+
+def cut_stage(args):
+    """one stage of the cutoff measurement in this process -> one JSON line"""
+    if not torch.cuda.is_available():
+        sys.exit("relax_steps_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    from grappa_amd.nonbonded import Cutoff, NonbondedBatch
+    from grappa_amd.relax import relax_graph
+    be = get_backend()
+    if args.stage == "device":
+        prop = torch.cuda.get_device_properties(0)
+        print(json.dumps({"device": f"{prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, "
+                                    f"{prop.total_memory / 2 ** 30:.0f} GiB; library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}"}))
+        return
+    n_atoms, S = (args.mid_atoms, args.steps) if args.stage == "mid" else (args.big_atoms, args.big_steps)
+    gh, nbp = chain_graph(n_atoms)
+    g, nb = gh.to("cuda"), NonbondedBatch([nbp]).to("cuda")
+    cuts = {"all pairs": None, "cut, prune=1": Cutoff(args.cutoff, args.switch or None, prune=True),
+            "cut, prune=0": Cutoff(args.cutoff, args.switch or None, prune=False)}
+    sides = {k: (lambda c=c: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True, **({} if c is None else {"cutoff": c})))
+             for k, c in cuts.items()}
+    out = {"atoms": n_atoms, "steps": S, "tuples": {lv: int(g.num_nodes(lv)) for lv in ("n2", "n3", "n4")}, "exceptions": int(nb.n_exceptions),
+           "ran": {}, "launches": {}}
+    res = {}
+    for k, fn in sides.items():
+        n0 = be.lib.grappa_launch_count(0)
+        res[k] = fn()
+        torch.cuda.synchronize()
+        out["launches"][k] = int(be.lib.grappa_launch_count(0) - n0)
+        out["ran"][k] = bool((res[k].steps == S).all()) and bool((res[k].status == 0).all())
+    out["prune_bits_equal"] = bool(torch.equal(res["cut, prune=1"].xyz.view(torch.int32), res["cut, prune=0"].xyz.view(torch.int32)))
+    out["dx_cut_all_pairs"] = float((res["cut, prune=1"].xyz - res["all pairs"].xyz).abs().max())
+    # what the cut energy kernel evaluates at the start coordinates, per work item
+    x = g.nodes["n1"].data["xyz"].contiguous()
+    plan = be.nonbonded_plan(nb.atom_molptr_host, nb.N, x.shape[1], x.device)
+    e, t = torch.empty(nb.B, x.shape[1], device=x.device), {}
+    for prune in (True, False):
+        t[prune] = torch.zeros(plan[1], dtype=torch.int32, device=x.device)
+        be.nonbonded(x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps, e, None, None,
+                     plan=plan, cutoff=Cutoff(args.cutoff, args.switch or None, prune=prune), tiles=t[prune])
+    out["items"], out["tiles"], out["all_tiles"] = int(plan[1]), int(t[True].sum()), int(t[False].sum())
+    out["ms"] = timed_alternately(sides, args.reps)
+    print(json.dumps(out))
+
+
+def cut_main(args):
+    """the cutoff measurement: every stage a child process under its own time limit"""
+    lines = [f"# command: python {' '.join(sys.argv)}",
+             f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}"]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def run(name):
+        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
+              [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mid_atoms", "big_atoms", "steps", "big_steps", "reps", "cutoff", "switch")]
+        p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout + p.stderr)
+            sys.exit(f"relax_steps_bench: stage {name} ended with status {p.returncode}; nothing more is started")
+        return json.loads(p.stdout.strip().splitlines()[-1])
+
+    say(f"# device: {run('device')['device']}")
+    say(f"# relax_graph(stepwise=True), tolerance 0, a fixed step count; cutoff {args.cutoff} A, switch {args.switch or 'none'}, reaction field 78.3; "
+        f"device events around whole runs, the three sides of a size timed alternately in one process of its own, {args.reps} runs each after one "
+        "warm-up run each; all run times in ms; tiles: evaluated by the cut energy kernel at the start coordinates, summed over its work items; "
+        "this file is the tool's output, unedited")
+    for name in ("mid", "big"):
+        r = run(name)
+        S = r["steps"]
+        say(f"chain: 1 molecule, {r['atoms']} atoms, C = 1, {', '.join(f'{lv} {n}' for lv, n in r['tuples'].items())}, {r['exceptions']} exceptions, "
+            f"bonded + nonbonded, {S} steps")
+        per = {}
+        for k in CUT_SIDES:
+            ms = np.array(r["ms"][k])
+            per[k] = float(np.median(ms)) / S
+            say(f"  {k:13s} {per[k]:9.4f} ms/step (min {ms.min() / S:9.4f} .. max {ms.max() / S:9.4f})  run {np.median(ms):9.2f} ms  "
+                f"{r['launches'][k]} library launches per run; all items ran {S} steps: {r['ran'][k]}")
+            say(f"                runs: {', '.join(f'{m:.2f}' for m in ms)} ms")
+        say(f"  tiles: {r['tiles']} of {r['all_tiles']} evaluated over {r['items']} work items: mean {r['tiles'] / max(r['items'], 1):.2f} of "
+            f"{r['all_tiles'] / max(r['items'], 1):.2f} per item ({100.0 * r['tiles'] / max(r['all_tiles'], 1):.1f} %)")
+        say(f"  prune=1 and prune=0 end at the same bits: {r['prune_bits_equal']}; largest |x_cut - x_all pairs| after {S} steps = {r['dx_cut_all_pairs']:.3e} A")
+        slow, fast = max(r["ms"]["cut, prune=1"]), min(r["ms"]["all pairs"])
+        say(f"  all pairs / cut, prune=1 = {per['all pairs'] / per['cut, prune=1']:.2f}x ms per step; cut, prune=0 / all pairs = "
+            f"{per['cut, prune=0'] / per['all pairs']:.2f}x; slowest pruned run {slow:.2f} ms, fastest all-pairs run {fast:.2f} ms: "
+            f"{'faster' if slow < fast else 'NOT faster'}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -84,7 +189,14 @@ def main():
     ap.add_argument("--big-steps", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--dry", action="store_true")
+    ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
+    ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
+    ap.add_argument("--stage", default=None, choices=CUT_STAGES)
     args = ap.parse_args()
+    if args.stage:
+        return cut_stage(args)
+    if args.cutoff and not args.dry:
+        return cut_main(args)
     if args.dry:
         for n in (args.mid_atoms, args.big_atoms):
             g, nbp = chain_graph(n)
