@@ -282,6 +282,14 @@ SIGNATURES = {
                                          _sz, _i, _i, _vp, _vp, _vp]),
     "grappa_md_steps_finish_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), _vp, _i, _i, _vp, _sz,
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise dynamics with X-H constraints (additions to ABI 11): the _cut_ calls with grappa_md_cons after the options
+    "grappa_md_steps_cons_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "grappa_md_steps_init_cons_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                           _vp, _vp, _vp, _vp, _i, _i, _vp, _sz]),
+    "grappa_md_steps_run_cons_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                          _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp]),
+    "grappa_md_steps_finish_cons_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                             _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -371,16 +371,16 @@ class MMBackend:
         return d, o
 
     @staticmethod
-    def _md_cons(constraints, B, dev, constrain_start):
+    def _md_cons(constraints, B, dev, constrain_start, who="md_langevin"):
         """grappa_md_cons from a ConstraintBatch on `dev`"""
         from .constraints import MAX_LEAVES, ConstraintBatch
         if not isinstance(constraints, ConstraintBatch):
-            raise TypeError(f"md_langevin: constraints must be a ConstraintBatch or None, got {type(constraints).__name__}")
+            raise TypeError(f"{who}: constraints must be a ConstraintBatch or None, got {type(constraints).__name__}")
         ptr, atoms, dd = constraints.cluster_molptr, constraints.cluster_atoms, constraints.cluster_d
         _tensors(dev, ((ptr, "cluster_molptr", _I32), (atoms, "cluster_atoms", _I32), (dd, "cluster_d", _F32)))
         K = int(atoms.shape[0])
         if ptr.numel() != B + 1 or atoms.shape != (K, MAX_LEAVES + 1) or dd.shape != (K, MAX_LEAVES):
-            raise ValueError(f"md_langevin: expected cluster_molptr ({B + 1},), cluster_atoms (K,{MAX_LEAVES + 1}), cluster_d (K,{MAX_LEAVES})")
+            raise ValueError(f"{who}: expected cluster_molptr ({B + 1},), cluster_atoms (K,{MAX_LEAVES + 1}), cluster_d (K,{MAX_LEAVES})")
         return _lib.MdCons(cluster_molptr=ptr.data_ptr(), cluster_atoms=atoms.data_ptr() if K else None, cluster_d=dd.data_ptr() if K else None,
                            K=K, tolerance=float(constraints.tolerance), constrain_start=int(bool(constrain_start)))
 
@@ -424,30 +424,55 @@ class MMBackend:
         cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls above, unchanged) -- the nonbonded force and
         energies of grappa_md_steps_*_cut_f32: `nonbonded(..., cutoff=)`'s; it needs nb; the workspace is then
         `grappa_md_steps_cut_workspace_bytes`; a step stays two launches."""
+        self._md_steps("md_steps", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps,
+                       status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, None, True)
+
+    def md_steps_cons(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                      frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None,
+                      cutoff=None, constraints=None, constrain_start=True) -> None:
+        """`md_steps` with X-H bond constraints (include/grappa_hip.h grappa_md_steps_*_cons_f32): its arguments plus constraints, a
+        `grappa_amd.constraints.ConstraintBatch` on xyz's device with any number of clusters per molecule (None: `md_steps` itself), and
+        constrain_start (True constrains the input first, False continues a run; init alone reads it).  The loop is `md_langevin`'s with
+        constraints, with its statuses 4 and 5; a step is three launches, four under a cutoff; the workspace is
+        `grappa_md_steps_cons_workspace_bytes`.  Like `md_steps` it has NO device sync."""
+        self._md_steps("md_steps_cons", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
+                       steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
+                       constrain_start)
+
+    def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                  frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start):
+        """init, the run calls and finish of one stepwise run: the plain calls, the _cut_ calls with a cutoff, the _cons_ calls with
+        constraints (and the cutoff or NULL)"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
-            raise ValueError(f"md_steps: steps_per_call must be an integer >= 1, got {steps_per_call}")
-        d, o = self._md_call("md_steps", plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
+            raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
+        d, o = self._md_call(who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
                              steps, status, frames_xyz, frames_epot, frames_ekin)
         dev, N, Cc, B = xyz.device, d.N, d.C, d.B
         if atom_counts_host is None:
-            raise ValueError("md_steps: atom_counts_host is required (the work-item table is built from it)")
-        counts = _atom_counts(atom_counts_host, N, B, "md_steps")
-        nd = _nb_tables_desc(nb, N, Cc, B, dev, "md_steps")
+            raise ValueError(f"{who}: atom_counts_host is required (the work-item table is built from it)")
+        counts = _atom_counts(atom_counts_host, N, B, who)
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, who)
         cut = None
         if cutoff is not None:
             if nb is None:
-                raise ValueError("md_steps: a cutoff needs the nonbonded tables (nb)")
-            cut = _cut_struct(cutoff, "md_steps")
+                raise ValueError(f"{who}: a cutoff needs the nonbonded tables (nb)")
+            cut = _cut_struct(cutoff, who)
+        cons = self._md_cons(constraints, B, dev, constrain_start, who) if constraints is not None else None
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        need = int((self.lib.grappa_md_steps_workspace_bytes if cut is None else self.lib.grappa_md_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
+        if cons is not None:
+            need = int(self.lib.grappa_md_steps_cons_workspace_bytes(N, Cc, B, n_blocks, cons.K, int(cut is not None)))
+        else:
+            need = int((self.lib.grappa_md_steps_workspace_bytes if cut is None else self.lib.grappa_md_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
         if workspace is None:
-            workspace = self._workspace(need, dev, "md_steps")
+            workspace = self._workspace(need, dev, who)
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if cut is None:
+        if cons is not None:
+            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons)), "_cons_f32"
+        elif cut is None:
             head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
         else:
             head, sfx = (st, C.byref(d), ndp, C.byref(cut), C.byref(o)), "_cut_f32"

@@ -1,10 +1,10 @@
-"""X-H bond constraints for the fused Langevin dynamics (`grappa_amd.dynamics`, csrc/dynamics_cons.hip; the loop is stated in
-include/grappa_hip.h at grappa_md_langevin_cons_f32).  Constraints come as star clusters: one centre atom and up to `MAX_LEAVES`
+"""X-H bond constraints for the Langevin dynamics, fused and stepwise (`grappa_amd.dynamics`, csrc/dynamics_cons.hip and
+csrc/dynamics_steps.hip; the loop is stated in include/grappa_hip.h at grappa_md_langevin_cons_f32).  Constraints come as star clusters: one centre atom and up to `MAX_LEAVES`
 leaves, each held at one length from the centre (X-H, XH2, XH3, XH4); an atom belongs to at most one cluster.
   Constraints           the clusters of ONE molecule: `clusters` (K, 5) int32 -- the centre, then the leaves, -1 = no leaf, as atom
                         indices within the molecule -- and `lengths` (K, 4) float32 in Angstrom (0 where there is no leaf)
   hydrogen_constraints  every bond between a hydrogen and a heavy atom of a `Parameters`, at its predicted equilibrium length
-  ConstraintBatch       the molecules of a batch concatenated, with `cluster_molptr`, for `HipBackend.md_langevin(constraints=...)`
+  ConstraintBatch       the molecules of a batch concatenated, with `cluster_molptr`, for `HipBackend.md_langevin(constraints=...)` and `md_steps_cons`
 Rigid water (SETTLE) and constraints other than these stars are out of scope."""
 from typing import Optional, Sequence
 

@@ -21,12 +21,11 @@
 
 #include "common.h"
 #include "desc_check.h"
+#include "md_cons.h"
 #include "md_noise.h"
 #include "rx_force.h"
 
 namespace {
-
-constexpr int CL = GRAPPA_MD_CONS_MAX_LEAVES;
 
 struct MdConsArgs {
     grappa_mm_desc mm;
@@ -56,168 +55,27 @@ struct MdConsShared {
     int cl[RX_MAX];              // the atom's cluster within the molecule, -1: none
 };
 
-// a thread's cluster: the centre, the L constrained leaves (packed to the front) and their squared lengths
-struct Cluster {
-    int L, a0, al[CL];
-    float w0, wl[CL], d2[CL];
-};
-
 __device__ __forceinline__ V3 xyz_of(float4 p) { return {p.x, p.y, p.z}; }
 
-// M y = b for a 4 x 4 system whose unused rows are identity rows: elimination without pivoting, written out
-__device__ __forceinline__ void solve4(float (&M)[CL][CL], float (&b)[CL], float (&y)[CL]) {
-#pragma unroll
-    for (int i = 0; i < CL; ++i) {
-        const float inv = 1.0f / M[i][i];
-#pragma unroll
-        for (int j = i + 1; j < CL; ++j) {
-            const float f = M[j][i] * inv;
-#pragma unroll
-            for (int c = i + 1; c < CL; ++c) M[j][c] -= f * M[i][c];
-            b[j] -= f * b[i];
-        }
+// a cluster's atoms in LDS as the slots of csrc/md_cons.h, which holds P, S and the drift
+struct LdsCluster {
+    const Cluster& c;
+    RxShared& sh;
+    MdConsShared& cs;
+    __device__ __forceinline__ int at(int s) const { return s == 0 ? c.a0 : c.al[s - 1]; }
+    __device__ __forceinline__ V3 x(int s) const { return xyz_of(sh.xs[at(s)]); }
+    __device__ __forceinline__ V3 v(int s) const { return xyz_of(cs.vw[at(s)]); }
+    __device__ __forceinline__ void set_x(int s, V3 p) {
+        float4 q = sh.xs[at(s)];
+        q.x = p.x, q.y = p.y, q.z = p.z;
+        sh.xs[at(s)] = q;
     }
-#pragma unroll
-    for (int i = CL - 1; i >= 0; --i) {
-        float s = b[i];
-#pragma unroll
-        for (int c = i + 1; c < CL; ++c) s -= M[i][c] * y[c];
-        y[i] = s / M[i][i];
+    __device__ __forceinline__ void set_v(int s, V3 p) {
+        float4 q = cs.vw[at(s)];
+        q.x = p.x, q.y = p.y, q.z = p.z;
+        cs.vw[at(s)] = q;
     }
-}
-
-// P: the cluster's velocities projected onto r_k . (v_k - v_0) = 0, one direct solve
-__device__ __forceinline__ void cons_project(const Cluster& c, const RxShared& sh, MdConsShared& cs) {
-    const V3 x0 = xyz_of(sh.xs[c.a0]);
-    float4 v0 = cs.vw[c.a0];
-    V3 r[CL];
-    float M[CL][CL], b[CL], mu[CL];
-#pragma unroll
-    for (int k = 0; k < CL; ++k) {
-        r[k] = {0.f, 0.f, 0.f}, b[k] = 0.f;
-        if (k < c.L) {
-            r[k] = xyz_of(sh.xs[c.al[k]]) - x0;
-            b[k] = dot(r[k], xyz_of(cs.vw[c.al[k]]) - xyz_of(v0));
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < CL; ++k)
-#pragma unroll
-        for (int l = 0; l < CL; ++l) {
-            M[k][l] = k == l ? 1.f : 0.f;
-            if (k < c.L && l < c.L) M[k][l] = c.w0 * dot(r[k], r[l]) + (k == l ? c.wl[k] * dot(r[k], r[k]) : 0.f);
-        }
-    solve4(M, b, mu);
-    V3 s = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < CL; ++k)
-        if (k < c.L) {
-            s = s + mu[k] * r[k];
-            if (c.wl[k] > 0.f) {
-                float4 v = cs.vw[c.al[k]];
-                const float f = c.wl[k] * mu[k];
-                v.x -= f * r[k].x, v.y -= f * r[k].y, v.z -= f * r[k].z;
-                cs.vw[c.al[k]] = v;
-            }
-        }
-    if (c.w0 > 0.f) {
-        v0.x += c.w0 * s.x, v0.y += c.w0 * s.y, v0.z += c.w0 * s.z;
-        cs.vw[c.a0] = v0;
-    }
-}
-
-// S: the cluster's coordinates in LDS brought back to its lengths along the bonds of the reference coordinates rref (relative to the
-// centre), the velocities corrected by the same displacement / (dt / 2) if `vel`.  false: not converged within the cap.
-__device__ __forceinline__ bool cons_shake(const Cluster& c, const V3 (&rref)[CL], RxShared& sh, MdConsShared& cs, float tol2, float ih2, bool vel) {
-    float4 x0 = sh.xs[c.a0];
-    V3 rt[CL], r[CL];
-    float lam[CL], sig[CL];
-#pragma unroll
-    for (int k = 0; k < CL; ++k) {
-        rt[k] = {0.f, 0.f, 0.f}, r[k] = {0.f, 0.f, 0.f}, lam[k] = 0.f, sig[k] = 0.f;
-        if (k < c.L) rt[k] = xyz_of(sh.xs[c.al[k]]) - xyz_of(x0);
-    }
-    V3 s = {0.f, 0.f, 0.f};
-    bool ok = false;
-    for (int it = 0; it <= GRAPPA_MD_CONS_MAX_ITER; ++it) {
-        s = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < CL; ++k)
-            if (k < c.L) s = s + lam[k] * rref[k];
-        ok = true;
-#pragma unroll
-        for (int k = 0; k < CL; ++k)
-            if (k < c.L) {
-                r[k] = rt[k] - (c.wl[k] * lam[k]) * rref[k] - c.w0 * s;
-                sig[k] = dot(r[k], r[k]) - c.d2[k];
-                if (!(fabsf(sig[k]) <= tol2 * c.d2[k])) ok = false;          // (a sigma that is not finite: not converged)
-            }
-        if (ok || it == GRAPPA_MD_CONS_MAX_ITER) break;
-        float J[CL][CL], dl[CL];
-#pragma unroll
-        for (int k = 0; k < CL; ++k)
-#pragma unroll
-            for (int l = 0; l < CL; ++l) {
-                J[k][l] = k == l ? 1.f : 0.f;
-                if (k < c.L && l < c.L) J[k][l] = -2.0f * (c.w0 * dot(r[k], rref[l]) + (k == l ? c.wl[k] * dot(r[k], rref[k]) : 0.f));
-            }
-        solve4(J, sig, dl);
-#pragma unroll
-        for (int k = 0; k < CL; ++k)
-            if (k < c.L) lam[k] -= dl[k];
-    }
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < CL; ++k)
-        if (k < c.L && !(fabsf(lam[k]) <= FLT_MAX)) finite = false;
-    if (!finite) return false;          // nothing to apply
-    if (c.w0 > 0.f) {
-        x0.x += c.w0 * s.x, x0.y += c.w0 * s.y, x0.z += c.w0 * s.z;
-        sh.xs[c.a0] = x0;
-        if (vel) {
-            float4 v = cs.vw[c.a0];
-            v.x += c.w0 * s.x * ih2, v.y += c.w0 * s.y * ih2, v.z += c.w0 * s.z * ih2;
-            cs.vw[c.a0] = v;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < CL; ++k)
-        if (k < c.L && c.wl[k] > 0.f) {          // (a frozen leaf keeps its bits: its bond is held by the centre alone)
-            float4 x = sh.xs[c.al[k]];
-            x.x = x0.x + r[k].x, x.y = x0.y + r[k].y, x.z = x0.z + r[k].z;
-            sh.xs[c.al[k]] = x;
-            if (vel) {
-                float4 v = cs.vw[c.al[k]];
-                const float f = c.wl[k] * lam[k] * ih2;
-                v.x -= f * rref[k].x, v.y -= f * rref[k].y, v.z -= f * rref[k].z;
-                cs.vw[c.al[k]] = v;
-            }
-        }
-    return ok;
-}
-
-// the reference bonds of the coordinates held, then a half drift of the cluster's moving atoms
-__device__ __forceinline__ void cons_drift(const Cluster& c, V3 (&rref)[CL], RxShared& sh, const MdConsShared& cs, float h2) {
-    float4 x0 = sh.xs[c.a0];
-#pragma unroll
-    for (int k = 0; k < CL; ++k) {
-        rref[k] = {0.f, 0.f, 0.f};
-        if (k < c.L) {
-            float4 x = sh.xs[c.al[k]];
-            rref[k] = xyz_of(x) - xyz_of(x0);
-            if (c.wl[k] > 0.f) {
-                const float4 v = cs.vw[c.al[k]];
-                x.x += h2 * v.x, x.y += h2 * v.y, x.z += h2 * v.z;
-                sh.xs[c.al[k]] = x;
-            }
-        }
-    }
-    if (c.w0 > 0.f) {
-        const float4 v = cs.vw[c.a0];
-        x0.x += h2 * v.x, x0.y += h2 * v.y, x0.z += h2 * v.z;
-        sh.xs[c.a0] = x0;
-    }
-}
+};
 
 // v -= (dt / 2) ACC w g on one atom (a frozen atom is not touched)
 __device__ __forceinline__ void cons_kick(MdConsShared& cs, int il, float hk) {
@@ -329,12 +187,7 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_cons_kernel(MdConsArgs a) {
         for (int k = 1; k <= CL; ++k)
             if (at[k] != -1) {
                 const float wk = cs.vw[at[k]].w;
-                if (cl.w0 + wk > 0.f) {
-#pragma unroll
-                    for (int j = 0; j < CL; ++j)          // (written out: cl.L is not a compile-time index)
-                        if (j == cl.L) cl.al[j] = at[k], cl.wl[j] = wk, cl.d2[j] = dd[k - 1] * dd[k - 1];
-                    ++cl.L;
-                }
+                cons_add_leaf(cl, at[k], wk, dd[k - 1]);
             }
     }
     const bool has_cl = cl.L > 0;
@@ -345,17 +198,14 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_cons_kernel(MdConsArgs a) {
         free_atom[k] = il < n && cs.cl[il] < 0 && cs.vw[il].w > 0.f;
     }
     V3 rref[CL];
+    LdsCluster st = {cl, sh, cs};
     bool fail = false;
     if (has_cl) {
         if (a.constrain_start) {
-#pragma unroll
-            for (int k = 0; k < CL; ++k) {
-                rref[k] = {0.f, 0.f, 0.f};
-                if (k < cl.L) rref[k] = xyz_of(sh.xs[cl.al[k]]) - xyz_of(sh.xs[cl.a0]);
-            }
-            if (!cons_shake(cl, rref, sh, cs, a.tol2, a.ih2, false)) fail = true;
+            cons_bonds(cl, rref, st);
+            if (!cons_shake(cl, rref, st, a.tol2, a.ih2, false)) fail = true;
         }
-        if (a.constrain_start || !a.vel_in) cons_project(cl, sh, cs);
+        if (a.constrain_start || !a.vel_in) cons_project(cl, st);
     }
     __syncthreads();
 
@@ -384,7 +234,7 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_cons_kernel(MdConsArgs a) {
 #pragma unroll
                 for (int k = 0; k < CL; ++k)
                     if (k < cl.L) cons_kick(cs, cl.al[k], a.hk);
-                cons_project(cl, sh, cs);
+                cons_project(cl, st);
             }
             if (a.save_every > 0 && ++since == a.save_every) {
                 since = 0;
@@ -457,20 +307,20 @@ __global__ __launch_bounds__(RX_NT) void md_langevin_cons_kernel(MdConsArgs a) {
 #pragma unroll
             for (int k = 0; k < CL; ++k)
                 if (k < cl.L) cons_kick(cs, cl.al[k], a.hk);
-            cons_project(cl, sh, cs);
-            cons_drift(cl, rref, sh, cs, a.h2);
-            if (!cons_shake(cl, rref, sh, cs, a.tol2, a.ih2, true)) fail = true;
-            cons_project(cl, sh, cs);
+            cons_project(cl, st);
+            cons_drift(cl, rref, st, a.h2);
+            if (!cons_shake(cl, rref, st, a.tol2, a.ih2, true)) fail = true;
+            cons_project(cl, st);
             if (a.thermostat) {
                 cons_noise(a, cs, cl.a0, key, (unsigned)c, step);
 #pragma unroll
                 for (int k = 0; k < CL; ++k)
                     if (k < cl.L) cons_noise(a, cs, cl.al[k], key, (unsigned)c, step);
-                cons_project(cl, sh, cs);
+                cons_project(cl, st);
             }
-            cons_drift(cl, rref, sh, cs, a.h2);
-            if (!cons_shake(cl, rref, sh, cs, a.tol2, a.ih2, true)) fail = true;
-            cons_project(cl, sh, cs);
+            cons_drift(cl, rref, st, a.h2);
+            if (!cons_shake(cl, rref, st, a.tol2, a.ih2, true)) fail = true;
+            cons_project(cl, st);
         }
         ++steps;
         __syncthreads();

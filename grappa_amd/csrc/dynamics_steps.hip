@@ -23,6 +23,9 @@
 //            csrc/nb_cut.h; the move launch's item writes the box of its own (block, conformations) after moving -- the box's only
 //            writer -- and the force launch reads all boxes across the launch boundary: a step stays two launches, init gains one (boxes
 //            and exception ranges).  Energies by grappa_nonbonded_fwd_cut_f32 at the held coordinates.
+//   constraints: grappa_md_steps_*_cons_f32 (cons == NULL or K == 0: the calls without).  X-H star clusters under g-BAOAB with P and S of
+//            csrc/md_cons.h; a cluster is integrated by the thread of its centre, and a step becomes move, boxes (with a cutoff),
+//            force, close: the section "X-H constraints" below states the decomposition, the launches and the hazards.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -30,6 +33,7 @@
 
 #include "common.h"
 #include "desc_check.h"
+#include "md_cons.h"
 #include "md_noise.h"
 #include "rs_force.h"
 
@@ -48,11 +52,13 @@ struct MsWs {
     int2* er;
     char* nbcut;                         // with a cutoff, frames and finish: the workspace of grappa_nonbonded_fwd_cut_f32
     size_t nbcut_bytes;
+    int* claim;                          // with constraints: per atom the cluster that holds it, -1: none [N]
+    int* cfail;                          // with constraints: a cluster owned by the block did not converge [n_blocks][C]
     size_t total;
 };
 
-// (the words of a cutoff lie behind the others: without one the layout is the one it was)
-MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false) {
+// (the words of a cutoff lie behind the others, those of constraints behind both: without either the layout is the one it was)
+MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false, bool cons = false) {
     MsWs w;
     WsCarve k{base};
     const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
@@ -68,6 +74,8 @@ MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false) 
         w.nbcut_bytes = grappa_nonbonded_cut_workspace_bytes(C, n_blocks);
         w.nbcut = k.take<char>(w.nbcut_bytes);
     }
+    w.claim = nullptr, w.cfail = nullptr;
+    if (cons) w.claim = k.take<int>((size_t)N), w.cfail = k.take<int>(kc);
     w.total = k.off;
     return w;
 }
@@ -131,18 +139,10 @@ struct MsMoveArgs {
     unsigned step;           // the global index of the step: the random stream's position
 };
 
-// the thread's (atom, conformation) of the item; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
+// B, A, O, A on atom i of conformation c (a frozen atom is not touched); CUT: the coordinates it leaves -> bxl[0..3)
 template <bool CUT>
-__device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& r, int k0, const int* stop, float* bxl) {
-    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
-    const int cl = t / ni, il = t - cl * ni;
-    const int i = r.i0 + il, c = r.c0 + cl;
-    const size_t item = (size_t)r.mol * C + c;
-    const bool writer = r.blk == k0 && il == 0;      // the molecule's first block: the one writer of the item's status and steps
-    if (stop[cl]) {                                  // a non-finite gradient: the item keeps the x and v it holds
-        if (writer) a.status[item] = 2;
-        return;
-    }
+__device__ __forceinline__ void ms_move_atom(const MsMoveArgs& a, const RsItem& r, int i, int c, float* bxl) {
+    const int C = a.q.C;
     const float m = a.mass[i];
     if (m > 0.f) {                                   // (a frozen atom is not touched)
         const size_t off = ((size_t)i * C + c) * 3;
@@ -162,7 +162,43 @@ __device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& 
         const size_t off = ((size_t)i * C + c) * 3;
         bxl[0] = a.x[off], bxl[1] = a.x[off + 1], bxl[2] = a.x[off + 2];
     }
+}
+
+// the thread's (atom, conformation) of the item; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
+template <bool CUT>
+__device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& r, int k0, const int* stop, float* bxl) {
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    const int cl = t / ni, il = t - cl * ni;
+    const int i = r.i0 + il, c = r.c0 + cl;
+    const size_t item = (size_t)r.mol * C + c;
+    const bool writer = r.blk == k0 && il == 0;      // the molecule's first block: the one writer of the item's status and steps
+    if (stop[cl]) {                                  // a non-finite gradient: the item keeps the x and v it holds
+        if (writer) a.status[item] = 2;
+        return;
+    }
+    ms_move_atom<CUT>(a, r, i, c, bxl);
     if (writer) a.steps[item] += 1;
+}
+
+// Has a block of the molecule flagged the conformation?  -> stop[0 .. nc), then a barrier.  Every workgroup of the molecule forms the same
+// OR from the same words, which the force launch before this one wrote: wavefront w takes the conformations w, w + 4, .., its lanes the
+// blocks.  BITS: the OR of the words themselves (with constraints a word holds more than one flag), else 1.
+template <bool BITS>
+__device__ __forceinline__ void ms_stop_flags(const int* bad, const RsItem& r, int C, int k0, int k1, int* stop) {
+    const int t = threadIdx.x, wave = t / GRAPPA_WAVE, lane = t & (GRAPPA_WAVE - 1);
+    for (int cc = wave; cc < r.nc; cc += MS_NW) {
+        int f = 0;
+        for (int k = k0 + lane; k < k1; k += GRAPPA_WAVE) f |= bad[(size_t)k * C + r.c0 + cc];
+        if constexpr (BITS) {
+            int code = 0;
+            for (int bit = 1; bit <= 4; bit <<= 1) code |= __builtin_amdgcn_ballot_w64((f & bit) != 0) != 0 ? bit : 0;
+            if (lane == 0) stop[cc] = code;
+        } else {
+            const bool any = __builtin_amdgcn_ballot_w64(f != 0) != 0;
+            if (lane == 0) stop[cc] = any ? 1 : 0;
+        }
+    }
+    __syncthreads();
 }
 
 // CUT: the item also writes the box of its own (block, conformations) at the coordinates it leaves (csrc/nb_cut.h): it is the box's only
@@ -173,17 +209,8 @@ __device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
     RsItem r;
     if (!rs_item(a.q, r)) return;
     const int C = a.q.C, t = threadIdx.x, ni = r.ni;
-    // has a block of the molecule flagged the conformation?  Every workgroup of the molecule forms the same OR from the same words, which
-    // the force launch before this one wrote: wavefront w takes the conformations w, w + 4, .., its lanes the blocks
     const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
-    const int wave = t / GRAPPA_WAVE, lane = t & (GRAPPA_WAVE - 1);
-    for (int cc = wave; cc < r.nc; cc += MS_NW) {
-        int f = 0;
-        for (int k = k0 + lane; k < k1; k += GRAPPA_WAVE) f |= a.bad[(size_t)k * C + r.c0 + cc];
-        const bool any = __builtin_amdgcn_ballot_w64(f != 0) != 0;
-        if (lane == 0) stop[cc] = any ? 1 : 0;
-    }
-    __syncthreads();
+    ms_stop_flags<false>(a.bad, r, C, k0, k1, stop);
     if constexpr (CUT) {
         __shared__ float bx[NB_NT * 3];
         if (t < ni * r.nc) ms_move_lane<true>(a, r, k0, stop, bx + 3 * t);
@@ -207,8 +234,10 @@ struct MsForceArgs {
     float* frame_xyz;        // the frame this step writes, or NULL
 };
 
-template <class Cut>
-__device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& cut) {
+// CONS (with constraints): the block's flag word also takes, as bit 1, the constraint-failure word that the launch before this one left for
+// the block (cfail), and the kinetic partial is left to the close launch, which follows the closing P
+template <bool CONS = false, class Cut>
+__device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& cut, const int* cfail = nullptr) {
     __shared__ RsShared sh;
     rs_force(a.f, sh, cut, [&](const RsItem& r, const RsLane& w, V3 gi) {
         const int C = a.f.q.C, ni = r.ni;
@@ -243,8 +272,12 @@ __device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& c
                 fb = fmaxf(fb, sh.red[1][o]);
             }
             const size_t o = (size_t)r.blk * C + w.c;
-            a.kpart[o] = sk;
-            a.bad[o] = fb != 0.f ? 1 : 0;
+            if constexpr (CONS) {
+                a.bad[o] = (fb != 0.f ? 1 : 0) | (cfail[o] != 0 ? 2 : 0);
+            } else {
+                a.kpart[o] = sk;
+                a.bad[o] = fb != 0.f ? 1 : 0;
+            }
         }
     });
 }
@@ -254,6 +287,350 @@ __global__ __launch_bounds__(NB_NT) void ms_force_kernel(MsForceArgs a) { ms_for
 __global__ __launch_bounds__(NB_NT) void ms_force_cut_kernel(MsForceArgs a, NbCutDev c) {
     __shared__ unsigned char near[NB_NT];
     ms_force_body(a, NbCut{c, near});
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_force_cons_kernel(MsForceArgs a, const int* cfail) { ms_force_body<true>(a, NbNoCut{}, cfail); }
+
+__global__ __launch_bounds__(NB_NT) void ms_force_cons_cut_kernel(MsForceArgs a, NbCutDev c, const int* cfail) {
+    __shared__ unsigned char near[NB_NT];
+    ms_force_body<true>(a, NbCut{c, near}, cfail);
+}
+
+// ------------------------------------------------------------------------------------------------ X-H constraints (grappa_md_steps_*_cons_f32)
+// g-BAOAB with the star clusters, P and S of csrc/md_cons.h, stated in include/grappa_hip.h at grappa_md_langevin_cons_f32.
+//   owner  : a cluster is integrated, all its atoms together, by the thread of its CENTRE -- the lane that the centre atom has in the
+//            work item of its block -- with the cluster's coordinates and velocities in registers; its leaves may lie in any block of
+//            the molecule.  A clustered atom is skipped by its ordinary owner; a free atom moves exactly as in ms_move_kernel.
+//   claim  : one word per atom, written during init: the cluster that holds the atom, -1 for a free atom.  It vets "no atom in two
+//            clusters" across workgroups (a launch stores, the next reads back) and then IS the ownership list: lane il of a block owns
+//            the cluster claim[i0 + il] if that atom is its centre, so a block's clusters are walked in ascending order of their centres
+//            with no list to build.
+//   step   : move (clusters: B P | A S P | O P | A S P, free atoms: B A O A; the block's constraint-failure word, fresh each launch),
+//            boxes (with a cutoff: rs_box_kernel, since a block's atoms may be moved by a sibling), force (the kick of every atom by
+//            its owner; the block's flag word takes the failure word as bit 1), close (clusters: P; the block's kinetic partial):
+//            three launches, four under a cutoff.
+//   hazards: as above, every word has one writer per launch and no workgroup reads what a sibling writes in the same launch.  x and v of
+//            a clustered atom are read and written by the centre's thread alone in move and close, by the atom's owner alone in
+//            force; cfail is written by move (its block) and read by force (its block); the flags are written by force and read by
+//            move; status and steps are written and read by the first block's move alone, and read by the later launches of the step.
+//   flags  : a block's word: bit 0 a non-finite gradient, bit 1 a constraint that did not converge (status 4), bit 2 the item's tables
+//            were refused (status 5; set once by the vet launch in every block of the molecule).  All are sticky.
+struct MscDev {
+    const int *molptr, *atoms;           // the caller's tables: [B+1], [K, CL+1]
+    const float* d;                      // [K, CL]
+    int K;
+    int *claim, *cfail;                  // the workspace's words
+    float tol2, ih2;                     // 2 tolerance, 2 / dt
+};
+
+// a cluster's state in registers as the slots of csrc/md_cons.h
+struct RegCluster {
+    V3 xs[CL + 1], vs[CL + 1];
+    __device__ __forceinline__ V3 x(int s) const { return xs[s]; }
+    __device__ __forceinline__ V3 v(int s) const { return vs[s]; }
+    __device__ __forceinline__ void set_x(int s, V3 p) { xs[s] = p; }
+    __device__ __forceinline__ void set_v(int s, V3 p) { vs[s] = p; }
+};
+
+// the checks a cluster passes by itself in a molecule of n atoms -> its atoms as the table holds them; false: refused
+__device__ __forceinline__ bool msc_cluster_ok(const MscDev& cn, int k, int n, int (&at)[CL + 1]) {
+    const int* p = cn.atoms + (size_t)k * (CL + 1);
+    const float* q = cn.d + (size_t)k * CL;
+#pragma unroll
+    for (int j = 0; j <= CL; ++j) at[j] = p[j];
+    bool ok = (unsigned)at[0] < (unsigned)n, leaf = false;
+#pragma unroll
+    for (int j = 1; j <= CL; ++j)
+        if (at[j] != -1) {
+            leaf = true;
+            const float dj = q[j - 1];
+            if ((unsigned)at[j] >= (unsigned)n || !(dj > 0.f && dj <= FLT_MAX)) ok = false;
+#pragma unroll
+            for (int l = 0; l < j; ++l)
+                if (at[l] == at[j]) ok = false;
+        }
+    return ok && leaf;          // a cluster has at least one leaf
+}
+
+// is atom i (of the item's molecule) the centre of a cluster?  -> that cluster with GLOBAL atom indices and its leaves packed (a leaf
+// whose two ends are frozen is no constraint); false: a free atom or a leaf.  The tables were vetted by init; an index that is out of
+// range all the same (other tables than init saw) is not followed.
+__device__ __forceinline__ bool msc_cluster_of(const MscDev& cn, const RsItem& r, int i, const float* __restrict__ mass, Cluster& cl) {
+    const int k = cn.claim[i];
+    if ((unsigned)k >= (unsigned)cn.K) return false;
+    const int* p = cn.atoms + (size_t)k * (CL + 1);
+    if (p[0] != i - r.m0) return false;
+    const float m = mass[i];
+    cl.L = 0, cl.a0 = i, cl.w0 = m > 0.f ? 1.0f / m : 0.f;
+#pragma unroll
+    for (int j = 0; j < CL; ++j) cl.al[j] = i, cl.wl[j] = 0.f, cl.d2[j] = 1.f;
+#pragma unroll
+    for (int j = 1; j <= CL; ++j) {
+        const int at = p[j];
+        if ((unsigned)at < (unsigned)(r.m1 - r.m0)) {
+            const float mk = mass[r.m0 + at];
+            cons_add_leaf(cl, r.m0 + at, mk > 0.f ? 1.0f / mk : 0.f, cn.d[(size_t)k * CL + j - 1]);
+        }
+    }
+    return true;
+}
+
+__device__ __forceinline__ V3 msc_ld3(const float* p, size_t off) { return {p[off], p[off + 1], p[off + 2]}; }
+__device__ __forceinline__ void msc_st3(float* p, size_t off, V3 a) { p[off] = a.x, p[off + 1] = a.y, p[off + 2] = a.z; }
+__device__ __forceinline__ int msc_slot_atom(const Cluster& cl, int s) { return s == 0 ? cl.a0 : cl.al[s - 1]; }
+__device__ __forceinline__ float msc_slot_w(const Cluster& cl, int s) { return s == 0 ? cl.w0 : cl.wl[s - 1]; }
+
+// the cluster's coordinates and velocities of conformation c: global memory -> registers, and back for its moving atoms
+__device__ __forceinline__ void msc_load(const Cluster& cl, int C, int c, const float* x, const float* v, RegCluster& st) {
+#pragma unroll
+    for (int s = 0; s <= CL; ++s) {
+        st.xs[s] = {0.f, 0.f, 0.f}, st.vs[s] = {0.f, 0.f, 0.f};
+        if (s <= cl.L) {
+            const size_t off = ((size_t)msc_slot_atom(cl, s) * C + c) * 3;
+            st.xs[s] = msc_ld3(x, off), st.vs[s] = msc_ld3(v, off);
+        }
+    }
+}
+__device__ __forceinline__ void msc_store(const Cluster& cl, int C, int c, float* x, float* v, const RegCluster& st) {
+#pragma unroll
+    for (int s = 0; s <= CL; ++s)
+        if (s <= cl.L && msc_slot_w(cl, s) > 0.f) {          // (a frozen atom keeps its bits)
+            const size_t off = ((size_t)msc_slot_atom(cl, s) * C + c) * 3;
+            if (x) msc_st3(x, off, st.xs[s]);
+            msc_st3(v, off, st.vs[s]);
+        }
+}
+
+// ---- init: the claim words and the failure words cleared
+__global__ __launch_bounds__(256) void msc_clear_kernel(int N, size_t kc, int* claim, int* cfail) {
+    const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (u < (size_t)N) claim[u] = -1;
+    if (u < kc) cfail[u] = 0;
+}
+
+// ---- init: every cluster that passes its own checks stores its index to its atoms' claim words (plain stores; the item of the
+// molecule's first block and first conformations walks the molecule's clusters)
+__global__ __launch_bounds__(NB_NT) void msc_claim_kernel(RsGeom q, MscDev cn) {
+    RsItem r;
+    if (!rs_item(q, r) || r.blk != nb_clamp(q.blk_ptr[r.mol], q.n_blocks) || r.c0 != 0) return;
+    const int n = r.m1 - r.m0, k0 = nb_clamp(cn.molptr[r.mol], cn.K), k1 = nb_clamp(cn.molptr[r.mol + 1], cn.K);
+    for (int k = k0 + (int)threadIdx.x; k < k1; k += NB_NT) {
+        int at[CL + 1];
+        if (!msc_cluster_ok(cn, k, n, at)) continue;
+#pragma unroll
+        for (int j = 0; j <= CL; ++j)
+            if (at[j] != -1) cn.claim[r.m0 + at[j]] = k;
+    }
+}
+
+// ---- init: every cluster reads its claims back: of two clusters that hold one atom at least one finds the other's index.  A molecule
+// with a refused cluster: status 5 and bit 2 in every block's flag word, for the conformations of this item (the items of the molecule's
+// first block, one per chunk of conformations, each decide the same from the same words).
+__global__ __launch_bounds__(NB_NT) void msc_vet_kernel(RsGeom q, MscDev cn, int* status, int* bad) {
+    RsItem r;
+    if (!rs_item(q, r)) return;
+    const int b0 = nb_clamp(q.blk_ptr[r.mol], q.n_blocks), b1 = nb_clamp(q.blk_ptr[r.mol + 1], q.n_blocks);
+    if (r.blk != b0) return;
+    const int n = r.m1 - r.m0, k0 = nb_clamp(cn.molptr[r.mol], cn.K), k1 = nb_clamp(cn.molptr[r.mol + 1], cn.K);
+    int invalid = 0;
+    for (int k = k0 + (int)threadIdx.x; k < k1; k += NB_NT) {
+        int at[CL + 1];
+        if (!msc_cluster_ok(cn, k, n, at)) {
+            invalid = 1;
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j <= CL; ++j)
+            if (at[j] != -1 && cn.claim[r.m0 + at[j]] != k) invalid = 1;          // another cluster claimed the atom too
+    }
+    if (!__syncthreads_or(invalid)) return;
+    const int C = q.C, t = threadIdx.x;
+    if (t < r.nc) status[(size_t)r.mol * C + r.c0 + t] = 5;
+    for (int u = t; u < (b1 - b0) * r.nc; u += NB_NT) bad[(size_t)(b0 + u / r.nc) * C + r.c0 + u % r.nc] = 4;
+}
+
+// the block's constraint-failure word of every conformation of the item: the OR over the block's cluster threads (fail: this thread's)
+__device__ __forceinline__ void msc_write_fail(const RsItem& r, int C, bool lane, bool fail, const int* live, int* cfail) {
+    __shared__ int cf[NB_CW];
+    const int t = threadIdx.x;
+    if (t < NB_CW) cf[t] = 0;
+    __syncthreads();
+    if (lane && fail) cf[t / r.ni] = 1;
+    __syncthreads();
+    if (t < r.nc && live[t]) cfail[(size_t)r.blk * C + r.c0 + t] = cf[t];
+}
+
+// ---- init: the start's S and P (after the init kernel, the claims and the vet; before the boxes and the first force)
+struct MscStartArgs {
+    RsGeom q;
+    float *x, *v;
+    const float* mass;
+    const int* status;
+    MscDev cn;
+    int constrain_start;
+};
+
+__global__ __launch_bounds__(NB_NT) void msc_start_kernel(MscStartArgs a) {
+    __shared__ int run[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x;
+    if (!rs_running(r, C, a.status, run)) return;      // (a refused item: nothing of it is touched)
+    const bool lane = t < r.ni * r.nc;
+    bool fail = false;
+    Cluster cl;
+    if (lane && run[t / r.ni] && msc_cluster_of(a.cn, r, r.i0 + t % r.ni, a.mass, cl) && cl.L > 0) {
+        const int c = r.c0 + t / r.ni;
+        RegCluster st;
+        msc_load(cl, C, c, a.x, a.v, st);
+        if (a.constrain_start) {
+            V3 rref[CL];
+            cons_bonds(cl, rref, st);
+            fail = !cons_shake(cl, rref, st, a.cn.tol2, a.cn.ih2, false);
+        }
+        cons_project(cl, st);
+        msc_store(cl, C, c, a.constrain_start ? a.x : nullptr, a.v, st);
+    }
+    msc_write_fail(r, C, lane, fail, run, a.cn.cfail);
+}
+
+// ---- move
+// the thread's (atom, conformation) of the item: a free atom as ms_move_lane moves it, a centre its whole cluster, a leaf nothing;
+// true: an S of the thread's cluster did not converge
+__device__ __forceinline__ bool msc_move_lane(const MsMoveArgs& a, const MscDev& cn, const RsItem& r, int k0, const int* stop) {
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    const int cc = t / ni, il = t - cc * ni;
+    const int i = r.i0 + il, c = r.c0 + cc;
+    const size_t item = (size_t)r.mol * C + c;
+    const bool writer = r.blk == k0 && il == 0;      // the molecule's first block: the one writer (and reader) of the item's status and steps
+    if (stop[cc]) {
+        // a flag the force launch left: the item keeps the x and v it holds.  A constraint failure (it wins over a non-finite gradient)
+        // also takes back the count of the step that failed; the start's S failing leaves 0.  Once: the status is then final.
+        if (writer && a.status[item] == RS_RUNNING) {
+            const bool cfail = (stop[cc] & 2) != 0;
+            a.status[item] = cfail ? 4 : 2;
+            if (cfail && a.steps[item] > 0) a.steps[item] -= 1;
+        }
+        return false;
+    }
+    if (writer) a.steps[item] += 1;
+    if (cn.claim[i] < 0) {
+        ms_move_atom<false>(a, r, i, c, nullptr);
+        return false;
+    }
+    Cluster cl;
+    if (!msc_cluster_of(cn, r, i, a.mass, cl) || cl.L == 0) return false;
+    RegCluster st;
+    msc_load(cl, C, c, a.x, a.v, st);
+    const unsigned long long key = a.mol_key[r.mol];
+    // B P
+#pragma unroll
+    for (int s = 0; s <= CL; ++s)
+        if (s <= cl.L && msc_slot_w(cl, s) > 0.f)
+            st.vs[s] = st.vs[s] - (a.k.hk * msc_slot_w(cl, s)) * msc_ld3(a.g, ((size_t)msc_slot_atom(cl, s) * C + c) * 3);
+    cons_project(cl, st);
+    // A S P
+    V3 rref[CL];
+    bool fail = false;
+    cons_drift(cl, rref, st, a.k.h2);
+    if (!cons_shake(cl, rref, st, cn.tol2, cn.ih2, true)) fail = true;
+    cons_project(cl, st);
+    // O P
+    if (a.k.thermostat) {
+#pragma unroll
+        for (int s = 0; s <= CL; ++s)
+            if (s <= cl.L && msc_slot_w(cl, s) > 0.f) {
+                const float w = msc_slot_w(cl, s);
+                st.vs[s] = a.k.c1 * st.vs[s] + (a.k.c2 * sqrtf(a.k.kt * w)) * md_normal3(key, (unsigned)(msc_slot_atom(cl, s) - r.m0), (unsigned)c, a.step, 0u);
+            }
+        cons_project(cl, st);
+    }
+    // A S P
+    cons_drift(cl, rref, st, a.k.h2);
+    if (!cons_shake(cl, rref, st, cn.tol2, cn.ih2, true)) fail = true;
+    cons_project(cl, st);
+    msc_store(cl, C, c, a.x, a.v, st);
+    return fail;
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_move_cons_kernel(MsMoveArgs a, MscDev cn) {
+    __shared__ int stop[NB_CW];
+    __shared__ int live[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x;
+    const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
+    ms_stop_flags<true>(a.bad, r, C, k0, k1, stop);
+    const bool lane = t < r.ni * r.nc;
+    const bool fail = lane && msc_move_lane(a, cn, r, k0, stop);
+    if (t < r.nc) live[t] = stop[t] == 0;          // (a stopped conformation keeps its failure word, as it keeps its x)
+    msc_write_fail(r, C, lane, fail, live, cn.cfail);
+}
+
+// ---- close: the closing P of the block's clusters, then the block's kinetic partial: over the block's atoms in ascending order, in
+// double, where a free atom gives m v^2, a centre the sum of its cluster's moving atoms (centre, then leaves in table order) and a leaf
+// nothing.  project == 0 (init): the partial alone.
+struct MscCloseArgs {
+    RsGeom q;
+    const float* x;
+    float* v;
+    const float* mass;
+    const int* status;
+    MscDev cn;
+    double* kpart;
+    int project;
+};
+
+__global__ __launch_bounds__(NB_NT) void msc_close_kernel(MscCloseArgs a) {
+    __shared__ int run[NB_CW];
+    __shared__ double kin[NB_NT];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x, ni = r.ni;
+    if (!rs_running(r, C, a.status, run)) return;
+    const int cc = t / ni, il = t - cc * ni;
+    const bool lane = t < ni * r.nc && run[cc] != 0;
+    double mv2 = 0.0;
+    if (lane) {
+        const int i = r.i0 + il, c = r.c0 + cc;
+        Cluster cl;
+        if (a.cn.claim[i] < 0) {
+            const float m = a.mass[i];
+            if (m > 0.f) {
+                const V3 vi = msc_ld3(a.v, ((size_t)i * C + c) * 3);
+                mv2 = (double)(m * dot(vi, vi));
+            }
+        } else if (msc_cluster_of(a.cn, r, i, a.mass, cl)) {
+            RegCluster st;
+            msc_load(cl, C, c, a.x, a.v, st);
+            if (a.project && cl.L > 0) {
+                cons_project(cl, st);
+                msc_store(cl, C, c, nullptr, a.v, st);
+            }
+#pragma unroll
+            for (int s = 0; s <= CL; ++s)
+                if (s <= cl.L && msc_slot_w(cl, s) > 0.f) mv2 += (double)(a.mass[msc_slot_atom(cl, s)] * dot(st.vs[s], st.vs[s]));
+        }
+    }
+    kin[t] = mv2;
+    __syncthreads();
+    if (lane && il == 0) {
+        double sk = 0.0;
+        for (int k = 0; k < ni; ++k) sk += kin[cc * ni + k];
+        a.kpart[(size_t)r.blk * C + r.c0 + cc] = sk;
+    }
+}
+
+// ---- finish: x and v of every item but a refused one -> xyz_out, vel_out (a thread per (atom, conformation) of the item)
+__global__ __launch_bounds__(NB_NT) void msc_copy_kernel(RsGeom q, const float* x, const float* v, const int* status, float* xyz_out, float* vel_out) {
+    RsItem r;
+    if (!rs_item(q, r)) return;
+    const int t = threadIdx.x;
+    if (t >= r.ni * r.nc) return;
+    const int cc = t / r.ni, i = r.i0 + t % r.ni, c = r.c0 + cc;
+    if (status[(size_t)r.mol * q.C + c] == 5) return;
+    const size_t off = ((size_t)i * q.C + c) * 3;
+    msc_st3(xyz_out, off, msc_ld3(x, off)), msc_st3(vel_out, off, msc_ld3(v, off));
 }
 
 // ------------------------------------------------------------------------------------------------ energies and outputs
@@ -269,9 +646,12 @@ struct MsOutArgs {
     int *steps, *status;
 };
 
+// CONS (with constraints): x and v are copied per item by msc_copy_kernel, an item whose tables were refused (5) gets its status and
+// nothing else, and a set constraint flag (bit 1 of a block's word) ends a running item with 4 and takes the failing step back
+template <bool CONS>
 __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a.final && gid < (size_t)a.N * a.C * 3) {
+    if (!CONS && a.final && gid < (size_t)a.N * a.C * 3) {
         a.xyz_out[gid] = a.x[gid];
         a.vel_out[gid] = a.v[gid];
     }
@@ -281,6 +661,10 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
     if (nb_clamp(a.atom_molptr[b + 1], a.N) <= nb_clamp(a.atom_molptr[b], a.N)) return;      // a molecule without atoms writes nothing
     const int st = a.status_ws[gid];
     if (!a.final && st != RS_RUNNING) return;       // a stopped item's later frames are not written
+    if (CONS && st == 5) {
+        a.status[gid] = 5;
+        return;
+    }
     // the kinetic partials and the flags of the item's blocks, in ascending block order
     const int k0 = nb_clamp(a.blk_ptr[b], a.n_blocks), k1 = nb_clamp(a.blk_ptr[b + 1], a.n_blocks);
     double ks = 0.0;
@@ -295,7 +679,12 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
         a.epot[gid] = (float)tot;
     }
     if (a.ekin) a.ekin[gid] = (float)((0.5 / MD_ACC) * ks);
-    if (a.final) {
+    if (a.final && CONS) {
+        const bool failed = st == RS_RUNNING && (flagged & 2) != 0;      // (the move launch that would have taken the step back never came)
+        const int n = a.steps_ws[gid];
+        a.steps[gid] = failed && n > 0 ? n - 1 : n;
+        a.status[gid] = st == RS_RUNNING ? ((flagged & 2) ? 4 : (flagged ? 2 : 0)) : st;
+    } else if (a.final) {
         a.steps[gid] = a.steps_ws[gid];
         a.status[gid] = st == RS_RUNNING ? (flagged ? 2 : 0) : st;      // (the gradient that closed the last step is tested here)
     }
@@ -306,7 +695,7 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
 
 // (a cutoff as the three calls carry it: RsCut / rs_cut_make of csrc/rs_force.h; c == NULL: none)
 void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const MsWs& w,
-                     const float* mass, float hk, float* frame_xyz, int n_items) {
+                     const float* mass, float hk, float* frame_xyz, int n_items, const int* cfail = nullptr) {
     MsForceArgs f;
     f.f = rs_force_in(mm, nb, q, w.x, w.status);
     f.v = w.v, f.g = w.g, f.mass = mass, f.bad = w.bad, f.kpart = w.kpart;
@@ -314,7 +703,10 @@ void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_d
     if (c) {
         NbCutDev d = c->dev;
         d.box = w.box, d.er = w.er;
-        GRAPPA_LAUNCH(ms_force_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d);
+        if (cfail) GRAPPA_LAUNCH(ms_force_cons_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d, cfail);
+        else GRAPPA_LAUNCH(ms_force_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d);
+    } else if (cfail) {
+        GRAPPA_LAUNCH(ms_force_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, cfail);
     } else {
         GRAPPA_LAUNCH(ms_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
     }
@@ -336,13 +728,34 @@ MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const 
     return a;
 }
 
-// the three calls, with and without a cutoff (c == NULL: none)
+// constraints as the three calls carry them: the caller's tables (cons->K > 0, checked) and the step's constants; the workspace's words
+// are set once it is laid out
+MscDev msc_dev(const grappa_md_cons* cons, const grappa_md_opts* o) {
+    MscDev d = {};
+    d.molptr = cons->cluster_molptr, d.atoms = cons->cluster_atoms, d.d = cons->cluster_d, d.K = cons->K;
+    d.tol2 = 2.0f * cons->tolerance;
+    if (o) d.ih2 = 1.0f / md_consts(o).h2;
+    return d;
+}
+
+void ms_launch_boxes(hipStream_t st, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w, int n_items) {
+    const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
+    GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+}
+
+void msc_launch_close(hipStream_t st, const RsGeom& q, const MsWs& w, const MscDev& cn, const float* mass, int project, int n_items) {
+    const MscCloseArgs a = {q, w.x, w.v, mass, w.status, cn, w.kpart, project};
+    GRAPPA_LAUNCH(msc_close_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
+}
+
+// the three calls, with and without a cutoff (c == NULL: none) and constraints (cons == NULL: none, the launches as they were)
 int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
-            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+            const grappa_md_cons* cons = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
@@ -356,17 +769,33 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     n = n > kc ? n : kc;
     GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
-    if (c && n_items > 0) {
-        const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
-        GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+    if (cons) {
+        // the tables vetted (clear, claim, read back), the start's S and P, then boxes, force and the kinetic partials: 6 to 8 launches
+        MscDev cn = msc_dev(cons, o);
+        cn.claim = w.claim, cn.cfail = w.cfail;
+        const size_t nk = (size_t)mm->N > kc ? (size_t)mm->N : kc;
+        GRAPPA_LAUNCH(msc_clear_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, mm->N, kc, w.claim, w.cfail);
+        if (n_items > 0) {
+            GRAPPA_LAUNCH(msc_claim_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn);
+            GRAPPA_LAUNCH(msc_vet_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn, w.status, w.bad);
+            if (cons->constrain_start || !vel_in) {
+                const MscStartArgs sa = {q, w.x, w.v, mass, w.status, cn, cons->constrain_start != 0};
+                GRAPPA_LAUNCH(msc_start_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, sa);
+            }
+            if (c) ms_launch_boxes(st, nb, q, w, n_items);
+            ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail);
+            msc_launch_close(st, q, w, cn, mass, 0, n_items);
+        }
+        return grappa_launch_status();
     }
+    if (c && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
     if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
     return grappa_launch_status();
 }
 
 int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
-           float* frames_xyz, float* frames_epot, float* frames_ekin) {
+           float* frames_xyz, float* frames_epot, float* frames_ekin, const grappa_md_cons* cons = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
@@ -374,11 +803,13 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const MdConsts k = md_consts(o);
+    MscDev cn = {};
+    if (cons) cn = msc_dev(cons, o), cn.claim = w.claim, cn.cfail = w.cfail;
     MsMoveArgs mv;
     mv.q = q, mv.x = w.x, mv.v = w.v, mv.g = w.g, mv.mass = mass, mv.mol_key = mol_key;
     mv.bad = w.bad, mv.status = w.status, mv.steps = w.steps, mv.k = k;
@@ -390,9 +821,17 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
         const size_t f = due ? (size_t)(done / o->save_every - 1 - frame0) : 0;
         if (n_items > 0) {
             mv.step = o->first_step + (unsigned)(step0 + s);
-            if (c) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
-            else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-            ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, due && frames_xyz ? frames_xyz + f * n3 : nullptr, n_items);
+            float* fx = due && frames_xyz ? frames_xyz + f * n3 : nullptr;
+            if (cons) {          // move, boxes (with a cutoff), force, close: 3 launches, 4 under a cutoff
+                GRAPPA_LAUNCH(ms_move_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, cn);
+                if (c) ms_launch_boxes(st, nb, q, w, n_items);
+                ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, fx, n_items, w.cfail);
+                msc_launch_close(st, q, w, cn, mass, 1, n_items);
+            } else {
+                if (c) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
+                else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
+                ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, fx, n_items);
+            }
         }
         if (due && (frames_epot || frames_ekin)) {
             if (frames_epot) {
@@ -402,7 +841,8 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             MsOutArgs a = ms_out_args(mm, nb, q, w);
             a.final = 0, a.with_epot = frames_epot != nullptr;
             a.epot = frames_epot ? frames_epot + f * bc : nullptr, a.ekin = frames_ekin ? frames_ekin + f * bc : nullptr;
-            GRAPPA_LAUNCH(ms_out_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
+            if (cons) GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
+            else GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
         }
     }
     return grappa_launch_status();
@@ -410,11 +850,11 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
 
 int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const int* table_dev,
               int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
-              int* status) {
+              int* status, const grappa_md_cons* cons = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
     if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
@@ -423,7 +863,12 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     a.final = 1, a.with_epot = 1;
     a.xyz_out = xyz_out, a.vel_out = vel_out, a.epot = epot, a.ekin = ekin, a.steps = steps, a.status = status;
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
-    GRAPPA_LAUNCH(ms_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    if (cons) {          // a refused item's outputs are not touched: x and v item by item
+        if (n_items > 0) GRAPPA_LAUNCH(msc_copy_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, rs_geom(mm, table_dev, n_blocks), w.x, w.v, w.status, xyz_out, vel_out);
+        GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
+    } else {
+        GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    }
     return grappa_launch_status();
 }
 
@@ -485,4 +930,63 @@ extern "C" int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc
     RsCut c;
     if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
+}
+
+// with X-H constraints: cons == NULL or K == 0 is the call above, with its launches and its bits
+namespace {
+// GRAPPA_OK: constraints to run with; 1: none, forward; < 0: refused
+int msc_check(const grappa_md_cons* cons) {
+    if (cons && cons->K < 0) return GRAPPA_ERR_ARG;
+    if (!cons || cons->K == 0) return 1;
+    if (!cons->cluster_molptr || !cons->cluster_atoms || !cons->cluster_d) return GRAPPA_ERR_ARG;
+    if (!(cons->tolerance >= 0x1p-20f && cons->tolerance <= 0x1p-7f)) return GRAPPA_ERR_ARG;          // (a NaN is refused)
+    return GRAPPA_OK;
+}
+}  // namespace
+
+extern "C" size_t grappa_md_steps_cons_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
+    return ms_layout(nullptr, N, C, B, n_blocks, with_cut != 0, K > 0).total;
+}
+
+extern "C" int grappa_md_steps_init_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                             const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass,
+                                             const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
+                                             int n_blocks, void* ws, size_t ws_bytes) {
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    if (cc == 1) return grappa_md_steps_init_cut_f32(stream, mm, nb, cut, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cons);
+}
+
+extern "C" int grappa_md_steps_run_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                            const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass,
+                                            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                            size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin) {
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    if (cc == 1)
+        return grappa_md_steps_run_cut_f32(stream, mm, nb, cut, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                                           frames_xyz, frames_epot, frames_ekin);
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
+                  frames_epot, frames_ekin, cons);
+}
+
+extern "C" int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                               const grappa_md_opts* o, const grappa_md_cons* cons, const int* table_dev, int n_items,
+                                               int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin,
+                                               int* steps, int* status) {
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    if (cc == 1)
+        return grappa_md_steps_finish_cut_f32(stream, mm, nb, cut, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin,
+                                              steps, status);
+    RsCut c;
+    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
+                     cons);
 }

@@ -12,14 +12,17 @@ that both take has not been decided here (tools/md_steps_bench.py measures it).
 
 Cutoff (`cutoff=`, a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom): the nonbonded term under OpenMM's `CutoffNonPeriodic`
 conventions -- reaction field, optional switch, exceptions uncut (`grappa_amd.nonbonded` states them) -- on the stepwise path only,
-whose force launch then skips the 64 x 64 atom tiles that lie beyond the cutoff; a step stays two launches.  It needs `nonbonded`;
+whose force launch then skips the 64 x 64 atom tiles that lie beyond the cutoff; a step stays two launches (four with constraints).  It needs `nonbonded`;
 `stepwise="auto"` goes stepwise whenever a cutoff is given.  The stepwise minimiser, the fused kernels, periodic boxes, PME and a
 long-range Lennard-Jones correction are out of scope (OpenMM / GROMACS).
 
-Constraints (`constraints=`, `grappa_amd.constraints`): X-H bonds held at fixed lengths, on the fused path only.  The loop is then
-g-BAOAB (Leimkuhler and Matthews, Proc. R. Soc. A 472, 20160138 (2016)) with one geodesic sub-step, csrc/dynamics_cons.hip
-(`grappa_md_langevin_cons_f32`): positions by a cluster-wise Newton iteration (M-SHAKE) of at most eight updates, velocities by a
-direct projection.  An atom draws the same noise with and without constraints.  Rigid water and the stepwise path are out of scope.
+Constraints (`constraints=`, `grappa_amd.constraints`): X-H bonds held at fixed lengths, on either path.  The loop is then
+g-BAOAB (Leimkuhler and Matthews, Proc. R. Soc. A 472, 20160138 (2016)) with one geodesic sub-step: positions by a cluster-wise Newton
+iteration (M-SHAKE) of at most eight updates, velocities by a direct projection (csrc/md_cons.h, one copy for both paths).  Fused:
+csrc/dynamics_cons.hip (`grappa_md_langevin_cons_f32`), at most 256 clusters in a molecule.  Stepwise: `grappa_md_steps_*_cons_f32`
+through `HipBackend.md_steps_cons`, molecules of any size with any number of clusters, with or without a cutoff; a cluster is
+integrated by the workgroup that holds its centre, and a step is three launches, four under a cutoff -- what a 2 fs step for a protein
+needs.  An atom draws the same noise with and without constraints, on either path.  Rigid water is out of scope.
 
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
@@ -33,7 +36,8 @@ be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An i
     4  (with constraints) a position constraint did not converge within its eight updates: stopped, the state is the one it held;
        `steps` counts the steps before the one that failed
     5  (with constraints) the molecule's constraint tables were refused on the device (an index outside the molecule, an atom in two
-       clusters, a length that is not positive and finite, more than 256 clusters): nothing else was written for the item
+       clusters, a length that is not positive and finite, on the fused path more than 256 clusters): nothing else was written for
+       the item
 The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
 has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
 """
@@ -113,6 +117,12 @@ class MDResult:
     frame_kinetic_energy: object = None
 
 
+def _steps_take_constraints() -> bool:
+    """does the backend run constraints on the stepwise path (`md_steps_cons`)?  Without it they run on the fused path only"""
+    from .backend import get_backend
+    return getattr(get_backend(), "md_steps_cons", None) is not None
+
+
 def _host_masses(masses, N):
     """(N,) float32 on the host, checked: finite and >= 0"""
     if isinstance(masses, torch.Tensor):
@@ -151,15 +161,16 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     limit, else the whole batch stepwise -- a batch is never split between the two paths (one batch, one decomposition, one set of
     bits).  No device sync on either path.  The graph is not modified.
     constraints: a `grappa_amd.constraints.ConstraintBatch` holding the batch's molecules in order (None: unconstrained, the calls
-    made are exactly those without this argument).  The fused path only: with constraints stepwise=True is refused, and so is "auto"
-    for a batch above the size limit.  constrain_start=True: the start coordinates are brought to the constraint lengths and the start
+    made are exactly those without this argument).  They run on the path that `stepwise` chooses: fused, or stepwise (`md_steps_cons`:
+    stepwise=True, or "auto" for a batch above the size limit or with a cutoff).  A backend without `md_steps_cons` runs them on the fused
+    path only and refuses the rest.  constrain_start=True: the start coordinates are brought to the constraint lengths and the start
     velocities projected first; False continues a run (with its xyz, velocities and first_step) bit for bit.  The first launch of
     a run gets the caller's constrain_start, later launches continue.  Statuses 4 and 5: see the module text; an item that ends with
     either in one launch of a run keeps that launch's results: later launches add no steps and no frames (NaN) for it.  A moving centre
     whose frozen leaves alone number four is refused (ValueError): they over-determine it.
     cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls made are exactly those without this argument):
-    see the module text.  It needs `nonbonded` and the stepwise path: "auto" then goes stepwise whatever the sizes, stepwise=False and
-    constraints are refused."""
+    see the module text.  It needs `nonbonded` and the stepwise path: "auto" then goes stepwise whatever the sizes, stepwise=False is
+    refused; constraints go with it."""
     from .backend import get_backend
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
@@ -169,7 +180,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
             raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
         if stepwise is False:
             raise ValueError('simulate: a cutoff runs on the stepwise path only: pass stepwise="auto" (or True)')
-        if constraints is not None:
+        if constraints is not None and not _steps_take_constraints():
             raise ValueError("simulate: constraints run on the fused path only, a cutoff on the stepwise path only")
     if isinstance(steps_per_launch, bool) or not isinstance(steps_per_launch, (int, np.integer)) or steps_per_launch < 1:
         raise ValueError(f"steps_per_launch must be an integer >= 1, got {steps_per_launch!r}")
@@ -188,7 +199,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         from .constraints import ConstraintBatch
         if not isinstance(constraints, ConstraintBatch):
             raise TypeError(f"constraints must be a ConstraintBatch or None, got {type(constraints).__name__}")
-        if use_steps:
+        if use_steps and not _steps_take_constraints():
             raise ValueError("simulate: constraints run on the fused path only (stepwise=False, or 'auto' with every molecule within the limit)")
         if constraints.B != len(counts):
             raise ValueError(f"the constraints describe {constraints.B} molecules, the batch has {len(counts)}")
@@ -231,7 +242,10 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
     total = torch.zeros(B, C, dtype=torch.int32, device=dev)
     x_in, v_in, done, launch = xyz, vel, 0, 0
-    held = None          # with constraints and more than one launch: the items that have ended, and what they ended with
+    # With constraints and more than one launch: the items that have ended, and what they ended with.  The stepwise path needs none of it
+    # within a call (init .. finish): there statuses 4 and 5 are sticky in the workspace, whatever the number of run calls; only a run
+    # longer than the library's cap on n_steps makes a second call, and this bookkeeping then carries an ended item across it.
+    held = None
     if constraints is not None and n_steps > seg:
         held = {"dead": torch.zeros(B, C, dtype=torch.bool, device=dev)}
         atom_item = torch.repeat_interleave(torch.arange(B), torch.tensor(counts, dtype=torch.long)).to(dev)
@@ -244,7 +258,10 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         args = (plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin, steps, status)
         kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
-        if use_steps:
+        if use_steps and constraints is not None:
+            get_backend().md_steps_cons(*args, steps_per_call=chunk, **kw, **({} if cutoff is None else {"cutoff": cutoff}),
+                                        constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
+        elif use_steps:
             get_backend().md_steps(*args, steps_per_call=chunk, **kw, **({} if cutoff is None else {"cutoff": cutoff}))
         elif constraints is not None:
             get_backend().md_langevin(*args, **kw, constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
@@ -293,7 +310,7 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
             raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
         if stepwise is False:
             raise ValueError('simulate: a cutoff runs on the stepwise path only: pass stepwise="auto" (or True)')
-        if constraints is not None:
+        if constraints is not None and not _steps_take_constraints():
             raise ValueError("simulate: constraints run on the fused path only, a cutoff on the stepwise path only")
         extra["cutoff"] = cutoff
     if constraints is not None:

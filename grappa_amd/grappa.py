@@ -81,10 +81,11 @@ class Grappa:
         (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules of any size.  **kw: velocities,
         seed, keys, first_step, steps_per_launch, constrain_start and the options of `MD_DEFAULTS` (see
         `grappa_amd.dynamics.simulate_graph`).  constraints: None, "h-bonds" (every X-H bond held at its predicted equilibrium length:
-        `grappa_amd.constraints.hydrogen_constraints`) or a `Constraints` in the molecule's atom order; the fused path only.
+        `grappa_amd.constraints.hydrogen_constraints`) or a `Constraints` in the molecule's atom order, on either path
+        (`constraints="h-bonds", stepwise="auto", cutoff=9.0`: a protein at 2 fs steps).
         cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom (None: all pairs): the nonbonded term with a cutoff and a
         reaction field on the stepwise path, which skips the atom tiles beyond it -- what makes a protein fast, not only movable; it
-        needs `nonbonded` and stepwise="auto" (or True), and refuses constraints"""
+        needs `nonbonded` and stepwise="auto" (or True)"""
         from .dynamics import simulate
         if cutoff is not None:
             kw = {**kw, "cutoff": cutoff}

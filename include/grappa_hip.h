@@ -787,7 +787,8 @@ int grappa_md_noise_f32(void* stream, const unsigned long long* mol_key, const i
  * vel_in = vel_out and first_step + a.  Same input, same bits; an item's bits depend neither on its place nor on its neighbours.
  * GRAPPA_ERR_ARG: the cases of grappa_md_langevin_f32, plus K < 0, a NULL table with K > 0, and a tolerance that is not finite, below
  * 2^-20 or above 2^-7.  cons == NULL or K == 0: the launch of grappa_md_langevin_f32 itself, hence its bits.  Constraints other than
- * these stars (rigid water, SETTLE), and constraints on the stepwise path, are not supported. */
+ * these stars (rigid water, SETTLE) are not supported.  Molecules above the size limit, and a nonbonded cutoff, go through
+ * grappa_md_steps_*_cons_f32 below. */
 #define GRAPPA_MD_CONS_MAX_LEAVES 4
 #define GRAPPA_MD_CONS_MAX_ITER 8
 typedef struct grappa_md_cons {
@@ -882,6 +883,54 @@ int grappa_md_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const gr
 int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                    const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
                                    float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status);
+/* The stepwise dynamics with X-H bond constraints (additions to ABI 11): the `_cut_` calls above with `const grappa_md_cons* cons` after
+ * the options; cut may be NULL (all pairs).  cons == NULL or K == 0 forwards to the `_cut_` call (which forwards to the plain one for
+ * cut == NULL): its launches, its bits.  Otherwise the loop is, word for word, the one stated at grappa_md_langevin_cons_f32 -- the star
+ * clusters, P, S with at most GRAPPA_MD_CONS_MAX_ITER updates, the tolerance range, constrain_start (read by init alone), the noise
+ * counters, the frozen-atom rules, status 4 with steps = the steps completed before the failing one (0 when the start's S failed), status
+ * 5, the frame rule -- for molecules of ANY size and any number of clusters: "at most 256 clusters" does not apply, "an atom is in at most
+ * one cluster" does.  Pass the same cut and cons tables to all three calls.
+ *   decomposition : a cluster is integrated, all its atoms together, by the thread that its CENTRE has in the work item of the centre's
+ *            block; its leaves may lie in any block of the molecule, so no order is asked of the table.  A clustered atom is skipped by
+ *            its ordinary owner in the integration; a free atom moves exactly as in grappa_md_steps_run_f32.
+ *   run    : a step is THREE launches, FOUR under a cutoff, whatever the shape, and nothing else without frames:
+ *            move  (clusters: v -= hk w g, P | A S P | O P | A S P; free atoms as above; the flags' OR, status and steps as above, where
+ *                  a set constraint flag gives status 4 and takes back the count of the failing step -- the first block's workgroup is the
+ *                  only writer of both words; per (block, conformation) the constraint-failure word of the block's own clusters, fresh
+ *                  each launch)
+ *            boxes (only with cut: a block's atoms may have been moved by a sibling, so the boxes need the launch boundary)
+ *            force (as above, with the closing kick of EVERY atom by its owner; the block's flag word also takes the block's
+ *                  constraint-failure word, so the flags stay the one array that move reads, and stay sticky)
+ *            close (clusters: the closing P; per (block, conformation) the kinetic partial, here the sum in double over the block's atoms
+ *                  in ascending order where a free atom gives m v^2, a centre the sum over its cluster's moving atoms -- the centre, then
+ *                  its leaves in table order -- and a leaf nothing.  ekin stays the ascending-block sum.)
+ *   init   : the launches of the `_cut_` init plus the table vet (3: claim words cleared, written, read back), the start's S and P (1,
+ *            unless constrain_start == 0 with vel_in given), and the kinetic partials (1): 6 or 7 launches, one more under a cutoff.
+ *   tables : vetted on the device during init: per cluster the checks of grappa_md_langevin_cons_f32; "no atom in two clusters" through
+ *            one claim word per atom in the workspace: a launch has every cluster store its index to its atoms' words with plain stores,
+ *            the next has it read them back, and of two clusters that hold one atom at least one sees the other.  A refused item gets
+ *            status 5 and nothing else: its xyz_out, vel_out, epot, ekin, steps and frames are untouched; its neighbours run.
+ *   finish : as above; the stop decision taken once more includes the constraint flag (status 4 with the failing step taken back), so
+ *            the failure flag survives any number of run calls: it lives in the workspace.
+ * Hazards: the rule above holds launch by launch: every word has one writer per launch and no workgroup reads in a launch what a sibling
+ * writes in it.  Bits: same input, same bits; they depend neither on the item's place or neighbours, nor on how steps are dealt to run
+ * calls, nor on where frames fall; they differ from the fused kernel's.  The continuation rule is grappa_md_langevin_cons_f32's
+ * (constrain_start = 0, first_step + a).  GRAPPA_ERR_ARG, nothing launched: the cases of the `_cut_` calls, plus K < 0, a NULL table with
+ * K > 0 and a tolerance that is not finite, below 2^-20 or above 2^-7.  The workspace is
+ * grappa_md_steps_cons_workspace_bytes(N, C, B, n_blocks, K, with_cut): that of the call forwarded to for K == 0, else 4 N + 4 n_blocks C
+ * bytes more; below it: GRAPPA_ERR_WORKSPACE, nothing launched. */
+size_t grappa_md_steps_cons_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut);
+int grappa_md_steps_init_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                  const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass, const unsigned long long* mol_key,
+                                  const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_steps_run_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                 const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass, const unsigned long long* mol_key,
+                                 const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
+                                 float* frames_xyz, float* frames_epot, float* frames_ekin);
+int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                    const grappa_md_opts* o, const grappa_md_cons* cons, const int* table_dev, int n_items, int n_blocks,
+                                    void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+                                    int* status);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

@@ -23,6 +23,18 @@ and the tiles the cut energy kernel evaluates per work item at the start coordin
 printed: the acceptance on the 50,046-atom graph is "the slowest pruned run is faster than the fastest all-pairs run".
 
     python tools/md_steps_bench.py --cutoff 10 [--switch 8] [--out profiles/md_steps_cutoff_bench.txt]
+
+With --constraints the tool measures X-H constraints on the stepwise path instead (same protocol): on the 513-atom and the 50,046-atom
+workload, all pairs and under a cutoff of --cutoff (default 9) A, the unconstrained stepwise run at 1 fs -- the yardstick, whose kernels
+this option does not touch -- against the constrained run at 2 fs and at 1 fs.  The workloads are the tool's chains with every second
+atom made the leaf of the atom before it, held at their bond's equilibrium length: half the atoms are leaves, as in a protein, though
+all in one-leaf clusters (a chain has no XH2 or XH3).  The leaves keep the chain's mass (--leaf-mass gives them another): an atom of
+1.008 amu INSIDE this synthetic backbone, with a second bond that is not constrained, stops the items within a few steps, and a stopped
+item is skipped by every later launch, so its time is not a rate.  It reports atoms, clusters, statuses, the item steps that were run
+and the time per step, constrained over unconstrained: below 2 -- the ratio of the time steps -- constraints pay.  A side whose items
+stopped early is marked: its time per step counts launches that did nothing.
+
+    python tools/md_steps_bench.py --constraints [--cutoff 9] [--out profiles/md_steps_cons_bench.txt]
 """
 import argparse
 import datetime
@@ -40,7 +52,11 @@ from md_bench import OPTS, Composed, _batch, _timed      # noqa: E402
 WORKLOADS = ("pool", "mid", "big")
 SIDES = {"pool": ("fused", "stepwise", "composed", "agreement"), "mid": ("stepwise", "composed"), "big": ("stepwise", "composed")}
 CUT_SIDES = ("stepwise", "cut", "cut_noprune", "tiles")
-STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:]]
+CONS_SIDES = ("free_1fs", "cons_2fs", "cons_1fs")
+CONS_DT = {"free_1fs": 0.001, "cons_2fs": 0.002, "cons_1fs": 0.001}
+STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:]] + \
+         [f"{w}:{s}:{p}" for w in WORKLOADS[1:] for s in CONS_SIDES for p in ("pairs", "cut")]
+
 STAGE_LIMIT = 300      # seconds, every stage
 AGREEMENT_STEPS = 50
 CARBON = 12.011
@@ -57,6 +73,24 @@ def _workload(args, which):
     n = args.mid_atoms if which == "mid" else args.big_atoms
     gh, nbp = chain_graph(n)
     return gh.to("cuda"), NonbondedBatch([nbp]).to("cuda"), np.full(n, CARBON, dtype=np.float32), 1, args.steps if which == "mid" else args.big_steps
+
+
+def _leaves(n, leaf_mass):
+    """every second atom of the n-atom chain a leaf held to the atom before it at the bond's equilibrium length
+    -> (masses (n,) float32, Constraints)"""
+    import numpy as np
+    from relax_steps_bench import chain
+    from grappa_amd.constraints import MAX_LEAVES, Constraints
+    _, xyz = chain(n)
+    x = xyz[:, 0, :].astype(np.float64)
+    centre = np.arange(0, n - 1, 2)
+    clusters = np.full((centre.size, MAX_LEAVES + 1), -1, dtype=np.int32)
+    clusters[:, 0], clusters[:, 1] = centre, centre + 1
+    lengths = np.zeros((centre.size, MAX_LEAVES), dtype=np.float32)
+    lengths[:, 0] = np.linalg.norm(x[centre + 1] - x[centre], axis=-1)          # chain_graph's bond_eq
+    masses = np.full(n, CARBON, dtype=np.float32)
+    masses[centre + 1] = leaf_mass
+    return masses, Constraints(clusters, lengths)
 
 
 def _all_timed(fn, reps):
@@ -88,12 +122,31 @@ def stage(args):
         print(json.dumps({"device": f"{prop.name}, {getattr(prop, 'gcnArchName', '?')}, {prop.multi_processor_count} CUs, "
                                     f"{prop.total_memory / 2 ** 30:.0f} GiB; library built for {be.lib.grappa_build_arch().decode()}; torch {torch.__version__}"}))
         return
-    which, side = args.stage.split(":")
+    which, side, pairs = (args.stage.split(":") + [None])[:3]
     g, nb, masses, confs, steps = _workload(args, which)
     counts = g.batch_num_nodes_host("n1")
     out = {"molecules": len(counts), "atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max()), "confs": confs}
     sim = lambda n, stepwise, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, stepwise=stepwise,      # noqa: E731
                                                    **{**OPTS, **kw})
+    if side in CONS_SIDES:
+        from grappa_amd.constraints import ConstraintBatch
+        from grappa_amd.nonbonded import Cutoff
+        masses, cons = _leaves(int(counts[0]), args.leaf_mass)
+        kw = {"dt": CONS_DT[side]}
+        if pairs == "cut":
+            kw["cutoff"] = Cutoff(args.cutoff or 9.0, args.switch or None)
+        if side != "free_1fs":
+            kw["constraints"] = ConstraintBatch([cons])
+        run = lambda: simulate_graph(g, masses, nb, n_steps=steps, steps_per_launch=args.steps_per_launch, stepwise=True, **{**OPTS, **kw})      # noqa: E731
+        n0 = be.lib.grappa_launch_count(0)
+        r = run()
+        torch.cuda.synchronize()
+        out["launches"], out["steps"], out["clusters"] = int(be.lib.grappa_launch_count(0) - n0), steps, cons.n_clusters if side != "free_1fs" else 0
+        out["item_steps"], out["statuses"] = int(r.steps.sum()), sorted(set(r.status.flatten().tolist()))
+        out["all_us"] = _all_timed(run, args.reps)
+        out["median_us"], out["min_us"] = float(sorted(out["all_us"])[len(out["all_us"]) // 2]), min(out["all_us"])
+        print(json.dumps(out))
+        return
     if side in ("cut", "cut_noprune", "tiles"):
         from grappa_amd.nonbonded import Cutoff
         cut = Cutoff(args.cutoff, args.switch or None, prune=side != "cut_noprune")
@@ -165,6 +218,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
     ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
+    ap.add_argument("--constraints", action="store_true", help="measure X-H constraints on the stepwise path (see the module text)")
+    ap.add_argument("--leaf-mass", type=float, default=CARBON, help="amu; the mass of the leaves with --constraints (the chain's own by default)")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -179,7 +234,7 @@ def main():
     def run(name):
         cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
               [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
-                                                                      "composed_steps", "reps", "cutoff", "switch")]
+                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass")]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
             sys.stderr.write(p.stdout + p.stderr)
@@ -196,7 +251,35 @@ def main():
     say(f"# device: {run('device')['device']}")
     say("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; steps/s = steps of the run / "
         "run time, whatever the batch holds; this file is the tool's output, unedited")
-    if args.cutoff:
+    if args.constraints:
+        args.cutoff = args.cutoff or 9.0
+        say(f"# X-H constraints on the stepwise path: every second atom a leaf ({args.leaf_mass} amu) held to the atom before it; cutoff {args.cutoff} A, "
+            f"switch {args.switch or 'none'}, reaction field 78.3; {OPTS['temperature']} K, friction {OPTS['friction']} / ps; all run times in ms")
+        for w in WORKLOADS[1:]:
+            for pairs, what in (("pairs", "all pairs"), ("cut", f"cutoff {args.cutoff} A")):
+                res = {side: run(f"{w}:{side}:{pairs}") for side in CONS_SIDES}
+                r = res["cons_2fs"]
+                say(f"{w}, {what}: {r['atoms']} atoms, {r['clusters']} clusters ({r['clusters']} leaves), C = {r['confs']}")
+                per = {}
+                for side in CONS_SIDES:
+                    q = res[side]
+                    per[side] = q["median_us"] / q["steps"]
+                    say(f"  {side:9s} dt {CONS_DT[side] * 1e3:.0f} fs {q['steps']:5d} steps  {per[side]:10.2f} us / step  {q['steps'] / (q['median_us'] * 1e-6) * CONS_DT[side] * 1e3 * 86.4e-3:10.3f} ns / day  "
+                        f"{q['launches']:6d} library launches  statuses {q['statuses']}  {q['item_steps']} item steps  "
+                        f"runs: {', '.join(f'{u / 1e3:.2f}' for u in q['all_us'])}"
+                        + ("" if q["item_steps"] == q["steps"] * q["confs"] else "  STOPPED EARLY: not a rate"))
+                # a constrained step costs the same at 1 fs and at 2 fs; where the 2 fs run stopped early (its time is not a rate) the
+                # 1 fs run, if it ran all its steps, stands for it
+                ran = {side: res[side]["item_steps"] == res[side]["steps"] * res[side]["confs"] for side in CONS_SIDES}
+                side = "cons_2fs" if ran["cons_2fs"] else "cons_1fs"
+                if not (ran[side] and ran["free_1fs"]):
+                    say("  time per step, constrained / unconstrained: no ratio, items stopped early on both constrained runs or on the yardstick")
+                    continue
+                ratio = per[side] / per["free_1fs"]
+                say(f"  time per step, constrained ({side}) / unconstrained (1 fs) = {ratio:.3f}: simulated time per wall time at 2 fs {2.0 / ratio:.2f}x "
+                    f"({'constraints pay' if ratio < 2.0 else 'constraints do NOT pay'}: the bound is the ratio of the time steps, 2)"
+                    + ("" if ran["cons_2fs"] else "; the 2 fs run itself stopped early on this synthetic chain"))
+    elif args.cutoff:
         say(f"# cutoff {args.cutoff} A, switch {args.switch or 'none'}, reaction field 78.3; all five run times of each side in ms; tiles: evaluated by the cut "
             "energy kernel at the start coordinates, summed over its work items")
         for w in WORKLOADS:
@@ -214,7 +297,7 @@ def main():
             say(f"  cut, prune=1 / all pairs = {rate['cut'] / rate['stepwise']:.2f}x steps/s; cut, prune=0 / all pairs = {rate['cut_noprune'] / rate['stepwise']:.2f}x; "
                 f"slowest pruned run {max(res['cut']['all_us']) / 1e3:.2f} ms, fastest all-pairs run {min(res['stepwise']['all_us']) / 1e3:.2f} ms: "
                 f"{'faster' if max(res['cut']['all_us']) < min(res['stepwise']['all_us']) else 'NOT faster'}")
-    for w in (() if args.cutoff else WORKLOADS):
+    for w in (() if args.cutoff or args.constraints else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:
             r = run(f"{w}:{side}")
