@@ -220,6 +220,42 @@ class MMBackend:
         _chk(self.lib.grappa_nonbonded_fwd_f32(self._stream(), C.byref(d), energy.data_ptr(), _ptr(term_energy), _ptr(grad), ws.data_ptr(), ws.numel()),
              "grappa_nonbonded_fwd_f32")
 
+    # ------------------------------------------------------------------ implicit solvent
+    def gb_obc(self, xyz, atom_molptr, charge, radius, scale, opts, energy, term_energy=None, grad=None, born=None, plan=None) -> None:
+        """GB/SA implicit solvent in the Onufriev-Bashford-Case form (include/grappa_hip.h grappa_gb_obc_fwd_f32 states the energy):
+        xyz (N,C,3), atom_molptr (B+1,) int32, charge / radius / scale (N,) float32; opts: the eight options of grappa_gb_desc by name
+        (`ImplicitSolvent.as_opts()`); plan (required): what `nonbonded_plan` returned for this atom_molptr and C.
+        -> energy (B,C), term_energy (2,B,C: polar, surface area) or None, grad (N,C,3) = +dE/dxyz or None, born (N,C) = the Born radii
+        or None.  Angstrom, kcal/mol, elementary charges.  4 launches, 3 without grad.  radius <= offset or scale <= 0 make the
+        molecule's results NaN (`GBParameters.validate` refuses them on the host).  Out of scope: a cutoff, HCT / GBn, a salt term."""
+        _xyz3(xyz, "gb_obc")
+        dev = xyz.device
+        _tensors(dev, [(xyz, "xyz", _F32), (atom_molptr, "atom_molptr", _I32), (charge, "charge", _F32), (radius, "radius", _F32),
+                       (scale, "scale", _F32), (energy, "energy", _F32), (term_energy, "term_energy", _F32), (grad, "grad", _F32),
+                       (born, "born", _F32)], ("term_energy", "grad", "born"))
+        N, Cc, B = xyz.shape[0], xyz.shape[1], atom_molptr.numel() - 1
+        if B < 0 or any(t.numel() != N for t in (charge, radius, scale)):
+            raise ValueError("gb_obc: atom_molptr must be (B+1,), charge / radius / scale (N,)")
+        if energy.numel() != B * Cc or (term_energy is not None and term_energy.numel() != 2 * B * Cc) or (grad is not None and grad.shape != xyz.shape) \
+                or (born is not None and born.numel() != N * Cc):
+            raise ValueError("gb_obc: expected energy (B,C), term_energy (2,B,C), grad (N,C,3), born (N,C)")
+        names = [f[0] for f in _lib.GbDesc._fields_ if f[0] not in ("radius", "scale")]
+        if sorted(opts) != sorted(names):
+            raise ValueError(f"gb_obc: opts must hold exactly {names}, got {sorted(opts)}")
+        if N == 0 or Cc == 0 or B == 0:
+            return
+        if plan is None or plan[0] is None:
+            raise ValueError("gb_obc: the plan of `nonbonded_plan` is required (the planned form is the only one)")
+        table, n_items, n_blocks, plan_c = plan
+        if plan_c != Cc or table.device != dev or table.dtype != torch.int32 or table.numel() < 4 + B + 1 + 4 * n_items:
+            raise ValueError(f"gb_obc: the plan was made for C = {plan_c} on {table.device}, the call has C = {Cc} on {dev}")
+        d = _lib.NbDesc()
+        d.N, d.C, d.B, d.xyz, d.atom_molptr, d.charge = N, Cc, B, xyz.data_ptr(), atom_molptr.data_ptr(), charge.data_ptr()
+        g = _lib.GbDesc(radius=radius.data_ptr(), scale=scale.data_ptr(), **{k: float(opts[k]) for k in names})
+        ws = self._workspace(int(self.lib.grappa_gb_obc_workspace_bytes(N, Cc, n_blocks)), dev)
+        _chk(self.lib.grappa_gb_obc_fwd_f32(self._stream(), C.byref(d), C.byref(g), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
+                                            _ptr(term_energy), _ptr(grad), _ptr(born), ws.data_ptr(), ws.numel()), "grappa_gb_obc_fwd_f32")
+
     # ------------------------------------------------------------------ relaxation
     def relax_max_atoms(self) -> int:
         return int(self.lib.grappa_relax_max_atoms())
@@ -439,10 +475,31 @@ class MMBackend:
                        steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
                        constrain_start)
 
+    def md_steps_gb(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
+                    frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None,
+                    constraints=None, constrain_start=True, gb=None, solvent="obc2", esolv=None, frames_esolv=None) -> None:
+        """`md_steps_cons` in GB/SA implicit solvent (include/grappa_hip.h grappa_md_steps_*_gb_f32): its arguments without the cutoff
+        (GB under a cutoff is not implemented) plus gb, a `grappa_amd.solvent.GBBatch` on xyz's device holding the batch's molecules in
+        order, and solvent, a model name or an `ImplicitSolvent`.  nb is required: it carries the charges.  constraints may be None.
+        epot then includes the solvent term; esolv (B,C) and frames_esolv (F,B,C) float32 or None -> the solvent term alone.  A step is
+        five launches, six with constraints; the workspace is `grappa_md_steps_gb_workspace_bytes`.  Like `md_steps` it has NO device
+        sync."""
+        from .solvent import GBBatch, as_implicit_solvent
+        sv = as_implicit_solvent(solvent)
+        if sv is None or not isinstance(gb, GBBatch):
+            raise TypeError(f"md_steps_gb: gb must be a GBBatch and solvent a model, got {type(gb).__name__}, {solvent!r}")
+        if nb is None:
+            raise ValueError("md_steps_gb: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
+        gb.check_offset(sv.offset)
+        self._md_steps("md_steps_gb", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
+                       steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, None, constraints,
+                       constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv)
+
     def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
-                  frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start):
+                  frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start,
+                  gb=None, solvent=None, esolv=None, frames_esolv=None):
         """init, the run calls and finish of one stepwise run: the plain calls, the _cut_ calls with a cutoff, the _cons_ calls with
-        constraints (and the cutoff or NULL)"""
+        constraints (and the cutoff or NULL), the _gb_ calls with an implicit solvent (and the constraints or NULL)"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
         d, o = self._md_call(who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
@@ -458,10 +515,21 @@ class MMBackend:
                 raise ValueError(f"{who}: a cutoff needs the nonbonded tables (nb)")
             cut = _cut_struct(cutoff, who)
         cons = self._md_cons(constraints, B, dev, constrain_start, who) if constraints is not None else None
+        gbd = None
+        if gb is not None:
+            F_ = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
+            _tensors(dev, ((gb.radius, "gb.radius", _F32), (gb.scale, "gb.scale", _F32), (esolv, "esolv", _F32), (frames_esolv, "frames_esolv", _F32)),
+                     ("esolv", "frames_esolv"))
+            if gb.radius.numel() != N or gb.scale.numel() != N or (esolv is not None and esolv.numel() != B * Cc) \
+                    or (frames_esolv is not None and frames_esolv.numel() != F_ * B * Cc):
+                raise ValueError(f"{who}: expected gb.radius / gb.scale ({N},), esolv (B,C), frames_esolv ({F_},B,C)")
+            gbd = _lib.GbDesc(radius=gb.radius.data_ptr(), scale=gb.scale.data_ptr(), **solvent.as_opts())
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        if cons is not None:
+        if gbd is not None:
+            need = int(self.lib.grappa_md_steps_gb_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
+        elif cons is not None:
             need = int(self.lib.grappa_md_steps_cons_workspace_bytes(N, Cc, B, n_blocks, cons.K, int(cut is not None)))
         else:
             need = int((self.lib.grappa_md_steps_workspace_bytes if cut is None else self.lib.grappa_md_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
@@ -470,7 +538,9 @@ class MMBackend:
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if cons is not None:
+        if gbd is not None:
+            head, sfx = (st, C.byref(d), ndp, None, C.byref(o), C.byref(cons) if cons is not None else None, C.byref(gbd)), "_gb_f32"
+        elif cons is not None:
             head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons)), "_cons_f32"
         elif cut is None:
             head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
@@ -480,7 +550,7 @@ class MMBackend:
         tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
         _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), f"grappa_md_steps_init{sfx}")
         F = o.n_steps // o.save_every if o.save_every > 0 else 0
-        every = o.save_every if F > 0 and any(t is not None for t in (frames_xyz, frames_epot, frames_ekin)) else 0
+        every = o.save_every if F > 0 and any(t is not None for t in (frames_xyz, frames_epot, frames_ekin, frames_esolv)) else 0
         chunk = int(steps_per_call)
         if every > 0:
             chunk = max(chunk // every, 1) * every
@@ -489,11 +559,11 @@ class MMBackend:
             n = min(chunk, o.n_steps - done)
             f0 = done // every if every > 0 else 0
             fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size()
-                  for t in (frames_xyz, frames_epot, frames_ekin)]
+                  for t in (frames_xyz, frames_epot, frames_ekin) + ((frames_esolv,) if gbd is not None else ())]
             _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), f"grappa_md_steps_run{sfx}")
             done += n
-        _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr()),
-             f"grappa_md_steps_finish{sfx}")
+        _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(),
+                    *((_ptr(esolv),) if gbd is not None else ())), f"grappa_md_steps_finish{sfx}")
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

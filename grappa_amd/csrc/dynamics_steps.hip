@@ -26,6 +26,8 @@
 //   constraints: grappa_md_steps_*_cons_f32 (cons == NULL or K == 0: the calls without).  X-H star clusters under g-BAOAB with P and S of
 //            csrc/md_cons.h; a cluster is integrated by the thread of its centre, and a step becomes move, boxes (with a cutoff),
 //            force, close: the section "X-H constraints" below states the decomposition, the launches and the hazards.
+//   solvent: grappa_md_steps_*_gb_f32 (gb == NULL: the calls without).  The section "implicit solvent" below: the force launch as it is,
+//            without its closing kick, then born, pair and chain of csrc/gb_pass.h; the chain launch's epilogue closes the step.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -33,6 +35,7 @@
 
 #include "common.h"
 #include "desc_check.h"
+#include "gb_pass.h"
 #include "md_cons.h"
 #include "md_noise.h"
 #include "rs_force.h"
@@ -690,6 +693,139 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ implicit solvent (grappa_md_steps_*_gb_f32)
+// GB/SA (include/grappa_hip.h grappa_gb_desc) as a term of the force: the three passes of csrc/gb_pass.h under the stopped-conformation
+// mask, behind the force launch, which runs AS IT IS with hk = 0 (no closing kick: the form init has always used) -- so the kernels of a
+// run without solvent are not touched by this section, and a run with it launches the very same force kernels.
+//   step   : move, force (g = bonded + nonbonded, the frame's coordinates, the flag), born, pair (the gradient at fixed B -> ggb), chain:
+//            its epilogue adds g + ggb + the chain sum in that order, writes g, gives the closing kick, ORs the non-finite test of the sum
+//            into the block's flag word and (without constraints) rewrites the block's kinetic partial.  5 launches; with constraints
+//            move, force, born, pair, chain, close: 6.  init gains the same three launches behind its force launch.
+//   hazards: born writes B, dBdI of its own (atom, conformation)s, pair reads B of every j and writes w and ggb of its own, chain reads w
+//            of every j and writes g, v of its own and the flag and partial of its own block: every word has one writer per launch and
+//            is read only across a launch boundary.  The flag word is the block's own, written by the force launch before.
+//   energies: grappa_gb_obc_fwd_f32 itself at the held coordinates, in a workspace region of its own (steps_gb_terms_at of
+//            csrc/rs_force.h), and one small launch that adds the eight terms in double in term order.
+struct MsGb {
+    const grappa_gb_desc* opts;
+    GbK k;
+};
+
+struct MsGbWs {
+    GbPassWs p;
+    float* ggb;                          // [N,C,3]: the gradient at fixed B
+    float *e_gb, *terms_gb;              // frames and finish: [B,C], [2,B,C]
+    char* fwd;                           // frames and finish: the workspace of grappa_gb_obc_fwd_f32
+    size_t fwd_bytes;
+    size_t total;
+};
+
+// (the words of the solvent lie behind all others: `off` = the total of ms_layout)
+MsGbWs ms_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks) {
+    MsGbWs g;
+    WsCarve k{base};
+    k.off = off;
+    g.p = gb_pass_ws(k, N, C);
+    g.ggb = k.take<float>((size_t)N * C * 3);
+    g.e_gb = k.take<float>((size_t)B * C), g.terms_gb = k.take<float>(2 * (size_t)B * C);
+    g.fwd_bytes = grappa_gb_obc_workspace_bytes(N, C, n_blocks > 0 ? n_blocks : 1);
+    g.fwd = k.take<char>(g.fwd_bytes);
+    g.total = k.off;
+    return g;
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_gb_born_kernel(GbArgs a) {
+    __shared__ GbShared sh;
+    gb_born_body<true>(a, sh);
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_gb_pair_kernel(GbArgs a) {
+    __shared__ GbShared sh;
+    gb_pair_body<true, false, true>(a, sh);
+}
+
+struct MsGbCloseArgs {
+    GbArgs a;
+    float *v, *g;
+    const float* mass;
+    int* bad;
+    double* kpart;
+    float hk;                // dt / 2 ACC; 0: no closing kick (init)
+};
+
+// CONS: the kinetic partial is left to the close launch, which follows the closing P
+template <bool CONS>
+__global__ __launch_bounds__(NB_NT) void ms_gb_chain_kernel(MsGbCloseArgs c) {
+    __shared__ GbShared sh;
+    gb_chain_body<true>(c.a, sh, [&](const GbLane& w, float cx, float cy, float cz) {
+        const int C = c.a.q.C, ni = w.r.ni;
+        float mv2 = 0.f, bad = 0.f;
+        if (w.owner) {
+            const size_t off = ((size_t)w.i * C + w.c) * 3;
+            const V3 gi = {(c.g[off] + c.a.gdir[off]) + cx, (c.g[off + 1] + c.a.gdir[off + 1]) + cy, (c.g[off + 2] + c.a.gdir[off + 2]) + cz};
+            c.g[off] = gi.x, c.g[off + 1] = gi.y, c.g[off + 2] = gi.z;
+            const float m = c.mass[w.i];
+            V3 vi = {c.v[off], c.v[off + 1], c.v[off + 2]};
+            if (m > 0.f) {
+                if (c.hk > 0.f) {          // the closing B of the step
+                    vi = vi - (c.hk * (1.0f / m)) * gi;
+                    c.v[off] = vi.x, c.v[off + 1] = vi.y, c.v[off + 2] = vi.z;
+                }
+                mv2 = m * dot(vi, vi);
+            }
+            if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;      // (written so that a NaN counts as non-finite)
+        }
+        __syncthreads();
+        if (w.owner) sh.red[0][w.l] = mv2, sh.red[1][w.l] = bad;
+        __syncthreads();
+        if (w.owner && w.il == 0) {      // the block's words of one conformation: over its atoms in ascending order, in double
+            double sk = 0.0;
+            float fb = 0.f;
+            for (int k = 0; k < ni; ++k) {
+                const int o = w.cl * ni + k;
+                sk += (double)sh.red[0][o];
+                fb = fmaxf(fb, sh.red[1][o]);
+            }
+            const size_t o = (size_t)w.r.blk * C + w.c;
+            if constexpr (!CONS) c.kpart[o] = sk;
+            if (fb != 0.f) c.bad[o] |= 1;          // (the block's own word, which the force launch before this one wrote)
+        }
+    });
+}
+
+// the three solvent launches behind a force launch that gave no closing kick
+void ms_launch_gb(hipStream_t st, const grappa_nb_desc* nb, const MsGb& gb, const RsGeom& q, const MsWs& w, const MsGbWs& gw, const float* mass,
+                  float hk, int n_items, bool cons) {
+    MsGbCloseArgs c = {};
+    c.a.q = q, c.a.x = w.x, c.a.charge = nb->charge, c.a.radius = gb.opts->radius, c.a.scale = gb.opts->scale, c.a.k = gb.k;
+    c.a.B = gw.p.B, c.a.dBdI = gw.p.dBdI, c.a.w = gw.p.w, c.a.gdir = gw.ggb, c.a.part = nullptr, c.a.born = nullptr, c.a.status = w.status;
+    c.v = w.v, c.g = w.g, c.mass = mass, c.bad = w.bad, c.kpart = w.kpart, c.hk = hk;
+    const dim3 grid((unsigned)n_items), block(NB_NT);
+    GRAPPA_LAUNCH(ms_gb_born_kernel, grid, block, 0, st, c.a);
+    GRAPPA_LAUNCH(ms_gb_pair_kernel, grid, block, 0, st, c.a);
+    if (cons) GRAPPA_LAUNCH(ms_gb_chain_kernel<true>, grid, block, 0, st, c);
+    else GRAPPA_LAUNCH(ms_gb_chain_kernel<false>, grid, block, 0, st, c);
+}
+
+// epot with the solvent's two terms, and esolv: the conditions of ms_out_kernel, which ran before it and left epot without them
+template <bool CONS>
+__global__ __launch_bounds__(256) void ms_out_gb_kernel(MsOutArgs a, const float* terms_gb, float* esolv) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, bc = (size_t)a.B * a.C;
+    if (gid >= bc) return;
+    const int b = (int)(gid / (unsigned)a.C);
+    if (nb_clamp(a.atom_molptr[b + 1], a.N) <= nb_clamp(a.atom_molptr[b], a.N)) return;
+    const int st = a.status_ws[gid];
+    if (!a.final && st != RS_RUNNING) return;
+    if (CONS && st == 5) return;
+    const double es = (double)terms_gb[gid] + (double)terms_gb[bc + gid];
+    if (a.epot) {
+        double tot = 0.0;
+        for (int q = 0; q < 6; ++q) tot += (double)((q < 4 || a.has_nb) ? a.terms[q * bc + gid] : 0.f);
+        a.epot[gid] = (float)(tot + es);
+    }
+    if (esolv) esolv[gid] = (float)es;
+}
+
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
@@ -751,12 +887,14 @@ void msc_launch_close(hipStream_t st, const RsGeom& q, const MsWs& w, const MscD
 // the three calls, with and without a cutoff (c == NULL: none) and constraints (cons == NULL: none, the launches as they were)
 int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
             const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
-            const grappa_md_cons* cons = nullptr) {
+            const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    MsGbWs gw = {};
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.n_blocks = n_blocks;
@@ -784,30 +922,36 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
             }
             if (c) ms_launch_boxes(st, nb, q, w, n_items);
             ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail);
+            if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, true);
             msc_launch_close(st, q, w, cn, mass, 0, n_items);
         }
         return grappa_launch_status();
     }
     if (c && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
     if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
+    if (gb && n_items > 0) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, false);
     return grappa_launch_status();
 }
 
 int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
-           float* frames_xyz, float* frames_epot, float* frames_ekin, const grappa_md_cons* cons = nullptr) {
+           float* frames_xyz, float* frames_epot, float* frames_ekin, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr,
+           float* frames_esolv = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
-    const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin);
+    const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin || frames_esolv);
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    MsGbWs gw = {};
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const MdConsts k = md_consts(o);
+    const float hkf = gb ? 0.f : k.hk;          // with the solvent the chain launch gives the closing kick
     MscDev cn = {};
     if (cons) cn = msc_dev(cons, o), cn.claim = w.claim, cn.cfail = w.cfail;
     MsMoveArgs mv;
@@ -825,24 +969,34 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             if (cons) {          // move, boxes (with a cutoff), force, close: 3 launches, 4 under a cutoff
                 GRAPPA_LAUNCH(ms_move_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, cn);
                 if (c) ms_launch_boxes(st, nb, q, w, n_items);
-                ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, fx, n_items, w.cfail);
+                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, w.cfail);
+                if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, true);
                 msc_launch_close(st, q, w, cn, mass, 1, n_items);
             } else {
                 if (c) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
                 else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-                ms_launch_force(st, mm, nb, c, q, w, mass, k.hk, fx, n_items);
+                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items);
+                if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, false);
             }
         }
-        if (due && (frames_epot || frames_ekin)) {
-            if (frames_epot) {
-                const int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
+        if (due && (frames_epot || frames_ekin || frames_esolv)) {
+            const bool terms = frames_epot || (gb && frames_esolv);
+            if (terms) {          // (a frame that asks for the solvent's energy alone does not need the six terms)
+                int erc = frames_epot ? ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w) : GRAPPA_OK;
+                if (erc == GRAPPA_OK && gb)
+                    erc = steps_gb_terms_at(stream, mm, nb, gb->opts, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
                 if (erc != GRAPPA_OK) return erc;
             }
             MsOutArgs a = ms_out_args(mm, nb, q, w);
-            a.final = 0, a.with_epot = frames_epot != nullptr;
+            a.final = 0, a.with_epot = terms && frames_epot != nullptr;
             a.epot = frames_epot ? frames_epot + f * bc : nullptr, a.ekin = frames_ekin ? frames_ekin + f * bc : nullptr;
             if (cons) GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
             else GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
+            if (gb && terms) {
+                float* fe = frames_esolv ? frames_esolv + f * bc : nullptr;
+                if (cons) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
+                else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
+            }
         }
     }
     return grappa_launch_status();
@@ -850,14 +1004,18 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
 
 int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const int* table_dev,
               int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
-              int* status, const grappa_md_cons* cons = nullptr) {
+              int* status, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, float* esolv = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    MsGbWs gw = {};
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
+    int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
+    if (erc == GRAPPA_OK && gb)
+        erc = steps_gb_terms_at(stream, mm, nb, gb->opts, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
     if (erc != GRAPPA_OK) return erc;
     MsOutArgs a = ms_out_args(mm, nb, rs_geom(mm, table_dev, n_blocks), w);
     a.final = 1, a.with_epot = 1;
@@ -868,6 +1026,10 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
         GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
     } else {
         GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    }
+    if (gb) {
+        if (cons) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
+        else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
     }
     return grappa_launch_status();
 }
@@ -989,4 +1151,67 @@ extern "C" int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_des
     if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
                      cons);
+}
+
+// with the GB/SA implicit solvent: gb == NULL is the call above, with its launches and its bits.  A cutoff together with the solvent, a
+// solvent without nb (it carries the charges), refused options or NULL tables: GRAPPA_ERR_ARG before anything else is looked at.
+namespace {
+// GRAPPA_OK: a solvent to run with (g filled); 1: none, forward; < 0: refused
+int ms_gb_check(const grappa_gb_desc* gb, const grappa_nb_desc* nb, const grappa_nb_cut* cut, MsGb& g) {
+    if (!gb) return 1;
+    if (cut || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k)) return GRAPPA_ERR_ARG;
+    g.opts = gb;
+    return GRAPPA_OK;
+}
+}  // namespace
+
+extern "C" size_t grappa_md_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks, int K) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
+    return ms_gb_layout(nullptr, ms_layout(nullptr, N, C, B, n_blocks, false, K > 0).total, N, C, B, n_blocks).total;
+}
+
+extern "C" int grappa_md_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                           const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
+                                           const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
+                                           int n_blocks, void* ws, size_t ws_bytes) {
+    MsGb g;
+    const int gc = ms_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1) return grappa_md_steps_init_cons_f32(stream, mm, nb, cut, o, cons, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_init(stream, mm, nb, nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cc == 1 ? nullptr : cons, &g);
+}
+
+extern "C" int grappa_md_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                          const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
+                                          const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                          size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin,
+                                          float* frames_esolv) {
+    MsGb g;
+    const int gc = ms_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1)
+        return grappa_md_steps_run_cons_f32(stream, mm, nb, cut, o, cons, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                                            frames_xyz, frames_epot, frames_ekin);
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_run(stream, mm, nb, nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz, frames_epot,
+                  frames_ekin, cc == 1 ? nullptr : cons, &g, frames_esolv);
+}
+
+extern "C" int grappa_md_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                             const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const int* table_dev,
+                                             int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot,
+                                             float* ekin, int* steps, int* status, float* esolv) {
+    MsGb g;
+    const int gc = ms_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1)
+        return grappa_md_steps_finish_cons_f32(stream, mm, nb, cut, o, cons, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin,
+                                               steps, status);
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
+                     cc == 1 ? nullptr : cons, &g, esolv);
 }

@@ -57,6 +57,17 @@ __device__ inline bool rs_item(const RsGeom& q, RsItem& r) {
     return true;
 }
 
+constexpr int RS_RUNNING = -1;           // status in the workspace of a stepwise path while an item runs
+
+// which of the item's conformations still run -> run[0 .. nc); false if none does.  One barrier.
+__device__ inline bool rs_running(const RsItem& r, int C, const int* __restrict__ status, int* run) {
+    if ((int)threadIdx.x < r.nc) run[threadIdx.x] = status[(size_t)r.mol * C + r.c0 + threadIdx.x] == RS_RUNNING;
+    __syncthreads();
+    int any = 0;
+    for (int cc = 0; cc < r.nc; ++cc) any |= run[cc];
+    return any != 0;
+}
+
 // the j-tiles of the item's molecule, and the molecule's first block (tile jt of the molecule is the atoms of block nb_first_block + jt)
 __device__ inline int nb_tiles(const RsItem& r) { return (r.m1 - r.m0 + NB_TJ - 1) / NB_TJ; }
 __device__ inline int nb_first_block(const RsItem& r) { return r.blk - (r.i0 - r.m0) / NB_T; }

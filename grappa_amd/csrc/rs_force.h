@@ -18,16 +18,7 @@
 
 namespace {
 
-constexpr int RS_RUNNING = -1;           // status in the workspace while an item runs
-
-// which of the item's conformations still run -> run[0 .. nc); false if none does.  One barrier.
-__device__ inline bool rs_running(const RsItem& r, int C, const int* __restrict__ status, int* run) {
-    if ((int)threadIdx.x < r.nc) run[threadIdx.x] = status[(size_t)r.mol * C + r.c0 + threadIdx.x] == RS_RUNNING;
-    __syncthreads();
-    int any = 0;
-    for (int cc = 0; cc < r.nc; ++cc) any |= run[cc];
-    return any != 0;
-}
+// (RS_RUNNING and rs_running, the stopped-conformation mask of an item: csrc/nb_plan.h)
 
 inline RsGeom rs_geom(const grappa_mm_desc* mm, const int* table_dev, int n_blocks) {
     RsGeom q;
@@ -138,6 +129,16 @@ inline int steps_terms_at(void* stream, const grappa_mm_desc* mm, const grappa_n
     float* te = terms + 4 * (size_t)mm->B * mm->C;
     if (cut) return grappa_nonbonded_fwd_cut_f32(stream, &ne, cut, table_dev, n_items, n_blocks, e_nb, te, nullptr, nullptr, nbws, nbws_bytes);
     return grappa_nonbonded_fwd_planned_f32(stream, &ne, table_dev, n_items, n_blocks, e_nb, te, nullptr, nbws, nbws_bytes);
+}
+
+// The two terms of the GB/SA implicit solvent at the held coordinates x by the library's own entry: the bits of grappa_gb_obc_fwd_f32
+// there.  e_gb [B,C], terms_gb [2,B,C] (polar, surface area); gbws: that call's workspace, a region of its own.
+inline int steps_gb_terms_at(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_gb_desc* gb, const int* table_dev,
+                             int n_items, int n_blocks, const float* x, float* e_gb, float* terms_gb, void* gbws, size_t gbws_bytes) {
+    grappa_nb_desc ne = *nb;
+    ne.xyz = x;
+    ne.atom_molptr = mm->atom_molptr;
+    return grappa_gb_obc_fwd_f32(stream, &ne, gb, table_dev, n_items, n_blocks, e_gb, terms_gb, nullptr, nullptr, gbws, gbws_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------ a cutoff on the stepwise paths

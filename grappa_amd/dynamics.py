@@ -1,5 +1,6 @@
 """Langevin molecular dynamics of molecules on the device under the full MM force field: the bonded terms Grappa predicts plus,
-optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all pairs.  Two paths run the same loop:
+optionally, Lennard-Jones + Coulomb (`grappa_amd.nonbonded`), in vacuum with all pairs (or, stepwise, in implicit solvent).  Two paths run
+the same loop:
   fused     one launch of csrc/dynamics.hip (`grappa_md_langevin_f32` through `HipBackend.md_langevin`) runs many steps of every
             (molecule, conformation): one workgroup each, coordinates in LDS, velocities in registers, no host round trip per step.
             Molecules of up to `relax_max_atoms()` atoms.  `stepwise=False` (the default) takes it and refuses a larger molecule.
@@ -23,6 +24,11 @@ csrc/dynamics_cons.hip (`grappa_md_langevin_cons_f32`), at most 256 clusters in 
 through `HipBackend.md_steps_cons`, molecules of any size with any number of clusters, with or without a cutoff; a cluster is
 integrated by the workgroup that holds its centre, and a step is three launches, four under a cutoff -- what a 2 fs step for a protein
 needs.  An atom draws the same noise with and without constraints, on either path.  Rigid water is out of scope.
+
+Implicit solvent (`implicit_solvent=`, `grappa_amd.solvent`): the GB/SA term of Onufriev, Bashford and Case added to the potential, on
+the stepwise path only (`grappa_md_steps_*_gb_f32` through `HipBackend.md_steps_gb`): three more passes of the tiled pair loop behind
+the force launch, a step of five launches, six with constraints.  It needs `nonbonded` (the charges) and the per-atom radii and scales
+(`gb=`), goes with constraints and not with a cutoff; `stepwise="auto"` goes stepwise whenever it is given.
 
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
@@ -115,6 +121,8 @@ class MDResult:
     frames: object = None
     frame_potential_energy: object = None
     frame_kinetic_energy: object = None
+    esolv: object = None              # with an implicit solvent: its part of potential_energy, shaped like it; else None
+    frames_esolv: object = None       # ... and of frame_potential_energy
 
 
 def _steps_take_constraints() -> bool:
@@ -147,7 +155,7 @@ def _host_keys(keys, seed, B):
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
                    offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, cutoff=None,
-                   **opts) -> MDResult:
+                   implicit_solvent=None, gb=None, **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -170,11 +178,31 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     whose frozen leaves alone number four is refused (ValueError): they over-determine it.
     cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls made are exactly those without this argument):
     see the module text.  It needs `nonbonded` and the stepwise path: "auto" then goes stepwise whatever the sizes, stepwise=False is
-    refused; constraints go with it."""
+    refused; constraints go with it.
+    implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum, the calls made are exactly those without
+    this argument) -- the GB/SA term of `grappa_amd.solvent` added to the potential, with gb, the batch's `grappa_amd.solvent.GBBatch`
+    on the graph's device (radius and scale per atom).  It needs `nonbonded` (the charges) and the stepwise path: "auto" then goes
+    stepwise whatever the sizes, stepwise=False is refused; constraints go with it, a cutoff does not (ValueError).  The result's
+    potential energies include the solvent term; `esolv` / `frames_esolv` hold it alone."""
     from .backend import get_backend
+    from .solvent import GBBatch, as_implicit_solvent
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
     cutoff = as_cutoff(cutoff)
+    solvent = as_implicit_solvent(implicit_solvent)
+    if solvent is not None:
+        if cutoff is not None:
+            raise ValueError("simulate: an implicit solvent under a cutoff is not implemented: pass one of the two")
+        if nonbonded is None:
+            raise ValueError("simulate: an implicit solvent needs the nonbonded parameters (nonbonded=): they carry the charges")
+        if stepwise is False:
+            raise ValueError('simulate: an implicit solvent runs on the stepwise path only: pass stepwise="auto" (or True)')
+        if not isinstance(gb, GBBatch):
+            raise TypeError(f"simulate: an implicit solvent needs gb=, the batch's GBBatch, got {type(gb).__name__}")
+        if getattr(get_backend(), "md_steps_gb", None) is None:
+            raise ValueError("simulate: the backend has no implicit solvent (md_steps_gb)")
+    elif gb is not None:
+        raise ValueError("simulate: gb= needs implicit_solvent=")
     if cutoff is not None:
         if nonbonded is None:
             raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
@@ -194,7 +222,11 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if above and stepwise is False:
         raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
                          f"(stepwise=True or stepwise='auto' runs molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None))
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None))
+    if solvent is not None:
+        if gb.counts != list(counts):
+            raise ValueError(f"the GB parameters describe molecules of {gb.counts} atoms, the batch has {list(counts)}")
+        gb.check_offset(solvent.offset)          # (the batch may have been checked against another offset than the solvent's)
     if constraints is not None:
         from .constraints import ConstraintBatch
         if not isinstance(constraints, ConstraintBatch):
@@ -234,6 +266,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if F:
         nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)      # noqa: E731
         frames, fe, fk = nan(F, N, C, 3), nan(F, B, C), nan(F, B, C)
+    es = f32(B, C) if solvent is not None else None
+    fs = torch.full((F, B, C), float("nan"), dtype=torch.float32, device=dev) if solvent is not None and F else None
     # one call of a seam runs `seg` steps: a launch of the fused kernel, or init / run calls of at most `chunk` steps / finish of the
     # stepwise path, whose options carry the library's cap on n_steps too; calls continue one another bit for bit
     seg = chunk if not use_steps else (MAX_STEPS_PER_LAUNCH // every * every if every > 0 else MAX_STEPS_PER_LAUNCH)
@@ -258,7 +292,11 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         args = (plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin, steps, status)
         kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
-        if use_steps and constraints is not None:
+        if solvent is not None:
+            get_backend().md_steps_gb(*args, steps_per_call=chunk, **kw, constraints=constraints,
+                                      constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
+                                      frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None)
+        elif use_steps and constraints is not None:
             get_backend().md_steps_cons(*args, steps_per_call=chunk, **kw, **({} if cutoff is None else {"cutoff": cutoff}),
                                         constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
         elif use_steps:
@@ -276,35 +314,54 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
             alive = ~held["dead"]
             atoms = alive[atom_item][:, :, None]
             total += torch.where(alive, steps, torch.zeros_like(steps))
-            for name, new, mask in (("x", x_out, atoms), ("v", v_out, atoms), ("epot", epot, alive), ("ekin", ekin, alive), ("status", status, alive)):
+            for name, new, mask in (("x", x_out, atoms), ("v", v_out, atoms), ("epot", epot, alive), ("ekin", ekin, alive), ("status", status, alive)) \
+                    + ((("esolv", es, alive),) if es is not None else ()):
                 held[name] = torch.where(mask, new, held[name]) if name in held else new.clone()
             if f1 > f0 and launch > 0:
                 nanf = torch.full((), float("nan"), dtype=torch.float32, device=dev)
                 frames[f0:f1] = torch.where(atoms[None], frames[f0:f1], nanf)
                 fe[f0:f1], fk[f0:f1] = torch.where(alive[None], fe[f0:f1], nanf), torch.where(alive[None], fk[f0:f1], nanf)
+                if fs is not None:
+                    fs[f0:f1] = torch.where(alive[None], fs[f0:f1], nanf)
             held["dead"] = held["dead"] | (alive & (status >= 4))
         x_in, v_in, done, launch = x_out, v_out, done + n, launch + 1
         if done >= n_steps:
             break
     if held is not None:
         x_in, v_in, epot, ekin, status = held["x"], held["v"], held["epot"], held["ekin"], held["status"]
+        es = held.get("esolv", es)
     temperature = 2.0 * ekin / (3.0 * KB * n_moving) if constraints is None else 2.0 * ekin / (KB * dof.clamp_min(1.0))
-    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk)
+    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs)
 
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
              seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, constraints=None,
-             constrain_start: bool = True, cutoff=None, **opts) -> MDResult:
+             constrain_start: bool = True, cutoff=None, implicit_solvent=None, gb=None, **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
     (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  stepwise: see `simulate_graph`
     (the stepwise path takes a molecule of any size).  constraints: the molecule's `grappa_amd.constraints.Constraints` in the order of
-    `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`.  cutoff: see `simulate_graph`."""
+    `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`.  cutoff: see `simulate_graph`.
+    implicit_solvent: see `simulate_graph`; gb: the molecule's `grappa_amd.solvent.GBParameters` in the order of `parameters.atoms`."""
+    from .solvent import GBBatch, GBParameters, as_implicit_solvent
     md_options(**opts)
     _stepwise_options(stepwise, 1)
     extra = {}
     cutoff = as_cutoff(cutoff)
+    solvent = as_implicit_solvent(implicit_solvent)
+    if solvent is not None:
+        if cutoff is not None:
+            raise ValueError("simulate: an implicit solvent under a cutoff is not implemented: pass one of the two")
+        if nonbonded is None:
+            raise ValueError("simulate: an implicit solvent needs the nonbonded parameters (nonbonded=): they carry the charges")
+        if stepwise is False:
+            raise ValueError('simulate: an implicit solvent runs on the stepwise path only: pass stepwise="auto" (or True)')
+        if not isinstance(gb, GBParameters):
+            raise TypeError(f"simulate: an implicit solvent needs gb=, the molecule's GBParameters, got {type(gb).__name__}")
+        extra.update(implicit_solvent=solvent, gb=GBBatch([gb], solvent.offset).to(device))
+    elif gb is not None:
+        raise ValueError("simulate: gb= needs implicit_solvent=")
     if cutoff is not None:
         if nonbonded is None:
             raise ValueError("simulate: a cutoff needs the nonbonded parameters (nonbonded=)")
@@ -341,4 +398,5 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
     has = r.frames is not None
     return MDResult(confs(r.xyz), confs(r.velocities), np64(r.potential_energy)[0], np64(r.kinetic_energy)[0], np64(r.temperature)[0],
                     r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0], np64(r.frames).transpose(2, 0, 1, 3) if has else None,
-                    np64(r.frame_potential_energy)[:, 0].T if has else None, np64(r.frame_kinetic_energy)[:, 0].T if has else None)
+                    np64(r.frame_potential_energy)[:, 0].T if has else None, np64(r.frame_kinetic_energy)[:, 0].T if has else None,
+                    np64(r.esolv)[0] if r.esolv is not None else None, np64(r.frames_esolv)[:, 0].T if r.frames_esolv is not None else None)

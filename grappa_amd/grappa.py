@@ -74,7 +74,7 @@ class Grappa:
         from .relax import torsion_scan
         return torsion_scan(self.predict(molecule), xyz, dihedral, angles, nonbonded, device=self.device, **kw)
 
-    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, **kw):
+    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, implicit_solvent=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
         the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
@@ -85,10 +85,20 @@ class Grappa:
         (`constraints="h-bonds", stepwise="auto", cutoff=9.0`: a protein at 2 fs steps).
         cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom (None: all pairs): the nonbonded term with a cutoff and a
         reaction field on the stepwise path, which skips the atom tiles beyond it -- what makes a protein fast, not only movable; it
-        needs `nonbonded` and stepwise="auto" (or True)"""
+        needs `nonbonded` and stepwise="auto" (or True).
+        implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum): the GB/SA term of
+        `grappa_amd.solvent` with the mbondi2 radii and OBC screening factors of the molecule's elements and bonds
+        (`GBParameters.from_elements`; gb= in **kw overrides them); it needs `nonbonded` and stepwise="auto" (or True), goes with
+        constraints and not with a cutoff (`implicit_solvent="obc2", constraints="h-bonds", stepwise="auto"`)"""
         from .dynamics import simulate
         if cutoff is not None:
             kw = {**kw, "cutoff": cutoff}
+        if implicit_solvent is not None:
+            from .solvent import GBParameters
+            kw = {**kw, "implicit_solvent": implicit_solvent}
+            if kw.get("gb") is None:
+                pos = {int(a): i for i, a in enumerate(molecule.atoms)}          # bonds name atoms by id; the tables go by position
+                kw["gb"] = GBParameters.from_elements(molecule.atomic_numbers, [(pos[int(a)], pos[int(b)]) for a, b in molecule.bonds])
         masses = [constants.ATOMIC_MASSES[int(z)] for z in molecule.atomic_numbers]
         parameters = self.predict(molecule)
         if isinstance(constraints, str):

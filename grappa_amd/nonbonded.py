@@ -196,6 +196,15 @@ class NonbondedBatch:
         """atom_molptr as the int32 host tensor the batch was built with, wherever `.to` has put the tables"""
         return self._molptr_host
 
+    def plan_for(self, n_confs: int, device):
+        """the work-item list of these molecules for C = n_confs on `device` (`HipBackend.nonbonded_plan`), made once and kept: what the
+        pair kernels of the nonbonded term and of the implicit solvent (`grappa_amd.solvent`) walk"""
+        from .backend import get_backend
+        plan = self._plans.get(n_confs)
+        if plan is None or (plan[0] is not None and plan[0].device != torch.device(device)):
+            plan = self._plans[n_confs] = get_backend().nonbonded_plan(self._molptr_host, self.N, n_confs, device)
+        return plan
+
     def to(self, device) -> "NonbondedBatch":
         for k in self._TENSORS:
             setattr(self, k, getattr(self, k).to(device))

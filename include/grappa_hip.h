@@ -556,6 +556,49 @@ int grappa_nonbonded_fwd_cut_f32(void* stream, const grappa_nb_desc* d, const gr
                                  size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Generalized-Born implicit solvent with a surface-area term (additions to ABI 11): GB/SA in the Onufriev-Bashford-Case form (OpenMM's
+ * GBSAOBCForce), in Angstrom, kcal/mol and elementary charges, K as above.  Per atom: the charge q_i of grappa_nb_desc, a radius R_i and
+ * a scale S_i.  GB knows no exceptions and no exclusions: every ordered pair i != j of a molecule counts, bonded or not (of nb only xyz,
+ * charge and atom_molptr are read).  With o_i = R_i - offset, s_j = S_j o_j, r = |x_i - x_j|:
+ *   I_i   = sum_{j != i} H(r, o_i, s_j);   H = 0 if o_i >= r + s_j, else with L = max(o_i, |r - s_j|), l = 1/L, u = 1/(r + s_j)
+ *           H = l - u + r (u^2 - l^2)/4 + ln(u/l)/(2r) + s_j^2 (l^2 - u^2)/(4r)   [+ 2 (1/o_i - l) if o_i < s_j - r]
+ *   psi_i = o_i I_i / 2;   B_i = 1 / (1/o_i - tanh(alpha psi - beta psi^2 + gamma psi^3) / R_i)          (the Born radius)
+ *   E_pol = -(K/2) (1/eps_in - 1/eps_out) sum_{i,j, i = j included} q_i q_j / f_ij,   f_ij = sqrt(r^2 + B_i B_j exp(-r^2 / (4 B_i B_j)))
+ *   E_sa  = sum_i 4 pi surface_tension (R_i + probe)^2 (R_i / B_i)^6
+ * obc2 is (alpha, beta, gamma) = (1, 0.8, 4.85), obc1 is (0.8, 0, 2.909125).  grad = +d(E_pol + E_sa)/dxyz, exactly: the part at fixed
+ * B, the chain through B_i into every r_ij of its own integral, and the chain through B_j into the same r_ij with the roles swapped.
+ * dH/dr = -(l^2 - u^2)(1 + s_j^2/r^2)/4 - ln(u/l)/(2 r^2) on every branch (H is stationary in l and u where they move with r); at the
+ * three branch borders, where H has a kink, one of the two one-sided values.
+ * Three passes over the work items of grappa_nonbonded_plan (planned form only; table and ws 16-byte aligned), each pass a launch,
+ * because a pass reads what EVERY item of the one before has written: born (I_i -> B_i and dB_i/dI_i), pair (the 1/f sums -> the
+ * gradient at fixed B, dE/dB_i, both energies per block in double), chain (the two chain parts, added to the gradient by its owner);
+ * then the blocks' energies are added per molecule.  4 launches, 3 with grad == NULL (no chain pass).  Fixed-order sums, no atomics,
+ * one writer per word and launch: same input, same bits, and a molecule's results do not depend on its place in the batch.
+ * Arithmetic: fp32; 1/x and 1/sqrt(x) are the hardware's approximations with one Newton step (half an ulp), exp and log the
+ * library's 1-ulp expf and logf, tanh as (1 - e)/(1 + e) and 1 - tanh^2 as 4 e/(1 + e)^2 from ONE e = expf(-2 |.|), so that the
+ * derivative keeps its relative accuracy where tanh saturates.  r = 0 between two distinct atoms or a NaN coordinate gives a
+ * non-finite gradient.  term_energy[2,B,C] = E_pol, E_sa; born[N,C] = B_i; each may be NULL: not written.
+ * GRAPPA_ERR_ARG, nothing launched and nothing written: a NULL required pointer (nb, nb->xyz, charge, atom_molptr, gb, radius, scale,
+ * energy, table_dev, ws), negative sizes, n_blocks > N / GRAPPA_NB_IBLOCK + B, a table or workspace that is not 16-byte aligned,
+ * options that are not finite, eps_in or eps_out <= 0, surface_tension < 0, probe < 0.  ws_bytes below
+ * grappa_gb_obc_workspace_bytes: GRAPPA_ERR_WORKSPACE.  radius and scale are device memory, which the host cannot read: an atom with
+ * radius <= offset or scale <= 0 (or either non-finite) makes every result of its molecule NaN -- the Python layer refuses such
+ * parameters before anything is uploaded.  A table made for another batch is walked away from item by item, as in the calls above.
+ * N == 0, C == 0 or B == 0: returns 0 without a launch.  Not here: a cutoff or tile pruning, HCT / GBn, a salt term. */
+typedef struct grappa_gb_desc {
+    const float *radius, *scale;      /* [N], device: R_i in A (> offset), S_i (> 0) */
+    float offset;                     /* A; OpenMM: 0.09 */
+    float alpha, beta, gamma;
+    float eps_in, eps_out;            /* solute and solvent dielectric, > 0 */
+    float surface_tension;            /* kcal/mol/A^2, >= 0; OpenMM's 2.25936 kJ/mol/nm^2 = 0.0054 */
+    float probe;                      /* A, >= 0; 1.4 */
+} grappa_gb_desc;
+size_t grappa_gb_obc_workspace_bytes(int N, int C, int n_blocks);
+int grappa_gb_obc_fwd_f32(void* stream, const grappa_nb_desc* nb, const grappa_gb_desc* gb, const int* table_dev, int n_items, int n_blocks,
+                          float* energy /*[B,C]*/, float* term_energy /*[2,B,C] polar, SA; may be NULL*/, float* grad /*[N,C,3]; may be NULL*/,
+                          float* born /*[N,C]; may be NULL*/, void* ws, size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Relaxation under the full MM force field (additions to ABI 11): FIRE (Bitzek et al. 2006) with unit masses and semi-implicit Euler,
  * one workgroup per (molecule b, conformation c), the whole minimisation in one launch.  E = the bonded energy of
  * grappa_mm_energy_fwd_f32 (+ the energy of grappa_nonbonded_fwd_f32 if nb != NULL; nb->xyz is ignored), g = +dE/dxyz, start = mm->xyz:
@@ -931,6 +974,34 @@ int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, cons
                                     const grappa_md_opts* o, const grappa_md_cons* cons, const int* table_dev, int n_items, int n_blocks,
                                     void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
                                     int* status);
+
+/* The stepwise dynamics in GB/SA implicit solvent (additions to ABI 11): the _cons_ calls with `const grappa_gb_desc* gb` after cons.
+ * gb == NULL: each forwards to its _cons_ call -- the launches and the bits of a run without solvent.  With gb the potential is the one
+ * above plus E_pol + E_sa of grappa_gb_obc_fwd_f32 (nb is required: it carries the charges; its exceptions do not touch the solvent
+ * term) and the force launch is followed by the three passes of that entry under the stopped-conformation mask:
+ *   step : move, force (as it is, without its closing kick), born, pair, chain -- the chain launch's epilogue adds the three gradients in
+ *          the order (bonded + nonbonded) + fixed-B part + chain parts, gives the closing kick, and tests the sum: a non-finite sum ends
+ *          the item with status 2 as a non-finite force gradient does.  5 launches, 6 with constraints (close follows); init gains 3.
+ *          The force kernels are the ones a run without solvent launches: nothing of them was changed for the solvent.
+ * epot includes the solvent term: the eight terms (six as before, E_pol, E_sa) added in double in that order, each from the library's
+ * own energy entry at the held coordinates; esolv [B,C] / frames_esolv [F,B,C] (NULL: not written) = E_pol + E_sa alone, written where
+ * epot is.  The workspace is grappa_md_steps_gb_workspace_bytes (the words of a run without solvent first, the solvent's behind them).
+ * GRAPPA_ERR_ARG before anything else is looked at: cut != NULL together with gb (GB under a cutoff is not implemented), nb == NULL,
+ * NULL radius or scale, options grappa_gb_obc_fwd_f32 refuses.  r = 0 between two distinct atoms (bonded or not: GB has no exclusions)
+ * gives status 2.  Not here: the fused dynamics, the minimisers, restraints. */
+size_t grappa_md_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks, int K);
+int grappa_md_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
+                                const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks,
+                                void* ws, size_t ws_bytes);
+int grappa_md_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                               const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
+                               const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+                               int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin, float* frames_esolv);
+int grappa_md_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                  const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const int* table_dev,
+                                  int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot,
+                                  float* ekin, int* steps, int* status, float* esolv);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

@@ -35,6 +35,15 @@ and the time per step, constrained over unconstrained: below 2 -- the ratio of t
 stopped early is marked: its time per step counts launches that did nothing.
 
     python tools/md_steps_bench.py --constraints [--cutoff 9] [--out profiles/md_steps_cons_bench.txt]
+
+With --implicit-solvent MODEL (obc2, obc1) the tool measures the GB/SA implicit solvent on the stepwise path instead (same protocol):
+per workload, in the same visit, the all-pairs vacuum step of this tree against the same run with the solvent (every atom with carbon's
+radius 1.7 A and scale 0.72: the cost does not depend on the values), all five times of each side, the ratio of the times per step
+and the library launches.  This mode has a fourth workload, t4l: T4 lysozyme (grappa_amd/data/t4_lysozyme.npz: 2,634 atoms with their
+elements, bonds, template charges and coordinates), bonded parameters made the way the chains' are (bonds and angles at rest in the
+structure, random small torsions), Lennard-Jones parameters by element, and the mbondi2 radii and OBC scales of its elements.
+
+    python tools/md_steps_bench.py --implicit-solvent obc2 [--out profiles/md_steps_gb_bench.txt]
 """
 import argparse
 import datetime
@@ -52,9 +61,11 @@ from md_bench import OPTS, Composed, _batch, _timed      # noqa: E402
 WORKLOADS = ("pool", "mid", "big")
 SIDES = {"pool": ("fused", "stepwise", "composed", "agreement"), "mid": ("stepwise", "composed"), "big": ("stepwise", "composed")}
 CUT_SIDES = ("stepwise", "cut", "cut_noprune", "tiles")
+GB_SIDES = ("stepwise", "gb")
+GB_WORKLOADS = ("pool", "mid", "t4l", "big")
 CONS_SIDES = ("free_1fs", "cons_2fs", "cons_1fs")
 CONS_DT = {"free_1fs": 0.001, "cons_2fs": 0.002, "cons_1fs": 0.001}
-STAGES = ["device"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:]] + \
+STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
          [f"{w}:{s}:{p}" for w in WORKLOADS[1:] for s in CONS_SIDES for p in ("pairs", "cut")]
 
 STAGE_LIMIT = 300      # seconds, every stage
@@ -70,9 +81,38 @@ def _workload(args, which):
         return g, nb, masses, args.confs, args.steps
     from relax_steps_bench import chain_graph
     from grappa_amd.nonbonded import NonbondedBatch
+    if which == "t4l":
+        gh, nbp, masses, _ = _t4l()
+        return gh.to("cuda"), NonbondedBatch([nbp]).to("cuda"), masses, 1, args.steps
     n = args.mid_atoms if which == "mid" else args.big_atoms
     gh, nbp = chain_graph(n)
     return gh.to("cuda"), NonbondedBatch([nbp]).to("cuda"), np.full(n, CARBON, dtype=np.float32), 1, args.steps if which == "mid" else args.big_steps
+
+
+def _t4l():
+    """T4 lysozyme -> (graph with k / eq at the tuple levels and xyz (n, 1, 3), NonbondedParameters, masses, GBParameters), on the host"""
+    import numpy as np
+    import torch
+    from grappa_amd import _hostlib, constants
+    from grappa_amd.datasets import _T4_PATH
+    from grappa_amd.nonbonded import NonbondedParameters
+    from grappa_amd.parameters import Parameters
+    from grappa_amd.relax import graph_from_parameters
+    from grappa_amd.solvent import GBParameters
+    d = np.load(_T4_PATH)
+    z, bonds, xyz = d["z"].astype(np.int64), d["bonds"].astype(np.int64).reshape(-1, 2), d["xyz"].astype(np.float64)
+    angles, propers = (np.asarray(a, dtype=np.int64) for a in _hostlib.enumerate_tuples(bonds))
+    angles, propers = angles.reshape(-1, 3), propers.reshape(-1, 4)
+    x = torch.from_numpy(xyz)
+    u, v = x[angles[:, 0]] - x[angles[:, 1]], x[angles[:, 2]] - x[angles[:, 1]]
+    theta = torch.atan2(torch.cross(u, v, dim=-1).norm(dim=-1), (u * v).sum(-1))
+    ks = np.random.default_rng(2).uniform(-1, 1, size=(propers.shape[0], 3)) * np.array([1.0, 0.5, 0.3])
+    p = Parameters(atoms=np.arange(len(z)), bonds=bonds, bond_k=np.full(len(bonds), 500.0), bond_eq=(x[bonds[:, 0]] - x[bonds[:, 1]]).norm(dim=-1).numpy(),
+                   angles=angles, angle_k=np.full(len(angles), 100.0), angle_eq=theta.numpy(), propers=propers, proper_ks=np.abs(ks),
+                   proper_phases=np.where(ks >= 0, 0.0, np.pi), impropers=None, improper_ks=None, improper_phases=None)
+    nbp = NonbondedParameters.from_bonds(bonds, d["charges"].astype(np.float64), np.where(z == 1, 1.1, 3.3), np.where(z == 1, 0.016, 0.1))
+    masses = np.array([constants.ATOMIC_MASSES[int(a)] for a in z], dtype=np.float32)
+    return graph_from_parameters(p, xyz[None].astype(np.float32)), nbp, masses, GBParameters.from_elements(z, bonds)
 
 
 def _leaves(n, leaf_mass):
@@ -160,11 +200,17 @@ def stage(args):
             be.nonbonded(x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps, e, None, None,
                          plan=plan, cutoff=Cutoff(args.cutoff, args.switch or None, prune=prune), tiles=t[prune])
         out["items"], out["tiles"], out["all_tiles"] = int(plan[1]), int(t[True].sum()), int(t[False].sum())
-    elif side in ("fused", "stepwise", "cut", "cut_noprune"):
+    elif side in ("fused", "stepwise", "cut", "cut_noprune", "gb"):
         sw = side != "fused"
         if side.startswith("cut"):
             plain = sim
             sim = lambda n, stepwise, **kw: plain(n, stepwise, cutoff=cut, **kw)      # noqa: E731
+        if side == "gb":
+            import numpy as np
+            from grappa_amd.solvent import GBBatch, GBParameters
+            gbb = GBBatch([_t4l()[3]] if which == "t4l" else [GBParameters(np.full(int(n), 1.7), np.full(int(n), 0.72)) for n in counts]).to("cuda")
+            plain = sim
+            sim = lambda n, stepwise, **kw: plain(n, stepwise, implicit_solvent=args.implicit_solvent, gb=gbb, **kw)      # noqa: E731
         n0 = be.lib.grappa_launch_count(0)
         r = sim(steps, sw)
         torch.cuda.synchronize()
@@ -172,7 +218,7 @@ def stage(args):
         # (an item that meets a non-finite gradient stops early: the rate counts the steps that were run)
         out["item_steps"], out["stopped"] = int(r.steps.sum()), int((r.status != 0).sum())
         out["median_us"], out["min_us"] = _timed(lambda: sim(steps, sw), args.reps)
-        if args.cutoff:          # every run of the five: the acceptance compares the slowest of one side with the fastest of another
+        if args.cutoff or args.implicit_solvent:          # every run of the five: the acceptance compares the slowest of one side with the fastest of another
             out["all_us"] = _all_timed(lambda: sim(steps, sw), args.reps)
             out["median_us"], out["min_us"] = float(sorted(out["all_us"])[len(out["all_us"]) // 2]), min(out["all_us"])
     elif side == "composed":
@@ -220,6 +266,7 @@ def main():
     ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
     ap.add_argument("--constraints", action="store_true", help="measure X-H constraints on the stepwise path (see the module text)")
     ap.add_argument("--leaf-mass", type=float, default=CARBON, help="amu; the mass of the leaves with --constraints (the chain's own by default)")
+    ap.add_argument("--implicit-solvent", default="", help="obc2 or obc1: measure the GB/SA implicit solvent on the stepwise path (see the module text)")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -234,7 +281,7 @@ def main():
     def run(name):
         cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
               [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
-                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass")]
+                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass", "implicit_solvent")]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
             sys.stderr.write(p.stdout + p.stderr)
@@ -297,7 +344,20 @@ def main():
             say(f"  cut, prune=1 / all pairs = {rate['cut'] / rate['stepwise']:.2f}x steps/s; cut, prune=0 / all pairs = {rate['cut_noprune'] / rate['stepwise']:.2f}x; "
                 f"slowest pruned run {max(res['cut']['all_us']) / 1e3:.2f} ms, fastest all-pairs run {min(res['stepwise']['all_us']) / 1e3:.2f} ms: "
                 f"{'faster' if max(res['cut']['all_us']) < min(res['stepwise']['all_us']) else 'NOT faster'}")
-    for w in (() if args.cutoff or args.constraints else WORKLOADS):
+    if args.implicit_solvent:
+        say(f"# GB/SA implicit solvent {args.implicit_solvent} on the stepwise path against the all-pairs vacuum step of the same tree; all five run "
+            "times of each side in ms")
+        for w in GB_WORKLOADS:
+            res = {side: run(f"{w}:{side}") for side in GB_SIDES}
+            r = res["stepwise"]
+            say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms ({r['smallest']}..{r['largest']} per molecule), C = {r['confs']}, "
+                f"bonded + nonbonded, dt {OPTS['dt']} ps, {OPTS['temperature']} K, friction {OPTS['friction']} / ps")
+            rate = {}
+            for side, what in (("stepwise", "vacuum"), ("gb", args.implicit_solvent)):
+                rate[side] = report(f"{what:12s}", res[side])
+                say(f"               runs: {', '.join(f'{u / 1e3:.2f}' for u in res[side]['all_us'])} ms")
+            say(f"  time per step, {args.implicit_solvent} / vacuum = {rate['stepwise'] / rate['gb']:.2f}")
+    for w in (() if args.cutoff or args.constraints or args.implicit_solvent else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:
             r = run(f"{w}:{side}")

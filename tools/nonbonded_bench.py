@@ -19,6 +19,12 @@ Device events around single calls, one warm-up call, five timed calls (all five 
 process of its own under a time limit, the parent never initialises the GPU and starts nothing after a stage that fails.
 
     python tools/nonbonded_bench.py --cutoff 10 [--switch 8] [--out profiles/nb_cutoff_bench.txt]
+
+With --gb MODEL (obc2, obc1) the tool measures the GB/SA implicit solvent (csrc/gb_obc.hip through HipBackend.gb_obc) instead, by the same
+protocol at the same three workloads: the planned all-pairs nonbonded kernel (energy, terms, gradient) against the solvent entry with
+and without the gradient (every atom with carbon's radius 1.7 A and scale 0.72: the cost does not depend on the values).
+
+    python tools/nonbonded_bench.py --gb obc2 [--out profiles/gb_bench.txt]
 """
 import argparse
 import json
@@ -163,6 +169,21 @@ def cut_stage(args):
     e_o, t_o, g_o = torch.empty(nb.B, x.shape[1], device="cuda"), torch.empty(2, nb.B, x.shape[1], device="cuda"), torch.empty_like(x)
     tabs = (x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps)
     plan = be.nonbonded_plan(nb.atom_molptr.cpu(), nb.N, x.shape[1], "cuda")
+    if args.gb:
+        from grappa_amd.solvent import ImplicitSolvent
+        opts = ImplicitSolvent(args.gb).as_opts()
+        R, S = torch.full((nb.N,), 1.7, device="cuda"), torch.full((nb.N,), 0.72, device="cuda")
+        br = torch.empty(nb.N, x.shape[1], device="cuda")
+        out = {"molecules": len(params), "atoms": int(n.sum()), "smallest": int(n.min()), "largest": int(n.max()), "confs": int(x.shape[1]), "items": int(plan[1])}
+        n0 = be.lib.grappa_launch_count(0)
+        be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, g_o, br, plan=plan)
+        out["launches"] = int(be.lib.grappa_launch_count(0) - n0)
+        out["all_pairs"] = five(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan))
+        out["gb"] = five(lambda: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, g_o, br, plan=plan))
+        out["gb_energy"] = five(lambda: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, None, None, plan=plan))
+        out["finite"] = bool(torch.isfinite(e_o).all()) and bool(torch.isfinite(g_o).all())
+        print(json.dumps(out))
+        return
     cut = {p: Cutoff(args.cutoff, args.switch or None, prune=p) for p in (True, False)}
     tiles = {p: torch.zeros(plan[1], dtype=torch.int32, device="cuda") for p in (True, False)}
     out = {"molecules": len(params), "atoms": int(n.sum()), "smallest": int(n.min()), "largest": int(n.max()), "confs": int(x.shape[1]), "items": int(plan[1])}
@@ -171,6 +192,41 @@ def cut_stage(args):
     out["cut_noprune"] = five(lambda: be.nonbonded(*tabs, e_o, t_o, g_o, plan=plan, cutoff=cut[False], tiles=tiles[False]))
     out["tiles"], out["all_tiles"] = int(tiles[True].sum()), int(tiles[False].sum())
     print(json.dumps(out))
+
+
+def gb_main(args):
+    import datetime
+    lines = [f"# command: python {' '.join(sys.argv)}", f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}"]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def run(name):
+        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name, f"--gb={args.gb}",
+               f"--mols={args.mols}", f"--confs={args.confs}", f"--mid-atoms={args.mid_atoms}", f"--chain-atoms={args.chain_atoms}"]
+        p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout + p.stderr)
+            sys.exit(f"nonbonded_bench: stage {name} ended with status {p.returncode}; nothing more is started")
+        return json.loads(p.stdout.strip().splitlines()[-1])
+
+    say(f"# device: {run('device')['device']}")
+    say(f"# GB/SA implicit solvent {args.gb} against the planned all-pairs nonbonded kernel, both into preallocated outputs; device events around "
+        "single calls, one warm-up call, five timed calls: median, all five; every workload a process of its own; this file is the tool's output, unedited")
+    for w in CUT_WORKLOADS:
+        r = run(w)
+        say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms ({r['smallest']}..{r['largest']} per molecule), C = {r['confs']}, {r['items']} work items; "
+            f"the solvent call makes {r['launches']} launches; outputs finite: {r['finite']}")
+        med = {}
+        for key, what in (("all_pairs", "LJ + Coulomb"), ("gb", f"{args.gb}"), ("gb_energy", f"{args.gb}, no gradient")):
+            med[key] = float(np.median(r[key]))
+            say(f"  {what:20s} {med[key]:12.1f} us  {1e6 / med[key]:10.1f} calls/s   runs: {', '.join(f'{u:.1f}' for u in r[key])} us")
+        say(f"  time per call, {args.gb} / LJ + Coulomb = {med['gb'] / med['all_pairs']:.2f}; without the gradient {med['gb_energy'] / med['all_pairs']:.2f}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def cut_main(args):
@@ -223,10 +279,13 @@ def main():
     ap.add_argument("--mid-atoms", type=int, default=513)
     ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
     ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
+    ap.add_argument("--gb", default="", help="obc2 or obc1: measure the GB/SA implicit solvent (see the module text)")
     ap.add_argument("--stage", default=None, choices=("device",) + CUT_WORKLOADS)
     args = ap.parse_args()
     if args.stage:
         return cut_stage(args)
+    if args.gb:
+        return gb_main(args)
     if args.cutoff:
         return cut_main(args)
     if not torch.cuda.is_available():
