@@ -75,7 +75,17 @@ __device__ inline unsigned a_row_amax(const grappa_gemm_desc& d, int m) {
     return v;
 }
 
-struct Quad { float x[4]; unsigned rm; };      // rm: pair-format sources only (the token row's largest magnitude); dead otherwise
+struct Quad { float x[4]; unsigned rm; };      // rm: pair-format sources that load their token's maximum per quad (the token row's largest magnitude); dead otherwise
+// Token maxima of a pair-format operand (ABI 8): per quad (a dword load whose address is the same in all the lanes of a token row, and a register
+// in each of the AHEAD sets), or once per wavefront and slab (load_token_maxima / token_max_of).  Measured (profiles/wgrad_group_items.txt): the
+// 256-row A operand, whose 64 lanes of a wavefront share ONE token, gains 2.5 % from the slab form (two loads become one, the rescale factors scalar
+// work); the 128-row B operand, one load per quad already and two tokens per wavefront, LOSES 5 % to it (two v_readlane and a select per quad).
+#ifndef GB_ROWMAX_A_SLAB
+#define GB_ROWMAX_A_SLAB 1              // 0 = per quad (the other leg of the A/B)
+#endif
+#ifndef GB_ROWMAX_B_SLAB
+#define GB_ROWMAX_B_SLAB 0              // 1 = B's maxima ride in lanes 16 .. 31 of A's load (or in a load of their own)
+#endif
 
 // slab element (row, kq..kq+3) owned by this thread for quad slot j of an operand with ROWS rows.
 // K-contiguous source: 4 lanes cover the 64 bytes of one row; k-major source: 64 lanes cover 64 consecutive rows of one k.
@@ -99,6 +109,23 @@ __device__ inline void quad_coords(int j, int& row, int& kq) {
 // bytes of one piece of an operand in an LDS stage: [row][16 k + pad] (ROWB per row), or -- KMV -- [k][row] (transposing reads)
 template <int ROWS, bool KMV> struct PieceBytes { static constexpr int value = KMV ? SK * ROWS * 2 : ROWS * ROWB; };
 
+// The operands are read through pointers in the GLOBAL address space, said so explicitly (as_global).  A kernel that takes its descriptor
+// as an argument gets that from the compiler; the grouped launch reads its descriptors from device memory, where a pointer is generic to
+// the compiler and every operand load a flat_load -- which counts on lgkmcnt as well as vmcnt and returns out of order, so that the
+// lgkmcnt(0) in front of the first MFMA of a step (the fragment reads) also waited for the global loads issued just before it: the memory
+// latency, exposed once per slab (the main-loop knock-outs of the k-major shapes: profiles/r2_gemm_f16x3_knockouts.txt).
+#ifndef GB_GLOBAL_LOADS
+#define GB_GLOBAL_LOADS 1               // 0 = generic pointers as the descriptor holds them (the other leg of the A/B)
+#endif
+#if GB_GLOBAL_LOADS
+#define GRAPPA_GLOBAL_AS __attribute__((address_space(1)))
+#else
+#define GRAPPA_GLOBAL_AS
+#endif
+typedef float gl_f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned gl_u32x4 __attribute__((ext_vector_type(4)));
+template <typename T> __device__ __forceinline__ const GRAPPA_GLOBAL_AS T* as_global(const T* q) { return (const GRAPPA_GLOBAL_AS T*)q; }
+
 // Loads never wait for their data: out-of-range rows and k are only CLAMPED here (the addresses stay inside the operand);
 // the k tail is zeroed when the slab is split and stored (store_quads<MASK>), AHEAD - 1 steps later.
 template <int NT, int ROWS, bool KCONT, bool VEC, bool KMV = false>
@@ -111,19 +138,19 @@ __device__ inline void load_quads(const float* __restrict__ src, int ld, int row
         if (!KCONT && KMV) {
             // four consecutive rows of one k: the (16-byte padded, host-checked) source row covers round_up(R, 4)
             const int gr = min(row0 + row, ((R + 3) & ~3) - 4);
-            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)(gk < Kend ? gk : 0) * ld + gr);
-            q[j].x[0] = v.x; q[j].x[1] = v.y; q[j].x[2] = v.z; q[j].x[3] = v.w;
+            const gl_f32x4 v = *reinterpret_cast<const GRAPPA_GLOBAL_AS gl_f32x4*>(as_global(src) + (size_t)(gk < Kend ? gk : 0) * ld + gr);
+            q[j].x[0] = v[0]; q[j].x[1] = v[1]; q[j].x[2] = v[2]; q[j].x[3] = v[3];
             continue;
         }
         const int gr = min(row0 + row, R - 1);          // out-of-range rows are clamped: their results are never stored
         if (KCONT && VEC) {
-            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)gr * ld + (gk < Kend ? gk : 0));   // K % 4 == 0 here
-            q[j].x[0] = v.x; q[j].x[1] = v.y; q[j].x[2] = v.z; q[j].x[3] = v.w;
+            const gl_f32x4 v = *reinterpret_cast<const GRAPPA_GLOBAL_AS gl_f32x4*>(as_global(src) + (size_t)gr * ld + (gk < Kend ? gk : 0));   // K % 4 == 0 here
+            q[j].x[0] = v[0]; q[j].x[1] = v[1]; q[j].x[2] = v[2]; q[j].x[3] = v[3];
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int ck = gk + e < Kend ? gk + e : 0;
-                q[j].x[e] = KCONT ? src[(size_t)gr * ld + ck] : src[(size_t)ck * ld + gr];
+                q[j].x[e] = KCONT ? as_global(src)[(size_t)gr * ld + ck] : as_global(src)[(size_t)ck * ld + gr];
             }
         }
     }
@@ -150,7 +177,7 @@ __device__ inline unsigned rescale_h2(unsigned v, unsigned f1, unsigned f2) {
 // segment is a sequence of 64-byte granules [8 HI | 8 HI | 8 LO | 8 LO] of 16 features, so chunk c holds ONE piece (c & 2: LO) of the 8
 // features 16 (c / 4) + 8 (c & 1) .. + 7 -- the 64 lanes of a wavefront read 1 KB of one token row in one instruction (the fp32 path's
 // access pattern; 8-byte HI / LO loads per 4 features measured 10 % slower than the fp32-operand kernel) -- plus the token's maximum
-template <int NT, int ROWS>
+template <int NT, int ROWS, bool PERQ>
 __device__ inline void load_quads_pairs(const uint16_t* __restrict__ src, int ld, const unsigned* __restrict__ rowmax, int row0, int k0, int R, int Kend,
                                         Quad (&q)[ROWS * 4 / NT]) {
 #pragma unroll
@@ -160,17 +187,42 @@ __device__ inline void load_quads_pairs(const uint16_t* __restrict__ src, int ld
         const int c = row >> 2;
         const int gk = k0 + kq < Kend ? k0 + kq : 0;
         const int gran = min((row0 >> 4) + (c >> 2), (R >> 4) - 1);               // granules beyond the operand's rows are clamped (never stored)
-        const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)gk * ld + 32 * gran + 8 * (c & 3));
-        q[j].x[0] = u2f(v.x); q[j].x[1] = u2f(v.y); q[j].x[2] = u2f(v.z); q[j].x[3] = u2f(v.w);
-        q[j].rm = rowmax[gk];
+        const gl_u32x4 v = *reinterpret_cast<const GRAPPA_GLOBAL_AS gl_u32x4*>(as_global(src) + (size_t)gk * ld + 32 * gran + 8 * (c & 3));
+        q[j].x[0] = u2f(v[0]); q[j].x[1] = u2f(v[1]); q[j].x[2] = u2f(v[2]); q[j].x[3] = u2f(v[3]);
+        if (PERQ) q[j].rm = as_global(rowmax)[gk];
     }
+}
+// The token maxima of one slab, once per wavefront and slab: lane t (< 16) receives the maximum of A's token k0 + t, lane 16 + t that of B's
+// (one coalesced dword load; with one operand taking them this way both lane groups read that operand's array; lanes 32 .. 63 repeat lanes
+// 0 .. 31).  Tokens beyond the K range are clamped like the quads' (their slab rows are zeroed when stored).
+template <bool A, bool B>
+__device__ inline unsigned load_token_maxima(const grappa_gemm_desc& d, int k0, int Kend) {
+    const int lane = threadIdx.x & 63, t = lane & 15;
+    const int gk = k0 + t < Kend ? k0 + t : 0;
+    const unsigned* src = (A && B) ? ((lane & 16) ? d.b_rowmax : d.a_rowmax) : (A ? d.a_rowmax : d.b_rowmax);
+    return as_global(src)[gk];
+}
+// ... and the maximum of the token of quad slot j out of them (lane0 = 0: A, 16: B).  The ROWS / 4 lanes that stage one token row are a whole
+// wavefront (ROWS = 256: one v_readlane with a wave-uniform index, and the rescale factors become scalar work) or half of one (ROWS = 128: two
+// and a select) -- quad_coords<.., KMV>: k = (wavefront * 64 + j * NT + lane) / (ROWS / 4)
+template <int NT, int ROWS>
+__device__ inline unsigned token_max_of(unsigned rmv, int lane0, int j) {
+    constexpr int LPT = ROWS / 4;
+    static_assert(LPT == 64 || LPT == 32, "a token row is staged by a whole wavefront or by half of one");
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int t0 = (wave * 64 + j * NT) / LPT;
+    const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)rmv, lane0 + t0);
+    if (LPT == 64) return r0;
+    const unsigned r1 = (unsigned)__builtin_amdgcn_readlane((int)rmv, lane0 + t0 + 1);
+    return (threadIdx.x & 32) ? r1 : r0;
 }
 // do_cs (the A operand of the tile_n == 0 workgroups): the bias gradient rides on the rescaled halves -- cs[0 .. 7] += this thread's piece of
 // its 8 features UNDER THE TENSOR'S SCALE, one v_dot2_f32_f16 per element (HI and LO sums and the scale 2^-s_T meet in the reduction behind
 // the main loop).  (Converting every half back to fp32 under its row's scale -- 3 vector instructions per element on a quarter of the
 // workgroups -- made the whole launch 11 % slower than the fp32-operand kernel: the grid waits for its slowest workgroups.)
-template <int NT, int ROWS, bool MASK>
-__device__ inline void store_quads_pairs(char* __restrict__ opbase, const Quad (&q)[ROWS * 4 / NT], int krem, int e_tensor, bool do_cs, float (&cs)[8]) {
+template <int NT, int ROWS, bool MASK, bool SLAB>
+__device__ inline void store_quads_pairs(char* __restrict__ opbase, const Quad (&q)[ROWS * 4 / NT], unsigned rmv, int lane0, int krem, int e_tensor, bool do_cs,
+                                         float (&cs)[8]) {
     constexpr int PIECE = PieceBytes<ROWS, true>::value;
     half2_t one_zero, zero_one;
     one_zero[0] = (_Float16)1.0f; one_zero[1] = (_Float16)0.0f;
@@ -180,7 +232,8 @@ __device__ inline void store_quads_pairs(char* __restrict__ opbase, const Quad (
         int row, kq;
         quad_coords<NT, ROWS, false, true>(j, row, kq);
         const int c = row >> 2, piece = (c >> 1) & 1, row8 = 16 * (c >> 2) + 8 * (c & 1);
-        const int d = max(e_tensor - (int)((q[j].rm >> 23) & 0xffu), 0), d1 = min(d, 14);
+        const unsigned rm = SLAB ? token_max_of<NT, ROWS>(rmv, lane0, j) : q[j].rm;
+        const int d = max(e_tensor - (int)((rm >> 23) & 0xffu), 0), d1 = min(d, 14);
         const unsigned f1 = pow2_neg_h2(d1), f2 = pow2_neg_h2(d - d1);
         unsigned w[4];
 #pragma unroll
@@ -392,7 +445,7 @@ struct KRange {
 template <int NT, int MODE, int BM, int BN, int WN, bool AK, bool BKC, bool VEC, bool KMV, bool TAIL, int PSRC>
 __device__ inline void pipeline_step(const grappa_gemm_desc& d, char* __restrict__ smem, f32x16 (&acc)[2][BN / WN / 32], int m0, int n0,
                                      const KRange& kr, int s, int wm0, int wn0, int lane, Quad (&la)[BM * 4 / NT], Quad (&lb)[BN * 4 / NT],
-                                     const Quad (&sa)[BM * 4 / NT], const Quad (&sb)[BN * 4 / NT],
+                                     const Quad (&sa)[BM * 4 / NT], const Quad (&sb)[BN * 4 / NT], unsigned& lrm, unsigned srm,
                                      const Frags<Pieces<MODE>::NP, 2, BN / WN / 32>& fc, Frags<Pieces<MODE>::NP, 2, BN / WN / 32>& fn,
                                      float (&cs)[8], bool do_cs, const int (&sha)[BM * 4 / NT][(!AK && KMV) ? 4 : 1],
                                      const int (&shb)[BN * 4 / NT][(!BKC && KMV) ? 4 : 1]) {
@@ -408,20 +461,23 @@ __device__ inline void pipeline_step(const grappa_gemm_desc& d, char* __restrict
     const bool do_load = !TAIL || s + AHEAD < kr.nsteps;
     // the operand is in the pair format (wgrad layout, KMV, H3 only)
     constexpr bool pa_ = (PSRC & 1) != 0, pb_ = (PSRC & 2) != 0;
+    constexpr bool sa_ = pa_ && GB_ROWMAX_A_SLAB, sb_ = pb_ && GB_ROWMAX_B_SLAB;       // token maxima once per wavefront and slab
     if (do_load && !(GB_KNOCK == 3 && !TAIL)) {
-        if constexpr (pa_) load_quads_pairs<NT, BM>(reinterpret_cast<const uint16_t*>(d.A), d.lda, d.a_rowmax, m0, kr.k_of(s + AHEAD), d.M, kr.kend, la);
+        if constexpr (pa_) load_quads_pairs<NT, BM, !sa_>(reinterpret_cast<const uint16_t*>(d.A), d.lda, d.a_rowmax, m0, kr.k_of(s + AHEAD), d.M, kr.kend, la);
         else load_quads<NT, BM, AK, VEC, AV>(d.A, d.lda, m0, kr.k_of(s + AHEAD), d.M, kr.kend, la);
-        if constexpr (pb_) load_quads_pairs<NT, BN>(reinterpret_cast<const uint16_t*>(d.B), d.ldb, d.b_rowmax, n0, kr.k_of(s + AHEAD), d.N, kr.kend, lb);
+        if constexpr (pb_) load_quads_pairs<NT, BN, !sb_>(reinterpret_cast<const uint16_t*>(d.B), d.ldb, d.b_rowmax, n0, kr.k_of(s + AHEAD), d.N, kr.kend, lb);
         else load_quads<NT, BN, BKC, VEC, BV>(d.B, d.ldb, n0, kr.k_of(s + AHEAD), d.N, kr.kend, lb);
+        // (last of the slab's loads: the wait in front of its first use, the token maxima, then covers the slab's data too)
+        if constexpr (sa_ || sb_) lrm = load_token_maxima<sa_, sb_>(d, kr.k_of(s + AHEAD), kr.kend);
     }
     __builtin_amdgcn_sched_barrier(0);
     char* nxt = smem + ((s + 1) & 1) * STAGE;
     mfma_range<MODE, TM, TN, 0, NFIRST>(fc, acc);
     if (do_store && !(GB_KNOCK == 4 && !TAIL)) {
         const int krem = TAIL ? kr.kend - kr.k_of(s + 1) : SK;
-        if constexpr (pa_) store_quads_pairs<NT, BM, TAIL>(nxt, sa, krem, 141 - sha[0][0], !AK && do_cs, cs);
+        if constexpr (pa_) store_quads_pairs<NT, BM, TAIL, sa_>(nxt, sa, srm, 0, krem, 141 - sha[0][0], !AK && do_cs, cs);
         else store_quads<NT, NP, BM, AK, TAIL, Pieces<MODE>::HALF, AV>(nxt, sa, krem, sha);
-        if constexpr (pb_) store_quads_pairs<NT, BN, TAIL>(nxt + NP * PA, sb, krem, 141 - shb[0][0], false, cs);
+        if constexpr (pb_) store_quads_pairs<NT, BN, TAIL, sb_>(nxt + NP * PA, sb, srm, 16, krem, 141 - shb[0][0], false, cs);
         else store_quads<NT, NP, BN, BKC, TAIL, Pieces<MODE>::HALF, BV>(nxt + NP * PA, sb, krem, shb);
         if (!AK && do_cs) {
             if constexpr (!pa_) quad_rowsum<NT, BM, AV, TAIL>(sa, krem, cs);
@@ -455,6 +511,7 @@ __device__ __forceinline__ void gemm_bf16x_body(const GemmParams& p, int nwg, in
     static_assert(PSRC == 0 || (MODE == H3 && KMV && !AK && !BKC), "pair-format sources: the wgrad layout of the fp16-split arithmetic only");
     static_assert(PSRC >= 0 && PSRC <= 3, "PSRC 4 (formats per product) is resolved by the grouped kernel");
     constexpr bool pa_ = (PSRC & 1) != 0, pb_ = (PSRC & 2) != 0;
+    constexpr bool sa_ = pa_ && GB_ROWMAX_A_SLAB, sb_ = pb_ && GB_ROWMAX_B_SLAB;
     constexpr int NP = Pieces<MODE>::NP, TM = 2, TN = BN / WN / 32;
     constexpr int NQA = BM * 4 / NT, NQB = BN * 4 / NT;
     constexpr bool AV = !AK && KMV, BV = !BKC && KMV;
@@ -509,16 +566,18 @@ __device__ __forceinline__ void gemm_bf16x_body(const GemmParams& p, int nwg, in
         static_assert(AHEAD % 2 == 0, "the fragment sets alternate with the slabs");
         Quad qa[AHEAD][NQA], qb[AHEAD][NQB];      // register sets: slab t lives in set t % AHEAD from its load to its split
         Frags<NP, TM, TN> fr[2];                  // fragments of even / odd slabs
+        unsigned rmx[AHEAD] = {};                 // pair-format A: the token maxima of slab t, 16 across the lanes (load_token_maxima)
 #pragma unroll
         for (int u = 0; u < AHEAD; ++u) {
-            if constexpr (pa_) load_quads_pairs<NT, BM>(reinterpret_cast<const uint16_t*>(d.A), d.lda, d.a_rowmax, m0, kr.k_of(u < nsteps ? u : 0), d.M, kr.kend, qa[u]);
+            if constexpr (pa_) load_quads_pairs<NT, BM, !sa_>(reinterpret_cast<const uint16_t*>(d.A), d.lda, d.a_rowmax, m0, kr.k_of(u < nsteps ? u : 0), d.M, kr.kend, qa[u]);
             else load_quads<NT, BM, AK, VEC, AV>(d.A, d.lda, m0, kr.k_of(u < nsteps ? u : 0), d.M, kr.kend, qa[u]);
-            if constexpr (pb_) load_quads_pairs<NT, BN>(reinterpret_cast<const uint16_t*>(d.B), d.ldb, d.b_rowmax, n0, kr.k_of(u < nsteps ? u : 0), d.N, kr.kend, qb[u]);
+            if constexpr (pb_) load_quads_pairs<NT, BN, !sb_>(reinterpret_cast<const uint16_t*>(d.B), d.ldb, d.b_rowmax, n0, kr.k_of(u < nsteps ? u : 0), d.N, kr.kend, qb[u]);
             else load_quads<NT, BN, BKC, VEC, BV>(d.B, d.ldb, n0, kr.k_of(u < nsteps ? u : 0), d.N, kr.kend, qb[u]);
+            if constexpr (sa_ || sb_) rmx[u] = load_token_maxima<sa_, sb_>(d, kr.k_of(u < nsteps ? u : 0), kr.kend);
         }
-        if constexpr (pa_) store_quads_pairs<NT, BM, true>(smem, qa[0], kr.kend - kr.kbeg, 141 - sha[0][0], !AK && do_cs, cs);
+        if constexpr (pa_) store_quads_pairs<NT, BM, true, sa_>(smem, qa[0], rmx[0], 0, kr.kend - kr.kbeg, 141 - sha[0][0], !AK && do_cs, cs);
         else store_quads<NT, NP, BM, AK, true, Pieces<MODE>::HALF, AV>(smem, qa[0], kr.kend - kr.kbeg, sha);
-        if constexpr (pb_) store_quads_pairs<NT, BN, true>(smem + NP * PA, qb[0], kr.kend - kr.kbeg, 141 - shb[0][0], false, cs);
+        if constexpr (pb_) store_quads_pairs<NT, BN, true, sb_>(smem + NP * PA, qb[0], rmx[0], 16, kr.kend - kr.kbeg, 141 - shb[0][0], false, cs);
         else store_quads<NT, NP, BN, BKC, true, Pieces<MODE>::HALF, BV>(smem + NP * PA, qb[0], kr.kend - kr.kbeg, shb);
         if (!AK && do_cs) {
             if constexpr (!pa_) quad_rowsum<NT, BM, AV, true>(qa[0], kr.kend - kr.kbeg, cs);
@@ -529,7 +588,7 @@ __device__ __forceinline__ void gemm_bf16x_body(const GemmParams& p, int nwg, in
         // step s stores slab s+1 (register set (s+1) % AHEAD) and loads slab s+AHEAD into the set slab s occupied
 #define GRAPPA_STEP(TAIL, U) \
     pipeline_step<NT, MODE, BM, BN, WN, AK, BKC, VEC, KMV, TAIL, PSRC>(d, smem, acc, m0, n0, kr, s + (U), wm0, wn0, lane, qa[U], qb[U], qa[((U) + 1) % AHEAD], \
-                                                                 qb[((U) + 1) % AHEAD], fr[(U) & 1], fr[((U) + 1) & 1], cs, do_cs, sha, shb)
+                                                                 qb[((U) + 1) % AHEAD], rmx[U], rmx[((U) + 1) % AHEAD], fr[(U) & 1], fr[((U) + 1) & 1], cs, do_cs, sha, shb)
         // main loop: AHEAD steps per trip (the register sets rotate); never stores the last slab of the range and every load
         // it issues is for an existing slab
         for (; s + 2 * AHEAD - 1 < nsteps; s += AHEAD) {
