@@ -267,6 +267,14 @@ SIGNATURES = {
                                             _sz, _i, _vp]),
     "grappa_relax_steps_finish_cut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(RelaxOpts), _vp, _i, _i, _vp,
                                                _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise minimiser in GB/SA implicit solvent (additions to ABI 11): the _cut_ calls with the solvent after cut; finish also takes esolv
+    "grappa_relax_steps_gb_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "grappa_relax_steps_init_gb_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(GbDesc), C.POINTER(RelaxOpts),
+                                            _vp, _i, _i, _vp, _sz, _vp]),
+    "grappa_relax_steps_run_gb_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(GbDesc), C.POINTER(RelaxOpts),
+                                           _vp, _i, _i, _vp, _sz, _i, _vp]),
+    "grappa_relax_steps_finish_gb_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(GbDesc), C.POINTER(RelaxOpts),
+                                              _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # Langevin dynamics under the full force field (additions to ABI 11)
     "grappa_md_langevin_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(MdOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp]),

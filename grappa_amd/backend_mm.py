@@ -336,36 +336,78 @@ class MMBackend:
         cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls above, unchanged) -- the nonbonded force and
         energy of grappa_relax_steps_*_cut_f32: `nonbonded(..., cutoff=)`'s; it needs nb; the workspace is then
         `grappa_relax_steps_cut_workspace_bytes`; a step stays four launches."""
-        _xyz3(xyz, "relax_steps")
+        self._relax_steps("relax_steps", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy, grad,
+                          atom_counts_host, check_every, workspace, cutoff)
+
+    def relax_steps_gb(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy=None, grad=None,
+                       atom_counts_host=None, check_every: int = 32, workspace=None, gb=None, solvent="obc2", esolv=None) -> None:
+        """`relax_steps` in GB/SA implicit solvent (include/grappa_hip.h grappa_relax_steps_*_gb_f32): its arguments without the cutoff
+        (GB under a cutoff is not implemented) plus gb, a `grappa_amd.solvent.GBBatch` on xyz's device holding the batch's molecules in
+        order, and solvent, a model name or an `ImplicitSolvent`.  nb is required: it carries the charges.  The loop minimises the
+        energy with the solvent term: energy includes it, esolv (B,C) float32 or None -> the solvent term alone, term_energy is then
+        (8,B,C) with the polar and the surface-area term in rows 6 and 7, and grad is the total gradient.  A step is seven launches;
+        the workspace is `grappa_relax_steps_gb_workspace_bytes`.  The same chunked loop: one `.item()` per check_every steps."""
+        from .solvent import GBBatch, as_implicit_solvent
+        sv = as_implicit_solvent(solvent)
+        if sv is None or not isinstance(gb, GBBatch):
+            raise TypeError(f"relax_steps_gb: gb must be a GBBatch and solvent a model, got {type(gb).__name__}, {solvent!r}")
+        if nb is None:
+            raise ValueError("relax_steps_gb: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
+        gb.check_offset(sv.offset)
+        self._relax_steps("relax_steps_gb", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy,
+                          grad, atom_counts_host, check_every, workspace, None, gb=gb, solvent=sv, esolv=esolv)
+
+    def _relax_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, xyz_out, energy, gmax, steps, status, term_energy, grad,
+                     atom_counts_host, check_every, workspace, cutoff, gb=None, solvent=None, esolv=None):
+        """init, the run calls and finish of one stepwise minimisation: the plain calls, the _cut_ calls with a cutoff, the _gb_ calls
+        with an implicit solvent"""
+        _xyz3(xyz, who)
         if isinstance(check_every, bool) or int(check_every) != check_every or check_every < 1:
-            raise ValueError(f"relax_steps: check_every must be an integer >= 1, got {check_every}")
+            raise ValueError(f"{who}: check_every must be an integer >= 1, got {check_every}")
         check_every = int(check_every)
         dev = xyz.device
         d = self._mm_desc(plan, xyz, ks, eqs, n_per, offset_torsion)
         N, Cc, B = d.N, d.C, d.B
-        _relax_outputs("relax_steps", xyz, B, xyz_out, energy, gmax, steps, status, term_energy, grad)
+        if gb is not None and term_energy is not None:          # (rows 6 and 7: the solvent's terms)
+            _tensors(dev, ((term_energy, "term_energy", _F32),))
+            if term_energy.numel() != 8 * B * Cc:
+                raise ValueError(f"{who}: expected term_energy (8,B,C)")
+            _relax_outputs(who, xyz, B, xyz_out, energy, gmax, steps, status, term_energy.reshape(-1)[:6 * B * Cc], grad)
+        else:
+            _relax_outputs(who, xyz, B, xyz_out, energy, gmax, steps, status, term_energy, grad)
         if atom_counts_host is None:
-            raise ValueError("relax_steps: atom_counts_host is required (the work-item table is built from it)")
-        counts = _atom_counts(atom_counts_host, N, B, "relax_steps")
-        nd = _nb_tables_desc(nb, N, Cc, B, dev, "relax_steps")
-        o = _opts_struct(_lib.RelaxOpts, opts, "relax_steps")
+            raise ValueError(f"{who}: atom_counts_host is required (the work-item table is built from it)")
+        counts = _atom_counts(atom_counts_host, N, B, who)
+        nd = _nb_tables_desc(nb, N, Cc, B, dev, who)
+        o = _opts_struct(_lib.RelaxOpts, opts, who)
         cut = None
         if cutoff is not None:
             if nb is None:
-                raise ValueError("relax_steps: a cutoff needs the nonbonded tables (nb)")
-            cut = _cut_struct(cutoff, "relax_steps")
+                raise ValueError(f"{who}: a cutoff needs the nonbonded tables (nb)")
+            cut = _cut_struct(cutoff, who)
+        gbd = None
+        if gb is not None:
+            _tensors(dev, ((gb.radius, "gb.radius", _F32), (gb.scale, "gb.scale", _F32), (esolv, "esolv", _F32)), ("esolv",))
+            if gb.radius.numel() != N or gb.scale.numel() != N or (esolv is not None and esolv.numel() != B * Cc):
+                raise ValueError(f"{who}: expected gb.radius / gb.scale ({N},), esolv (B,C)")
+            gbd = _lib.GbDesc(radius=gb.radius.data_ptr(), scale=gb.scale.data_ptr(), **solvent.as_opts())
         if N == 0 or Cc == 0 or B == 0:
             return
         table = self._item_table(nb, counts, N, Cc, dev)
         table_dev, n_items, n_blocks, _ = table
-        need = int((self.lib.grappa_relax_steps_workspace_bytes if cut is None else self.lib.grappa_relax_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
+        if gbd is not None:
+            need = int(self.lib.grappa_relax_steps_gb_workspace_bytes(N, Cc, B, n_blocks))
+        else:
+            need = int((self.lib.grappa_relax_steps_workspace_bytes if cut is None else self.lib.grappa_relax_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
         if workspace is None:
-            workspace = self._workspace(need, dev, "relax_steps")
+            workspace = self._workspace(need, dev, who)
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         n_running = torch.zeros(1, dtype=torch.int32, device=dev)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if cut is None:
+        if gbd is not None:
+            head, sfx = (st, C.byref(d), ndp, None, C.byref(gbd), C.byref(o)), "_gb_f32"
+        elif cut is None:
             head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
         else:
             head, sfx = (st, C.byref(d), ndp, C.byref(cut), C.byref(o)), "_cut_f32"
@@ -380,7 +422,7 @@ class MMBackend:
             if int(n_running.item()) <= 0:          # the one host sync per chunk
                 break
         _chk(finish(*common, xyz_out.data_ptr(), energy.data_ptr(), _ptr(term_energy), _ptr(grad), gmax.data_ptr(), steps.data_ptr(),
-                    status.data_ptr()), f"grappa_relax_steps_finish{sfx}")
+                    status.data_ptr(), *((_ptr(esolv),) if gbd is not None else ())), f"grappa_relax_steps_finish{sfx}")
 
     # ------------------------------------------------------------------ dynamics
     def _md_call(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,

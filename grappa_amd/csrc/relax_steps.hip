@@ -24,6 +24,8 @@
 //            csrc/nb_cut.h; the move launch's item writes the box of its own (block, conformations) after moving -- the box's only
 //            writer -- and the force launch reads all boxes across the launch boundary: a step stays four launches, init gains one (boxes
 //            and exception ranges).  The finish's nonbonded energy by grappa_nonbonded_fwd_cut_f32 at the held coordinates.
+//   solvent: grappa_relax_steps_*_gb_f32 (gb == NULL: the calls without).  The section "implicit solvent" below: the force launch as it
+//            is, then born, pair and chain of csrc/gb_pass.h; the chain launch's epilogue completes g and rewrites the block's partials.
 // Same input, same bits; a molecule's bits do not depend on its place in the batch.
 #include <float.h>
 #include <limits.h>
@@ -32,6 +34,7 @@
 #include "common.h"
 #include "desc_check.h"
 #include "fire.h"
+#include "gb_pass.h"
 #include "rs_force.h"
 
 namespace {
@@ -362,6 +365,127 @@ __global__ __launch_bounds__(256) void rs_out_kernel(RsOutArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ implicit solvent (grappa_relax_steps_*_gb_f32)
+// GB/SA (include/grappa_hip.h grappa_gb_desc) as a term of the minimised energy: the three passes of csrc/gb_pass.h under the
+// stopped-conformation mask, behind the force launch, which runs AS IT IS -- so the kernels of a call without solvent are not touched by
+// this section, and a call with it launches the very same decide, vel, move and force kernels.
+//   step   : decide, vel, move, force (g = bonded + nonbonded and the partials of THAT gradient), born, pair (the gradient at fixed B ->
+//            ggb), chain: its epilogue adds g + ggb + the chain sum in that order, writes g and rewrites the block's four partials from
+//            the total gradient and the unchanged v.  7 launches.  init gains the same three launches behind its force launch.
+//   hazards: born writes B, dBdI of its own (atom, conformation)s, pair reads B of every j and writes w and ggb of its own, chain reads w
+//            of every j and writes g and the partials of its own block: every word has one writer per launch and is read only across a
+//            launch boundary.  The force launch's partials are overwritten before the next decide reads them; decide stays the only
+//            writer of the per-item state, and a non-finite total gradient reaches it as max |g_i| = inf: status 2 by the path it has.
+//   energies: grappa_gb_obc_fwd_f32 itself at the held coordinates, in a workspace region of its own (steps_gb_terms_at of
+//            csrc/rs_force.h), and one small launch that adds the eight terms in double in term order.
+struct RsGb {
+    const grappa_gb_desc* opts;
+    GbK k;
+};
+
+struct RsGbWs {
+    GbPassWs p;
+    float* ggb;                          // [N,C,3]: the gradient at fixed B
+    float *e_gb, *terms_gb;              // finish: [B,C], [2,B,C]
+    char* fwd;                           // finish: the workspace of grappa_gb_obc_fwd_f32
+    size_t fwd_bytes;
+    size_t total;
+};
+
+// (the words of the solvent lie behind all others: `off` = the total of rs_layout)
+RsGbWs rs_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks) {
+    RsGbWs g;
+    WsCarve k{base};
+    k.off = off;
+    g.p = gb_pass_ws(k, N, C);
+    g.ggb = k.take<float>((size_t)N * C * 3);
+    g.e_gb = k.take<float>((size_t)B * C), g.terms_gb = k.take<float>(2 * (size_t)B * C);
+    g.fwd_bytes = grappa_gb_obc_workspace_bytes(N, C, n_blocks > 0 ? n_blocks : 1);
+    g.fwd = k.take<char>(g.fwd_bytes);
+    g.total = k.off;
+    return g;
+}
+
+__global__ __launch_bounds__(NB_NT) void rs_gb_born_kernel(GbArgs a) {
+    __shared__ GbShared sh;
+    gb_born_body<true>(a, sh);
+}
+
+__global__ __launch_bounds__(NB_NT) void rs_gb_pair_kernel(GbArgs a) {
+    __shared__ GbShared sh;
+    gb_pair_body<true, false, true>(a, sh);
+}
+
+struct RsGbChainArgs {
+    GbArgs gb;
+    const float* v;
+    float* g;
+    double* part;
+};
+
+// (the partials: the text of rs_force_body's epilogue from `const V3 vi` on, word for word -- tests/test_host_relax_gb.py compares the two)
+__global__ __launch_bounds__(NB_NT) void rs_gb_chain_kernel(RsGbChainArgs a) {
+    __shared__ GbShared sh;
+    gb_chain_body<true>(a.gb, sh, [&](const GbLane& w, float cx, float cy, float cz) {
+        const RsItem& r = w.r;
+        const int C = a.gb.q.C, ni = r.ni;
+        float pP = 0.f, pF = 0.f, pv = 0.f, pg = 0.f;
+        if (w.owner) {
+            const size_t off = ((size_t)w.i * C + w.c) * 3;
+            const float* d = a.gb.gdir;
+            const V3 gi = {(a.g[off] + d[off]) + cx, (a.g[off + 1] + d[off + 1]) + cy, (a.g[off + 2] + d[off + 2]) + cz};
+            a.g[off] = gi.x, a.g[off + 1] = gi.y, a.g[off + 2] = gi.z;
+            const V3 vi = {a.v[off], a.v[off + 1], a.v[off + 2]};
+            const float g2 = dot(gi, gi), gn = sqrtf(g2);
+            pP = -dot(gi, vi);          // F = -g
+            pF = g2;
+            pv = dot(vi, vi);
+            pg = gn <= FLT_MAX ? gn : INFINITY;      // (written so that a NaN counts as non-finite)
+        }
+        __syncthreads();
+        if (w.owner) sh.red[0][w.l] = pP, sh.red[1][w.l] = pF, sh.red[2][w.l] = pv, sh.red[3][w.l] = pg;
+        __syncthreads();
+        if (w.owner && w.il == 0) {      // the block's partials of one conformation: over its atoms in ascending order, in double
+            double sP = 0.0, sF = 0.0, sv = 0.0;
+            float mg = 0.f;
+            for (int k = 0; k < ni; ++k) {
+                const int o = w.cl * ni + k;
+                sP += (double)sh.red[0][o], sF += (double)sh.red[1][o], sv += (double)sh.red[2][o];
+                mg = fmaxf(mg, sh.red[3][o]);
+            }
+            double* o = a.part + ((size_t)r.blk * C + w.c) * 4;
+            o[0] = sP, o[1] = sF, o[2] = sv, o[3] = (double)mg;
+        }
+    });
+}
+
+// energy with the solvent's two terms, term_energy's rows 6 and 7 and esolv: the conditions of rs_out_kernel, which ran before it and
+// left energy without them; the sum in ms_out_gb_kernel's order (csrc/dynamics_steps.hip)
+__global__ __launch_bounds__(256) void rs_out_gb_kernel(RsOutArgs a, const float* terms_gb, float* esolv) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, bc = (size_t)a.B * a.C;
+    if (gid >= bc) return;
+    const int b = (int)(gid / (unsigned)a.C);
+    if (nb_clamp(a.atom_molptr[b + 1], a.N) <= nb_clamp(a.atom_molptr[b], a.N)) return;
+    const double es = (double)terms_gb[gid] + (double)terms_gb[bc + gid];
+    double tot = 0.0;
+    for (int q = 0; q < 6; ++q) tot += (double)((q < 4 || a.has_nb) ? a.terms[q * bc + gid] : 0.f);
+    a.energy[gid] = (float)(tot + es);
+    if (a.term_energy) a.term_energy[6 * bc + gid] = terms_gb[gid], a.term_energy[7 * bc + gid] = terms_gb[bc + gid];
+    if (esolv) esolv[gid] = (float)es;
+}
+
+// the three solvent launches behind a force launch
+void rs_launch_gb(hipStream_t st, const grappa_nb_desc* nb, const RsGb& gb, const RsGeom& q, const RsWs& w, const RsGbWs& gw, int n_items) {
+    RsGbChainArgs c = {};
+    c.gb.q = q, c.gb.x = w.x, c.gb.charge = nb->charge, c.gb.radius = gb.opts->radius, c.gb.scale = gb.opts->scale, c.gb.k = gb.k;
+    c.gb.B = gw.p.B, c.gb.dBdI = gw.p.dBdI, c.gb.w = gw.p.w, c.gb.gdir = gw.ggb, c.gb.part = nullptr, c.gb.born = nullptr, c.gb.status = w.s.status;
+    c.v = w.v, c.g = w.g, c.part = w.part;
+    const dim3 grid((unsigned)n_items), block(NB_NT);
+    GRAPPA_LAUNCH(rs_gb_born_kernel, grid, block, 0, st, c.gb);
+    GRAPPA_LAUNCH(rs_gb_pair_kernel, grid, block, 0, st, c.gb);
+    GRAPPA_LAUNCH(rs_gb_chain_kernel, grid, block, 0, st, c);
+}
+
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
@@ -381,14 +505,16 @@ void rs_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_d
     }
 }
 
-// the three calls, with and without a cutoff (c == NULL: none)
+// the three calls, with and without a cutoff (c == NULL: none) and an implicit solvent (gb == NULL: none, the launches as they were)
 int rs_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o, const int* table_dev,
-            int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
+            int n_items, int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev, const RsGb* gb = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!n_running_dev) return GRAPPA_ERR_ARG;
     const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    RsGbWs gw = {};
+    if (gb) gw = rs_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     RsInitArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B;
@@ -404,18 +530,21 @@ int rs_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
         GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
     }
     if (n_items > 0) rs_launch_force(st, mm, nb, c, q, w, n_items);
+    if (gb && n_items > 0) rs_launch_gb(st, nb, *gb, q, w, gw, n_items);
     return grappa_launch_status();
 }
 
 int rs_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o, const int* table_dev,
-           int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps, int* n_running_dev) {
+           int n_items, int n_blocks, void* ws, size_t ws_bytes, int n_steps, int* n_running_dev, const RsGb* gb = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!n_running_dev) return GRAPPA_ERR_ARG;
     const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    RsGbWs gw = {};
+    if (gb) gw = rs_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     RsDecideArgs dc;
@@ -432,6 +561,7 @@ int rs_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             if (c) GRAPPA_LAUNCH(rs_move_cut_kernel, dim3(items), dim3(NB_NT), 0, st, u, w.box);
             else GRAPPA_LAUNCH(rs_move_kernel, dim3(items), dim3(NB_NT), 0, st, u);
             rs_launch_force(st, mm, nb, c, q, w, n_items);
+            if (gb) rs_launch_gb(st, nb, *gb, q, w, gw, n_items);
         }
     }
     return grappa_launch_status();
@@ -439,12 +569,14 @@ int rs_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
 
 int rs_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_relax_opts* o,
               const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* energy, float* term_energy,
-              float* grad, float* gmax, int* steps, int* status) {
+              float* grad, float* gmax, int* steps, int* status, const RsGb* gb = nullptr, float* esolv = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && relax_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !energy || !gmax || !steps || !status) return GRAPPA_ERR_ARG;
     const RsWs w = rs_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr);
-    if (ws_bytes < w.total) return GRAPPA_ERR_WORKSPACE;
+    RsGbWs gw = {};
+    if (gb) gw = rs_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const size_t bc = (size_t)mm->B * mm->C;
@@ -458,6 +590,10 @@ int rs_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
                       : steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
                                        sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
     if (erc != GRAPPA_OK) return erc;
+    if (gb) {
+        const int grc = steps_gb_terms_at(stream, mm, nb, gb->opts, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
+        if (grc != GRAPPA_OK) return grc;
+    }
     RsOutArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.has_nb = nb != nullptr;
     a.atom_molptr = mm->atom_molptr;
@@ -465,6 +601,7 @@ int rs_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     a.xyz_out = xyz_out, a.energy = energy, a.term_energy = term_energy, a.grad = grad, a.gmax = gmax, a.steps = steps, a.status = status;
     const size_t n3 = (size_t)mm->N * mm->C * 3, n = n3 > bc ? n3 : bc;
     GRAPPA_LAUNCH(rs_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    if (gb) GRAPPA_LAUNCH(rs_out_gb_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
     return grappa_launch_status();
 }
 
@@ -523,4 +660,66 @@ extern "C" int grappa_relax_steps_finish_cut_f32(void* stream, const grappa_mm_d
     if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
     return rs_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy, term_energy, grad,
                      gmax, steps, status);
+}
+
+// with the GB/SA implicit solvent: gb == NULL is the call above (the _cut_ one with a cut, else the plain one), with its launches and
+// its bits.  A cutoff together with the solvent, a solvent without nb or charges, refused options or NULL tables: GRAPPA_ERR_ARG before
+// anything else is looked at.
+namespace {
+// GRAPPA_OK: a solvent to run with (g filled); 1: none, forward; < 0: refused
+int rs_gb_check(const grappa_gb_desc* gb, const grappa_nb_desc* nb, const grappa_nb_cut* cut, RsGb& g) {
+    if (!gb) return 1;
+    if (cut || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k)) return GRAPPA_ERR_ARG;
+    g.opts = gb;
+    return GRAPPA_OK;
+}
+}  // namespace
+
+extern "C" size_t grappa_relax_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
+    return rs_gb_layout(nullptr, rs_layout(nullptr, N, C, B, n_blocks).total, N, C, B, n_blocks).total;
+}
+
+extern "C" int grappa_relax_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                              const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items,
+                                              int n_blocks, void* ws, size_t ws_bytes, int* n_running_dev) {
+    RsGb g;
+    const int gc = rs_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1) {
+        if (cut) return grappa_relax_steps_init_cut_f32(stream, mm, nb, cut, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_running_dev);
+        return grappa_relax_steps_init_f32(stream, mm, nb, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_running_dev);
+    }
+    return rs_init(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_running_dev, &g);
+}
+
+extern "C" int grappa_relax_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                             const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items,
+                                             int n_blocks, void* ws, size_t ws_bytes, int n_steps, int* n_running_dev) {
+    RsGb g;
+    const int gc = rs_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1) {
+        if (cut) return grappa_relax_steps_run_cut_f32(stream, mm, nb, cut, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_steps, n_running_dev);
+        return grappa_relax_steps_run_f32(stream, mm, nb, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_steps, n_running_dev);
+    }
+    return rs_run(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, n_steps, n_running_dev, &g);
+}
+
+extern "C" int grappa_relax_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                                const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items,
+                                                int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* energy, float* term_energy,
+                                                float* grad, float* gmax, int* steps, int* status, float* esolv) {
+    RsGb g;
+    const int gc = rs_gb_check(gb, nb, cut, g);
+    if (gc < 0) return gc;
+    if (gc == 1) {
+        if (cut)
+            return grappa_relax_steps_finish_cut_f32(stream, mm, nb, cut, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy,
+                                                     term_energy, grad, gmax, steps, status);
+        return grappa_relax_steps_finish_f32(stream, mm, nb, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy, term_energy, grad,
+                                             gmax, steps, status);
+    }
+    return rs_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, energy, term_energy, grad, gmax, steps,
+                     status, &g, esolv);
 }

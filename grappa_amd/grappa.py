@@ -54,17 +54,29 @@ class Grappa:
         g = g.to("cpu")
         return Parameters.from_dgl(g)
 
-    def relax(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, check_every: int = 32, cutoff=None, **opts):
+    def relax(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, check_every: int = 32, cutoff=None, implicit_solvent=None,
+              **opts):
         """`predict` followed by `grappa_amd.relax.relax`: the conformations xyz (n_confs, n_atoms, 3) of `molecule` minimised on the
         device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in the molecule's atom order) -> RelaxResult.
         stepwise=False: the fused kernel (molecules up to `relax_max_atoms()` atoms); True or "auto": the stepwise path for molecules
         of any size, which syncs with the host once per chunk of `check_every` steps (see `grappa_amd.relax.relax_graph`).
         cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance in Angstrom (None: all pairs): the minimisation under the nonbonded
         cutoff that `simulate(..., cutoff=)` runs under, on the stepwise path; the result's energy is then the sum of the cut terms;
-        it needs `nonbonded` and stepwise="auto" (or True)"""
+        it needs `nonbonded` and stepwise="auto" (or True).
+        implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum): the minimisation under the GB/SA
+        Hamiltonian that `simulate(..., implicit_solvent=)` runs under, with the radii and screening factors of the molecule's
+        elements and bonds (`GBParameters.from_elements`; gb= in **opts overrides them); the result's energy then includes the
+        solvent term and `esolv` holds it alone; it needs `nonbonded` and stepwise="auto" (or True) and goes with neither a cutoff
+        nor restraints"""
         from .relax import relax
         if cutoff is not None:
             opts = {**opts, "cutoff": cutoff}
+        if implicit_solvent is not None:
+            from .solvent import GBParameters
+            opts = {**opts, "implicit_solvent": implicit_solvent}
+            if opts.get("gb") is None:
+                pos = {int(a): i for i, a in enumerate(molecule.atoms)}          # bonds name atoms by id; the tables go by position
+                opts["gb"] = GBParameters.from_elements(molecule.atomic_numbers, [(pos[int(a)], pos[int(b)]) for a, b in molecule.bonds])
         return relax(self.predict(molecule), xyz, nonbonded, device=self.device, stepwise=stepwise, check_every=check_every, **opts)
 
     def torsion_scan(self, molecule: Molecule, xyz, dihedral, angles=None, nonbonded=None, **kw):

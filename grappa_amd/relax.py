@@ -22,6 +22,13 @@ launches.  The minimiser then works on that energy: `RelaxResult.energy` (and th
 Hamiltonian a `simulate` with the same cutoff starts under.  It needs `nonbonded`; `stepwise="auto"` goes stepwise whenever a cutoff
 is given, `stepwise=False` is refused.  The fused kernels, restraints (and so `torsion_scan`), periodic boxes, PME and a long-range
 Lennard-Jones correction have no cutoff.
+
+Implicit solvent (`implicit_solvent=`, `grappa_amd.solvent`): the minimisation under the GB/SA Hamiltonian that
+`simulate(..., implicit_solvent=)` runs under, on the stepwise path (`grappa_relax_steps_*_gb_f32` through `HipBackend.relax_steps_gb`):
+three more passes of the tiled pair loop behind the force launch, seven launches per step.  `RelaxResult.energy` then includes the
+solvent term and `RelaxResult.esolv` holds it alone.  The rules are `simulate`'s: it needs `nonbonded` and the per-atom radii and
+screening factors (`gb=`), `stepwise="auto"` goes stepwise whenever it is given, and `stepwise=False`, a cutoff and restraints are
+refused.  All pairs only; the fused minimiser, restraints and `torsion_scan` have no solvent; no HCT / GBn model and no salt term.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -80,6 +87,7 @@ class RelaxResult:
     status: object
     restraint_energy: object = None          # with restraints: E_r at xyz (energy stays the force field's), else None
     dihedrals: object = None                 # with restraints: the restrained dihedrals at xyz, (R, C) / (R, n_confs) in radians, else None
+    esolv: object = None                     # with an implicit solvent: its part of energy, shaped like it; else None
 
     @property
     def converged(self):
@@ -105,6 +113,28 @@ def _cutoff_options(cutoff, nonbonded, stepwise, restraints):
         if restraints is not None:
             raise ValueError("relax: restraints are taken by the fused minimiser only, a cutoff on the stepwise path only")
     return cutoff
+
+
+def _solvent_options(implicit_solvent, gb, nonbonded, stepwise, restraints, cutoff, gb_type):
+    """the rules of an implicit solvent (those of `simulate`), decided on the host before anything is built -> an `ImplicitSolvent` or
+    None; gb_type: what gb= has to be at this door"""
+    from .solvent import as_implicit_solvent
+    solvent = as_implicit_solvent(implicit_solvent)
+    if solvent is None:
+        if gb is not None:
+            raise ValueError("relax: gb= needs implicit_solvent=")
+        return None
+    if cutoff is not None:
+        raise ValueError("relax: an implicit solvent under a cutoff is not implemented: pass one of the two")
+    if nonbonded is None:
+        raise ValueError("relax: an implicit solvent needs the nonbonded parameters (nonbonded=): they carry the charges")
+    if stepwise is False:
+        raise ValueError('relax: an implicit solvent runs on the stepwise path only: pass stepwise="auto" (or True)')
+    if restraints is not None:
+        raise ValueError("relax: restraints are taken by the fused minimiser only, an implicit solvent on the stepwise path only")
+    if not isinstance(gb, gb_type):
+        raise TypeError(f"relax: an implicit solvent needs gb=, the {gb_type.__name__} of the molecules, got {type(gb).__name__}")
+    return solvent
 
 
 def graph_coordinates(g, terms):
@@ -138,7 +168,7 @@ def graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev):
 
 def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
                 offset_torsion: bool = False, stepwise=False, check_every: int = CHECK_EVERY_DEFAULT, restraints=None, cutoff=None,
-                **opts) -> RelaxResult:
+                implicit_solvent=None, gb=None, **opts) -> RelaxResult:
     """Relax every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` / `eq` at the tuple levels,
     exactly what `Energy` reads, through the same plan.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded
     terms only).  **opts: see RELAX_DEFAULTS.  The graph is not modified.
@@ -153,11 +183,20 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     path only: with restraints stepwise=True raises, and "auto" raises for a batch that holds a molecule above the limit.
     cutoff: a `grappa_amd.nonbonded.Cutoff` or a distance (None: all pairs, the calls made are exactly those without this argument):
     see the module text.  `energy` is then the sum of the cut terms.  It needs `nonbonded` and the stepwise path: "auto" then goes
-    stepwise whatever the sizes, stepwise=False and restraints are refused."""
+    stepwise whatever the sizes, stepwise=False and restraints are refused.
+    implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum, the calls made are exactly those without
+    this argument) -- the GB/SA term of `grappa_amd.solvent` added to the minimised energy, with gb, the batch's
+    `grappa_amd.solvent.GBBatch` on the graph's device.  `energy` then includes the solvent term and the result's `esolv` (B, C) holds
+    it alone.  It needs `nonbonded` and the stepwise path: "auto" then goes stepwise whatever the sizes; stepwise=False, a cutoff and
+    restraints are refused."""
     from .backend import get_backend
+    from .solvent import GBBatch
     o = relax_options(**opts)
     stepwise, check_every = _stepwise_options(stepwise, check_every)
     cutoff = _cutoff_options(cutoff, nonbonded, stepwise, restraints)
+    solvent = _solvent_options(implicit_solvent, gb, nonbonded, stepwise, restraints, cutoff, GBBatch)
+    if solvent is not None and getattr(get_backend(), "relax_steps_gb", None) is None:
+        raise ValueError("relax: the backend has no implicit solvent for the minimiser (relax_steps_gb)")
     terms = list(terms)
     if restraints is not None:
         from .restraints import RestraintBatch
@@ -175,8 +214,14 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     if above and stepwise is False:
         raise ValueError(f"relax: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused "
                          f"minimiser (stepwise=True or stepwise='auto' relaxes molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None))
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None))
     B, C = plan.B, xyz.shape[1]
+    if solvent is not None:
+        if gb.counts != list(counts):
+            raise ValueError(f"the GB parameters describe molecules of {gb.counts} atoms, the batch has {list(counts)}")
+        if gb.radius.device != dev:
+            raise ValueError(f"the GB parameters are on {gb.radius.device}, the graph on {dev}")
+        gb.check_offset(solvent.offset)          # (the batch may have been checked against another offset than the solvent's)
     if restraints is not None:
         if restraints.B != B or restraints.C != C:
             raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
@@ -195,6 +240,11 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
     if restraints is not None:
         er, phi = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(restraints.R, C, dtype=torch.float32, device=dev)
         restr = dict(restraints=restraints, restraint_energy=er, dihedral_out=phi)
+    if solvent is not None:
+        es = torch.zeros(B, C, dtype=torch.float32, device=dev)
+        get_backend().relax_steps_gb(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
+                                     atom_counts_host=counts, check_every=check_every, gb=gb, solvent=solvent, esolv=es)
+        return RelaxResult(out, energy, gmax, steps, status, er, phi, es)
     if use_steps:
         get_backend().relax_steps(plan, xyz, ks, eqs, n_per, bool(offset_torsion), nonbonded, o, out, energy, gmax, steps, status,
                                   atom_counts_host=counts, check_every=check_every, **({} if cutoff is None else {"cutoff": cutoff}))
@@ -254,19 +304,27 @@ def graph_from_parameters(parameters: Parameters, xyz):
 
 
 def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, stepwise=False,
-          check_every: int = CHECK_EVERY_DEFAULT, restraints=None, cutoff=None, **opts) -> RelaxResult:
+          check_every: int = CHECK_EVERY_DEFAULT, restraints=None, cutoff=None, implicit_solvent=None, gb=None, **opts) -> RelaxResult:
     """Relax the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`, whose atoms are in the
     order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom -> RelaxResult with xyz of the same shape
     (float64) and energy / gradient_max / steps / status of shape (n_confs,).  stepwise, check_every: see `relax_graph` (the stepwise
     path takes a molecule of any size and syncs with the host once per chunk of `check_every` steps).
     restraints: a `grappa_amd.restraints.Restraints` whose indices are in the order of `parameters.atoms` (None: none); the result
     then carries restraint_energy (n_confs,) and dihedrals (R, n_confs), and `energy` stays the force field's.  The fused path only.
-    cutoff: see `relax_graph` (`energy` is then the sum of the cut terms; the stepwise path only, no restraints)."""
+    cutoff: see `relax_graph` (`energy` is then the sum of the cut terms; the stepwise path only, no restraints).
+    implicit_solvent: see `relax_graph`; gb: the molecule's `grappa_amd.solvent.GBParameters` in the order of `parameters.atoms`.  The
+    result then carries esolv (n_confs,), and `energy` includes it."""
+    from .solvent import GBBatch, GBParameters
     relax_options(**opts)
     _stepwise_options(stepwise, check_every)
     extra = {}
     if _cutoff_options(cutoff, nonbonded, stepwise, restraints) is not None:
         extra["cutoff"] = as_cutoff(cutoff)
+    solvent = _solvent_options(implicit_solvent, gb, nonbonded, stepwise, restraints, extra.get("cutoff"), GBParameters)
+    if solvent is not None:
+        if gb.n_atoms != np.asarray(parameters.atoms).reshape(-1).shape[0]:
+            raise ValueError(f"the GB parameters describe {gb.n_atoms} atoms, the molecule has {np.asarray(parameters.atoms).reshape(-1).shape[0]}")
+        extra.update(implicit_solvent=solvent, gb=GBBatch([gb], solvent.offset).to(device))
     g = graph_from_parameters(parameters, xyz)
     batch = None
     if restraints is not None:
@@ -289,6 +347,8 @@ def relax(parameters: Parameters, xyz, nonbonded: Optional[NonbondedParameters] 
                       r.gradient_max.cpu().numpy()[0].astype(np.float64), r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0])
     if batch is not None:
         res.restraint_energy, res.dihedrals = r.restraint_energy.cpu().numpy()[0].astype(np.float64), r.dihedrals.cpu().numpy().astype(np.float64)
+    if r.esolv is not None:
+        res.esolv = r.esolv.cpu().numpy()[0].astype(np.float64)
     return res
 
 
@@ -335,10 +395,14 @@ def torsion_scan(parameters: Parameters, xyz, dihedral, angles=None, nonbonded: 
     launch, one workgroup per point.  The points are INDEPENDENT: each starts from the input with one side of the bond rotated to its
     angle (`scan_starts`), nothing is propagated from a neighbouring point -- so a point can end in another basin than its neighbours.
     **opts: the options of `relax` (RELAX_DEFAULTS).  With the default k FIRE's defaults are stable (the restraint is softer than
-    every bond); whether a point reached the tolerance is in `status`.  It takes no cutoff: restraints are the fused minimiser's."""
+    every bond); whether a point reached the tolerance is in `status`.  It takes no cutoff and no implicit solvent: restraints are the
+    fused minimiser's."""
     from .restraints import Restraints
     if "cutoff" in opts:
         raise ValueError("torsion_scan: takes no cutoff (restraints are taken by the fused minimiser only, a cutoff runs on the stepwise path only)")
+    if "implicit_solvent" in opts or "gb" in opts:
+        raise ValueError("torsion_scan: takes no implicit solvent (restraints are taken by the fused minimiser only, a solvent runs on the "
+                         "stepwise path only)")
     if angles is None:
         angles = -np.pi + np.deg2rad(15.0) * np.arange(24)
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)

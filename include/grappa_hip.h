@@ -728,6 +728,38 @@ int grappa_relax_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, co
                                       const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
                                       size_t ws_bytes, float* xyz_out, float* energy, float* term_energy, float* grad, float* gmax,
                                       int* steps, int* status);
+/* The stepwise minimiser in GB/SA implicit solvent (additions to ABI 11): the three _cut_ calls with `const grappa_gb_desc* gb` after
+ * cut, and `float* esolv` at the end of finish.  gb == NULL: each forwards to the call above (the _cut_ one if cut != NULL, else the plain
+ * one) -- its launches, its bits.  With gb the minimised energy is the one above plus E_pol + E_sa of grappa_gb_obc_fwd_f32 (nb is
+ * required: it carries the charges; its exceptions do not touch the solvent term), cut must be NULL (GB under a cutoff is not
+ * implemented) and the force launch is followed by the three passes of that entry under the stopped-conformation mask:
+ *   step   : decide, vel, move, force (as they are), born, pair, chain -- the chain launch's epilogue adds the three gradients in the order
+ *            (bonded + nonbonded) + fixed-B part + chain parts, writes g and rewrites the block's partials of P, |F|^2, |v|^2 and
+ *            max |g_i| from the sum and the unchanged v, by the arithmetic of the force launch's epilogue.  7 launches per step; init
+ *            gains the same three: 5.  decide stays the only writer of the per-item state: a non-finite sum ends the item with status 2
+ *            as a non-finite force gradient does.  The decide, vel, move and force kernels are the ones a call without solvent launches.
+ *   finish : the sequence above (decide, the six terms, the copy kernel), grappa_gb_obc_fwd_f32 at xyz_out in a workspace region of
+ *            its own, and one small launch: energy = the eight terms (six as before, E_pol, E_sa) added in double in that order, esolv
+ *            [B,C] (NULL: not written) = E_pol + E_sa alone, and term_energy, if given, is [8,B,C] with E_pol and E_sa in rows 6 and 7
+ *            (the entry's bits).  grad is the total gradient.  9 launches (5 without solvent).
+ * The workspace is grappa_relax_steps_gb_workspace_bytes(N, C, B, n_blocks): the words of a call without solvent first (the plain
+ * layout, unchanged), behind them B, dBdI, w [N,C], the fixed-B gradient [N,C,3], [3,B,C] energies and the workspace of
+ * grappa_gb_obc_fwd_f32, each piece on a 256-byte boundary; ws_bytes below it is GRAPPA_ERR_WORKSPACE, nothing launched.
+ * GRAPPA_ERR_ARG before anything else is looked at, nothing launched and nothing written: cut != NULL together with gb, nb == NULL or
+ * without charges, NULL radius or scale, options grappa_gb_obc_fwd_f32 refuses.  r = 0 between two distinct atoms (bonded or not: GB
+ * has no exclusions) gives status 2; a radius <= offset or a scale <= 0 makes its molecule's gradient NaN: status 2.  Not here: the fused
+ * minimiser, restraints, a cutoff, the HCT / GBn models, a salt term. */
+size_t grappa_relax_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks);
+int grappa_relax_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                   const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
+                                   void* ws, size_t ws_bytes, int* n_running_dev);
+int grappa_relax_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                  const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
+                                  void* ws, size_t ws_bytes, int n_steps, int* n_running_dev);
+int grappa_relax_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                     const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
+                                     void* ws, size_t ws_bytes, float* xyz_out, float* energy, float* term_energy, float* grad, float* gmax,
+                                     int* steps, int* status, float* esolv);
 
 /* ------------------------------------------------------------------------------------------------
  * Langevin molecular dynamics under the full MM force field (additions to ABI 11): BAOAB (Leimkuhler and Matthews 2013; on-step
@@ -988,7 +1020,7 @@ int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, cons
  * epot is.  The workspace is grappa_md_steps_gb_workspace_bytes (the words of a run without solvent first, the solvent's behind them).
  * GRAPPA_ERR_ARG before anything else is looked at: cut != NULL together with gb (GB under a cutoff is not implemented), nb == NULL,
  * NULL radius or scale, options grappa_gb_obc_fwd_f32 refuses.  r = 0 between two distinct atoms (bonded or not: GB has no exclusions)
- * gives status 2.  Not here: the fused dynamics, the minimisers, restraints. */
+ * gives status 2.  Not here: the fused dynamics, the fused minimiser, restraints. */
 size_t grappa_md_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks, int K);
 int grappa_md_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                 const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,

@@ -17,7 +17,15 @@ all pairs, the cutoff with prune = 1 and with prune = 0 -- timed alternately by 
 runs each), all run times printed, with the tiles the cut energy kernel evaluates at the start coordinates.  Every size is a child
 process of its own under `timeout`; after one that fails nothing more is started.
 
+With --implicit-solvent MODEL (obc2, obc1) the tool measures relax(..., implicit_solvent=) instead: per size the all-pairs vacuum step
+against the step in the solvent, on the same tree, timed alternately by the same protocol (device events, one warm-up run, `--reps` runs
+each), all run times printed with the library launches.  Four sizes: the pool batch, a 513-atom chain, T4 lysozyme
+(grappa_amd/data/t4_lysozyme.npz with mbondi2 radii from its elements) and the 50,046-atom chain; the pool and the chains carry carbon's
+radius and screening factor on every atom.  Every size is a child process of its own under `timeout`; after one that fails nothing more
+is started.
+
     python tools/relax_steps_bench.py [--out profiles/relax_steps_bench.txt] [--steps 128] [--big-steps 16] [--reps 5]
+    python tools/relax_steps_bench.py --implicit-solvent obc2 [--out profiles/relax_steps_gb_bench.txt]
     python tools/relax_steps_bench.py --cutoff 10 [--switch 8] [--out profiles/relax_steps_cutoff_bench.txt]
     python tools/relax_steps_bench.py --dry          # build the inputs on the CPU and stop (a rehearsal: nothing is timed)
 """
@@ -130,6 +138,88 @@ def cut_stage(args):
     print(json.dumps(out))
 
 
+GB_STAGES = ("gb_pool", "gb_513", "gb_t4l", "gb_big")
+GB_SIDES = ("vacuum", "solvent")
+
+
+def gb_stage(args):
+    """one size of the solvent measurement in this process -> one JSON line"""
+    if not torch.cuda.is_available():
+        sys.exit("relax_steps_bench: needs a GPU (there is nothing to time without one)")
+    from grappa_amd.backend import get_backend
+    from grappa_amd.nonbonded import NonbondedBatch
+    from grappa_amd.relax import relax_graph
+    from grappa_amd.solvent import GBBatch, GBParameters
+    be = get_backend()
+    S = args.big_steps if args.stage == "gb_big" else args.steps
+    if args.stage == "gb_pool":
+        g, nb = pool_batch(args.mols, args.confs)
+        what = f"pool: {args.mols} molecules, C = {args.confs}"
+    elif args.stage == "gb_t4l":
+        from md_steps_bench import _t4l
+        gh, nbp, _, gbp = _t4l()
+        g, nb = gh.to("cuda"), NonbondedBatch([nbp]).to("cuda")
+        what = "T4 lysozyme: 1 molecule, C = 1"
+    else:
+        gh, nbp = chain_graph(513 if args.stage == "gb_513" else args.big_atoms)
+        g, nb = gh.to("cuda"), NonbondedBatch([nbp]).to("cuda")
+        what = "chain: 1 molecule, C = 1"
+    counts = [int(c) for c in g.batch_num_nodes_host("n1")]
+    gbs = [gbp] if args.stage == "gb_t4l" else [GBParameters(np.full(n, 1.7), np.full(n, 0.72)) for n in counts]
+    gbb = GBBatch(gbs).to("cuda")
+    sides = {"vacuum": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True),
+             "solvent": lambda: relax_graph(g, nb, tolerance=0.0, max_steps=S, stepwise=True, implicit_solvent=args.implicit_solvent, gb=gbb)}
+    out = {"what": what, "atoms": int(sum(counts)), "steps": S, "ran": {}, "launches": {}}
+    for k, fn in sides.items():
+        n0 = be.lib.grappa_launch_count(0)
+        r = fn()
+        torch.cuda.synchronize()
+        out["launches"][k] = int(be.lib.grappa_launch_count(0) - n0)
+        out["ran"][k] = bool((r.steps == S).all()) and bool((r.status == 0).all())
+    out["ms"] = timed_alternately(sides, args.reps)
+    print(json.dumps(out))
+
+
+def gb_main(args):
+    """the solvent measurement: every size a child process under its own time limit"""
+    lines = [f"# command: python {' '.join(sys.argv)}",
+             f"# date: {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}"]
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def run(name):
+        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
+              [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "big_atoms", "steps", "big_steps", "reps", "implicit_solvent")]
+        p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout + p.stderr)
+            sys.exit(f"relax_steps_bench: stage {name} ended with status {p.returncode}; nothing more is started")
+        return json.loads(p.stdout.strip().splitlines()[-1])
+
+    say(f"# device: {run('device')['device']}")
+    say(f"# relax_graph(stepwise=True), tolerance 0, a fixed step count: all pairs in vacuum against GB/SA {args.implicit_solvent} on the same tree; "
+        f"device events around whole runs, the two sides of a size timed alternately in one process of its own, {args.reps} runs each after one "
+        "warm-up run each; all run times in ms; this file is the tool's output, unedited")
+    for name in GB_STAGES:
+        r = run(name)
+        S = r["steps"]
+        say(f"{r['what']}, {r['atoms']} atoms, bonded + nonbonded, {S} steps")
+        per = {}
+        for k in GB_SIDES:
+            ms = np.array(r["ms"][k])
+            per[k] = float(np.median(ms)) / S
+            say(f"  {k:8s} {per[k]:9.4f} ms/step (min {ms.min() / S:9.4f} .. max {ms.max() / S:9.4f})  run {np.median(ms):9.2f} ms  "
+                f"{r['launches'][k]} library launches per run; all items ran {S} steps: {r['ran'][k]}")
+            say(f"           runs: {', '.join(f'{m:.2f}' for m in ms)} ms")
+        say(f"  solvent / vacuum = {per['solvent'] / per['vacuum']:.2f}x ms per step")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def cut_main(args):
     """the cutoff measurement: every stage a child process under its own time limit"""
     lines = [f"# command: python {' '.join(sys.argv)}",
@@ -191,10 +281,15 @@ def main():
     ap.add_argument("--dry", action="store_true")
     ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
     ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
-    ap.add_argument("--stage", default=None, choices=CUT_STAGES)
+    ap.add_argument("--implicit-solvent", default="", help="obc2 or obc1: measure the GB/SA implicit solvent (see the module text)")
+    ap.add_argument("--stage", default=None, choices=CUT_STAGES + GB_STAGES)
     args = ap.parse_args()
+    if args.stage in GB_STAGES:
+        return gb_stage(args)
     if args.stage:
         return cut_stage(args)
+    if args.implicit_solvent and not args.dry:
+        return gb_main(args)
     if args.cutoff and not args.dry:
         return cut_main(args)
     if args.dry:
