@@ -97,6 +97,11 @@ class GbDesc(C.Structure):
                 ("gamma", C.c_float), ("eps_in", C.c_float), ("eps_out", C.c_float), ("surface_tension", C.c_float), ("probe", C.c_float)]
 
 
+class GbCut(C.Structure):
+    """grappa_gb_cut (additions to ABI 11): the cutoff of the GB/SA implicit solvent, per call"""
+    _fields_ = [("cutoff", C.c_float), ("prune", C.c_int)]
+
+
 class RelaxOpts(C.Structure):
     """grappa_relax_opts (additions to ABI 11): the options of the fused FIRE minimiser, per call"""
     _fields_ = [("tolerance", C.c_float), ("max_steps", C.c_int), ("dt_start", C.c_float), ("dt_max", C.c_float), ("max_disp", C.c_float),
@@ -247,6 +252,9 @@ SIGNATURES = {
     # GB/SA implicit solvent, OBC (additions to ABI 11)
     "grappa_gb_obc_workspace_bytes": (_sz, [_i, _i, _i]),
     "grappa_gb_obc_fwd_f32": (_i, [_vp, C.POINTER(NbDesc), C.POINTER(GbDesc), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "grappa_gb_obc_cut_workspace_bytes": (_sz, [_i, _i, _i]),
+    "grappa_gb_obc_fwd_cut_f32": (_i, [_vp, C.POINTER(NbDesc), C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _sz]),
     # relaxation under the full force field (additions to ABI 11)
     "grappa_relax_max_atoms": (_i, []),
     "grappa_relax_fire_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(RelaxOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -315,6 +323,13 @@ SIGNATURES = {
                                         C.POINTER(GbDesc), _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "grappa_md_steps_finish_gb_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
                                            C.POINTER(GbDesc), _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_md_steps_gbcut_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "grappa_md_steps_init_gbcut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                            C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _vp, _vp, _vp, _i, _i, _vp, _sz]),
+    "grappa_md_steps_run_gbcut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                           C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    "grappa_md_steps_finish_gbcut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                              C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

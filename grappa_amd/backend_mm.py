@@ -221,14 +221,22 @@ class MMBackend:
              "grappa_nonbonded_fwd_f32")
 
     # ------------------------------------------------------------------ implicit solvent
-    def gb_obc(self, xyz, atom_molptr, charge, radius, scale, opts, energy, term_energy=None, grad=None, born=None, plan=None) -> None:
+    def gb_obc(self, xyz, atom_molptr, charge, radius, scale, opts, energy, term_energy=None, grad=None, born=None, plan=None, cut=None,
+               tiles=None) -> None:
         """GB/SA implicit solvent in the Onufriev-Bashford-Case form (include/grappa_hip.h grappa_gb_obc_fwd_f32 states the energy):
         xyz (N,C,3), atom_molptr (B+1,) int32, charge / radius / scale (N,) float32; opts: the eight options of grappa_gb_desc by name
         (`ImplicitSolvent.as_opts()`); plan (required): what `nonbonded_plan` returned for this atom_molptr and C.
         -> energy (B,C), term_energy (2,B,C: polar, surface area) or None, grad (N,C,3) = +dE/dxyz or None, born (N,C) = the Born radii
         or None.  Angstrom, kcal/mol, elementary charges.  4 launches, 3 without grad.  radius <= offset or scale <= 0 make the
-        molecule's results NaN (`GBParameters.validate` refuses them on the host).  Out of scope: a cutoff, HCT / GBn, a salt term."""
+        molecule's results NaN (`GBParameters.validate` refuses them on the host).
+        cut: None (all pairs, the call above) or the two options of grappa_gb_cut by name (`ImplicitSolvent.cut_opts()`) --
+        grappa_gb_obc_fwd_cut_f32: every pair sum over j != i keeps the pairs with r < cutoff only, far tiles are skipped (prune); one
+        launch more.  tiles: an int32 tensor of n_items or None -> the tiles each work item evaluated.
+        Out of scope: HCT / GBn, a salt term."""
         _xyz3(xyz, "gb_obc")
+        if tiles is not None and cut is None:
+            raise ValueError("gb_obc: tiles needs a cutoff")
+        gc = None if cut is None else _opts_struct(_lib.GbCut, cut, "gb_obc: cut")
         dev = xyz.device
         _tensors(dev, [(xyz, "xyz", _F32), (atom_molptr, "atom_molptr", _I32), (charge, "charge", _F32), (radius, "radius", _F32),
                        (scale, "scale", _F32), (energy, "energy", _F32), (term_energy, "term_energy", _F32), (grad, "grad", _F32),
@@ -252,6 +260,16 @@ class MMBackend:
         d = _lib.NbDesc()
         d.N, d.C, d.B, d.xyz, d.atom_molptr, d.charge = N, Cc, B, xyz.data_ptr(), atom_molptr.data_ptr(), charge.data_ptr()
         g = _lib.GbDesc(radius=radius.data_ptr(), scale=scale.data_ptr(), **{k: float(opts[k]) for k in names})
+        if gc is not None:
+            if tiles is not None:
+                _tensors(dev, ((tiles, "tiles", _I32),))
+                if tiles.numel() != n_items:
+                    raise ValueError(f"gb_obc: tiles must hold one int32 per work item ({n_items})")
+            ws = self._workspace(int(self.lib.grappa_gb_obc_cut_workspace_bytes(N, Cc, n_blocks)), dev)
+            _chk(self.lib.grappa_gb_obc_fwd_cut_f32(self._stream(), C.byref(d), C.byref(g), C.byref(gc), table.data_ptr(), n_items, n_blocks,
+                                                    energy.data_ptr(), _ptr(term_energy), _ptr(grad), _ptr(born), _ptr(tiles), ws.data_ptr(),
+                                                    ws.numel()), "grappa_gb_obc_fwd_cut_f32")
+            return
         ws = self._workspace(int(self.lib.grappa_gb_obc_workspace_bytes(N, Cc, n_blocks)), dev)
         _chk(self.lib.grappa_gb_obc_fwd_f32(self._stream(), C.byref(d), C.byref(g), table.data_ptr(), n_items, n_blocks, energy.data_ptr(),
                                             _ptr(term_energy), _ptr(grad), _ptr(born), ws.data_ptr(), ws.numel()), "grappa_gb_obc_fwd_f32")
@@ -351,6 +369,8 @@ class MMBackend:
         sv = as_implicit_solvent(solvent)
         if sv is None or not isinstance(gb, GBBatch):
             raise TypeError(f"relax_steps_gb: gb must be a GBBatch and solvent a model, got {type(gb).__name__}, {solvent!r}")
+        if sv.cutoff is not None:
+            raise ValueError("relax_steps_gb: the implicit solvent's cutoff serves the energy entry and the stepwise dynamics: the minimiser does not run under it")
         if nb is None:
             raise ValueError("relax_steps_gb: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
         gb.check_offset(sv.offset)
@@ -519,29 +539,36 @@ class MMBackend:
 
     def md_steps_gb(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                     frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000, workspace=None,
-                    constraints=None, constrain_start=True, gb=None, solvent="obc2", esolv=None, frames_esolv=None) -> None:
-        """`md_steps_cons` in GB/SA implicit solvent (include/grappa_hip.h grappa_md_steps_*_gb_f32): its arguments without the cutoff
-        (GB under a cutoff is not implemented) plus gb, a `grappa_amd.solvent.GBBatch` on xyz's device holding the batch's molecules in
+                    constraints=None, constrain_start=True, gb=None, solvent="obc2", esolv=None, frames_esolv=None, cutoff=None) -> None:
+        """`md_steps_cons` in GB/SA implicit solvent (include/grappa_hip.h grappa_md_steps_*_gb_f32): its arguments (the cutoff last, see
+        below) plus gb, a `grappa_amd.solvent.GBBatch` on xyz's device holding the batch's molecules in
         order, and solvent, a model name or an `ImplicitSolvent`.  nb is required: it carries the charges.  constraints may be None.
         epot then includes the solvent term; esolv (B,C) and frames_esolv (F,B,C) float32 or None -> the solvent term alone.  A step is
         five launches, six with constraints; the workspace is `grappa_md_steps_gb_workspace_bytes`.  Like `md_steps` it has NO device
-        sync."""
+        sync.
+        A solvent with a cutoff of its own (`ImplicitSolvent(cutoff=)`, `solvent.cut_opts()`) runs the grappa_md_steps_*_gbcut_f32
+        calls: the three passes under that cutoff, far tiles skipped.  cutoff: the NONBONDED cutoff (a `Cutoff` or a distance), taken
+        only beside a solvent that has a cutoff; one set of boxes serves both."""
         from .solvent import GBBatch, as_implicit_solvent
         sv = as_implicit_solvent(solvent)
         if sv is None or not isinstance(gb, GBBatch):
             raise TypeError(f"md_steps_gb: gb must be a GBBatch and solvent a model, got {type(gb).__name__}, {solvent!r}")
+        if cutoff is not None and sv.cutoff is None:
+            raise ValueError("md_steps_gb: a nonbonded cutoff beside the implicit solvent needs a solvent with a cutoff of its own "
+                             "(ImplicitSolvent(cutoff=))")
         if nb is None:
             raise ValueError("md_steps_gb: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
         gb.check_offset(sv.offset)
         self._md_steps("md_steps_gb", plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
-                       steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, None, constraints,
+                       steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
                        constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv)
 
     def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                   frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start,
                   gb=None, solvent=None, esolv=None, frames_esolv=None):
         """init, the run calls and finish of one stepwise run: the plain calls, the _cut_ calls with a cutoff, the _cons_ calls with
-        constraints (and the cutoff or NULL), the _gb_ calls with an implicit solvent (and the constraints or NULL)"""
+        constraints (and the cutoff or NULL), the _gb_ calls with an implicit solvent (and the constraints or NULL), the _gbcut_ calls with
+        a solvent that carries a cutoff (and the nonbonded cutoff or NULL)"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
         d, o = self._md_call(who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
@@ -566,10 +593,14 @@ class MMBackend:
                     or (frames_esolv is not None and frames_esolv.numel() != F_ * B * Cc):
                 raise ValueError(f"{who}: expected gb.radius / gb.scale ({N},), esolv (B,C), frames_esolv ({F_},B,C)")
             gbd = _lib.GbDesc(radius=gb.radius.data_ptr(), scale=gb.scale.data_ptr(), **solvent.as_opts())
+            gco = solvent.cut_opts()
+            gbc = None if gco is None else _opts_struct(_lib.GbCut, gco, f"{who}: the solvent's cutoff")
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        if gbd is not None:
+        if gbd is not None and gbc is not None:
+            need = int(self.lib.grappa_md_steps_gbcut_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
+        elif gbd is not None:
             need = int(self.lib.grappa_md_steps_gb_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
         elif cons is not None:
             need = int(self.lib.grappa_md_steps_cons_workspace_bytes(N, Cc, B, n_blocks, cons.K, int(cut is not None)))
@@ -580,7 +611,10 @@ class MMBackend:
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if gbd is not None:
+        if gbd is not None and gbc is not None:
+            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons) if cons is not None else None,
+                         C.byref(gbd), C.byref(gbc)), "_gbcut_f32"
+        elif gbd is not None:
             head, sfx = (st, C.byref(d), ndp, None, C.byref(o), C.byref(cons) if cons is not None else None, C.byref(gbd)), "_gb_f32"
         elif cons is not None:
             head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons)), "_cons_f32"

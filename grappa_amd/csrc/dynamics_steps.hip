@@ -706,9 +706,17 @@ __global__ __launch_bounds__(256) void ms_out_kernel(MsOutArgs a) {
 //            is read only across a launch boundary.  The flag word is the block's own, written by the force launch before.
 //   energies: grappa_gb_obc_fwd_f32 itself at the held coordinates, in a workspace region of its own (steps_gb_terms_at of
 //            csrc/rs_force.h), and one small launch that adds the eight terms in double in term order.
+//   cutoff  : grappa_md_steps_*_gbcut_f32 (include/grappa_hip.h grappa_gb_cut).  The three passes run under the GbCut policy of
+//            csrc/gb_loop.h -- the text the energy entry instantiates -- and read the boxes that the launches of a nonbonded cutoff
+//            write: rs_box_kernel in init and behind a constrained move, the move launch itself otherwise.  ONE set of boxes serves
+//            both cutoffs; the nonbonded cutoff may be given beside the solvent's (the force launch is then its NbCut instantiation,
+//            untouched) or not.  A step gains no launch over the all-pairs solvent step except the box launch behind a constrained
+//            move, which a nonbonded cutoff adds as well.  Energies: grappa_gb_obc_fwd_cut_f32 itself (steps_gb_cut_terms_at).
 struct MsGb {
     const grappa_gb_desc* opts;
     GbK k;
+    const grappa_gb_cut* cut;            // NULL: all pairs
+    GbCutDev cdev;                       // (box is set once the workspace is laid out)
 };
 
 struct MsGbWs {
@@ -721,14 +729,15 @@ struct MsGbWs {
 };
 
 // (the words of the solvent lie behind all others: `off` = the total of ms_layout)
-MsGbWs ms_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks) {
+MsGbWs ms_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks, bool gbcut = false) {
     MsGbWs g;
     WsCarve k{base};
     k.off = off;
     g.p = gb_pass_ws(k, N, C);
     g.ggb = k.take<float>((size_t)N * C * 3);
     g.e_gb = k.take<float>((size_t)B * C), g.terms_gb = k.take<float>(2 * (size_t)B * C);
-    g.fwd_bytes = grappa_gb_obc_workspace_bytes(N, C, n_blocks > 0 ? n_blocks : 1);
+    g.fwd_bytes = gbcut ? grappa_gb_obc_cut_workspace_bytes(N, C, n_blocks > 0 ? n_blocks : 1)
+                        : grappa_gb_obc_workspace_bytes(N, C, n_blocks > 0 ? n_blocks : 1);
     g.fwd = k.take<char>(g.fwd_bytes);
     g.total = k.off;
     return g;
@@ -753,44 +762,68 @@ struct MsGbCloseArgs {
     float hk;                // dt / 2 ACC; 0: no closing kick (init)
 };
 
-// CONS: the kinetic partial is left to the close launch, which follows the closing P
+// the chain launch's epilogue (gb_chain_body's epi); CONS: the kinetic partial is left to the close launch, which follows the closing P
+template <bool CONS>
+__device__ __forceinline__ void ms_gb_close(const MsGbCloseArgs& c, GbShared& sh, const GbLane& w, float cx, float cy, float cz) {
+    const int C = c.a.q.C, ni = w.r.ni;
+    float mv2 = 0.f, bad = 0.f;
+    if (w.owner) {
+        const size_t off = ((size_t)w.i * C + w.c) * 3;
+        const V3 gi = {(c.g[off] + c.a.gdir[off]) + cx, (c.g[off + 1] + c.a.gdir[off + 1]) + cy, (c.g[off + 2] + c.a.gdir[off + 2]) + cz};
+        c.g[off] = gi.x, c.g[off + 1] = gi.y, c.g[off + 2] = gi.z;
+        const float m = c.mass[w.i];
+        V3 vi = {c.v[off], c.v[off + 1], c.v[off + 2]};
+        if (m > 0.f) {
+            if (c.hk > 0.f) {          // the closing B of the step
+                vi = vi - (c.hk * (1.0f / m)) * gi;
+                c.v[off] = vi.x, c.v[off + 1] = vi.y, c.v[off + 2] = vi.z;
+            }
+            mv2 = m * dot(vi, vi);
+        }
+        if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;      // (written so that a NaN counts as non-finite)
+    }
+    __syncthreads();
+    if (w.owner) sh.red[0][w.l] = mv2, sh.red[1][w.l] = bad;
+    __syncthreads();
+    if (w.owner && w.il == 0) {      // the block's words of one conformation: over its atoms in ascending order, in double
+        double sk = 0.0;
+        float fb = 0.f;
+        for (int k = 0; k < ni; ++k) {
+            const int o = w.cl * ni + k;
+            sk += (double)sh.red[0][o];
+            fb = fmaxf(fb, sh.red[1][o]);
+        }
+        const size_t o = (size_t)w.r.blk * C + w.c;
+        if constexpr (!CONS) c.kpart[o] = sk;
+        if (fb != 0.f) c.bad[o] |= 1;          // (the block's own word, which the force launch before this one wrote)
+    }
+}
+
 template <bool CONS>
 __global__ __launch_bounds__(NB_NT) void ms_gb_chain_kernel(MsGbCloseArgs c) {
     __shared__ GbShared sh;
-    gb_chain_body<true>(c.a, sh, [&](const GbLane& w, float cx, float cy, float cz) {
-        const int C = c.a.q.C, ni = w.r.ni;
-        float mv2 = 0.f, bad = 0.f;
-        if (w.owner) {
-            const size_t off = ((size_t)w.i * C + w.c) * 3;
-            const V3 gi = {(c.g[off] + c.a.gdir[off]) + cx, (c.g[off + 1] + c.a.gdir[off + 1]) + cy, (c.g[off + 2] + c.a.gdir[off + 2]) + cz};
-            c.g[off] = gi.x, c.g[off + 1] = gi.y, c.g[off + 2] = gi.z;
-            const float m = c.mass[w.i];
-            V3 vi = {c.v[off], c.v[off + 1], c.v[off + 2]};
-            if (m > 0.f) {
-                if (c.hk > 0.f) {          // the closing B of the step
-                    vi = vi - (c.hk * (1.0f / m)) * gi;
-                    c.v[off] = vi.x, c.v[off + 1] = vi.y, c.v[off + 2] = vi.z;
-                }
-                mv2 = m * dot(vi, vi);
-            }
-            if (!(sqrtf(dot(gi, gi)) <= FLT_MAX)) bad = 1.f;      // (written so that a NaN counts as non-finite)
-        }
-        __syncthreads();
-        if (w.owner) sh.red[0][w.l] = mv2, sh.red[1][w.l] = bad;
-        __syncthreads();
-        if (w.owner && w.il == 0) {      // the block's words of one conformation: over its atoms in ascending order, in double
-            double sk = 0.0;
-            float fb = 0.f;
-            for (int k = 0; k < ni; ++k) {
-                const int o = w.cl * ni + k;
-                sk += (double)sh.red[0][o];
-                fb = fmaxf(fb, sh.red[1][o]);
-            }
-            const size_t o = (size_t)w.r.blk * C + w.c;
-            if constexpr (!CONS) c.kpart[o] = sk;
-            if (fb != 0.f) c.bad[o] |= 1;          // (the block's own word, which the force launch before this one wrote)
-        }
-    });
+    gb_chain_body<true>(c.a, sh, [&](const GbLane& w, float cx, float cy, float cz) { ms_gb_close<CONS>(c, sh, w, cx, cy, cz); });
+}
+
+// the three passes under the solvent's cutoff: the bodies of the energy entry's cut kernels under the stopped-conformation mask
+__global__ __launch_bounds__(NB_NT) void ms_gb_born_cut_kernel(GbArgs a, GbCutDev d) {
+    __shared__ GbShared sh;
+    __shared__ unsigned char near[NB_NT];
+    gb_born_body<true, GbCut>(a, sh, GbCut{d, near, 0});
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_gb_pair_cut_kernel(GbArgs a, GbCutDev d) {
+    __shared__ GbShared sh;
+    __shared__ unsigned char near[NB_NT];
+    gb_pair_body<true, false, true, GbCut>(a, sh, GbCut{d, near, 0});
+}
+
+template <bool CONS>
+__global__ __launch_bounds__(NB_NT) void ms_gb_chain_cut_kernel(MsGbCloseArgs c, GbCutDev d) {
+    __shared__ GbShared sh;
+    __shared__ unsigned char near[NB_NT];
+    gb_chain_body<true, GbCut>(
+        c.a, sh, [&](const GbLane& w, float cx, float cy, float cz) { ms_gb_close<CONS>(c, sh, w, cx, cy, cz); }, GbCut{d, near, 0});
 }
 
 // the three solvent launches behind a force launch that gave no closing kick
@@ -801,6 +834,15 @@ void ms_launch_gb(hipStream_t st, const grappa_nb_desc* nb, const MsGb& gb, cons
     c.a.B = gw.p.B, c.a.dBdI = gw.p.dBdI, c.a.w = gw.p.w, c.a.gdir = gw.ggb, c.a.part = nullptr, c.a.born = nullptr, c.a.status = w.status;
     c.v = w.v, c.g = w.g, c.mass = mass, c.bad = w.bad, c.kpart = w.kpart, c.hk = hk;
     const dim3 grid((unsigned)n_items), block(NB_NT);
+    if (gb.cut) {
+        GbCutDev d = gb.cdev;
+        d.box = w.box;
+        GRAPPA_LAUNCH(ms_gb_born_cut_kernel, grid, block, 0, st, c.a, d);
+        GRAPPA_LAUNCH(ms_gb_pair_cut_kernel, grid, block, 0, st, c.a, d);
+        if (cons) GRAPPA_LAUNCH(ms_gb_chain_cut_kernel<true>, grid, block, 0, st, c, d);
+        else GRAPPA_LAUNCH(ms_gb_chain_cut_kernel<false>, grid, block, 0, st, c, d);
+        return;
+    }
     GRAPPA_LAUNCH(ms_gb_born_kernel, grid, block, 0, st, c.a);
     GRAPPA_LAUNCH(ms_gb_pair_kernel, grid, block, 0, st, c.a);
     if (cons) GRAPPA_LAUNCH(ms_gb_chain_kernel<true>, grid, block, 0, st, c);
@@ -891,9 +933,10 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
+    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
     if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
@@ -920,14 +963,14 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
                 const MscStartArgs sa = {q, w.x, w.v, mass, w.status, cn, cons->constrain_start != 0};
                 GRAPPA_LAUNCH(msc_start_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, sa);
             }
-            if (c) ms_launch_boxes(st, nb, q, w, n_items);
+            if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
             ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail);
             if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, true);
             msc_launch_close(st, q, w, cn, mass, 0, n_items);
         }
         return grappa_launch_status();
     }
-    if (c && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
+    if (boxes && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
     if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
     if (gb && n_items > 0) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, false);
     return grappa_launch_status();
@@ -944,9 +987,10 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
+    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
     if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
@@ -968,12 +1012,12 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             float* fx = due && frames_xyz ? frames_xyz + f * n3 : nullptr;
             if (cons) {          // move, boxes (with a cutoff), force, close: 3 launches, 4 under a cutoff
                 GRAPPA_LAUNCH(ms_move_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, cn);
-                if (c) ms_launch_boxes(st, nb, q, w, n_items);
+                if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
                 ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, w.cfail);
                 if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, true);
                 msc_launch_close(st, q, w, cn, mass, 1, n_items);
             } else {
-                if (c) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
+                if (boxes) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
                 else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
                 ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items);
                 if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, false);
@@ -984,7 +1028,8 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             if (terms) {          // (a frame that asks for the solvent's energy alone does not need the six terms)
                 int erc = frames_epot ? ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w) : GRAPPA_OK;
                 if (erc == GRAPPA_OK && gb)
-                    erc = steps_gb_terms_at(stream, mm, nb, gb->opts, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
+                    erc = steps_gb_cut_terms_at(stream, mm, nb, gb->opts, gb->cut, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd,
+                                                gw.fwd_bytes);
                 if (erc != GRAPPA_OK) return erc;
             }
             MsOutArgs a = ms_out_args(mm, nb, q, w);
@@ -1008,14 +1053,15 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, c != nullptr, cons != nullptr);
+    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
+    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks);
+    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
     if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
     if (erc == GRAPPA_OK && gb)
-        erc = steps_gb_terms_at(stream, mm, nb, gb->opts, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
+        erc = steps_gb_cut_terms_at(stream, mm, nb, gb->opts, gb->cut, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
     if (erc != GRAPPA_OK) return erc;
     MsOutArgs a = ms_out_args(mm, nb, rs_geom(mm, table_dev, n_blocks), w);
     a.final = 1, a.with_epot = 1;
@@ -1161,6 +1207,15 @@ int ms_gb_check(const grappa_gb_desc* gb, const grappa_nb_desc* nb, const grappa
     if (!gb) return 1;
     if (cut || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k)) return GRAPPA_ERR_ARG;
     g.opts = gb;
+    g.cut = nullptr;
+    return GRAPPA_OK;
+}
+
+// the solvent under its cutoff (gbcut != NULL): gb is required; the nonbonded cutoff may be given beside it
+int ms_gbcut_check(const grappa_gb_desc* gb, const grappa_gb_cut* gbcut, const grappa_nb_desc* nb, MsGb& g) {
+    if (!gb || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k) || !gb_cut_consts(gbcut, g.cdev)) return GRAPPA_ERR_ARG;
+    g.opts = gb;
+    g.cut = gbcut;
     return GRAPPA_OK;
 }
 }  // namespace
@@ -1213,5 +1268,60 @@ extern "C" int grappa_md_steps_finish_gb_f32(void* stream, const grappa_mm_desc*
     const int cc = msc_check(cons);
     if (cc < 0) return cc;
     return ms_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
+                     cc == 1 ? nullptr : cons, &g, esolv);
+}
+
+// with the solvent under its own cutoff (grappa_gb_cut): gbcut == NULL is the call above -- its launches, its bits, its refusals, that of
+// cut together with gb included.  With gbcut, gb is required and cut, the nonbonded cutoff, may be given too.
+extern "C" size_t grappa_md_steps_gbcut_workspace_bytes(int N, int C, int B, int n_blocks, int K) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
+    return ms_gb_layout(nullptr, ms_layout(nullptr, N, C, B, n_blocks, true, K > 0).total, N, C, B, n_blocks, true).total;
+}
+
+extern "C" int grappa_md_steps_init_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                              const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                              const grappa_gb_cut* gbcut, const float* mass, const unsigned long long* mol_key,
+                                              const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+    if (!gbcut) return grappa_md_steps_init_gb_f32(stream, mm, nb, cut, o, cons, gb, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    MsGb g;
+    RsCut c;
+    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cc == 1 ? nullptr : cons,
+                   &g);
+}
+
+extern "C" int grappa_md_steps_run_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                             const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                             const grappa_gb_cut* gbcut, const float* mass, const unsigned long long* mol_key,
+                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
+                                             float* frames_xyz, float* frames_epot, float* frames_ekin, float* frames_esolv) {
+    if (!gbcut)
+        return grappa_md_steps_run_gb_f32(stream, mm, nb, cut, o, cons, gb, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                                          frames_xyz, frames_epot, frames_ekin, frames_esolv);
+    MsGb g;
+    RsCut c;
+    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
+                  frames_epot, frames_ekin, cc == 1 ? nullptr : cons, &g, frames_esolv);
+}
+
+extern "C" int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                                const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                                const grappa_gb_cut* gbcut, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                                size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status,
+                                                float* esolv) {
+    if (!gbcut)
+        return grappa_md_steps_finish_gb_f32(stream, mm, nb, cut, o, cons, gb, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot,
+                                             ekin, steps, status, esolv);
+    MsGb g;
+    RsCut c;
+    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
                      cc == 1 ? nullptr : cons, &g, esolv);
 }

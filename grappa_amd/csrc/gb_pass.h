@@ -9,6 +9,8 @@
 //            the caller's epilogue
 // pair reads B of every j and chain reads w of every j, which other workgroups write: each pass boundary is a launch boundary.
 // MD (the dynamics): a conformation that has stopped (status != running) is neither loaded nor evaluated nor written, as in rs_force.
+// Cut (csrc/gb_loop.h; GbNoCut, the default, is the text as it was): under GbCut a pair with gb_r2 >= rc2 adds nothing to any of the
+// three sums -- the same fp32 r2 and the same test in all three, before any reciprocal or transcendental -- and a far tile is skipped.
 #pragma once
 #include <math.h>
 
@@ -69,10 +71,26 @@ __device__ inline bool gb_lane(const GbArgs& a, GbShared& sh, GbLane& w) {
     return true;
 }
 
-template <bool MD, class Pass>
-__device__ __forceinline__ void gb_pass_loop(const GbArgs& a, const GbLane& w, GbShared& sh, Pass& pass) {
-    if constexpr (MD) gb_tile_loop(a.x, w.r, a.q.C, w.s, w.JS, w.i, w.c, w.cl, w.active, sh.run, sh.xs, sh.ps, pass);
-    else gb_tile_loop(a.x, w.r, a.q.C, w.s, w.JS, w.i, w.c, w.cl, w.active, nullptr, sh.xs, sh.ps, pass);
+__device__ __forceinline__ float gb_cut_rc2(const GbNoCut&) { return 0.f; }
+__device__ __forceinline__ float gb_cut_rc2(const GbCut& cut) { return cut.c.rc2; }
+
+template <bool MD, class Pass, class Cut>
+__device__ __forceinline__ void gb_pass_loop(const GbArgs& a, const GbLane& w, GbShared& sh, Pass& pass, Cut& cut) {
+    if constexpr (MD) gb_tile_loop(a.x, w.r, a.q.C, w.s, w.JS, w.i, w.c, w.cl, w.active, sh.run, sh.xs, sh.ps, pass, cut);
+    else gb_tile_loop(a.x, w.r, a.q.C, w.s, w.JS, w.i, w.c, w.cl, w.active, nullptr, sh.xs, sh.ps, pass, cut);
+}
+
+// r2 of a pair and whether the pair is inside: without a cutoff the expression as it always stood (the compiler contracts it as it
+// likes), under one gb_r2 and the test of grappa_gb_cut (a NaN r2 is inside, and is found as a non-finite result)
+template <bool CUT>
+__device__ __forceinline__ bool gb_inside(float dx, float dy, float dz, float rc2, float& r2) {
+    if constexpr (CUT) {
+        r2 = gb_r2(dx, dy, dz);
+        return !(r2 >= rc2);
+    } else {
+        r2 = dx * dx + dy * dy + dz * dz;
+        return true;
+    }
 }
 
 // the slices of NV values of one (atom, conformation), added in slice order by the owner (one barrier)
@@ -89,30 +107,38 @@ __device__ inline void gb_slices(const GbLane& w, GbShared& sh, float (&v)[NV]) 
 }
 
 // ------------------------------------------------------------------------------------------------ born
+template <bool CUT>
 struct GbBornPass {
     const GbArgs& a;
     float oi, ioi, I;
+    float rc2;                    // (CUT)
     __device__ __forceinline__ float4 jatom(int j) const {
         const float o = a.radius[j] - a.k.offset;
         return make_float4(0.f, o, a.scale[j] * o, 0.f);
     }
     __device__ __forceinline__ float jconf(int, int) const { return 0.f; }
     __device__ __forceinline__ void pair(float dx, float dy, float dz, const float4& pj, float) {
-        const float r2 = dx * dx + dy * dy + dz * dz;
+        float r2;
+        if (!gb_inside<CUT>(dx, dy, dz, rc2, r2)) return;
         const float ir = gb_rsqrt(r2);
         I += gb_h(r2 * ir, ir, oi, ioi, pj.z);
     }
 };
 
-template <bool MD>
-__device__ __forceinline__ void gb_born_body(const GbArgs& a, GbShared& sh) {
+// tiles (Cut only): [n_items] or NULL, the tiles the item evaluated -- the same in all three passes, written here
+template <bool MD, class Cut = GbNoCut>
+__device__ __forceinline__ void gb_born_body(const GbArgs& a, GbShared& sh, Cut cut = Cut{}, int* tiles = nullptr) {
     GbLane w;
     if (!gb_lane<MD>(a, sh, w)) return;
+    if constexpr (Cut::on)
+        if (!nb_cut_blocks_ok(w.r, a.q.n_blocks)) return;
     const int C = a.q.C;
     const float R = a.radius[w.i], S = a.scale[w.i];
     const float o = R - a.k.offset;
-    GbBornPass pass{a, o, gb_rcp(o), 0.f};
-    gb_pass_loop<MD>(a, w, sh, pass);
+    GbBornPass<Cut::on> pass{a, o, gb_rcp(o), 0.f, gb_cut_rc2(cut)};
+    gb_pass_loop<MD>(a, w, sh, pass, cut);
+    if constexpr (Cut::on)
+        if (tiles && threadIdx.x == 0) tiles[blockIdx.x] = cut.count;
     float v[1] = {pass.I};
     gb_slices(w, sh, v);
     if (w.owner) {
@@ -136,15 +162,17 @@ __device__ __forceinline__ void gb_born_body(const GbArgs& a, GbShared& sh) {
 }
 
 // ------------------------------------------------------------------------------------------------ pair
-template <bool G>
+template <bool G, bool CUT>
 struct GbPairPass {
     const GbArgs& a;
     float qi, Bi;
+    float rc2;                    // (CUT)
     float e, db, gx, gy, gz;      // sum q_j / f, sum q_j B_j exp(-D) (1 + D) / f^3, sum q_j (1 - exp(-D)/4) / f^3 (x_i - x_j)
     __device__ __forceinline__ float4 jatom(int j) const { return make_float4(a.charge[j], 0.f, 0.f, 0.f); }
     __device__ __forceinline__ float jconf(int j, int c) const { return a.B[(size_t)j * a.q.C + c]; }
     __device__ __forceinline__ void pair(float dx, float dy, float dz, const float4& pj, float Bj) {
-        const float r2 = dx * dx + dy * dy + dz * dz;
+        float r2;
+        if (!gb_inside<CUT>(dx, dy, dz, rc2, r2)) return;
         const float P = Bi * Bj;
         const float D = 0.25f * r2 * gb_rcp(P);
         const float ex = expf(-D);
@@ -162,15 +190,17 @@ struct GbPairPass {
 };
 
 // G: the gradient at fixed B -> a.gdir; E: the block's energies -> a.part
-template <bool G, bool E, bool MD>
-__device__ __forceinline__ void gb_pair_body(const GbArgs& a, GbShared& sh) {
+template <bool G, bool E, bool MD, class Cut = GbNoCut>
+__device__ __forceinline__ void gb_pair_body(const GbArgs& a, GbShared& sh, Cut cut = Cut{}) {
     GbLane w;
     if (!gb_lane<MD>(a, sh, w)) return;
+    if constexpr (Cut::on)
+        if (!nb_cut_blocks_ok(w.r, a.q.n_blocks)) return;
     const int C = a.q.C;
     const size_t at = (size_t)w.i * C + w.c;
     const float qi = a.charge[w.i], Bi = a.B[at];
-    GbPairPass<G> pass{a, qi, Bi, 0.f, 0.f, 0.f, 0.f, 0.f};
-    gb_pass_loop<MD>(a, w, sh, pass);
+    GbPairPass<G, Cut::on> pass{a, qi, Bi, gb_cut_rc2(cut), 0.f, 0.f, 0.f, 0.f, 0.f};
+    gb_pass_loop<MD>(a, w, sh, pass, cut);
     float v[5] = {pass.e, pass.db, pass.gx, pass.gy, pass.gz};
     gb_slices(w, sh, v);
     float epol = 0.f, esa = 0.f;
@@ -206,17 +236,20 @@ __device__ __forceinline__ void gb_pair_body(const GbArgs& a, GbShared& sh) {
 }
 
 // ------------------------------------------------------------------------------------------------ chain
+template <bool CUT>
 struct GbChainPass {
     const GbArgs& a;
     float oi, si, wi;
     float gx, gy, gz;
+    float rc2;                    // (CUT)
     __device__ __forceinline__ float4 jatom(int j) const {
         const float o = a.radius[j] - a.k.offset;
         return make_float4(0.f, o, a.scale[j] * o, 0.f);
     }
     __device__ __forceinline__ float jconf(int j, int c) const { return a.w[(size_t)j * a.q.C + c]; }
     __device__ __forceinline__ void pair(float dx, float dy, float dz, const float4& pj, float wj) {
-        const float r2 = dx * dx + dy * dy + dz * dz;
+        float r2;
+        if (!gb_inside<CUT>(dx, dy, dz, rc2, r2)) return;
         const float ir = gb_rsqrt(r2);
         const float r = r2 * ir, ir2 = ir * ir;
         const float f = __builtin_fmaf(wi, gb_dh(r, ir2, oi, pj.z), wj * gb_dh(r, ir2, pj.y, si)) * ir;
@@ -228,14 +261,16 @@ struct GbChainPass {
 
 // epi(w, gx, gy, gz) runs in EVERY thread of an item that was not refused, after the barrier that follows the slices' words in sh.red
 // (the sums are the chain gradient only where w.owner); it may use barriers, and must pass one before it writes sh.red
-template <bool MD, class Epi>
-__device__ __forceinline__ void gb_chain_body(const GbArgs& a, GbShared& sh, Epi epi) {
+template <bool MD, class Cut = GbNoCut, class Epi>
+__device__ __forceinline__ void gb_chain_body(const GbArgs& a, GbShared& sh, Epi epi, Cut cut = Cut{}) {
     GbLane w;
     if (!gb_lane<MD>(a, sh, w)) return;
+    if constexpr (Cut::on)
+        if (!nb_cut_blocks_ok(w.r, a.q.n_blocks)) return;
     const size_t at = (size_t)w.i * a.q.C + w.c;
     const float o = a.radius[w.i] - a.k.offset;
-    GbChainPass pass{a, o, a.scale[w.i] * o, a.w[at], 0.f, 0.f, 0.f};
-    gb_pass_loop<MD>(a, w, sh, pass);
+    GbChainPass<Cut::on> pass{a, o, a.scale[w.i] * o, a.w[at], 0.f, 0.f, 0.f, gb_cut_rc2(cut)};
+    gb_pass_loop<MD>(a, w, sh, pass, cut);
     float v[3] = {pass.gx, pass.gy, pass.gz};
     gb_slices(w, sh, v);
     epi(w, v[0], v[1], v[2]);

@@ -139,16 +139,20 @@ __device__ inline float nb_cut_gap2(const float4 lo_i, const float4 hi_i, const 
 
 // The verdicts of the item's tiles jt0 .. jt0 + NB_NT - 1 (those below ntiles) -> near[0 .. NB_NT): thread t takes tile jt0 + t.  Every
 // thread of the workgroup calls it; two barriers (the first lets the readers of the previous verdicts finish).  blk: the item's block,
-// kb0: the first block of its molecule, run: which of its nc conformations still run (NULL: all).
-__device__ inline void nb_cut_decide(const NbCutDev& c, int C, int blk, int kb0, int ntiles, int jt0, int c0, int nc, const int* run,
+// kb0: the first block of its molecule, run: which of its nc conformations still run (NULL: all).  ER = false: the boxes alone decide (the
+// implicit solvent of csrc/gb_loop.h, which knows no exceptions; Dev then needs thr, prune and box only).
+template <bool ER = true, class Dev>
+__device__ inline void nb_cut_decide(const Dev& c, int C, int blk, int kb0, int ntiles, int jt0, int c0, int nc, const int* run,
                                      unsigned char* near) {
     const int t = threadIdx.x, jt = jt0 + t;
     __syncthreads();
     if (jt < ntiles) {
         bool ev = c.prune == 0;
-        if (!ev) {
-            const int2 e = c.er[blk];
-            ev = jt >= e.x && jt <= e.y;
+        if constexpr (ER) {
+            if (!ev) {
+                const int2 e = c.er[blk];
+                ev = jt >= e.x && jt <= e.y;
+            }
         }
         for (int cc = 0; cc < nc && !ev; ++cc) {
             if (run && !run[cc]) continue;

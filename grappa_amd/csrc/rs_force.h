@@ -141,6 +141,18 @@ inline int steps_gb_terms_at(void* stream, const grappa_mm_desc* mm, const grapp
     return grappa_gb_obc_fwd_f32(stream, &ne, gb, table_dev, n_items, n_blocks, e_gb, terms_gb, nullptr, nullptr, gbws, gbws_bytes);
 }
 
+// ... under the solvent's cutoff (gbcut == NULL: the call above): grappa_gb_obc_fwd_cut_f32 itself, no second energy path
+inline int steps_gb_cut_terms_at(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_gb_desc* gb,
+                                 const grappa_gb_cut* gbcut, const int* table_dev, int n_items, int n_blocks, const float* x, float* e_gb,
+                                 float* terms_gb, void* gbws, size_t gbws_bytes) {
+    if (!gbcut) return steps_gb_terms_at(stream, mm, nb, gb, table_dev, n_items, n_blocks, x, e_gb, terms_gb, gbws, gbws_bytes);
+    grappa_nb_desc ne = *nb;
+    ne.xyz = x;
+    ne.atom_molptr = mm->atom_molptr;
+    return grappa_gb_obc_fwd_cut_f32(stream, &ne, gb, gbcut, table_dev, n_items, n_blocks, e_gb, terms_gb, nullptr, nullptr, nullptr, gbws,
+                                     gbws_bytes);
+}
+
 // ------------------------------------------------------------------------------------------------ a cutoff on the stepwise paths
 // a cutoff as the three calls of a stepwise path carry it: the caller's options and the device constants made of them
 struct RsCut {

@@ -29,6 +29,12 @@ Implicit solvent (`implicit_solvent=`, `grappa_amd.solvent`): the GB/SA term of 
 the stepwise path only (`grappa_md_steps_*_gb_f32` through `HipBackend.md_steps_gb`): three more passes of the tiled pair loop behind
 the force launch, a step of five launches, six with constraints.  It needs `nonbonded` (the charges) and the per-atom radii and scales
 (`gb=`), goes with constraints and not with a cutoff; `stepwise="auto"` goes stepwise whenever it is given.
+A solvent with a cutoff of its own, `implicit_solvent=ImplicitSolvent("obc2", cutoff=12.0)`, runs under the pairwise truncation of
+`grappa_amd.solvent` (`grappa_md_steps_*_gbcut_f32`): far tiles are skipped in all three passes, and a step gains no launch (with
+constraints the box launch that a nonbonded cutoff adds as well).  Beside such a solvent -- and only beside it -- `cutoff=` is taken too:
+the nonbonded cutoff of the paragraph above, on one set of boxes.  A reaction field already screens the Coulomb term; OpenMM runs GB
+with the reaction-field dielectric 1, so `cutoff=Cutoff(rc, rs, rf_dielectric=1.0)` is the usual companion (what the caller passes is
+not overridden).  The truncated solvent energy jumps where a pair crosses the cutoff: such a run does not conserve energy.
 
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
@@ -182,7 +188,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum, the calls made are exactly those without
     this argument) -- the GB/SA term of `grappa_amd.solvent` added to the potential, with gb, the batch's `grappa_amd.solvent.GBBatch`
     on the graph's device (radius and scale per atom).  It needs `nonbonded` (the charges) and the stepwise path: "auto" then goes
-    stepwise whatever the sizes, stepwise=False is refused; constraints go with it, a cutoff does not (ValueError).  The result's
+    stepwise whatever the sizes, stepwise=False is refused; constraints go with it, a cutoff does not (ValueError) unless the solvent
+    carries a cutoff of its own (`ImplicitSolvent(cutoff=)`: the solvent is truncated pairwise, and `cutoff=` beside it is taken).  The result's
     potential energies include the solvent term; `esolv` / `frames_esolv` hold it alone."""
     from .backend import get_backend
     from .solvent import GBBatch, as_implicit_solvent
@@ -191,7 +198,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     cutoff = as_cutoff(cutoff)
     solvent = as_implicit_solvent(implicit_solvent)
     if solvent is not None:
-        if cutoff is not None:
+        if cutoff is not None and solvent.cutoff is None:          # (beside a solvent that has a cutoff of its own it is taken)
             raise ValueError("simulate: an implicit solvent under a cutoff is not implemented: pass one of the two")
         if nonbonded is None:
             raise ValueError("simulate: an implicit solvent needs the nonbonded parameters (nonbonded=): they carry the charges")
@@ -295,7 +302,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         if solvent is not None:
             get_backend().md_steps_gb(*args, steps_per_call=chunk, **kw, constraints=constraints,
                                       constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
-                                      frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None)
+                                      frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None,
+                                      **({} if cutoff is None else {"cutoff": cutoff}))
         elif use_steps and constraints is not None:
             get_backend().md_steps_cons(*args, steps_per_call=chunk, **kw, **({} if cutoff is None else {"cutoff": cutoff}),
                                         constraints=constraints, constrain_start=bool(constrain_start) and launch == 0)
@@ -351,7 +359,7 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
     cutoff = as_cutoff(cutoff)
     solvent = as_implicit_solvent(implicit_solvent)
     if solvent is not None:
-        if cutoff is not None:
+        if cutoff is not None and solvent.cutoff is None:          # (beside a solvent that has a cutoff of its own it is taken)
             raise ValueError("simulate: an implicit solvent under a cutoff is not implemented: pass one of the two")
         if nonbonded is None:
             raise ValueError("simulate: an implicit solvent needs the nonbonded parameters (nonbonded=): they carry the charges")

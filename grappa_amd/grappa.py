@@ -101,7 +101,9 @@ class Grappa:
         implicit_solvent: "obc2", "obc1" or a `grappa_amd.solvent.ImplicitSolvent` (None: vacuum): the GB/SA term of
         `grappa_amd.solvent` with the mbondi2 radii and OBC screening factors of the molecule's elements and bonds
         (`GBParameters.from_elements`; gb= in **kw overrides them); it needs `nonbonded` and stepwise="auto" (or True), goes with
-        constraints and not with a cutoff (`implicit_solvent="obc2", constraints="h-bonds", stepwise="auto"`)"""
+        constraints and not with a cutoff (`implicit_solvent="obc2", constraints="h-bonds", stepwise="auto"`) -- unless the solvent
+        carries a cutoff of its own: `implicit_solvent=ImplicitSolvent("obc2", cutoff=12.0)` truncates the solvent pairwise and skips
+        far tiles, and then `cutoff=` (usually `Cutoff(rc, rs, rf_dielectric=1.0)`) is taken beside it"""
         from .dynamics import simulate
         if cutoff is not None:
             kw = {**kw, "cutoff": cutoff}

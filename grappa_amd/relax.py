@@ -124,6 +124,9 @@ def _solvent_options(implicit_solvent, gb, nonbonded, stepwise, restraints, cuto
         if gb is not None:
             raise ValueError("relax: gb= needs implicit_solvent=")
         return None
+    if solvent.cutoff is not None:
+        raise ValueError("relax: the implicit solvent's cutoff (ImplicitSolvent(cutoff=)) serves the energy entry and the stepwise dynamics: the "
+                         "minimiser does not run under it, and does not silently minimise on the all-pairs surface")
     if cutoff is not None:
         raise ValueError("relax: an implicit solvent under a cutoff is not implemented: pass one of the two")
     if nonbonded is None:

@@ -8,8 +8,15 @@ with the charge q_i of the nonbonded parameters, a radius R_i and a scale S_i pe
     E_sa  = sum_i 4 pi surface_tension (R_i + probe)^2 (R_i / B_i)^6
 
 "obc2" is (alpha, beta, gamma) = (1, 0.8, 4.85), "obc1" is (0.8, 0, 2.909125).  The gradient is the exact +dE/dxyz (not the force).
-The arithmetic runs in csrc/gb_obc.hip through `HipBackend.gb_obc`; there is no CPU evaluator.  Out of scope: a cutoff, the HCT and
-GBn models, a salt term.
+The arithmetic runs in csrc/gb_obc.hip through `HipBackend.gb_obc`; there is no CPU evaluator.
+
+`ImplicitSolvent(cutoff=rc)` truncates the model pairwise, as OpenMM's `GBSAOBCForce` does under `CutoffNonPeriodic`: an ordered pair
+i != j counts in I_i, in E_pol and in the chain rule only if r_ij < rc; the terms i = j and E_sa are not cut; nothing is shifted or
+switched, so the energy jumps by the pair's terms where a pair crosses rc, and Born radii under a short cutoff differ from the all-pairs
+ones.  Far 64 x 64 tiles are skipped (prune=True; the same bits as prune=False).  The cutoff serves the energy (`GBBatch.evaluate`,
+`solvent_energy`) and the stepwise dynamics (`simulate(..., implicit_solvent=ImplicitSolvent(cutoff=))`); the minimiser refuses a
+solvent that carries one.  Out of scope: the HCT and GBn models, a salt term, a smoothed truncation, a separate cutoff for the Born
+integral.
 """
 import math
 from dataclasses import dataclass
@@ -34,13 +41,16 @@ def _num(v) -> bool:
 @dataclass(frozen=True)
 class ImplicitSolvent:
     """the options of the GB/SA model (grappa_gb_desc): model "obc2" or "obc1"; the dielectrics finite and > 0; surface_tension
-    (kcal/mol/A^2; 0.0054 is OpenMM's 2.25936 kJ/mol/nm^2) and probe (A) finite and >= 0; offset (A) finite and >= 0"""
+    (kcal/mol/A^2; 0.0054 is OpenMM's 2.25936 kJ/mol/nm^2) and probe (A) finite and >= 0; offset (A) finite and >= 0; cutoff (A): None
+    (all pairs) or finite and > 0 with a square float32 holds (grappa_gb_cut); prune: skip far tiles (the same bits either way)"""
     model: str = "obc2"
     solute_dielectric: float = 1.0
     solvent_dielectric: float = 78.5
     surface_tension: float = 0.0054
     probe: float = 1.4
     offset: float = 0.09
+    cutoff: Optional[float] = None
+    prune: bool = True
 
     def __post_init__(self):
         if self.model not in MODELS:
@@ -51,12 +61,24 @@ class ImplicitSolvent:
         for k in ("surface_tension", "probe", "offset"):
             if not _num(getattr(self, k)) or getattr(self, k) < 0:
                 raise ValueError(f"implicit solvent: {k} must be a finite number >= 0, got {getattr(self, k)!r}")
+        if self.cutoff is not None:
+            ok = _num(self.cutoff) and self.cutoff > 0 and float(self.cutoff) * float(self.cutoff) <= float(np.finfo(np.float32).max)
+            if not ok:
+                raise ValueError(f"implicit solvent: cutoff must be None or a finite number > 0 whose square float32 holds, got {self.cutoff!r}")
+        if not isinstance(self.prune, (bool, np.bool_)):
+            raise ValueError(f"implicit solvent: prune must be True or False, got {self.prune!r}")
 
     def as_opts(self) -> dict:
         """the eight options of grappa_gb_desc by name"""
         a, b, g = MODELS[self.model]
         return {"offset": float(self.offset), "alpha": a, "beta": b, "gamma": g, "eps_in": float(self.solute_dielectric),
                 "eps_out": float(self.solvent_dielectric), "surface_tension": float(self.surface_tension), "probe": float(self.probe)}
+
+    def cut_opts(self) -> Optional[dict]:
+        """None without a cutoff, else the two options of grappa_gb_cut by name"""
+        if self.cutoff is None:
+            return None
+        return {"cutoff": float(self.cutoff), "prune": int(bool(self.prune))}
 
 
 def as_implicit_solvent(solvent: Union[None, str, "ImplicitSolvent"]) -> Optional["ImplicitSolvent"]:
@@ -144,10 +166,12 @@ class GBBatch:
             setattr(self, k, getattr(self, k).to(device))
         return self
 
-    def evaluate(self, nb, xyz: torch.Tensor, solvent="obc2", terms: bool = False, gradient: bool = True, born_radii: bool = False):
+    def evaluate(self, nb, xyz: torch.Tensor, solvent="obc2", terms: bool = False, gradient: bool = True, born_radii: bool = False,
+                 tiles: bool = False):
         """nb: the `NonbondedBatch` of the same molecules on the same device (its charges, atom_molptr and cache of plans); xyz (N, C, 3)
         float32 there -> dict of energy (B, C), grad (N, C, 3) or None, terms (2, B, C: polar, surface area) or None, born (N, C) or
-        None"""
+        None, tiles (n_items,) int32 or None.  A solvent with a cutoff runs grappa_gb_obc_fwd_cut_f32; tiles=True (which needs one)
+        returns the 64 x 64 tiles each work item of the plan evaluated."""
         from .backend import get_backend
         solvent = as_implicit_solvent(solvent)
         if solvent is None:
@@ -167,16 +191,27 @@ class GBBatch:
         grad = torch.zeros_like(xyz) if gradient else None
         te = torch.zeros(2, self.B, C, dtype=torch.float32, device=xyz.device) if terms else None
         born = torch.zeros(self.N, C, dtype=torch.float32, device=xyz.device) if born_radii else None
-        be.gb_obc(xyz, nb.atom_molptr, nb.charge, self.radius, self.scale, solvent.as_opts(), energy, te, grad, born, plan=plan)
-        return {"energy": energy, "grad": grad, "terms": te, "born": born}
+        cut = solvent.cut_opts()
+        if cut is None:
+            if tiles:
+                raise ValueError("GBBatch.evaluate: tiles needs a solvent with a cutoff")
+            be.gb_obc(xyz, nb.atom_molptr, nb.charge, self.radius, self.scale, solvent.as_opts(), energy, te, grad, born, plan=plan)
+            return {"energy": energy, "grad": grad, "terms": te, "born": born, "tiles": None}
+        nt = torch.zeros(int(plan[1]) if plan[0] is not None else 0, dtype=torch.int32, device=xyz.device) if tiles else None
+        be.gb_obc(xyz, nb.atom_molptr, nb.charge, self.radius, self.scale, solvent.as_opts(), energy, te, grad, born, plan=plan, cut=cut,
+                  tiles=nt)
+        return {"energy": energy, "grad": grad, "terms": te, "born": born, "tiles": nt}
 
 
-def solvent_energy(nonbonded_params, gb_params, xyz, device="cuda", model="obc2", terms: bool = False, born_radii: bool = False):
+def solvent_energy(nonbonded_params, gb_params, xyz, device="cuda", model="obc2", terms: bool = False, born_radii: bool = False,
+                   tiles: bool = False):
     """Solvation energies and gradients of one molecule or a list of molecules, numpy in and out.  nonbonded_params: the
     `NonbondedParameters` (they carry the charges); gb_params: the `GBParameters`; xyz: (n_confs, n_atoms, 3) in Angstrom, or a list
     of such arrays sharing n_confs; model: "obc2", "obc1" or an `ImplicitSolvent`.
     -> (energy (n_confs,), gradient (n_confs, n_atoms, 3)) in kcal/mol and kcal/mol/A, with terms=True followed by the polar and the
-    surface-area part of the energy, with born_radii=True by the Born radii (n_confs, n_atoms) in A; for a list, a list of such tuples."""
+    surface-area part of the energy, with born_radii=True by the Born radii (n_confs, n_atoms) in A; for a list, a list of such tuples.
+    An `ImplicitSolvent` with a cutoff is evaluated under it; tiles=True (which needs one) then returns (that result, tiles): the second
+    the int array of 64 x 64 tiles each work item of the batch evaluated."""
     from .nonbonded import NonbondedBatch, NonbondedParameters
     solvent = as_implicit_solvent(model)
     if solvent is None:
@@ -195,7 +230,7 @@ def solvent_energy(nonbonded_params, gb_params, xyz, device="cuda", model="obc2"
     gb = GBBatch(glist, solvent.offset).to(device)
     nb = NonbondedBatch(plist).to(device)
     flat = np.concatenate([x.transpose(1, 0, 2) for x in xs], axis=0).astype(np.float32)
-    out = gb.evaluate(nb, torch.from_numpy(np.ascontiguousarray(flat)).to(device), solvent, terms=terms, born_radii=born_radii)
+    out = gb.evaluate(nb, torch.from_numpy(np.ascontiguousarray(flat)).to(device), solvent, terms=terms, born_radii=born_radii, tiles=tiles)
     energy, grad = out["energy"].cpu().numpy(), out["grad"].cpu().numpy()
     te = out["terms"].cpu().numpy() if terms else None
     born = out["born"].cpu().numpy() if born_radii else None
@@ -208,4 +243,5 @@ def solvent_energy(nonbonded_params, gb_params, xyz, device="cuda", model="obc2"
         if born_radii:
             r = r + (born[ptr[b]:ptr[b + 1]].T.astype(np.float64),)
         res.append(r)
-    return res[0] if single else res
+    res = res[0] if single else res
+    return (res, out["tiles"].cpu().numpy()) if tiles else res

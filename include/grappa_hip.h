@@ -584,7 +584,8 @@ int grappa_nonbonded_fwd_cut_f32(void* stream, const grappa_nb_desc* d, const gr
  * grappa_gb_obc_workspace_bytes: GRAPPA_ERR_WORKSPACE.  radius and scale are device memory, which the host cannot read: an atom with
  * radius <= offset or scale <= 0 (or either non-finite) makes every result of its molecule NaN -- the Python layer refuses such
  * parameters before anything is uploaded.  A table made for another batch is walked away from item by item, as in the calls above.
- * N == 0, C == 0 or B == 0: returns 0 without a launch.  Not here: a cutoff or tile pruning, HCT / GBn, a salt term. */
+ * N == 0, C == 0 or B == 0: returns 0 without a launch.  Not here: HCT / GBn, a salt term (a cutoff with tile pruning: grappa_gb_cut
+ * below). */
 typedef struct grappa_gb_desc {
     const float *radius, *scale;      /* [N], device: R_i in A (> offset), S_i (> 0) */
     float offset;                     /* A; OpenMM: 0.09 */
@@ -597,6 +598,39 @@ size_t grappa_gb_obc_workspace_bytes(int N, int C, int n_blocks);
 int grappa_gb_obc_fwd_f32(void* stream, const grappa_nb_desc* nb, const grappa_gb_desc* gb, const int* table_dev, int n_items, int n_blocks,
                           float* energy /*[B,C]*/, float* term_energy /*[2,B,C] polar, SA; may be NULL*/, float* grad /*[N,C,3]; may be NULL*/,
                           float* born /*[N,C]; may be NULL*/, void* ws, size_t ws_bytes);
+
+/* GB/SA under a cutoff (additions to ABI 11): the pairwise truncation of OpenMM's GBSAOBCForce under CutoffNonPeriodic.  The energy is
+ * grappa_gb_desc's with every sum over j != i restricted to the pairs inside:
+ *   I_i   = sum_{j != i, inside} H(r, o_i, s_j);   psi_i, B_i as above
+ *   E_pol = -(K/2) (1/eps_in - 1/eps_out) (sum_i q_i^2 / B_i + sum_{i != j, inside} q_i q_j / f_ij)      (the terms i = j are not cut)
+ *   E_sa  = sum_i 4 pi surface_tension (R_i + probe)^2 (R_i / B_i)^6                                           (not cut)
+ * A pair is inside unless r2 >= rc2, with the fp32 r2 = ((dx dx + dy dy) + dz dz) of d = x_i - x_j, products and sums rounded one by
+ * one in that order, and rc2 = (float)((double)cutoff * cutoff): a NaN r2 is therefore evaluated and found as a non-finite result, as
+ * above.  All three passes form this one r2 (one device function), test it the same way and use it in the pair's arithmetic, so that
+ * the chain rule differentiates the energy that born and pair evaluated: grad is the exact derivative of the energy above wherever no
+ * pair sits at the cutoff.  Nothing is shifted or switched: the energy JUMPS by the pair's terms where a pair crosses the cutoff (its H
+ * in both Born integrals and what they move, and its q_i q_j / f_ij), and the Born radii under a short cutoff differ from the
+ * all-pairs ones (an integral over fewer spheres: larger radii).
+ * prune: tile (i-block I, j-block J) of a work item is evaluated iff prune == 0 or, for a conformation of the item, NOT d2 > thr, with
+ * d2 the squared gap of the blocks' bounding boxes as grappa_nb_cut forms it (fp32, rounded one by one) and thr = (float)(rc2 (1 +
+ * 2^-18)); GB has no exceptions, so the boxes alone decide.  Every pair of a skipped tile has r2 >= rc2 (r2 has at most five roundings
+ * beside the gap's), so prune = 0 and prune = 1 give the same bits -- for finite coordinates: a NaN in ONE axis
+ * of a far block zeroes that axis' gap only, so its tile may still be skipped under prune = 1 where prune = 0 spreads the NaN to the
+ * far rows too (the NaN's own molecule is non-finite either way; grappa_nb_cut behaves alike).  tiles[k]: the tiles item k evaluated (the
+ * same in all three passes; the born pass writes it).
+ * One launch writes the boxes of every (block, conformation), then the passes follow as above: 5 launches, 4 with grad == NULL.
+ * GRAPPA_ERR_ARG, nothing launched and nothing written: gbcut == NULL, a cutoff that is not finite and > 0 or whose square overflows, a
+ * prune other than 0 or 1, n_blocks * C > INT_MAX, and every refusal of grappa_gb_obc_fwd_f32.  ws_bytes below
+ * grappa_gb_obc_cut_workspace_bytes (the words of grappa_gb_obc_workspace_bytes and behind them 32 n_blocks C bytes of boxes):
+ * GRAPPA_ERR_WORKSPACE. */
+typedef struct grappa_gb_cut {
+    float cutoff;   /* A, finite, > 0 */
+    int   prune;    /* 1: skip far tiles; 0: evaluate every tile -- the same bits */
+} grappa_gb_cut;
+size_t grappa_gb_obc_cut_workspace_bytes(int N, int C, int n_blocks);
+int grappa_gb_obc_fwd_cut_f32(void* stream, const grappa_nb_desc* nb, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                              const int* table_dev, int n_items, int n_blocks, float* energy, float* term_energy, float* grad, float* born,
+                              int* tiles /*[n_items] or NULL*/, void* ws, size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Relaxation under the full MM force field (additions to ABI 11): FIRE (Bitzek et al. 2006) with unit masses and semi-implicit Euler,
@@ -1034,6 +1068,40 @@ int grappa_md_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const 
                                   const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const int* table_dev,
                                   int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot,
                                   float* ekin, int* steps, int* status, float* esolv);
+
+/* The stepwise dynamics with the solvent under ITS cutoff (additions to ABI 11): the _gb_ calls with `const grappa_gb_cut* gbcut`
+ * directly after gb.  gbcut == NULL: each forwards to its _gb_ call -- its launches, its bits, its refusals, that of cut together with
+ * gb included.  With gbcut, gb is required, the solvent term is the truncated energy of grappa_gb_cut (born, pair and chain are the
+ * cut instantiations of the bodies grappa_gb_obc_fwd_cut_f32 launches, under the stopped-conformation mask), and cut, the NONBONDED
+ * cutoff, may be given too: the force launch is then what it is under a nonbonded cutoff without solvent, else what it is without one
+ * -- untouched either way.  A reaction field already screens; OpenMM runs GB with the reaction-field dielectric 1, so a grappa_nb_cut
+ * with rf_dielectric = 1 is the usual companion (the caller's choice: nothing is overridden).
+ * ONE set of boxes serves both cutoffs, written once per step by the launch that writes them under a nonbonded cutoff: the move
+ * launch, or with constraints the box launch behind the constrained move; in init the box launch in front of the force.
+ *   step : move (with the boxes), force, born, pair, chain: 5 launches as above; with constraints move, boxes, force, born, pair,
+ *          chain, close: 7 (the box launch is the one a nonbonded cutoff adds to a constrained step; giving cut as well adds nothing
+ *          more).  init gains the box launch.
+ * epot and esolv: the solvent's terms come from grappa_gb_obc_fwd_cut_f32 itself at the held coordinates, in a workspace region of its
+ * own; with cut the six others from grappa_nonbonded_fwd_cut_f32 as in the _cut_ calls.  No second energy path.
+ * The truncated energy jumps where a pair crosses the solvent's cutoff, so a run under it does not conserve energy (DESIGN.md section
+ * 22 gives the size of a jump).  The workspace is grappa_md_steps_gbcut_workspace_bytes (it holds the boxes and the region of
+ * grappa_nonbonded_fwd_cut_f32 whether cut is given or not); ws_bytes below what the call needs: GRAPPA_ERR_WORKSPACE.
+ * GRAPPA_ERR_ARG before anything else is looked at: gbcut without gb, a cutoff or prune grappa_gb_obc_fwd_cut_f32 refuses, options of
+ * cut that grappa_md_steps_*_cut_f32 refuses, and every refusal of the _gb_ calls but that of cut. */
+size_t grappa_md_steps_gbcut_workspace_bytes(int N, int C, int B, int n_blocks, int K);
+int grappa_md_steps_init_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                   const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                   const float* mass, const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
+                                   int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_steps_run_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                  const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                  const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks,
+                                  void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot,
+                                  float* frames_ekin, float* frames_esolv);
+int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                     const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                     const grappa_gb_cut* gbcut, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
+                                     float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status, float* esolv);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

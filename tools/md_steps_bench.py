@@ -44,6 +44,10 @@ elements, bonds, template charges and coordinates), bonded parameters made the w
 structure, random small torsions), Lennard-Jones parameters by element, and the mbondi2 radii and OBC scales of its elements.
 
     python tools/md_steps_bench.py --implicit-solvent obc2 [--out profiles/md_steps_gb_bench.txt]
+With --gb-cutoff R beside it the solvent step is also measured under the solvent's own cutoff (`ImplicitSolvent(cutoff=R)`, the
+grappa_md_steps_*_gbcut_f32 calls): prune = 1 and prune = 0, with --cutoff RC [--switch RS] also with the nonbonded cutoff
+`Cutoff(RC, RS, 1.0)` beside it, and the tiles the solvent's energy entry evaluates at the start coordinates:
+    python tools/md_steps_bench.py --implicit-solvent obc2 --gb-cutoff 10 [--cutoff 10] [--out profiles/md_steps_gb_cut_bench.txt]
 """
 import argparse
 import datetime
@@ -63,9 +67,10 @@ SIDES = {"pool": ("fused", "stepwise", "composed", "agreement"), "mid": ("stepwi
 CUT_SIDES = ("stepwise", "cut", "cut_noprune", "tiles")
 GB_SIDES = ("stepwise", "gb")
 GB_WORKLOADS = ("pool", "mid", "t4l", "big")
+GBCUT_SIDES = ("gbcut", "gbcut_noprune", "gbboth")          # the solvent under its own cutoff; gbboth: with the nonbonded cutoff beside it
 CONS_SIDES = ("free_1fs", "cons_2fs", "cons_1fs")
 CONS_DT = {"free_1fs": 0.001, "cons_2fs": 0.002, "cons_1fs": 0.001}
-STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
+STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:{s}" for w in GB_WORKLOADS for s in GBCUT_SIDES + ("gbtiles",)] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
          [f"{w}:{s}:{p}" for w in WORKLOADS[1:] for s in CONS_SIDES for p in ("pairs", "cut")]
 
 STAGE_LIMIT = 300      # seconds, every stage
@@ -200,17 +205,31 @@ def stage(args):
             be.nonbonded(x, nb.atom_molptr, nb.charge, nb.sigma, nb.epsilon, nb.exc_ptr, nb.exc_atom, nb.exc_qq, nb.exc_sigma, nb.exc_eps, e, None, None,
                          plan=plan, cutoff=Cutoff(args.cutoff, args.switch or None, prune=prune), tiles=t[prune])
         out["items"], out["tiles"], out["all_tiles"] = int(plan[1]), int(t[True].sum()), int(t[False].sum())
-    elif side in ("fused", "stepwise", "cut", "cut_noprune", "gb"):
+    elif side == "gbtiles":          # what the solvent's cut energy entry evaluates at the start coordinates, per work item
+        import numpy as np
+        from grappa_amd.solvent import GBBatch, GBParameters, ImplicitSolvent
+        gbb = GBBatch([_t4l()[3]] if which == "t4l" else [GBParameters(np.full(int(n), 1.7), np.full(int(n), 0.72)) for n in counts]).to("cuda")
+        x = g.nodes["n1"].data["xyz"].contiguous()
+        t = {p: gbb.evaluate(nb, x, ImplicitSolvent(args.implicit_solvent, cutoff=args.gb_cutoff, prune=p), gradient=False, tiles=True)["tiles"]
+             for p in (True, False)}
+        out["items"], out["tiles"], out["all_tiles"] = int(t[True].numel()), int(t[True].sum()), int(t[False].sum())
+    elif side in ("fused", "stepwise", "cut", "cut_noprune", "gb") + GBCUT_SIDES:
         sw = side != "fused"
         if side.startswith("cut"):
             plain = sim
             sim = lambda n, stepwise, **kw: plain(n, stepwise, cutoff=cut, **kw)      # noqa: E731
-        if side == "gb":
+        if side == "gb" or side in GBCUT_SIDES:
             import numpy as np
-            from grappa_amd.solvent import GBBatch, GBParameters
+            from grappa_amd.solvent import GBBatch, GBParameters, ImplicitSolvent
             gbb = GBBatch([_t4l()[3]] if which == "t4l" else [GBParameters(np.full(int(n), 1.7), np.full(int(n), 0.72)) for n in counts]).to("cuda")
             plain = sim
-            sim = lambda n, stepwise, **kw: plain(n, stepwise, implicit_solvent=args.implicit_solvent, gb=gbb, **kw)      # noqa: E731
+            sv, more = args.implicit_solvent, {}
+            if side in GBCUT_SIDES:
+                sv = ImplicitSolvent(args.implicit_solvent, cutoff=args.gb_cutoff, prune=side != "gbcut_noprune")
+            if side == "gbboth":          # the nonbonded cutoff beside it, reaction-field dielectric 1: OpenMM's companion of GB
+                from grappa_amd.nonbonded import Cutoff
+                more = {"cutoff": Cutoff(args.cutoff, args.switch or None, 1.0)}
+            sim = lambda n, stepwise, **kw: plain(n, stepwise, implicit_solvent=sv, gb=gbb, **more, **kw)      # noqa: E731
         n0 = be.lib.grappa_launch_count(0)
         r = sim(steps, sw)
         torch.cuda.synchronize()
@@ -267,6 +286,7 @@ def main():
     ap.add_argument("--constraints", action="store_true", help="measure X-H constraints on the stepwise path (see the module text)")
     ap.add_argument("--leaf-mass", type=float, default=CARBON, help="amu; the mass of the leaves with --constraints (the chain's own by default)")
     ap.add_argument("--implicit-solvent", default="", help="obc2 or obc1: measure the GB/SA implicit solvent on the stepwise path (see the module text)")
+    ap.add_argument("--gb-cutoff", type=float, default=0.0, help="A; with --implicit-solvent: also measure the solvent under this cutoff of its own")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -281,7 +301,7 @@ def main():
     def run(name):
         cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
               [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
-                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass", "implicit_solvent")]
+                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass", "implicit_solvent", "gb_cutoff")]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
             sys.stderr.write(p.stdout + p.stderr)
@@ -326,7 +346,7 @@ def main():
                 say(f"  time per step, constrained ({side}) / unconstrained (1 fs) = {ratio:.3f}: simulated time per wall time at 2 fs {2.0 / ratio:.2f}x "
                     f"({'constraints pay' if ratio < 2.0 else 'constraints do NOT pay'}: the bound is the ratio of the time steps, 2)"
                     + ("" if ran["cons_2fs"] else "; the 2 fs run itself stopped early on this synthetic chain"))
-    elif args.cutoff:
+    elif args.cutoff and not args.implicit_solvent:
         say(f"# cutoff {args.cutoff} A, switch {args.switch or 'none'}, reaction field 78.3; all five run times of each side in ms; tiles: evaluated by the cut "
             "energy kernel at the start coordinates, summed over its work items")
         for w in WORKLOADS:
@@ -357,6 +377,20 @@ def main():
                 rate[side] = report(f"{what:12s}", res[side])
                 say(f"               runs: {', '.join(f'{u / 1e3:.2f}' for u in res[side]['all_us'])} ms")
             say(f"  time per step, {args.implicit_solvent} / vacuum = {rate['stepwise'] / rate['gb']:.2f}")
+            if args.gb_cutoff > 0:
+                sides = [s_ for s_ in GBCUT_SIDES if s_ != "gbboth" or args.cutoff]
+                names = {"gbcut": f"cut {args.gb_cutoff:g} A, prune=1", "gbcut_noprune": f"cut {args.gb_cutoff:g} A, prune=0",
+                         "gbboth": f"both cut ({args.cutoff:g} A)"}
+                for side in sides:
+                    res[side] = run(f"{w}:{side}")
+                    rate[side] = report(f"{names[side]:20s}", res[side])
+                    say(f"               runs: {', '.join(f'{u / 1e3:.2f}' for u in res[side]['all_us'])} ms")
+                t = run(f"{w}:gbtiles")
+                say(f"  solvent tiles: {t['tiles']} of {t['all_tiles']} evaluated over {t['items']} work items ({100.0 * t['tiles'] / max(t['all_tiles'], 1):.1f} %)")
+                say(f"  steps/s, solvent cut prune=1 / all-pairs solvent = {rate['gbcut'] / rate['gb']:.2f}x; prune=0 / all-pairs solvent = "
+                    f"{rate['gbcut_noprune'] / rate['gb']:.2f}x; slowest pruned run {max(res['gbcut']['all_us']) / 1e3:.2f} ms, fastest all-pairs solvent run "
+                    f"{min(res['gb']['all_us']) / 1e3:.2f} ms: {'faster' if max(res['gbcut']['all_us']) < min(res['gb']['all_us']) else 'NOT faster'}"
+                    + (f"; with the nonbonded cutoff beside it {rate['gbboth'] / rate['gb']:.2f}x" if "gbboth" in rate else ""))
     for w in (() if args.cutoff or args.constraints or args.implicit_solvent else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:

@@ -25,6 +25,9 @@ protocol at the same three workloads: the planned all-pairs nonbonded kernel (en
 and without the gradient (every atom with carbon's radius 1.7 A and scale 0.72: the cost does not depend on the values).
 
     python tools/nonbonded_bench.py --gb obc2 [--out profiles/gb_bench.txt]
+With --gb-cutoff R beside it, the solvent is also measured under its own cutoff (`ImplicitSolvent(cutoff=R)`, grappa_gb_obc_fwd_cut_f32):
+all pairs against prune = 1 against prune = 0, the three taking turns call by call, with the tiles evaluated out of all tiles:
+    python tools/nonbonded_bench.py --gb obc2 --gb-cutoff 10 [--out profiles/gb_cut_bench.txt]
 """
 import argparse
 import json
@@ -150,6 +153,21 @@ def five(fn):
     return us
 
 
+def five_in_turn(fns):
+    """one warm-up call each, then five rounds in which the calls take turns, each between device events -> {name: the five times in us}"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(5):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(), fn(), b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3)
+    return us
+
+
 def cut_stage(args):
     """one workload of the cutoff measurement in this (child) process -> a JSON line on stdout"""
     if not torch.cuda.is_available():
@@ -182,6 +200,17 @@ def cut_stage(args):
         out["gb"] = five(lambda: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, g_o, br, plan=plan))
         out["gb_energy"] = five(lambda: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, None, None, plan=plan))
         out["finite"] = bool(torch.isfinite(e_o).all()) and bool(torch.isfinite(g_o).all())
+        if args.gb_cutoff > 0:
+            copts = {p: ImplicitSolvent(args.gb, cutoff=args.gb_cutoff, prune=p).cut_opts() for p in (True, False)}
+            tiles = {p: torch.zeros(plan[1], dtype=torch.int32, device="cuda") for p in (True, False)}
+            call = lambda p: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, g_o, br, plan=plan, cut=copts[p], tiles=tiles[p])      # noqa: E731
+            n0 = be.lib.grappa_launch_count(0)
+            call(True)
+            out["cut_launches"] = int(be.lib.grappa_launch_count(0) - n0)
+            out.update(five_in_turn({"turn_all": lambda: be.gb_obc(x, nb.atom_molptr, nb.charge, R, S, opts, e_o, t_o, g_o, br, plan=plan),
+                                     "turn_prune": lambda: call(True), "turn_noprune": lambda: call(False)}))
+            out["tiles"], out["all_tiles"] = int(tiles[True].sum()), int(tiles[False].sum())
+            out["finite"] = out["finite"] and bool(torch.isfinite(e_o).all()) and bool(torch.isfinite(g_o).all())
         print(json.dumps(out))
         return
     cut = {p: Cutoff(args.cutoff, args.switch or None, prune=p) for p in (True, False)}
@@ -203,7 +232,7 @@ def gb_main(args):
         print(s, flush=True)
 
     def run(name):
-        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name, f"--gb={args.gb}",
+        cmd = ["timeout", "-k", "10", str(CUT_STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name, f"--gb={args.gb}", f"--gb-cutoff={args.gb_cutoff}",
                f"--mols={args.mols}", f"--confs={args.confs}", f"--mid-atoms={args.mid_atoms}", f"--chain-atoms={args.chain_atoms}"]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
@@ -223,6 +252,14 @@ def gb_main(args):
             med[key] = float(np.median(r[key]))
             say(f"  {what:20s} {med[key]:12.1f} us  {1e6 / med[key]:10.1f} calls/s   runs: {', '.join(f'{u:.1f}' for u in r[key])} us")
         say(f"  time per call, {args.gb} / LJ + Coulomb = {med['gb'] / med['all_pairs']:.2f}; without the gradient {med['gb_energy'] / med['all_pairs']:.2f}")
+        if args.gb_cutoff > 0:
+            say(f"  under a solvent cutoff of {args.gb_cutoff:g} A ({r['cut_launches']} launches), the three taking turns; tiles evaluated {r['tiles']} of {r['all_tiles']} "
+                f"({100.0 * r['tiles'] / max(r['all_tiles'], 1):.1f} %)")
+            for key, what in (("turn_all", f"{args.gb}, all pairs"), ("turn_prune", "cutoff, prune = 1"), ("turn_noprune", "cutoff, prune = 0")):
+                med[key] = float(np.median(r[key]))
+                say(f"  {what:20s} {med[key]:12.1f} us  {1e6 / med[key]:10.1f} calls/s   runs: {', '.join(f'{u:.1f}' for u in r[key])} us")
+            say(f"  all pairs / prune = 1 = {med['turn_all'] / med['turn_prune']:.2f} (fastest all pairs / slowest pruned {min(r['turn_all']) / max(r['turn_prune']):.2f}); "
+                f"prune = 0 / all pairs = {med['turn_noprune'] / med['turn_all']:.2f}")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
@@ -280,6 +317,7 @@ def main():
     ap.add_argument("--cutoff", type=float, default=0.0, help="A; > 0: measure the nonbonded cutoff (see the module text)")
     ap.add_argument("--switch", type=float, default=0.0, help="A; the switch distance of the cutoff (0: none)")
     ap.add_argument("--gb", default="", help="obc2 or obc1: measure the GB/SA implicit solvent (see the module text)")
+    ap.add_argument("--gb-cutoff", type=float, default=0.0, help="A; with --gb: also measure the solvent under this cutoff of its own")
     ap.add_argument("--stage", default=None, choices=("device",) + CUT_WORKLOADS)
     args = ap.parse_args()
     if args.stage:
