@@ -126,6 +126,12 @@ class MdCons(C.Structure):
                 ("tolerance", C.c_float), ("constrain_start", C.c_int)]
 
 
+class MdRestr(C.Structure):
+    """grappa_md_restr (additions to ABI 11): tethers and dihedral restraints of the stepwise dynamics, per call"""
+    _fields_ = [("pos_k", C.c_void_p), ("pos_ref", C.c_void_p), ("dih_molptr", C.c_void_p), ("dih_atoms", C.c_void_p), ("dih_k", C.c_void_p),
+                ("dih_target", C.c_void_p), ("R", C.c_int)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -330,6 +336,16 @@ SIGNATURES = {
                                            C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "grappa_md_steps_finish_gbcut_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
                                               C.POINTER(GbDesc), C.POINTER(GbCut), _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the stepwise dynamics with restraints (additions to ABI 11)
+    "grappa_md_steps_restr_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "grappa_md_steps_init_restr_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                            C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), _vp, _vp, _vp, _vp, _i, _i, _vp, _sz]),
+    "grappa_md_steps_run_restr_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                           C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i,
+                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_md_steps_finish_restr_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                              C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -563,12 +563,50 @@ class MMBackend:
                        steps, status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
                        constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv)
 
+    def md_steps_restr(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps,
+                       status, frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000,
+                       workspace=None, constraints=None, constrain_start=True, gb=None, solvent=None, esolv=None, frames_esolv=None, cutoff=None,
+                       restraints=None, restraint_reference=None, restraint_energy=None, dihedral_out=None, frames_restraint_energy=None,
+                       frames_dihedrals=None) -> None:
+        """the stepwise dynamics with restraints (include/grappa_hip.h grappa_md_steps_*_restr_f32): `md_steps_gb`'s arguments with gb /
+        solvent optional (None: vacuum; constraints and cutoff as `md_steps_cons` takes them), plus restraints, a
+        `grappa_amd.restraints.RestraintBatch` on xyz's device (tethers and dihedral restraints; `frozen` must be None: the caller folds
+        frozen atoms into the masses), restraint_reference (N,C,3) float32 or None (the tethers' reference; None: xyz -- a continued run
+        must pass the original reference), restraint_energy (B,C) float32 (required) -> E_r at xyz_out, dihedral_out (R,C) or None -> the
+        restrained dihedrals there, frames_restraint_energy (F,B,C) / frames_dihedrals (F,R,C) or None -> the same per frame.  epot stays
+        the force field's (plus the solvent's).  Status 5: the item's restraint (or constraint) tables were refused.  A step has the
+        launches of the same call without restraints.  Like `md_steps` it has NO device sync."""
+        from .restraints import RestraintBatch
+        from .solvent import GBBatch, as_implicit_solvent
+        who = "md_steps_restr"
+        if not isinstance(restraints, RestraintBatch):
+            raise TypeError(f"{who}: restraints must be a RestraintBatch, got {type(restraints).__name__}")
+        if restraints.frozen is not None:
+            raise ValueError(f"{who}: frozen atoms are not sent down: fold them into the masses (mass 0) and pass restraints without `frozen`")
+        if restraint_energy is None:
+            raise ValueError(f"{who}: restraint_energy (B,C) is required")
+        sv = as_implicit_solvent(solvent) if gb is not None or solvent is not None else None
+        if (sv is None) != (gb is None) or (gb is not None and not isinstance(gb, GBBatch)):
+            raise TypeError(f"{who}: gb (a GBBatch) and solvent (a model) go together, got {type(gb).__name__}, {solvent!r}")
+        if sv is not None:
+            if cutoff is not None and sv.cutoff is None:
+                raise ValueError(f"{who}: a nonbonded cutoff beside the implicit solvent needs a solvent with a cutoff of its own "
+                                 "(ImplicitSolvent(cutoff=))")
+            if nb is None:
+                raise ValueError(f"{who}: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
+            gb.check_offset(sv.offset)
+        self._md_steps(who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps,
+                       status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
+                       constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv,
+                       restr=(restraints, restraint_reference, restraint_energy, dihedral_out, frames_restraint_energy, frames_dihedrals))
+
     def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                   frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start,
-                  gb=None, solvent=None, esolv=None, frames_esolv=None):
+                  gb=None, solvent=None, esolv=None, frames_esolv=None, restr=None):
         """init, the run calls and finish of one stepwise run: the plain calls, the _cut_ calls with a cutoff, the _cons_ calls with
         constraints (and the cutoff or NULL), the _gb_ calls with an implicit solvent (and the constraints or NULL), the _gbcut_ calls with
-        a solvent that carries a cutoff (and the nonbonded cutoff or NULL)"""
+        a solvent that carries a cutoff (and the nonbonded cutoff or NULL), the _restr_ calls with restraints (and each of the others or
+        NULL)"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
         d, o = self._md_call(who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
@@ -595,10 +633,37 @@ class MMBackend:
             gbd = _lib.GbDesc(radius=gb.radius.data_ptr(), scale=gb.scale.data_ptr(), **solvent.as_opts())
             gco = solvent.cut_opts()
             gbc = None if gco is None else _opts_struct(_lib.GbCut, gco, f"{who}: the solvent's cutoff")
+        rr = None
+        if restr is not None:
+            r, ref, er, phi, fer, fphi = restr
+            R = int(r.dih_atoms.shape[0])
+            F_ = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
+            _tensors(dev, ((r.dih_molptr, "dih_molptr", _I32), (r.dih_atoms, "dih_atoms", _I32), (r.dih_k, "dih_k", _F32), (r.dih_target, "dih_target", _F32),
+                           (r.pos_k, "pos_k", _F32), (ref, "restraint_reference", _F32), (er, "restraint_energy", _F32), (phi, "dihedral_out", _F32),
+                           (fer, "frames_restraint_energy", _F32), (fphi, "frames_dihedrals", _F32)),
+                     ("pos_k", "restraint_reference", "dihedral_out", "frames_restraint_energy", "frames_dihedrals"))
+            if r.dih_molptr.numel() != B + 1 or r.dih_atoms.shape != (R, 4) or r.dih_k.numel() != R or r.dih_target.numel() != R * Cc \
+                    or (r.pos_k is not None and r.pos_k.numel() != N) or (ref is not None and ref.shape != xyz.shape):
+                raise ValueError(f"{who}: expected dih_molptr ({B + 1},), dih_atoms (R,4), dih_k (R,), dih_target (R,{Cc}), pos_k ({N},), "
+                                 f"restraint_reference {tuple(xyz.shape)}")
+            if er.numel() != B * Cc or (phi is not None and phi.numel() != R * Cc) or (fer is not None and fer.numel() != F_ * B * Cc) \
+                    or (fphi is not None and fphi.numel() != F_ * R * Cc):
+                raise ValueError(f"{who}: expected restraint_energy (B,C), dihedral_out ({R},{Cc}), frames_restraint_energy ({F_},B,C), "
+                                 f"frames_dihedrals ({F_},{R},{Cc})")
+            if R * Cc >= 2 ** 31:
+                raise ValueError(f"{who}: R * C must stay below 2^31, got {R} * {Cc}")
+            if ref is not None and r.pos_k is None:
+                ref = None          # (no tether reads it)
+            rr = _lib.MdRestr(pos_k=_ptr(r.pos_k), pos_ref=_ptr(ref), dih_molptr=r.dih_molptr.data_ptr() if R else None,
+                              dih_atoms=r.dih_atoms.data_ptr() if R else None, dih_k=r.dih_k.data_ptr() if R else None,
+                              dih_target=r.dih_target.data_ptr() if R else None, R=R)
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        if gbd is not None and gbc is not None:
+        if rr is not None:
+            need = int(self.lib.grappa_md_steps_restr_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0, int(cut is not None),
+                                                                      int(gbd is not None), int(gbd is not None and gbc is not None)))
+        elif gbd is not None and gbc is not None:
             need = int(self.lib.grappa_md_steps_gbcut_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
         elif gbd is not None:
             need = int(self.lib.grappa_md_steps_gb_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
@@ -611,7 +676,11 @@ class MMBackend:
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
         st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if gbd is not None and gbc is not None:
+        if rr is not None:
+            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons) if cons is not None else None,
+                         C.byref(gbd) if gbd is not None else None, C.byref(gbc) if gbd is not None and gbc is not None else None,
+                         C.byref(rr)), "_restr_f32"
+        elif gbd is not None and gbc is not None:
             head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons) if cons is not None else None,
                          C.byref(gbd), C.byref(gbc)), "_gbcut_f32"
         elif gbd is not None:
@@ -626,7 +695,8 @@ class MMBackend:
         tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
         _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), f"grappa_md_steps_init{sfx}")
         F = o.n_steps // o.save_every if o.save_every > 0 else 0
-        every = o.save_every if F > 0 and any(t is not None for t in (frames_xyz, frames_epot, frames_ekin, frames_esolv)) else 0
+        frame_outs = (frames_xyz, frames_epot, frames_ekin, frames_esolv) + ((restr[4], restr[5]) if rr is not None else ())
+        every = o.save_every if F > 0 and any(t is not None for t in frame_outs) else 0
         chunk = int(steps_per_call)
         if every > 0:
             chunk = max(chunk // every, 1) * every
@@ -635,11 +705,13 @@ class MMBackend:
             n = min(chunk, o.n_steps - done)
             f0 = done // every if every > 0 else 0
             fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size()
-                  for t in (frames_xyz, frames_epot, frames_ekin) + ((frames_esolv,) if gbd is not None else ())]
+                  for t in (frames_xyz, frames_epot, frames_ekin) + ((frames_esolv,) if gbd is not None or rr is not None else ())
+                  + ((restr[4], restr[5]) if rr is not None else ())]
             _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), f"grappa_md_steps_run{sfx}")
             done += n
         _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(),
-                    *((_ptr(esolv),) if gbd is not None else ())), f"grappa_md_steps_finish{sfx}")
+                    *((_ptr(esolv),) if gbd is not None or rr is not None else ()),
+                    *((restr[2].data_ptr(), _ptr(restr[3])) if rr is not None else ())), f"grappa_md_steps_finish{sfx}")
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

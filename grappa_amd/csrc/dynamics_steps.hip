@@ -28,6 +28,9 @@
 //            force, close: the section "X-H constraints" below states the decomposition, the launches and the hazards.
 //   solvent: grappa_md_steps_*_gb_f32 (gb == NULL: the calls without).  The section "implicit solvent" below: the force launch as it is,
 //            without its closing kick, then born, pair and chain of csrc/gb_pass.h; the chain launch's epilogue closes the step.
+//   restraints: grappa_md_steps_*_restr_f32 (r == NULL or empty tables: the calls without).  Tethers and dihedral restraints of
+//            csrc/md_restr.h: their gradient is added to the owner's gi at the head of the force launch's epilogue, the one place
+//            every Hamiltonian above passes through (the section "restraints" below); a step gains no launch, init gains two.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -38,6 +41,7 @@
 #include "gb_pass.h"
 #include "md_cons.h"
 #include "md_noise.h"
+#include "md_restr.h"
 #include "rs_force.h"
 
 namespace {
@@ -168,7 +172,8 @@ __device__ __forceinline__ void ms_move_atom(const MsMoveArgs& a, const RsItem& 
 }
 
 // the thread's (atom, conformation) of the item; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
-template <bool CUT>
+// KEEP (with restraints): a stopped item that no longer runs keeps the status it has (5: its tables were refused)
+template <bool CUT, bool KEEP = false>
 __device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& r, int k0, const int* stop, float* bxl) {
     const int C = a.q.C, t = threadIdx.x, ni = r.ni;
     const int cl = t / ni, il = t - cl * ni;
@@ -176,7 +181,11 @@ __device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& 
     const size_t item = (size_t)r.mol * C + c;
     const bool writer = r.blk == k0 && il == 0;      // the molecule's first block: the one writer of the item's status and steps
     if (stop[cl]) {                                  // a non-finite gradient: the item keeps the x and v it holds
-        if (writer) a.status[item] = 2;
+        if constexpr (KEEP) {
+            if (writer && a.status[item] == RS_RUNNING) a.status[item] = 2;
+        } else {
+            if (writer) a.status[item] = 2;
+        }
         return;
     }
     ms_move_atom<CUT>(a, r, i, c, bxl);
@@ -206,7 +215,7 @@ __device__ __forceinline__ void ms_stop_flags(const int* bad, const RsItem& r, i
 
 // CUT: the item also writes the box of its own (block, conformations) at the coordinates it leaves (csrc/nb_cut.h): it is the box's only
 // writer, the force launch after it the reader.  A stopped conformation keeps its box, as it keeps its x.
-template <bool CUT>
+template <bool CUT, bool KEEP = false>
 __device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
     __shared__ int stop[NB_CW];
     RsItem r;
@@ -216,15 +225,17 @@ __device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
     ms_stop_flags<false>(a.bad, r, C, k0, k1, stop);
     if constexpr (CUT) {
         __shared__ float bx[NB_NT * 3];
-        if (t < ni * r.nc) ms_move_lane<true>(a, r, k0, stop, bx + 3 * t);
+        if (t < ni * r.nc) ms_move_lane<true, KEEP>(a, r, k0, stop, bx + 3 * t);
         nb_cut_box_write(bx, stop, ni, r.nc, r.blk, C, r.c0, box);
     } else {
-        if (t < ni * r.nc) ms_move_lane<false>(a, r, k0, stop, nullptr);
+        if (t < ni * r.nc) ms_move_lane<false, KEEP>(a, r, k0, stop, nullptr);
     }
 }
 
 __global__ __launch_bounds__(NB_NT) void ms_move_kernel(MsMoveArgs a) { ms_move_body<false>(a, nullptr); }
 __global__ __launch_bounds__(NB_NT) void ms_move_cut_kernel(MsMoveArgs a, float4* box) { ms_move_body<true>(a, box); }
+__global__ __launch_bounds__(NB_NT) void ms_move_restr_kernel(MsMoveArgs a) { ms_move_body<false, true>(a, nullptr); }
+__global__ __launch_bounds__(NB_NT) void ms_move_restr_cut_kernel(MsMoveArgs a, float4* box) { ms_move_body<true, true>(a, box); }
 
 // ------------------------------------------------------------------------------------------------ force
 struct MsForceArgs {
@@ -239,12 +250,38 @@ struct MsForceArgs {
 
 // CONS (with constraints): the block's flag word also takes, as bit 1, the constraint-failure word that the launch before this one left for
 // the block (cfail), and the kinetic partial is left to the close launch, which follows the closing P
-template <bool CONS = false, class Cut>
-__device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& cut, const int* cfail = nullptr) {
+// RESTR (with restraints, csrc/md_restr.h): the owner adds to gi -- before g is written, before the closing kick and before the
+// non-finite test -- the molecule's restrained dihedrals that name its atom in ascending r, then its tether.  The row range and the rows
+// are workgroup-uniform loads; the rows' atoms are read from x in global memory, which no launch writes while the force launch runs.
+template <bool CONS = false, bool RESTR = false, class Cut>
+__device__ __forceinline__ void ms_force_body(const MsForceArgs& a, const Cut& cut, const int* cfail = nullptr, const MrDev& mr = MrDev{}) {
     __shared__ RsShared sh;
     rs_force(a.f, sh, cut, [&](const RsItem& r, const RsLane& w, V3 gi) {
         const int C = a.f.q.C, ni = r.ni;
         float mv2 = 0.f, bad = 0.f;
+        if constexpr (RESTR) {
+            int k0, nr;
+            mr_rows(mr, r.mol, k0, nr);
+            if (w.owner) {
+                const int n = r.m1 - r.m0, il = w.i - r.m0;
+                for (int k = k0; k < k0 + nr; ++k) {
+                    int4 at;
+                    if (!mr_row(mr, k, n, at)) continue;
+                    const int p = at.x == il ? 0 : (at.y == il ? 1 : (at.z == il ? 2 : (at.w == il ? 3 : -1)));
+                    if (p >= 0) {
+                        V3 d0, d1, d2, d3;
+                        const float phi = dihedral_geom(ldv(a.f.x, r.m0 + at.x, C, w.c), ldv(a.f.x, r.m0 + at.y, C, w.c),
+                                                        ldv(a.f.x, r.m0 + at.z, C, w.c), ldv(a.f.x, r.m0 + at.w, C, w.c), d0, d1, d2, d3);
+                        const float coef = mr.k[k] * sinf(phi - mr.target[(size_t)k * C + w.c]);
+                        gi = gi + coef * (p == 0 ? d0 : (p == 1 ? d1 : (p == 2 ? d2 : d3)));
+                    }
+                }
+                if (mr.pos_k) {
+                    const float pk = mr.pos_k[w.i];
+                    if (pk != 0.f) gi = gi + pk * (ldv(a.f.x, w.i, C, w.c) - ldv(mr.ref, w.i, C, w.c));
+                }
+            }
+        }
         if (w.owner) {
             const size_t off = ((size_t)w.i * C + w.c) * 3;
             a.g[off] = gi.x, a.g[off + 1] = gi.y, a.g[off + 2] = gi.z;
@@ -297,6 +334,23 @@ __global__ __launch_bounds__(NB_NT) void ms_force_cons_kernel(MsForceArgs a, con
 __global__ __launch_bounds__(NB_NT) void ms_force_cons_cut_kernel(MsForceArgs a, NbCutDev c, const int* cfail) {
     __shared__ unsigned char near[NB_NT];
     ms_force_body<true>(a, NbCut{c, near}, cfail);
+}
+
+// the four with restraints: new kernels, the four above are what they were
+__global__ __launch_bounds__(NB_NT) void ms_force_restr_kernel(MsForceArgs a, MrDev m) { ms_force_body<false, true>(a, NbNoCut{}, nullptr, m); }
+
+__global__ __launch_bounds__(NB_NT) void ms_force_restr_cut_kernel(MsForceArgs a, NbCutDev c, MrDev m) {
+    __shared__ unsigned char near[NB_NT];
+    ms_force_body<false, true>(a, NbCut{c, near}, nullptr, m);
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_force_restr_cons_kernel(MsForceArgs a, const int* cfail, MrDev m) {
+    ms_force_body<true, true>(a, NbNoCut{}, cfail, m);
+}
+
+__global__ __launch_bounds__(NB_NT) void ms_force_restr_cons_cut_kernel(MsForceArgs a, NbCutDev c, const int* cfail, MrDev m) {
+    __shared__ unsigned char near[NB_NT];
+    ms_force_body<true, true>(a, NbCut{c, near}, cfail, m);
 }
 
 // ------------------------------------------------------------------------------------------------ X-H constraints (grappa_md_steps_*_cons_f32)
@@ -873,11 +927,21 @@ __global__ __launch_bounds__(256) void ms_out_gb_kernel(MsOutArgs a, const float
 
 // (a cutoff as the three calls carry it: RsCut / rs_cut_make of csrc/rs_force.h; c == NULL: none)
 void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const MsWs& w,
-                     const float* mass, float hk, float* frame_xyz, int n_items, const int* cfail = nullptr) {
+                     const float* mass, float hk, float* frame_xyz, int n_items, const int* cfail = nullptr, const MrDev* mr = nullptr) {
     MsForceArgs f;
     f.f = rs_force_in(mm, nb, q, w.x, w.status);
     f.v = w.v, f.g = w.g, f.mass = mass, f.bad = w.bad, f.kpart = w.kpart;
     f.hk = hk, f.frame_xyz = frame_xyz;
+    if (mr) {          // with restraints: the four restrained instantiations
+        const dim3 grid((unsigned)n_items), block(NB_NT);
+        NbCutDev d = {};
+        if (c) d = c->dev, d.box = w.box, d.er = w.er;
+        if (c && cfail) GRAPPA_LAUNCH(ms_force_restr_cons_cut_kernel, grid, block, 0, st, f, d, cfail, *mr);
+        else if (c) GRAPPA_LAUNCH(ms_force_restr_cut_kernel, grid, block, 0, st, f, d, *mr);
+        else if (cfail) GRAPPA_LAUNCH(ms_force_restr_cons_kernel, grid, block, 0, st, f, cfail, *mr);
+        else GRAPPA_LAUNCH(ms_force_restr_kernel, grid, block, 0, st, f, *mr);
+        return;
+    }
     if (c) {
         NbCutDev d = c->dev;
         d.box = w.box, d.er = w.er;
@@ -926,10 +990,47 @@ void msc_launch_close(hipStream_t st, const RsGeom& q, const MsWs& w, const MscD
     GRAPPA_LAUNCH(msc_close_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
 }
 
+// ------------------------------------------------------------------------------------------------ restraints (grappa_md_steps_*_restr_f32)
+// Tethers and dihedral restraints of csrc/md_restr.h on every Hamiltonian above.
+//   gradient: every variant launches ms_force_body, whose epilogue holds the owner's gi before g is written, before the closing kick and
+//            before the non-finite test; the restrained instantiations add the restraint gradient there.  What follows reads that g and
+//            recomputes nothing: the next move launch (with constraints ms_move_cons_kernel, B P) reads g; msc_close_kernel reads x and v
+//            only (the closing P and the kinetic partial), no gradient; in solvent the force launch runs with hk == 0 and the chain
+//            launch's epilogue (ms_gb_close) reads g, adds ggb and the chain sum, writes g, kicks and tests the sum.  So no launch per
+//            step is added and no word has a second writer.
+//   hazards : x is written by move alone and read by force (its own and, for a row's atoms, other blocks': across the launch
+//            boundary); the reference is written once by init; g is written by the owner in force (and chain), read by the next move;
+//            status 5 and bit 2 of the flag words are written by the vet launch of init, before the first force launch reads status.
+//   status 5: as with constraints, a refused item never runs and its outputs are not touched: the move launches of a restrained run
+//            leave a status that is not RS_RUNNING alone (KEEP), and the finish copies x and v item by item (msc_copy_kernel,
+//            ms_out_kernel<true>).
+//   energies: mr_energy_kernel at the held coordinates, where the six terms are evaluated: on frame steps and at finish.  epot stays
+//            the force field's (plus the solvent's); E_r is reported beside it.
+//   workspace: the reference [N,C,3], behind every other word.
+struct MsRestr {
+    MrDev dev;                           // (dev.ref is set once the workspace is laid out)
+    const float* ref_src;                // the caller's pos_ref, or NULL: mm->xyz as init receives it
+};
+
+float* ms_restr_ref(char* base, size_t off, int N, int C, size_t& total) {
+    WsCarve k{base};
+    k.off = off;
+    float* ref = k.take<float>((size_t)N * C * 3);
+    total = k.off;
+    return ref;
+}
+
+MrEnergyArgs mr_energy_args(const grappa_mm_desc* mm, const MsWs& w, const MrDev& m, int final, float* erestr, float* phi) {
+    MrEnergyArgs a = {};
+    a.N = mm->N, a.C = mm->C, a.B = mm->B, a.final = final;
+    a.atom_molptr = mm->atom_molptr, a.x = w.x, a.status = w.status, a.m = m, a.erestr = erestr, a.phi = phi;
+    return a;
+}
+
 // the three calls, with and without a cutoff (c == NULL: none) and constraints (cons == NULL: none, the launches as they were)
 int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
             const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
-            const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr) {
+            const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, const MsRestr* rs = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
@@ -937,7 +1038,11 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
     if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
+    size_t total = gb ? gw.total : w.total;
+    MrDev mrd = {};
+    const MrDev* mr = nullptr;
+    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
+    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.n_blocks = n_blocks;
@@ -950,6 +1055,17 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     n = n > kc ? n : kc;
     GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    // with restraints: the reference into the workspace and the tables vetted, behind the init kernel (and the constraints' vet) and in
+    // front of everything that reads status
+    const auto restr_init = [&]() {
+        if (!mr) return;
+        if (mr->pos_k) {
+            const size_t n3 = (size_t)mm->N * mm->C * 3;
+            GRAPPA_LAUNCH(mr_ref_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, n3, rs->ref_src ? rs->ref_src : mm->xyz,
+                          const_cast<float*>(mr->ref));
+        }
+        if (n_items > 0) GRAPPA_LAUNCH(mr_vet_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, *mr, w.status, w.bad);
+    };
     if (cons) {
         // the tables vetted (clear, claim, read back), the start's S and P, then boxes, force and the kinetic partials: 6 to 8 launches
         MscDev cn = msc_dev(cons, o);
@@ -959,19 +1075,21 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
         if (n_items > 0) {
             GRAPPA_LAUNCH(msc_claim_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn);
             GRAPPA_LAUNCH(msc_vet_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn, w.status, w.bad);
+            restr_init();
             if (cons->constrain_start || !vel_in) {
                 const MscStartArgs sa = {q, w.x, w.v, mass, w.status, cn, cons->constrain_start != 0};
                 GRAPPA_LAUNCH(msc_start_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, sa);
             }
             if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
-            ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail);
+            ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail, mr);
             if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, true);
             msc_launch_close(st, q, w, cn, mass, 0, n_items);
         }
         return grappa_launch_status();
     }
+    restr_init();
     if (boxes && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
-    if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items);
+    if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, nullptr, mr);
     if (gb && n_items > 0) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, false);
     return grappa_launch_status();
 }
@@ -979,11 +1097,12 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
 int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
            float* frames_xyz, float* frames_epot, float* frames_ekin, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr,
-           float* frames_esolv = nullptr) {
+           float* frames_esolv = nullptr, const MsRestr* rs = nullptr, float* frames_erestr = nullptr, float* frames_phi = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
-    const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin || frames_esolv);
+    const bool frames_r = rs && (frames_erestr || frames_phi);
+    const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin || frames_esolv || frames_r);
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
@@ -991,7 +1110,11 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
     if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
+    size_t total = gb ? gw.total : w.total;
+    MrDev mrd = {};
+    const MrDev* mr = nullptr;
+    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
+    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const MdConsts k = md_consts(o);
@@ -1013,13 +1136,15 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             if (cons) {          // move, boxes (with a cutoff), force, close: 3 launches, 4 under a cutoff
                 GRAPPA_LAUNCH(ms_move_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, cn);
                 if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
-                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, w.cfail);
+                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, w.cfail, mr);
                 if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, true);
                 msc_launch_close(st, q, w, cn, mass, 1, n_items);
             } else {
-                if (boxes) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
+                if (mr && boxes) GRAPPA_LAUNCH(ms_move_restr_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
+                else if (mr) GRAPPA_LAUNCH(ms_move_restr_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
+                else if (boxes) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
                 else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items);
+                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, nullptr, mr);
                 if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, false);
             }
         }
@@ -1035,13 +1160,18 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             MsOutArgs a = ms_out_args(mm, nb, q, w);
             a.final = 0, a.with_epot = terms && frames_epot != nullptr;
             a.epot = frames_epot ? frames_epot + f * bc : nullptr, a.ekin = frames_ekin ? frames_ekin + f * bc : nullptr;
-            if (cons) GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
+            if (cons || mr) GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
             else GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
             if (gb && terms) {
                 float* fe = frames_esolv ? frames_esolv + f * bc : nullptr;
-                if (cons) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
+                if (cons || mr) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
                 else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
             }
+        }
+        if (due && frames_r) {          // E_r and the restrained dihedrals of the frame, at the coordinates the step left
+            const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 0, frames_erestr ? frames_erestr + f * bc : nullptr,
+                                                  frames_phi ? frames_phi + f * (size_t)mr->R * mm->C : nullptr);
+            GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
         }
     }
     return grappa_launch_status();
@@ -1049,7 +1179,8 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
 
 int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const int* table_dev,
               int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
-              int* status, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, float* esolv = nullptr) {
+              int* status, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, float* esolv = nullptr, const MsRestr* rs = nullptr,
+              float* erestr = nullptr, float* dih_phi = nullptr) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
@@ -1057,7 +1188,11 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
     MsGbWs gw = {};
     if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    if (ws_bytes < (gb ? gw.total : w.total)) return GRAPPA_ERR_WORKSPACE;
+    size_t total = gb ? gw.total : w.total;
+    MrDev mrd = {};
+    const MrDev* mr = nullptr;
+    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
+    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
     if (erc == GRAPPA_OK && gb)
@@ -1067,15 +1202,19 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     a.final = 1, a.with_epot = 1;
     a.xyz_out = xyz_out, a.vel_out = vel_out, a.epot = epot, a.ekin = ekin, a.steps = steps, a.status = status;
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
-    if (cons) {          // a refused item's outputs are not touched: x and v item by item
+    if (cons || mr) {          // a refused item's outputs are not touched: x and v item by item
         if (n_items > 0) GRAPPA_LAUNCH(msc_copy_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, rs_geom(mm, table_dev, n_blocks), w.x, w.v, w.status, xyz_out, vel_out);
         GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
     } else {
         GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     }
     if (gb) {
-        if (cons) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
+        if (cons || mr) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
         else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
+    }
+    if (mr) {
+        const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 1, erestr, dih_phi);
+        GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
     }
     return grappa_launch_status();
 }
@@ -1324,4 +1463,121 @@ extern "C" int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_de
     if (cc < 0) return cc;
     return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
                      cc == 1 ? nullptr : cons, &g, esolv);
+}
+
+// with restraints (grappa_md_restr): r == NULL, or R == 0 with pos_k == NULL, is the call above -- its launches, its bits, its refusals;
+// erestr is then written as 0 for molecules that have atoms, and the frames' restraint outputs are not written.
+namespace {
+struct MsCallPlan {
+    RsCut c;
+    MsGb g;
+    bool has_cut, has_gb;
+    const grappa_md_cons* cons;
+};
+
+// GRAPPA_OK: restraints to run with (m filled); 1: none, forward; < 0: refused
+int mr_check(const grappa_md_restr* r, const grappa_mm_desc* mm, MsRestr& m) {
+    if (!r) return 1;
+    if (r->R < 0 || (r->R > 0 && (!r->dih_molptr || !r->dih_atoms || !r->dih_k || !r->dih_target)) || (r->pos_ref && !r->pos_k))
+        return GRAPPA_ERR_ARG;
+    if (r->R > 0 && mm && mm->C > 0 && (long long)r->R * mm->C >= (1LL << 31)) return GRAPPA_ERR_ARG;
+    if (r->R == 0 && !r->pos_k) return 1;
+    m.dev = MrDev{};
+    m.dev.pos_k = r->pos_k, m.dev.R = r->R;
+    if (r->R > 0) m.dev.molptr = r->dih_molptr, m.dev.atoms = r->dih_atoms, m.dev.k = r->dih_k, m.dev.target = r->dih_target;
+    m.ref_src = r->pos_ref;
+    return GRAPPA_OK;
+}
+
+// the refusals of the _gbcut_ family, in its order: the solvent (with or without its cutoff), the nonbonded cutoff, the constraints
+int ms_call_plan(const grappa_nb_desc* nb, const grappa_nb_cut* cut, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                 const grappa_gb_cut* gbcut, MsCallPlan& p) {
+    p.has_cut = p.has_gb = false, p.cons = nullptr;
+    if (gbcut) {
+        if (ms_gbcut_check(gb, gbcut, nb, p.g) < 0) return GRAPPA_ERR_ARG;
+        p.has_gb = true;
+    } else if (gb) {
+        const int gc = ms_gb_check(gb, nb, cut, p.g);
+        if (gc < 0) return gc;
+        p.has_gb = true;
+    }
+    if (cut) {
+        if (!rs_cut_make(cut, nb, p.c)) return GRAPPA_ERR_ARG;
+        p.has_cut = true;
+    }
+    const int cc = msc_check(cons);
+    if (cc < 0) return cc;
+    p.cons = cc == 1 ? nullptr : cons;
+    return GRAPPA_OK;
+}
+}  // namespace
+
+extern "C" size_t grappa_md_steps_restr_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut, int with_gb, int with_gbcut) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
+    const bool gbcut = with_gbcut != 0, gb = with_gb != 0 || gbcut;
+    size_t total = ms_layout(nullptr, N, C, B, n_blocks, with_cut != 0 || gbcut, K > 0).total;
+    if (gb) total = ms_gb_layout(nullptr, total, N, C, B, n_blocks, gbcut).total;
+    ms_restr_ref(nullptr, total, N, C, total);
+    return total;
+}
+
+extern "C" int grappa_md_steps_init_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                              const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                              const grappa_gb_cut* gbcut, const grappa_md_restr* r, const float* mass,
+                                              const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
+                                              int n_blocks, void* ws, size_t ws_bytes) {
+    MsRestr m;
+    const int rc = mr_check(r, mm, m);
+    if (rc < 0) return rc;
+    if (rc == 1)
+        return grappa_md_steps_init_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    MsCallPlan p;
+    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
+    if (pc < 0) return pc;
+    return ms_init(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, p.cons,
+                   p.has_gb ? &p.g : nullptr, &m);
+}
+
+extern "C" int grappa_md_steps_run_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                             const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                             const grappa_gb_cut* gbcut, const grappa_md_restr* r, const float* mass,
+                                             const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
+                                             size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin,
+                                             float* frames_esolv, float* frames_erestr, float* frames_phi) {
+    MsRestr m;
+    const int rc = mr_check(r, mm, m);
+    if (rc < 0) return rc;
+    if (rc == 1)
+        return grappa_md_steps_run_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0,
+                                             n_steps, frames_xyz, frames_epot, frames_ekin, frames_esolv);
+    MsCallPlan p;
+    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
+    if (pc < 0) return pc;
+    return ms_run(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
+                  frames_epot, frames_ekin, p.cons, p.has_gb ? &p.g : nullptr, frames_esolv, &m, frames_erestr, frames_phi);
+}
+
+extern "C" int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                                const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                                const grappa_gb_cut* gbcut, const grappa_md_restr* r, const int* table_dev, int n_items,
+                                                int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin,
+                                                int* steps, int* status, float* esolv, float* erestr, float* dih_phi) {
+    if (!erestr) return GRAPPA_ERR_ARG;
+    MsRestr m;
+    const int rc = mr_check(r, mm, m);
+    if (rc < 0) return rc;
+    if (rc == 1) {
+        const int fc = grappa_md_steps_finish_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out,
+                                                        vel_out, epot, ekin, steps, status, esolv);
+        if (fc != GRAPPA_OK || !mm || mm->N <= 0 || mm->C <= 0 || mm->B <= 0 || !mm->atom_molptr) return fc;
+        const size_t bc = (size_t)mm->B * mm->C;
+        GRAPPA_LAUNCH(mr_zero_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), mm->atom_molptr,
+                      mm->N, mm->B, mm->C, erestr);
+        return grappa_launch_status();
+    }
+    MsCallPlan p;
+    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
+    if (pc < 0) return pc;
+    return ms_finish(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps,
+                     status, p.cons, p.has_gb ? &p.g : nullptr, esolv, &m, erestr, dih_phi);
 }

@@ -36,6 +36,17 @@ the nonbonded cutoff of the paragraph above, on one set of boxes.  A reaction fi
 with the reaction-field dielectric 1, so `cutoff=Cutoff(rc, rs, rf_dielectric=1.0)` is the usual companion (what the caller passes is
 not overridden).  The truncated solvent energy jumps where a pair crosses the cutoff: such a run does not conserve energy.
 
+Restraints (`restraints=`, `grappa_amd.restraints`): harmonic tethers to a reference structure and periodic dihedral restraints
+k (1 - cos(phi - target)) with one target per conformation, on the stepwise path only (`grappa_md_steps_*_restr_f32` through
+`HipBackend.md_steps_restr`), with every combination of cutoff, constraints and implicit solvent that path takes: their gradient is
+added in the force launch, a step gains no launch.  Two protocols: restrained equilibration (heavy atoms tethered while the rest
+thermalises) and umbrella sampling along a torsion -- the C conformations of one call are the C windows, and `frames_dihedrals` is the
+time series of the biased dihedral that WHAM / MBAR read (WHAM itself is not here).  `stepwise="auto"` goes stepwise whenever they are
+given.  The tethers' reference is `restraint_reference` (default: the call's xyz); a run continued with `first_step` must pass the
+ORIGINAL reference, or the tethers move to the start of the continuing call.  Frozen atoms (`Restraints.frozen`) become atoms of mass 0.
+The potential energies stay the force field's (plus the solvent's); `restraint_energy` is reported beside them.  Not built: restraints in
+the fused dynamics, distance, angle or flat-bottomed restraints, more than 16 dihedrals per molecule, time-dependent targets.
+
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
 mass 0 is frozen.  The random stream has no state: an atom's noise is a function of its molecule's 64-bit key (`mol_keys`), its index
@@ -47,9 +58,10 @@ be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An i
        the launch); it cannot occur on the stepwise path
     4  (with constraints) a position constraint did not converge within its eight updates: stopped, the state is the one it held;
        `steps` counts the steps before the one that failed
-    5  (with constraints) the molecule's constraint tables were refused on the device (an index outside the molecule, an atom in two
-       clusters, a length that is not positive and finite, on the fused path more than 256 clusters): nothing else was written for
-       the item
+    5  (with constraints or restraints) constraint or restraint tables refused on the device (an index outside the molecule, an atom
+       in two clusters, a length that is not positive and finite, on the fused path more than 256 clusters; a restrained dihedral
+       with a repeated atom, a negative or non-finite stiffness, a non-finite target, more than 16 rows): nothing else was written
+       for the item
 The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
 has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
 """
@@ -129,6 +141,10 @@ class MDResult:
     frame_kinetic_energy: object = None
     esolv: object = None              # with an implicit solvent: its part of potential_energy, shaped like it; else None
     frames_esolv: object = None       # ... and of frame_potential_energy
+    restraint_energy: object = None           # with restraints: E_r at xyz (potential_energy stays the force field's), (B, C) / (n_confs,)
+    dihedrals: object = None                  # with restraints: the restrained dihedrals at xyz in radians, (R, C) / (R, n_confs)
+    frames_restraint_energy: object = None    # ... per frame: (F, B, C) / (n_confs, n_frames); a frame not reached is NaN
+    frames_dihedrals: object = None           # ... per frame: (F, R, C) / (R, n_confs, n_frames)
 
 
 def _steps_take_constraints() -> bool:
@@ -161,7 +177,7 @@ def _host_keys(keys, seed, B):
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
                    offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, cutoff=None,
-                   implicit_solvent=None, gb=None, **opts) -> MDResult:
+                   implicit_solvent=None, gb=None, restraints=None, restraint_reference=None, **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -190,11 +206,29 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     on the graph's device (radius and scale per atom).  It needs `nonbonded` (the charges) and the stepwise path: "auto" then goes
     stepwise whatever the sizes, stepwise=False is refused; constraints go with it, a cutoff does not (ValueError) unless the solvent
     carries a cutoff of its own (`ImplicitSolvent(cutoff=)`: the solvent is truncated pairwise, and `cutoff=` beside it is taken).  The result's
-    potential energies include the solvent term; `esolv` / `frames_esolv` hold it alone."""
+    potential energies include the solvent term; `esolv` / `frames_esolv` hold it alone.
+    restraints: a `grappa_amd.restraints.RestraintBatch` for the graph's molecules and C on the graph's device (None: none, the calls
+    made are exactly those without this argument): tethers and dihedral restraints, see the module text.  The stepwise path only:
+    stepwise=False raises, "auto" goes stepwise; they go with every combination of cutoff, constraints and implicit solvent.  Frozen
+    atoms of the batch get mass 0 before anything reads the masses.  restraint_reference: (N, C, 3) on the graph's device, the
+    tethers' reference (None: xyz, resolved once; every launch of a long run gets that tensor, never its own start).  The result carries
+    restraint_energy (B, C), dihedrals (R, C) and, with frames, frames_restraint_energy (F, B, C) and frames_dihedrals (F, R, C)."""
     from .backend import get_backend
     from .solvent import GBBatch, as_implicit_solvent
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
+    if restraints is not None:
+        from .restraints import RestraintBatch
+        if not isinstance(restraints, RestraintBatch):
+            raise TypeError(f"restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
+        if stepwise is False:
+            raise ValueError('simulate: restraints run on the stepwise path only: pass stepwise="auto" (or True)')
+        if getattr(get_backend(), "md_steps_restr", None) is None:
+            raise ValueError("simulate: the backend has no restraints on the stepwise dynamics (md_steps_restr)")
+        if constraints is not None and not _steps_take_constraints():
+            raise ValueError("simulate: constraints run on the fused path only, restraints on the stepwise path only")
+    elif restraint_reference is not None:
+        raise ValueError("simulate: restraint_reference needs restraints=")
     cutoff = as_cutoff(cutoff)
     solvent = as_implicit_solvent(implicit_solvent)
     if solvent is not None:
@@ -229,7 +263,7 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if above and stepwise is False:
         raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
                          f"(stepwise=True or stepwise='auto' runs molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None))
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None or restraints is not None))
     if solvent is not None:
         if gb.counts != list(counts):
             raise ValueError(f"the GB parameters describe molecules of {gb.counts} atoms, the batch has {list(counts)}")
@@ -245,6 +279,20 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     N, B, C = plan.N, plan.B, xyz.shape[1]
     m_host = _host_masses(masses, N)
+    ref = None
+    if restraints is not None:
+        from .relax import check_restraint_batch
+        check_restraint_batch(restraints, B, C, counts, dev)
+        if restraints.frozen is not None:          # frozen atoms: mass 0, before n_moving, the degrees of freedom and check_masses read it
+            m_host = np.where(restraints.frozen.cpu().numpy().reshape(-1) != 0, np.float32(0.0), m_host).astype(np.float32)
+            import copy
+            restraints = copy.copy(restraints)          # (the `frozen` array is not sent down)
+            restraints.frozen = None
+        ref = xyz
+        if restraint_reference is not None:
+            if not isinstance(restraint_reference, torch.Tensor) or restraint_reference.shape != xyz.shape or restraint_reference.device != dev:
+                raise ValueError(f"restraint_reference must be a {tuple(xyz.shape)} tensor on {dev}")
+            ref = restraint_reference.detach().float().contiguous()
     k_host = _host_keys(keys, seed, B)
     mass = torch.from_numpy(m_host).to(dev)
     key = torch.from_numpy(k_host.view(np.int64).copy()).to(dev)
@@ -275,6 +323,11 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         frames, fe, fk = nan(F, N, C, 3), nan(F, B, C), nan(F, B, C)
     es = f32(B, C) if solvent is not None else None
     fs = torch.full((F, B, C), float("nan"), dtype=torch.float32, device=dev) if solvent is not None and F else None
+    er = phi = fer = fphi = None
+    if restraints is not None:
+        er, phi = f32(B, C), f32(restraints.R, C)
+        if F:
+            fer, fphi = nan(F, B, C), nan(F, restraints.R, C)
     # one call of a seam runs `seg` steps: a launch of the fused kernel, or init / run calls of at most `chunk` steps / finish of the
     # stepwise path, whose options carry the library's cap on n_steps too; calls continue one another bit for bit
     seg = chunk if not use_steps else (MAX_STEPS_PER_LAUNCH // every * every if every > 0 else MAX_STEPS_PER_LAUNCH)
@@ -287,9 +340,11 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     # within a call (init .. finish): there statuses 4 and 5 are sticky in the workspace, whatever the number of run calls; only a run
     # longer than the library's cap on n_steps makes a second call, and this bookkeeping then carries an ended item across it.
     held = None
-    if constraints is not None and n_steps > seg:
+    if (constraints is not None or restraints is not None) and n_steps > seg:
         held = {"dead": torch.zeros(B, C, dtype=torch.bool, device=dev)}
         atom_item = torch.repeat_interleave(torch.arange(B), torch.tensor(counts, dtype=torch.long)).to(dev)
+        if restraints is not None:
+            row_item = torch.repeat_interleave(torch.arange(B, device=dev), (restraints.dih_molptr[1:] - restraints.dih_molptr[:-1]).long())
     while True:
         n = min(seg, n_steps - done)
         f0, f1 = (done // every, (done + n) // every) if every > 0 else (0, 0)
@@ -299,7 +354,14 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         args = (plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin, steps, status)
         kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
-        if solvent is not None:
+        if restraints is not None:
+            get_backend().md_steps_restr(*args, steps_per_call=chunk, **kw, constraints=constraints,
+                                         constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
+                                         frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None,
+                                         **({} if cutoff is None else {"cutoff": cutoff}), restraints=restraints, restraint_reference=ref,
+                                         restraint_energy=er, dihedral_out=phi, frames_restraint_energy=fer[f0:f1] if f1 > f0 else None,
+                                         frames_dihedrals=fphi[f0:f1] if f1 > f0 else None)
+        elif solvent is not None:
             get_backend().md_steps_gb(*args, steps_per_call=chunk, **kw, constraints=constraints,
                                       constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
                                       frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None,
@@ -323,7 +385,9 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
             atoms = alive[atom_item][:, :, None]
             total += torch.where(alive, steps, torch.zeros_like(steps))
             for name, new, mask in (("x", x_out, atoms), ("v", v_out, atoms), ("epot", epot, alive), ("ekin", ekin, alive), ("status", status, alive)) \
-                    + ((("esolv", es, alive),) if es is not None else ()):
+                    + ((("esolv", es, alive),) if es is not None else ()) + ((("er", er, alive), ("phi", phi, None)) if er is not None else ()):
+                if name == "phi":          # (a row belongs to the molecule that holds it)
+                    mask = alive[row_item]
                 held[name] = torch.where(mask, new, held[name]) if name in held else new.clone()
             if f1 > f0 and launch > 0:
                 nanf = torch.full((), float("nan"), dtype=torch.float32, device=dev)
@@ -331,6 +395,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
                 fe[f0:f1], fk[f0:f1] = torch.where(alive[None], fe[f0:f1], nanf), torch.where(alive[None], fk[f0:f1], nanf)
                 if fs is not None:
                     fs[f0:f1] = torch.where(alive[None], fs[f0:f1], nanf)
+                if fer is not None:
+                    fer[f0:f1], fphi[f0:f1] = torch.where(alive[None], fer[f0:f1], nanf), torch.where(alive[row_item][None], fphi[f0:f1], nanf)
             held["dead"] = held["dead"] | (alive & (status >= 4))
         x_in, v_in, done, launch = x_out, v_out, done + n, launch + 1
         if done >= n_steps:
@@ -338,24 +404,39 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if held is not None:
         x_in, v_in, epot, ekin, status = held["x"], held["v"], held["epot"], held["ekin"], held["status"]
         es = held.get("esolv", es)
+        er, phi = held.get("er", er), held.get("phi", phi)
+    if fer is not None and restraints.R == 0 and restraints.pos_k is None:
+        fer = torch.where(torch.isnan(fe), fe, torch.zeros_like(fe))          # (nothing restrains: the library writes no frame of E_r; it is 0)
     temperature = 2.0 * ekin / (3.0 * KB * n_moving) if constraints is None else 2.0 * ekin / (KB * dof.clamp_min(1.0))
-    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs)
+    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs, er, phi, fer, fphi)
 
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
              seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, constraints=None,
-             constrain_start: bool = True, cutoff=None, implicit_solvent=None, gb=None, **opts) -> MDResult:
+             constrain_start: bool = True, cutoff=None, implicit_solvent=None, gb=None, restraints=None, restraint_reference=None,
+             **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
     (n_confs, n_frames, n_atoms, 3), frame energies (n_confs, n_frames) and the others (n_confs,).  stepwise: see `simulate_graph`
     (the stepwise path takes a molecule of any size).  constraints: the molecule's `grappa_amd.constraints.Constraints` in the order of
     `parameters.atoms` (None: unconstrained), constrain_start: see `simulate_graph`.  cutoff: see `simulate_graph`.
-    implicit_solvent: see `simulate_graph`; gb: the molecule's `grappa_amd.solvent.GBParameters` in the order of `parameters.atoms`."""
+    implicit_solvent: see `simulate_graph`; gb: the molecule's `grappa_amd.solvent.GBParameters` in the order of `parameters.atoms`.
+    restraints: the molecule's `grappa_amd.restraints.Restraints` in the order of `parameters.atoms` (None: none), restraint_reference
+    (n_confs, n_atoms, 3) or None (xyz): see `simulate_graph`; the result then carries restraint_energy (n_confs,), dihedrals
+    (R, n_confs), frames_restraint_energy (n_confs, n_frames) and frames_dihedrals (R, n_confs, n_frames)."""
     from .solvent import GBBatch, GBParameters, as_implicit_solvent
     md_options(**opts)
     _stepwise_options(stepwise, 1)
     extra = {}
+    if restraints is not None:
+        from .restraints import Restraints
+        if not isinstance(restraints, Restraints):
+            raise TypeError(f"restraints must be Restraints or None, got {type(restraints).__name__}")
+        if stepwise is False:
+            raise ValueError('simulate: restraints run on the stepwise path only: pass stepwise="auto" (or True)')
+    elif restraint_reference is not None:
+        raise ValueError("simulate: restraint_reference needs restraints=")
     cutoff = as_cutoff(cutoff)
     solvent = as_implicit_solvent(implicit_solvent)
     if solvent is not None:
@@ -399,6 +480,14 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
         if v.shape != np.asarray(xyz).shape:
             raise ValueError(f"velocities must have the shape of xyz {np.asarray(xyz).shape}, got {v.shape}")
         vel = torch.from_numpy(np.ascontiguousarray(v.transpose(1, 0, 2))).to(device)
+    if restraints is not None:
+        from .restraints import RestraintBatch
+        extra["restraints"] = RestraintBatch([restraints], int(np.asarray(xyz).shape[0]), atom_counts=[n]).to(device)
+        if restraint_reference is not None:
+            ref = np.asarray(restraint_reference, dtype=np.float32)
+            if ref.shape != np.asarray(xyz).shape:
+                raise ValueError(f"restraint_reference must have the shape of xyz {np.asarray(xyz).shape}, got {ref.shape}")
+            extra["restraint_reference"] = torch.from_numpy(np.ascontiguousarray(ref.transpose(1, 0, 2))).to(device)
     r = simulate_graph(g.to(device), m_host, nb, velocities=vel, seed=seed, keys=keys, first_step=first_step, steps_per_launch=steps_per_launch,
                        stepwise=stepwise, **extra, **opts)
     np64 = lambda t: t.cpu().numpy().astype(np.float64)      # noqa: E731
@@ -407,4 +496,8 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
     return MDResult(confs(r.xyz), confs(r.velocities), np64(r.potential_energy)[0], np64(r.kinetic_energy)[0], np64(r.temperature)[0],
                     r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0], np64(r.frames).transpose(2, 0, 1, 3) if has else None,
                     np64(r.frame_potential_energy)[:, 0].T if has else None, np64(r.frame_kinetic_energy)[:, 0].T if has else None,
-                    np64(r.esolv)[0] if r.esolv is not None else None, np64(r.frames_esolv)[:, 0].T if r.frames_esolv is not None else None)
+                    np64(r.esolv)[0] if r.esolv is not None else None, np64(r.frames_esolv)[:, 0].T if r.frames_esolv is not None else None,
+                    np64(r.restraint_energy)[0] if r.restraint_energy is not None else None,
+                    np64(r.dihedrals) if r.dihedrals is not None else None,
+                    np64(r.frames_restraint_energy)[:, 0].T if r.frames_restraint_energy is not None else None,
+                    np64(r.frames_dihedrals).transpose(1, 2, 0) if r.frames_dihedrals is not None else None)

@@ -86,7 +86,8 @@ class Grappa:
         from .relax import torsion_scan
         return torsion_scan(self.predict(molecule), xyz, dihedral, angles, nonbonded, device=self.device, **kw)
 
-    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, implicit_solvent=None, **kw):
+    def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, implicit_solvent=None,
+                 restraints=None, restraint_reference=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
         the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
@@ -103,8 +104,16 @@ class Grappa:
         (`GBParameters.from_elements`; gb= in **kw overrides them); it needs `nonbonded` and stepwise="auto" (or True), goes with
         constraints and not with a cutoff (`implicit_solvent="obc2", constraints="h-bonds", stepwise="auto"`) -- unless the solvent
         carries a cutoff of its own: `implicit_solvent=ImplicitSolvent("obc2", cutoff=12.0)` truncates the solvent pairwise and skips
-        far tiles, and then `cutoff=` (usually `Cutoff(rc, rs, rf_dielectric=1.0)`) is taken beside it"""
+        far tiles, and then `cutoff=` (usually `Cutoff(rc, rs, rf_dielectric=1.0)`) is taken beside it.
+        restraints: a `grappa_amd.restraints.Restraints` in the molecule's atom order (None: none) -- tethers to
+        restraint_reference (n_confs, n_atoms, 3; None: xyz), dihedral restraints with one target per conformation (the windows of an
+        umbrella run) and frozen atoms, on the stepwise path with any of the above (stepwise="auto" or True): see
+        `grappa_amd.dynamics.simulate`"""
         from .dynamics import simulate
+        if restraints is not None:
+            kw = {**kw, "restraints": restraints, "restraint_reference": restraint_reference}
+        elif restraint_reference is not None:
+            raise ValueError("simulate: restraint_reference needs restraints=")
         if cutoff is not None:
             kw = {**kw, "cutoff": cutoff}
         if implicit_solvent is not None:

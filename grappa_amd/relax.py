@@ -102,6 +102,20 @@ def _stepwise_options(stepwise, check_every):
     return stepwise, int(check_every)
 
 
+def check_restraint_batch(restraints, B, C, counts, dev):
+    """a `RestraintBatch` against the graph it is to restrain (B molecules of `counts` atoms in C conformations on `dev`): the checks
+    `relax_graph` and `simulate_graph` share"""
+    if restraints.B != B or restraints.C != C:
+        raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
+    if restraints.atom_counts is not None and list(restraints.atom_counts) != counts:
+        raise ValueError("the restraint batch does not describe the graph's molecules (atoms per molecule differ)")
+    for b, r in enumerate(restraints.items):
+        if r is not None and r.n_dihedrals and int(r.dihedrals.max()) >= counts[b]:
+            raise ValueError(f"molecule {b}: a restrained dihedral names atom {int(r.dihedrals.max())}, the molecule has {counts[b]} atoms")
+    if restraints.dih_molptr.device != dev:
+        raise ValueError(f"the restraint batch is on {restraints.dih_molptr.device}, the graph on {dev}")
+
+
 def _cutoff_options(cutoff, nonbonded, stepwise, restraints):
     """the rules of a cutoff (those of `simulate`), decided on the host before anything is built -> a `Cutoff` or None"""
     cutoff = as_cutoff(cutoff)
@@ -226,15 +240,7 @@ def relax_graph(g, nonbonded: Optional[NonbondedBatch] = None, *, terms=("n2", "
             raise ValueError(f"the GB parameters are on {gb.radius.device}, the graph on {dev}")
         gb.check_offset(solvent.offset)          # (the batch may have been checked against another offset than the solvent's)
     if restraints is not None:
-        if restraints.B != B or restraints.C != C:
-            raise ValueError(f"the restraint batch describes {restraints.B} molecules in {restraints.C} conformations, the graph {B} in {C}")
-        if restraints.atom_counts is not None and list(restraints.atom_counts) != counts:
-            raise ValueError("the restraint batch does not describe the graph's molecules (atoms per molecule differ)")
-        for b, r in enumerate(restraints.items):
-            if r is not None and r.n_dihedrals and int(r.dihedrals.max()) >= counts[b]:
-                raise ValueError(f"molecule {b}: a restrained dihedral names atom {int(r.dihedrals.max())}, the molecule has {counts[b]} atoms")
-        if restraints.dih_molptr.device != dev:
-            raise ValueError(f"the restraint batch is on {restraints.dih_molptr.device}, the graph on {dev}")
+        check_restraint_batch(restraints, B, C, counts, dev)
     ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     out = torch.empty_like(xyz)
     energy, gmax = torch.zeros(B, C, dtype=torch.float32, device=dev), torch.zeros(B, C, dtype=torch.float32, device=dev)

@@ -1,12 +1,14 @@
 """Restraints for the fused FIRE minimiser (`grappa_amd.relax`, csrc/relax.hip; the objective is stated in include/grappa_hip.h at
-grappa_relax_fire_restr_f32): frozen atoms, harmonic tethers to the start coordinates and periodic dihedral restraints
-k (1 - cos(phi - target)) with one target per conformation -- what "optimise the hydrogens only", "relax, but stay near the input" and
-a relaxed torsion scan need.
+grappa_relax_fire_restr_f32) and for the stepwise dynamics (`grappa_amd.dynamics`, csrc/md_restr.h; grappa_md_steps_*_restr_f32):
+frozen atoms, harmonic tethers to the start coordinates (in the dynamics: to `restraint_reference`, by default the start) and periodic
+dihedral restraints k (1 - cos(phi - target)) with one target per conformation -- what "optimise the hydrogens only", "relax, but stay
+near the input", a relaxed torsion scan, a restrained equilibration and the windows of an umbrella run along a torsion need.  In the
+dynamics a frozen atom is an atom of mass 0: `simulate` folds `frozen` into the masses.
   Restraints      the restraints of ONE molecule, atom indices in the order of the molecule's atoms
   RestraintBatch  the molecules of a batch concatenated, with `dih_molptr`, for `HipBackend.relax_fire(restraints=...)`
   set_dihedral    host numpy: rotate one side of a bond rigidly so that a dihedral takes a value (the starts of a torsion scan)
-Units: Angstrom, kcal/mol, radians.  Distance and angle restraints, flat-bottomed wells and restraints on the stepwise minimiser are out
-of scope."""
+Units: Angstrom, kcal/mol, radians.  Distance and angle restraints, flat-bottomed wells, time-dependent targets, restraints on the
+stepwise minimiser and on the fused dynamics are out of scope."""
 from typing import Optional, Sequence
 
 import numpy as np

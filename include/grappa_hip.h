@@ -782,7 +782,7 @@ int grappa_relax_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, co
  * GRAPPA_ERR_ARG before anything else is looked at, nothing launched and nothing written: cut != NULL together with gb, nb == NULL or
  * without charges, NULL radius or scale, options grappa_gb_obc_fwd_f32 refuses.  r = 0 between two distinct atoms (bonded or not: GB
  * has no exclusions) gives status 2; a radius <= offset or a scale <= 0 makes its molecule's gradient NaN: status 2.  Not here: the fused
- * minimiser, restraints, a cutoff, the HCT / GBn models, a salt term. */
+ * minimiser, restraints (the stepwise DYNAMICS take them: grappa_md_steps_*_restr_f32), a cutoff, the HCT / GBn models, a salt term. */
 size_t grappa_relax_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks);
 int grappa_relax_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                    const grappa_gb_desc* gb, const grappa_relax_opts* o, const int* table_dev, int n_items, int n_blocks,
@@ -1054,7 +1054,7 @@ int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, cons
  * epot is.  The workspace is grappa_md_steps_gb_workspace_bytes (the words of a run without solvent first, the solvent's behind them).
  * GRAPPA_ERR_ARG before anything else is looked at: cut != NULL together with gb (GB under a cutoff is not implemented), nb == NULL,
  * NULL radius or scale, options grappa_gb_obc_fwd_f32 refuses.  r = 0 between two distinct atoms (bonded or not: GB has no exclusions)
- * gives status 2.  Not here: the fused dynamics, the fused minimiser, restraints. */
+ * gives status 2.  Not here: the fused dynamics, the fused minimiser (restraints: grappa_md_steps_*_restr_f32 below). */
 size_t grappa_md_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks, int K);
 int grappa_md_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                 const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
@@ -1102,6 +1102,60 @@ int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_desc* mm, con
                                      const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
                                      const grappa_gb_cut* gbcut, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
                                      float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status, float* esolv);
+
+/* The stepwise dynamics with restraints (additions to ABI 11): the _gbcut_ calls with `const grappa_md_restr* r` directly after gbcut.
+ * cut, cons, gb and gbcut are each optional under the _gbcut_ family's own rules (gbcut == NULL: the rules of the _gb_ calls, gb == NULL:
+ * those of the _cons_ calls, and so on down).  The integrator sees the gradient of E_ff (+ solvent) + E_r,
+ *   E_r(b,c) = sum_r dih_k_r (1 - cos(phi_r - dih_target_{r,c})) + sum_i 0.5 pos_k_i |x_{i,c} - ref_{i,c}|^2,
+ * the restraint energy of grappa_relax_fire_restr_f32 with an explicit reference; phi is the library's dihedral.  Per (atom,
+ * conformation) the gradient is formed in a fixed order: the force field's, exactly as the force launch forms it; + dih_k_r sin(phi_r -
+ * target) dphi_r/dx_i for the molecule's rows that name the atom, in ascending r; + pos_k_i (x_i - ref_i).  It is added in the force
+ * launch's epilogue, before g is written, before the closing kick and before the non-finite test, so every launch behind it (the
+ * solvent's chain, the constrained close, the next move) reads it: a step gains no launch.  Same input, same bits; no atomics; an item's
+ * bits do not depend on its place in the batch.
+ *   ref    : pos_ref [N,C,3], or NULL: mm->xyz as init receives it.  init copies it into the workspace; run and finish read that copy.
+ *            A run continued with first_step must pass the ORIGINAL reference: with NULL the tethers move to the start of the
+ *            continuing call.  There is no `frozen`: a mass of 0 freezes an atom.
+ *   vet    : one launch of init, per (molecule, conformation): atom indices in [0, n) and the four of a row distinct, dih_k finite and
+ *            >= 0, the conformation's targets finite, pos_k finite and >= 0, at most GRAPPA_RELAX_MAX_DIHEDRALS rows on the molecule,
+ *            dih_molptr monotone and within [0, R].  A refused item gets status 5 (constraint or restraint tables refused) and never
+ *            runs: its xyz_out, vel_out, epot, ekin, steps, erestr, dih_phi and frames are untouched, its neighbours run.  A NaN target
+ *            refuses its conformation only.  A non-finite pos_ref under a positive pos_k has no check of its own: it makes the gradient
+ *            non-finite, which is status 2 by the force launch's own test.
+ *   energy : epot / frames_epot stay the force field's (plus the solvent's).  erestr [B,C] (required) and dih_phi [R,C] (NULL: not
+ *            written) = E_r and the restrained dihedrals at xyz_out; frames_erestr [F,B,C] and frames_phi [F,R,C] (NULL: not written)
+ *            the same on frame steps, for running items.  One workgroup per (molecule, conformation): the tethers in double (thread t
+ *            the atoms t, t + 256, .. ascending, the 256 rows added in order), then the dihedral rows in ascending r.
+ * r == NULL, or R == 0 with pos_k == NULL, is the _gbcut_ call itself: its launches, its bits, its refusals; erestr is then written as
+ * 0 for molecules that have atoms and the frames' restraint outputs are not written.  GRAPPA_ERR_ARG, nothing launched and nothing
+ * written: R < 0, a NULL dih_* table with R > 0, pos_ref without pos_k, a NULL erestr (finish), R * C >= 2^31.  The workspace is
+ * grappa_md_steps_restr_workspace_bytes(N, C, B, n_blocks, K, with_cut, with_gb, with_gbcut): the layout of the call without
+ * restraints, unchanged, and the reference behind it.  Not here: restraints in the fused dynamics, anything in the minimisers, distance,
+ * angle or flat-bottomed restraints, more than GRAPPA_RELAX_MAX_DIHEDRALS dihedrals per molecule, time-dependent targets. */
+typedef struct grappa_md_restr {
+    const float* pos_k;      /* [N] or NULL */
+    const float* pos_ref;    /* [N,C,3] or NULL: mm->xyz as init receives it */
+    const int*   dih_molptr; /* [B+1], NULL iff R == 0 */
+    const int*   dih_atoms;  /* [R,4] within the molecule */
+    const float* dih_k;      /* [R] */
+    const float* dih_target; /* [R,C] */
+    int R;
+} grappa_md_restr;
+size_t grappa_md_steps_restr_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut, int with_gb, int with_gbcut);
+int grappa_md_steps_init_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                   const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                   const grappa_md_restr* r, const float* mass, const unsigned long long* mol_key, const float* vel_in,
+                                   const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_steps_run_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                  const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                  const grappa_md_restr* r, const float* mass, const unsigned long long* mol_key, const int* table_dev,
+                                  int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz,
+                                  float* frames_epot, float* frames_ekin, float* frames_esolv, float* frames_erestr, float* frames_phi);
+int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                     const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+                                     const grappa_gb_cut* gbcut, const grappa_md_restr* r, const int* table_dev, int n_items, int n_blocks,
+                                     void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+                                     int* status, float* esolv, float* erestr, float* dih_phi);
 
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:

@@ -48,6 +48,15 @@ With --gb-cutoff R beside it the solvent step is also measured under the solvent
 grappa_md_steps_*_gbcut_f32 calls): prune = 1 and prune = 0, with --cutoff RC [--switch RS] also with the nonbonded cutoff
 `Cutoff(RC, RS, 1.0)` beside it, and the tiles the solvent's energy entry evaluates at the start coordinates:
     python tools/md_steps_bench.py --implicit-solvent obc2 --gb-cutoff 10 [--cutoff 10] [--out profiles/md_steps_gb_cut_bench.txt]
+
+With --restraints the tool measures restraints on the stepwise path instead (`simulate_graph(restraints=)`, the
+grappa_md_steps_*_restr_f32 calls): on the 513-atom chain, T4 lysozyme and the 50,046-atom chain, a tether of 10 kcal/mol/A^2 on every
+heavy atom and one restrained dihedral (on T4 lysozyme its first proper, on the chains the proper whose two angles are farthest from
+straight; 239 kcal/mol, target 0.5 rad from the start) against the same run
+without restraints -- whose kernels this option does not touch -- IN THE SAME PROCESS, the two sides alternating run by run after one
+warm-up run of each.  All times of each side, the ratio of the medians and the library launches.  It is not a gate: no target is set.
+
+    python tools/md_steps_bench.py --restraints [--out profiles/md_steps_restr_bench.txt]
 """
 import argparse
 import datetime
@@ -70,7 +79,9 @@ GB_WORKLOADS = ("pool", "mid", "t4l", "big")
 GBCUT_SIDES = ("gbcut", "gbcut_noprune", "gbboth")          # the solvent under its own cutoff; gbboth: with the nonbonded cutoff beside it
 CONS_SIDES = ("free_1fs", "cons_2fs", "cons_1fs")
 CONS_DT = {"free_1fs": 0.001, "cons_2fs": 0.002, "cons_1fs": 0.001}
-STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:{s}" for w in GB_WORKLOADS for s in GBCUT_SIDES + ("gbtiles",)] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
+RESTR_WORKLOADS = ("mid", "t4l", "big")
+RESTR_POS_K, RESTR_DIH_K, RESTR_DIH_SHIFT = 10.0, 239.0, 0.5
+STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:restr" for w in RESTR_WORKLOADS] + [f"{w}:{s}" for w in GB_WORKLOADS for s in GBCUT_SIDES + ("gbtiles",)] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
          [f"{w}:{s}:{p}" for w in WORKLOADS[1:] for s in CONS_SIDES for p in ("pairs", "cut")]
 
 STAGE_LIMIT = 300      # seconds, every stage
@@ -138,6 +149,51 @@ def _leaves(n, leaf_mass):
     return masses, Constraints(clusters, lengths)
 
 
+def _restraints(g, which, n):
+    """a tether on every heavy atom and one restrained dihedral (the first proper) of the workload's one molecule -> RestraintBatch (host)"""
+    import numpy as np
+    from grappa_amd.restraints import RestraintBatch, Restraints, dihedral_angle
+    x = g.nodes["n1"].data["xyz"][:, 0].double().cpu().numpy()
+    if which == "t4l":
+        from grappa_amd import _hostlib
+        from grappa_amd.datasets import _T4_PATH
+        d = np.load(_T4_PATH)
+        heavy = d["z"].astype(np.int64) > 1
+        row = np.asarray(_hostlib.enumerate_tuples(d["bonds"].astype(np.int64).reshape(-1, 2))[1], dtype=np.int64).reshape(-1, 4)[0]
+    else:
+        # a chain of carbons: four consecutive atoms are a proper.  Most of the chain is nearly straight, where a dihedral is ill
+        # defined (dphi/dx grows as 1 / sin of the two angles: a restraint there is stiff beyond what a 1 fs step resolves), so the
+        # proper with the two angles farthest from 180 degrees among the first 2000 atoms is taken
+        m = min(n, 2000)
+        u, v = x[:m - 2] - x[1:m - 1], x[2:m] - x[1:m - 1]
+        s = np.linalg.norm(np.cross(u, v), axis=1) / (np.linalg.norm(u, axis=1) * np.linalg.norm(v, axis=1))
+        first = int(np.minimum(s[:-1], s[1:]).argmax())
+        heavy, row = np.ones(n, dtype=bool), np.arange(first, first + 4)
+    target = dihedral_angle(x, *[int(a) for a in row]) + RESTR_DIH_SHIFT
+    res = Restraints(position_k=np.where(heavy, RESTR_POS_K, 0.0), dihedrals=[row], dihedral_k=[RESTR_DIH_K],
+                     dihedral_targets=[(target + np.pi) % (2 * np.pi) - np.pi])
+    return RestraintBatch([res], 1, atom_counts=[n]), int(heavy.sum())
+
+
+def _alternating(fns, reps):
+    """one warm-up run of each side, then `reps` rounds in which the sides run one after the other, device events around each whole run
+    -> the times of each side in us"""
+    import torch
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    us = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3)
+    return us
+
+
 def _all_timed(fn, reps):
     """md_bench._timed's protocol (one warm-up run, device events around whole runs), every time kept"""
     import torch
@@ -173,6 +229,21 @@ def stage(args):
     out = {"molecules": len(counts), "atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max()), "confs": confs}
     sim = lambda n, stepwise, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, stepwise=stepwise,      # noqa: E731
                                                    **{**OPTS, **kw})
+    if side == "restr":
+        rb, tethered = _restraints(g, which, int(counts[0]))
+        rb = rb.to("cuda")
+        runs = (lambda: sim(steps, True), lambda: sim(steps, True, restraints=rb))
+        for key, fn in zip(("plain", "restr"), runs):
+            n0 = be.lib.grappa_launch_count(0)
+            r = fn()
+            torch.cuda.synchronize()
+            out[key] = {"launches": int(be.lib.grappa_launch_count(0) - n0), "item_steps": int(r.steps.sum()), "stopped": int((r.status != 0).sum())}
+        out["restraint_energy"] = float(r.restraint_energy.sum())
+        for key, us in zip(("plain", "restr"), _alternating(runs, args.reps)):
+            out[key]["all_us"], out[key]["median_us"] = us, float(sorted(us)[len(us) // 2])
+        out["steps"], out["tethered"] = steps, tethered
+        print(json.dumps(out))
+        return
     if side in CONS_SIDES:
         from grappa_amd.constraints import ConstraintBatch
         from grappa_amd.nonbonded import Cutoff
@@ -287,6 +358,7 @@ def main():
     ap.add_argument("--leaf-mass", type=float, default=CARBON, help="amu; the mass of the leaves with --constraints (the chain's own by default)")
     ap.add_argument("--implicit-solvent", default="", help="obc2 or obc1: measure the GB/SA implicit solvent on the stepwise path (see the module text)")
     ap.add_argument("--gb-cutoff", type=float, default=0.0, help="A; with --implicit-solvent: also measure the solvent under this cutoff of its own")
+    ap.add_argument("--restraints", action="store_true", help="measure restraints on the stepwise path (see the module text)")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -318,7 +390,20 @@ def main():
     say(f"# device: {run('device')['device']}")
     say("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; steps/s = steps of the run / "
         "run time, whatever the batch holds; this file is the tool's output, unedited")
-    if args.constraints:
+    if args.restraints:
+        say(f"# restraints on the stepwise path: a tether of {RESTR_POS_K} kcal/mol/A^2 on every heavy atom and one restrained dihedral ({RESTR_DIH_K} "
+            f"kcal/mol, target {RESTR_DIH_SHIFT} rad from the start) against the same all-pairs run without them, in the same process, sides "
+            "alternating; all run times of each side in ms")
+        for w in RESTR_WORKLOADS:
+            r = run(f"{w}:restr")
+            say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms, {r['tethered']} tethered, C = {r['confs']}, bonded + nonbonded, dt {OPTS['dt']} ps, "
+                f"{OPTS['temperature']} K, friction {OPTS['friction']} / ps, {r['steps']} steps; E_r at the end {r['restraint_energy']:.2f} kcal/mol")
+            for key, what in (("plain", "no restraints"), ("restr", "restraints")):
+                q = r[key]
+                say(f"  {what:14s} {q['median_us'] / r['steps']:10.2f} us / step  {r['steps'] / (q['median_us'] * 1e-6):10.1f} steps/s  {q['launches']:6d} library "
+                    f"launches  runs: {', '.join(f'{u / 1e3:.2f}' for u in q['all_us'])} ms" + (f"  ({q['stopped']} items stopped early)" if q["stopped"] else ""))
+            say(f"  time per step, restraints / none = {r['restr']['median_us'] / r['plain']['median_us']:.3f}")
+    elif args.constraints:
         args.cutoff = args.cutoff or 9.0
         say(f"# X-H constraints on the stepwise path: every second atom a leaf ({args.leaf_mass} amu) held to the atom before it; cutoff {args.cutoff} A, "
             f"switch {args.switch or 'none'}, reaction field 78.3; {OPTS['temperature']} K, friction {OPTS['friction']} / ps; all run times in ms")
@@ -391,7 +476,7 @@ def main():
                     f"{rate['gbcut_noprune'] / rate['gb']:.2f}x; slowest pruned run {max(res['gbcut']['all_us']) / 1e3:.2f} ms, fastest all-pairs solvent run "
                     f"{min(res['gb']['all_us']) / 1e3:.2f} ms: {'faster' if max(res['gbcut']['all_us']) < min(res['gb']['all_us']) else 'NOT faster'}"
                     + (f"; with the nonbonded cutoff beside it {rate['gbboth'] / rate['gb']:.2f}x" if "gbboth" in rate else ""))
-    for w in (() if args.cutoff or args.constraints or args.implicit_solvent else WORKLOADS):
+    for w in (() if args.cutoff or args.constraints or args.implicit_solvent or args.restraints else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:
             r = run(f"{w}:{side}")
