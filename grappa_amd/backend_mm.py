@@ -600,13 +600,25 @@ class MMBackend:
                        constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv,
                        restr=(restraints, restraint_reference, restraint_energy, dihedral_out, frames_restraint_energy, frames_dihedrals))
 
+    # The six families of grappa_md_steps_* entries, narrowest first.  A family takes the optional structs of the one before it plus one
+    # (a family IS the widest call with the others NULL), so a row says only which: the structs of its head behind (stream, mm, nb), the
+    # arguments of its workspace_bytes behind n_blocks, and how many of the optional outputs -- (frames_)esolv, (frames_)erestr, phi --
+    # its run and finish take behind the required ones.
+    _MD_STEPS_FAMILIES = {
+        "":       (("o",), (), 0),
+        "_cut":   (("cut", "o"), (), 0),
+        "_cons":  (("cut", "o", "cons"), ("K", "with_cut"), 0),
+        "_gb":    (("cut", "o", "cons", "gb"), ("K",), 1),
+        "_gbcut": (("cut", "o", "cons", "gb", "gbcut"), ("K",), 1),
+        "_restr": (("cut", "o", "cons", "gb", "gbcut", "restr"), ("K", "with_cut", "with_gb", "with_gbcut"), 3),
+    }
+
     def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                   frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start,
                   gb=None, solvent=None, esolv=None, frames_esolv=None, restr=None):
-        """init, the run calls and finish of one stepwise run: the plain calls, the _cut_ calls with a cutoff, the _cons_ calls with
-        constraints (and the cutoff or NULL), the _gb_ calls with an implicit solvent (and the constraints or NULL), the _gbcut_ calls with
-        a solvent that carries a cutoff (and the nonbonded cutoff or NULL), the _restr_ calls with restraints (and each of the others or
-        NULL)"""
+        """init, the run calls and finish of one stepwise run, through the narrowest family of entries that expresses it: the widest
+        option the run has (restraints, the solvent's cutoff, the solvent, constraints, the nonbonded cutoff, none) names the family,
+        and `_MD_STEPS_FAMILIES` says what that family's calls take; every option the run lacks goes down as NULL"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
         d, o = self._md_call(who, plan, xyz, ks, eqs, n_per, offset_torsion, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin,
@@ -622,22 +634,21 @@ class MMBackend:
                 raise ValueError(f"{who}: a cutoff needs the nonbonded tables (nb)")
             cut = _cut_struct(cutoff, who)
         cons = self._md_cons(constraints, B, dev, constrain_start, who) if constraints is not None else None
-        gbd = None
+        F = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0          # frames of the run
+        gbd = gbc = None
         if gb is not None:
-            F_ = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
             _tensors(dev, ((gb.radius, "gb.radius", _F32), (gb.scale, "gb.scale", _F32), (esolv, "esolv", _F32), (frames_esolv, "frames_esolv", _F32)),
                      ("esolv", "frames_esolv"))
             if gb.radius.numel() != N or gb.scale.numel() != N or (esolv is not None and esolv.numel() != B * Cc) \
-                    or (frames_esolv is not None and frames_esolv.numel() != F_ * B * Cc):
-                raise ValueError(f"{who}: expected gb.radius / gb.scale ({N},), esolv (B,C), frames_esolv ({F_},B,C)")
+                    or (frames_esolv is not None and frames_esolv.numel() != F * B * Cc):
+                raise ValueError(f"{who}: expected gb.radius / gb.scale ({N},), esolv (B,C), frames_esolv ({F},B,C)")
             gbd = _lib.GbDesc(radius=gb.radius.data_ptr(), scale=gb.scale.data_ptr(), **solvent.as_opts())
             gco = solvent.cut_opts()
             gbc = None if gco is None else _opts_struct(_lib.GbCut, gco, f"{who}: the solvent's cutoff")
-        rr = None
+        rr = er = phi = fer = fphi = None
         if restr is not None:
             r, ref, er, phi, fer, fphi = restr
             R = int(r.dih_atoms.shape[0])
-            F_ = o.n_steps // o.save_every if o.save_every > 0 and o.n_steps > 0 else 0
             _tensors(dev, ((r.dih_molptr, "dih_molptr", _I32), (r.dih_atoms, "dih_atoms", _I32), (r.dih_k, "dih_k", _F32), (r.dih_target, "dih_target", _F32),
                            (r.pos_k, "pos_k", _F32), (ref, "restraint_reference", _F32), (er, "restraint_energy", _F32), (phi, "dihedral_out", _F32),
                            (fer, "frames_restraint_energy", _F32), (fphi, "frames_dihedrals", _F32)),
@@ -646,10 +657,10 @@ class MMBackend:
                     or (r.pos_k is not None and r.pos_k.numel() != N) or (ref is not None and ref.shape != xyz.shape):
                 raise ValueError(f"{who}: expected dih_molptr ({B + 1},), dih_atoms (R,4), dih_k (R,), dih_target (R,{Cc}), pos_k ({N},), "
                                  f"restraint_reference {tuple(xyz.shape)}")
-            if er.numel() != B * Cc or (phi is not None and phi.numel() != R * Cc) or (fer is not None and fer.numel() != F_ * B * Cc) \
-                    or (fphi is not None and fphi.numel() != F_ * R * Cc):
-                raise ValueError(f"{who}: expected restraint_energy (B,C), dihedral_out ({R},{Cc}), frames_restraint_energy ({F_},B,C), "
-                                 f"frames_dihedrals ({F_},{R},{Cc})")
+            if er.numel() != B * Cc or (phi is not None and phi.numel() != R * Cc) or (fer is not None and fer.numel() != F * B * Cc) \
+                    or (fphi is not None and fphi.numel() != F * R * Cc):
+                raise ValueError(f"{who}: expected restraint_energy (B,C), dihedral_out ({R},{Cc}), frames_restraint_energy ({F},B,C), "
+                                 f"frames_dihedrals ({F},{R},{Cc})")
             if R * Cc >= 2 ** 31:
                 raise ValueError(f"{who}: R * C must stay below 2^31, got {R} * {Cc}")
             if ref is not None and r.pos_k is None:
@@ -660,42 +671,23 @@ class MMBackend:
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        if rr is not None:
-            need = int(self.lib.grappa_md_steps_restr_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0, int(cut is not None),
-                                                                      int(gbd is not None), int(gbd is not None and gbc is not None)))
-        elif gbd is not None and gbc is not None:
-            need = int(self.lib.grappa_md_steps_gbcut_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
-        elif gbd is not None:
-            need = int(self.lib.grappa_md_steps_gb_workspace_bytes(N, Cc, B, n_blocks, cons.K if cons is not None else 0))
-        elif cons is not None:
-            need = int(self.lib.grappa_md_steps_cons_workspace_bytes(N, Cc, B, n_blocks, cons.K, int(cut is not None)))
-        else:
-            need = int((self.lib.grappa_md_steps_workspace_bytes if cut is None else self.lib.grappa_md_steps_cut_workspace_bytes)(N, Cc, B, n_blocks))
+        have = {"cut": cut, "o": o, "cons": cons, "gb": gbd, "gbcut": gbc, "restr": rr}
+        fam = next((f"_{k}" for k in ("restr", "gbcut", "gb", "cons", "cut") if have[k] is not None), "")
+        head_names, size_names, n_opt = self._MD_STEPS_FAMILIES[fam]
+        sizes = {"K": cons.K if cons is not None else 0, "with_cut": int(cut is not None), "with_gb": int(gbd is not None),
+                 "with_gbcut": int(gbc is not None)}
+        need = int(getattr(self.lib, f"grappa_md_steps{fam}_workspace_bytes")(N, Cc, B, n_blocks, *(sizes[k] for k in size_names)))
         if workspace is None:
             workspace = self._workspace(need, dev, who)
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
-        st, ndp = self._stream(), (C.byref(nd) if nd is not None else None)
-        if rr is not None:
-            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons) if cons is not None else None,
-                         C.byref(gbd) if gbd is not None else None, C.byref(gbc) if gbd is not None and gbc is not None else None,
-                         C.byref(rr)), "_restr_f32"
-        elif gbd is not None and gbc is not None:
-            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons) if cons is not None else None,
-                         C.byref(gbd), C.byref(gbc)), "_gbcut_f32"
-        elif gbd is not None:
-            head, sfx = (st, C.byref(d), ndp, None, C.byref(o), C.byref(cons) if cons is not None else None, C.byref(gbd)), "_gb_f32"
-        elif cons is not None:
-            head, sfx = (st, C.byref(d), ndp, C.byref(cut) if cut is not None else None, C.byref(o), C.byref(cons)), "_cons_f32"
-        elif cut is None:
-            head, sfx = (st, C.byref(d), ndp, C.byref(o)), "_f32"
-        else:
-            head, sfx = (st, C.byref(d), ndp, C.byref(cut), C.byref(o)), "_cut_f32"
+        sfx = f"{fam}_f32"
         init, run, finish = (getattr(self.lib, f"grappa_md_steps_{n}{sfx}") for n in ("init", "run", "finish"))
+        head = (self._stream(), C.byref(d), C.byref(nd) if nd is not None else None,
+                *(C.byref(have[k]) if have[k] is not None else None for k in head_names))
         tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
         _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), f"grappa_md_steps_init{sfx}")
-        F = o.n_steps // o.save_every if o.save_every > 0 else 0
-        frame_outs = (frames_xyz, frames_epot, frames_ekin, frames_esolv) + ((restr[4], restr[5]) if rr is not None else ())
+        frame_outs = (frames_xyz, frames_epot, frames_ekin, frames_esolv, fer, fphi)
         every = o.save_every if F > 0 and any(t is not None for t in frame_outs) else 0
         chunk = int(steps_per_call)
         if every > 0:
@@ -704,14 +696,11 @@ class MMBackend:
         while done < o.n_steps:
             n = min(chunk, o.n_steps - done)
             f0 = done // every if every > 0 else 0
-            fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size()
-                  for t in (frames_xyz, frames_epot, frames_ekin) + ((frames_esolv,) if gbd is not None or rr is not None else ())
-                  + ((restr[4], restr[5]) if rr is not None else ())]
+            fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size() for t in frame_outs[:3 + n_opt]]
             _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), f"grappa_md_steps_run{sfx}")
             done += n
         _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(),
-                    *((_ptr(esolv),) if gbd is not None or rr is not None else ()),
-                    *((restr[2].data_ptr(), _ptr(restr[3])) if rr is not None else ())), f"grappa_md_steps_finish{sfx}")
+                    *(_ptr(t) for t in (esolv, er, phi)[:n_opt])), f"grappa_md_steps_finish{sfx}")
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

@@ -19,18 +19,24 @@
 //   and end  coordinates (mm_energy_kernel, nb_pairs_kernel + nb_reduce_kernel through their entry points: no second energy code path)
 //            and one small launch that adds the six terms in double in term order and the kinetic partials in ascending block order.
 //   noise  : csrc/md_noise.h, keyed by (mol_key, atom WITHIN the molecule, conformation, global step, purpose): the fused kernel's stream.
-//   cutoff : grappa_md_steps_*_cut_f32 (cut == NULL: the calls without).  The force launch is rs_force under the cut policy of
-//            csrc/nb_cut.h; the move launch's item writes the box of its own (block, conformations) after moving -- the box's only
-//            writer -- and the force launch reads all boxes across the launch boundary: a step stays two launches, init gains one (boxes
-//            and exception ranges).  Energies by grappa_nonbonded_fwd_cut_f32 at the held coordinates.
-//   constraints: grappa_md_steps_*_cons_f32 (cons == NULL or K == 0: the calls without).  X-H star clusters under g-BAOAB with P and S of
-//            csrc/md_cons.h; a cluster is integrated by the thread of its centre, and a step becomes move, boxes (with a cutoff),
-//            force, close: the section "X-H constraints" below states the decomposition, the launches and the hazards.
-//   solvent: grappa_md_steps_*_gb_f32 (gb == NULL: the calls without).  The section "implicit solvent" below: the force launch as it is,
-//            without its closing kick, then born, pair and chain of csrc/gb_pass.h; the chain launch's epilogue closes the step.
-//   restraints: grappa_md_steps_*_restr_f32 (r == NULL or empty tables: the calls without).  Tethers and dihedral restraints of
-//            csrc/md_restr.h: their gradient is added to the owner's gi at the head of the force launch's epilogue, the one place
-//            every Hamiltonian above passes through (the section "restraints" below); a step gains no launch, init gains two.
+//   options: a run may have a nonbonded cutoff, X-H constraints, an implicit solvent (with or without a cutoff of its own) and
+//            restraints.  Every entry resolves the optional pointers it takes into ONE plan (MsPlan, ms_plan: the section "the run plan"
+//            below) -- what the run has, every refusal, the derived flags -- and ms_init / ms_run / ms_finish act on that plan with the
+//            workspace carved for it in one place (ms_carve).  The six families of entries (plain, _cut_, _cons_, _gb_, _gbcut_,
+//            _restr_) differ in the pointers they take and in nothing else: a family is the widest call with the others NULL, and an
+//            option that is absent (NULL; K == 0; R == 0 without tethers) launches what the family without it launches.
+//   cutoff : the force launch is rs_force under the cut policy of csrc/nb_cut.h; the move launch's item writes the box of its own
+//            (block, conformations) after moving -- the box's only writer -- and the force launch reads all boxes across the launch
+//            boundary: a step stays two launches, init gains one (boxes and exception ranges).  Energies by
+//            grappa_nonbonded_fwd_cut_f32 at the held coordinates.
+//   constraints: X-H star clusters under g-BAOAB with P and S of csrc/md_cons.h; a cluster is integrated by the thread of its centre,
+//            and a step becomes move, boxes (with a cutoff), force, close: the section "X-H constraints" below states the
+//            decomposition, the launches and the hazards.
+//   solvent: the section "implicit solvent" below: the force launch as it is, without its closing kick, then born, pair and chain of
+//            csrc/gb_pass.h; the chain launch's epilogue closes the step.
+//   restraints: tethers and dihedral restraints of csrc/md_restr.h: their gradient is added to the owner's gi at the head of the force
+//            launch's epilogue, the one place every Hamiltonian above passes through (the section "restraints" below); a step gains
+//            no launch, init gains two.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -65,7 +71,7 @@ struct MsWs {
 };
 
 // (the words of a cutoff lie behind the others, those of constraints behind both: without either the layout is the one it was)
-MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut = false, bool cons = false) {
+MsWs ms_layout(char* base, int N, int C, int B, int n_blocks, bool cut, bool cons) {
     MsWs w;
     WsCarve k{base};
     const size_t n3 = (size_t)N * C * 3, bc = (size_t)B * C, kc = (size_t)n_blocks * C;
@@ -783,7 +789,7 @@ struct MsGbWs {
 };
 
 // (the words of the solvent lie behind all others: `off` = the total of ms_layout)
-MsGbWs ms_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks, bool gbcut = false) {
+MsGbWs ms_gb_layout(char* base, size_t off, int N, int C, int B, int n_blocks, bool gbcut) {
     MsGbWs g;
     WsCarve k{base};
     k.off = off;
@@ -925,71 +931,6 @@ __global__ __launch_bounds__(256) void ms_out_gb_kernel(MsOutArgs a, const float
 // ------------------------------------------------------------------------------------------------ host
 // (the argument checks the three calls share: steps_seam_check of csrc/desc_check.h; GRAPPA_SEAM_EMPTY: nothing to do)
 
-// (a cutoff as the three calls carry it: RsCut / rs_cut_make of csrc/rs_force.h; c == NULL: none)
-void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const MsWs& w,
-                     const float* mass, float hk, float* frame_xyz, int n_items, const int* cfail = nullptr, const MrDev* mr = nullptr) {
-    MsForceArgs f;
-    f.f = rs_force_in(mm, nb, q, w.x, w.status);
-    f.v = w.v, f.g = w.g, f.mass = mass, f.bad = w.bad, f.kpart = w.kpart;
-    f.hk = hk, f.frame_xyz = frame_xyz;
-    if (mr) {          // with restraints: the four restrained instantiations
-        const dim3 grid((unsigned)n_items), block(NB_NT);
-        NbCutDev d = {};
-        if (c) d = c->dev, d.box = w.box, d.er = w.er;
-        if (c && cfail) GRAPPA_LAUNCH(ms_force_restr_cons_cut_kernel, grid, block, 0, st, f, d, cfail, *mr);
-        else if (c) GRAPPA_LAUNCH(ms_force_restr_cut_kernel, grid, block, 0, st, f, d, *mr);
-        else if (cfail) GRAPPA_LAUNCH(ms_force_restr_cons_kernel, grid, block, 0, st, f, cfail, *mr);
-        else GRAPPA_LAUNCH(ms_force_restr_kernel, grid, block, 0, st, f, *mr);
-        return;
-    }
-    if (c) {
-        NbCutDev d = c->dev;
-        d.box = w.box, d.er = w.er;
-        if (cfail) GRAPPA_LAUNCH(ms_force_cons_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d, cfail);
-        else GRAPPA_LAUNCH(ms_force_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, d);
-    } else if (cfail) {
-        GRAPPA_LAUNCH(ms_force_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f, cfail);
-    } else {
-        GRAPPA_LAUNCH(ms_force_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, f);
-    }
-}
-
-// steps_terms_at of csrc/rs_force.h at w.x, in the part of this workspace that the cut or the planned nonbonded call takes
-int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const int* table_dev, int n_items,
-                    int n_blocks, const MsWs& w) {
-    if (c) return steps_terms_at(stream, mm, nb, c->opts, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbcut, w.nbcut_bytes);
-    return steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
-                          sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
-}
-
-MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w) {
-    MsOutArgs a = {};
-    a.N = mm->N, a.C = mm->C, a.B = mm->B, a.n_blocks = q.n_blocks, a.has_nb = nb != nullptr;
-    a.atom_molptr = mm->atom_molptr, a.blk_ptr = q.blk_ptr;
-    a.x = w.x, a.v = w.v, a.terms = w.terms, a.kpart = w.kpart, a.bad = w.bad, a.status_ws = w.status, a.steps_ws = w.steps;
-    return a;
-}
-
-// constraints as the three calls carry them: the caller's tables (cons->K > 0, checked) and the step's constants; the workspace's words
-// are set once it is laid out
-MscDev msc_dev(const grappa_md_cons* cons, const grappa_md_opts* o) {
-    MscDev d = {};
-    d.molptr = cons->cluster_molptr, d.atoms = cons->cluster_atoms, d.d = cons->cluster_d, d.K = cons->K;
-    d.tol2 = 2.0f * cons->tolerance;
-    if (o) d.ih2 = 1.0f / md_consts(o).h2;
-    return d;
-}
-
-void ms_launch_boxes(hipStream_t st, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w, int n_items) {
-    const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
-    GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
-}
-
-void msc_launch_close(hipStream_t st, const RsGeom& q, const MsWs& w, const MscDev& cn, const float* mass, int project, int n_items) {
-    const MscCloseArgs a = {q, w.x, w.v, mass, w.status, cn, w.kpart, project};
-    GRAPPA_LAUNCH(msc_close_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
-}
-
 // ------------------------------------------------------------------------------------------------ restraints (grappa_md_steps_*_restr_f32)
 // Tethers and dihedral restraints of csrc/md_restr.h on every Hamiltonian above.
 //   gradient: every variant launches ms_force_body, whose epilogue holds the owner's gi before g is written, before the closing kick and
@@ -1020,6 +961,185 @@ float* ms_restr_ref(char* base, size_t off, int N, int C, size_t& total) {
     return ref;
 }
 
+// ------------------------------------------------------------------------------------------------ the run plan
+// What a run has, resolved ONCE per call from the optional pointers of its entry: a family of entries is the widest call with the
+// pointers it does not take NULL, and what a plan without an option launches is what the narrower family launches.  The plan lives on
+// the caller's stack and is rebuilt by every call, as RsCut and MsGb always were.
+struct MsHas {                           // what lays claim to words of the workspace
+    bool cut, cons, gb, gbcut, restr;    // the nonbonded cutoff, constraints, the solvent, the solvent's own cutoff, restraints
+    bool boxes() const { return cut || gbcut; }          // either cutoff reads the blocks' boxes
+};
+
+struct MsPlan {
+    MsHas has;
+    RsCut cut;                           // has.cut: RsCut / rs_cut_make of csrc/rs_force.h
+    const grappa_md_cons* cons;          // has.cons: the caller's tables (K > 0), else NULL
+    MsGb gb;                             // has.gb; gb.cut is the solvent's cutoff (has.gbcut) or NULL
+    MsRestr restr;                       // has.restr
+    const RsCut* c() const { return has.cut ? &cut : nullptr; }
+};
+
+// Every refusal an option can meet, in one place: GRAPPA_ERR_ARG, else GRAPPA_OK with p filled.  An entry asks this before it looks at
+// anything else, so a refused option is refused for an empty batch too.
+//   cut   : bad options, or no nb
+//   cons  : K < 0; with K > 0 a NULL table or a tolerance outside [2^-20, 2^-7] (a NaN is refused).  NULL or K == 0: none
+//   gb    : no nb or no charges (the solvent reads them), NULL radius / scale, bad options; cut beside a solvent that has no cutoff of
+//           its own; gbcut without gb, or with bad options
+//   r     : R < 0, a NULL dihedral table with R > 0, R * C >= 2^31, pos_ref without pos_k.  NULL, or R == 0 with pos_k == NULL: none
+int ms_plan(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut, const grappa_md_cons* cons, const grappa_gb_desc* gb,
+            const grappa_gb_cut* gbcut, const grappa_md_restr* r, MsPlan& p) {
+    p = MsPlan{};
+    if (cut) {
+        if (!rs_cut_make(cut, nb, p.cut)) return GRAPPA_ERR_ARG;
+        p.has.cut = true;
+    }
+    if (cons && cons->K != 0) {
+        if (cons->K < 0 || !cons->cluster_molptr || !cons->cluster_atoms || !cons->cluster_d) return GRAPPA_ERR_ARG;
+        if (!(cons->tolerance >= 0x1p-20f && cons->tolerance <= 0x1p-7f)) return GRAPPA_ERR_ARG;
+        p.cons = cons, p.has.cons = true;
+    }
+    if (gb || gbcut) {
+        if (!gb || (cut && !gbcut) || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, p.gb.k)) return GRAPPA_ERR_ARG;
+        if (gbcut && !gb_cut_consts(gbcut, p.gb.cdev)) return GRAPPA_ERR_ARG;
+        p.gb.opts = gb, p.gb.cut = gbcut;
+        p.has.gb = true, p.has.gbcut = gbcut != nullptr;
+    }
+    if (r) {
+        if (r->R < 0 || (r->R > 0 && (!r->dih_molptr || !r->dih_atoms || !r->dih_k || !r->dih_target)) || (r->pos_ref && !r->pos_k))
+            return GRAPPA_ERR_ARG;
+        if (r->R > 0 && mm && mm->C > 0 && (long long)r->R * mm->C >= (1LL << 31)) return GRAPPA_ERR_ARG;
+        if (r->R > 0 || r->pos_k) {
+            p.has.restr = true;
+            p.restr.dev.pos_k = r->pos_k, p.restr.dev.R = r->R, p.restr.ref_src = r->pos_ref;
+            if (r->R > 0) p.restr.dev.molptr = r->dih_molptr, p.restr.dev.atoms = r->dih_atoms, p.restr.dev.k = r->dih_k, p.restr.dev.target = r->dih_target;
+        }
+    }
+    return GRAPPA_OK;
+}
+
+// A plan's words in the workspace (base == NULL: sizes only).  The cut's words lie behind the base's, those of constraints behind both
+// (ms_layout), the solvent's behind those, the restraints' reference last: a narrower plan's layout is a prefix of a wider one's.
+struct MsCarve {
+    MsWs w;
+    MsGbWs gw;                           // has.gb
+    float* ref;                          // has.restr
+    size_t total;
+};
+
+MsCarve ms_carve(char* base, int N, int C, int B, int n_blocks, const MsHas& h) {
+    MsCarve k = {};
+    k.w = ms_layout(base, N, C, B, n_blocks, h.boxes(), h.cons);
+    k.total = k.w.total;
+    if (h.gb) k.gw = ms_gb_layout(base, k.total, N, C, B, n_blocks, h.gbcut), k.total = k.gw.total;
+    if (h.restr) k.ref = ms_restr_ref(base, k.total, N, C, k.total);
+    return k;
+}
+
+// (the *_workspace_bytes entries: constraints count with K > 0)
+size_t ms_bytes(int N, int C, int B, int n_blocks, int K, MsHas h) {
+    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
+    h.cons = K > 0;
+    return ms_carve(nullptr, N, C, B, n_blocks, h).total;
+}
+
+// the restraints as the kernels take them, their reference where the workspace holds it
+MrDev ms_restr_dev(const MsPlan& p, const MsCarve& k) {
+    MrDev m = p.restr.dev;
+    m.ref = k.ref;
+    return m;
+}
+
+// ------------------------------------------------------------------------------------------------ launches
+// the force launch: restraints x constraints (cfail != NULL) x cutoff, chosen here and nowhere else.  hk == 0: no closing kick
+void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const RsGeom& q, const MsWs& w,
+                     const float* mass, float hk, float* frame_xyz, int n_items, const int* cfail, const MrDev* mr) {
+    MsForceArgs f;
+    f.f = rs_force_in(mm, nb, q, w.x, w.status);
+    f.v = w.v, f.g = w.g, f.mass = mass, f.bad = w.bad, f.kpart = w.kpart;
+    f.hk = hk, f.frame_xyz = frame_xyz;
+    const dim3 grid((unsigned)n_items), block(NB_NT);
+    NbCutDev d = {};
+    if (c) d = c->dev, d.box = w.box, d.er = w.er;
+    if (mr) {
+        if (c && cfail) GRAPPA_LAUNCH(ms_force_restr_cons_cut_kernel, grid, block, 0, st, f, d, cfail, *mr);
+        else if (c) GRAPPA_LAUNCH(ms_force_restr_cut_kernel, grid, block, 0, st, f, d, *mr);
+        else if (cfail) GRAPPA_LAUNCH(ms_force_restr_cons_kernel, grid, block, 0, st, f, cfail, *mr);
+        else GRAPPA_LAUNCH(ms_force_restr_kernel, grid, block, 0, st, f, *mr);
+    } else {
+        if (c && cfail) GRAPPA_LAUNCH(ms_force_cons_cut_kernel, grid, block, 0, st, f, d, cfail);
+        else if (c) GRAPPA_LAUNCH(ms_force_cut_kernel, grid, block, 0, st, f, d);
+        else if (cfail) GRAPPA_LAUNCH(ms_force_cons_kernel, grid, block, 0, st, f, cfail);
+        else GRAPPA_LAUNCH(ms_force_kernel, grid, block, 0, st, f);
+    }
+}
+
+// the move launch: constraints, else restraints x boxes, chosen here and nowhere else
+void ms_launch_move(hipStream_t st, const MsPlan& p, const MsMoveArgs& mv, const MscDev& cn, const MsWs& w, int n_items) {
+    const dim3 grid((unsigned)n_items), block(NB_NT);
+    if (p.has.cons) GRAPPA_LAUNCH(ms_move_cons_kernel, grid, block, 0, st, mv, cn);
+    else if (p.has.restr && p.has.boxes()) GRAPPA_LAUNCH(ms_move_restr_cut_kernel, grid, block, 0, st, mv, w.box);
+    else if (p.has.restr) GRAPPA_LAUNCH(ms_move_restr_kernel, grid, block, 0, st, mv);
+    else if (p.has.boxes()) GRAPPA_LAUNCH(ms_move_cut_kernel, grid, block, 0, st, mv, w.box);
+    else GRAPPA_LAUNCH(ms_move_kernel, grid, block, 0, st, mv);
+}
+
+// The energy terms at w.x, by the library's own entries.  six: the six of steps_terms_at (csrc/rs_force.h), in the part of this workspace
+// that the cut or the planned nonbonded call takes (a frame that asks for the solvent's energy alone does not need them); with a
+// solvent its two terms, in a region of their own.
+int ms_launch_terms(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const MsPlan& p, const int* table_dev, int n_items,
+                    int n_blocks, const MsCarve& k, bool six) {
+    const MsWs& w = k.w;
+    int rc = GRAPPA_OK;
+    if (six && p.has.cut)
+        rc = steps_terms_at(stream, mm, nb, p.cut.opts, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbcut, w.nbcut_bytes);
+    else if (six)
+        rc = steps_terms_at(stream, mm, nb, nullptr, table_dev, n_items, n_blocks, w.x, w.e_mm, w.e_nb, w.terms, w.nbpart,
+                            sizeof(double) * 2 * (size_t)n_blocks * (size_t)mm->C);
+    if (rc == GRAPPA_OK && p.has.gb)
+        rc = steps_gb_cut_terms_at(stream, mm, nb, p.gb.opts, p.gb.cut, table_dev, n_items, n_blocks, w.x, k.gw.e_gb, k.gw.terms_gb, k.gw.fwd,
+                                   k.gw.fwd_bytes);
+    return rc;
+}
+
+MsOutArgs ms_out_args(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w) {
+    MsOutArgs a = {};
+    a.N = mm->N, a.C = mm->C, a.B = mm->B, a.n_blocks = q.n_blocks, a.has_nb = nb != nullptr;
+    a.atom_molptr = mm->atom_molptr, a.blk_ptr = q.blk_ptr;
+    a.x = w.x, a.v = w.v, a.terms = w.terms, a.kpart = w.kpart, a.bad = w.bad, a.status_ws = w.status, a.steps_ws = w.steps;
+    return a;
+}
+
+// ms_out_kernel over `threads` threads and, with the solvent's terms, ms_out_gb_kernel behind it.  item_wise (constraints or restraints):
+// a refused item's outputs are not touched
+void ms_launch_out(hipStream_t st, const MsOutArgs& a, bool item_wise, size_t threads, const float* terms_gb, float* esolv) {
+    const dim3 grid((unsigned)((threads + 255) / 256)), grid_bc((unsigned)(((size_t)a.B * a.C + 255) / 256)), block(256);
+    if (item_wise) GRAPPA_LAUNCH(ms_out_kernel<true>, grid, block, 0, st, a);
+    else GRAPPA_LAUNCH(ms_out_kernel<false>, grid, block, 0, st, a);
+    if (!terms_gb) return;
+    if (item_wise) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, grid_bc, block, 0, st, a, terms_gb, esolv);
+    else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, grid_bc, block, 0, st, a, terms_gb, esolv);
+}
+
+// constraints as the three calls carry them: the caller's tables (cons->K > 0, checked), the step's constants and the workspace's words
+MscDev msc_dev(const grappa_md_cons* cons, const grappa_md_opts* o, const MsWs& w) {
+    MscDev d = {};
+    d.molptr = cons->cluster_molptr, d.atoms = cons->cluster_atoms, d.d = cons->cluster_d, d.K = cons->K;
+    d.claim = w.claim, d.cfail = w.cfail;
+    d.tol2 = 2.0f * cons->tolerance;
+    d.ih2 = 1.0f / md_consts(o).h2;
+    return d;
+}
+
+void ms_launch_boxes(hipStream_t st, const grappa_nb_desc* nb, const RsGeom& q, const MsWs& w, int n_items) {
+    const RsBoxArgs b = {q, w.x, nb->exc_ptr, nb->exc_atom, w.box, w.er};
+    GRAPPA_LAUNCH(rs_box_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, b);
+}
+
+void msc_launch_close(hipStream_t st, const RsGeom& q, const MsWs& w, const MscDev& cn, const float* mass, int project, int n_items) {
+    const MscCloseArgs a = {q, w.x, w.v, mass, w.status, cn, w.kpart, project};
+    GRAPPA_LAUNCH(msc_close_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, a);
+}
+
 MrEnergyArgs mr_energy_args(const grappa_mm_desc* mm, const MsWs& w, const MrDev& m, int final, float* erestr, float* phi) {
     MrEnergyArgs a = {};
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.final = final;
@@ -1027,22 +1147,28 @@ MrEnergyArgs mr_energy_args(const grappa_mm_desc* mm, const MsWs& w, const MrDev
     return a;
 }
 
-// the three calls, with and without a cutoff (c == NULL: none) and constraints (cons == NULL: none, the launches as they were)
-int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
-            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes,
-            const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, const MsRestr* rs = nullptr) {
+// ------------------------------------------------------------------------------------------------ the three calls
+// what an entry may be asked to write beyond the state: NULL where it is not asked for or its family has no such output
+struct MsFrames {
+    float *xyz, *epot, *ekin, *esolv, *erestr, *phi;
+};
+
+struct MsEnds {
+    float *xyz, *vel, *epot, *ekin;      // required, as steps and status are
+    int *steps, *status;
+    float *esolv, *erestr, *phi;
+};
+
+int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const MsPlan& p, const float* mass,
+            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
-    MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    size_t total = gb ? gw.total : w.total;
-    MrDev mrd = {};
-    const MrDev* mr = nullptr;
-    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
-    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
+    const MsCarve cv = ms_carve((char*)ws, mm->N, mm->C, mm->B, n_blocks, p.has);
+    if (ws_bytes < cv.total) return GRAPPA_ERR_WORKSPACE;
+    const MsWs& w = cv.w;
+    const MrDev mrd = ms_restr_dev(p, cv);
+    const MrDev* mr = p.has.restr ? &mrd : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MsInitArgs a;
     a.N = mm->N, a.C = mm->C, a.B = mm->B, a.n_blocks = n_blocks;
@@ -1055,72 +1181,63 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     n = n > kc ? n : kc;
     GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
-    // with restraints: the reference into the workspace and the tables vetted, behind the init kernel (and the constraints' vet) and in
-    // front of everything that reads status
-    const auto restr_init = [&]() {
-        if (!mr) return;
-        if (mr->pos_k) {
-            const size_t n3 = (size_t)mm->N * mm->C * 3;
-            GRAPPA_LAUNCH(mr_ref_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, n3, rs->ref_src ? rs->ref_src : mm->xyz,
-                          const_cast<float*>(mr->ref));
-        }
-        if (n_items > 0) GRAPPA_LAUNCH(mr_vet_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, *mr, w.status, w.bad);
-    };
-    if (cons) {
-        // the tables vetted (clear, claim, read back), the start's S and P, then boxes, force and the kinetic partials: 6 to 8 launches
-        MscDev cn = msc_dev(cons, o);
-        cn.claim = w.claim, cn.cfail = w.cfail;
+    const dim3 grid((unsigned)n_items), block(NB_NT);
+    MscDev cn = {};
+    if (p.cons) {          // the tables vetted: clear, claim, read back
+        cn = msc_dev(p.cons, o, w);
         const size_t nk = (size_t)mm->N > kc ? (size_t)mm->N : kc;
         GRAPPA_LAUNCH(msc_clear_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, mm->N, kc, w.claim, w.cfail);
-        if (n_items > 0) {
-            GRAPPA_LAUNCH(msc_claim_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn);
-            GRAPPA_LAUNCH(msc_vet_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, cn, w.status, w.bad);
-            restr_init();
-            if (cons->constrain_start || !vel_in) {
-                const MscStartArgs sa = {q, w.x, w.v, mass, w.status, cn, cons->constrain_start != 0};
-                GRAPPA_LAUNCH(msc_start_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, sa);
-            }
-            if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
-            ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, w.cfail, mr);
-            if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, true);
-            msc_launch_close(st, q, w, cn, mass, 0, n_items);
-        }
-        return grappa_launch_status();
+        if (n_items == 0) return grappa_launch_status();
+        GRAPPA_LAUNCH(msc_claim_kernel, grid, block, 0, st, q, cn);
+        GRAPPA_LAUNCH(msc_vet_kernel, grid, block, 0, st, q, cn, w.status, w.bad);
     }
-    restr_init();
-    if (boxes && n_items > 0) ms_launch_boxes(st, nb, q, w, n_items);
-    if (n_items > 0) ms_launch_force(st, mm, nb, c, q, w, mass, 0.f, nullptr, n_items, nullptr, mr);
-    if (gb && n_items > 0) ms_launch_gb(st, nb, *gb, q, w, gw, mass, 0.f, n_items, false);
+    // with restraints: the reference into the workspace and the tables vetted, behind the init kernel (and the constraints' vet) and in
+    // front of everything that reads status
+    if (mr && mr->pos_k) {
+        const size_t n3 = (size_t)mm->N * mm->C * 3;
+        GRAPPA_LAUNCH(mr_ref_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, n3, p.restr.ref_src ? p.restr.ref_src : mm->xyz, cv.ref);
+    }
+    if (n_items == 0) return grappa_launch_status();
+    if (mr) GRAPPA_LAUNCH(mr_vet_kernel, grid, block, 0, st, q, *mr, w.status, w.bad);
+    // the start's S and P (with constraints), the boxes (with either cutoff), the gradient at the start without a kick, the solvent's
+    // share of it, and with constraints the kinetic partials
+    if (p.cons && (p.cons->constrain_start || !vel_in)) {
+        const MscStartArgs sa = {q, w.x, w.v, mass, w.status, cn, p.cons->constrain_start != 0};
+        GRAPPA_LAUNCH(msc_start_kernel, grid, block, 0, st, sa);
+    }
+    if (p.has.boxes()) ms_launch_boxes(st, nb, q, w, n_items);
+    ms_launch_force(st, mm, nb, p.c(), q, w, mass, 0.f, nullptr, n_items, w.cfail, mr);
+    if (p.has.gb) ms_launch_gb(st, nb, p.gb, q, w, cv.gw, mass, 0.f, n_items, p.has.cons);
+    if (p.cons) msc_launch_close(st, q, w, cn, mass, 0, n_items);
     return grappa_launch_status();
 }
 
-int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const float* mass,
+int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const MsPlan& p, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
-           float* frames_xyz, float* frames_epot, float* frames_ekin, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr,
-           float* frames_esolv = nullptr, const MsRestr* rs = nullptr, float* frames_erestr = nullptr, float* frames_phi = nullptr) {
+           MsFrames fr) {
+    // an output of an option the plan lacks is no output of this run: dropped before anything asks whether the run writes frames
+    if (!p.has.gb) fr.esolv = nullptr;
+    if (!p.has.restr) fr.erestr = fr.phi = nullptr;
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc < 0) return rc;
     if (n_steps < 1 || step0 < 0 || (long long)step0 + n_steps > o->n_steps) return GRAPPA_ERR_ARG;
-    const bool frames_r = rs && (frames_erestr || frames_phi);
-    const bool frames = o->save_every > 0 && (frames_xyz || frames_epot || frames_ekin || frames_esolv || frames_r);
+    const bool frames_e = fr.epot || fr.ekin || fr.esolv, frames_r = fr.erestr || fr.phi;
+    const bool frames = o->save_every > 0 && (fr.xyz || frames_e || frames_r);
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
-    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
-    MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    size_t total = gb ? gw.total : w.total;
-    MrDev mrd = {};
-    const MrDev* mr = nullptr;
-    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
-    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
+    const MsCarve cv = ms_carve((char*)ws, mm->N, mm->C, mm->B, n_blocks, p.has);
+    if (ws_bytes < cv.total) return GRAPPA_ERR_WORKSPACE;
+    const MsWs& w = cv.w;
+    const MrDev mrd = ms_restr_dev(p, cv);
+    const MrDev* mr = p.has.restr ? &mrd : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const MdConsts k = md_consts(o);
-    const float hkf = gb ? 0.f : k.hk;          // with the solvent the chain launch gives the closing kick
+    const float hkf = p.has.gb ? 0.f : k.hk;          // with the solvent the chain launch gives the closing kick
+    const bool item_wise = p.has.cons || p.has.restr;
     MscDev cn = {};
-    if (cons) cn = msc_dev(cons, o), cn.claim = w.claim, cn.cfail = w.cfail;
+    if (p.cons) cn = msc_dev(p.cons, o, w);
     MsMoveArgs mv;
     mv.q = q, mv.x = w.x, mv.v = w.v, mv.g = w.g, mv.mass = mass, mv.mol_key = mol_key;
     mv.bad = w.bad, mv.status = w.status, mv.steps = w.steps, mv.k = k;
@@ -1131,250 +1248,186 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
         const bool due = frames && done % o->save_every == 0;
         const size_t f = due ? (size_t)(done / o->save_every - 1 - frame0) : 0;
         if (n_items > 0) {
+            // move, force: 2 launches; with constraints move, boxes (with either cutoff), force, close: 3 or 4; the solvent's three
+            // behind the force launch
             mv.step = o->first_step + (unsigned)(step0 + s);
-            float* fx = due && frames_xyz ? frames_xyz + f * n3 : nullptr;
-            if (cons) {          // move, boxes (with a cutoff), force, close: 3 launches, 4 under a cutoff
-                GRAPPA_LAUNCH(ms_move_cons_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, cn);
-                if (boxes) ms_launch_boxes(st, nb, q, w, n_items);
-                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, w.cfail, mr);
-                if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, true);
-                msc_launch_close(st, q, w, cn, mass, 1, n_items);
-            } else {
-                if (mr && boxes) GRAPPA_LAUNCH(ms_move_restr_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
-                else if (mr) GRAPPA_LAUNCH(ms_move_restr_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-                else if (boxes) GRAPPA_LAUNCH(ms_move_cut_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv, w.box);
-                else GRAPPA_LAUNCH(ms_move_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, mv);
-                ms_launch_force(st, mm, nb, c, q, w, mass, hkf, fx, n_items, nullptr, mr);
-                if (gb) ms_launch_gb(st, nb, *gb, q, w, gw, mass, k.hk, n_items, false);
-            }
+            ms_launch_move(st, p, mv, cn, w, n_items);
+            if (p.has.cons && p.has.boxes()) ms_launch_boxes(st, nb, q, w, n_items);
+            ms_launch_force(st, mm, nb, p.c(), q, w, mass, hkf, due && fr.xyz ? fr.xyz + f * n3 : nullptr, n_items, w.cfail, mr);
+            if (p.has.gb) ms_launch_gb(st, nb, p.gb, q, w, cv.gw, mass, k.hk, n_items, p.has.cons);
+            if (p.has.cons) msc_launch_close(st, q, w, cn, mass, 1, n_items);
         }
-        if (due && (frames_epot || frames_ekin || frames_esolv)) {
-            const bool terms = frames_epot || (gb && frames_esolv);
-            if (terms) {          // (a frame that asks for the solvent's energy alone does not need the six terms)
-                int erc = frames_epot ? ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w) : GRAPPA_OK;
-                if (erc == GRAPPA_OK && gb)
-                    erc = steps_gb_cut_terms_at(stream, mm, nb, gb->opts, gb->cut, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd,
-                                                gw.fwd_bytes);
+        if (due && frames_e) {
+            const bool terms = fr.epot || fr.esolv;
+            if (terms) {
+                const int erc = ms_launch_terms(stream, mm, nb, p, table_dev, n_items, n_blocks, cv, fr.epot != nullptr);
                 if (erc != GRAPPA_OK) return erc;
             }
             MsOutArgs a = ms_out_args(mm, nb, q, w);
-            a.final = 0, a.with_epot = terms && frames_epot != nullptr;
-            a.epot = frames_epot ? frames_epot + f * bc : nullptr, a.ekin = frames_ekin ? frames_ekin + f * bc : nullptr;
-            if (cons || mr) GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
-            else GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
-            if (gb && terms) {
-                float* fe = frames_esolv ? frames_esolv + f * bc : nullptr;
-                if (cons || mr) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
-                else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, fe);
-            }
+            a.final = 0, a.with_epot = fr.epot != nullptr;
+            a.epot = fr.epot ? fr.epot + f * bc : nullptr, a.ekin = fr.ekin ? fr.ekin + f * bc : nullptr;
+            ms_launch_out(st, a, item_wise, bc, p.has.gb && terms ? cv.gw.terms_gb : nullptr, fr.esolv ? fr.esolv + f * bc : nullptr);
         }
         if (due && frames_r) {          // E_r and the restrained dihedrals of the frame, at the coordinates the step left
-            const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 0, frames_erestr ? frames_erestr + f * bc : nullptr,
-                                                  frames_phi ? frames_phi + f * (size_t)mr->R * mm->C : nullptr);
+            const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 0, fr.erestr ? fr.erestr + f * bc : nullptr,
+                                                  fr.phi ? fr.phi + f * (size_t)mr->R * mm->C : nullptr);
             GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
         }
     }
     return grappa_launch_status();
 }
 
-int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const RsCut* c, const grappa_md_opts* o, const int* table_dev,
-              int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
-              int* status, const grappa_md_cons* cons = nullptr, const MsGb* gb = nullptr, float* esolv = nullptr, const MsRestr* rs = nullptr,
-              float* erestr = nullptr, float* dih_phi = nullptr) {
+int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const MsPlan& p, const int* table_dev,
+              int n_items, int n_blocks, void* ws, size_t ws_bytes, const MsEnds& e) {
     const int rc = steps_seam_check(mm, nb, o && md_opts_ok(o), table_dev, n_items, n_blocks, ws);
     if (rc != GRAPPA_OK) return rc < 0 ? rc : GRAPPA_OK;
-    if (!xyz_out || !vel_out || !epot || !ekin || !steps || !status) return GRAPPA_ERR_ARG;
-    const bool boxes = c != nullptr || (gb && gb->cut);          // either cutoff reads the blocks' boxes
-    const MsWs w = ms_layout((char*)ws, mm->N, mm->C, mm->B, n_blocks, boxes, cons != nullptr);
-    MsGbWs gw = {};
-    if (gb) gw = ms_gb_layout((char*)ws, w.total, mm->N, mm->C, mm->B, n_blocks, gb->cut != nullptr);
-    size_t total = gb ? gw.total : w.total;
-    MrDev mrd = {};
-    const MrDev* mr = nullptr;
-    if (rs) mrd = rs->dev, mrd.ref = ms_restr_ref((char*)ws, total, mm->N, mm->C, total), mr = &mrd;
-    if (ws_bytes < total) return GRAPPA_ERR_WORKSPACE;
+    if (!e.xyz || !e.vel || !e.epot || !e.ekin || !e.steps || !e.status) return GRAPPA_ERR_ARG;
+    const MsCarve cv = ms_carve((char*)ws, mm->N, mm->C, mm->B, n_blocks, p.has);
+    if (ws_bytes < cv.total) return GRAPPA_ERR_WORKSPACE;
+    const MsWs& w = cv.w;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int erc = ms_launch_terms(stream, mm, nb, c, table_dev, n_items, n_blocks, w);
-    if (erc == GRAPPA_OK && gb)
-        erc = steps_gb_cut_terms_at(stream, mm, nb, gb->opts, gb->cut, table_dev, n_items, n_blocks, w.x, gw.e_gb, gw.terms_gb, gw.fwd, gw.fwd_bytes);
+    const int erc = ms_launch_terms(stream, mm, nb, p, table_dev, n_items, n_blocks, cv, true);
     if (erc != GRAPPA_OK) return erc;
-    MsOutArgs a = ms_out_args(mm, nb, rs_geom(mm, table_dev, n_blocks), w);
+    const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    MsOutArgs a = ms_out_args(mm, nb, q, w);
     a.final = 1, a.with_epot = 1;
-    a.xyz_out = xyz_out, a.vel_out = vel_out, a.epot = epot, a.ekin = ekin, a.steps = steps, a.status = status;
-    const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C, n = n3 > bc ? n3 : bc;
-    if (cons || mr) {          // a refused item's outputs are not touched: x and v item by item
-        if (n_items > 0) GRAPPA_LAUNCH(msc_copy_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, rs_geom(mm, table_dev, n_blocks), w.x, w.v, w.status, xyz_out, vel_out);
-        GRAPPA_LAUNCH(ms_out_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a);
-    } else {
-        GRAPPA_LAUNCH(ms_out_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    a.xyz_out = e.xyz, a.vel_out = e.vel, a.epot = e.epot, a.ekin = e.ekin, a.steps = e.steps, a.status = e.status;
+    const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C;
+    const bool item_wise = p.has.cons || p.has.restr;          // a refused item's outputs are not touched: x and v item by item
+    if (item_wise && n_items > 0) GRAPPA_LAUNCH(msc_copy_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, w.x, w.v, w.status, e.xyz, e.vel);
+    ms_launch_out(st, a, item_wise, item_wise || n3 < bc ? bc : n3, p.has.gb ? cv.gw.terms_gb : nullptr, e.esolv);
+    if (p.has.restr) {
+        const MrEnergyArgs ea = mr_energy_args(mm, w, ms_restr_dev(p, cv), 1, e.erestr, e.phi);
+        GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, ea);
     }
-    if (gb) {
-        if (cons || mr) GRAPPA_LAUNCH(ms_out_gb_kernel<true>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
-        else GRAPPA_LAUNCH(ms_out_gb_kernel<false>, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, a, gw.terms_gb, esolv);
-    }
-    if (mr) {
-        const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 1, erestr, dih_phi);
-        GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
-    }
+    return grappa_launch_status();
+}
+
+// without restraints the _restr_ finish still owes its caller erestr: 0 for the molecules that have atoms, behind a finish that succeeded
+int ms_zero_erestr(void* stream, const grappa_mm_desc* mm, float* erestr) {
+    if (!mm || mm->N <= 0 || mm->C <= 0 || mm->B <= 0 || !mm->atom_molptr) return GRAPPA_OK;
+    const size_t bc = (size_t)mm->B * mm->C;
+    GRAPPA_LAUNCH(mr_zero_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), mm->atom_molptr, mm->N,
+                  mm->B, mm->C, erestr);
     return grappa_launch_status();
 }
 
 }  // namespace
 
-extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
-    return ms_layout(nullptr, N, C, B, n_blocks).total;
-}
+// ------------------------------------------------------------------------------------------------ the entries
+// Six families of four: each takes the optional pointers of the one before it plus one, builds the plan from those it takes (the
+// others NULL), returns GRAPPA_ERR_ARG if the plan is refused, and makes the call.  None calls another.
+extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks) { return ms_bytes(N, C, B, n_blocks, 0, MsHas{}); }
 
 extern "C" int grappa_md_steps_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                         const float* mass, const unsigned long long* mol_key, const float* vel_in, const int* table_dev,
                                         int n_items, int n_blocks, void* ws, size_t ws_bytes) {
-    return ms_init(stream, mm, nb, nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    MsPlan p;
+    if (ms_plan(mm, nb, nullptr, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                        const float* mass, const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks,
                                        void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot,
                                        float* frames_ekin) {
-    return ms_run(stream, mm, nb, nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz, frames_epot,
-                  frames_ekin);
+    MsPlan p;
+    if (ms_plan(mm, nb, nullptr, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin});
 }
 
 extern "C" int grappa_md_steps_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o,
                                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out,
                                           float* vel_out, float* epot, float* ekin, int* steps, int* status) {
-    return ms_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
+    MsPlan p;
+    if (ms_plan(mm, nb, nullptr, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes, MsEnds{xyz_out, vel_out, epot, ekin, steps, status});
 }
 
-// with a cutoff: cut == NULL is the call above; bad options in cut, or a cut without nb, are refused before anything else is looked at
+// with a nonbonded cutoff (cut)
 extern "C" size_t grappa_md_steps_cut_workspace_bytes(int N, int C, int B, int n_blocks) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0) return 0;
-    return ms_layout(nullptr, N, C, B, n_blocks, true).total;
+    MsHas h = {};
+    h.cut = true;
+    return ms_bytes(N, C, B, n_blocks, 0, h);
 }
 
 extern "C" int grappa_md_steps_init_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                             const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const float* vel_in,
                                             const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                            const grappa_md_opts* o, const float* mass, const unsigned long long* mol_key, const int* table_dev,
                                            int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps, float* frames_xyz,
                                            float* frames_epot, float* frames_ekin) {
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
-                  frames_epot, frames_ekin);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin});
 }
 
 extern "C" int grappa_md_steps_finish_cut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                               const grappa_md_opts* o, const int* table_dev, int n_items, int n_blocks, void* ws,
                                               size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
                                               int* status) {
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, nullptr, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes, MsEnds{xyz_out, vel_out, epot, ekin, steps, status});
 }
 
-// with X-H constraints: cons == NULL or K == 0 is the call above, with its launches and its bits
-namespace {
-// GRAPPA_OK: constraints to run with; 1: none, forward; < 0: refused
-int msc_check(const grappa_md_cons* cons) {
-    if (cons && cons->K < 0) return GRAPPA_ERR_ARG;
-    if (!cons || cons->K == 0) return 1;
-    if (!cons->cluster_molptr || !cons->cluster_atoms || !cons->cluster_d) return GRAPPA_ERR_ARG;
-    if (!(cons->tolerance >= 0x1p-20f && cons->tolerance <= 0x1p-7f)) return GRAPPA_ERR_ARG;          // (a NaN is refused)
-    return GRAPPA_OK;
-}
-}  // namespace
-
+// with X-H constraints (cons)
 extern "C" size_t grappa_md_steps_cons_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
-    return ms_layout(nullptr, N, C, B, n_blocks, with_cut != 0, K > 0).total;
+    MsHas h = {};
+    h.cut = with_cut != 0;
+    return ms_bytes(N, C, B, n_blocks, K, h);
 }
 
 extern "C" int grappa_md_steps_init_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                              const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass,
                                              const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
                                              int n_blocks, void* ws, size_t ws_bytes) {
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    if (cc == 1) return grappa_md_steps_init_cut_f32(stream, mm, nb, cut, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cons);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                             const grappa_md_opts* o, const grappa_md_cons* cons, const float* mass,
                                             const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
                                             size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin) {
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    if (cc == 1)
-        return grappa_md_steps_run_cut_f32(stream, mm, nb, cut, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
-                                           frames_xyz, frames_epot, frames_ekin);
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
-                  frames_epot, frames_ekin, cons);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin});
 }
 
 extern "C" int grappa_md_steps_finish_cons_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                                const grappa_md_opts* o, const grappa_md_cons* cons, const int* table_dev, int n_items,
                                                int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin,
                                                int* steps, int* status) {
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    if (cc == 1)
-        return grappa_md_steps_finish_cut_f32(stream, mm, nb, cut, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin,
-                                              steps, status);
-    RsCut c;
-    if (cut && !rs_cut_make(cut, nb, c)) return GRAPPA_ERR_ARG;
-    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
-                     cons);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, nullptr, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes, MsEnds{xyz_out, vel_out, epot, ekin, steps, status});
 }
 
-// with the GB/SA implicit solvent: gb == NULL is the call above, with its launches and its bits.  A cutoff together with the solvent, a
-// solvent without nb (it carries the charges), refused options or NULL tables: GRAPPA_ERR_ARG before anything else is looked at.
-namespace {
-// GRAPPA_OK: a solvent to run with (g filled); 1: none, forward; < 0: refused
-int ms_gb_check(const grappa_gb_desc* gb, const grappa_nb_desc* nb, const grappa_nb_cut* cut, MsGb& g) {
-    if (!gb) return 1;
-    if (cut || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k)) return GRAPPA_ERR_ARG;
-    g.opts = gb;
-    g.cut = nullptr;
-    return GRAPPA_OK;
-}
-
-// the solvent under its cutoff (gbcut != NULL): gb is required; the nonbonded cutoff may be given beside it
-int ms_gbcut_check(const grappa_gb_desc* gb, const grappa_gb_cut* gbcut, const grappa_nb_desc* nb, MsGb& g) {
-    if (!gb || !nb || !nb->charge || !gb->radius || !gb->scale || !gb_consts(gb, g.k) || !gb_cut_consts(gbcut, g.cdev)) return GRAPPA_ERR_ARG;
-    g.opts = gb;
-    g.cut = gbcut;
-    return GRAPPA_OK;
-}
-}  // namespace
-
+// with the GB/SA implicit solvent (gb): no nonbonded cutoff beside it in this family
 extern "C" size_t grappa_md_steps_gb_workspace_bytes(int N, int C, int B, int n_blocks, int K) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
-    return ms_gb_layout(nullptr, ms_layout(nullptr, N, C, B, n_blocks, false, K > 0).total, N, C, B, n_blocks).total;
+    MsHas h = {};
+    h.gb = true;
+    return ms_bytes(N, C, B, n_blocks, K, h);
 }
 
 extern "C" int grappa_md_steps_init_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                            const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const float* mass,
                                            const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
                                            int n_blocks, void* ws, size_t ws_bytes) {
-    MsGb g;
-    const int gc = ms_gb_check(gb, nb, cut, g);
-    if (gc < 0) return gc;
-    if (gc == 1) return grappa_md_steps_init_cons_f32(stream, mm, nb, cut, o, cons, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_init(stream, mm, nb, nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cc == 1 ? nullptr : cons, &g);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1382,53 +1435,36 @@ extern "C" int grappa_md_steps_run_gb_f32(void* stream, const grappa_mm_desc* mm
                                           const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
                                           size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin,
                                           float* frames_esolv) {
-    MsGb g;
-    const int gc = ms_gb_check(gb, nb, cut, g);
-    if (gc < 0) return gc;
-    if (gc == 1)
-        return grappa_md_steps_run_cons_f32(stream, mm, nb, cut, o, cons, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
-                                            frames_xyz, frames_epot, frames_ekin);
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_run(stream, mm, nb, nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz, frames_epot,
-                  frames_ekin, cc == 1 ? nullptr : cons, &g, frames_esolv);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin, frames_esolv});
 }
 
 extern "C" int grappa_md_steps_finish_gb_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                              const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const int* table_dev,
                                              int n_items, int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot,
                                              float* ekin, int* steps, int* status, float* esolv) {
-    MsGb g;
-    const int gc = ms_gb_check(gb, nb, cut, g);
-    if (gc < 0) return gc;
-    if (gc == 1)
-        return grappa_md_steps_finish_cons_f32(stream, mm, nb, cut, o, cons, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin,
-                                               steps, status);
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_finish(stream, mm, nb, nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
-                     cc == 1 ? nullptr : cons, &g, esolv);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, nullptr, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes,
+                     MsEnds{xyz_out, vel_out, epot, ekin, steps, status, esolv});
 }
 
-// with the solvent under its own cutoff (grappa_gb_cut): gbcut == NULL is the call above -- its launches, its bits, its refusals, that of
-// cut together with gb included.  With gbcut, gb is required and cut, the nonbonded cutoff, may be given too.
+// with the solvent under its own cutoff (gbcut, include/grappa_hip.h grappa_gb_cut): gb is then required, and cut may be given beside it
 extern "C" size_t grappa_md_steps_gbcut_workspace_bytes(int N, int C, int B, int n_blocks, int K) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
-    return ms_gb_layout(nullptr, ms_layout(nullptr, N, C, B, n_blocks, true, K > 0).total, N, C, B, n_blocks, true).total;
+    MsHas h = {};
+    h.gb = h.gbcut = true;
+    return ms_bytes(N, C, B, n_blocks, K, h);
 }
 
 extern "C" int grappa_md_steps_init_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
                                               const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb,
                                               const grappa_gb_cut* gbcut, const float* mass, const unsigned long long* mol_key,
                                               const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
-    if (!gbcut) return grappa_md_steps_init_gb_f32(stream, mm, nb, cut, o, cons, gb, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
-    MsGb g;
-    RsCut c;
-    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_init(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, cc == 1 ? nullptr : cons,
-                   &g);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1436,16 +1472,10 @@ extern "C" int grappa_md_steps_run_gbcut_f32(void* stream, const grappa_mm_desc*
                                              const grappa_gb_cut* gbcut, const float* mass, const unsigned long long* mol_key,
                                              const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
                                              float* frames_xyz, float* frames_epot, float* frames_ekin, float* frames_esolv) {
-    if (!gbcut)
-        return grappa_md_steps_run_gb_f32(stream, mm, nb, cut, o, cons, gb, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
-                                          frames_xyz, frames_epot, frames_ekin, frames_esolv);
-    MsGb g;
-    RsCut c;
-    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_run(stream, mm, nb, cut ? &c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
-                  frames_epot, frames_ekin, cc == 1 ? nullptr : cons, &g, frames_esolv);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin, frames_esolv});
 }
 
 extern "C" int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1453,72 +1483,18 @@ extern "C" int grappa_md_steps_finish_gbcut_f32(void* stream, const grappa_mm_de
                                                 const grappa_gb_cut* gbcut, const int* table_dev, int n_items, int n_blocks, void* ws,
                                                 size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status,
                                                 float* esolv) {
-    if (!gbcut)
-        return grappa_md_steps_finish_gb_f32(stream, mm, nb, cut, o, cons, gb, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot,
-                                             ekin, steps, status, esolv);
-    MsGb g;
-    RsCut c;
-    if (ms_gbcut_check(gb, gbcut, nb, g) < 0 || (cut && !rs_cut_make(cut, nb, c))) return GRAPPA_ERR_ARG;
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    return ms_finish(stream, mm, nb, cut ? &c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps, status,
-                     cc == 1 ? nullptr : cons, &g, esolv);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, nullptr, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes,
+                     MsEnds{xyz_out, vel_out, epot, ekin, steps, status, esolv});
 }
 
-// with restraints (grappa_md_restr): r == NULL, or R == 0 with pos_k == NULL, is the call above -- its launches, its bits, its refusals;
-// erestr is then written as 0 for molecules that have atoms, and the frames' restraint outputs are not written.
-namespace {
-struct MsCallPlan {
-    RsCut c;
-    MsGb g;
-    bool has_cut, has_gb;
-    const grappa_md_cons* cons;
-};
-
-// GRAPPA_OK: restraints to run with (m filled); 1: none, forward; < 0: refused
-int mr_check(const grappa_md_restr* r, const grappa_mm_desc* mm, MsRestr& m) {
-    if (!r) return 1;
-    if (r->R < 0 || (r->R > 0 && (!r->dih_molptr || !r->dih_atoms || !r->dih_k || !r->dih_target)) || (r->pos_ref && !r->pos_k))
-        return GRAPPA_ERR_ARG;
-    if (r->R > 0 && mm && mm->C > 0 && (long long)r->R * mm->C >= (1LL << 31)) return GRAPPA_ERR_ARG;
-    if (r->R == 0 && !r->pos_k) return 1;
-    m.dev = MrDev{};
-    m.dev.pos_k = r->pos_k, m.dev.R = r->R;
-    if (r->R > 0) m.dev.molptr = r->dih_molptr, m.dev.atoms = r->dih_atoms, m.dev.k = r->dih_k, m.dev.target = r->dih_target;
-    m.ref_src = r->pos_ref;
-    return GRAPPA_OK;
-}
-
-// the refusals of the _gbcut_ family, in its order: the solvent (with or without its cutoff), the nonbonded cutoff, the constraints
-int ms_call_plan(const grappa_nb_desc* nb, const grappa_nb_cut* cut, const grappa_md_cons* cons, const grappa_gb_desc* gb,
-                 const grappa_gb_cut* gbcut, MsCallPlan& p) {
-    p.has_cut = p.has_gb = false, p.cons = nullptr;
-    if (gbcut) {
-        if (ms_gbcut_check(gb, gbcut, nb, p.g) < 0) return GRAPPA_ERR_ARG;
-        p.has_gb = true;
-    } else if (gb) {
-        const int gc = ms_gb_check(gb, nb, cut, p.g);
-        if (gc < 0) return gc;
-        p.has_gb = true;
-    }
-    if (cut) {
-        if (!rs_cut_make(cut, nb, p.c)) return GRAPPA_ERR_ARG;
-        p.has_cut = true;
-    }
-    const int cc = msc_check(cons);
-    if (cc < 0) return cc;
-    p.cons = cc == 1 ? nullptr : cons;
-    return GRAPPA_OK;
-}
-}  // namespace
-
+// with restraints (r, include/grappa_hip.h grappa_md_restr).  The finish requires erestr whatever the plan holds; without restraints it is
+// written as 0 for molecules that have atoms, and the frames' restraint outputs are not written.
 extern "C" size_t grappa_md_steps_restr_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut, int with_gb, int with_gbcut) {
-    if (N <= 0 || C <= 0 || B <= 0 || n_blocks < 0 || K < 0) return 0;
-    const bool gbcut = with_gbcut != 0, gb = with_gb != 0 || gbcut;
-    size_t total = ms_layout(nullptr, N, C, B, n_blocks, with_cut != 0 || gbcut, K > 0).total;
-    if (gb) total = ms_gb_layout(nullptr, total, N, C, B, n_blocks, gbcut).total;
-    ms_restr_ref(nullptr, total, N, C, total);
-    return total;
+    MsHas h = {};
+    h.cut = with_cut != 0, h.gbcut = with_gbcut != 0, h.gb = with_gb != 0 || h.gbcut, h.restr = true;
+    return ms_bytes(N, C, B, n_blocks, K, h);
 }
 
 extern "C" int grappa_md_steps_init_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1526,16 +1502,9 @@ extern "C" int grappa_md_steps_init_restr_f32(void* stream, const grappa_mm_desc
                                               const grappa_gb_cut* gbcut, const grappa_md_restr* r, const float* mass,
                                               const unsigned long long* mol_key, const float* vel_in, const int* table_dev, int n_items,
                                               int n_blocks, void* ws, size_t ws_bytes) {
-    MsRestr m;
-    const int rc = mr_check(r, mm, m);
-    if (rc < 0) return rc;
-    if (rc == 1)
-        return grappa_md_steps_init_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
-    MsCallPlan p;
-    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
-    if (pc < 0) return pc;
-    return ms_init(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes, p.cons,
-                   p.has_gb ? &p.g : nullptr, &m);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, r, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
 }
 
 extern "C" int grappa_md_steps_run_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1544,17 +1513,10 @@ extern "C" int grappa_md_steps_run_restr_f32(void* stream, const grappa_mm_desc*
                                              const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws,
                                              size_t ws_bytes, int step0, int n_steps, float* frames_xyz, float* frames_epot, float* frames_ekin,
                                              float* frames_esolv, float* frames_erestr, float* frames_phi) {
-    MsRestr m;
-    const int rc = mr_check(r, mm, m);
-    if (rc < 0) return rc;
-    if (rc == 1)
-        return grappa_md_steps_run_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0,
-                                             n_steps, frames_xyz, frames_epot, frames_ekin, frames_esolv);
-    MsCallPlan p;
-    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
-    if (pc < 0) return pc;
-    return ms_run(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps, frames_xyz,
-                  frames_epot, frames_ekin, p.cons, p.has_gb ? &p.g : nullptr, frames_esolv, &m, frames_erestr, frames_phi);
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, r, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin, frames_esolv, frames_erestr, frames_phi});
 }
 
 extern "C" int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
@@ -1562,22 +1524,9 @@ extern "C" int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_de
                                                 const grappa_gb_cut* gbcut, const grappa_md_restr* r, const int* table_dev, int n_items,
                                                 int n_blocks, void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin,
                                                 int* steps, int* status, float* esolv, float* erestr, float* dih_phi) {
-    if (!erestr) return GRAPPA_ERR_ARG;
-    MsRestr m;
-    const int rc = mr_check(r, mm, m);
-    if (rc < 0) return rc;
-    if (rc == 1) {
-        const int fc = grappa_md_steps_finish_gbcut_f32(stream, mm, nb, cut, o, cons, gb, gbcut, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out,
-                                                        vel_out, epot, ekin, steps, status, esolv);
-        if (fc != GRAPPA_OK || !mm || mm->N <= 0 || mm->C <= 0 || mm->B <= 0 || !mm->atom_molptr) return fc;
-        const size_t bc = (size_t)mm->B * mm->C;
-        GRAPPA_LAUNCH(mr_zero_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), mm->atom_molptr,
-                      mm->N, mm->B, mm->C, erestr);
-        return grappa_launch_status();
-    }
-    MsCallPlan p;
-    const int pc = ms_call_plan(nb, cut, cons, gb, gbcut, p);
-    if (pc < 0) return pc;
-    return ms_finish(stream, mm, nb, p.has_cut ? &p.c : nullptr, o, table_dev, n_items, n_blocks, ws, ws_bytes, xyz_out, vel_out, epot, ekin, steps,
-                     status, p.cons, p.has_gb ? &p.g : nullptr, esolv, &m, erestr, dih_phi);
+    MsPlan p;
+    if (!erestr || ms_plan(mm, nb, cut, cons, gb, gbcut, r, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    const int fc = ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes,
+                             MsEnds{xyz_out, vel_out, epot, ekin, steps, status, esolv, erestr, dih_phi});
+    return fc != GRAPPA_OK || p.has.restr ? fc : ms_zero_erestr(stream, mm, erestr);
 }

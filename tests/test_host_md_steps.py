@@ -217,6 +217,46 @@ def test_one_copy_of_the_noise_and_of_the_force():
     assert defs("steps_terms_at") == ["rs_force.h"] and "nb_loop.h" in src("Makefile")
 
 
+def _top_level_blocks(text):
+    """-> [(header, body)] of the functions and structs of a source text that open at column 0 and close with a brace at column 0 (or
+    on their first line); comments stripped, namespace braces skipped"""
+    blocks, cur = [], None
+    for line in re.sub(r"//.*", "", text).split("\n"):
+        line = line.rstrip()
+        if cur is None:
+            if line[:1] in ("", " ", "#", "}") or line.startswith("namespace") or (line.endswith(";") and "{" not in line):
+                continue
+            cur = []
+        cur.append(line)
+        if line in ("}", "};") or (len(cur) == 1 and line.endswith("}")):
+            head, _, body = "\n".join(cur).partition("{")
+            blocks.append((head, body))
+            cur = None
+    assert cur is None
+    return blocks
+
+
+def test_the_entries_share_one_plan_and_one_carve():
+    """csrc/dynamics_steps.hip: no grappa_md_steps_* entry calls another -- each builds the plan from the pointers it takes and makes
+    the call, in a handful of statements -- and the workspace is carved in one function: ms_layout, ms_gb_layout and ms_restr_ref have
+    one caller each"""
+    blocks = _top_level_blocks(open(os.path.join(ROOT, "grappa_amd", "csrc", "dynamics_steps.hip")).read())
+    entries = [(h, b) for h, b in blocks if 'extern "C"' in h and "grappa_md_steps_" in h]
+    families = ("", "_cut", "_cons", "_gb", "_gbcut", "_restr")
+    names = {f"grappa_md_steps_{c}{f}_f32" for c in ("init", "run", "finish") for f in families} | {f"grappa_md_steps{f}_workspace_bytes" for f in families}
+    assert len(entries) == 24 and {re.search(r"grappa_md_steps_\w+", h).group(0) for h, _ in entries} == names
+    for h, b in entries:
+        name = re.search(r"grappa_md_steps_\w+", h).group(0)
+        assert "grappa_md_steps_" not in b, f"{name} names another entry"
+        assert b.count(";") <= 5, f"{name} has grown: {b.count(';')} statements"
+        assert "_workspace_bytes" in name or "ms_plan(" in b, f"{name} does not build the plan"
+    for fn in ("ms_layout", "ms_gb_layout", "ms_restr_ref"):
+        callers = [h for h, b in blocks if re.search(r"\b" + fn + r"\(", b)]
+        assert len(callers) == 1 and "ms_carve(" in callers[0], (fn, callers)
+    for fn in ("ms_plan", "ms_carve"):
+        assert sum(1 for h, _ in blocks if re.search(r"\b" + fn + r"\(", h)) == 1, f"{fn} is not defined once"
+
+
 def test_the_inputs_of_the_gpu_tests_are_finite_and_mostly_steady():
     """A condition on the inputs, not a measurement: every restated state is finite, and over all (item, step count) pairs of the
     trajectory cases at most one in ten is not steady (tests/test_gpu_md.py _gate_state), for x and for v -- a gate calibrated by
