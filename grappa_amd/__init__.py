@@ -19,8 +19,10 @@ from .relax import RelaxResult, ScanResult, relax, relax_graph, torsion_scan
 from .dynamics import MDResult, simulate, simulate_graph
 from .constraints import ConstraintBatch, Constraints, hydrogen_constraints
 from .restraints import RestraintBatch, Restraints, set_dihedral
+from .replica import ReplicaExchange, acceptance
 
 __all__ = ["MolBatch", "batch", "unbatch", "set_number_confs", "delete_dummy_confs", "Molecule", "Parameters", "GrappaModel",
            "Energy", "MolwiseLoss", "get_default_model_config", "model_from_config", "model_from_dict", "model_from_tag", "model_from_path", "Grappa", "FastEvaluator", "Evaluator", "eval_model",
            "TrainSchedule", "DeviceDataset", "Dataset", "MolData", "Trainer", "RelaxResult", "relax", "relax_graph", "MDResult", "simulate", "simulate_graph",
-           "Constraints", "ConstraintBatch", "hydrogen_constraints", "Restraints", "RestraintBatch", "set_dihedral", "ScanResult", "torsion_scan"]
+           "Constraints", "ConstraintBatch", "hydrogen_constraints", "Restraints", "RestraintBatch", "set_dihedral", "ScanResult", "torsion_scan",
+           "ReplicaExchange", "acceptance"]

@@ -132,6 +132,11 @@ class MdRestr(C.Structure):
                 ("dih_target", C.c_void_p), ("R", C.c_int)]
 
 
+class MdRemd(C.Structure):
+    """grappa_md_remd (additions to ABI 11): a temperature ladder over the conformations of a stepwise run, with or without exchanges"""
+    _fields_ = [("temperatures", C.c_void_p), ("slots_in", C.c_void_p), ("exchange_every", C.c_int), ("init_at_ladder", C.c_int)]
+
+
 class PLossDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("mol_ptr", C.c_void_p * 6), ("p", C.c_void_p * 6), ("ref", C.c_void_p * 6),
                 ("width", C.c_int * 6), ("ref_width", C.c_int * 6), ("fac", C.c_float * 6), ("reg", C.c_float * 6),
@@ -346,6 +351,17 @@ SIGNATURES = {
     "grappa_md_steps_finish_restr_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
                                               C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp,
                                               _vp, _vp, _vp, _vp, _vp]),
+    # temperature ladders and replica exchange on the stepwise dynamics (additions to ABI 11)
+    "grappa_md_remd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "grappa_md_remd_init_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                     C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), C.POINTER(MdRemd), _vp, _vp, _vp, _vp, _i, _i, _vp,
+                                     _sz]),
+    "grappa_md_remd_run_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                    C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), C.POINTER(MdRemd), _vp, _vp, _vp, _i, _i, _vp, _sz,
+                                    _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "grappa_md_remd_finish_f32": (_i, [_vp, C.POINTER(MMDesc), C.POINTER(NbDesc), C.POINTER(NbCut), C.POINTER(MdOpts), C.POINTER(MdCons),
+                                       C.POINTER(GbDesc), C.POINTER(GbCut), C.POINTER(MdRestr), C.POINTER(MdRemd), _vp, _i, _i, _vp, _sz, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "grappa_loss_ef_fwd_bwd_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "grappa_loss_param_fwd_bwd_f32": (_i, [_vp, C.POINTER(PLossDesc), _vp, C.POINTER(VP6)]),
     "grappa_eval_se_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -4,6 +4,7 @@ is a helper here.  It uses `self.lib`, `self._stream()` and `self._workspace()` 
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -600,7 +601,52 @@ class MMBackend:
                        constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv,
                        restr=(restraints, restraint_reference, restraint_energy, dihedral_out, frames_restraint_energy, frames_dihedrals))
 
-    # The six families of grappa_md_steps_* entries, narrowest first.  A family takes the optional structs of the one before it plus one
+    def md_steps_remd(self, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps,
+                      status, frames_xyz=None, frames_epot=None, frames_ekin=None, atom_counts_host=None, steps_per_call: int = 1000,
+                      workspace=None, constraints=None, constrain_start=True, gb=None, solvent=None, esolv=None, frames_esolv=None, cutoff=None,
+                      restraints=None, restraint_reference=None, restraint_energy=None, dihedral_out=None, frames_restraint_energy=None,
+                      frames_dihedrals=None, temperatures=None, slots=None, exchange_every: int = 0, init_at_ladder: bool = True,
+                      slots_out=None, exchange_slots=None, exchange_epot=None, exchange_erestr=None) -> None:
+        """the stepwise dynamics on a temperature ladder, with or without replica exchange (include/grappa_hip.h grappa_md_remd_*_f32):
+        `md_steps_restr`'s arguments with restraints optional too, plus temperatures (C,) float32 on xyz's device (kelvin; slot s of the
+        ladder), slots (B,C) int32 or None (the slot every replica starts in, a permutation per molecule; None: slot c), exchange_every
+        (K; 0: a ladder without exchanges), init_at_ladder (velocities that are drawn: at the replica's slot temperature, else at
+        init_temperature), slots_out (B,C) int32 (required) -> the slots at the end, and the logs of the run's X = n_steps // K attempts,
+        each (X,B,C) or None: exchange_slots int32 (the slots after the attempt), exchange_epot / exchange_erestr float32 (the energies the
+        decision read).  With K > 0 and a log, opts["first_step"] must be a multiple of K.  temperatures None: no ladder, the _restr_ family's
+        calls through the ladder's entries (slots_out is then c).  Status 5: also a slots row that is no permutation or a
+        temperature the ladder refuses.  run calls are cut at multiples of both save_every and K.  NO device sync."""
+        from .restraints import RestraintBatch
+        from .solvent import GBBatch, as_implicit_solvent
+        who = "md_steps_remd"
+        restr = None
+        if restraints is not None:
+            if not isinstance(restraints, RestraintBatch):
+                raise TypeError(f"{who}: restraints must be a RestraintBatch or None, got {type(restraints).__name__}")
+            if restraints.frozen is not None:
+                raise ValueError(f"{who}: frozen atoms are not sent down: fold them into the masses (mass 0) and pass restraints without `frozen`")
+            if restraint_energy is None:
+                raise ValueError(f"{who}: restraint_energy (B,C) is required with restraints")
+            restr = (restraints, restraint_reference, restraint_energy, dihedral_out, frames_restraint_energy, frames_dihedrals)
+        sv = as_implicit_solvent(solvent) if gb is not None or solvent is not None else None
+        if (sv is None) != (gb is None) or (gb is not None and not isinstance(gb, GBBatch)):
+            raise TypeError(f"{who}: gb (a GBBatch) and solvent (a model) go together, got {type(gb).__name__}, {solvent!r}")
+        if sv is not None:
+            if cutoff is not None and sv.cutoff is None:
+                raise ValueError(f"{who}: a nonbonded cutoff beside the implicit solvent needs a solvent with a cutoff of its own "
+                                 "(ImplicitSolvent(cutoff=))")
+            if nb is None:
+                raise ValueError(f"{who}: the implicit solvent needs the nonbonded tables (nb): they carry the charges")
+            gb.check_offset(sv.offset)
+        if isinstance(exchange_every, bool) or int(exchange_every) != exchange_every or exchange_every < 0:
+            raise ValueError(f"{who}: exchange_every must be an integer >= 0, got {exchange_every!r}")
+        self._md_steps(who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps,
+                       status, frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints,
+                       constrain_start, gb=gb, solvent=sv, esolv=esolv, frames_esolv=frames_esolv, restr=restr,
+                       remd=(temperatures, slots, int(exchange_every), bool(init_at_ladder), slots_out, exchange_slots, exchange_epot,
+                             exchange_erestr))
+
+    # The seven families of entries, narrowest first.  A family takes the optional structs of the one before it plus one
     # (a family IS the widest call with the others NULL), so a row says only which: the structs of its head behind (stream, mm, nb), the
     # arguments of its workspace_bytes behind n_blocks, and how many of the optional outputs -- (frames_)esolv, (frames_)erestr, phi --
     # its run and finish take behind the required ones.
@@ -611,13 +657,24 @@ class MMBackend:
         "_gb":    (("cut", "o", "cons", "gb"), ("K",), 1),
         "_gbcut": (("cut", "o", "cons", "gb", "gbcut"), ("K",), 1),
         "_restr": (("cut", "o", "cons", "gb", "gbcut", "restr"), ("K", "with_cut", "with_gb", "with_gbcut"), 3),
+        # (the ladder's entries are named grappa_md_remd_*, not grappa_md_steps_*_remd_*: `_md_steps_entry`; behind the optional outputs
+        # its run takes the three logs and its finish slots_out)
+        "_remd":  (("cut", "o", "cons", "gb", "gbcut", "restr", "remd"), ("K", "with_cut", "with_gb", "with_gbcut", "with_restr"), 3),
     }
+
+    def _md_steps_entry(self, fam, which):
+        """the entry `which` (workspace_bytes, init, run, finish) of a family -> (function, name)"""
+        if fam == "_remd":
+            name = f"grappa_md_remd_{which}" + ("" if which == "workspace_bytes" else "_f32")
+        else:
+            name = f"grappa_md_steps{fam}_workspace_bytes" if which == "workspace_bytes" else f"grappa_md_steps_{which}{fam}_f32"
+        return getattr(self.lib, name), name
 
     def _md_steps(self, who, plan, xyz, ks, eqs, n_per, offset_torsion, nb, opts, mass, mol_key, vel_in, xyz_out, vel_out, epot, ekin, steps, status,
                   frames_xyz, frames_epot, frames_ekin, atom_counts_host, steps_per_call, workspace, cutoff, constraints, constrain_start,
-                  gb=None, solvent=None, esolv=None, frames_esolv=None, restr=None):
+                  gb=None, solvent=None, esolv=None, frames_esolv=None, restr=None, remd=None):
         """init, the run calls and finish of one stepwise run, through the narrowest family of entries that expresses it: the widest
-        option the run has (restraints, the solvent's cutoff, the solvent, constraints, the nonbonded cutoff, none) names the family,
+        option the run has (a ladder, restraints, the solvent's cutoff, the solvent, constraints, the nonbonded cutoff, none) names the family,
         and `_MD_STEPS_FAMILIES` says what that family's calls take; every option the run lacks goes down as NULL"""
         if isinstance(steps_per_call, bool) or int(steps_per_call) != steps_per_call or steps_per_call < 1:
             raise ValueError(f"{who}: steps_per_call must be an integer >= 1, got {steps_per_call}")
@@ -668,39 +725,59 @@ class MMBackend:
             rr = _lib.MdRestr(pos_k=_ptr(r.pos_k), pos_ref=_ptr(ref), dih_molptr=r.dih_molptr.data_ptr() if R else None,
                               dih_atoms=r.dih_atoms.data_ptr() if R else None, dih_k=r.dih_k.data_ptr() if R else None,
                               dih_target=r.dih_target.data_ptr() if R else None, R=R)
+        xr, K, slots_out, logs = None, 0, None, (None, None, None)
+        if remd is not None:
+            temps, slots_in, K, at_ladder, slots_out, *logs = remd
+            X = o.n_steps // K if K > 0 else 0          # attempts of the run
+            _tensors(dev, ((temps, "temperatures", _F32), (slots_in, "slots", _I32), (slots_out, "slots_out", _I32), (logs[0], "exchange_slots", _I32),
+                           (logs[1], "exchange_epot", _F32), (logs[2], "exchange_erestr", _F32)),
+                     ("temperatures", "slots", "exchange_slots", "exchange_epot", "exchange_erestr"))
+            if temps is None and (slots_in is not None or K != 0):
+                raise ValueError(f"{who}: slots and exchange_every need temperatures")
+            if (temps is not None and temps.numel() != Cc) or (slots_in is not None and slots_in.numel() != B * Cc) or slots_out.numel() != B * Cc \
+                    or any(t is not None and t.numel() != X * B * Cc for t in logs):
+                raise ValueError(f"{who}: expected temperatures ({Cc},), slots / slots_out (B,C), the exchange logs ({X},B,C)")
+            if X == 0:
+                logs = (None, None, None)
+            if temps is not None:          # (None: no ladder -- the entries then make the _restr_ family's calls and write slots_out as c)
+                xr = _lib.MdRemd(temperatures=temps.data_ptr(), slots_in=_ptr(slots_in), exchange_every=K, init_at_ladder=int(at_ladder))
+            if er is None:          # (the finish owes its caller erestr whatever the plan holds)
+                er = torch.empty(B * Cc, dtype=_F32, device=dev)
         if N == 0 or Cc == 0 or B == 0:
             return
         table_dev, n_items, n_blocks, _ = self._item_table(nb, counts, N, Cc, dev)
-        have = {"cut": cut, "o": o, "cons": cons, "gb": gbd, "gbcut": gbc, "restr": rr}
-        fam = next((f"_{k}" for k in ("restr", "gbcut", "gb", "cons", "cut") if have[k] is not None), "")
+        have = {"cut": cut, "o": o, "cons": cons, "gb": gbd, "gbcut": gbc, "restr": rr, "remd": xr}
+        fam = "_remd" if remd is not None else next((f"_{k}" for k in ("restr", "gbcut", "gb", "cons", "cut") if have[k] is not None), "")
         head_names, size_names, n_opt = self._MD_STEPS_FAMILIES[fam]
         sizes = {"K": cons.K if cons is not None else 0, "with_cut": int(cut is not None), "with_gb": int(gbd is not None),
-                 "with_gbcut": int(gbc is not None)}
-        need = int(getattr(self.lib, f"grappa_md_steps{fam}_workspace_bytes")(N, Cc, B, n_blocks, *(sizes[k] for k in size_names)))
+                 "with_gbcut": int(gbc is not None), "with_restr": int(rr is not None)}
+        need = int(self._md_steps_entry(fam, "workspace_bytes")[0](N, Cc, B, n_blocks, *(sizes[k] for k in size_names)))
         if workspace is None:
             workspace = self._workspace(need, dev, who)
         else:
             _flat(workspace, "workspace", dev, torch.uint8)
-        sfx = f"{fam}_f32"
-        init, run, finish = (getattr(self.lib, f"grappa_md_steps_{n}{sfx}") for n in ("init", "run", "finish"))
+        (init, init_name), (run, run_name), (finish, finish_name) = (self._md_steps_entry(fam, n) for n in ("init", "run", "finish"))
         head = (self._stream(), C.byref(d), C.byref(nd) if nd is not None else None,
                 *(C.byref(have[k]) if have[k] is not None else None for k in head_names))
         tail = (table_dev.data_ptr(), n_items, n_blocks, workspace.data_ptr(), workspace.numel())
-        _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), f"grappa_md_steps_init{sfx}")
+        _chk(init(*head, mass.data_ptr(), mol_key.data_ptr(), _ptr(vel_in), *tail), init_name)
         frame_outs = (frames_xyz, frames_epot, frames_ekin, frames_esolv, fer, fphi)
         every = o.save_every if F > 0 and any(t is not None for t in frame_outs) else 0
         chunk = int(steps_per_call)
-        if every > 0:
-            chunk = max(chunk // every, 1) * every
+        align = math.lcm(every if every > 0 else 1, K if K > 0 else 1)          # a run call is cut where frames and attempts both allow
+        if align > 1:
+            chunk = max(chunk // align, 1) * align
         done = 0
         while done < o.n_steps:
             n = min(chunk, o.n_steps - done)
             f0 = done // every if every > 0 else 0
             fr = [None if t is None or every == 0 else t.data_ptr() + f0 * (t.numel() // F) * t.element_size() for t in frame_outs[:3 + n_opt]]
-            _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), f"grappa_md_steps_run{sfx}")
+            if remd is not None:          # the rows of the logs of this call's attempts
+                fr += [None if t is None else t.data_ptr() + (done // K) * B * Cc * t.element_size() for t in logs]
+            _chk(run(*head, mass.data_ptr(), mol_key.data_ptr(), *tail, done, n, *fr), run_name)
             done += n
         _chk(finish(*head, *tail, xyz_out.data_ptr(), vel_out.data_ptr(), epot.data_ptr(), ekin.data_ptr(), steps.data_ptr(), status.data_ptr(),
-                    *(_ptr(t) for t in (esolv, er, phi)[:n_opt])), f"grappa_md_steps_finish{sfx}")
+                    *(_ptr(t) for t in (esolv, er, phi)[:n_opt]), *((slots_out.data_ptr(),) if remd is not None else ())), finish_name)
 
     def md_noise(self, mol_key, atom_molptr, C_, step: int, purpose: int, out) -> None:
         """the normal deviates `md_langevin` draws for one step (include/grappa_hip.h grappa_md_noise_f32): mol_key (B,) int64,

@@ -37,6 +37,9 @@
 //   restraints: tethers and dihedral restraints of csrc/md_restr.h: their gradient is added to the owner's gi at the head of the force
 //            launch's epilogue, the one place every Hamiltonian above passes through (the section "restraints" below); a step gains
 //            no launch, init gains two.
+//   ladders: a temperature per conformation and replica exchange between neighbouring slots (csrc/md_remd.h, the section "ladders"
+//            below; the entries grappa_md_remd_*_f32): the move launch reads kt of the item's slot, and behind every K-th step an
+//            exchange launch and a rescale launch follow the energy launches of a frame; a step gains no launch.
 // Same input, same bits; a molecule's bits depend neither on its place in the batch nor on how the steps are dealt out to run calls.
 #include <float.h>
 #include <limits.h>
@@ -47,6 +50,7 @@
 #include "gb_pass.h"
 #include "md_cons.h"
 #include "md_noise.h"
+#include "md_remd.h"
 #include "md_restr.h"
 #include "rs_force.h"
 
@@ -102,11 +106,15 @@ struct MsInitArgs {
     float kt0;
     unsigned first_step;
     MsWs w;
+    const float* lad_t;      // the ladder form: temperatures[C], the start velocities drawn at the replica's slot temperature
+    const int* lad_slots;    // ... the caller's slots_in [B,C], or NULL: slot = c
 };
 
 // a thread per (atom, conformation): x = start, v = vel_in (a frozen atom: 0) or the draw at init_temperature; the first B * C threads
 // also set the items' state, the first n_blocks * C the blocks' words
-__global__ __launch_bounds__(256) void ms_init_kernel(MsInitArgs a) {
+// LADDER: kt0 per conformation, ACC kB T of the slot the replica starts in (a slot out of range, which mx_init_kernel refuses, is clamped)
+template <bool LADDER>
+__device__ __forceinline__ void ms_init_body(const MsInitArgs& a) {
     const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int N = a.N, C = a.C, B = a.B;
     if (u < (size_t)N * C) {
@@ -116,15 +124,20 @@ __global__ __launch_bounds__(256) void ms_init_kernel(MsInitArgs a) {
         if (m > 0.f) {          // (a mass that is zero, negative or NaN: a frozen atom, v = 0)
             if (a.vel_in) {
                 v = {a.vel_in[3 * u], a.vel_in[3 * u + 1], a.vel_in[3 * u + 2]};
-            } else if (a.kt0 > 0.f) {
+            } else if (LADDER || a.kt0 > 0.f) {
                 int lo = 0, hi = B - 1;          // the last molecule that starts at or before the atom
                 while (lo < hi) {
                     const int mid = (lo + hi + 1) >> 1;
                     if (nb_clamp(a.atom_molptr[mid], N) <= atom) lo = mid; else hi = mid - 1;
                 }
                 const int m0 = nb_clamp(a.atom_molptr[lo], N), m1 = nb_clamp(a.atom_molptr[lo + 1], N);
-                if (atom >= m0 && atom < m1)          // (an atom that no molecule holds keeps v = 0)
-                    v = sqrtf(a.kt0 * (1.0f / m)) * md_normal3(a.mol_key[lo], (unsigned)(atom - m0), (unsigned)c, a.first_step, 1u);
+                float kt0 = a.kt0;
+                if constexpr (LADDER) {
+                    const int s = a.lad_slots ? a.lad_slots[(size_t)lo * C + c] : c;
+                    kt0 = mx_kt(a.lad_t[s < 0 ? 0 : (s >= C ? C - 1 : s)]);
+                }
+                if (atom >= m0 && atom < m1 && (!LADDER || kt0 > 0.f))          // (an atom that no molecule holds keeps v = 0)
+                    v = sqrtf(kt0 * (1.0f / m)) * md_normal3(a.mol_key[lo], (unsigned)(atom - m0), (unsigned)c, a.first_step, 1u);
             }
         }
         a.w.x[3 * u] = a.start[3 * u], a.w.x[3 * u + 1] = a.start[3 * u + 1], a.w.x[3 * u + 2] = a.start[3 * u + 2];
@@ -140,6 +153,9 @@ __global__ __launch_bounds__(256) void ms_init_kernel(MsInitArgs a) {
     if (u < (size_t)a.n_blocks * C) a.w.bad[u] = 0, a.w.kpart[u] = 0.0;
 }
 
+__global__ __launch_bounds__(256) void ms_init_kernel(MsInitArgs a) { ms_init_body<false>(a); }
+__global__ __launch_bounds__(256) void ms_init_ladder_kernel(MsInitArgs a) { ms_init_body<true>(a); }
+
 // ------------------------------------------------------------------------------------------------ move
 struct MsMoveArgs {
     RsGeom q;
@@ -150,10 +166,18 @@ struct MsMoveArgs {
     int *status, *steps;
     MdConsts k;
     unsigned step;           // the global index of the step: the random stream's position
+    const float* kt_item;    // the ladder form: ACC kB T of the slot each item holds [B,C] (csrc/md_remd.h), read in place of k.kt
 };
 
+// ACC kB T of the thermostat step: the call's, or on a ladder (csrc/md_remd.h) that of the slot the item holds
+template <bool LADDER>
+__device__ __forceinline__ float ms_kt(const MsMoveArgs& a, size_t item) {
+    if constexpr (LADDER) return a.kt_item[item];
+    else return a.k.kt;
+}
+
 // B, A, O, A on atom i of conformation c (a frozen atom is not touched); CUT: the coordinates it leaves -> bxl[0..3)
-template <bool CUT>
+template <bool CUT, bool LADDER = false>
 __device__ __forceinline__ void ms_move_atom(const MsMoveArgs& a, const RsItem& r, int i, int c, float* bxl) {
     const int C = a.q.C;
     const float m = a.mass[i];
@@ -166,7 +190,7 @@ __device__ __forceinline__ void ms_move_atom(const MsMoveArgs& a, const RsItem& 
         float xx = a.x[off], xy = a.x[off + 1], xz = a.x[off + 2];
         xx += a.k.h2 * vk.x, xy += a.k.h2 * vk.y, xz += a.k.h2 * vk.z;
         if (a.k.thermostat)
-            vk = a.k.c1 * vk + (a.k.c2 * sqrtf(a.k.kt * im)) * md_normal3(a.mol_key[r.mol], (unsigned)(i - r.m0), (unsigned)c, a.step, 0u);
+            vk = a.k.c1 * vk + (a.k.c2 * sqrtf(ms_kt<LADDER>(a, (size_t)r.mol * C + c) * im)) * md_normal3(a.mol_key[r.mol], (unsigned)(i - r.m0), (unsigned)c, a.step, 0u);
         xx += a.k.h2 * vk.x, xy += a.k.h2 * vk.y, xz += a.k.h2 * vk.z;
         a.x[off] = xx, a.x[off + 1] = xy, a.x[off + 2] = xz;
         a.v[off] = vk.x, a.v[off + 1] = vk.y, a.v[off + 2] = vk.z;
@@ -179,7 +203,7 @@ __device__ __forceinline__ void ms_move_atom(const MsMoveArgs& a, const RsItem& 
 
 // the thread's (atom, conformation) of the item; CUT: the coordinates it leaves -> bxl[0..3) (not for a stopped conformation)
 // KEEP (with restraints): a stopped item that no longer runs keeps the status it has (5: its tables were refused)
-template <bool CUT, bool KEEP = false>
+template <bool CUT, bool KEEP = false, bool LADDER = false>
 __device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& r, int k0, const int* stop, float* bxl) {
     const int C = a.q.C, t = threadIdx.x, ni = r.ni;
     const int cl = t / ni, il = t - cl * ni;
@@ -194,7 +218,7 @@ __device__ __forceinline__ void ms_move_lane(const MsMoveArgs& a, const RsItem& 
         }
         return;
     }
-    ms_move_atom<CUT>(a, r, i, c, bxl);
+    ms_move_atom<CUT, LADDER>(a, r, i, c, bxl);
     if (writer) a.steps[item] += 1;
 }
 
@@ -221,7 +245,7 @@ __device__ __forceinline__ void ms_stop_flags(const int* bad, const RsItem& r, i
 
 // CUT: the item also writes the box of its own (block, conformations) at the coordinates it leaves (csrc/nb_cut.h): it is the box's only
 // writer, the force launch after it the reader.  A stopped conformation keeps its box, as it keeps its x.
-template <bool CUT, bool KEEP = false>
+template <bool CUT, bool KEEP = false, bool LADDER = false>
 __device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
     __shared__ int stop[NB_CW];
     RsItem r;
@@ -231,10 +255,10 @@ __device__ __forceinline__ void ms_move_body(const MsMoveArgs& a, float4* box) {
     ms_stop_flags<false>(a.bad, r, C, k0, k1, stop);
     if constexpr (CUT) {
         __shared__ float bx[NB_NT * 3];
-        if (t < ni * r.nc) ms_move_lane<true, KEEP>(a, r, k0, stop, bx + 3 * t);
+        if (t < ni * r.nc) ms_move_lane<true, KEEP, LADDER>(a, r, k0, stop, bx + 3 * t);
         nb_cut_box_write(bx, stop, ni, r.nc, r.blk, C, r.c0, box);
     } else {
-        if (t < ni * r.nc) ms_move_lane<false, KEEP>(a, r, k0, stop, nullptr);
+        if (t < ni * r.nc) ms_move_lane<false, KEEP, LADDER>(a, r, k0, stop, nullptr);
     }
 }
 
@@ -242,6 +266,9 @@ __global__ __launch_bounds__(NB_NT) void ms_move_kernel(MsMoveArgs a) { ms_move_
 __global__ __launch_bounds__(NB_NT) void ms_move_cut_kernel(MsMoveArgs a, float4* box) { ms_move_body<true>(a, box); }
 __global__ __launch_bounds__(NB_NT) void ms_move_restr_kernel(MsMoveArgs a) { ms_move_body<false, true>(a, nullptr); }
 __global__ __launch_bounds__(NB_NT) void ms_move_restr_cut_kernel(MsMoveArgs a, float4* box) { ms_move_body<true, true>(a, box); }
+// on a ladder (csrc/md_remd.h): new kernels, the four above are what they were.  The ladder's vet may refuse an item (5), so both are KEEP
+__global__ __launch_bounds__(NB_NT) void ms_move_ladder_kernel(MsMoveArgs a) { ms_move_body<false, true, true>(a, nullptr); }
+__global__ __launch_bounds__(NB_NT) void ms_move_cut_ladder_kernel(MsMoveArgs a, float4* box) { ms_move_body<true, true, true>(a, box); }
 
 // ------------------------------------------------------------------------------------------------ force
 struct MsForceArgs {
@@ -560,6 +587,7 @@ __global__ __launch_bounds__(NB_NT) void msc_start_kernel(MscStartArgs a) {
 // ---- move
 // the thread's (atom, conformation) of the item: a free atom as ms_move_lane moves it, a centre its whole cluster, a leaf nothing;
 // true: an S of the thread's cluster did not converge
+template <bool LADDER = false>
 __device__ __forceinline__ bool msc_move_lane(const MsMoveArgs& a, const MscDev& cn, const RsItem& r, int k0, const int* stop) {
     const int C = a.q.C, t = threadIdx.x, ni = r.ni;
     const int cc = t / ni, il = t - cc * ni;
@@ -578,7 +606,7 @@ __device__ __forceinline__ bool msc_move_lane(const MsMoveArgs& a, const MscDev&
     }
     if (writer) a.steps[item] += 1;
     if (cn.claim[i] < 0) {
-        ms_move_atom<false>(a, r, i, c, nullptr);
+        ms_move_atom<false, LADDER>(a, r, i, c, nullptr);
         return false;
     }
     Cluster cl;
@@ -604,7 +632,7 @@ __device__ __forceinline__ bool msc_move_lane(const MsMoveArgs& a, const MscDev&
         for (int s = 0; s <= CL; ++s)
             if (s <= cl.L && msc_slot_w(cl, s) > 0.f) {
                 const float w = msc_slot_w(cl, s);
-                st.vs[s] = a.k.c1 * st.vs[s] + (a.k.c2 * sqrtf(a.k.kt * w)) * md_normal3(key, (unsigned)(msc_slot_atom(cl, s) - r.m0), (unsigned)c, a.step, 0u);
+                st.vs[s] = a.k.c1 * st.vs[s] + (a.k.c2 * sqrtf(ms_kt<LADDER>(a, item) * w)) * md_normal3(key, (unsigned)(msc_slot_atom(cl, s) - r.m0), (unsigned)c, a.step, 0u);
             }
         cons_project(cl, st);
     }
@@ -627,6 +655,22 @@ __global__ __launch_bounds__(NB_NT) void ms_move_cons_kernel(MsMoveArgs a, MscDe
     const bool lane = t < r.ni * r.nc;
     const bool fail = lane && msc_move_lane(a, cn, r, k0, stop);
     if (t < r.nc) live[t] = stop[t] == 0;          // (a stopped conformation keeps its failure word, as it keeps its x)
+    msc_write_fail(r, C, lane, fail, live, cn.cfail);
+}
+
+// on a ladder (csrc/md_remd.h): the kernel above with msc_move_lane<true>.  A kernel of its own text, not a shared body: moved into a
+// function the compiler schedules the unladdered kernel differently, and that kernel is to stay the code it was
+__global__ __launch_bounds__(NB_NT) void ms_move_cons_ladder_kernel(MsMoveArgs a, MscDev cn) {
+    __shared__ int stop[NB_CW];
+    __shared__ int live[NB_CW];
+    RsItem r;
+    if (!rs_item(a.q, r)) return;
+    const int C = a.q.C, t = threadIdx.x;
+    const int k0 = nb_clamp(a.q.blk_ptr[r.mol], a.q.n_blocks), k1 = nb_clamp(a.q.blk_ptr[r.mol + 1], a.q.n_blocks);
+    ms_stop_flags<true>(a.bad, r, C, k0, k1, stop);
+    const bool lane = t < r.ni * r.nc;
+    const bool fail = lane && msc_move_lane<true>(a, cn, r, k0, stop);
+    if (t < r.nc) live[t] = stop[t] == 0;
     msc_write_fail(r, C, lane, fail, live, cn.cfail);
 }
 
@@ -961,12 +1005,45 @@ float* ms_restr_ref(char* base, size_t off, int N, int C, size_t& total) {
     return ref;
 }
 
+// ------------------------------------------------------------------------------------------------ ladders (grappa_md_remd_*_f32)
+// A temperature ladder over the C conformations of a call, with or without exchanges between neighbouring slots: csrc/md_remd.h states
+// the replicas, the slots and the kernels.
+//   move    : the LADDER instantiations of the move launches read kt of the item's slot from kt_item; everything else of a step stays.
+//   attempt : behind the step whose global index g is a multiple of exchange_every, after that step's own frame outputs: the energies
+//            by the launches a frame uses (ms_launch_terms, ms_launch_out, mr_energy_kernel) into workspace scratch -- or, where the
+//            frame of this very step asked for them, the frame's own rows: nothing is evaluated twice -- then ms_exchange_kernel (one
+//            workgroup per molecule) and ms_rescale_kernel (one per item).  x and g are untouched, so no force is recomputed.
+//   hazards : slot, who, kt_item and scale are written by the exchange launch alone (init apart) and read by the rescale launch and the
+//            next move launch; v and the kinetic partials are written by the rescale launch between a step's last launch and the next
+//            step's move.  The exchange launch reads status and the flag words, which the step's launches wrote.
+//   status 5: a slots_in row that is no permutation, or a temperature the ladder refuses: mx_init_kernel, as the restraints' vet.  A
+//            run on a ladder is therefore item-wise like a restrained one (the KEEP moves, the item-wise finish).
+//   workspace: the ladder's words behind every other word.
+struct MsRemd {
+    const float* temperatures;
+    const int* slots_in;
+    int every, init_at_ladder;
+};
+
+MxDev ms_remd_layout(char* base, size_t off, int B, int C, size_t& total) {
+    WsCarve k{base};
+    k.off = off;
+    const size_t bc = (size_t)B * C;
+    MxDev x = {};
+    x.slot = k.take<int>(bc), x.who = k.take<int>(bc);
+    x.kt_item = k.take<float>(bc), x.scale = k.take<float>(bc);
+    x.epot = k.take<float>(bc), x.erestr = k.take<float>(bc);
+    total = k.off;
+    return x;
+}
+
 // ------------------------------------------------------------------------------------------------ the run plan
 // What a run has, resolved ONCE per call from the optional pointers of its entry: a family of entries is the widest call with the
 // pointers it does not take NULL, and what a plan without an option launches is what the narrower family launches.  The plan lives on
 // the caller's stack and is rebuilt by every call, as RsCut and MsGb always were.
 struct MsHas {                           // what lays claim to words of the workspace
     bool cut, cons, gb, gbcut, restr;    // the nonbonded cutoff, constraints, the solvent, the solvent's own cutoff, restraints
+    bool remd;                           // a temperature ladder
     bool boxes() const { return cut || gbcut; }          // either cutoff reads the blocks' boxes
 };
 
@@ -976,7 +1053,9 @@ struct MsPlan {
     const grappa_md_cons* cons;          // has.cons: the caller's tables (K > 0), else NULL
     MsGb gb;                             // has.gb; gb.cut is the solvent's cutoff (has.gbcut) or NULL
     MsRestr restr;                       // has.restr
+    MsRemd remd;                         // has.remd
     const RsCut* c() const { return has.cut ? &cut : nullptr; }
+    bool keep() const { return has.restr || has.remd; }      // an item may be refused (5) by a vet of init other than the constraints'
 };
 
 // Every refusal an option can meet, in one place: GRAPPA_ERR_ARG, else GRAPPA_OK with p filled.  An entry asks this before it looks at
@@ -986,8 +1065,10 @@ struct MsPlan {
 //   gb    : no nb or no charges (the solvent reads them), NULL radius / scale, bad options; cut beside a solvent that has no cutoff of
 //           its own; gbcut without gb, or with bad options
 //   r     : R < 0, a NULL dihedral table with R > 0, R * C >= 2^31, pos_ref without pos_k.  NULL, or R == 0 with pos_k == NULL: none
+//   x     : a NULL ladder, exchange_every < 0, exchanges without a thermostat (o: friction > 0 is asked of it).  NULL: none
 int ms_plan(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut, const grappa_md_cons* cons, const grappa_gb_desc* gb,
-            const grappa_gb_cut* gbcut, const grappa_md_restr* r, MsPlan& p) {
+            const grappa_gb_cut* gbcut, const grappa_md_restr* r, MsPlan& p, const grappa_md_remd* x = nullptr,
+            const grappa_md_opts* o = nullptr) {
     p = MsPlan{};
     if (cut) {
         if (!rs_cut_make(cut, nb, p.cut)) return GRAPPA_ERR_ARG;
@@ -1014,15 +1095,22 @@ int ms_plan(const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_
             if (r->R > 0) p.restr.dev.molptr = r->dih_molptr, p.restr.dev.atoms = r->dih_atoms, p.restr.dev.k = r->dih_k, p.restr.dev.target = r->dih_target;
         }
     }
+    if (x) {
+        if (!x->temperatures || x->exchange_every < 0 || (x->exchange_every > 0 && !(o && o->friction > 0.f))) return GRAPPA_ERR_ARG;
+        p.has.remd = true;
+        p.remd = MsRemd{x->temperatures, x->slots_in, x->exchange_every, x->init_at_ladder};
+    }
     return GRAPPA_OK;
 }
 
 // A plan's words in the workspace (base == NULL: sizes only).  The cut's words lie behind the base's, those of constraints behind both
-// (ms_layout), the solvent's behind those, the restraints' reference last: a narrower plan's layout is a prefix of a wider one's.
+// (ms_layout), the solvent's behind those, the restraints' reference behind those, the ladder's words last: a narrower plan's layout is a
+// prefix of a wider one's.
 struct MsCarve {
     MsWs w;
     MsGbWs gw;                           // has.gb
     float* ref;                          // has.restr
+    MxDev x;                             // has.remd (x.temperatures is set by ms_remd_dev)
     size_t total;
 };
 
@@ -1032,6 +1120,7 @@ MsCarve ms_carve(char* base, int N, int C, int B, int n_blocks, const MsHas& h) 
     k.total = k.w.total;
     if (h.gb) k.gw = ms_gb_layout(base, k.total, N, C, B, n_blocks, h.gbcut), k.total = k.gw.total;
     if (h.restr) k.ref = ms_restr_ref(base, k.total, N, C, k.total);
+    if (h.remd) k.x = ms_remd_layout(base, k.total, B, C, k.total);
     return k;
 }
 
@@ -1047,6 +1136,13 @@ MrDev ms_restr_dev(const MsPlan& p, const MsCarve& k) {
     MrDev m = p.restr.dev;
     m.ref = k.ref;
     return m;
+}
+
+// the ladder as the kernels take it: the caller's temperatures and the workspace's words
+MxDev ms_remd_dev(const MsPlan& p, const MsCarve& k) {
+    MxDev x = k.x;
+    x.temperatures = p.remd.temperatures;
+    return x;
 }
 
 // ------------------------------------------------------------------------------------------------ launches
@@ -1073,9 +1169,15 @@ void ms_launch_force(hipStream_t st, const grappa_mm_desc* mm, const grappa_nb_d
     }
 }
 
-// the move launch: constraints, else restraints x boxes, chosen here and nowhere else
+// the move launch: the ladder x (constraints, else refusable items x boxes), chosen here and nowhere else (on a ladder every item is refusable)
 void ms_launch_move(hipStream_t st, const MsPlan& p, const MsMoveArgs& mv, const MscDev& cn, const MsWs& w, int n_items) {
     const dim3 grid((unsigned)n_items), block(NB_NT);
+    if (p.has.remd) {
+        if (p.has.cons) GRAPPA_LAUNCH(ms_move_cons_ladder_kernel, grid, block, 0, st, mv, cn);
+        else if (p.has.boxes()) GRAPPA_LAUNCH(ms_move_cut_ladder_kernel, grid, block, 0, st, mv, w.box);
+        else GRAPPA_LAUNCH(ms_move_ladder_kernel, grid, block, 0, st, mv);
+        return;
+    }
     if (p.has.cons) GRAPPA_LAUNCH(ms_move_cons_kernel, grid, block, 0, st, mv, cn);
     else if (p.has.restr && p.has.boxes()) GRAPPA_LAUNCH(ms_move_restr_cut_kernel, grid, block, 0, st, mv, w.box);
     else if (p.has.restr) GRAPPA_LAUNCH(ms_move_restr_kernel, grid, block, 0, st, mv);
@@ -1153,10 +1255,16 @@ struct MsFrames {
     float *xyz, *epot, *ekin, *esolv, *erestr, *phi;
 };
 
+struct MsExch {                          // the logs of a run's attempts [X,B,C], each NULL where it is not asked for
+    int* slot;
+    float *epot, *erestr;
+};
+
 struct MsEnds {
     float *xyz, *vel, *epot, *ekin;      // required, as steps and status are
     int *steps, *status;
     float *esolv, *erestr, *phi;
+    int* slots;                          // the ladder's entries: required there
 };
 
 int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const MsPlan& p, const float* mass,
@@ -1175,12 +1283,20 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
     a.atom_molptr = mm->atom_molptr, a.start = mm->xyz, a.vel_in = vel_in, a.mass = mass, a.mol_key = mol_key;
     a.kt0 = md_consts(o).kt0, a.first_step = o->first_step;
     a.w = w;
+    const bool at_ladder = p.has.remd && p.remd.init_at_ladder != 0;
+    a.lad_t = at_ladder ? p.remd.temperatures : nullptr, a.lad_slots = at_ladder ? p.remd.slots_in : nullptr;
     size_t n = (size_t)mm->N * mm->C;
     const size_t bc = (size_t)mm->B * mm->C, kc = (size_t)n_blocks * mm->C;
     n = n > bc ? n : bc;
     n = n > kc ? n : kc;
-    GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    if (at_ladder) GRAPPA_LAUNCH(ms_init_ladder_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    else GRAPPA_LAUNCH(ms_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
+    if (p.has.remd) {          // the ladder vetted and its words set, behind the init kernel and in front of everything that reads status
+        const MxInitArgs xa = {mm->N, mm->C, mm->B, n_blocks, mm->atom_molptr, q.blk_ptr, p.remd.slots_in, p.remd.every > 0, ms_remd_dev(p, cv),
+                               w.status, w.bad};
+        GRAPPA_LAUNCH(mx_init_kernel, dim3((unsigned)mm->B), dim3(256), 0, st, xa);
+    }
     const dim3 grid((unsigned)n_items), block(NB_NT);
     MscDev cn = {};
     if (p.cons) {          // the tables vetted: clear, claim, read back
@@ -1214,7 +1330,7 @@ int ms_init(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, co
 
 int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_md_opts* o, const MsPlan& p, const float* mass,
            const unsigned long long* mol_key, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
-           MsFrames fr) {
+           MsFrames fr, MsExch ex = MsExch{}) {
     // an output of an option the plan lacks is no output of this run: dropped before anything asks whether the run writes frames
     if (!p.has.gb) fr.esolv = nullptr;
     if (!p.has.restr) fr.erestr = fr.phi = nullptr;
@@ -1224,6 +1340,10 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     const bool frames_e = fr.epot || fr.ekin || fr.esolv, frames_r = fr.erestr || fr.phi;
     const bool frames = o->save_every > 0 && (fr.xyz || frames_e || frames_r);
     if (frames && step0 % o->save_every != 0) return GRAPPA_ERR_ARG;
+    // a ladder with exchanges: K; its logs ask that the call begin on an attempt's boundary, so that row i is attempt base / K + 1 + i
+    const unsigned K = p.has.remd ? (unsigned)p.remd.every : 0u, base = o->first_step + (unsigned)step0;
+    if (K == 0) ex = MsExch{};
+    if ((ex.slot || ex.epot || ex.erestr) && base % K != 0) return GRAPPA_ERR_ARG;
     if (rc != GRAPPA_OK) return GRAPPA_OK;
     if (!mass || !mol_key) return GRAPPA_ERR_ARG;
     const MsCarve cv = ms_carve((char*)ws, mm->N, mm->C, mm->B, n_blocks, p.has);
@@ -1235,10 +1355,12 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
     const RsGeom q = rs_geom(mm, table_dev, n_blocks);
     const MdConsts k = md_consts(o);
     const float hkf = p.has.gb ? 0.f : k.hk;          // with the solvent the chain launch gives the closing kick
-    const bool item_wise = p.has.cons || p.has.restr;
+    const bool item_wise = p.has.cons || p.keep();
+    const MxDev xd = ms_remd_dev(p, cv);
     MscDev cn = {};
     if (p.cons) cn = msc_dev(p.cons, o, w);
     MsMoveArgs mv;
+    mv.kt_item = p.has.remd ? xd.kt_item : nullptr;
     mv.q = q, mv.x = w.x, mv.v = w.v, mv.g = w.g, mv.mass = mass, mv.mol_key = mol_key;
     mv.bad = w.bad, mv.status = w.status, mv.steps = w.steps, mv.k = k;
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C;
@@ -1257,12 +1379,14 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             if (p.has.gb) ms_launch_gb(st, nb, p.gb, q, w, cv.gw, mass, k.hk, n_items, p.has.cons);
             if (p.has.cons) msc_launch_close(st, q, w, cn, mass, 1, n_items);
         }
+        // the energy terms at the coordinates the step left: for the frame, for the attempt, once for both
+        const bool exch = K > 0 && (base + (unsigned)s + 1u) % K == 0;
+        const bool six = (due && fr.epot) || exch, terms = six || (due && fr.esolv);
+        if (terms) {
+            const int erc = ms_launch_terms(stream, mm, nb, p, table_dev, n_items, n_blocks, cv, six);
+            if (erc != GRAPPA_OK) return erc;
+        }
         if (due && frames_e) {
-            const bool terms = fr.epot || fr.esolv;
-            if (terms) {
-                const int erc = ms_launch_terms(stream, mm, nb, p, table_dev, n_items, n_blocks, cv, fr.epot != nullptr);
-                if (erc != GRAPPA_OK) return erc;
-            }
             MsOutArgs a = ms_out_args(mm, nb, q, w);
             a.final = 0, a.with_epot = fr.epot != nullptr;
             a.epot = fr.epot ? fr.epot + f * bc : nullptr, a.ekin = fr.ekin ? fr.ekin + f * bc : nullptr;
@@ -1272,6 +1396,32 @@ int ms_run(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, con
             const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 0, fr.erestr ? fr.erestr + f * bc : nullptr,
                                                   fr.phi ? fr.phi + f * (size_t)mr->R * mm->C : nullptr);
             GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
+        }
+        if (exch) {
+            // the attempt behind this step: epot and E_r as a frame at this step reports them -- the frame's own rows where it has them,
+            // else the same launches into the ladder's scratch -- then the decisions, then the swapped replicas' velocities
+            const unsigned g = base + (unsigned)s + 1u;
+            const float *ue = due && fr.epot ? fr.epot + f * bc : nullptr, *ur = due && mr && fr.erestr ? fr.erestr + f * bc : nullptr;
+            if (!ue) {
+                MsOutArgs a = ms_out_args(mm, nb, q, w);
+                a.final = 0, a.with_epot = 1, a.epot = xd.epot;
+                ms_launch_out(st, a, item_wise, bc, p.has.gb ? cv.gw.terms_gb : nullptr, nullptr);
+                ue = xd.epot;
+            }
+            if (mr && !ur) {
+                const MrEnergyArgs e = mr_energy_args(mm, w, *mr, 0, xd.erestr, nullptr);
+                GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, e);
+                ur = xd.erestr;
+            }
+            const size_t row = (size_t)(g / K - base / K - 1u) * bc;
+            const MxExchArgs xa = {mm->N, mm->C, mm->B, n_blocks, mm->atom_molptr, q.blk_ptr, mol_key, w.status, w.bad, xd, ue, ur, g,
+                                   (int)((g / K) & 1u), ex.slot ? ex.slot + row : nullptr, ex.epot ? ex.epot + row : nullptr,
+                                   ex.erestr ? ex.erestr + row : nullptr};
+            GRAPPA_LAUNCH(ms_exchange_kernel, dim3((unsigned)mm->B), dim3(256), 0, st, xa);
+            if (n_items > 0) {
+                const MxRescaleArgs ra = {q, w.v, w.kpart, xd.scale};
+                GRAPPA_LAUNCH(ms_rescale_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, ra);
+            }
         }
     }
     return grappa_launch_status();
@@ -1293,13 +1443,16 @@ int ms_finish(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, 
     a.final = 1, a.with_epot = 1;
     a.xyz_out = e.xyz, a.vel_out = e.vel, a.epot = e.epot, a.ekin = e.ekin, a.steps = e.steps, a.status = e.status;
     const size_t n3 = (size_t)mm->N * mm->C * 3, bc = (size_t)mm->B * mm->C;
-    const bool item_wise = p.has.cons || p.has.restr;          // a refused item's outputs are not touched: x and v item by item
+    const bool item_wise = p.has.cons || p.keep();          // a refused item's outputs are not touched: x and v item by item
     if (item_wise && n_items > 0) GRAPPA_LAUNCH(msc_copy_kernel, dim3((unsigned)n_items), dim3(NB_NT), 0, st, q, w.x, w.v, w.status, e.xyz, e.vel);
     ms_launch_out(st, a, item_wise, item_wise || n3 < bc ? bc : n3, p.has.gb ? cv.gw.terms_gb : nullptr, e.esolv);
     if (p.has.restr) {
         const MrEnergyArgs ea = mr_energy_args(mm, w, ms_restr_dev(p, cv), 1, e.erestr, e.phi);
         GRAPPA_LAUNCH(mr_energy_kernel, dim3((unsigned)bc), dim3(MR_NT), 0, st, ea);
     }
+    if (e.slots)          // the ladder's entries: the slot every item holds (no ladder: c)
+        GRAPPA_LAUNCH(mx_slots_out_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, mm->atom_molptr, mm->N, mm->B, mm->C, w.status,
+                      p.has.remd ? cv.x.slot : nullptr, e.slots);
     return grappa_launch_status();
 }
 
@@ -1315,7 +1468,7 @@ int ms_zero_erestr(void* stream, const grappa_mm_desc* mm, float* erestr) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the entries
-// Six families of four: each takes the optional pointers of the one before it plus one, builds the plan from those it takes (the
+// Seven families of four (the seventh, grappa_md_remd_*, at the end of the file): each takes the optional pointers of the one before it plus one, builds the plan from those it takes (the
 // others NULL), returns GRAPPA_ERR_ARG if the plan is refused, and makes the call.  None calls another.
 extern "C" size_t grappa_md_steps_workspace_bytes(int N, int C, int B, int n_blocks) { return ms_bytes(N, C, B, n_blocks, 0, MsHas{}); }
 
@@ -1528,5 +1681,47 @@ extern "C" int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_de
     if (!erestr || ms_plan(mm, nb, cut, cons, gb, gbcut, r, p) != GRAPPA_OK) return GRAPPA_ERR_ARG;
     const int fc = ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes,
                              MsEnds{xyz_out, vel_out, epot, ekin, steps, status, esolv, erestr, dih_phi});
+    return fc != GRAPPA_OK || p.has.restr ? fc : ms_zero_erestr(stream, mm, erestr);
+}
+
+// on a temperature ladder, with or without exchanges (x, include/grappa_hip.h grappa_md_remd): the _restr_ calls with x directly after r.
+// x == NULL is the _restr_ call itself; the finish then writes slots_out as c.
+extern "C" size_t grappa_md_remd_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut, int with_gb, int with_gbcut,
+                                                 int with_restr) {
+    MsHas h = {};
+    h.cut = with_cut != 0, h.gbcut = with_gbcut != 0, h.gb = with_gb != 0 || h.gbcut, h.restr = with_restr != 0, h.remd = true;
+    return ms_bytes(N, C, B, n_blocks, K, h);
+}
+
+extern "C" int grappa_md_remd_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                       const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                       const grappa_md_restr* r, const grappa_md_remd* x, const float* mass, const unsigned long long* mol_key,
+                                       const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes) {
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, r, p, x, o) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_init(stream, mm, nb, o, p, mass, mol_key, vel_in, table_dev, n_items, n_blocks, ws, ws_bytes);
+}
+
+extern "C" int grappa_md_remd_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                      const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                      const grappa_md_restr* r, const grappa_md_remd* x, const float* mass, const unsigned long long* mol_key,
+                                      const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
+                                      float* frames_xyz, float* frames_epot, float* frames_ekin, float* frames_esolv, float* frames_erestr,
+                                      float* frames_phi, int* exch_slot, float* exch_epot, float* exch_erestr) {
+    MsPlan p;
+    if (ms_plan(mm, nb, cut, cons, gb, gbcut, r, p, x, o) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    return ms_run(stream, mm, nb, o, p, mass, mol_key, table_dev, n_items, n_blocks, ws, ws_bytes, step0, n_steps,
+                  MsFrames{frames_xyz, frames_epot, frames_ekin, frames_esolv, frames_erestr, frames_phi}, MsExch{exch_slot, exch_epot, exch_erestr});
+}
+
+extern "C" int grappa_md_remd_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                                         const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                                         const grappa_md_restr* r, const grappa_md_remd* x, const int* table_dev, int n_items, int n_blocks,
+                                         void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
+                                         int* status, float* esolv, float* erestr, float* dih_phi, int* slots_out) {
+    MsPlan p;
+    if (!erestr || !slots_out || ms_plan(mm, nb, cut, cons, gb, gbcut, r, p, x, o) != GRAPPA_OK) return GRAPPA_ERR_ARG;
+    const int fc = ms_finish(stream, mm, nb, o, p, table_dev, n_items, n_blocks, ws, ws_bytes,
+                             MsEnds{xyz_out, vel_out, epot, ekin, steps, status, esolv, erestr, dih_phi, slots_out});
     return fc != GRAPPA_OK || p.has.restr ? fc : ms_zero_erestr(stream, mm, erestr);
 }

@@ -47,6 +47,15 @@ ORIGINAL reference, or the tethers move to the start of the continuing call.  Fr
 The potential energies stay the force field's (plus the solvent's); `restraint_energy` is reported beside them.  Not built: restraints in
 the fused dynamics, distance, angle or flat-bottomed restraints, more than 16 dihedrals per molecule, time-dependent targets.
 
+Replicas (`replicas=`, `grappa_amd.replica.ReplicaExchange`): a temperature ladder over the C conformations of the call, with or
+without replica exchange, on the stepwise path only (`grappa_md_remd_*_f32` through `HipBackend.md_steps_remd`), with every combination
+of cutoff, constraints, implicit solvent and restraints that path takes.  Conformation c is a replica that keeps its coordinates and its
+noise stream; the thermostat step reads the temperature of the slot it holds, and behind every `exchange_every`-th step neighbouring
+slots attempt a Metropolis swap on the potential energy (plus the restraint energy); a step gains no launch, a step with an attempt the
+energy launches of a frame and two small ones.  `temperature` is then unused; velocities that are drawn are drawn at the replica's
+slot temperature unless `init_temperature` is given.  `stepwise="auto"` goes stepwise whenever they are given.  The result carries
+`slots`, `exchange_slots` and `exchange_energy`; `grappa_amd.replica.acceptance` gives the acceptance per pair.
+
 The integrator is BAOAB (Leimkuhler and Matthews, J. Chem. Phys. 138, 174102 (2013)); the loop, the random stream and the units are
 stated in include/grappa_hip.h.  Units: Angstrom, kcal/mol, amu, ps, K.  With friction = 0 it is velocity Verlet (NVE).  An atom of
 mass 0 is frozen.  The random stream has no state: an atom's noise is a function of its molecule's 64-bit key (`mol_keys`), its index
@@ -61,7 +70,7 @@ be cut into launches anywhere (`steps_per_launch`) without changing a bit.  An i
     5  (with constraints or restraints) constraint or restraint tables refused on the device (an index outside the molecule, an atom
        in two clusters, a length that is not positive and finite, on the fused path more than 256 clusters; a restrained dihedral
        with a repeated atom, a negative or non-finite stiffness, a non-finite target, more than 16 rows): nothing else was written
-       for the item
+       for the item; with replicas also a row of start slots that is no permutation, or a temperature the ladder refuses
 The defaults (`MD_DEFAULTS`: 1 fs, 300 K, 1/ps) are common choices for unconstrained small molecules and are NOT tuned: nothing here
 has measured which time step a given molecule tolerates (a step of 1 fs with free X-H bonds is at the edge of what BAOAB resolves).
 """
@@ -141,6 +150,9 @@ class MDResult:
     frame_kinetic_energy: object = None
     esolv: object = None              # with an implicit solvent: its part of potential_energy, shaped like it; else None
     frames_esolv: object = None       # ... and of frame_potential_energy
+    slots: object = None                      # with replicas: the slot of the ladder every replica holds at the end, (B, C) / (n_confs,)
+    exchange_slots: object = None             # ... the slots after each of the run's X attempts, (X, B, C) / (X, n_confs)
+    exchange_energy: object = None            # ... epot + E_r as the decisions read them, float64, (X, B, C) / (X, n_confs); NaN: stopped
     restraint_energy: object = None           # with restraints: E_r at xyz (potential_energy stays the force field's), (B, C) / (n_confs,)
     dihedrals: object = None                  # with restraints: the restrained dihedrals at xyz in radians, (R, C) / (R, n_confs)
     frames_restraint_energy: object = None    # ... per frame: (F, B, C) / (n_confs, n_frames); a frame not reached is NaN
@@ -177,7 +189,7 @@ def _host_keys(keys, seed, B):
 def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, velocities=None, seed: int = 0, keys=None, first_step: int = 0,
                    steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, terms=("n2", "n3", "n4", "n4_improper"), suffix: str = "",
                    offset_torsion: bool = False, stepwise=False, constraints=None, constrain_start: bool = True, cutoff=None,
-                   implicit_solvent=None, gb=None, restraints=None, restraint_reference=None, **opts) -> MDResult:
+                   implicit_solvent=None, gb=None, restraints=None, restraint_reference=None, replicas=None, **opts) -> MDResult:
     """Run `n_steps` BAOAB steps of every (molecule, conformation) of a parametrised batched graph: `xyz` (N, C, 3) at n1 and `k` /
     `eq` at the tuple levels, exactly what `Energy` and `relax_graph` read.  masses: (N,) in amu on the host (0: a frozen atom),
     checked before the upload.  nonbonded: the batch's `NonbondedBatch` on the graph's device (None: bonded terms only).
@@ -212,11 +224,31 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     stepwise=False raises, "auto" goes stepwise; they go with every combination of cutoff, constraints and implicit solvent.  Frozen
     atoms of the batch get mass 0 before anything reads the masses.  restraint_reference: (N, C, 3) on the graph's device, the
     tethers' reference (None: xyz, resolved once; every launch of a long run gets that tensor, never its own start).  The result carries
-    restraint_energy (B, C), dihedrals (R, C) and, with frames, frames_restraint_energy (F, B, C) and frames_dihedrals (F, R, C)."""
+    restraint_energy (B, C), dihedrals (R, C) and, with frames, frames_restraint_energy (F, B, C) and frames_dihedrals (F, R, C).
+    replicas: a `grappa_amd.replica.ReplicaExchange` whose ladder has one temperature per conformation (None: none, the calls made are
+    exactly those without this argument): see the module text.  The stepwise path only: stepwise=False raises, "auto" goes stepwise;
+    it goes with every combination of cutoff, constraints, implicit solvent and restraints.  Exchanges need friction > 0 and a
+    first_step that is a multiple of exchange_every.  Velocities that are drawn are drawn at the replica's slot temperature iff
+    init_temperature was left at None.  The result carries slots (B, C), exchange_slots (X, B, C) and exchange_energy (X, B, C); a run
+    is continued with `ReplicaExchange(..., slots=result.slots)`, velocities= and first_step=."""
     from .backend import get_backend
     from .solvent import GBBatch, as_implicit_solvent
     o = md_options(**opts)
     stepwise, _ = _stepwise_options(stepwise, 1)
+    if replicas is not None:
+        from .replica import ReplicaExchange
+        if not isinstance(replicas, ReplicaExchange):
+            raise TypeError(f"replicas must be a ReplicaExchange or None, got {type(replicas).__name__}")
+        if stepwise is False:
+            raise ValueError('simulate: replicas run on the stepwise path only: pass stepwise="auto" (or True)')
+        if getattr(get_backend(), "md_steps_remd", None) is None:
+            raise ValueError("simulate: the backend has no temperature ladders on the stepwise dynamics (md_steps_remd)")
+        if constraints is not None and not _steps_take_constraints():
+            raise ValueError("simulate: constraints run on the fused path only, replicas on the stepwise path only")
+        if replicas.exchange_every > 0 and not o["friction"] > 0:
+            raise ValueError("simulate: replica exchange needs a thermostat (friction > 0)")
+        if replicas.exchange_every > 0 and int(first_step) % replicas.exchange_every != 0:
+            raise ValueError(f"simulate: first_step must be a multiple of exchange_every ({replicas.exchange_every}), got {first_step!r}")
     if restraints is not None:
         from .restraints import RestraintBatch
         if not isinstance(restraints, RestraintBatch):
@@ -263,7 +295,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if above and stepwise is False:
         raise ValueError(f"simulate: a molecule of {max(counts)} atoms is above the limit of {limit} atoms per molecule of the fused dynamics "
                          f"(stepwise=True or stepwise='auto' runs molecules of any size)")
-    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None or restraints is not None))
+    use_steps = stepwise is True or (stepwise == "auto" and (above or cutoff is not None or solvent is not None or restraints is not None
+                                                             or replicas is not None))
     if solvent is not None:
         if gb.counts != list(counts):
             raise ValueError(f"the GB parameters describe molecules of {gb.counts} atoms, the batch has {list(counts)}")
@@ -278,6 +311,8 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
             raise ValueError(f"the constraints describe {constraints.B} molecules, the batch has {len(counts)}")
     ks, eqs, n_per = graph_force_field(g, plan, counts, nonbonded, terms, suffix, dev)
     N, B, C = plan.N, plan.B, xyz.shape[1]
+    if replicas is not None and replicas.C != C:
+        raise ValueError(f"the ladder has {replicas.C} temperatures, the batch has {C} conformations")
     m_host = _host_masses(masses, N)
     ref = None
     if restraints is not None:
@@ -328,9 +363,26 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         er, phi = f32(B, C), f32(restraints.R, C)
         if F:
             fer, fphi = nan(F, B, C), nan(F, restraints.R, C)
+    ladder = None
+    if replicas is not None:          # the ladder on the device, the slots of the run and the logs of its X attempts
+        K = replicas.exchange_every
+        X = n_steps // K if K > 0 else 0
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)      # noqa: E731
+        s0 = replicas.slots_for(B)
+        ladder = {"T": torch.from_numpy(replicas.temperatures).to(dev), "slots": None if s0 is None else torch.from_numpy(s0).to(dev),
+                  "out": i32(B, C), "xs": i32(X, B, C) if X else None,
+                  "xe": torch.full((X, B, C), float("nan"), dtype=torch.float32, device=dev) if X else None,
+                  "xr": torch.full((X, B, C), float("nan"), dtype=torch.float32, device=dev) if X and restraints is not None else None,
+                  "at_ladder": opts.get("init_temperature") is None}
     # one call of a seam runs `seg` steps: a launch of the fused kernel, or init / run calls of at most `chunk` steps / finish of the
     # stepwise path, whose options carry the library's cap on n_steps too; calls continue one another bit for bit
     seg = chunk if not use_steps else (MAX_STEPS_PER_LAUNCH // every * every if every > 0 else MAX_STEPS_PER_LAUNCH)
+    if ladder is not None and replicas.exchange_every > 0:          # (a call of the seam ends where frames and attempts both allow)
+        import math
+        both = math.lcm(every if every > 0 else 1, replicas.exchange_every)
+        if both > MAX_STEPS_PER_LAUNCH:
+            raise ValueError(f"save_every and exchange_every must have a common multiple of at most {MAX_STEPS_PER_LAUNCH}, got {both}")
+        seg = MAX_STEPS_PER_LAUNCH // both * both
     bufs = [(torch.empty_like(xyz), torch.empty_like(xyz)) for _ in range(2 if n_steps > seg else 1)]
     epot, ekin = f32(B, C), f32(B, C)
     steps, status = torch.zeros(B, C, dtype=torch.int32, device=dev), torch.zeros(B, C, dtype=torch.int32, device=dev)
@@ -354,7 +406,21 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
         args = (plan, x_in, ks, eqs, n_per, bool(offset_torsion), nonbonded, call, mass, key, v_in, x_out, v_out, epot, ekin, steps, status)
         kw = dict(frames_xyz=frames[f0:f1] if f1 > f0 else None, frames_epot=fe[f0:f1] if f1 > f0 else None,
                   frames_ekin=fk[f0:f1] if f1 > f0 else None, atom_counts_host=counts)
-        if restraints is not None:
+        if ladder is not None:
+            K = replicas.exchange_every
+            a0, a1 = (done // K, (done + n) // K) if K > 0 else (0, 0)
+            rows = lambda t: t[a0:a1] if t is not None and a1 > a0 else None      # noqa: E731
+            rkw = {} if restraints is None else dict(
+                restraints=restraints, restraint_reference=ref, restraint_energy=er, dihedral_out=phi,
+                frames_restraint_energy=fer[f0:f1] if f1 > f0 else None, frames_dihedrals=fphi[f0:f1] if f1 > f0 else None)
+            get_backend().md_steps_remd(*args, steps_per_call=chunk, **kw, constraints=constraints,
+                                        constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
+                                        frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None,
+                                        **({} if cutoff is None else {"cutoff": cutoff}), **rkw, temperatures=ladder["T"],
+                                        slots=ladder["slots"], exchange_every=K, init_at_ladder=ladder["at_ladder"], slots_out=ladder["out"],
+                                        exchange_slots=rows(ladder["xs"]), exchange_epot=rows(ladder["xe"]), exchange_erestr=rows(ladder["xr"]))
+            ladder["slots"] = ladder["out"].clone() if n_steps > seg else ladder["out"]          # (the next call of a long run starts there)
+        elif restraints is not None:
             get_backend().md_steps_restr(*args, steps_per_call=chunk, **kw, constraints=constraints,
                                          constrain_start=bool(constrain_start) and launch == 0, gb=gb, solvent=solvent, esolv=es,
                                          frames_esolv=fs[f0:f1] if fs is not None and f1 > f0 else None,
@@ -408,13 +474,20 @@ def simulate_graph(g, masses, nonbonded: Optional[NonbondedBatch] = None, *, vel
     if fer is not None and restraints.R == 0 and restraints.pos_k is None:
         fer = torch.where(torch.isnan(fe), fe, torch.zeros_like(fe))          # (nothing restrains: the library writes no frame of E_r; it is 0)
     temperature = 2.0 * ekin / (3.0 * KB * n_moving) if constraints is None else 2.0 * ekin / (KB * dof.clamp_min(1.0))
-    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs, er, phi, fer, fphi)
+    if ladder is None:
+        return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs, restraint_energy=er, dihedrals=phi,
+                        frames_restraint_energy=fer, frames_dihedrals=fphi)
+    xen = None
+    if ladder["xe"] is not None:
+        xen = ladder["xe"].double() + (ladder["xr"].double() if ladder["xr"] is not None else 0.0)
+    return MDResult(x_in, v_in, epot, ekin, temperature, total, status, frames, fe, fk, es, fs, slots=ladder["out"], exchange_slots=ladder["xs"],
+                    exchange_energy=xen, restraint_energy=er, dihedrals=phi, frames_restraint_energy=fer, frames_dihedrals=fphi)
 
 
 def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedParameters] = None, device="cuda", *, velocities=None,
              seed: int = 0, keys=None, first_step: int = 0, steps_per_launch: int = STEPS_PER_LAUNCH_DEFAULT, stepwise=False, constraints=None,
              constrain_start: bool = True, cutoff=None, implicit_solvent=None, gb=None, restraints=None, restraint_reference=None,
-             **opts) -> MDResult:
+             replicas=None, **opts) -> MDResult:
     """Run the conformations of ONE molecule under the parameters `Grappa.predict` returned (+ `nonbonded`; masses, nonbonded and
     velocities in the order of `parameters.atoms`), numpy in and out: xyz (n_confs, n_atoms, 3) in Angstrom, masses (n_atoms,) in amu,
     velocities (n_confs, n_atoms, 3) in A/ps or None -> MDResult (float64) with xyz and velocities of that shape, frames
@@ -424,11 +497,22 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
     implicit_solvent: see `simulate_graph`; gb: the molecule's `grappa_amd.solvent.GBParameters` in the order of `parameters.atoms`.
     restraints: the molecule's `grappa_amd.restraints.Restraints` in the order of `parameters.atoms` (None: none), restraint_reference
     (n_confs, n_atoms, 3) or None (xyz): see `simulate_graph`; the result then carries restraint_energy (n_confs,), dihedrals
-    (R, n_confs), frames_restraint_energy (n_confs, n_frames) and frames_dihedrals (R, n_confs, n_frames)."""
+    (R, n_confs), frames_restraint_energy (n_confs, n_frames) and frames_dihedrals (R, n_confs, n_frames).
+    replicas: a `grappa_amd.replica.ReplicaExchange` with one temperature per conformation (None: none): see `simulate_graph`; the
+    result then carries slots (n_confs,), exchange_slots (X, n_confs) and exchange_energy (X, n_confs)."""
     from .solvent import GBBatch, GBParameters, as_implicit_solvent
     md_options(**opts)
     _stepwise_options(stepwise, 1)
     extra = {}
+    if replicas is not None:
+        from .replica import ReplicaExchange
+        if not isinstance(replicas, ReplicaExchange):
+            raise TypeError(f"replicas must be a ReplicaExchange or None, got {type(replicas).__name__}")
+        if stepwise is False:
+            raise ValueError('simulate: replicas run on the stepwise path only: pass stepwise="auto" (or True)')
+        if replicas.C != int(np.asarray(xyz).shape[0]):
+            raise ValueError(f"the ladder has {replicas.C} temperatures, the molecule has {int(np.asarray(xyz).shape[0])} conformations")
+        extra["replicas"] = replicas
     if restraints is not None:
         from .restraints import Restraints
         if not isinstance(restraints, Restraints):
@@ -497,7 +581,10 @@ def simulate(parameters: Parameters, xyz, masses, nonbonded: Optional[NonbondedP
                     r.steps.cpu().numpy()[0], r.status.cpu().numpy()[0], np64(r.frames).transpose(2, 0, 1, 3) if has else None,
                     np64(r.frame_potential_energy)[:, 0].T if has else None, np64(r.frame_kinetic_energy)[:, 0].T if has else None,
                     np64(r.esolv)[0] if r.esolv is not None else None, np64(r.frames_esolv)[:, 0].T if r.frames_esolv is not None else None,
-                    np64(r.restraint_energy)[0] if r.restraint_energy is not None else None,
-                    np64(r.dihedrals) if r.dihedrals is not None else None,
-                    np64(r.frames_restraint_energy)[:, 0].T if r.frames_restraint_energy is not None else None,
-                    np64(r.frames_dihedrals).transpose(1, 2, 0) if r.frames_dihedrals is not None else None)
+                    slots=r.slots.cpu().numpy()[0] if r.slots is not None else None,
+                    exchange_slots=r.exchange_slots.cpu().numpy()[:, 0] if r.exchange_slots is not None else None,
+                    exchange_energy=np64(r.exchange_energy)[:, 0] if r.exchange_energy is not None else None,
+                    restraint_energy=np64(r.restraint_energy)[0] if r.restraint_energy is not None else None,
+                    dihedrals=np64(r.dihedrals) if r.dihedrals is not None else None,
+                    frames_restraint_energy=np64(r.frames_restraint_energy)[:, 0].T if r.frames_restraint_energy is not None else None,
+                    frames_dihedrals=np64(r.frames_dihedrals).transpose(1, 2, 0) if r.frames_dihedrals is not None else None)

@@ -87,7 +87,7 @@ class Grappa:
         return torsion_scan(self.predict(molecule), xyz, dihedral, angles, nonbonded, device=self.device, **kw)
 
     def simulate(self, molecule: Molecule, xyz, nonbonded=None, *, stepwise=False, constraints=None, cutoff=None, implicit_solvent=None,
-                 restraints=None, restraint_reference=None, **kw):
+                 restraints=None, restraint_reference=None, replicas=None, **kw):
         """`predict` followed by `grappa_amd.dynamics.simulate`: Langevin dynamics (BAOAB) of the conformations xyz
         (n_confs, n_atoms, 3) of `molecule` on the device under the predicted bonded parameters (+ `nonbonded`: NonbondedParameters in
         the molecule's atom order), with the atomic masses of `constants.ATOMIC_MASSES` -> MDResult.  stepwise=False: the fused kernel
@@ -108,8 +108,12 @@ class Grappa:
         restraints: a `grappa_amd.restraints.Restraints` in the molecule's atom order (None: none) -- tethers to
         restraint_reference (n_confs, n_atoms, 3; None: xyz), dihedral restraints with one target per conformation (the windows of an
         umbrella run) and frozen atoms, on the stepwise path with any of the above (stepwise="auto" or True): see
-        `grappa_amd.dynamics.simulate`"""
+        `grappa_amd.dynamics.simulate`
+        replicas: a `grappa_amd.replica.ReplicaExchange` with one temperature per conformation (None: none) -- a temperature ladder
+        over the conformations, with or without replica exchange, on the stepwise path with any of the above (stepwise="auto" or True)"""
         from .dynamics import simulate
+        if replicas is not None:
+            kw = {**kw, "replicas": replicas}
         if restraints is not None:
             kw = {**kw, "restraints": restraints, "restraint_reference": restraint_reference}
         elif restraint_reference is not None:

@@ -1157,6 +1157,74 @@ int grappa_md_steps_finish_restr_f32(void* stream, const grappa_mm_desc* mm, con
                                      void* ws, size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps,
                                      int* status, float* esolv, float* erestr, float* dih_phi);
 
+/* Temperature ladders and replica exchange on the stepwise dynamics (additions to ABI 11): the _restr_ calls with
+ * `const grappa_md_remd* x` directly after r; cut, cons, gb, gbcut and r are each optional under the _restr_ family's own rules.
+ *   ladder : temperatures[C], fp32 in kelvin, in device memory.  Slot s has kt_s = (float)(ACC kB (double)T_s): the expression of the
+ *            scalar temperature, the same bits.
+ *   replica: every (molecule b, conformation c) is a replica.  It keeps its coordinates, its noise stream (keyed by c, as ever) and its
+ *            index c for the whole run; what moves is the SLOT it holds.  The workspace keeps per item slot[b,c], its inverse
+ *            who[b,s], kt_item[b,c] and scale[b,c].  Each molecule of a batch has its own ladder state over the same temperatures.
+ *            Start: slot[b,c] = c, or slots_in[B,C], which must be a permutation of 0 .. C-1 per molecule.
+ *   vet    : one launch of init, per molecule: every temperature finite and >= 0 (with exchanges: > 0), the molecule's slots_in row a
+ *            permutation.  A refused molecule's items get status 5 and never run; their outputs are untouched, their neighbours run.
+ *   O step : reads kt_item[b,c] in place of ACC kB temperature; c1, c2, the noise and B, A, O, A are what they were.  o->temperature
+ *            must still be valid and is otherwise unused.
+ *   start  : with vel_in == NULL the velocities are drawn at the replica's slot temperature if init_at_ladder != 0, at the scalar
+ *            o->init_temperature otherwise.
+ *   attempt: with exchange_every = K > 0, behind the step whose global index g = first_step + step0 + s + 1 is a multiple of K, after
+ *            that step's own frame outputs.  The attempt's number is a = g / K; its pairs are the slots (s, s + 1) with s = a (mod 2),
+ *            0 <= s <= C - 2.  K == 0: a ladder without exchanges.
+ *   energy : with lo = who[b,s], hi = who[b,s+1]: U = (double)epot + (double)erestr, the fp32 values a frame at this step reports (the
+ *            force field plus the solvent; E_r, 0 without restraints), by the launches a frame uses, into workspace scratch -- or the
+ *            frame's own rows where the frame of the same step asked for them: nothing is evaluated twice.
+ *   decision: beta = 1 / (kB (double)T); D = (beta_s - beta_{s+1}) (U_lo - U_hi); u = ((double)w0 + 0.5) 2^-32 with w0 word 0 of
+ *            Philox4x32-10(key = mol_key[b], counter = (s, 0, g, 2)) -- purpose 2, which no other draw uses; accepted iff D >= 0 or
+ *            u < exp(D), all in double.  A pair is not attempted if either replica no longer runs (its status, or a flag that the
+ *            step's launches set on one of its blocks) or either U is not finite.
+ *   swap   : on acceptance the two replicas swap slot, who and kt_item, and the velocities of each are multiplied by
+ *            f = (float)sqrt((double)T_new / (double)T_old).  x and g are untouched: no force is recomputed.  The kinetic partials of
+ *            the replica's blocks are multiplied by (double)f * f, so an ekin reported before the next step agrees with
+ *            sum m v^2 / 2 within rounding, NOT bit for bit.
+ *   logs   : exch_slot, exch_epot, exch_erestr [X,B,C], each NULL: not written; X = the attempts of the call, row i belongs to attempt
+ *            (first_step + step0) / K + 1 + i, and with a log (first_step + step0) % K != 0 is GRAPPA_ERR_ARG of THAT run call (it
+ *            launches and writes nothing; init has run by then, as with a step0 off the period of save_every).  Without logs a run
+ *            call may begin anywhere.  exch_slot holds the
+ *            slots after the attempt, the energies are those the decision read (NaN for a replica that no longer runs; a refused
+ *            item's rows are untouched).
+ *   finish : slots_out [B,C] (required): the slot every item holds, for molecules with atoms but refused items.
+ * Launches: init gains one (the vet); a step gains none; a step with an attempt gains the energy launches a frame with epot (and E_r)
+ * at that step makes, unless that frame is written anyway, plus two (exchange, rescale); finish gains one (slots_out).
+ * Same input, same bits; no atomics; every word has one writer per launch (the pairs of an attempt are disjoint); a replica's bits
+ * depend neither on the batch around its molecule nor on how the steps are dealt out to run calls.
+ * x == NULL is the _restr_ call itself: its launches, its bits, its refusals; slots_out is then written as c.  GRAPPA_ERR_ARG, nothing
+ * launched and nothing written: NULL temperatures, exchange_every < 0, exchange_every > 0 with friction == 0 (exchanges need a
+ * thermostat), a NULL slots_out (finish), every refusal of the _restr_ calls; of the run call alone, the log boundary above.  The
+ * workspace is grappa_md_remd_workspace_bytes: the
+ * layout of the call without a ladder, unchanged, and the ladder's words behind it.  Not here: Hamiltonian exchange between umbrella
+ * windows, the fused dynamics, coordinate exchange, non-neighbour pairs, per-replica friction or dt, annealing schedules. */
+typedef struct grappa_md_remd {
+    const float* temperatures;   /* [C] device */
+    const int*   slots_in;       /* [B,C] device or NULL */
+    int exchange_every;          /* 0: ladder only */
+    int init_at_ladder;
+} grappa_md_remd;
+size_t grappa_md_remd_workspace_bytes(int N, int C, int B, int n_blocks, int K, int with_cut, int with_gb, int with_gbcut, int with_restr);
+int grappa_md_remd_init_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                            const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                            const grappa_md_restr* r, const grappa_md_remd* x, const float* mass, const unsigned long long* mol_key,
+                            const float* vel_in, const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes);
+int grappa_md_remd_run_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                           const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                           const grappa_md_restr* r, const grappa_md_remd* x, const float* mass, const unsigned long long* mol_key,
+                           const int* table_dev, int n_items, int n_blocks, void* ws, size_t ws_bytes, int step0, int n_steps,
+                           float* frames_xyz, float* frames_epot, float* frames_ekin, float* frames_esolv, float* frames_erestr,
+                           float* frames_phi, int* exch_slot, float* exch_epot, float* exch_erestr);
+int grappa_md_remd_finish_f32(void* stream, const grappa_mm_desc* mm, const grappa_nb_desc* nb, const grappa_nb_cut* cut,
+                              const grappa_md_opts* o, const grappa_md_cons* cons, const grappa_gb_desc* gb, const grappa_gb_cut* gbcut,
+                              const grappa_md_restr* r, const grappa_md_remd* x, const int* table_dev, int n_items, int n_blocks, void* ws,
+                              size_t ws_bytes, float* xyz_out, float* vel_out, float* epot, float* ekin, int* steps, int* status,
+                              float* esolv, float* erestr, float* dih_phi, int* slots_out);
+
 /* ------------------------------------------------------------------------------------------------
  * MolwiseLoss (training/loss.py:45-167 with utils/graph_utils.py:35-86), one workgroup per molecule:
  *  l_m = wE*mean_c((E-<E>)-(Eref-<Eref>))^2 + wG*mean_{a,c,xyz}(G-Gref)^2   over real conformations

@@ -57,6 +57,15 @@ without restraints -- whose kernels this option does not touch -- IN THE SAME PR
 warm-up run of each.  All times of each side, the ratio of the medians and the library launches.  It is not a gate: no target is set.
 
     python tools/md_steps_bench.py --restraints [--out profiles/md_steps_restr_bench.txt]
+
+With --replicas C [--exchange-every K] the tool measures temperature ladders on the stepwise path instead (`simulate_graph(replicas=)`,
+the grappa_md_remd_*_f32 calls): on the 513-atom chain and T4 lysozyme, each with its start coordinates in C conformations, the scalar
+run of the C conformations -- whose kernels this option does not touch -- against the same run on a ladder of C temperatures from 300 K
+up in steps of 10 K without exchanges and, with K > 0, with an attempt every K steps, IN THE SAME PROCESS, the sides alternating run by
+run after one warm-up run of each.  All times of each side, the ratios of the medians, the library launches and the accepted swaps.
+It is not a gate: no target is set.
+
+    python tools/md_steps_bench.py --replicas 8 --exchange-every 100 [--out profiles/md_steps_remd_bench.txt]
 """
 import argparse
 import datetime
@@ -81,7 +90,9 @@ CONS_SIDES = ("free_1fs", "cons_2fs", "cons_1fs")
 CONS_DT = {"free_1fs": 0.001, "cons_2fs": 0.002, "cons_1fs": 0.001}
 RESTR_WORKLOADS = ("mid", "t4l", "big")
 RESTR_POS_K, RESTR_DIH_K, RESTR_DIH_SHIFT = 10.0, 239.0, 0.5
-STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:restr" for w in RESTR_WORKLOADS] + [f"{w}:{s}" for w in GB_WORKLOADS for s in GBCUT_SIDES + ("gbtiles",)] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
+REMD_WORKLOADS = ("mid", "t4l")
+REMD_T0, REMD_DT = 300.0, 10.0
+STAGES = ["device", "t4l:stepwise", "t4l:gb"] + [f"{w}:remd" for w in REMD_WORKLOADS] + [f"{w}:restr" for w in RESTR_WORKLOADS] + [f"{w}:{s}" for w in GB_WORKLOADS for s in GBCUT_SIDES + ("gbtiles",)] + [f"{w}:{s}" for w in WORKLOADS for s in SIDES[w] + CUT_SIDES[1:] + GB_SIDES[1:]] + \
          [f"{w}:{s}:{p}" for w in WORKLOADS[1:] for s in CONS_SIDES for p in ("pairs", "cut")]
 
 STAGE_LIMIT = 300      # seconds, every stage
@@ -229,6 +240,28 @@ def stage(args):
     out = {"molecules": len(counts), "atoms": int(counts.sum()), "smallest": int(counts.min()), "largest": int(counts.max()), "confs": confs}
     sim = lambda n, stepwise, **kw: simulate_graph(g, masses, nb, n_steps=n, steps_per_launch=args.steps_per_launch, stepwise=stepwise,      # noqa: E731
                                                    **{**OPTS, **kw})
+    if side == "remd":
+        import numpy as np
+        from grappa_amd.replica import ReplicaExchange
+        C, K = args.replicas, args.exchange_every
+        g.nodes["n1"].data["xyz"] = g.nodes["n1"].data["xyz"][:, :1].expand(-1, C, -1).contiguous()          # the start in C conformations
+        T = REMD_T0 + REMD_DT * np.arange(C)
+        sides = [("plain", lambda: sim(steps, True)), ("ladder", lambda: sim(steps, True, replicas=ReplicaExchange(T)))]
+        if K > 0:
+            sides.append(("exchange", lambda: sim(steps, True, replicas=ReplicaExchange(T, K))))
+        for key, fn in sides:
+            n0 = be.lib.grappa_launch_count(0)
+            r = fn()
+            torch.cuda.synchronize()
+            out[key] = {"launches": int(be.lib.grappa_launch_count(0) - n0), "item_steps": int(r.steps.sum()), "stopped": int((r.status != 0).sum())}
+        if K > 0:
+            xs = torch.cat([torch.arange(C, dtype=torch.int32, device=r.exchange_slots.device).expand(1, len(counts), C), r.exchange_slots])
+            out["attempts"], out["swapped"] = int(r.exchange_slots.shape[0]), int((xs[1:] != xs[:-1]).sum()) // 2
+        for (key, _), us in zip(sides, _alternating([fn for _, fn in sides], args.reps)):
+            out[key]["all_us"], out[key]["median_us"] = us, float(sorted(us)[len(us) // 2])
+        out["steps"], out["confs"], out["sides"] = steps, C, [k for k, _ in sides]
+        print(json.dumps(out))
+        return
     if side == "restr":
         rb, tethered = _restraints(g, which, int(counts[0]))
         rb = rb.to("cuda")
@@ -359,6 +392,8 @@ def main():
     ap.add_argument("--implicit-solvent", default="", help="obc2 or obc1: measure the GB/SA implicit solvent on the stepwise path (see the module text)")
     ap.add_argument("--gb-cutoff", type=float, default=0.0, help="A; with --implicit-solvent: also measure the solvent under this cutoff of its own")
     ap.add_argument("--restraints", action="store_true", help="measure restraints on the stepwise path (see the module text)")
+    ap.add_argument("--replicas", type=int, default=0, help="C > 0: measure a temperature ladder of C slots on the stepwise path (see the module text)")
+    ap.add_argument("--exchange-every", type=int, default=0, help="K; with --replicas: also measure an exchange attempt every K steps")
     ap.add_argument("--stage", default=None, choices=STAGES)
     args = ap.parse_args()
     if args.stage:
@@ -373,7 +408,8 @@ def main():
     def run(name):
         cmd = ["timeout", "-k", "10", str(STAGE_LIMIT), sys.executable, os.path.abspath(__file__), "--stage", name] + \
               [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("mols", "confs", "mid_atoms", "big_atoms", "steps", "big_steps", "steps_per_launch",
-                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass", "implicit_solvent", "gb_cutoff")]
+                                                                      "composed_steps", "reps", "cutoff", "switch", "leaf_mass", "implicit_solvent", "gb_cutoff",
+                                                                      "replicas", "exchange_every")]
         p = subprocess.run(cmd, capture_output=True, text=True)          # (waits for the child: one GPU process at a time)
         if p.returncode != 0:
             sys.stderr.write(p.stdout + p.stderr)
@@ -390,7 +426,25 @@ def main():
     say(f"# device: {run('device')['device']}")
     say("# device events around whole runs, median (min) after one warm-up run; every stage a process of its own; steps/s = steps of the run / "
         "run time, whatever the batch holds; this file is the tool's output, unedited")
-    if args.restraints:
+    if args.replicas:
+        say(f"# temperature ladders on the stepwise path: C = {args.replicas} conformations of the start, slots at {REMD_T0} K + {REMD_DT} K s, "
+            f"exchange attempts every {args.exchange_every or 'never'} steps, against the scalar run of the same conformations, in the same process, "
+            "sides alternating; all run times of each side in ms")
+        names = {"plain": "scalar", "ladder": "ladder, K = 0", "exchange": f"ladder, K = {args.exchange_every}"}
+        for w in REMD_WORKLOADS:
+            r = run(f"{w}:remd")
+            say(f"{w}: {r['molecules']} molecule(s), {r['atoms']} atoms, C = {r['confs']}, bonded + nonbonded, dt {OPTS['dt']} ps, friction {OPTS['friction']} "
+                f"/ ps, {r['steps']} steps" + (f"; {r['attempts']} attempts, {r['swapped']} accepted swaps" if "attempts" in r else ""))
+            for key in r["sides"]:
+                q = r[key]
+                say(f"  {names[key]:16s} {q['median_us'] / r['steps']:10.2f} us / step  {r['steps'] / (q['median_us'] * 1e-6):10.1f} steps/s  {q['launches']:6d} "
+                    f"library launches  runs: {', '.join(f'{u / 1e3:.2f}' for u in q['all_us'])} ms" + (f"  ({q['stopped']} items stopped early)" if q["stopped"] else ""))
+            say(f"  time per step, ladder / scalar = {r['ladder']['median_us'] / r['plain']['median_us']:.3f}")
+            if "exchange" in r:
+                extra = (r["exchange"]["median_us"] - r["ladder"]["median_us"]) / max(r["attempts"], 1)
+                say(f"  time per step, exchanging / scalar = {r['exchange']['median_us'] / r['plain']['median_us']:.3f}; an attempt costs "
+                    f"{extra:.1f} us = {extra / (r['plain']['median_us'] / r['steps']):.2f} scalar steps")
+    elif args.restraints:
         say(f"# restraints on the stepwise path: a tether of {RESTR_POS_K} kcal/mol/A^2 on every heavy atom and one restrained dihedral ({RESTR_DIH_K} "
             f"kcal/mol, target {RESTR_DIH_SHIFT} rad from the start) against the same all-pairs run without them, in the same process, sides "
             "alternating; all run times of each side in ms")
@@ -476,7 +530,7 @@ def main():
                     f"{rate['gbcut_noprune'] / rate['gb']:.2f}x; slowest pruned run {max(res['gbcut']['all_us']) / 1e3:.2f} ms, fastest all-pairs solvent run "
                     f"{min(res['gb']['all_us']) / 1e3:.2f} ms: {'faster' if max(res['gbcut']['all_us']) < min(res['gb']['all_us']) else 'NOT faster'}"
                     + (f"; with the nonbonded cutoff beside it {rate['gbboth'] / rate['gb']:.2f}x" if "gbboth" in rate else ""))
-    for w in (() if args.cutoff or args.constraints or args.implicit_solvent or args.restraints else WORKLOADS):
+    for w in (() if args.cutoff or args.constraints or args.implicit_solvent or args.restraints or args.replicas else WORKLOADS):
         rate, head = {}, None
         for side in SIDES[w]:
             r = run(f"{w}:{side}")
